@@ -19,12 +19,19 @@ forward`, default), which returns the exact num_rendered of every frame; the lib
 count right behind preprocess, so the call does not stall the stream.  The same loop through the
 additive deferred-count entry point (`GaussianRasterizer.forward_deferred`, C ABI
 grpg_forward_deferred: status checked a few frames behind, overflowed frames rendered again and
-counted in `frames_rendered_twice`) is timed right after it and reported under `entry_points`
-(`--entry deferred` makes it the headline instead).  The streams, the output buffer and the allocator
-pools of ALL streams exist before the warm-up: the W warm-up frames run through exactly the loop that
-is timed afterwards.
+counted in `frames_rendered_twice`) is timed right after it (with --full) and reported under
+`entry_points` (`--entry deferred` makes it the headline instead).  The streams, the output buffer and
+the allocator pools of ALL streams exist before the warm-up: the W warm-up frames run through exactly
+the loop that is timed afterwards.
 
-Extra objects in the line:
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps and the result line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall milliseconds of one timed
+step, the config, and `stages_ms`: the render stage's events recorded inside the timed loop).  `--full`
+adds every side measurement listed below; the timed loop is the same in both modes.
+`--dump-outputs DIR` writes what the timed path computed in its last step, DIR/frame.npy: rank 0's
+uint8 frame [3, H, W] (clamp + pack of the op's colour) as float32.
+
+Extra objects in the line (--full only):
   roofline        dominant kernel (render_forward_kernel): algorithmic bytes per launch
                   (44*R + 8*T + 20*N, SURVEY.md §8(d) / DESIGN.md §6) / the kernel's OWN average duration:
                   HIP events on the op's stream around the launch with one frame in flight (a pass of
@@ -118,11 +125,22 @@ def parse():
     ap.add_argument("--binning-mode", type=int, default=0,
                     help="0 speculative binning capacity + deferred num_rendered wait (default), "
                          "1 exact (reference-like mid-frame wait)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (serial stage pass, re-timing guard, second entry point, "
+                         "op events, frame latency, delivery, render_all, strong scaling, statistics and rooflines, "
+                         "train and simulator legs, CPU baseline); off by default: a plain run sets up, warms up, "
+                         "times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as "
+                         "DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-baseline-worker", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, form the process group, count them with one all_reduce, print "
                          "that and exit (no rendering: checks the launch path, also without a GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def effective_cores():
@@ -717,10 +735,12 @@ def main():
                                                          if world > 1 else None)}), flush=True)
             raise
 
+        full = args.full    # everything below the headline figure (up to the result line) is --full only
+
         # short serial (one stream) pass: per-stage durations without the interference of the
         # overlapped frames, reported beside the timed-region figures
         iso_sum, iso_calls = [0.0] * 8, 0
-        if stage_timing:
+        if full and stage_timing:
             _C.set_stage_timing(1)
             for s in range(min(max(K, 10), 20)):
                 tj.pack_u8(render_frame(frames_of(s)))
@@ -739,11 +759,18 @@ def main():
             _C.set_stage_timing(0)
             attempts.append(elapsed)
 
+        # --dump-outputs: what the timed path left for its caller in the last timed step -- this rank's
+        # uint8 frame [3, H, W] (clamp + pack of the op's colour), copied before any later loop reuses
+        # the slot
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            dumped = {"frame": local[(K - 1) % local.shape[0]].float().cpu().numpy()}
+
         # The other entry point through the very same loop (untimed warm-up of W frames first):
         # reported beside the headline under entry_points, never as `value`.
         entry_fps = {args.entry: world * K / elapsed}
         other = "forward" if args.entry == "deferred" else "deferred"
-        if not args.no_secondary:
+        if full and not args.no_secondary:
             use_deferred[0] = other == "deferred"
             redone_keep = redone_frames[0]
             frame_loop(max(Wm, 2 * ns))
@@ -774,7 +801,7 @@ def main():
         # SURVEY.md §8(d) "Timing method": hipEvent pair around the op alone (all of its launches,
         # one frame in flight, eval entry), median / p95 over 50 frames
         op_events = None
-        if world == 1:
+        if full and world == 1:
             evs = []
             for k in range(51):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -791,7 +818,7 @@ def main():
 
         # the reference's own timer (render.py:30-60): synchronize-bracketed wall time per frame
         latency = None
-        if world == 1:
+        if full and world == 1:
             latency = hz.time_frames(lambda k: tj.pack_u8(render_frame(k)), 51)
             latency["method"] = ("torch.cuda.synchronize(); t0; op + clamp + pack; synchronize; t1 per "
                                  "frame on one stream, first frame excluded (render.py:30-60)")
@@ -800,7 +827,7 @@ def main():
         # rgb8 on the device and lands in pinned host memory (3 B/pixel over PCIe), consumed one
         # frame behind the producer.  Reported beside the headline figure, never as `value`.
         delivery = None
-        if world == 1 and not args.no_delivery:
+        if full and world == 1 and not args.no_delivery:
             nd = K
             fd = tj.FrameDelivery(H, W, depth=2 * ns, truncate=True)
             # untimed priming: the rgb8 staging tensors of every stream's allocator pool and the first
@@ -853,7 +880,7 @@ def main():
         # background alone, objects alone -- street_gaussian_renderer.py:13-40); the additive layered forward
         # does it in one pass.  Side leg on the bench scene with ten actor-sized clusters marked as objects.
         render_all_leg = None
-        if world == 1 and not args.no_delivery and not args.checkpoint:
+        if full and world == 1 and not args.no_delivery and not args.checkpoint:
             obj = torch.zeros(P, dtype=torch.bool, device=dev)
             for k_ in range(10):
                 c_ = torch.tensor([(-1) ** k_ * 2.0, 1.0, 8.0 + 6.0 * k_], device=dev)
@@ -900,7 +927,7 @@ def main():
         # ranks by the product's own trajectory.render_sharded (side streams, in-place pack, batched
         # asynchronous gather), wall time including the gather
         strong = None
-        if not args.no_strong and NUM_FRAMES >= world:
+        if full and not args.no_strong and NUM_FRAMES >= world:
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize()
@@ -932,24 +959,25 @@ def main():
 
         # untimed statistics pass: V and R of the frames this rank rendered
         Vs, Rs, pair_evals = [], [], []
-        e = torch.Tensor([])
-        sem0 = torch.zeros(P, 0, device=dev)
-        for s in range(min(K, 50)):
-            rs = rasterizers[frames_of(s) % NUM_FRAMES].raster_settings
-            out = _C.rasterize_gaussians(rs.bg, sc.means3D, e, sem0, sc.opacity, sc.scales,
-                                         sc.rotations, rs.scale_modifier, e, rs.viewmatrix,
-                                         rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
-                                         rs.image_width, sc.shs, rs.sh_degree, rs.campos, False, False)
-            Rs.append(int(out[0]))
-            Vs.append(int((out[5] > 0).sum()))
-            if s < 4:   # (pixel, splat) pairs the blend walks: sum over pixels of the last contributor's index
-                from gaussianrpg_amd.rasterizer import debug_export
-                dbg = debug_export(out[6], out[7], out[8], P, int(out[0]), H, W)
-                pair_evals.append(int(dbg["n_contrib"].to(torch.int64).sum()))
+        if full:
+            e = torch.Tensor([])
+            sem0 = torch.zeros(P, 0, device=dev)
+            for s in range(min(K, 50)):
+                rs = rasterizers[frames_of(s) % NUM_FRAMES].raster_settings
+                out = _C.rasterize_gaussians(rs.bg, sc.means3D, e, sem0, sc.opacity, sc.scales,
+                                             sc.rotations, rs.scale_modifier, e, rs.viewmatrix,
+                                             rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
+                                             rs.image_width, sc.shs, rs.sh_degree, rs.campos, False, False)
+                Rs.append(int(out[0]))
+                Vs.append(int((out[5] > 0).sum()))
+                if s < 4:   # (pixel, splat) pairs the blend walks: sum over pixels of the last contributor's index
+                    from gaussianrpg_amd.rasterizer import debug_export
+                    dbg = debug_export(out[6], out[7], out[8], P, int(out[0]), H, W)
+                    pair_evals.append(int(dbg["n_contrib"].to(torch.int64).sum()))
         torch.cuda.synchronize()
 
     train = None
-    if rank == 0 and world == 1 and not args.no_train:
+    if full and rank == 0 and world == 1 and not args.no_train:
         del local
         torch.cuda.empty_cache()
         try:
@@ -958,7 +986,7 @@ def main():
             train = {"error": repr(exc)}
 
     simulator = None
-    if rank == 0 and world == 1 and not args.no_delivery and not args.checkpoint:
+    if full and rank == 0 and world == 1 and not args.no_delivery and not args.checkpoint:
         torch.cuda.empty_cache()
         try:
             simulator = simulator_leg(dev)
@@ -966,98 +994,11 @@ def main():
             simulator = {"error": repr(exc)}
 
     if rank == 0:
-        T_tiles = ((W + 15) // 16) * ((H + 15) // 16)
-        N = W * H
-        R_avg = sum(Rs) / len(Rs)
-        V_avg = sum(Vs) / len(Vs)
         fps = world * K / elapsed
         ms_per_step = 1000.0 * elapsed / K
         # the timed region records the render stage only (see set_stage_timing(2) above)
         stages = {n: (stage_sum[i] / ncalls if ncalls and (stage_sum[i] > 0 or n == "render") else None)
                   for i, n in enumerate(STAGES)}
-        stages_iso = {n: (iso_sum[i] / iso_calls if iso_calls else None) for i, n in enumerate(STAGES)}
-        render_ms = stages["render"]
-        b_render = 44.0 * R_avg + 8.0 * T_tiles + 20.0 * N
-        b_frame = P * (48 + 12 * M) + 40.0 * V_avg + 88.0 * R_avg + 16.0 * T_tiles + 20.0 * N
-        # HBM bytes per launch of the dominant kernel and its VALU counters from the PMC passes of
-        # tools/profile_gpu.sh (separate rocprofv3 --pmc runs; FETCH_SIZE / WRITE_SIZE corrected as
-        # MI355X_MICROARCH.md prescribes), if a profile of this same workload AND this round's kernels
-        # has been committed; otherwise null.  Not measurable inside this process.
-        traffic, pmc, pmc_file = None, None, None
-        for name in ("round6_traffic.json", "round5_traffic.json", "round4_traffic.json", "round3_traffic.json"):
-            try:
-                tr = json.load(open(os.path.join(ROOT, "profiles", name)))
-                wl = tr.get("workload", {})
-                if wl.get("P") == P and wl.get("width") == W and wl.get("height") == H:
-                    pmc = tr["render_forward_kernel"]
-                    # round 6: record gathers count in full in FETCH_SIZE, streams at one half (calibrated,
-                    # profiles/round6_fetch_calibration.json); older files only have the all-streams correction
-                    traffic = pmc.get("hbm_bytes_calibrated", pmc["hbm_bytes_corrected"])
-                    pmc_file = "profiles/" + name
-                    break
-            except Exception:
-                traffic, pmc = None, None
-
-        def hbm_roof(kernel_ms, how):
-            ach = b_render / (kernel_ms * 1e-3) / 1e9
-            return {"kernel": "render_forward_kernel", "bound": "hbm", "achieved": ach,
-                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                    "traffic": traffic, "traffic_source": pmc_file,
-                    "algorithmic_bytes_per_launch": b_render, "avg_launch_ms": kernel_ms,
-                    "measured": how}
-
-        # `roofline`: the kernel's own duration (one frame in flight); `roofline_overlapped`: its wall
-        # duration inside the timed region, where the other frames' kernels share the chip
-        roof = roof_overlapped = roof_valu = None
-        serial_render_ms = stages_iso["render"]
-        if serial_render_ms:
-            roof = hbm_roof(serial_render_ms,
-                            "HIP events on the op's stream around the launch, %d frames with one frame in "
-                            "flight, right behind the timed region" % iso_calls)
-            roof["note"] = ("render is VALU-bound, not HBM-bound (about 25 flop per pixel-splat pair): see "
-                            "roofline_valu and DESIGN.md §6")
-        if render_ms:
-            roof_overlapped = hbm_roof(render_ms,
-                                       "HIP events around the launch INSIDE the timed region: %d streams, "
-                                       "several frames' kernels share the chip (time-sharing, not the "
-                                       "kernel's speed)" % ns)
-        if serial_render_ms:
-            pairs = sum(pair_evals) / len(pair_evals) if pair_evals else None
-            roof_valu = {"kernel": "render_forward_kernel", "bound": "valu",
-                         "pair_evals_per_frame": pairs,
-                         "pair_evals_per_s": pairs / (serial_render_ms * 1e-3) if pairs else None,
-                         "pair_evals_definition": "sum over pixels of n_contrib (list entries a pixel walks "
-                                                  "before it terminates: what the reference's schedule evaluates)"}
-            if pmc and pmc.get("SQ_INSTS_VALU"):
-                # VALU busy share from counters alone, no clock assumed: SQ_ACTIVE_INST_VALU counts
-                # quad-cycles summed over the 1024 SIMDs, GRBM_GUI_ACTIVE cycles summed over the 8 XCDs
-                busy = None
-                if pmc.get("SQ_ACTIVE_INST_VALU") and pmc.get("GRBM_GUI_ACTIVE"):
-                    busy = (pmc["SQ_ACTIVE_INST_VALU"] * 4.0 / 1024.0) / (pmc["GRBM_GUI_ACTIVE"] / 8.0)
-                roof_valu.update({
-                    "wave_valu_instructions_per_launch": pmc["SQ_INSTS_VALU"],
-                    "valu_busy_quad_cycles_per_launch": pmc.get("SQ_ACTIVE_INST_VALU"),
-                    "kernel_cycles_per_launch": pmc["GRBM_GUI_ACTIVE"] / 8.0 if pmc.get("GRBM_GUI_ACTIVE") else None,
-                    "frac": busy,
-                    "frac_definition": "share of the kernel's cycles in which a SIMD's vector ALU is executing, averaged "
-                                       "over the 1024 SIMDs: (SQ_ACTIVE_INST_VALU x 4 / 1024) / (GRBM_GUI_ACTIVE / 8), "
-                                       "both from the committed PMC passes of this workload",
-                    "cycles_per_valu_instruction": (pmc["SQ_ACTIVE_INST_VALU"] * 4.0 / pmc["SQ_INSTS_VALU"]
-                                                    if pmc.get("SQ_ACTIVE_INST_VALU") else None),
-                    "instr_per_s": pmc["SQ_INSTS_VALU"] / (serial_render_ms * 1e-3),
-                    "peak_instr_per_s": VALU_PEAK_GINSTR * 1e9,
-                    "frac_of_peak_instr_rate": pmc["SQ_INSTS_VALU"] / (serial_render_ms * 1e-3) / (VALU_PEAK_GINSTR * 1e9),
-                    "peak_source": "tools/ubench/valu_rate.hip (profiles/round3_valu_rate.txt): %.0f G wave-instr/s "
-                                   "chip-wide for dependency-free v_fma_f32 (2.25 cycles per instruction and SIMD at "
-                                   "the 1.8-2.2 GHz the part sustains under full VALU load); v_pk_fma_f32 / "
-                                   "v_pk_mul_f32 need 4.15 cycles and v_exp_f32 8.1, so a mix of them saturates the "
-                                   "VALU below the plain-fma instruction rate: frac (busy cycles) is the bound"
-                                   % VALU_PEAK_GINSTR,
-                    "counters_source": pmc_file})
-        # reference-schedule traffic: what CR/rasterizer_impl.cu moves per frame on top of
-        # the algorithmic bytes -- 64-bit keys + 32-bit values through a 6-pass sort, per-pixel ranges
-        b_ref = b_frame + 128.0 * R_avg + 27.0 * V_avg + 16.0 * P
-        ach_f = b_frame / (ms_per_step * 1e-3) / 1e9
         line = {
             "metric": "frames/sec @1920x1280, ~2M Gaussians; achieved HBM GB/s vs peak",
             "value": fps, "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": Wm,
@@ -1069,11 +1010,8 @@ def main():
                                     "configs[2]: scene-002-like synthetic street scene (seed %d), " % SCENE_SEED) +
                                    "forward op + clamp + uint8 pack per frame, %d-pose drive, "
                                    "frames sharded round-robin over ranks" % NUM_FRAMES,
-                       "P": P, "V_avg": V_avg, "R_avg": R_avg, "T": T_tiles, "width": W,
-                       "height": H, "sh_degree": sc.sh_degree, "M": M, "S": 0,
+                       "P": P, "width": W, "height": H, "sh_degree": sc.sh_degree, "M": M, "S": 0,
                        "streams_per_gpu": ns,
-                       "single_stream_frame_latency_ms": latency["median_ms"] if latency else None,
-                       "single_stream_op_device_ms": op_events["median_ms"] if op_events else None,
                        "binning_mode": "exact" if args.binning_mode else "speculative",
                        "binning_algorithm": "hierarchical" if STAGES is STAGES_HIER else "sort",
                        "entry_point": ("GaussianRasterizer.forward" if args.entry == "forward"
@@ -1081,50 +1019,149 @@ def main():
                        "deferred_count": args.entry == "deferred", "frames_rendered_twice": redone_frames[0],
                        "gather_batch_frames": args.gather_batch if world > 1 else None,
                        "parallelism": "replicas x%d, frame-sharded, final uint8 gather" % world},
-            # ONE FRAME IN FLIGHT on one stream -- what the closed-loop simulator (simulator.py:226-243: pose in,
-            # image out, strictly sequential) and render.py's timer see; `value` above keeps three frames in flight
-            "single_stream": None if latency is None or op_events is None else {
-                "frame_latency_median_ms": latency["median_ms"],
-                "frames_per_s": 1000.0 / latency["median_ms"],
-                "op_device_time_median_ms": op_events["median_ms"],
-                "serial_stage_sum_ms": serial_sum_ms,
-                "what": "frame_latency: synchronize-bracketed wall time of op + clamp + uint8 pack per frame "
-                        "(render.py:30-60's timer); op_device_time: HIP events around the op alone; details under "
-                        "frame_latency / op_device_time"},
             "collective_backend": (("rccl" if backend == "nccl" else backend) if world > 1 else None),
             "rccl_ranks_seen": ranks_seen[0],     # all_reduce of ones over the job's process group
-            "roofline": roof,
-            "roofline_overlapped": roof_overlapped,
-            "roofline_valu": roof_valu,
-            "frame_roofline": {"bound": "hbm", "achieved": ach_f, "peak": HBM_PEAK_GBS,
-                               "unit": "GB/s", "frac": ach_f / HBM_PEAK_GBS,
-                               "algorithmic_bytes_per_frame": b_frame,
-                               "reference_schedule_bytes_per_frame": b_ref,
-                               "note": "B_alg = P(48+12M) + 40V + 88R + 16T + 20N; B_ref = B_alg + 128R + 27V + 16P "
-                                       "(SURVEY.md §8(d)) is what the reference's own schedule would move"},
-            "entry_points": {
-                "headline": args.entry,
-                "forward": entry_fps.get("forward"),
-                "forward_deferred": entry_fps.get("deferred"),
-                "unit": "frames/s",
-                "frames_rendered_twice_other_entry": redone_other,
-                "what": "the same %d-stream loop through GaussianRasterizer.forward (the reference's unchanged "
-                        "surface: exact num_rendered returned by every call) and through the additive "
-                        "forward_deferred (status checked 4 frames behind)" % ns},
-            "op_device_time": op_events,
             "stages_ms": stages,
-            "stages_ms_serial": stages_iso,
-            "serial_stage_sum_ms": serial_sum_ms,
-            "timed_region_attempts_s": attempts,
-            "frame_latency": latency,
-            "delivery": delivery,
-            "render_all": render_all_leg,
-            "simulator_frame": simulator,
-            "strong_scaling": strong,
-            "train": train,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(int(R_avg))
+        if full:
+            T_tiles = ((W + 15) // 16) * ((H + 15) // 16)
+            N = W * H
+            R_avg = sum(Rs) / len(Rs)
+            V_avg = sum(Vs) / len(Vs)
+            stages_iso = {n: (iso_sum[i] / iso_calls if iso_calls else None) for i, n in enumerate(STAGES)}
+            render_ms = stages["render"]
+            b_render = 44.0 * R_avg + 8.0 * T_tiles + 20.0 * N
+            b_frame = P * (48 + 12 * M) + 40.0 * V_avg + 88.0 * R_avg + 16.0 * T_tiles + 20.0 * N
+            # HBM bytes per launch of the dominant kernel and its VALU counters from the PMC passes of
+            # tools/profile_gpu.sh (separate rocprofv3 --pmc runs; FETCH_SIZE / WRITE_SIZE corrected as
+            # MI355X_MICROARCH.md prescribes), if a profile of this same workload AND this round's kernels
+            # has been committed; otherwise null.  Not measurable inside this process.
+            traffic, pmc, pmc_file = None, None, None
+            for name in ("round6_traffic.json", "round5_traffic.json", "round4_traffic.json", "round3_traffic.json"):
+                try:
+                    tr = json.load(open(os.path.join(ROOT, "profiles", name)))
+                    wl = tr.get("workload", {})
+                    if wl.get("P") == P and wl.get("width") == W and wl.get("height") == H:
+                        pmc = tr["render_forward_kernel"]
+                        # round 6: record gathers count in full in FETCH_SIZE, streams at one half (calibrated,
+                        # profiles/round6_fetch_calibration.json); older files only have the all-streams correction
+                        traffic = pmc.get("hbm_bytes_calibrated", pmc["hbm_bytes_corrected"])
+                        pmc_file = "profiles/" + name
+                        break
+                except Exception:
+                    traffic, pmc = None, None
+
+            def hbm_roof(kernel_ms, how):
+                ach = b_render / (kernel_ms * 1e-3) / 1e9
+                return {"kernel": "render_forward_kernel", "bound": "hbm", "achieved": ach,
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                        "traffic": traffic, "traffic_source": pmc_file,
+                        "algorithmic_bytes_per_launch": b_render, "avg_launch_ms": kernel_ms,
+                        "measured": how}
+
+            # `roofline`: the kernel's own duration (one frame in flight); `roofline_overlapped`: its wall
+            # duration inside the timed region, where the other frames' kernels share the chip
+            roof = roof_overlapped = roof_valu = None
+            serial_render_ms = stages_iso["render"]
+            if serial_render_ms:
+                roof = hbm_roof(serial_render_ms,
+                                "HIP events on the op's stream around the launch, %d frames with one frame in "
+                                "flight, right behind the timed region" % iso_calls)
+                roof["note"] = ("render is VALU-bound, not HBM-bound (about 25 flop per pixel-splat pair): see "
+                                "roofline_valu and DESIGN.md §6")
+            if render_ms:
+                roof_overlapped = hbm_roof(render_ms,
+                                           "HIP events around the launch INSIDE the timed region: %d streams, "
+                                           "several frames' kernels share the chip (time-sharing, not the "
+                                           "kernel's speed)" % ns)
+            if serial_render_ms:
+                pairs = sum(pair_evals) / len(pair_evals) if pair_evals else None
+                roof_valu = {"kernel": "render_forward_kernel", "bound": "valu",
+                             "pair_evals_per_frame": pairs,
+                             "pair_evals_per_s": pairs / (serial_render_ms * 1e-3) if pairs else None,
+                             "pair_evals_definition": "sum over pixels of n_contrib (list entries a pixel walks "
+                                                      "before it terminates: what the reference's schedule evaluates)"}
+                if pmc and pmc.get("SQ_INSTS_VALU"):
+                    # VALU busy share from counters alone, no clock assumed: SQ_ACTIVE_INST_VALU counts
+                    # quad-cycles summed over the 1024 SIMDs, GRBM_GUI_ACTIVE cycles summed over the 8 XCDs
+                    busy = None
+                    if pmc.get("SQ_ACTIVE_INST_VALU") and pmc.get("GRBM_GUI_ACTIVE"):
+                        busy = (pmc["SQ_ACTIVE_INST_VALU"] * 4.0 / 1024.0) / (pmc["GRBM_GUI_ACTIVE"] / 8.0)
+                    roof_valu.update({
+                        "wave_valu_instructions_per_launch": pmc["SQ_INSTS_VALU"],
+                        "valu_busy_quad_cycles_per_launch": pmc.get("SQ_ACTIVE_INST_VALU"),
+                        "kernel_cycles_per_launch": pmc["GRBM_GUI_ACTIVE"] / 8.0 if pmc.get("GRBM_GUI_ACTIVE") else None,
+                        "frac": busy,
+                        "frac_definition": "share of the kernel's cycles in which a SIMD's vector ALU is executing, averaged "
+                                           "over the 1024 SIMDs: (SQ_ACTIVE_INST_VALU x 4 / 1024) / (GRBM_GUI_ACTIVE / 8), "
+                                           "both from the committed PMC passes of this workload",
+                        "cycles_per_valu_instruction": (pmc["SQ_ACTIVE_INST_VALU"] * 4.0 / pmc["SQ_INSTS_VALU"]
+                                                        if pmc.get("SQ_ACTIVE_INST_VALU") else None),
+                        "instr_per_s": pmc["SQ_INSTS_VALU"] / (serial_render_ms * 1e-3),
+                        "peak_instr_per_s": VALU_PEAK_GINSTR * 1e9,
+                        "frac_of_peak_instr_rate": pmc["SQ_INSTS_VALU"] / (serial_render_ms * 1e-3) / (VALU_PEAK_GINSTR * 1e9),
+                        "peak_source": "tools/ubench/valu_rate.hip (profiles/round3_valu_rate.txt): %.0f G wave-instr/s "
+                                       "chip-wide for dependency-free v_fma_f32 (2.25 cycles per instruction and SIMD at "
+                                       "the 1.8-2.2 GHz the part sustains under full VALU load); v_pk_fma_f32 / "
+                                       "v_pk_mul_f32 need 4.15 cycles and v_exp_f32 8.1, so a mix of them saturates the "
+                                       "VALU below the plain-fma instruction rate: frac (busy cycles) is the bound"
+                                       % VALU_PEAK_GINSTR,
+                        "counters_source": pmc_file})
+            # reference-schedule traffic: what CR/rasterizer_impl.cu moves per frame on top of
+            # the algorithmic bytes -- 64-bit keys + 32-bit values through a 6-pass sort, per-pixel ranges
+            b_ref = b_frame + 128.0 * R_avg + 27.0 * V_avg + 16.0 * P
+            ach_f = b_frame / (ms_per_step * 1e-3) / 1e9
+            line["config"].update({
+                "V_avg": V_avg, "R_avg": R_avg, "T": T_tiles,
+                "single_stream_frame_latency_ms": latency["median_ms"] if latency else None,
+                "single_stream_op_device_ms": op_events["median_ms"] if op_events else None})
+            line.update({
+                # ONE FRAME IN FLIGHT on one stream -- what the closed-loop simulator (simulator.py:226-243: pose in,
+                # image out, strictly sequential) and render.py's timer see; `value` above keeps three frames in flight
+                "single_stream": None if latency is None or op_events is None else {
+                    "frame_latency_median_ms": latency["median_ms"],
+                    "frames_per_s": 1000.0 / latency["median_ms"],
+                    "op_device_time_median_ms": op_events["median_ms"],
+                    "serial_stage_sum_ms": serial_sum_ms,
+                    "what": "frame_latency: synchronize-bracketed wall time of op + clamp + uint8 pack per frame "
+                            "(render.py:30-60's timer); op_device_time: HIP events around the op alone; details under "
+                            "frame_latency / op_device_time"},
+                "roofline": roof,
+                "roofline_overlapped": roof_overlapped,
+                "roofline_valu": roof_valu,
+                "frame_roofline": {"bound": "hbm", "achieved": ach_f, "peak": HBM_PEAK_GBS,
+                                   "unit": "GB/s", "frac": ach_f / HBM_PEAK_GBS,
+                                   "algorithmic_bytes_per_frame": b_frame,
+                                   "reference_schedule_bytes_per_frame": b_ref,
+                                   "note": "B_alg = P(48+12M) + 40V + 88R + 16T + 20N; B_ref = B_alg + 128R + 27V + 16P "
+                                           "(SURVEY.md §8(d)) is what the reference's own schedule would move"},
+                "entry_points": {
+                    "headline": args.entry,
+                    "forward": entry_fps.get("forward"),
+                    "forward_deferred": entry_fps.get("deferred"),
+                    "unit": "frames/s",
+                    "frames_rendered_twice_other_entry": redone_other,
+                    "what": "the same %d-stream loop through GaussianRasterizer.forward (the reference's unchanged "
+                            "surface: exact num_rendered returned by every call) and through the additive "
+                            "forward_deferred (status checked 4 frames behind)" % ns},
+                "op_device_time": op_events,
+                "stages_ms_serial": stages_iso,
+                "serial_stage_sum_ms": serial_sum_ms,
+                "timed_region_attempts_s": attempts,
+                "frame_latency": latency,
+                "delivery": delivery,
+                "render_all": render_all_leg,
+                "simulator_frame": simulator,
+                "strong_scaling": strong,
+                "train": train,
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(int(R_avg))
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            import numpy as np
+            for name, arr in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr.astype(np.float32))
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -1,8 +1,9 @@
 # quick A/B of the frame loop: bash tools/gpu_ab.sh tag [ENV=val ...]   (one bench line per call)
 cd $GRAFT_REPO_ROOT
 tag=$1; shift
-env "$@" timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train --no-strong --no-delivery ${AB_ARGS:-} > gpurun_out/ab_$tag.json 2> gpurun_out/ab_$tag.err
-python - gpurun_out/ab_$tag.json <<'PY'
+OUT=${OUT:-bench_out}; mkdir -p $OUT   # results folder (OUT=<dir> to choose another)
+env "$@" timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-train --no-strong --no-delivery ${AB_ARGS:-} > $OUT/ab_$tag.json 2> $OUT/ab_$tag.err
+python - $OUT/ab_$tag.json <<'PY'
 import json,sys
 try:
     d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

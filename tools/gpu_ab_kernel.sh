@@ -6,7 +6,7 @@ pat=$1; shift
 for v in base "$@"; do
   pre=""; [ $v != base ] && pre="$ROOT/build/variants/libgrpg_rasterizer_$v.so"
   for rep in 1 2; do
-  LD_PRELOAD=$pre timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_${v}_$rep -o stats -- python $ROOT/bench.py --steps 20 --warmup 5 --streams 1 --no-cpu-baseline --no-train --no-strong --no-delivery --no-secondary > /dev/null 2> $OUT/ab_$v.err
+  LD_PRELOAD=$pre timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_${v}_$rep -o stats -- python $ROOT/bench.py --full --steps 20 --warmup 5 --streams 1 --no-cpu-baseline --no-train --no-strong --no-delivery --no-secondary > /dev/null 2> $OUT/ab_$v.err
   f=$(find $OUT/ab_${v}_$rep -name "*kernel_stats.csv" | head -1)
   python3 - "$f" "$v" "$pat" <<'PY'
 import csv,sys

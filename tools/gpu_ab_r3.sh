@@ -6,7 +6,7 @@ for v in cur r3; do
   pre=""; [ $v = r3 ] && pre="$ROOT/build/variants/libgrpg_rasterizer_r3.so"
   for st in 20 200; do
     wu=5; [ $st = 200 ] && wu=20
-    LD_PRELOAD=$pre timeout 300 python bench.py --steps $st --warmup $wu --no-cpu-baseline --no-train --no-strong --no-delivery > $OUT/ab_${v}_${st}_$rep.json 2> $OUT/ab_${v}_${st}_$rep.err
+    LD_PRELOAD=$pre timeout 300 python bench.py --full --steps $st --warmup $wu --no-cpu-baseline --no-train --no-strong --no-delivery > $OUT/ab_${v}_${st}_$rep.json 2> $OUT/ab_${v}_${st}_$rep.err
     python - $OUT/ab_${v}_${st}_$rep.json $v $st <<'PY'
 import json,sys
 try:

@@ -6,7 +6,7 @@ variants=$1; reps=${2:-2}; extra=${3:-}
 for rep in $(seq 1 $reps); do
 for v in cur $variants; do
   pre=""; [ $v != cur ] && pre="$ROOT/build/variants/libgrpg_rasterizer_$v.so"
-  LD_PRELOAD=$pre timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train --no-strong --no-delivery $extra > $OUT/abv_${v}_$rep.json 2> $OUT/abv_${v}_$rep.err
+  LD_PRELOAD=$pre timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-train --no-strong --no-delivery $extra > $OUT/abv_${v}_$rep.json 2> $OUT/abv_${v}_$rep.err
   python - $OUT/abv_${v}_$rep.json $v <<'PY'
 import json,sys
 try:

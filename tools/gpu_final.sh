@@ -9,9 +9,9 @@ timeout 1100 python -m pytest tests -q -m gpu --maxfail=10 --timeout=500 --durat
 echo "pytest rc=$?"; tail -14 $OUT/pytest_gpu.log
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 for i in 1 2; do
-  timeout 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_final_$i.json 2> $OUT/bench_final_$i.err; echo "bench$i rc=$?"
+  timeout 500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_final_$i.json 2> $OUT/bench_final_$i.err; echo "bench$i rc=$?"
 done
-timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-train > $OUT/bench_200.json 2> $OUT/bench_200.err; echo "b200 rc=$?"
+timeout 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-train > $OUT/bench_200.json 2> $OUT/bench_200.err; echo "b200 rc=$?"
 python - <<'PY'
 import json,os
 root=os.environ.get("GRAFT_REPO_ROOT",".")

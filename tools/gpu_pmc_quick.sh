@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $OUT/pmc_$tag -o pmc -- \
-    python $ROOT/bench.py --steps 4 --warmup 1 --streams 1 --no-cpu-baseline --no-stage-timing --no-train --no-strong --no-delivery > /dev/null 2> $OUT/pmc_$tag.err
+    python $ROOT/bench.py --full --steps 4 --warmup 1 --streams 1 --no-cpu-baseline --no-stage-timing --no-train --no-strong --no-delivery > /dev/null 2> $OUT/pmc_$tag.err
 echo "pmc $tag rc=$?"
 f=$(find $OUT/pmc_$tag -name "*counter_collection.csv" | head -1)
 python3 - "$f" "$pat" <<'PY'

@@ -2,7 +2,7 @@
 # bench.py with the simulator_frame leg (short), printing the legs of interest
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$ROOT/gpurun_out; mkdir -p $OUT; cd $ROOT
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 ${BENCH_ARGS:-} > $OUT/r6_bench.json 2> $OUT/r6_bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 ${BENCH_ARGS:-} > $OUT/r6_bench.json 2> $OUT/r6_bench.err; echo "bench rc=$?"
 tail -3 $OUT/r6_bench.err
 python - <<'PY'
 import json,os

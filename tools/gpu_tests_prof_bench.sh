@@ -11,7 +11,7 @@ tail -${TAIL:-30} $OUT/pytest_gpu.log
 fi
 PROF_ARGS="--streams 1" bash tools/gpu_prof_quick.sh s1 2>&1 | cut -c1-150
 cd $ROOT
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train > $OUT/bench_a.json 2> $OUT/bench_a.err; echo "bench rc=$?"
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-train > $OUT/bench_a.json 2> $OUT/bench_a.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 try:
