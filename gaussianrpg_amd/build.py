@@ -40,6 +40,8 @@ HIP_UNITS = {
     "knn.hip": ["-ffp-contract=off"],
     # hardware float atomics for the cube-map gradient
     "sky.hip": ["-munsafe-fp-atomics"],
+    # fused SSIM + L1 loss: no atomics, deterministic fixed-order reduction
+    "ssim.hip": [],
     "api.hip": [],
 }
 HEADERS = ["common.h", "gaussian_math.h", "blend_math.h", "compose_math.h", os.path.join(ROOT, "include", "grpg_rasterizer.h")]

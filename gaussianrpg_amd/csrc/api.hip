@@ -1686,6 +1686,54 @@ int grpg_knn_mean_dist2(int P, const float* points, float* mean_dists,
   return GRPG_OK;
 }
 
+size_t grpg_ssim_workspace_bytes(int B, int C, int height, int width) {
+  if (B <= 0 || C <= 0 || height <= 0 || width <= 0) return 0;
+  return ssim_workspace_bytes(B, C, height, width);
+}
+
+namespace {
+int ssim_check(int B, int C, int height, int width, const float* img1, const float* img2,
+               const unsigned char* mask, int mask_batch, int mask_channels) {
+  if (B <= 0 || C <= 0 || height <= 0 || width <= 0)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: B, C, height and width must be positive");
+  if ((long long)B * C * height * width > 0x7FFFFFFFll)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: B*C*H*W must be < 2^31");
+  if (!img1 || !img2) return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: NULL image pointer");
+  if (mask && ((mask_batch != 1 && mask_batch != B) || (mask_channels != 1 && mask_channels != C)))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: the mask must have 1 or B images of 1 or C channels");
+  return GRPG_OK;
+}
+}  // namespace
+
+int grpg_ssim_forward(int B, int C, int height, int width, const float* img1, const float* img2,
+                      const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
+                      float w_ssim, float* stats, float* saved, void* workspace, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (int rc = ssim_check(B, C, height, width, img1, img2, mask, mask_batch, mask_channels)) return rc;
+  if (!stats || !workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: NULL stats / workspace");
+  if ((uintptr_t)workspace & 7) return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: workspace must be 8-byte aligned");
+  launch_ssim_forward((hipStream_t)hip_stream, B, C, height, width, img1, img2, mask, mask_batch,
+                      mask_channels, w_l1, w_ssim, stats, saved, (char*)workspace);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_ssim_backward(int B, int C, int height, int width, const float* img1, const float* img2,
+                       const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
+                       float w_ssim, const float* stats, const float* saved, const float* grad_stats,
+                       float* grad_img1, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (int rc = ssim_check(B, C, height, width, img1, img2, mask, mask_batch, mask_channels)) return rc;
+  if (!stats || !saved || !grad_stats || !grad_img1)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: NULL stats / saved partials / gradient pointer");
+  launch_ssim_backward((hipStream_t)hip_stream, B, C, height, width, img1, img2, mask, mask_batch,
+                       mask_channels, w_l1, w_ssim, stats, saved, grad_stats, grad_img1);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
 int grpg_debug_export(int P, int R, int width, int height, const char* geom_buffer,
                       const char* binning_buffer, const char* image_buffer, uint64_t* keys_sorted,
                       uint32_t* point_list, uint32_t* ranges, uint32_t* n_contrib, float* means2D,

@@ -629,4 +629,14 @@ void launch_sky_backward(hipStream_t st, const float* cube, int res, const float
 size_t knn_workspace_bytes(int P);
 void launch_knn(hipStream_t s, int P, const float* points, float* mean_dists, char* workspace);
 
+// fused SSIM + L1 loss (ssim.hip)
+size_t ssim_workspace_bytes(int B, int C, int H, int W);
+void launch_ssim_forward(hipStream_t st, int B, int C, int H, int W, const float* x1, const float* x2,
+                         const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
+                         float w_ssim, float* stats, float* saved, char* workspace);
+void launch_ssim_backward(hipStream_t st, int B, int C, int H, int W, const float* x1, const float* x2,
+                          const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
+                          float w_ssim, const float* stats, const float* saved, const float* grad_stats,
+                          float* grad_x1);
+
 }  // namespace grpg

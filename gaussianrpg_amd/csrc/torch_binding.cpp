@@ -1101,6 +1101,69 @@ torch::Tensor distCUDA2(const torch::Tensor& points) {
   return means;
 }
 
+// Fused SSIM + L1 loss (gaussianrpg_amd/loss.py).  img1 / img2: float32 [B,C,H,W] on one device (made contiguous
+// here); mask: empty or uint8 [1|B, 1|C, H, W].  Returns (stats [4 + B], saved partials [3,B,C,H,W] or empty).
+namespace {
+void ssim_args(const torch::Tensor& img1, const torch::Tensor& img2, const torch::Tensor& mask) {
+  TORCH_CHECK(img1.is_cuda() && img2.is_cuda(), "ssim: images must live on a ROCm/HIP device (no CPU path)");
+  TORCH_CHECK(img1.scalar_type() == torch::kFloat32 && img2.scalar_type() == torch::kFloat32,
+              "ssim: images must be float32");
+  TORCH_CHECK(img1.dim() == 4 && img1.sizes() == img2.sizes(), "ssim: images must be two [B,C,H,W] of one shape");
+  TORCH_CHECK(img1.device() == img2.device(), "ssim: images on different devices");
+  if (mask.defined() && mask.numel() > 0) {
+    TORCH_CHECK(mask.device() == img1.device() && mask.scalar_type() == torch::kUInt8 && mask.dim() == 4 &&
+                    mask.size(2) == img1.size(2) && mask.size(3) == img1.size(3),
+                "ssim: mask must be uint8 [1|B, 1|C, H, W] on the images' device");
+  }
+}
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor> SsimForward(const torch::Tensor& img1, const torch::Tensor& img2,
+                                                     const torch::Tensor& mask, const double w_l1,
+                                                     const double w_ssim, const bool save_partials) {
+  ssim_args(img1, img2, mask);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(img1.device());
+  const torch::Tensor a = img1.contiguous(), b = img2.contiguous();
+  const bool has_mask = mask.defined() && mask.numel() > 0;
+  const torch::Tensor m = has_mask ? mask.contiguous() : mask;
+  const int B = a.size(0), C = a.size(1), H = a.size(2), W = a.size(3);
+  auto fopts = a.options();
+  torch::Tensor stats = torch::empty({4 + B}, fopts);
+  torch::Tensor saved = save_partials ? torch::empty({3, B, C, H, W}, fopts) : torch::empty({0}, fopts);
+  const size_t ws_bytes = grpg_ssim_workspace_bytes(B, C, H, W);
+  torch::Tensor ws = torch::empty({(long long)(ws_bytes > 0 ? ws_bytes : 8)}, a.options().dtype(torch::kByte));
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int rc = grpg_ssim_forward(B, C, H, W, a.data_ptr<float>(), b.data_ptr<float>(),
+                                   has_mask ? m.data_ptr<uint8_t>() : nullptr, has_mask ? m.size(0) : 1,
+                                   has_mask ? m.size(1) : 1, (float)w_l1, (float)w_ssim, stats.data_ptr<float>(),
+                                   save_partials ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (void*)stream);
+  if (rc != GRPG_OK) raise_abi_error("grpg_ssim_forward", rc);
+  return std::make_tuple(stats, saved);
+}
+
+torch::Tensor SsimBackward(const torch::Tensor& img1, const torch::Tensor& img2, const torch::Tensor& mask,
+                           const double w_l1, const double w_ssim, const torch::Tensor& stats,
+                           const torch::Tensor& saved, const torch::Tensor& grad_stats) {
+  ssim_args(img1, img2, mask);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(img1.device());
+  const torch::Tensor a = img1.contiguous(), b = img2.contiguous();
+  const bool has_mask = mask.defined() && mask.numel() > 0;
+  const torch::Tensor m = has_mask ? mask.contiguous() : mask;
+  const int B = a.size(0), C = a.size(1), H = a.size(2), W = a.size(3);
+  TORCH_CHECK(stats.numel() == 4 + B && saved.numel() == 3 * a.numel(), "ssim_backward: stats / saved do not match");
+  const torch::Tensor g = grad_stats.to(a.device(), torch::kFloat32).contiguous();
+  TORCH_CHECK(g.numel() == 4 + B, "ssim_backward: grad_stats must have 4 + B elements");
+  torch::Tensor grad = torch::empty_like(a);
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int rc = grpg_ssim_backward(B, C, H, W, a.data_ptr<float>(), b.data_ptr<float>(),
+                                    has_mask ? m.data_ptr<uint8_t>() : nullptr, has_mask ? m.size(0) : 1,
+                                    has_mask ? m.size(1) : 1, (float)w_l1, (float)w_ssim, stats.data_ptr<float>(),
+                                    saved.data_ptr<float>(), g.data_ptr<float>(), grad.data_ptr<float>(),
+                                    (void*)stream);
+  if (rc != GRPG_OK) raise_abi_error("grpg_ssim_backward", rc);
+  return grad;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rasterize_gaussians", &RasterizeGaussians);
   m.def("rasterize_gaussians_eval", &RasterizeGaussiansEval);
@@ -1108,6 +1171,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rasterize_gaussians_layers", &RasterizeGaussiansLayers);
   m.def("frame_status", &FrameStatus, pybind11::arg("ticket"), pybind11::arg("wait") = true);
   m.def("distCUDA2", &distCUDA2);
+  m.def("ssim_forward", &SsimForward);     // (stats [4+B], saved partials)
+  m.def("ssim_backward", &SsimBackward);
   m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);
   m.def("rasterize_gaussians_backward_lean", &RasterizeGaussiansBackwardLean);
   m.def("mark_visible", &markVisible);

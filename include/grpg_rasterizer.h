@@ -628,6 +628,34 @@ GRPG_API int grpg_knn_mean_dist2(int P, const float* points, float* mean_dists,
                                  grpg_alloc_fn workspace_alloc, void* workspace_user,
                                  void* hip_stream);
 
+/*
+ * Fused SSIM + L1 training loss (no counterpart in the extension; replaces the PyTorch code of
+ * lib/utils/loss_utils.py:21-36,81-121 and the mix of train.py:116-118):
+ *   loss = w_l1 * L1 + w_ssim * (1 - SSIM),   with w_l1 = (1 - lambda_dssim) * lambda_l1, w_ssim = lambda_dssim.
+ * img1, img2: device fp32 [B,C,H,W], contiguous.  mask: NULL or device uint8 [mask_batch, mask_channels, H, W]
+ * (mask_batch 1 or B, mask_channels 1 or C; nonzero = selected), applied like loss_utils: both images are zeroed
+ * outside the mask before any moment is taken; the SSIM mean runs over all B*C*H*W positions, the L1 mean over the
+ * selected elements only (an all-false mask gives a NaN L1, as the reference).  11x11 Gaussian window, sigma 1.5,
+ * zero padding (the only window loss_utils.ssim is used with).
+ * grpg_ssim_forward writes stats[4 + B] (device fp32): [0] loss, [1] L1 mean, [2] SSIM mean, [3] number of selected
+ * elements, [4 + b] SSIM mean of image b.  saved: NULL (no gradient wanted) or device fp32 [3,B,C,H,W] that receives
+ * the per-pixel partials the backward reads.  workspace: device memory of grpg_ssim_workspace_bytes(B, C, H, W)
+ * bytes, 8-byte aligned (per-workgroup partial sums; reduced in a fixed order: identical calls give identical bits).
+ * grpg_ssim_backward: grad_stats (device fp32 [4 + B]) is the upstream gradient of the stats vector (entries 0, 1,
+ * 2 and 4.. are used; it is read on the device, no host synchronisation); stats / saved as the forward left them;
+ * writes every element of grad_img1 (device fp32 [B,C,H,W]).  No gradient with respect to img2.
+ * Both run asynchronously on hip_stream.  Purely additive exports: GRPG_ABI_VERSION stays 7.
+ * Returns GRPG_OK, GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT for bad shapes / pointers.
+ */
+GRPG_API size_t grpg_ssim_workspace_bytes(int B, int C, int height, int width);
+GRPG_API int grpg_ssim_forward(int B, int C, int height, int width, const float* img1, const float* img2,
+                               const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
+                               float w_ssim, float* stats, float* saved, void* workspace, void* hip_stream);
+GRPG_API int grpg_ssim_backward(int B, int C, int height, int width, const float* img1, const float* img2,
+                                const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
+                                float w_ssim, const float* stats, const float* saved, const float* grad_stats,
+                                float* grad_img1, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
