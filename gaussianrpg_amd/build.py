@@ -42,6 +42,9 @@ HIP_UNITS = {
     "sky.hip": ["-munsafe-fp-atomics"],
     # fused SSIM + L1 loss: no atomics, deterministic fixed-order reduction
     "ssim.hip": [],
+    # fused lidar / sky / object-alpha losses: the error plane bit-identical to PyTorch's float32
+    # expression (no FMA contraction); integer atomics only
+    "aux_loss.hip": ["-ffp-contract=off"],
     "api.hip": [],
 }
 HEADERS = ["common.h", "gaussian_math.h", "blend_math.h", "compose_math.h", os.path.join(ROOT, "include", "grpg_rasterizer.h")]

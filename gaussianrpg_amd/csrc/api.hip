@@ -1734,6 +1734,65 @@ int grpg_ssim_backward(int B, int C, int height, int width, const float* img1, c
   return GRPG_OK;
 }
 
+size_t grpg_aux_loss_workspace_bytes(int height, int width) {
+  if (height <= 0 || width <= 0 || (long long)height * width > 0x7FFFFFFFll) return 0;
+  return aux_loss_workspace_bytes(height, width);
+}
+
+namespace {
+int aux_check(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
+              const unsigned char* sky_mask, const float* acc_obj, const unsigned char* obj_bound,
+              float lambda_depth_lidar, float lambda_sky, float lambda_reg, const void* workspace) {
+  if (height <= 0 || width <= 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: height and width must be positive");
+  if ((long long)height * width > 0x7FFFFFFFll)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: H*W must be < 2^31");
+  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: NULL workspace");
+  if ((uintptr_t)workspace & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: workspace must be 16-byte aligned");
+  if (lambda_depth_lidar > 0.f && lidar_depth && (!depth || !acc))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: the lidar term needs depth and acc");
+  if (lambda_sky > 0.f && sky_mask && !acc) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: the sky term needs acc");
+  if (lambda_reg > 0.f && obj_bound && !acc_obj)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: the object term needs acc_obj");
+  return GRPG_OK;
+}
+}  // namespace
+
+int grpg_aux_loss_forward(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
+                          const unsigned char* mask, const unsigned char* sky_mask, const float* acc_obj,
+                          const unsigned char* obj_bound, float sky_scale, float lambda_depth_lidar,
+                          float lambda_sky, float lambda_reg, float* stats, void* workspace, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (int rc = aux_check(height, width, depth, acc, lidar_depth, sky_mask, acc_obj, obj_bound, lambda_depth_lidar,
+                         lambda_sky, lambda_reg, workspace))
+    return rc;
+  if (!stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: NULL stats");
+  const AuxPlanes planes{depth, acc, lidar_depth, mask, sky_mask, acc_obj, obj_bound};
+  launch_aux_loss_forward((hipStream_t)hip_stream, height, width, planes, sky_scale, lambda_depth_lidar,
+                          lambda_sky, lambda_reg, stats, (char*)workspace);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_aux_loss_backward(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
+                           const unsigned char* mask, const unsigned char* sky_mask, const float* acc_obj,
+                           const unsigned char* obj_bound, float sky_scale, float lambda_depth_lidar,
+                           float lambda_sky, float lambda_reg, const float* grad_stats, const void* workspace,
+                           float* grad_depth, float* grad_acc, float* grad_acc_obj, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (int rc = aux_check(height, width, depth, acc, lidar_depth, sky_mask, acc_obj, obj_bound, lambda_depth_lidar,
+                         lambda_sky, lambda_reg, workspace))
+    return rc;
+  if (!grad_stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: NULL grad_stats");
+  const AuxPlanes planes{depth, acc, lidar_depth, mask, sky_mask, acc_obj, obj_bound};
+  launch_aux_loss_backward((hipStream_t)hip_stream, height, width, planes, sky_scale, lambda_depth_lidar,
+                           lambda_sky, lambda_reg, grad_stats, (const char*)workspace, grad_depth, grad_acc,
+                           grad_acc_obj);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
 int grpg_debug_export(int P, int R, int width, int height, const char* geom_buffer,
                       const char* binning_buffer, const char* image_buffer, uint64_t* keys_sorted,
                       uint32_t* point_list, uint32_t* ranges, uint32_t* n_contrib, float* means2D,

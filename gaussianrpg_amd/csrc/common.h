@@ -639,4 +639,21 @@ void launch_ssim_backward(hipStream_t st, int B, int C, int H, int W, const floa
                           float w_ssim, const float* stats, const float* saved, const float* grad_stats,
                           float* grad_x1);
 
+// fused lidar-depth / sky / object-alpha losses (aux_loss.hip).  Planes H*W, NULL when absent.
+struct AuxPlanes {
+  const float* depth;
+  const float* acc;
+  const float* lidar;
+  const unsigned char* mask;
+  const unsigned char* sky;
+  const float* acc_obj;
+  const unsigned char* bound;
+};
+size_t aux_loss_workspace_bytes(int H, int W);
+void launch_aux_loss_forward(hipStream_t st, int H, int W, const AuxPlanes& planes, float sky_scale,
+                             float lam_lidar, float lam_sky, float lam_reg, float* stats, char* workspace);
+void launch_aux_loss_backward(hipStream_t st, int H, int W, const AuxPlanes& planes, float sky_scale,
+                              float lam_lidar, float lam_sky, float lam_reg, const float* grad_stats,
+                              const char* workspace, float* grad_depth, float* grad_acc, float* grad_acc_obj);
+
 }  // namespace grpg

@@ -1164,6 +1164,88 @@ torch::Tensor SsimBackward(const torch::Tensor& img1, const torch::Tensor& img2,
   return grad;
 }
 
+// Fused lidar-depth / sky / object-alpha losses (gaussianrpg_amd/loss.py).  Every plane is empty (absent) or a
+// contiguous H*W tensor on one device: float32 for depth / acc / lidar_depth / acc_obj, uint8 for the masks.
+// Returns (stats [9], workspace); the workspace carries the selection state to the backward.
+namespace {
+struct AuxIn {
+  int H, W;
+  torch::Device dev = torch::kCPU;
+};
+
+const float* aux_f(const torch::Tensor& t) { return t.numel() ? t.data_ptr<float>() : nullptr; }
+const unsigned char* aux_u8(const torch::Tensor& t) { return t.numel() ? t.data_ptr<uint8_t>() : nullptr; }
+
+AuxIn aux_args(const int64_t H, const int64_t W, const std::vector<torch::Tensor>& planes,
+               const std::vector<torch::Tensor>& masks) {
+  AuxIn in;
+  TORCH_CHECK(H > 0 && W > 0 && H * W <= 0x7FFFFFFFll, "aux_loss: H and W must be positive with H*W < 2^31");
+  in.H = (int)H;
+  in.W = (int)W;
+  bool any = false;
+  auto check = [&](const torch::Tensor& t, const c10::ScalarType ty, const char* what) {
+    if (!t.defined() || t.numel() == 0) return;
+    TORCH_CHECK(t.is_cuda(), "aux_loss: ", what, " must live on a ROCm/HIP device (no CPU path)");
+    TORCH_CHECK(t.scalar_type() == ty && t.numel() == H * W && t.is_contiguous(), "aux_loss: ", what,
+                " must be a contiguous ", ty == torch::kFloat32 ? "float32" : "uint8", " plane of H*W elements");
+    if (any) TORCH_CHECK(t.device() == in.dev, "aux_loss: planes on different devices");
+    in.dev = t.device();
+    any = true;
+  };
+  for (const auto& t : planes) check(t, torch::kFloat32, "plane");
+  for (const auto& t : masks) check(t, torch::kUInt8, "mask");
+  TORCH_CHECK(any, "aux_loss: no input plane");
+  return in;
+}
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor> AuxLossForward(
+    const int64_t H, const int64_t W, const torch::Tensor& depth, const torch::Tensor& acc,
+    const torch::Tensor& lidar, const torch::Tensor& mask, const torch::Tensor& sky, const torch::Tensor& acc_obj,
+    const torch::Tensor& bound, const double sky_scale, const double lam_lidar, const double lam_sky,
+    const double lam_reg) {
+  const AuxIn in = aux_args(H, W, {depth, acc, lidar, acc_obj}, {mask, sky, bound});
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.dev);
+  auto fopts = torch::TensorOptions().dtype(torch::kFloat32).device(in.dev);
+  torch::Tensor stats = torch::empty({9}, fopts);
+  const size_t ws_bytes = grpg_aux_loss_workspace_bytes(in.H, in.W);
+  torch::Tensor ws = torch::empty({(long long)ws_bytes}, fopts.dtype(torch::kByte));
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int rc = grpg_aux_loss_forward(in.H, in.W, aux_f(depth), aux_f(acc), aux_f(lidar), aux_u8(mask), aux_u8(sky),
+                                       aux_f(acc_obj), aux_u8(bound), (float)sky_scale, (float)lam_lidar,
+                                       (float)lam_sky, (float)lam_reg, stats.data_ptr<float>(), ws.data_ptr(),
+                                       (void*)stream);
+  if (rc != GRPG_OK) raise_abi_error("grpg_aux_loss_forward", rc);
+  return std::make_tuple(stats, ws);
+}
+
+// Returns (grad_depth, grad_acc, grad_acc_obj), each [H*W] or empty when not wanted.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> AuxLossBackward(
+    const int64_t H, const int64_t W, const torch::Tensor& depth, const torch::Tensor& acc,
+    const torch::Tensor& lidar, const torch::Tensor& mask, const torch::Tensor& sky, const torch::Tensor& acc_obj,
+    const torch::Tensor& bound, const double sky_scale, const double lam_lidar, const double lam_sky,
+    const double lam_reg, const torch::Tensor& grad_stats, const torch::Tensor& ws, const bool want_depth,
+    const bool want_acc, const bool want_acc_obj) {
+  const AuxIn in = aux_args(H, W, {depth, acc, lidar, acc_obj}, {mask, sky, bound});
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.dev);
+  TORCH_CHECK(ws.device() == in.dev && (size_t)ws.numel() == grpg_aux_loss_workspace_bytes(in.H, in.W),
+              "aux_loss_backward: workspace does not match");
+  const torch::Tensor g = grad_stats.to(in.dev, torch::kFloat32).contiguous();
+  TORCH_CHECK(g.numel() == 9, "aux_loss_backward: grad_stats must have 9 elements");
+  auto fopts = torch::TensorOptions().dtype(torch::kFloat32).device(in.dev);
+  auto plane = [&](bool want) { return want ? torch::empty({H * W}, fopts) : torch::empty({0}, fopts); };
+  torch::Tensor gd = plane(want_depth), ga = plane(want_acc), go = plane(want_acc_obj);
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int rc = grpg_aux_loss_backward(in.H, in.W, aux_f(depth), aux_f(acc), aux_f(lidar), aux_u8(mask), aux_u8(sky),
+                                        aux_f(acc_obj), aux_u8(bound), (float)sky_scale, (float)lam_lidar,
+                                        (float)lam_sky, (float)lam_reg, g.data_ptr<float>(), ws.data_ptr(),
+                                        want_depth ? gd.data_ptr<float>() : nullptr,
+                                        want_acc ? ga.data_ptr<float>() : nullptr,
+                                        want_acc_obj ? go.data_ptr<float>() : nullptr, (void*)stream);
+  if (rc != GRPG_OK) raise_abi_error("grpg_aux_loss_backward", rc);
+  return std::make_tuple(gd, ga, go);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rasterize_gaussians", &RasterizeGaussians);
   m.def("rasterize_gaussians_eval", &RasterizeGaussiansEval);
@@ -1173,6 +1255,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("distCUDA2", &distCUDA2);
   m.def("ssim_forward", &SsimForward);     // (stats [4+B], saved partials)
   m.def("ssim_backward", &SsimBackward);
+  m.def("aux_loss_forward", &AuxLossForward);    // (stats [9], workspace)
+  m.def("aux_loss_backward", &AuxLossBackward);
   m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);
   m.def("rasterize_gaussians_backward_lean", &RasterizeGaussiansBackwardLean);
   m.def("mark_visible", &markVisible);

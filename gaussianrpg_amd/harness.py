@@ -339,19 +339,27 @@ def simulator_frame(scene: Scene, cam: CameraTensors, sky=None, K=None, w2c=None
 def train_loss(render_pkg: dict, gt_image: torch.Tensor, lidar_depth: Optional[torch.Tensor] = None,
                sky_mask: Optional[torch.Tensor] = None, lambda_l1: float = 1.0,
                lambda_depth_lidar: float = 0.1, lambda_sky: float = 0.05, *, lambda_dssim: float = 0.0,
-               mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+               mask: Optional[torch.Tensor] = None, fused_aux: bool = False) -> torch.Tensor:
     """The loss mix of train.py:110-127,164-176 that reaches the op's four outputs: L1 on rgb
     (loss_utils.l1_loss), the sky term on acc, the lidar term on depth / (acc + 1e-10) keeping the
     smallest 95 % of the errors.  (SSIM, semantic and the regularisers do not change which output
     gradients are non-zero.)  lambda_dssim > 0 or a mask: the rgb term is the reference's full
     train.py:118 mix (1 - lambda_dssim) * lambda_l1 * L1 + lambda_dssim * (1 - SSIM), computed by the
-    fused kernels of gaussianrpg_amd.loss; the defaults keep the plain L1 term."""
+    fused kernels of gaussianrpg_amd.loss; the defaults keep the plain L1 term.  fused_aux=True: the sky and
+    lidar terms come from the fused kernels of gaussianrpg_amd.loss.aux_loss (no host sync; the lidar guard is
+    the reference's torch.nonzero(depth_mask).any()); the default keeps the PyTorch terms."""
     image, acc, depth = render_pkg["rgb"], render_pkg["acc"], render_pkg["depth"]
     if lambda_dssim == 0.0 and mask is None:
         loss = lambda_l1 * torch.abs(image - gt_image).mean()
     else:
         from .loss import l1_ssim_loss
         loss = l1_ssim_loss(image, gt_image, mask, lambda_l1=lambda_l1, lambda_dssim=lambda_dssim)[0]
+    if fused_aux:
+        if (sky_mask is not None and lambda_sky > 0) or (lidar_depth is not None and lambda_depth_lidar > 0):
+            from .loss import aux_loss
+            loss = loss + aux_loss(depth, acc, lidar_depth=lidar_depth, sky_mask=sky_mask,
+                                   lambda_depth_lidar=lambda_depth_lidar, lambda_sky=lambda_sky)[0]
+        return loss
     if sky_mask is not None and lambda_sky > 0:
         a = torch.clamp(acc, min=1e-6, max=1.0 - 1e-6)
         loss = loss + lambda_sky * torch.where(sky_mask, -torch.log(1 - a), -torch.log(a)).mean()

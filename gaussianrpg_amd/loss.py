@@ -15,12 +15,30 @@ bool (or uint8) tensor that broadcasts against the image the way ``torch.where(m
 Only the first image receives a gradient.  No host synchronisation in forward or backward.  There is no
 CPU or PyTorch fallback: CPU tensors, other dtypes, window_size != 11, mismatched shapes and a second
 image that requires a gradient are errors.
+
+The auxiliary terms of train.py (csrc/aux_loss.hip), on float32 planes [H,W] or [1,H,W] and bool (or uint8)
+masks of the same H x W:
+
+  lidar_depth_loss(depth, acc, lidar_depth, mask=None)   == train.py:164-176 (lidar_depth_loss)
+  sky_loss(acc, sky_mask, scale=1.0)                      == train.py:121-127 (sky_loss, times lambda_sky_scale)
+  obj_acc_loss(acc_obj, obj_bound)                        == train.py:145-158 (obj_acc_loss)
+  aux_loss(depth, acc, *, lidar_depth=None, mask=None, sky_mask=None, sky_scale=1.0, acc_obj=None,
+           obj_bound=None, lambda_depth_lidar=0.0, lambda_sky=0.0, lambda_reg=0.0)
+      == lambda_depth_lidar * lidar + lambda_sky * sky + lambda_reg * obj in one forward and one backward launch
+      chain; returns (loss, terms), terms a dict of detached device scalars for scalar_dict with the keys of the
+      terms that are on ('lidar_depth_loss', 'sky_loss', 'obj_acc_loss').  A lambda of 0 or a missing
+      lidar_depth / sky_mask / acc_obj / obj_bound turns its term off (not evaluated, no gradient).
+
+The lidar term keeps the reference's guard exactly, on the device: 0 with a zero gradient when no pixel is selected
+or only flat index 0 is; NaN with a zero gradient when one other pixel is.  Ties at the k-th smallest error share
+its weight evenly.  No host synchronisation in forward or backward.
 """
 import torch
 
 from .rasterizer import _C
 
-__all__ = ["ssim", "l1_loss", "l1_ssim_loss"]
+__all__ = ["ssim", "l1_loss", "l1_ssim_loss", "aux_loss", "lidar_depth_loss", "sky_loss", "obj_acc_loss",
+           "lidar_selection"]
 
 
 def _check(img1, img2, what=("img1", "img2")):
@@ -121,3 +139,129 @@ def l1_ssim_loss(image, gt, mask=None, lambda_l1=1.0, lambda_dssim=0.2):
     _check(image, gt, ("image", "gt"))
     stats = _run(image, gt, mask, (1.0 - lambda_dssim) * lambda_l1, lambda_dssim)
     return stats[0], stats[1].detach(), stats[2].detach()
+
+
+# ---- auxiliary terms: lidar depth, sky, object alpha (csrc/aux_loss.hip) ----
+
+def _aux_plane(t, name, hw, mask=False):
+    """None or a [H,W] / [1,H,W] device plane -> (flat contiguous tensor or None, hw)."""
+    if t is None:
+        return None, hw
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("gaussianrpg_amd.loss: %s must be a torch.Tensor" % name)
+    if mask:
+        if t.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("gaussianrpg_amd.loss: %s must be a bool (or uint8) tensor (got %s)" % (name, t.dtype))
+    elif t.dtype != torch.float32:
+        raise TypeError("gaussianrpg_amd.loss: %s must be float32 (got %s)" % (name, t.dtype))
+    if not (t.dim() == 2 or (t.dim() == 3 and t.shape[0] == 1)):
+        raise ValueError("gaussianrpg_amd.loss: %s must be [H,W] or [1,H,W] (got %s)" % (name, tuple(t.shape)))
+    if hw is not None and tuple(t.shape[-2:]) != hw[:2]:
+        raise ValueError("gaussianrpg_amd.loss: %s is %s, another plane is %dx%d" % (name, tuple(t.shape), *hw[:2]))
+    flat = t.reshape(-1)
+    if mask:
+        flat = flat.contiguous().view(torch.uint8) if flat.dtype == torch.bool else flat.contiguous()
+    else:
+        flat = flat.contiguous()
+    return flat, (int(t.shape[-2]), int(t.shape[-1]), t.device)
+
+
+class _AuxLoss(torch.autograd.Function):
+    """flat planes -> (stats [9]: total, lidar, sky, obj, N, k, t, c_lt, c_eq; workspace)."""
+
+    @staticmethod
+    def forward(ctx, depth, acc, acc_obj, lidar, mask, sky, bound, cfg):
+        H, W, sky_scale, lams = cfg
+        stats, ws = _C.aux_loss_forward(H, W, depth, acc, lidar, mask, sky, acc_obj, bound, sky_scale, *lams)
+        ctx.save_for_backward(depth, acc, acc_obj, lidar, mask, sky, bound, ws)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(ws)
+        return stats, ws
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_stats, _grad_ws):
+        depth, acc, acc_obj, lidar, mask, sky, bound, ws = ctx.saved_tensors
+        H, W, sky_scale, lams = ctx.cfg
+        want = [bool(ctx.needs_input_grad[i]) and t.numel() > 0 for i, t in enumerate((depth, acc, acc_obj))]
+        if not any(want):
+            return (None,) * 8
+        if grad_stats is None:
+            grad_stats = torch.zeros(9, dtype=torch.float32, device=ws.device)
+        gd, ga, go = _C.aux_loss_backward(H, W, depth, acc, lidar, mask, sky, acc_obj, bound, sky_scale, *lams,
+                                          grad_stats.contiguous(), ws, *want)
+        return (gd if want[0] else None, ga if want[1] else None, go if want[2] else None) + (None,) * 5
+
+
+def _aux_run(depth, acc, lidar_depth, mask, sky_mask, sky_scale, acc_obj, obj_bound, lambda_depth_lidar,
+             lambda_sky, lambda_reg):
+    lam_l, lam_s, lam_r = float(lambda_depth_lidar), float(lambda_sky), float(lambda_reg)
+    lidar_on = lam_l > 0 and lidar_depth is not None
+    sky_on = lam_s > 0 and sky_mask is not None
+    obj_on = lam_r > 0 and acc_obj is not None and obj_bound is not None
+    if lidar_on and (depth is None or acc is None):
+        raise ValueError("gaussianrpg_amd.loss: the lidar depth term needs depth and acc")
+    if sky_on and acc is None:
+        raise ValueError("gaussianrpg_amd.loss: the sky term needs acc")
+    if lidar_on and lidar_depth.requires_grad:
+        raise ValueError("gaussianrpg_amd.loss: lidar_depth requires a gradient; the fused loss differentiates only "
+                         "depth, acc and acc_obj (the reference's lidar depth never requires one)")
+    hw = None
+    planes = {}
+    for name, t, on, is_mask in (("depth", depth, lidar_on, False), ("acc", acc, lidar_on or sky_on, False),
+                                 ("lidar_depth", lidar_depth, lidar_on, False), ("mask", mask, lidar_on, True),
+                                 ("sky_mask", sky_mask, sky_on, True), ("acc_obj", acc_obj, obj_on, False),
+                                 ("obj_bound", obj_bound, obj_on, True)):
+        planes[name], hw = _aux_plane(t if on else None, name, hw, is_mask)
+    if hw is None:
+        raise ValueError("gaussianrpg_amd.loss: no auxiliary term is on (every lambda is 0 or its plane is missing)")
+    for name, t in planes.items():
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError("gaussianrpg_amd.loss: %s must live on a ROCm/HIP device (torch device 'cuda'); "
+                               "the fused loss is MI355X-native and has no CPU path" % name)
+        if t.device != hw[2]:
+            raise ValueError("gaussianrpg_amd.loss: %s on %s, another plane on %s" % (name, t.device, hw[2]))
+    empty = torch.empty(0, device=hw[2])
+    args = [planes[k] if planes[k] is not None else empty
+            for k in ("depth", "acc", "acc_obj", "lidar_depth", "mask", "sky_mask", "obj_bound")]
+    stats, ws = _AuxLoss.apply(*args, (hw[0], hw[1], float(sky_scale), (lam_l, lam_s, lam_r)))
+    return stats, ws, (lidar_on, sky_on, obj_on)
+
+
+def aux_loss(depth, acc, *, lidar_depth=None, mask=None, sky_mask=None, sky_scale=1.0, acc_obj=None,
+             obj_bound=None, lambda_depth_lidar=0.0, lambda_sky=0.0, lambda_reg=0.0):
+    """lambda_depth_lidar * lidar + lambda_sky * sky + lambda_reg * obj (train.py:121-127,145-158,164-176).
+    Returns (loss, terms); terms holds detached device scalars of the terms that are on."""
+    stats, _, on = _aux_run(depth, acc, lidar_depth, mask, sky_mask, sky_scale, acc_obj, obj_bound,
+                            lambda_depth_lidar, lambda_sky, lambda_reg)
+    terms = {name: stats[i].detach() for i, name, flag in
+             ((1, "lidar_depth_loss", on[0]), (2, "sky_loss", on[1]), (3, "obj_acc_loss", on[2])) if flag}
+    return stats[0], terms
+
+
+def lidar_depth_loss(depth, acc, lidar_depth, mask=None):
+    """train.py:164-176: mean of the smallest 95 % of |depth / (acc + 1e-10) - lidar_depth| over
+    (lidar_depth > 0) & mask, with the reference's zero-term guard."""
+    return _aux_run(depth, acc, lidar_depth, mask, None, 1.0, None, None, 1.0, 0.0, 0.0)[0][1]
+
+
+def sky_loss(acc, sky_mask, scale=1.0):
+    """train.py:121-127: mean(where(sky_mask, -log(1 - a), -log(a))) * scale, a = clamp(acc, 1e-6, 1 - 1e-6)."""
+    return _aux_run(None, acc, None, None, sky_mask, scale, None, None, 0.0, 1.0, 0.0)[0][2]
+
+
+def obj_acc_loss(acc_obj, obj_bound):
+    """train.py:145-158: mean(where(obj_bound, -(a log a + (1 - a) log(1 - a)), -log(1 - a))),
+    a = clamp(acc_obj, 1e-6, 1 - 1e-6)."""
+    return _aux_run(None, None, None, None, None, 1.0, acc_obj, obj_bound, 0.0, 0.0, 1.0)[0][3]
+
+
+def lidar_selection(depth, acc, lidar_depth, mask=None):
+    """The lidar term's selection as the device computed it, without a gradient: a dict of device tensors,
+    'N', 'k', 'c_lt', 'c_eq' (exact int64) and 't' (float32, the k-th smallest error; 0 when k == 0)."""
+    with torch.no_grad():
+        _, ws, _ = _aux_run(depth, acc, lidar_depth, mask, None, 1.0, None, None, 1.0, 0.0, 0.0)
+    counts = ws[:32].view(torch.int64)
+    return {"N": counts[0], "k": counts[1], "c_lt": counts[2], "c_eq": counts[3], "t": ws[32:36].view(torch.float32)[0]}

@@ -656,6 +656,50 @@ GRPG_API int grpg_ssim_backward(int B, int C, int height, int width, const float
                                 float w_ssim, const float* stats, const float* saved, const float* grad_stats,
                                 float* grad_img1, void* hip_stream);
 
+/*
+ * Fused lidar-depth, sky and object-alpha training losses (no counterpart in the extension; replace the PyTorch
+ * code of train.py:121-127 (sky), 145-158 (obj_acc_loss) and 164-176 (lidar depth)).  Planes: device fp32 H*W,
+ * contiguous (depth, acc, lidar_depth, acc_obj); masks: device uint8 H*W, nonzero = true (mask, sky_mask,
+ * obj_bound).  A term is evaluated only when its lambda > 0 and its gating plane is non-NULL (lidar: lidar_depth,
+ * sky: sky_mask, obj: obj_bound); it then needs its render planes (lidar: depth and acc; sky: acc; obj: acc_obj).
+ * A term that is off is 0, not part of the total, and gets no gradient.
+ *   lidar = mean of the k = floor(0.95 N) smallest e = |depth / (acc + 1e-10) - lidar_depth| (float32, the
+ *           reference's operand order) over sel = (lidar_depth > 0) & mask, N = |sel| (mask NULL: all true).
+ *           Zero-term rule (the reference's torch.nonzero(depth_mask).any() guard): N == 0, or N == 1 with the
+ *           selected pixel at flat index 0, give 0 and a zero gradient; N == 1 elsewhere gives NaN (k == 0) and
+ *           a zero gradient.  Ties at the k-th value t: c_lt errors lie below t, c_eq equal it; each tied element
+ *           gets weight (k - c_lt) / c_eq (the value is that of any choice among ties).
+ *   sky   = sky_scale * mean over H*W of where(sky_mask, -log(1 - a), -log(a)), a = clamp(acc, 1e-6, 1 - 1e-6).
+ *   obj   = mean over H*W of where(obj_bound, -(a log a + (1 - a) log(1 - a)), -log(1 - a)),
+ *           a = clamp(acc_obj, 1e-6, 1 - 1e-6).
+ *   total = lambda_depth_lidar * lidar + lambda_sky * sky + lambda_reg * obj.
+ * grpg_aux_loss_forward writes stats[9] (device fp32): [0] total, [1] lidar, [2] sky, [3] obj, [4] N, [5] k,
+ * [6] t (0 when k == 0), [7] c_lt, [8] c_eq (the counts are exact in fp32 below 2^24).  workspace: device memory
+ * of grpg_aux_loss_workspace_bytes(H, W) bytes, 16-byte aligned; it must be kept unchanged from a forward to its
+ * backward.  Its first 32 bytes hold N, k, c_lt, c_eq as exact uint64 and the next 4 bytes the bits of t.
+ * grpg_aux_loss_backward: the same planes, sky_scale and lambdas as the forward; grad_stats (device fp32 [9], entries
+ * 0..3 used) is the upstream gradient of the stats vector, read on the device together with k, t, c_lt, c_eq and
+ * the zero-term flag (no host synchronisation); writes every element of each non-NULL gradient plane grad_depth,
+ * grad_acc (lidar and sky contributions summed) and grad_acc_obj (device fp32 H*W).
+ * Both run asynchronously on hip_stream; identical calls give identical bits.  Purely additive exports:
+ * GRPG_ABI_VERSION stays 7.  Returns GRPG_OK, GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT for
+ * bad sizes / pointers.
+ */
+GRPG_API size_t grpg_aux_loss_workspace_bytes(int height, int width);
+GRPG_API int grpg_aux_loss_forward(int height, int width, const float* depth, const float* acc,
+                                   const float* lidar_depth, const unsigned char* mask,
+                                   const unsigned char* sky_mask, const float* acc_obj,
+                                   const unsigned char* obj_bound, float sky_scale, float lambda_depth_lidar,
+                                   float lambda_sky, float lambda_reg, float* stats, void* workspace,
+                                   void* hip_stream);
+GRPG_API int grpg_aux_loss_backward(int height, int width, const float* depth, const float* acc,
+                                    const float* lidar_depth, const unsigned char* mask,
+                                    const unsigned char* sky_mask, const float* acc_obj,
+                                    const unsigned char* obj_bound, float sky_scale, float lambda_depth_lidar,
+                                    float lambda_sky, float lambda_reg, const float* grad_stats,
+                                    const void* workspace, float* grad_depth, float* grad_acc,
+                                    float* grad_acc_obj, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
