@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <sys/syscall.h>
 #include <unistd.h>
 
@@ -1789,6 +1790,147 @@ int grpg_aux_loss_backward(int height, int width, const float* depth, const floa
   launch_aux_loss_backward((hipStream_t)hip_stream, height, width, planes, sky_scale, lambda_depth_lidar,
                            lambda_sky, lambda_reg, grad_stats, (const char*)workspace, grad_depth, grad_acc,
                            grad_acc_obj);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+// ---- fused multi-tensor Adam step and densification statistics (optim.hip) ----
+namespace {
+// Both entries return without a host wait, so the pinned table an asynchronous copy reads must outlive the call: a
+// ring of growable slots, each guarded by an event recorded behind its copy.  A slot comes round again 32 calls
+// later (16 iterations of a trainer that makes both calls); the host waits for the device only when it has run
+// that far ahead of it.
+struct OptimStagingSlot {
+  char* host = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;
+  bool used = false;
+};
+constexpr int OPTIM_STAGING_SLOTS = 32;
+static_assert(sizeof(DensifyRangeDev) == 32, "the header documents 32 bytes per range");
+thread_local OptimStagingSlot g_optim_staging[OPTIM_STAGING_SLOTS];
+thread_local int g_optim_staging_next = 0;
+OptimStagingSlot* optim_staging_acquire(size_t bytes) {
+  OptimStagingSlot& b = g_optim_staging[g_optim_staging_next];
+  g_optim_staging_next = (g_optim_staging_next + 1) % OPTIM_STAGING_SLOTS;
+  if (!b.ev && hipEventCreateWithFlags(&b.ev, hipEventDisableTiming) != hipSuccess) return nullptr;
+  if (b.used) (void)hipEventSynchronize(b.ev);
+  if (b.bytes < bytes) {
+    if (b.host) (void)hipHostFree(b.host);
+    b.host = nullptr;
+    b.bytes = 0;
+    size_t cap = 4096;
+    while (cap < bytes) cap *= 2;
+    if (hipHostMalloc((void**)&b.host, cap, hipHostMallocDefault) != hipSuccess) return nullptr;
+    b.bytes = cap;
+  }
+  b.used = true;
+  return &b;
+}
+}  // namespace
+
+size_t grpg_adam_workspace_bytes(int num_segments) {
+  if (num_segments <= 0) return 0;
+  return sizeof(AdamSegmentDev) * (size_t)num_segments;
+}
+
+int grpg_adam_step(const grpg_adam_segment* segments, int num_segments, grpg_alloc_fn table_alloc,
+                   void* table_user, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (num_segments < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: negative segment count");
+  if (num_segments == 0) return GRPG_OK;
+  if (!segments) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: NULL segment table");
+  if (!table_alloc) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: NULL table allocator");
+  int live = 0;
+  unsigned long long chunks = 0;
+  for (int i = 0; i < num_segments; i++) {
+    const grpg_adam_segment& g = segments[i];
+    if (g.n < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: segment with negative n");
+    if (g.n == 0) continue;
+    if (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: segment with a NULL array and n > 0");
+    if (((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 3)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: arrays must be 4-byte aligned");
+    if (!std::isfinite(g.bc2_sqrt) || !(g.bc2_sqrt > 0.f))
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: bc2_sqrt must be finite and positive");
+    if (!std::isfinite(g.step_size) || !std::isfinite(g.beta2) || !std::isfinite(g.one_minus_beta1) ||
+        !std::isfinite(g.one_minus_beta2) || !std::isfinite(g.eps))
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: non-finite coefficient");
+    live++;
+    chunks += ((unsigned long long)g.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+  }
+  if (live == 0) return GRPG_OK;              // nothing but empty tensors: no launch
+  if (chunks > 0xFFFFFFFFull) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: more than 2^32 chunks of 4096 elements");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const size_t bytes = sizeof(AdamSegmentDev) * (size_t)live;
+  OptimStagingSlot* stg = optim_staging_acquire(bytes);
+  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
+  AdamSegmentDev* host = (AdamSegmentDev*)stg->host;
+  uint32_t first = 0;
+  int k = 0;
+  for (int i = 0; i < num_segments; i++) {
+    const grpg_adam_segment& g = segments[i];
+    if (g.n == 0) continue;
+    AdamSegmentDev& d = host[k++];
+    d.param = g.param; d.grad = g.grad; d.exp_avg = g.exp_avg; d.exp_avg_sq = g.exp_avg_sq;
+    d.n = (unsigned long long)g.n;
+    d.step_size = g.step_size; d.bc2_sqrt = g.bc2_sqrt; d.beta2 = g.beta2;
+    d.one_minus_beta1 = g.one_minus_beta1; d.one_minus_beta2 = g.one_minus_beta2; d.eps = g.eps;
+    d.first_chunk = first;
+    d.vec = (((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15) == 0;
+    first += (uint32_t)((d.n + ADAM_CHUNK - 1) / ADAM_CHUNK);
+  }
+  char* dev = table_alloc(grpg_adam_workspace_bytes(num_segments), table_user);
+  if (!dev) return fail(GRPG_ERR_ALLOC, "adam_step: the table allocator returned NULL");
+  if ((uintptr_t)dev & 7) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: the table must be 8-byte aligned");
+  HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(stg->ev, stream));
+  launch_adam_step(stream, (const AdamSegmentDev*)dev, live, first);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_densify_stats(int P, const float* grad_xyz, const int* radii, const grpg_range* ranges, int num_ranges,
+                       float* const* accum, float* const* denom, float* const* max_radii,
+                       grpg_alloc_fn table_alloc, void* table_user, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (P < 0 || num_ranges < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: negative count");
+  if (P == 0 || num_ranges == 0) return GRPG_OK;
+  if (!grad_xyz || !radii) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: NULL grad_xyz / radii");
+  if (!ranges || !accum || !denom || !max_radii)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: NULL range table");
+  if (!table_alloc) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: NULL table allocator");
+  int live = 0, prev_end = 0;
+  for (int i = 0; i < num_ranges; i++) {
+    const grpg_range& r = ranges[i];
+    if (r.start < prev_end || r.end < r.start || r.end > P)
+      return fail(GRPG_ERR_INVALID_ARGUMENT,
+                  "densify_stats: ranges must be half-open [start, end), ascending, disjoint and within [0, P)");
+    prev_end = r.end;
+    if (r.end == r.start) continue;
+    if (!accum[i] || !denom[i] || !max_radii[i])
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: non-empty range with a NULL array");
+    live++;
+  }
+  if (live == 0) return GRPG_OK;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const size_t bytes = sizeof(DensifyRangeDev) * (size_t)live;
+  OptimStagingSlot* stg = optim_staging_acquire(bytes);
+  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
+  DensifyRangeDev* host = (DensifyRangeDev*)stg->host;
+  int k = 0;
+  for (int i = 0; i < num_ranges; i++) {
+    if (ranges[i].end == ranges[i].start) continue;
+    host[k++] = DensifyRangeDev{accum[i], denom[i], max_radii[i], ranges[i].start, ranges[i].end};
+  }
+  char* dev = table_alloc(sizeof(DensifyRangeDev) * (size_t)num_ranges, table_user);
+  if (!dev) return fail(GRPG_ERR_ALLOC, "densify_stats: the table allocator returned NULL");
+  if ((uintptr_t)dev & 7) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: the table must be 8-byte aligned");
+  HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(stg->ev, stream));
+  launch_densify_stats(stream, P, grad_xyz, radii, (const DensifyRangeDev*)dev, live);
   HIP_TRY(hipGetLastError());
   return GRPG_OK;
 }

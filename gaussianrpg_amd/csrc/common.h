@@ -656,4 +656,26 @@ void launch_aux_loss_backward(hipStream_t st, int H, int W, const AuxPlanes& pla
                               float lam_lidar, float lam_sky, float lam_reg, const float* grad_stats,
                               const char* workspace, float* grad_depth, float* grad_acc, float* grad_acc_obj);
 
+// fused multi-tensor Adam step and densification statistics (optim.hip).  The device tables api.hip uploads.
+constexpr uint32_t ADAM_CHUNK = 4096;      // elements per unit of work; a chunk never straddles two segments
+struct AdamSegmentDev {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  unsigned long long n;                    // elements (> 0)
+  float step_size, bc2_sqrt, beta2, one_minus_beta1, one_minus_beta2, eps;
+  uint32_t first_chunk;                    // chunks of the segments before this one
+  uint32_t vec;                            // all four arrays 16-byte aligned: 16-byte loads and stores
+};
+struct DensifyRangeDev {
+  float* accum;                            // [n, 2]
+  float* denom;                            // [n]
+  float* max_radii;                        // [n]
+  int start, end;                          // half-open range of the composed frame, n = end - start > 0
+};
+void launch_adam_step(hipStream_t st, const AdamSegmentDev* table, int num_segments, uint32_t total_chunks);
+void launch_densify_stats(hipStream_t st, int P, const float* grad_xyz, const int* radii,
+                          const DensifyRangeDev* ranges, int num_ranges);
+
 }  // namespace grpg

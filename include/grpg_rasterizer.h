@@ -700,6 +700,70 @@ GRPG_API int grpg_aux_loss_backward(int height, int width, const float* depth, c
                                     const void* workspace, float* grad_depth, float* grad_acc,
                                     float* grad_acc_obj, void* hip_stream);
 
+/*
+ * The tail of the training iteration (no counterpart in the extension; replace the PyTorch code of
+ * gaussian_model.py:316-317 optimizer.step() and street_gaussian_model.py:555-578 set_max_radii2D /
+ * add_densification_stats).
+ *
+ * grpg_adam_step: the step of torch.optim.Adam (amsgrad = False, weight_decay = 0, maximize = False) over every
+ * listed tensor in ONE launch, one pass over the data.  Per element, float32, one rounding per operation:
+ *   m = m + (g - m) * one_minus_beta1
+ *   v = v * beta2 + (g * g) * one_minus_beta2
+ *   p = p - step_size * (m / (sqrt(v) / bc2_sqrt + eps))
+ * A segment is one parameter tensor: param / grad / exp_avg / exp_avg_sq are device fp32 arrays of n elements,
+ * 4-byte aligned (16-byte aligned arrays are read and written 16 bytes at a time), no two segments overlapping.
+ * The coefficients travel per segment, so tensors of optimizers with different steps, learning rates or betas
+ * share the launch; the caller computes them in double from the tensor's own step count t (after its increment)
+ * and rounds once: step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), one_minus_beta1 = 1 - beta1,
+ * one_minus_beta2 = 1 - beta2 (1 - (float)beta would be off by up to 2^-24 / (1 - beta) relative).  A parameter
+ * without a gradient is simply not listed.  Segments with n == 0 are accepted and cost nothing.
+ * table_alloc is asked once for grpg_adam_workspace_bytes(num_segments) bytes of device memory (8-byte aligned)
+ * for the segment table, which is uploaded asynchronously on hip_stream from pinned staging; the memory must
+ * stay valid until the work queued on hip_stream has run (a stream-ordered allocator's block is fine).
+ * No host synchronisation (the pinned staging is a ring of 32 tables per thread, shared with grpg_densify_stats: the
+ * host waits only when it is 32 such calls ahead of the device); identical calls give identical bits.
+ * Returns GRPG_OK, GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT for a negative count or n, a
+ * NULL array with n > 0, a misaligned array, a non-finite coefficient or a non-positive bc2_sqrt (checked
+ * before anything is queued), GRPG_ERR_ALLOC when table_alloc returns NULL.
+ */
+typedef struct grpg_adam_segment {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  long long n;
+  float step_size;
+  float bc2_sqrt;
+  float beta2;
+  float one_minus_beta1;
+  float one_minus_beta2;
+  float eps;
+} grpg_adam_segment;
+GRPG_API size_t grpg_adam_workspace_bytes(int num_segments);   /* pure size query: needs no device */
+GRPG_API int grpg_adam_step(const grpg_adam_segment* segments, int num_segments, grpg_alloc_fn table_alloc,
+                            void* table_user, void* hip_stream);
+
+/*
+ * grpg_densify_stats: for every Gaussian i of a composed frame of P Gaussians with radii[i] > 0 (the visibility
+ * filter) that lies in range r = [start, end) -- HALF-OPEN, where the reference's graph_gaussian_range stores the
+ * inclusive [start, end - 1] -- with j = i - start and g = grad_xyz[i] (device fp32 [P,3], viewspace_points.grad):
+ *   accum[r][j,0] += sqrt(g.x^2 + g.y^2);  accum[r][j,1] += |g.z|;  denom[r][j] += 1;
+ *   max_radii[r][j] = max(max_radii[r][j], (float)radii[i])
+ * radii: device int32 [P].  ranges: HOST array, ascending and disjoint, within [0, P]; empty ranges are
+ * accepted.  accum / denom / max_radii: HOST arrays of num_ranges device pointers (fp32 [n,2] / [n] / [n],
+ * n = end - start).  Rows of invisible Gaussians are not touched.  One launch, no atomics, no host
+ * synchronisation.  table_alloc is asked once for num_ranges * 32 bytes of device memory (8-byte aligned), with
+ * the lifetime rule of grpg_adam_step.  Errors as grpg_adam_step.
+ */
+typedef struct grpg_range {
+  int start;
+  int end;
+} grpg_range;
+GRPG_API int grpg_densify_stats(int P, const float* grad_xyz, const int* radii, const grpg_range* ranges,
+                                int num_ranges, float* const* accum, float* const* denom,
+                                float* const* max_radii, grpg_alloc_fn table_alloc, void* table_user,
+                                void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
