@@ -166,21 +166,23 @@ uint32_t capacity_from_hint(const CapKey& k, uint32_t* coarse_cap, bool* far) {
   *coarse_cap = 0u;
   return 0u;
 }
+// the hint of this key, or a fresh one in a free / the least recently used slot (g_hint_mu held)
+CapHint* hint_slot(const CapKey& k) {
+  for (auto& h : g_hints)
+    if (h.valid && same_key(h.key, k)) return &h;
+  CapHint* slot = &g_hints[0];
+  for (auto& h : g_hints) {
+    if (!h.valid) { slot = &h; break; }
+    if (h.stamp < slot->stamp) slot = &h;
+  }
+  *slot = CapHint{};
+  slot->key = k;
+  slot->valid = true;
+  return slot;
+}
 void update_hint(const CapKey& k, uint32_t R, uint32_t Rc, bool far) {
   std::lock_guard<std::mutex> lk(g_hint_mu);
-  CapHint* slot = nullptr;
-  for (auto& h : g_hints)
-    if (h.valid && same_key(h.key, k)) { slot = &h; break; }
-  if (!slot) {
-    slot = &g_hints[0];
-    for (auto& h : g_hints) {
-      if (!h.valid) { slot = &h; break; }
-      if (h.stamp < slot->stamp) slot = &h;
-    }
-    *slot = CapHint{};
-    slot->key = k;
-    slot->valid = true;
-  }
+  CapHint* slot = hint_slot(k);
   const uint32_t decayed = slot->high - slot->high / 64;   // lets the mark follow a shrinking scene
   slot->high = R > decayed ? R : decayed;
   // decays on sort-binning frames too (Rc == 0 there), so it never outlives `high`
@@ -495,19 +497,7 @@ int grpg_set_capacity_hint(int P, int width, int height, unsigned instances, uns
   HIP_TRY(hipGetDevice(&dev));
   const CapKey k = {dev, P, width, height};
   std::lock_guard<std::mutex> lk(g_hint_mu);
-  CapHint* slot = nullptr;
-  for (auto& h : g_hints)
-    if (h.valid && same_key(h.key, k)) { slot = &h; break; }
-  if (!slot) {
-    slot = &g_hints[0];
-    for (auto& h : g_hints) {
-      if (!h.valid) { slot = &h; break; }
-      if (h.stamp < slot->stamp) slot = &h;
-    }
-    *slot = CapHint{};
-    slot->key = k;
-    slot->valid = true;
-  }
+  CapHint* slot = hint_slot(k);
   slot->once = instances ? instances : 1u;
   slot->once_c = coarse_pairs ? coarse_pairs : 1u;
   slot->stamp = ++g_hint_clock;
@@ -548,6 +538,18 @@ BwdStagingSlot* bwd_staging_acquire() {
   return &b;
 }
 
+// one row of the device segment table; pad1: the model's class bit in a layered composed forward, else NULL
+void fill_segment(SegmentDev& d, const grpg_model_segment& g, uint32_t start, const void* pad1) {
+  d.xyz = g.xyz; d.scaling = g.scaling; d.rotation = g.rotation; d.opacity = g.opacity;
+  d.fdc = g.features_dc; d.frest = g.features_rest; d.flip = g.flip; d.pad1 = pad1;
+  d.start = start; d.count = (uint32_t)g.count;
+  d.fourier_dim = g.fourier_dim; d.rigid = g.rigid;
+  for (int k = 0; k < 4; k++) d.rot[k] = g.obj_rot[k];
+  for (int k = 0; k < 3; k++) d.trans[k] = g.obj_trans[k];
+  d.pad0 = 0.f;
+  for (int k = 0; k < MAX_FOURIER; k++) d.idft[k] = g.idft[k];
+}
+
 // grpg_forward_layers: the class of every Gaussian and the two extra plane pairs
 struct LayerArgs {
   const unsigned char* segment_class;   // composed frames: [num_segments] HOST bytes (NULL: the segment's rigid flag)
@@ -556,87 +558,165 @@ struct LayerArgs {
   float* out_color_bg; float* out_alpha_bg; float* out_color_obj; float* out_alpha_obj;
 };
 
-// Shared body of grpg_forward (segs == NULL: flat input tensors) and grpg_forward_composed (segs:
-// per-model raw parameters, P = sum of their counts, the flat pointers are NULL).
-int forward_impl(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_fn binning_alloc,
-                 void* binning_user, grpg_alloc_fn image_alloc, void* image_user, int P, int D,
-                 int M, int S, const float* background, int width, int height,
-                 const float* means3D, const float* shs, const float* colors_precomp,
-                 const float* semantics, const float* opacities, const float* scales,
-                 float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                 const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                 float tan_fovx, float tan_fovy, float* out_color,
-                 float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug,
-                 void* hip_stream, const grpg_model_segment* segs, int nseg, unsigned flags = 0u,
-                 DeferSlot* defer = nullptr, bool force_pass3 = false, const LayerArgs* layers = nullptr,
-                 const FrameEpilogue* epi = nullptr) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (P < 0 || width <= 0 || height <= 0 || S < 0 || M < 0)
+// One forward frame as an entry point hands it to forward_impl.  Every extern "C" forward fills the fields it has;
+// the rest stay zero / NULL.  segs == NULL: flat input tensors (grpg_forward); segs: per-model raw parameters
+// (grpg_forward_composed), P = sum of their counts, the flat pointers stay NULL.
+struct FrameRequest {
+  grpg_alloc_fn geometry_alloc = nullptr, binning_alloc = nullptr, image_alloc = nullptr;
+  void *geometry_user = nullptr, *binning_user = nullptr, *image_user = nullptr;
+  int P = 0, D = 0, M = 0, S = 0, width = 0, height = 0;
+  float scale_modifier = 0.f, tan_fovx = 0.f, tan_fovy = 0.f;
+  int debug = 0;
+  hipStream_t stream = nullptr;
+  unsigned flags = 0u;
+  const float *means3D = nullptr, *shs = nullptr, *colors_precomp = nullptr, *semantics = nullptr,
+              *opacities = nullptr, *scales = nullptr, *rotations = nullptr, *cov3D_precomp = nullptr;
+  const float *background = nullptr, *viewmatrix = nullptr, *projmatrix = nullptr, *cam_pos = nullptr;
+  float *out_color = nullptr, *out_depth = nullptr, *out_alpha = nullptr, *out_semantic = nullptr;
+  int* radii = nullptr;
+  const grpg_model_segment* segs = nullptr;
+  int nseg = 0;
+  DeferSlot* defer = nullptr;           // grpg_forward_deferred: the slot the frame's count is published to
+  const LayerArgs* layers = nullptr;    // a layered frame
+  const FrameEpilogue* epi = nullptr;   // grpg_forward_frame: sky composite / clamp / bytes behind the blend
+  // an evaluation frame (GRPG_FORWARD_NO_BACKWARD: no backward can follow) is not a training frame
+  bool training() const { return (flags & GRPG_FORWARD_NO_BACKWARD) == 0u; }
+};
+
+// the argument checks of every forward, behind ensure_device
+int validate(const FrameRequest& q) {
+  if (q.P < 0 || q.width <= 0 || q.height <= 0 || q.S < 0 || q.M < 0)
     return fail(GRPG_ERR_INVALID_ARGUMENT, "negative size");
-  if (!geometry_alloc || !binning_alloc || !image_alloc)
+  if (!q.geometry_alloc || !q.binning_alloc || !q.image_alloc)
     return fail(GRPG_ERR_INVALID_ARGUMENT, "buffer allocators must not be NULL");
-  if (!background || !viewmatrix || !projmatrix || !cam_pos)
+  if (!q.background || !q.viewmatrix || !q.projmatrix || !q.cam_pos)
     return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL camera/background/output pointer");
   // the float planes may be left out only when a frame epilogue delivers the bytes instead (grpg_forward_frame)
-  if ((!out_color || !out_depth || !out_alpha) && !(epi && !epi->planes && epi->rgb8))
+  if ((!q.out_color || !q.out_depth || !q.out_alpha) && !(q.epi && !q.epi->planes && q.epi->rgb8))
     return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL camera/background/output pointer");
-  if (epi && ((flags & GRPG_FORWARD_NO_BACKWARD) == 0u || S != 0))
+  if (q.epi && (q.training() || q.S != 0))
     return fail(GRPG_ERR_INVALID_ARGUMENT, "a frame epilogue needs an evaluation frame without semantic planes");
-  if ((unsigned)P > ID_MASK) return fail(GRPG_ERR_INVALID_ARGUMENT, "P must be < 2^28");
-  if (P > 0 && segs == nullptr) {
-    if (!means3D || !opacities) return fail(GRPG_ERR_INVALID_ARGUMENT, "means3D/opacities NULL");
-    if (!cov3D_precomp && (!scales || !rotations))
+  if ((unsigned)q.P > ID_MASK) return fail(GRPG_ERR_INVALID_ARGUMENT, "P must be < 2^28");
+  if (q.P > 0 && q.segs == nullptr) {
+    if (!q.means3D || !q.opacities) return fail(GRPG_ERR_INVALID_ARGUMENT, "means3D/opacities NULL");
+    if (!q.cov3D_precomp && (!q.scales || !q.rotations))
       return fail(GRPG_ERR_INVALID_ARGUMENT, "need scales+rotations or cov3D_precomp");
-    if (!colors_precomp && (!shs || M <= 0))
+    if (!q.colors_precomp && (!q.shs || q.M <= 0))
       return fail(GRPG_ERR_INVALID_ARGUMENT, "need shs (M>0) or colors_precomp");
-    if (!colors_precomp && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
+    if (!q.colors_precomp && (q.D < 0 || q.D > 3 || (q.D + 1) * (q.D + 1) > q.M))
       return fail(GRPG_ERR_INVALID_ARGUMENT, "SH degree needs (D+1)^2 <= M, D <= 3");
-    if (S > 0 && (!semantics || !out_semantic))
+    if (q.S > 0 && (!q.semantics || !q.out_semantic))
       return fail(GRPG_ERR_INVALID_ARGUMENT, "semantics/out_semantic NULL with S>0");
   }
-  hipStream_t stream = (hipStream_t)hip_stream;
-  const CameraArgs cam = make_camera(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
-  const uint32_t T = (uint32_t)cam.gx * (uint32_t)cam.gy;
-  const size_t N = (size_t)width * height;
+  return GRPG_OK;
+}
 
-  // an evaluation frame (no backward can follow) carves the blob without the gradient records
-  const GeomLayout GL = geom_layout((size_t)P, (flags & GRPG_FORWARD_NO_BACKWARD) == 0u);
-  const ImgLayout IL = img_layout(T, N);
-  char* geom = geometry_alloc(GL.total, geometry_user);
-  char* img = image_alloc(IL.total, image_user);
-  if (!geom || !img) return fail(GRPG_ERR_ALLOC, "geometry/image buffer allocation failed");
-  remember_geom(geom, P, (flags & GRPG_FORWARD_NO_BACKWARD) == 0u);
+uint32_t num_tiles(const CameraArgs& c) { return (uint32_t)c.gx * (uint32_t)c.gy; }
 
-  float4* rec_w = (float4*)(geom + GL.rec);
+// What the stages of one forward frame share: the request, the carved geometry / image blobs, the frame's mode
+// switches, and the stages themselves in the order forward_impl runs them.  Built once the two blobs are allocated.
+struct Frame {
+  const FrameRequest& q;
+  const CameraArgs cam;
+  const GeomLayout GL;
+  const ImgLayout IL;
+  char* const geom;
+  char* const img;
+  Frame(const FrameRequest& q_, const CameraArgs& cam_, const GeomLayout& GL_, const ImgLayout& IL_, char* geom_,
+        char* img_) : q(q_), cam(cam_), GL(GL_), IL(IL_), geom(geom_), img(img_) { setup_drain(); }
+  Frame(const Frame&) = delete;   // (epi may point at epi_drained)
+
+  const int debug = q.debug;            // (STAGE_CHECK)
+  const hipStream_t stream = q.stream;
+  const bool training = q.training();
+  const uint32_t T = num_tiles(cam);
+  const size_t N = (size_t)q.width * q.height;
+
+  float4* const rec_w = (float4*)(geom + GL.rec);
   const RecView rec = {rec_w};
-  uint32_t* key_a = (uint32_t*)(geom + GL.key_a);
-  uint32_t* key_b = (uint32_t*)(geom + GL.key_b);
-  uint32_t* val_a = (uint32_t*)(geom + GL.val_a);
-  uint32_t* val_b = (uint32_t*)(geom + GL.val_b);
-  uint32_t* tiles = (uint32_t*)(geom + GL.tiles);
-  uint32_t* offsets = (uint32_t*)(geom + GL.offsets);
-  int* radii_int = radii ? radii : (int*)(geom + GL.radii);
-  uint32_t* table = (uint32_t*)(geom + GL.table);
-  uint32_t* totals = (uint32_t*)(geom + GL.totals);
-  uint32_t* block_sums = (uint32_t*)(geom + GL.block_sums);
-  uint32_t* ds_table = (uint32_t*)(geom + GL.ds_table);
-  BlobHeader* gh = (BlobHeader*)geom;
-  uint2* ranges = (uint2*)(img + IL.ranges);
-  uint32_t* n_contrib = (uint32_t*)(img + IL.n_contrib);
-  uint32_t* work = (uint32_t*)(img + IL.work);
+  uint32_t* const key_a = (uint32_t*)(geom + GL.key_a);
+  uint32_t* const key_b = (uint32_t*)(geom + GL.key_b);
+  uint32_t* const val_a = (uint32_t*)(geom + GL.val_a);
+  uint32_t* const val_b = (uint32_t*)(geom + GL.val_b);
+  uint32_t* const tiles = (uint32_t*)(geom + GL.tiles);
+  uint32_t* const offsets = (uint32_t*)(geom + GL.offsets);
+  int* const radii_int = q.radii ? q.radii : (int*)(geom + GL.radii);
+  uint32_t* const table = (uint32_t*)(geom + GL.table);
+  uint32_t* const totals = (uint32_t*)(geom + GL.totals);
+  uint32_t* const block_sums = (uint32_t*)(geom + GL.block_sums);
+  uint32_t* const ds_table = (uint32_t*)(geom + GL.ds_table);
+  uint32_t* const tiles_sorted = (uint32_t*)(geom + GL.tiles_sorted);
+  uint32_t* const emit_win = (uint32_t*)(geom + GL.emit_win);
+  uint2* const rect_sorted = (uint2*)(geom + GL.rect_sorted);
+  uint4* const pre_counts = (uint4*)(geom + GL.pre_counts);
+  BlobHeader* const gh = (BlobHeader*)geom;
+  uint2* const ranges = (uint2*)(img + IL.ranges);
+  uint32_t* const n_contrib = (uint32_t*)(img + IL.n_contrib);
+  uint32_t* const work = (uint32_t*)(img + IL.work);
+
+  // Instance capacity of the binning blob.  Speculative mode (default): from the high-water mark
+  // of earlier frames of this (device, P, W, H), so the blob is carved and every kernel of the
+  // frame is enqueued BEFORE the host learns num_rendered; the kernels read the count from device
+  // memory.  Exact mode, or no history yet: wait for the count first, like the reference
+  // (rasterizer_impl.cu:284).
+  const bool spec_mode = g_binning_mode.load() == GRPG_BINNING_SPECULATIVE;
+  const bool fat_sort = depth_sort_is_fat(GL.nchunks_ds);
+  // hierarchical binning needs the compacted depth order of the fat sort (its coarse scan gathers
+  // the super-tile counts by sorted id); otherwise emit + partition
+  const uint32_t NS = super_tiles(cam.gx, cam.gy);
+  const bool hier = fat_sort && binning_is_hier() && NS <= 65536u;   // 16 id bits in a coarse key
+  // hierarchical binning on a grid of <= 255 x 255 tiles: the tile rectangles ride through the
+  // depth sort as a packed payload and arrive in depth order together with the super-tile counts
+  // (sort.hip RectPayload); larger grids: the coarse scan gathers them by sorted id instead
+  const bool rect_sorted_by_sort = hier && cam.gx <= 255 && cam.gy <= 255;
+  uint2* const rects = hier ? (uint2*)(geom + GL.rects) : nullptr;
+  // a training forward leaves blend checkpoints of its long tile lists behind the binning blob
+  // (common.h CK_*; the backward starts its segments from them)
+  const bool with_ckpt = training && q.S == 0;
+  // work-list classes of the frame's render.  A layered frame: the plain frame's classes, plus one flag per tile
+  // -- does its list hold an object entry (preprocess sets the flags; they live in the image blob's checkpoint-count
+  // area, which only a training forward uses) -- that sends short tiles WITH objects down the quarter-wave path
+  const LayerArgs* const layers = q.layers;
+  unsigned char* const tile_obj = layers ? (unsigned char*)(img + IL.ck_count) : nullptr;
+  const uint32_t tile_obj_words = layers ? (T + 3u) / 4u : 0u;
+  const TileClasses frame_classes = layers ? tile_classes_layers(tile_obj, cam.gx) : tile_classes(q.S);
+  const LayerMarks marks = {layers ? layers->layer_class : nullptr, tile_obj, cam.gx};
+
+  const FrameEpilogue* epi = q.epi;     // the request's, or epi_drained
+  FrameEpilogue epi_drained;
+  uint32_t drain_cnt_words = 0u;
+  StageTimer tm{stream, g_timing_enabled};
+
+  // ---- set by begin() (P > 0) ----
+  HostWord* hw = nullptr;
+  // where the speculative frame publishes its count: the thread's word, or the deferred frame's own
+  uint32_t* pub_ptr = nullptr;          // ... as the device addresses it
+  const uint32_t* pub_host = nullptr;   // ... as the host reads it, once pub_ev has fired
+  hipEvent_t pub_ev = nullptr;
+  CapKey ck{-1, 0, 0, 0};
+  bool speculative = false;             // the tail is enqueued for remembered capacities, before the count is known
+  // Fourth pass of the depth sort (sort.hip): needed when the visible depth keys span >= 2^27
+  // values -- a property of the scene's scale that does not change from frame to frame.  Its two
+  // launches are only enqueued when the previous frame of this shape needed them (or nothing is
+  // known yet); a frame that turns out to need them without having them is rendered again.
+  bool with_pass3 = true;
+  // The binning blob and the capacities it is carved for, written by carve_bin() only.  Rcap: instances (point
+  // list); Ccap: coarse (Gaussian, super-tile) pairs, <= Rcap.  All zero: not carved yet (no history / exact mode).
+  char* bin = nullptr;
+  BinLayout BL{};
+  uint32_t Rcap = 0u, Ccap = 0u;
+  const uint32_t* sorted_gid = nullptr; // ids in depth order, once the depth sort is enqueued
 
   // A frame whose bytes go to pinned host memory is DRAINED (render_fwd.hip FrameEpi) when its width allows whole
   // 16-byte pieces per tile row (W % 16 == 0; whole 64-byte lines per unit when W % 64 == 0): staging bytes in the n_contrib plane (an evaluation frame tracks no n_contrib: 4 bytes
   // per pixel lie idle), the units' arrival counters behind the layered frame's tile flags in the checkpoint-count
   // area (a training forward's; T / 4 of its 4 T words).  GRPG_DRAIN_WGS (experiments): workgroups that carry the
   // units, 0 = the blending waves store straight into host memory.
-  FrameEpilogue epi_drained;
-  uint32_t drain_cnt_words = 0u;
-  if (epi && epi->rgb8 && epi->rgb8_host && (width & 15) == 0 && P > 0) {
+  void setup_drain() {
+    if (!(epi && epi->rgb8 && epi->rgb8_host && (q.width & 15) == 0 && q.P > 0)) return;
     static const int drain_cfg = [] { const char* v = getenv("GRPG_DRAIN_WGS"); return v ? atoi(v) : FRAME_DRAIN_WGS; }();
     // every unit needs a slot (64 per drain wave, RW_WAVES waves per workgroup), the counters 3 T words at most
-    const uint32_t NU = (uint32_t)((width + 63) / 64) * (uint32_t)cam.gy;
+    const uint32_t NU = (uint32_t)((q.width + 63) / 64) * (uint32_t)cam.gy;
     uint32_t wgs = (uint32_t)drain_cfg > (NU + 255u) / 256u ? (uint32_t)drain_cfg : (NU + 255u) / 256u;
     if (wgs > 3u * T / 256u) wgs = 3u * T / 256u;
     if (drain_cfg > 0 && wgs > 0u && wgs * 256u >= NU) {
@@ -649,100 +729,94 @@ int forward_impl(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_f
     }
   }
 
-  StageTimer tm(stream, g_timing_enabled);
-  uint32_t R = 0;
+  // P == 0: the reference launches nothing and its pre-zeroed planes stay zero
+  // (rasterize_points.cu:85-86,123); write the zeros explicitly.
+  int empty_frame() {
+    if (q.out_color) HIP_TRY(hipMemsetAsync(q.out_color, 0, 3 * N * 4, stream));
+    if (q.out_depth) HIP_TRY(hipMemsetAsync(q.out_depth, 0, N * 4, stream));
+    if (q.out_alpha) HIP_TRY(hipMemsetAsync(q.out_alpha, 0, N * 4, stream));
+    if (epi) launch_frame_epilogue_empty(stream, q.width, q.height, *epi, q.out_color);   // sky over nothing, bytes
+    if (q.S > 0 && q.out_semantic) HIP_TRY(hipMemsetAsync(q.out_semantic, 0, (size_t)q.S * N * 4, stream));
+    HIP_TRY(hipMemsetAsync(n_contrib, 0, N * 4, stream));
+    if (layers) {
+      // ONE contract for an empty layer (ADVICE r5): its colour plane is layer_background, its alpha plane zero --
+      // what the kernels write for an empty class when P > 0, and what the reference's render_kernel returns for a
+      // model set without Gaussians (street_gaussian_renderer.py:131-144: ones on a white background, acc zeros)
+      launch_fill_layer_planes(stream, N, layers->layer_background, layers->out_color_bg, layers->out_alpha_bg,
+                               layers->out_color_obj, layers->out_alpha_obj);
+    }
+    char* bin0 = q.binning_alloc(bin_layout(0).total, q.binning_user);
+    if (!bin0) return fail(GRPG_ERR_ALLOC, "binning buffer allocation failed");
+    launch_frame_init(stream, geom, bin0, img, 0u, 0u, 0u, (uint32_t)q.width, (uint32_t)q.height,
+                      (uint32_t)q.S, ranges, T, work, geom + GL.zero_begin, GL.zero_end - GL.zero_begin,
+                      training);
+    return GRPG_OK;
+  }
 
-  if (P > 0) {
+  // The one place the binning blob and its capacities change: carved for `cap` instances and `ccap` coarse pairs
+  // (+ the blend checkpoints of a training forward behind it).
+  int carve_bin(uint32_t cap, uint32_t ccap) {
+    Rcap = cap;
+    Ccap = ccap;
+    BL = hier ? bin_layout((size_t)Rcap, T, NS, Ccap) : bin_layout((size_t)Rcap);
+    bin = q.binning_alloc(BL.total + (with_ckpt ? ckpt_bytes(ckpt_slots(Rcap)) : 0), q.binning_user);
+    if (!bin) return fail(GRPG_ERR_ALLOC, "binning buffer allocation failed");
+    return GRPG_OK;
+  }
+
+  // P > 0: the thread's pinned words, where the count is published, and whether the frame can be enqueued whole
+  // for capacities remembered from earlier frames of its shape (then the blob is carved here)
+  int begin(bool force_pass3) {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    HostWord* hw = host_word();
+    hw = host_word();
     if (!hw) return fail(GRPG_ERR_HIP, "pinned host word / event allocation failed");
     if (int rc = check_async_error(hw)) return rc;
-    // where the speculative frame publishes its count: the thread's word, or the deferred frame's own
-    uint32_t* const pub_ptr = defer ? defer->dev_ptr : hw->dev_ptr;
-    hipEvent_t const pub_ev = defer ? defer->ev : hw->ev;
-    // Instance capacity of the binning blob.  Speculative mode (default): from the high-water mark
-    // of earlier frames of this (device, P, W, H), so the blob is carved and every kernel of the
-    // frame is enqueued BEFORE the host learns num_rendered; the kernels read the count from device
-    // memory.  Exact mode, or no history yet: wait for the count first, like the reference
-    // (rasterizer_impl.cu:284).
-    const bool fat_sort = depth_sort_is_fat(GL.nchunks_ds);
-    // hierarchical binning needs the compacted depth order of the fat sort (its coarse scan gathers
-    // the super-tile counts by sorted id); otherwise emit + partition
-    const uint32_t NS = super_tiles(cam.gx, cam.gy);
-    const bool hier = fat_sort && binning_is_hier() && NS <= 65536u;   // 16 id bits in a coarse key
-    // cap: instances (point list); ccap: coarse (Gaussian, super-tile) pairs, <= cap
-    auto layout_for = [&](uint32_t cap, uint32_t ccap) {
-      return hier ? bin_layout((size_t)cap, T, NS, ccap) : bin_layout((size_t)cap);
-    };
-    // a training forward leaves blend checkpoints of its long tile lists behind the binning blob
-    // (common.h CK_*; the backward starts its segments from them)
-    const bool with_ckpt = (flags & GRPG_FORWARD_NO_BACKWARD) == 0u && S == 0;
-    // work-list classes of the frame's render.  A layered frame: the plain frame's classes, plus one flag per tile
-    // -- does its list hold an object entry (preprocess sets the flags; they live in the image blob's checkpoint-count
-    // area, which only a training forward uses) -- that sends short tiles WITH objects down the quarter-wave path
-    unsigned char* const tile_obj = layers ? (unsigned char*)(img + IL.ck_count) : nullptr;
-    const uint32_t tile_obj_words = layers ? (T + 3u) / 4u : 0u;
-    const TileClasses frame_classes = layers ? tile_classes_layers(tile_obj, cam.gx) : tile_classes(S);
-    const LayerMarks marks = {layers ? layers->layer_class : nullptr, tile_obj, cam.gx};
-    auto blob_bytes = [&](const BinLayout& L, uint32_t cap) {
-      return L.total + (with_ckpt ? ckpt_bytes(ckpt_slots(cap)) : 0);
-    };
-    const CapKey ck = {dev, P, width, height};
-    uint32_t Ccap = 0u;
+    pub_ptr = q.defer ? q.defer->dev_ptr : hw->dev_ptr;
+    pub_host = q.defer ? q.defer->host_ptr : hw->host_ptr;
+    pub_ev = q.defer ? q.defer->ev : hw->ev;
+    ck = {dev, q.P, q.width, q.height};
+    uint32_t ccap = 0u;
     bool hint_far = true;
-    uint32_t Rcap = g_binning_mode.load() == GRPG_BINNING_SPECULATIVE ? capacity_from_hint(ck, &Ccap, &hint_far) : 0u;
-    const bool speculative = Rcap != 0u;
-    // Fourth pass of the depth sort (sort.hip): needed when the visible depth keys span >= 2^27
-    // values -- a property of the scene's scale that does not change from frame to frame.  Its two
-    // launches are only enqueued when the previous frame of this shape needed them (or nothing is
-    // known yet); a frame that turns out to need them without having them is rendered again.
-    const bool with_pass3 = force_pass3 || !speculative || hint_far;
-    char* bin = nullptr;
-    BinLayout BL{};
-    if (speculative) {
-      BL = layout_for(Rcap, Ccap);
-      bin = binning_alloc(blob_bytes(BL, Rcap), binning_user);
-      if (!bin) return fail(GRPG_ERR_ALLOC, "binning buffer allocation failed");
+    const uint32_t cap = spec_mode ? capacity_from_hint(ck, &ccap, &hint_far) : 0u;
+    speculative = cap != 0u;
+    with_pass3 = force_pass3 || !speculative || hint_far;
+    return speculative ? carve_bin(cap, ccap) : GRPG_OK;
+  }
+
+  // composed frame -- segment table: host structs -> pinned staging -> the geometry blob (asynchronous copy)
+  int stage_segments(SegmentDev* seg_dev) {
+    if (!g_seg_staging)
+      HIP_TRY(hipHostMalloc((void**)&g_seg_staging, sizeof(SegmentDev) * MAX_SEGMENTS, hipHostMallocDefault));
+    uint32_t start = 0;
+    for (int i = 0; i < q.nseg; i++) {
+      const grpg_model_segment& g = q.segs[i];
+      const bool obj = layers && (layers->segment_class ? layers->segment_class[i] != 0 : g.rigid != 0);
+      fill_segment(g_seg_staging[i], g, start, (const void*)(uintptr_t)(obj ? 1u : 0u));
+      start += (uint32_t)g.count;
     }
+    HIP_TRY(hipMemcpyAsync(seg_dev, g_seg_staging, sizeof(SegmentDev) * (size_t)q.nseg,
+                           hipMemcpyHostToDevice, stream));
+    return GRPG_OK;
+  }
+
+  // Everything that does not depend on the binning capacities: frame init, preprocess, the count's publish, the
+  // depth sort.  (A frame without a carved blob -- bin all zero -- initialises the other two blobs only.)
+  int enqueue_head() {
     tm.mark(0);
-    launch_frame_init(stream, geom, bin, img, (uint32_t)P, fat_sort ? 0u : (uint32_t)P, Rcap,
-                      (uint32_t)width, (uint32_t)height, (uint32_t)S, ranges, T, work,
-                      geom + GL.zero_begin, GL.zero_end - GL.zero_begin,
-                      (flags & GRPG_FORWARD_NO_BACKWARD) == 0u,
+    launch_frame_init(stream, geom, bin, img, (uint32_t)q.P, fat_sort ? 0u : (uint32_t)q.P, Rcap,
+                      (uint32_t)q.width, (uint32_t)q.height, (uint32_t)q.S, ranges, T, work,
+                      geom + GL.zero_begin, GL.zero_end - GL.zero_begin, training,
                       drain_cnt_words ? (uint32_t*)(img + IL.ck_count) : (uint32_t*)tile_obj,
                       drain_cnt_words ? T + drain_cnt_words : tile_obj_words);   // (drained: flags and counters in one sweep)
-    uint2* rects = hier ? (uint2*)(geom + GL.rects) : nullptr;
-    uint2* rect_sorted = (uint2*)(geom + GL.rect_sorted);
-    uint4* pre_counts = (uint4*)(geom + GL.pre_counts);
-    if (segs == nullptr) {
-      launch_preprocess(stream, P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
-                        cov3D_precomp, colors_precomp, cam, radii_int, rec_w, key_a, tiles, rects,
+    if (q.segs == nullptr) {
+      launch_preprocess(stream, q.P, q.D, q.M, q.means3D, q.scales, q.scale_modifier, q.rotations, q.opacities,
+                        q.shs, q.cov3D_precomp, q.colors_precomp, cam, radii_int, rec_w, key_a, tiles, rects,
                         fat_sort ? ds_table : nullptr, pre_counts, marks);
     } else {
-      // segment table: host structs -> pinned staging -> the geometry blob (asynchronous copy)
-      if (!g_seg_staging)
-        HIP_TRY(hipHostMalloc((void**)&g_seg_staging, sizeof(SegmentDev) * MAX_SEGMENTS, hipHostMallocDefault));
-      uint32_t start = 0;
-      for (int i = 0; i < nseg; i++) {
-        SegmentDev& d = g_seg_staging[i];
-        const grpg_model_segment& g = segs[i];
-        d.xyz = g.xyz; d.scaling = g.scaling; d.rotation = g.rotation; d.opacity = g.opacity;
-        d.fdc = g.features_dc; d.frest = g.features_rest; d.flip = g.flip;
-        d.pad1 = (const void*)(uintptr_t)(layers ? ((layers->segment_class ? layers->segment_class[i] != 0
-                                                                           : g.rigid != 0) ? 1u : 0u) : 0u);
-        d.start = start; d.count = (uint32_t)g.count;
-        d.fourier_dim = g.fourier_dim; d.rigid = g.rigid;
-        for (int k = 0; k < 4; k++) d.rot[k] = g.obj_rot[k];
-        for (int k = 0; k < 3; k++) d.trans[k] = g.obj_trans[k];
-        d.pad0 = 0.f;
-        for (int k = 0; k < MAX_FOURIER; k++) d.idft[k] = g.idft[k];
-        start += (uint32_t)g.count;
-      }
       SegmentDev* seg_dev = (SegmentDev*)(geom + GL.seg_table);
-      HIP_TRY(hipMemcpyAsync(seg_dev, g_seg_staging, sizeof(SegmentDev) * (size_t)nseg,
-                             hipMemcpyHostToDevice, stream));
-      launch_preprocess_composed(stream, P, D, M, seg_dev, nseg, scale_modifier, cam, radii_int, rec_w,
+      if (int rc = stage_segments(seg_dev)) return rc;
+      launch_preprocess_composed(stream, q.P, q.D, q.M, seg_dev, q.nseg, q.scale_modifier, cam, radii_int, rec_w,
                                  key_a, tiles, rects, fat_sort ? ds_table : nullptr, pre_counts, marks);
     }
     // num_rendered (and the coarse pair count) as sums of the per-Gaussian counts: in the pinned
@@ -758,276 +832,265 @@ int forward_impl(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_f
     const bool fold_publish = fat_sort;
 #endif
     if (!fold_publish) {
-      launch_publish_counts(stream, pre_counts, (uint32_t)((P + 255) / 256), pub_ptr, &gh->R_pre);
+      launch_publish_counts(stream, pre_counts, (uint32_t)((q.P + 255) / 256), pub_ptr, &gh->R_pre);
       HIP_TRY(hipEventRecord(pub_ev, stream));
     }
     STAGE_CHECK("preprocess");
     tm.mark(1);
     // (depth_bits, id) order: stable sort of ids by the 32-bit depth key.
-    uint32_t* tiles_sorted = (uint32_t*)(geom + GL.tiles_sorted);
-    const uint32_t* sorted_gid;
-    // hierarchical binning on a grid of <= 255 x 255 tiles: the tile rectangles ride through the
-    // depth sort as a packed payload and arrive in depth order together with the super-tile counts
-    // (sort.hip RectPayload); larger grids: the coarse scan gathers them by sorted id instead
-    const bool rect_sorted_by_sort = hier && cam.gx <= 255 && cam.gy <= 255;
     if (fat_sort) {   // drops the culled Gaussians: V pairs remain
-      const uint32_t pnb = (uint32_t)((P + 255) / 256);
+      const uint32_t pnb = (uint32_t)((q.P + 255) / 256);
       uint32_t* key_c = (uint32_t*)(geom + GL.key_c);
       uint32_t* val_c = (uint32_t*)(geom + GL.val_c);
       if (rect_sorted_by_sort)   // scratch: rect_sorted's own first half, the not yet written offsets, aux_c
-        depth_sort_fat(stream, (uint32_t)P, key_a, val_a, key_b, val_b, key_c, val_c, ds_table,
+        depth_sort_fat(stream, (uint32_t)q.P, key_a, val_a, key_b, val_b, key_c, val_c, ds_table,
                        GL.nchunks_ds, &gh->V, &gh->key_base, with_pass3,
                        rects, (uint32_t*)rect_sorted, offsets,
                        (uint32_t*)(geom + GL.aux_c), rect_sorted, tiles_sorted, pre_counts, pnb, fold_publish,
                        pub_ptr, &gh->R_pre, pub_ev);
       else
-        depth_sort_fat(stream, (uint32_t)P, key_a, val_a, key_b, val_b, key_c, val_c, ds_table,
+        depth_sort_fat(stream, (uint32_t)q.P, key_a, val_a, key_b, val_b, key_c, val_c, ds_table,
                        GL.nchunks_ds, &gh->V, &gh->key_base, with_pass3,
                        nullptr, nullptr, nullptr, nullptr, nullptr,
                        nullptr, pre_counts, pnb, fold_publish, pub_ptr, &gh->R_pre, pub_ev);
       sorted_gid = val_a;
     } else {          // culled keys sort last (tile count 0); V stays P
-      const bool in_b = radix_sort_pairs(stream, (uint32_t)P, nullptr, key_a, val_a, key_b, val_b, true,
+      const bool in_b = radix_sort_pairs(stream, (uint32_t)q.P, nullptr, key_a, val_a, key_b, val_b, true,
                                          0, 32, table, totals, GL.nchunks_sort, false, tiles,
                                          tiles_sorted);
       sorted_gid = in_b ? val_b : val_a;  // 4 passes -> back in "a"
     }
     STAGE_CHECK("depth sort");
     tm.begin_tail();
-    uint32_t* emit_win = (uint32_t*)(geom + GL.emit_win);
-    // sort path: exclusive offsets of the per-Gaussian tile counts in depth order (the count itself
-    // is already on its way to the host, see above)
-    auto scan_tiles = [&]() -> int {
-      tm.mark(2);
-      launch_offsets_scan(stream, (uint32_t)P, &gh->V, tiles_sorted, fat_sort ? sorted_gid : nullptr, tiles,
-                          offsets, block_sums, GL.nblocks_scan, &gh->R, nullptr, emit_win,
-                          GL.emit_win_cap);
-      STAGE_CHECK("offsets scan");
-      return GRPG_OK;
-    };
-    auto render_tail = [&](char* binp, const BinLayout& L, const uint32_t* point_list, uint32_t cap,
-                           bool classified) -> int {
-      tm.mark(6);
-      const CkptArgs ck = {(float*)(binp + L.total), (uint32_t*)(img + IL.ck_count),
-                           (uint32_t*)(img + IL.bwd_ctl), (BlobHeader*)binp,
-                           (uint32_t)(L.total / 256), ckpt_slots(cap)};
-      if (layers)
-        launch_render_layers(stream, ranges, const_cast<uint32_t*>(point_list), rec, width, height, cam.gx, cam.gy,
-                             background, out_color, out_depth, out_alpha, work, frame_classes, cap,
-                             classified, layers->layer_background, layers->out_color_bg,
-                             layers->out_alpha_bg, layers->out_color_obj, layers->out_alpha_obj,
-                             PCErr{&((BlobHeader*)img)->pc_timeout, hw->dev_ptr + 3}, epi);
-      else
-      launch_render_forward(stream, ranges, point_list, rec, width, height, cam.gx, cam.gy, background,
-                            out_color, out_depth, out_alpha, n_contrib, work, frame_classes, cap,
-                            (flags & GRPG_FORWARD_NO_BACKWARD) == 0u, classified,
-                            with_ckpt ? &ck : nullptr,
-                            PCErr{&((BlobHeader*)img)->pc_timeout, hw->dev_ptr + 3},
-                            S > 0 ? semantics : nullptr, S, out_semantic, epi);
-      STAGE_CHECK("render");
-      if (debug)   // the stage check has synchronised: a hand-over timeout of THIS frame is known
-        if (int rc = check_async_error(hw)) return rc;
-      tm.mark(7);
-      if (S > RENDER_NSEM) {   // the first RENDER_NSEM planes rode in the render launch
-        launch_render_semantic(stream, ranges, point_list, rec, semantics, S, RENDER_NSEM, width, height,
-                               cam.gx, cam.gy, out_semantic);
-        STAGE_CHECK("semantic render");
-      }
-      tm.mark(-1);
-      return GRPG_OK;
-    };
+    return GRPG_OK;
+  }
 
+  // The tail of the frame -- everything that works on the binning blob, and so is enqueued again after a capacity
+  // overflow: the binning for the blob as carved, then the render.
+  int enqueue_tail() {
+    if (hier) return tail_hier();
+    // sort path: exclusive offsets of the per-Gaussian tile counts in depth order (the count itself
+    // is already on its way to the host, see enqueue_head)
+    tm.mark(2);
+    launch_offsets_scan(stream, (uint32_t)q.P, &gh->V, tiles_sorted, fat_sort ? sorted_gid : nullptr, tiles,
+                        offsets, block_sums, GL.nblocks_scan, &gh->R, nullptr, emit_win,
+                        GL.emit_win_cap);
+    STAGE_CHECK("offsets scan");
+    return tail_sort();
+  }
+
+  // sort path: everything behind the offsets scan
+  int tail_sort() {
+    const BinLayout& L = BL;
+    const uint32_t cap = Rcap;
     const int tbits = bits_for(T);
     const int passes = radix_sort_num_passes(0, tbits);
     const int bits0 = radix_sort_first_pass_bits(0, tbits);
-    // sort path: everything behind the offsets scan, for a binning blob of capacity `cap`
-    auto tail_sort = [&](char* binp, const BinLayout& L, uint32_t cap) -> int {
-      uint32_t* bkey_a = (uint32_t*)(binp + L.key_a);
-      uint32_t* bkey_b = (uint32_t*)(binp + L.key_b);
-      uint32_t* bval_a = (uint32_t*)(binp + L.val_a);
-      uint32_t* bval_b = (uint32_t*)(binp + L.val_b);
-      uint32_t* btable = (uint32_t*)(binp + L.table);
-      uint32_t* btotals = (uint32_t*)(binp + L.totals);
-      tm.mark(3);
-      // emit into whichever pair makes the LAST pass land in "a" (point_list lives in val_a)
-      const bool start_in_b = (passes & 1) != 0;
-      launch_emit(stream, &gh->V, &gh->R, cap, sorted_gid, offsets, emit_win, GL.emit_win_cap, rec,
-                  cam.gx, cam.gy, start_in_b ? bkey_b : bkey_a, start_in_b ? bval_b : bval_a,
-                  passes > 0 ? btable : nullptr, (1u << bits0) - 1u, L.nchunks_sort);
-      STAGE_CHECK("emit");
-      tm.mark(4);
-      if (passes > 0 && cap > 0) {
-        bool res_b;
-        if (start_in_b)
-          res_b = !radix_sort_pairs(stream, cap, &gh->R, bkey_b, bval_b, bkey_a, bval_a, false, 0, tbits,
-                                    btable, btotals, L.nchunks_sort, true);
-        else
-          res_b = radix_sort_pairs(stream, cap, &gh->R, bkey_a, bval_a, bkey_b, bval_b, false, 0, tbits,
-                                   btable, btotals, L.nchunks_sort, true);
-        if (res_b) return fail(GRPG_ERR_HIP, "internal: tile sort landed in the wrong buffer");
-      }
-      STAGE_CHECK("tile sort");
-      tm.mark(5);
-      launch_tile_ranges(stream, &gh->R, cap, bkey_a, ranges, T);
-      STAGE_CHECK("tile ranges");
-      return render_tail(binp, L, bval_a, cap, false);
-    };
-    // hierarchical path (hier_binning.hip): everything behind the depth sort.  Stage slots: 2 = scan
-    // over the super-tile counts, 3 = coarse emit, 4 = coarse partition + super-tile runs,
-    // 5 = segment counts, tile ranges and the point-list fill.
+    uint32_t* bkey_a = (uint32_t*)(bin + L.key_a);
+    uint32_t* bkey_b = (uint32_t*)(bin + L.key_b);
+    uint32_t* bval_a = (uint32_t*)(bin + L.val_a);
+    uint32_t* bval_b = (uint32_t*)(bin + L.val_b);
+    uint32_t* btable = (uint32_t*)(bin + L.table);
+    uint32_t* btotals = (uint32_t*)(bin + L.totals);
+    tm.mark(3);
+    // emit into whichever pair makes the LAST pass land in "a" (point_list lives in val_a)
+    const bool start_in_b = (passes & 1) != 0;
+    uint32_t *const key0 = start_in_b ? bkey_b : bkey_a, *const val0 = start_in_b ? bval_b : bval_a;
+    uint32_t *const key1 = start_in_b ? bkey_a : bkey_b, *const val1 = start_in_b ? bval_a : bval_b;
+    launch_emit(stream, &gh->V, &gh->R, cap, sorted_gid, offsets, emit_win, GL.emit_win_cap, rec,
+                cam.gx, cam.gy, key0, val0, passes > 0 ? btable : nullptr, (1u << bits0) - 1u, L.nchunks_sort);
+    STAGE_CHECK("emit");
+    tm.mark(4);
+    if (passes > 0 && cap > 0) {
+      const bool in_1 = radix_sort_pairs(stream, cap, &gh->R, key0, val0, key1, val1, false, 0, tbits,
+                                         btable, btotals, L.nchunks_sort, true);
+      if ((in_1 ? key1 : key0) != bkey_a) return fail(GRPG_ERR_HIP, "internal: tile sort landed in the wrong buffer");
+    }
+    STAGE_CHECK("tile sort");
+    tm.mark(5);
+    launch_tile_ranges(stream, &gh->R, cap, bkey_a, ranges, T);
+    STAGE_CHECK("tile ranges");
+    return render_tail(bval_a, false);
+  }
+
+  // hierarchical path (hier_binning.hip): everything behind the depth sort.  Stage slots: 2 = scan
+  // over the super-tile counts, 3 = coarse emit, 4 = coarse partition + super-tile runs,
+  // 5 = segment counts, tile ranges and the point-list fill.
+  int tail_hier() {
+    const BinLayout& L = BL;
+    char* const binp = bin;
+    const uint32_t cap = Rcap, ccap = Ccap;
     const int sgx = (cam.gx + STILE - 1) / STILE, sgy = (cam.gy + STILE - 1) / STILE;
     const int cbits = bits_for(NS);
     const int cpasses = radix_sort_num_passes(0, cbits);
     const int cbits0 = radix_sort_first_pass_bits(0, cbits);
-    auto tail_hier = [&](char* binp, const BinLayout& L, uint32_t cap, uint32_t ccap) -> int {
-      uint32_t* ckey_a = (uint32_t*)(binp + L.key_a);
-      uint32_t* ckey_b = (uint32_t*)(binp + L.key_b);
-      uint32_t* cval_a = (uint32_t*)(binp + L.val_b);
-      uint32_t* cval_b = (uint32_t*)(binp + L.val_c);
-      uint32_t* plist = (uint32_t*)(binp + L.val_a);
-      uint32_t* btable = (uint32_t*)(binp + L.table);
-      uint32_t* btotals = (uint32_t*)(binp + L.totals);
-      uint2* cranges = (uint2*)(binp + L.cranges);
-      tm.mark(2);
-      // counts and rectangles already in depth order (from the sort's last pass): the emit scans the offsets it
-      // needs itself from the block sums (binning.hip emit_coarse_fused_kernel); otherwise the two-launch scan
-      const bool fused_emit = rect_sorted_by_sort && emit_coarse_fused_ok(GL.nblocks_scan) && !UNFUSED_COARSE_EMIT;
-      if (fused_emit)
-        launch_offsets_reduce(stream, (uint32_t)P, &gh->V, tiles_sorted, block_sums, GL.nblocks_scan);
-      else if (rect_sorted_by_sort)
-        launch_offsets_scan(stream, (uint32_t)P, &gh->V, tiles_sorted, nullptr, nullptr, offsets,
-                            block_sums, GL.nblocks_scan, &gh->Rc, nullptr, emit_win, GL.emit_win_cap);
-      else
-        launch_offsets_scan(stream, (uint32_t)P, &gh->V, tiles_sorted, sorted_gid, nullptr, offsets,
-                            block_sums, GL.nblocks_scan, &gh->Rc, nullptr, emit_win, GL.emit_win_cap, rects,
-                            rect_sorted);
-      STAGE_CHECK("coarse offsets scan");
-      tm.mark(3);
-      if (fused_emit)
-        launch_emit_coarse_fused(stream, &gh->V, &gh->Rc, ccap, sorted_gid, tiles_sorted, block_sums,
-                                 GL.nblocks_scan, rect_sorted, sgx, ckey_a, cval_a, cpasses > 0 ? btable : nullptr,
-                                 (1u << cbits0) - 1u, L.nchunks_coarse, cranges, NS);
-      else
-        launch_emit_coarse(stream, &gh->V, &gh->Rc, ccap, sorted_gid, rect_sorted, offsets, emit_win,
-                           GL.emit_win_cap, sgx, sgy, ckey_a, cval_a, cpasses > 0 ? btable : nullptr,
-                           (1u << cbits0) - 1u, L.nchunks_coarse, cranges, NS);
-      STAGE_CHECK("coarse emit");
-      tm.mark(4);
-      bool in_b = false;
-      if (cpasses > 0 && ccap > 0)
-        in_b = radix_sort_pairs(stream, ccap, &gh->Rc, ckey_a, cval_a, ckey_b, cval_b, false, 0, cbits,
-                                btable, btotals, L.nchunks_coarse, true);
-      STAGE_CHECK("coarse partition");
-      const uint32_t* ckey = in_b ? ckey_b : ckey_a;
-      // one pass (<= 256 super-tiles): its digit totals ARE the run lengths; otherwise find the runs
-      const bool runs_from_totals = cpasses == 1 && ccap > 0;
-      if (!runs_from_totals) launch_tile_ranges(stream, &gh->Rc, ccap, ckey, cranges, NS, 0xFFFFu);
-      STAGE_CHECK("super-tile runs");
-      tm.mark(5);
-      const uint32_t* cval = in_b ? cval_b : cval_a;
-      launch_hier_count(stream, cranges, runs_from_totals ? btotals : nullptr, NS, binp + L.seg_desc, (uint2*)(binp + L.st_seg),
-                        (uint32_t*)(binp + L.nseg), L.max_seg, ckey, cam.gx, cam.gy,
-                        (uint32_t*)(binp + L.seg_table), (uint32_t*)(binp + L.tile_tot),
-                        (uint32_t*)(binp + L.tile_start), ranges, &gh->R, nullptr,
-                        &gh->Rc, (BlobHeader*)binp, cap, ccap, work, frame_classes);
-      STAGE_CHECK("tile counts");
-      launch_hier_fill(stream, binp + L.seg_desc, (const uint32_t*)(binp + L.nseg), L.max_seg, ckey, cval, rec,
-                       cam.gx, cam.gy, (const uint32_t*)(binp + L.seg_table),
-                       (const uint32_t*)(binp + L.tile_start), cap, plist);
-      STAGE_CHECK("point list fill");
-      return render_tail(binp, L, plist, cap, true);
-    };
-    auto carve = [&](uint32_t cap, uint32_t ccap, bool rezero) -> int {
-      Rcap = cap;
-      Ccap = ccap;
-      BL = layout_for(Rcap, Ccap);
-      bin = binning_alloc(blob_bytes(BL, Rcap), binning_user);
-      if (!bin) return fail(GRPG_ERR_ALLOC, "binning buffer allocation failed");
-      launch_bin_header(stream, bin, (uint32_t)P, Rcap, (uint32_t)width, (uint32_t)height, (uint32_t)S,
-                        rezero ? ranges : nullptr, T, rezero ? work : nullptr);
-      return GRPG_OK;
-    };
-    const bool spec_mode = g_binning_mode.load() == GRPG_BINNING_SPECULATIVE;
+    uint32_t* ckey_a = (uint32_t*)(binp + L.key_a);
+    uint32_t* ckey_b = (uint32_t*)(binp + L.key_b);
+    uint32_t* cval_a = (uint32_t*)(binp + L.val_b);
+    uint32_t* cval_b = (uint32_t*)(binp + L.val_c);
+    uint32_t* plist = (uint32_t*)(binp + L.val_a);
+    uint32_t* btable = (uint32_t*)(binp + L.table);
+    uint32_t* btotals = (uint32_t*)(binp + L.totals);
+    uint2* cranges = (uint2*)(binp + L.cranges);
+    tm.mark(2);
+    // counts and rectangles already in depth order (from the sort's last pass): the emit scans the offsets it
+    // needs itself from the block sums (binning.hip emit_coarse_fused_kernel); otherwise the two-launch scan
+    const bool fused_emit = rect_sorted_by_sort && emit_coarse_fused_ok(GL.nblocks_scan) && !UNFUSED_COARSE_EMIT;
+    if (fused_emit)
+      launch_offsets_reduce(stream, (uint32_t)q.P, &gh->V, tiles_sorted, block_sums, GL.nblocks_scan);
+    else if (rect_sorted_by_sort)
+      launch_offsets_scan(stream, (uint32_t)q.P, &gh->V, tiles_sorted, nullptr, nullptr, offsets,
+                          block_sums, GL.nblocks_scan, &gh->Rc, nullptr, emit_win, GL.emit_win_cap);
+    else
+      launch_offsets_scan(stream, (uint32_t)q.P, &gh->V, tiles_sorted, sorted_gid, nullptr, offsets,
+                          block_sums, GL.nblocks_scan, &gh->Rc, nullptr, emit_win, GL.emit_win_cap, rects,
+                          rect_sorted);
+    STAGE_CHECK("coarse offsets scan");
+    tm.mark(3);
+    if (fused_emit)
+      launch_emit_coarse_fused(stream, &gh->V, &gh->Rc, ccap, sorted_gid, tiles_sorted, block_sums,
+                               GL.nblocks_scan, rect_sorted, sgx, ckey_a, cval_a, cpasses > 0 ? btable : nullptr,
+                               (1u << cbits0) - 1u, L.nchunks_coarse, cranges, NS);
+    else
+      launch_emit_coarse(stream, &gh->V, &gh->Rc, ccap, sorted_gid, rect_sorted, offsets, emit_win,
+                         GL.emit_win_cap, sgx, sgy, ckey_a, cval_a, cpasses > 0 ? btable : nullptr,
+                         (1u << cbits0) - 1u, L.nchunks_coarse, cranges, NS);
+    STAGE_CHECK("coarse emit");
+    tm.mark(4);
+    bool in_b = false;
+    if (cpasses > 0 && ccap > 0)
+      in_b = radix_sort_pairs(stream, ccap, &gh->Rc, ckey_a, cval_a, ckey_b, cval_b, false, 0, cbits,
+                              btable, btotals, L.nchunks_coarse, true);
+    STAGE_CHECK("coarse partition");
+    const uint32_t* ckey = in_b ? ckey_b : ckey_a;
+    // one pass (<= 256 super-tiles): its digit totals ARE the run lengths; otherwise find the runs
+    const bool runs_from_totals = cpasses == 1 && ccap > 0;
+    if (!runs_from_totals) launch_tile_ranges(stream, &gh->Rc, ccap, ckey, cranges, NS, 0xFFFFu);
+    STAGE_CHECK("super-tile runs");
+    tm.mark(5);
+    const uint32_t* cval = in_b ? cval_b : cval_a;
+    launch_hier_count(stream, cranges, runs_from_totals ? btotals : nullptr, NS, binp + L.seg_desc, (uint2*)(binp + L.st_seg),
+                      (uint32_t*)(binp + L.nseg), L.max_seg, ckey, cam.gx, cam.gy,
+                      (uint32_t*)(binp + L.seg_table), (uint32_t*)(binp + L.tile_tot),
+                      (uint32_t*)(binp + L.tile_start), ranges, &gh->R, nullptr,
+                      &gh->Rc, (BlobHeader*)binp, cap, ccap, work, frame_classes);
+    STAGE_CHECK("tile counts");
+    launch_hier_fill(stream, binp + L.seg_desc, (const uint32_t*)(binp + L.nseg), L.max_seg, ckey, cval, rec,
+                     cam.gx, cam.gy, (const uint32_t*)(binp + L.seg_table),
+                     (const uint32_t*)(binp + L.tile_start), cap, plist);
+    STAGE_CHECK("point list fill");
+    return render_tail(plist, true);
+  }
 
-    // Speculative: the whole frame is enqueued for the remembered capacities, then the host reads
-    // the count (published right behind preprocess: normally there already).  No history / exact
-    // mode: read the count first, carve the blob for it, then enqueue the tail -- like the
-    // reference's one blocking read (rasterizer_impl.cu:284), only much earlier in the frame.
-    uint32_t Rc_seen = 0u;   // coarse count of this frame, once the host has seen it
-    auto run_tail = [&]() -> int {
-      if (hier) return tail_hier(bin, BL, Rcap, Ccap);
-      if (int rc = scan_tiles()) return rc;
-      return tail_sort(bin, BL, Rcap);
-    };
-    if (speculative) {
-      if (int rc = run_tail()) return rc;
+  // the render over the finished point list (classified: the binning has already sorted the tiles into work lists)
+  int render_tail(const uint32_t* point_list, bool classified) {
+    const uint32_t cap = Rcap;
+    tm.mark(6);
+    const CkptArgs ckpt = {(float*)(bin + BL.total), (uint32_t*)(img + IL.ck_count),
+                           (uint32_t*)(img + IL.bwd_ctl), (BlobHeader*)bin,
+                           (uint32_t)(BL.total / 256), ckpt_slots(cap)};
+    if (layers)
+      launch_render_layers(stream, ranges, const_cast<uint32_t*>(point_list), rec, q.width, q.height, cam.gx, cam.gy,
+                           q.background, q.out_color, q.out_depth, q.out_alpha, work, frame_classes, cap,
+                           classified, layers->layer_background, layers->out_color_bg,
+                           layers->out_alpha_bg, layers->out_color_obj, layers->out_alpha_obj,
+                           PCErr{&((BlobHeader*)img)->pc_timeout, hw->dev_ptr + 3}, epi);
+    else
+      launch_render_forward(stream, ranges, point_list, rec, q.width, q.height, cam.gx, cam.gy, q.background,
+                            q.out_color, q.out_depth, q.out_alpha, n_contrib, work, frame_classes, cap,
+                            training, classified, with_ckpt ? &ckpt : nullptr,
+                            PCErr{&((BlobHeader*)img)->pc_timeout, hw->dev_ptr + 3},
+                            q.S > 0 ? q.semantics : nullptr, q.S, q.out_semantic, epi);
+    STAGE_CHECK("render");
+    if (debug)   // the stage check has synchronised: a hand-over timeout of THIS frame is known
+      if (int rc = check_async_error(hw)) return rc;
+    tm.mark(7);
+    if (q.S > RENDER_NSEM) {   // the first RENDER_NSEM planes rode in the render launch
+      launch_render_semantic(stream, ranges, point_list, rec, q.semantics, q.S, RENDER_NSEM, q.width, q.height,
+                             cam.gx, cam.gy, q.out_semantic);
+      STAGE_CHECK("semantic render");
+    }
+    tm.mark(-1);
+    return GRPG_OK;
+  }
+
+  // A blob for the counts just read.  First frame of a shape / exact mode: nothing was carved yet.  Capacity
+  // overflow: the speculative tail clamped its work to the old capacities and its results are discarded (tile
+  // ranges and work lists are cleared again); both counts are exact, so one redo on a larger blob settles it.
+  int recarve(uint32_t R, uint32_t Rc) {
+    uint32_t cap = Rcap, ccap = Ccap;
+    if (!speculative) {
+      cap = spec_mode ? padded_capacity(R) : R;
+      ccap = hier ? (spec_mode ? padded_capacity(Rc) : Rc) : cap;
+    } else {
+      if (R > Rcap) cap = padded_capacity(R);
+      if (hier && Rc > Ccap) ccap = padded_capacity(Rc);
+    }
+    if (ccap > cap) ccap = cap;     // a (Gaussian, super-tile) pair holds >= 1 instance
+    const bool redo = speculative;
+    if (redo) tm.restart_tail();
+    if (int rc = carve_bin(cap, ccap)) return rc;
+    launch_bin_header(stream, bin, (uint32_t)q.P, Rcap, (uint32_t)q.width, (uint32_t)q.height, (uint32_t)q.S,
+                      redo ? ranges : nullptr, T, redo ? work : nullptr);
+    return GRPG_OK;
+  }
+};
+
+// Shared body of every forward entry point.
+// Speculative (capacities remembered from earlier frames of this shape): the whole frame is enqueued, then the host
+// reads the count (published right behind preprocess: normally there already).  No history / exact
+// mode: read the count first, carve the blob for it, then enqueue the tail -- like the
+// reference's one blocking read (rasterizer_impl.cu:284), only much earlier in the frame.
+int forward_impl(const FrameRequest& q, bool force_pass3 = false) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (int rc = validate(q)) return rc;
+  const CameraArgs cam = make_camera(q.viewmatrix, q.projmatrix, q.cam_pos, q.width, q.height, q.tan_fovx, q.tan_fovy);
+  // an evaluation frame carves the geometry blob without the gradient records
+  const GeomLayout GL = geom_layout((size_t)q.P, q.training());
+  const ImgLayout IL = img_layout(num_tiles(cam), (size_t)q.width * q.height);
+  char* geom = q.geometry_alloc(GL.total, q.geometry_user);
+  char* img = q.image_alloc(IL.total, q.image_user);
+  if (!geom || !img) return fail(GRPG_ERR_ALLOC, "geometry/image buffer allocation failed");
+  remember_geom(geom, q.P, q.training());
+  Frame f(q, cam, GL, IL, geom, img);
+  DeferSlot* const defer = q.defer;
+  uint32_t R = 0;
+  if (q.P == 0) {
+    if (int rc = f.empty_frame()) return rc;
+  } else {
+    if (int rc = f.begin(force_pass3)) return rc;
+    if (int rc = f.enqueue_head()) return rc;
+    if (f.speculative) {
+      if (int rc = f.enqueue_tail()) return rc;
       if (defer) {
         // deferred frame: the count is checked by grpg_frame_status, nothing to wait for here
         defer->state = 1;
-        defer->Rcap = Rcap; defer->Ccap = Ccap; defer->hier = hier; defer->key = ck;
-        defer->with_pass3 = with_pass3 || !fat_sort;
-        tm.finish();
+        defer->Rcap = f.Rcap; defer->Ccap = f.Ccap; defer->hier = f.hier; defer->key = f.ck;
+        defer->with_pass3 = f.with_pass3 || !f.fat_sort;
+        f.tm.finish();
         return 0;
       }
     }
-    HIP_TRY(hipEventSynchronize(pub_ev));
-    R = (defer ? defer->host_ptr : hw->host_ptr)[0];
-    if (hier) Rc_seen = (defer ? defer->host_ptr : hw->host_ptr)[1];
-    const bool far_seen = fat_sort && (defer ? defer->host_ptr : hw->host_ptr)[2] != 0u;
+    // the counts as published behind preprocess: num_rendered, coarse pairs, did the depth keys need the fourth pass
+    HIP_TRY(hipEventSynchronize(f.pub_ev));
+    R = f.pub_host[0];
+    const uint32_t Rc = f.hier ? f.pub_host[1] : 0u;
+    const bool far = f.fat_sort && f.pub_host[2] != 0u;
     if (R > 0x7FFFFFFFu) return fail(GRPG_ERR_INVALID_ARGUMENT, "num_rendered exceeds int32");
-    if (far_seen && !with_pass3) {
+    if (far && !f.with_pass3) {
       // the scene's depth range grew beyond what three sort passes order: this frame's lists are in
       // the wrong order.  Remember it and render the frame again, this time with the fourth pass.
-      update_hint(ck, R, Rc_seen, true);
-      return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user,
-                          P, D, M, S, background, width, height, means3D, shs, colors_precomp, semantics,
-                          opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                          cam_pos, tan_fovx, tan_fovy, out_color, out_depth, out_alpha, out_semantic, radii,
-                          debug, hip_stream, segs, nseg, flags, defer, true, layers, epi);
+      update_hint(f.ck, R, Rc, true);
+      return forward_impl(q, true);
     }
-    if (!speculative || R > Rcap || (hier && Rc_seen > Ccap)) {
-      // first frame of a shape / exact mode: carve for the count just read.  Capacity overflow: the
-      // speculative tail clamped its work to the old capacities and its results are discarded; both
-      // counts are exact, so one redo on a larger blob settles it.
-      const bool redo = speculative;
-      uint32_t cap = Rcap, ccap = Ccap;
-      if (!speculative) {
-        cap = spec_mode ? padded_capacity(R) : R;
-        ccap = hier ? (spec_mode ? padded_capacity(Rc_seen) : Rc_seen) : cap;
-      } else {
-        if (R > Rcap) cap = padded_capacity(R);
-        if (hier && Rc_seen > Ccap) ccap = padded_capacity(Rc_seen);
-      }
-      if (ccap > cap) ccap = cap;     // a (Gaussian, super-tile) pair holds >= 1 instance
-      if (redo) tm.restart_tail();
-      if (int rc = carve(cap, ccap, redo)) return rc;
-      if (int rc = run_tail()) return rc;
+    if (!f.speculative || R > f.Rcap || (f.hier && Rc > f.Ccap)) {
+      if (int rc = f.recarve(R, Rc)) return rc;
+      if (int rc = f.enqueue_tail()) return rc;
     }
-    if (R > 0x7FFFFFFFu) return fail(GRPG_ERR_INVALID_ARGUMENT, "num_rendered exceeds int32");
-    update_hint(ck, R, Rc_seen, far_seen);
-    tm.finish();
+    update_hint(f.ck, R, Rc, far);
+    f.tm.finish();
     if (defer) { defer->state = 2; defer->result = (int)R; }   // no capacity history: ran synchronously
-  } else {
-    // P == 0: the reference launches nothing and its pre-zeroed planes stay zero
-    // (rasterize_points.cu:85-86,123); write the zeros explicitly.
-    if (out_color) HIP_TRY(hipMemsetAsync(out_color, 0, 3 * N * 4, stream));
-    if (out_depth) HIP_TRY(hipMemsetAsync(out_depth, 0, N * 4, stream));
-    if (out_alpha) HIP_TRY(hipMemsetAsync(out_alpha, 0, N * 4, stream));
-    if (epi) launch_frame_epilogue_empty(stream, width, height, *epi, out_color);   // sky over nothing, bytes
-    if (S > 0 && out_semantic) HIP_TRY(hipMemsetAsync(out_semantic, 0, (size_t)S * N * 4, stream));
-    HIP_TRY(hipMemsetAsync(n_contrib, 0, N * 4, stream));
-    if (layers) {
-      // ONE contract for an empty layer (ADVICE r5): its colour plane is layer_background, its alpha plane zero --
-      // what the kernels write for an empty class when P > 0, and what the reference's render_kernel returns for a
-      // model set without Gaussians (street_gaussian_renderer.py:131-144: ones on a white background, acc zeros)
-      launch_fill_layer_planes(stream, N, layers->layer_background, layers->out_color_bg, layers->out_alpha_bg,
-                               layers->out_color_obj, layers->out_alpha_obj);
-    }
-    char* bin = binning_alloc(bin_layout(0).total, binning_user);
-    if (!bin) return fail(GRPG_ERR_ALLOC, "binning buffer allocation failed");
-    launch_frame_init(stream, geom, bin, img, 0u, 0u, 0u, (uint32_t)width, (uint32_t)height,
-                      (uint32_t)S, ranges, T, work, geom + GL.zero_begin, GL.zero_end - GL.zero_begin,
-                      (flags & GRPG_FORWARD_NO_BACKWARD) == 0u);
   }
   if (defer && defer->state == 0) { defer->state = 2; defer->result = (int)R; }
   return (int)R;
@@ -1100,6 +1163,39 @@ int check_segments(const grpg_model_segment* segs, int nseg, int M, long long* P
   return GRPG_OK;
 }
 
+// the model of a composed entry point: its segments and the SH degree they share -> P
+int check_composed_model(const grpg_model_segment* segs, int nseg, int D, int M, long long* P_out) {
+  if (int rc = check_segments(segs, nseg, M, P_out)) return rc;
+  if (M < 1 || M > 16 || D < 0 || D > 3 || (D + 1) * (D + 1) > M)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "SH degree needs (D+1)^2 <= M <= 16");
+  return GRPG_OK;
+}
+
+// The layer arguments of an entry point -> *out: &la for a layered frame, NULL for a plain one.  The layer planes
+// come all four or not at all; `optional` (grpg_forward_frame / _composed_frame): none of them is a plain frame,
+// otherwise (the _layers entries) all four are required.  `flat`: layer_class classes the Gaussians (a composed
+// frame's segment_class may be NULL).
+int check_layers(const LayerArgs& la, long long P, bool flat, bool optional, const LayerArgs** out) {
+  const int n = (la.out_color_bg != nullptr) + (la.out_alpha_bg != nullptr) + (la.out_color_obj != nullptr) +
+                (la.out_alpha_obj != nullptr);
+  *out = nullptr;
+  if (optional) {
+    if (n == 0) return GRPG_OK;
+    if (n != 4) return fail(GRPG_ERR_INVALID_ARGUMENT, "layer planes: give all four or none");
+    if (!la.layer_background || (flat && P > 0 && !la.layer_class))
+      return fail(GRPG_ERR_INVALID_ARGUMENT, flat ? "a layered frame needs layer_class and layer_background"
+                                                  : "a layered frame needs layer_background");
+  } else {
+    if (!la.layer_background || n != 4)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL layer background / layer plane pointer");
+    if (flat && P > 0 && !la.layer_class) return fail(GRPG_ERR_INVALID_ARGUMENT, "layer_class NULL");
+  }
+  if ((unsigned long long)P >= (1ull << 27))   // (a negative P of a flat entry as well)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "a layered frame needs P < 2^27 (the class travels in bit 27 of the point list)");
+  *out = &la;
+  return GRPG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1114,12 +1210,12 @@ int grpg_forward(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_f
                  float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                  float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug,
                  void* hip_stream) {
-  (void)prefiltered;  // reference: __trap() on a culled point when set; always False in practice
-  return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc,
-                      image_user, P, D, M, S, background, width, height, means3D, shs, colors_precomp,
-                      semantics, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                      viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth,
-                      out_alpha, out_semantic, radii, debug, hip_stream, nullptr, 0);
+  // (prefiltered -- reference: __trap() on a culled point when set; always False in practice)
+  return grpg_forward_flags(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D,
+                            M, S, background, width, height, means3D, shs, colors_precomp, semantics, opacities,
+                            scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                            tan_fovx, tan_fovy, prefiltered, out_color, out_depth, out_alpha, out_semantic, radii,
+                            debug, hip_stream, 0u);
 }
 
 int grpg_forward_flags(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_fn binning_alloc,
@@ -1133,11 +1229,17 @@ int grpg_forward_flags(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_a
                        float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug,
                        void* hip_stream, unsigned flags) {
   (void)prefiltered;
-  return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc,
-                      image_user, P, D, M, S, background, width, height, means3D, shs, colors_precomp,
-                      semantics, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                      viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth,
-                      out_alpha, out_semantic, radii, debug, hip_stream, nullptr, 0, flags);
+  FrameRequest q;
+  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
+  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
+  q.P = P; q.D = D; q.M = M; q.S = S; q.background = background; q.width = width; q.height = height;
+  q.means3D = means3D; q.shs = shs; q.colors_precomp = colors_precomp; q.semantics = semantics;
+  q.opacities = opacities; q.scales = scales; q.scale_modifier = scale_modifier; q.rotations = rotations;
+  q.cov3D_precomp = cov3D_precomp; q.viewmatrix = viewmatrix; q.projmatrix = projmatrix; q.cam_pos = cam_pos;
+  q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy; q.out_color = out_color; q.out_depth = out_depth;
+  q.out_alpha = out_alpha; q.out_semantic = out_semantic; q.radii = radii; q.debug = debug;
+  q.stream = (hipStream_t)hip_stream; q.flags = flags;
+  return forward_impl(q);
 }
 
 int grpg_forward_layers(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_fn binning_alloc,
@@ -1151,17 +1253,18 @@ int grpg_forward_layers(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_
                         float* out_depth, float* out_alpha, float* out_color_bg, float* out_alpha_bg,
                         float* out_color_obj, float* out_alpha_obj, int* radii, int debug, void* hip_stream) {
   g_last_error.clear();
-  if (!layer_background || !out_color_bg || !out_alpha_bg || !out_color_obj || !out_alpha_obj)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL layer background / layer plane pointer");
-  if (P > 0 && !layer_class) return fail(GRPG_ERR_INVALID_ARGUMENT, "layer_class NULL");
-  if ((unsigned)P >= (1u << 27))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "a layered frame needs P < 2^27 (the class travels in bit 27 of the point list)");
   const LayerArgs la = {nullptr, layer_class, layer_background, out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj};
-  return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D,
-                      M, 0, background, width, height, means3D, shs, colors_precomp, nullptr, opacities, scales,
-                      scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
-                      tan_fovy, out_color, out_depth, out_alpha, nullptr, radii, debug, hip_stream, nullptr, 0,
-                      GRPG_FORWARD_NO_BACKWARD, nullptr, false, &la);
+  FrameRequest q;
+  if (int rc = check_layers(la, P, true, false, &q.layers)) return rc;
+  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
+  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
+  q.P = P; q.D = D; q.M = M; q.background = background; q.width = width; q.height = height;
+  q.means3D = means3D; q.shs = shs; q.colors_precomp = colors_precomp; q.opacities = opacities;
+  q.scales = scales; q.scale_modifier = scale_modifier; q.rotations = rotations; q.cov3D_precomp = cov3D_precomp;
+  q.viewmatrix = viewmatrix; q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx;
+  q.tan_fovy = tan_fovy; q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha;
+  q.radii = radii; q.debug = debug; q.stream = (hipStream_t)hip_stream; q.flags = GRPG_FORWARD_NO_BACKWARD;
+  return forward_impl(q);
 }
 
 int grpg_forward_deferred(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_fn binning_alloc,
@@ -1180,12 +1283,17 @@ int grpg_forward_deferred(grpg_alloc_fn geometry_alloc, void* geometry_user, grp
   if (!ticket) return fail(GRPG_ERR_INVALID_ARGUMENT, "ticket must not be NULL");
   DeferSlot* d = defer_acquire(ticket);
   if (!d) return fail(GRPG_ERR_HIP, "pinned status words / event allocation failed");
-  const int rc = forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc,
-                              image_user, P, D, M, S, background, width, height, means3D, shs,
-                              colors_precomp, semantics, opacities, scales, scale_modifier, rotations,
-                              cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
-                              out_color, out_depth, out_alpha, out_semantic, radii, debug, hip_stream,
-                              nullptr, 0, flags, d);
+  FrameRequest q;
+  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
+  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
+  q.P = P; q.D = D; q.M = M; q.S = S; q.background = background; q.width = width; q.height = height;
+  q.means3D = means3D; q.shs = shs; q.colors_precomp = colors_precomp; q.semantics = semantics;
+  q.opacities = opacities; q.scales = scales; q.scale_modifier = scale_modifier; q.rotations = rotations;
+  q.cov3D_precomp = cov3D_precomp; q.viewmatrix = viewmatrix; q.projmatrix = projmatrix; q.cam_pos = cam_pos;
+  q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy; q.out_color = out_color; q.out_depth = out_depth;
+  q.out_alpha = out_alpha; q.out_semantic = out_semantic; q.radii = radii; q.debug = debug;
+  q.stream = (hipStream_t)hip_stream; q.flags = flags; q.defer = d;
+  const int rc = forward_impl(q);
   if (rc < 0) { d->state = 2; d->result = rc; return rc; }
   return GRPG_OK;
 }
@@ -1218,14 +1326,16 @@ int grpg_forward_composed_flags(grpg_alloc_fn geometry_alloc, void* geometry_use
   g_last_error.clear();
   if (int rc = ensure_device()) return rc;
   long long P = 0;
-  if (int rc = check_segments(segments, num_segments, M, &P)) return rc;
-  if (M < 1 || M > 16 || D < 0 || D > 3 || (D + 1) * (D + 1) > M)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "SH degree needs (D+1)^2 <= M <= 16");
-  return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc,
-                      image_user, (int)P, D, M, 0, background, width, height, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, viewmatrix,
-                      projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth, out_alpha, nullptr,
-                      radii, debug, hip_stream, segments, num_segments, flags);
+  if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
+  FrameRequest q;
+  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
+  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
+  q.segs = segments; q.nseg = num_segments; q.P = (int)P; q.D = D; q.M = M; q.background = background;
+  q.width = width; q.height = height; q.scale_modifier = scale_modifier; q.viewmatrix = viewmatrix;
+  q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy;
+  q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha; q.radii = radii; q.debug = debug;
+  q.stream = (hipStream_t)hip_stream; q.flags = flags;
+  return forward_impl(q);
 }
 
 int grpg_forward_composed_layers(grpg_alloc_fn geometry_alloc, void* geometry_user,
@@ -1242,19 +1352,18 @@ int grpg_forward_composed_layers(grpg_alloc_fn geometry_alloc, void* geometry_us
   g_last_error.clear();
   if (int rc = ensure_device()) return rc;
   long long P = 0;
-  if (int rc = check_segments(segments, num_segments, M, &P)) return rc;
-  if (M < 1 || M > 16 || D < 0 || D > 3 || (D + 1) * (D + 1) > M)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "SH degree needs (D+1)^2 <= M <= 16");
-  if (!layer_background || !out_color_bg || !out_alpha_bg || !out_color_obj || !out_alpha_obj)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL layer background / layer plane pointer");
-  if (P >= (1ll << 27))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "a layered frame needs P < 2^27 (the class travels in bit 27 of the point list)");
+  if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
   const LayerArgs la = {segment_class, nullptr, layer_background, out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj};
-  return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc,
-                      image_user, (int)P, D, M, 0, background, width, height, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, viewmatrix,
-                      projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth, out_alpha, nullptr,
-                      radii, debug, hip_stream, segments, num_segments, GRPG_FORWARD_NO_BACKWARD, nullptr, false, &la);
+  FrameRequest q;
+  if (int rc = check_layers(la, P, false, false, &q.layers)) return rc;
+  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
+  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
+  q.segs = segments; q.nseg = num_segments; q.P = (int)P; q.D = D; q.M = M; q.background = background;
+  q.width = width; q.height = height; q.scale_modifier = scale_modifier; q.viewmatrix = viewmatrix;
+  q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy;
+  q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha; q.radii = radii; q.debug = debug;
+  q.stream = (hipStream_t)hip_stream; q.flags = GRPG_FORWARD_NO_BACKWARD;
+  return forward_impl(q);
 }
 
 // grpg_frame_epilogue -> FrameEpilogue (pointers checked); returns GRPG_OK or fails
@@ -1270,12 +1379,6 @@ static int resolve_epilogue(const grpg_frame_epilogue* e, bool planes, FrameEpil
   return GRPG_OK;
 }
 
-// layer planes: all four or none
-static int layer_planes_given(const float* a, const float* b, const float* c, const float* d) {
-  const int n = (a != nullptr) + (b != nullptr) + (c != nullptr) + (d != nullptr);
-  return n == 4 ? 1 : (n == 0 ? 0 : -1);
-}
-
 int grpg_forward_frame(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_fn binning_alloc,
                        void* binning_user, grpg_alloc_fn image_alloc, void* image_user, int P, int D, int M,
                        const float* background, int width, int height, const float* means3D, const float* shs,
@@ -1287,21 +1390,23 @@ int grpg_forward_frame(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_a
                        float* out_alpha_bg, float* out_color_obj, float* out_alpha_obj, int* radii, int debug,
                        void* hip_stream, const grpg_frame_epilogue* epilogue) {
   g_last_error.clear();
-  const int lay = layer_planes_given(out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj);
-  if (lay < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "layer planes: give all four or none");
-  if (lay && (!layer_background || (P > 0 && !layer_class)))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "a layered frame needs layer_class and layer_background");
-  if (lay && (unsigned)P >= (1u << 27))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "a layered frame needs P < 2^27 (the class travels in bit 27 of the point list)");
-  const bool planes = out_color && out_depth && out_alpha;
-  FrameEpilogue fe{};
-  if (epilogue) if (int rc = resolve_epilogue(epilogue, planes, &fe)) return rc;
   const LayerArgs la = {nullptr, layer_class, layer_background, out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj};
-  return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D,
-                      M, 0, background, width, height, means3D, shs, colors_precomp, nullptr, opacities, scales,
-                      scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
-                      tan_fovy, out_color, out_depth, out_alpha, nullptr, radii, debug, hip_stream, nullptr, 0,
-                      GRPG_FORWARD_NO_BACKWARD, nullptr, false, lay ? &la : nullptr, epilogue ? &fe : nullptr);
+  FrameRequest q;
+  if (int rc = check_layers(la, P, true, true, &q.layers)) return rc;
+  FrameEpilogue fe{};
+  if (epilogue) {
+    if (int rc = resolve_epilogue(epilogue, out_color && out_depth && out_alpha, &fe)) return rc;
+    q.epi = &fe;
+  }
+  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
+  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
+  q.P = P; q.D = D; q.M = M; q.background = background; q.width = width; q.height = height;
+  q.means3D = means3D; q.shs = shs; q.colors_precomp = colors_precomp; q.opacities = opacities;
+  q.scales = scales; q.scale_modifier = scale_modifier; q.rotations = rotations; q.cov3D_precomp = cov3D_precomp;
+  q.viewmatrix = viewmatrix; q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx;
+  q.tan_fovy = tan_fovy; q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha;
+  q.radii = radii; q.debug = debug; q.stream = (hipStream_t)hip_stream; q.flags = GRPG_FORWARD_NO_BACKWARD;
+  return forward_impl(q);
 }
 
 int grpg_forward_composed_frame(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_fn binning_alloc,
@@ -1317,24 +1422,23 @@ int grpg_forward_composed_frame(grpg_alloc_fn geometry_alloc, void* geometry_use
   g_last_error.clear();
   if (int rc = ensure_device()) return rc;
   long long P = 0;
-  if (int rc = check_segments(segments, num_segments, M, &P)) return rc;
-  if (M < 1 || M > 16 || D < 0 || D > 3 || (D + 1) * (D + 1) > M)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "SH degree needs (D+1)^2 <= M <= 16");
-  const int lay = layer_planes_given(out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj);
-  if (lay < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "layer planes: give all four or none");
-  if (lay && !layer_background) return fail(GRPG_ERR_INVALID_ARGUMENT, "a layered frame needs layer_background");
-  if (lay && P >= (1ll << 27))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "a layered frame needs P < 2^27 (the class travels in bit 27 of the point list)");
-  const bool planes = out_color && out_depth && out_alpha;
-  FrameEpilogue fe{};
-  if (epilogue) if (int rc = resolve_epilogue(epilogue, planes, &fe)) return rc;
+  if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
   const LayerArgs la = {segment_class, nullptr, layer_background, out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj};
-  return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc,
-                      image_user, (int)P, D, M, 0, background, width, height, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, scale_modifier, nullptr, nullptr, viewmatrix,
-                      projmatrix, cam_pos, tan_fovx, tan_fovy, out_color, out_depth, out_alpha, nullptr,
-                      radii, debug, hip_stream, segments, num_segments, GRPG_FORWARD_NO_BACKWARD, nullptr, false,
-                      lay ? &la : nullptr, epilogue ? &fe : nullptr);
+  FrameRequest q;
+  if (int rc = check_layers(la, P, false, true, &q.layers)) return rc;
+  FrameEpilogue fe{};
+  if (epilogue) {
+    if (int rc = resolve_epilogue(epilogue, out_color && out_depth && out_alpha, &fe)) return rc;
+    q.epi = &fe;
+  }
+  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
+  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
+  q.segs = segments; q.nseg = num_segments; q.P = (int)P; q.D = D; q.M = M; q.background = background;
+  q.width = width; q.height = height; q.scale_modifier = scale_modifier; q.viewmatrix = viewmatrix;
+  q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy;
+  q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha; q.radii = radii; q.debug = debug;
+  q.stream = (hipStream_t)hip_stream; q.flags = GRPG_FORWARD_NO_BACKWARD;
+  return forward_impl(q);
 }
 
 int grpg_forward_composed(grpg_alloc_fn geometry_alloc, void* geometry_user,
@@ -1363,10 +1467,8 @@ int grpg_backward_composed(const grpg_model_segment* segments, const grpg_model_
   g_last_error.clear();
   if (int rc = ensure_device()) return rc;
   long long Pll = 0;
-  if (int rc = check_segments(segments, num_segments, M, &Pll)) return rc;
+  if (int rc = check_composed_model(segments, num_segments, D, M, &Pll)) return rc;
   const int P = (int)Pll;
-  if (M < 1 || M > 16 || D < 0 || D > 3 || (D + 1) * (D + 1) > M)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "SH degree needs (D+1)^2 <= M <= 16");
   if (!grads || !geom_buffer || !binning_buffer || !image_buffer)
     return fail(GRPG_ERR_BAD_BUFFER, "NULL gradient table / state buffer");
   if (int rc = geom_check_backward(geom_buffer, P, (hipStream_t)hip_stream)) return rc;
@@ -1395,17 +1497,8 @@ int grpg_backward_composed(const grpg_model_segment* segments, const grpg_model_
   if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
   uint32_t start = 0;
   for (int i = 0; i < num_segments; i++) {
-    SegmentDev& d = stg->segs[i];
-    const grpg_model_segment& g = segments[i];
-    d.xyz = g.xyz; d.scaling = g.scaling; d.rotation = g.rotation; d.opacity = g.opacity;
-    d.fdc = g.features_dc; d.frest = g.features_rest; d.flip = g.flip; d.pad1 = nullptr;
-    d.start = start; d.count = (uint32_t)g.count;
-    d.fourier_dim = g.fourier_dim; d.rigid = g.rigid;
-    for (int k = 0; k < 4; k++) d.rot[k] = g.obj_rot[k];
-    for (int k = 0; k < 3; k++) d.trans[k] = g.obj_trans[k];
-    d.pad0 = 0.f;
-    for (int k = 0; k < MAX_FOURIER; k++) d.idft[k] = g.idft[k];
-    start += (uint32_t)g.count;
+    fill_segment(stg->segs[i], segments[i], start, nullptr);
+    start += (uint32_t)segments[i].count;
     stg->grads[i] = grads[i];
   }
   SegmentDev* seg_dev = (SegmentDev*)(geom_buffer + GL.seg_table);
@@ -1449,17 +1542,8 @@ int grpg_compose(const grpg_model_segment* segments, int num_segments, int M, fl
   std::vector<SegmentDev> host((size_t)num_segments);
   uint32_t start = 0;
   for (int i = 0; i < num_segments; i++) {
-    SegmentDev& d = host[(size_t)i];
-    const grpg_model_segment& g = segments[i];
-    d.xyz = g.xyz; d.scaling = g.scaling; d.rotation = g.rotation; d.opacity = g.opacity;
-    d.fdc = g.features_dc; d.frest = g.features_rest; d.flip = g.flip; d.pad1 = nullptr;
-    d.start = start; d.count = (uint32_t)g.count;
-    d.fourier_dim = g.fourier_dim; d.rigid = g.rigid;
-    for (int k = 0; k < 4; k++) d.rot[k] = g.obj_rot[k];
-    for (int k = 0; k < 3; k++) d.trans[k] = g.obj_trans[k];
-    d.pad0 = 0.f;
-    for (int k = 0; k < MAX_FOURIER; k++) d.idft[k] = g.idft[k];
-    start += (uint32_t)g.count;
+    fill_segment(host[(size_t)i], segments[i], start, nullptr);
+    start += (uint32_t)segments[i].count;
   }
   SegmentDev* dev_tab = nullptr;
   HIP_TRY(hipMalloc((void**)&dev_tab, sizeof(SegmentDev) * host.size()));
