@@ -33,7 +33,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .rasterizer import GaussianRasterizationSettings, _C
+from .rasterizer import GaussianRasterizationSettings, _C, _frame_result, _layers_result, _or_empty, _white
 
 MAX_FOURIER = 8     # GRPG_MAX_FOURIER
 
@@ -159,6 +159,13 @@ def _pack(models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]]):
     return lists, pose_t, idft_t
 
 
+def _object_flags(object_models):
+    """uint8 [n] on the host, 1 = the model belongs to the object layer; empty: every posed model (actor) does."""
+    if object_models is None:
+        return torch.empty(0, dtype=torch.uint8)
+    return torch.tensor([1 if f else 0 for f in object_models], dtype=torch.uint8)
+
+
 def compose(models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]]):
     """The composition alone: (means3D [P,3], scales [P,3], rotations [P,4], opacity [P,1],
     shs [P,M,3]) -- what get_xyz / get_scaling / get_rotation / get_opacity / get_features of the
@@ -226,20 +233,15 @@ class ComposedRasterizer(nn.Module):
         every plane is bit-identical to that call on ``compose(models, poses)``'s output."""
         rs = self.raster_settings
         lists, pose_t, idft_t = _pack(models, poses)
-        dev = models[0].xyz.device
         if layer_bg is None:
-            layer_bg = torch.ones(3, dtype=torch.float32, device=dev)
-        flags = torch.empty(0, dtype=torch.uint8) if object_models is None else \
-            torch.tensor([1 if f else 0 for f in object_models], dtype=torch.uint8)
+            layer_bg = _white(models[0].xyz.device)
         with torch.no_grad():
-            (num_rendered, color, depth, alpha, radii, color_bg, alpha_bg, color_obj,
-             alpha_obj) = _C.rasterize_gaussians_composed_layers(
-                rs.bg, layer_bg, flags, *lists, pose_t, idft_t, rs.scale_modifier, rs.viewmatrix, rs.projmatrix,
-                rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.sh_degree, rs.campos, rs.debug)
-        self.num_rendered = num_rendered
-        return {"color": color, "radii": radii, "depth": depth, "alpha": alpha,
-                "color_background": color_bg, "alpha_background": alpha_bg,
-                "color_object": color_obj, "alpha_object": alpha_obj}
+            out = _C.rasterize_gaussians_composed_layers(
+                rs.bg, layer_bg, _object_flags(object_models), *lists, pose_t, idft_t, rs.scale_modifier,
+                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.sh_degree,
+                rs.campos, rs.debug)
+        self.num_rendered = out[0]
+        return _layers_result(out)
 
     def forward_frame(self, models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]], *,
                       sky_cube=None, ray_matrix=None, sky_fill=0.0, clamp=True, planes=False, rgb8=True,
@@ -257,30 +259,17 @@ class ComposedRasterizer(nn.Module):
         ``alpha``, with ``layers=True`` the four layer planes; ``radii``, ``num_rendered``."""
         rs = self.raster_settings
         lists, pose_t, idft_t = _pack(models, poses)
-        dev = models[0].xyz.device
-        e = torch.Tensor([])
         if layers and layer_bg is None:
-            layer_bg = torch.ones(3, dtype=torch.float32, device=dev)
-        flags = torch.empty(0, dtype=torch.uint8) if object_models is None else \
-            torch.tensor([1 if f else 0 for f in object_models], dtype=torch.uint8)
+            layer_bg = _white(models[0].xyz.device)
+        layer_bg, sky_cube, ray_matrix = _or_empty(layer_bg, sky_cube, ray_matrix)
         with torch.no_grad():
-            (n, frame, color, depth, alpha, radii, color_bg, alpha_bg, color_obj,
-             alpha_obj) = _C.rasterize_gaussians_composed_frame(
-                rs.bg, e if layer_bg is None else layer_bg, flags, bool(layers), *lists, pose_t, idft_t,
+            ret = _C.rasterize_gaussians_composed_frame(
+                rs.bg, layer_bg, _object_flags(object_models), bool(layers), *lists, pose_t, idft_t,
                 rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
-                rs.image_width, rs.sh_degree, rs.campos, rs.debug, e if sky_cube is None else sky_cube,
-                e if ray_matrix is None else ray_matrix, float(sky_fill), bool(clamp), bool(planes), bool(rgb8),
-                bool(truncate), out)
-        self.num_rendered = n
-        res = {"num_rendered": n, "radii": radii}
-        if rgb8:
-            res["rgb8"] = frame
-        if planes:
-            res.update(rgb=color, depth=depth, alpha=alpha)
-        if layers:
-            res.update(color_background=color_bg, alpha_background=alpha_bg, color_object=color_obj,
-                       alpha_object=alpha_obj)
-        return res
+                rs.image_width, rs.sh_degree, rs.campos, rs.debug, sky_cube, ray_matrix, float(sky_fill), bool(clamp),
+                bool(planes), bool(rgb8), bool(truncate), out)
+        self.num_rendered = ret[0]
+        return _frame_result(ret, rgb8, planes, layers)
 
     def forward(self, models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]], means2D=None):
         rs = self.raster_settings

@@ -56,6 +56,178 @@ void require_device(const torch::Tensor& means3D) {
                            "): " + grpg_last_error());
 }
 
+// ---- the pieces every forward binding is made of: entry checks -> pointers -> outputs -> one call -> tuple ----
+
+// entry checks of the flat bindings, in this order: dims, device, dtype
+void check_means3D(const torch::Tensor& means3D) {
+  if (means3D.ndimension() != 2 || means3D.size(1) != 3) {
+    AT_ERROR("means3D must have dimensions (num_points, 3)");   // rasterize_points.cu:58-60
+  }
+  require_device(means3D);
+  TORCH_CHECK(means3D.scalar_type() == torch::kFloat32, "means3D must be float32");
+}
+
+// The camera of a frame.  Two steps, because the checks run in the order of the reference's argument list and
+// the flat bindings look at the model's tensors between the background colours and the matrices.
+enum class LayerBg { kIfLayered, kAlways };
+struct CameraPtrs {
+  const float *bg = nullptr, *layer_bg = nullptr, *view = nullptr, *proj = nullptr, *pos = nullptr;
+  torch::Tensor keep[5];
+  CameraPtrs(const torch::Tensor& like, const torch::Tensor& background, const torch::Tensor* layer_background) {
+    bg = fptr(background, like, "background", keep[0]);
+    if (layer_background) layer_bg = fptr(*layer_background, like, "layer_background", keep[1]);
+  }
+  void pose(const torch::Tensor& like, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
+            const torch::Tensor& campos) {
+    view = fptr(viewmatrix, like, "viewmatrix", keep[2]);
+    proj = fptr(projmatrix, like, "projmatrix", keep[3]);
+    pos = fptr(campos, like, "campos", keep[4]);
+  }
+  // forward only (the backward takes what its forward took)
+  void require(const LayerBg mode, const bool layered) const {
+    if (mode == LayerBg::kAlways) {
+      TORCH_CHECK(bg && layer_bg && view && proj && pos, "bg/layer_bg/viewmatrix/projmatrix/campos must be non-empty");
+    } else {
+      TORCH_CHECK(bg && view && proj && pos, "bg/viewmatrix/projmatrix/campos must be non-empty");
+      TORCH_CHECK(!layered || layer_bg, "layer_background must be non-empty in a layered frame");
+    }
+  }
+};
+
+// The flat model of rasterize_gaussians (pack_segments below is the composed counterpart).
+struct FlatModelPtrs {
+  const float *means, *sh, *colors, *semantics = nullptr, *opacity, *scales, *rotations, *cov3D;
+  int P, M = 0;
+  torch::Tensor keep[8];
+};
+FlatModelPtrs flat_model_ptrs(const torch::Tensor& means3D, const torch::Tensor& sh, const torch::Tensor& colors,
+                              const torch::Tensor* semantics, const torch::Tensor& opacity,
+                              const torch::Tensor& scales, const torch::Tensor& rotations,
+                              const torch::Tensor& cov3D_precomp) {
+  FlatModelPtrs g;
+  g.P = means3D.size(0);
+  if (sh.size(0) != 0) g.M = sh.size(1);   // rasterize_points.cu:88-92
+  g.means = fptr(means3D, means3D, "means3D", g.keep[0]);
+  g.sh = fptr(sh, means3D, "sh", g.keep[1]);
+  g.colors = fptr(colors, means3D, "colors_precomp", g.keep[2]);
+  if (semantics) g.semantics = fptr(*semantics, means3D, "semantics", g.keep[3]);
+  g.opacity = fptr(opacity, means3D, "opacities", g.keep[4]);
+  g.scales = fptr(scales, means3D, "scales", g.keep[5]);
+  g.rotations = fptr(rotations, means3D, "rotations", g.keep[6]);
+  g.cov3D = fptr(cov3D_precomp, means3D, "cov3D_precomp", g.keep[7]);
+  return g;
+}
+
+// layer_class: uint8 / bool [P] on the device, != 0 = object; NULL for an empty model
+const unsigned char* layer_class_ptr(const torch::Tensor& layer_class, const torch::Tensor& means3D,
+                                     torch::Tensor& keep) {
+  const int64_t P = means3D.size(0);
+  TORCH_CHECK(layer_class.numel() == P && layer_class.device() == means3D.device() &&
+                  (layer_class.scalar_type() == torch::kUInt8 || layer_class.scalar_type() == torch::kBool),
+              "layer_class must be a uint8 / bool tensor of P elements on the device of means3D");
+  keep = layer_class.contiguous();
+  return P > 0 ? (const unsigned char*)keep.data_ptr() : nullptr;
+}
+
+// object_model: uint8 / bool [n] on the HOST, != 0 = the model belongs to the object layer; empty (NULL): actors = objects
+const unsigned char* object_model_ptr(const torch::Tensor& object_model, const size_t num_models, torch::Tensor& keep) {
+  if (object_model.numel() == 0) return nullptr;
+  TORCH_CHECK(object_model.numel() == (int64_t)num_models && !object_model.is_cuda() &&
+                  (object_model.scalar_type() == torch::kUInt8 || object_model.scalar_type() == torch::kBool),
+              "object_model must be a uint8 / bool HOST tensor with one element per model");
+  keep = object_model.contiguous();
+  return (const unsigned char*)keep.data_ptr();
+}
+
+// returns (num_rendered, rgb8, color, depth, alpha, radii, color_bg, alpha_bg, color_obj, alpha_obj); tensors that
+// were not asked for are empty
+typedef std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+                   torch::Tensor, torch::Tensor, torch::Tensor> FrameResult;
+
+// What a forward call writes: the three private blobs (grown through resize_blob), radii and the planes.  A plane
+// that was not asked for is an empty [0] tensor and its pointer is NULL; so are the semantic plane's pointer at
+// S == 0 and the radii's at P == 0 (the composition refuses empty models: never there).
+struct ForwardOutputs {
+  torch::Tensor geom, binning, img, radii, color, depth, alpha, semantic, color_bg, alpha_bg, color_obj, alpha_obj;
+  float *p_color, *p_depth, *p_alpha, *p_semantic = nullptr, *p_color_bg, *p_alpha_bg, *p_color_obj, *p_alpha_obj;
+  int* p_radii;
+
+  ForwardOutputs(const torch::Tensor& like, const int64_t P, const int H, const int W, const c10::optional<int> S,
+                 const bool want_planes, const bool layered) {
+    const auto fo = like.options().dtype(torch::kFloat32);
+    // every element of these planes is written by the library: no zero-fill pass needed
+    auto plane = [&](const bool wanted, const int channels, float*& p) {
+      torch::Tensor t = wanted ? torch::empty({channels, H, W}, fo) : torch::empty({0}, fo);
+      p = wanted ? t.data_ptr<float>() : nullptr;
+      return t;
+    };
+    color = plane(want_planes, GRPG_NUM_CHANNELS, p_color);
+    depth = plane(want_planes, 1, p_depth);
+    alpha = plane(want_planes, 1, p_alpha);
+    if (S.has_value()) {
+      semantic = torch::empty({*S, H, W}, fo);
+      if (*S > 0) p_semantic = semantic.data_ptr<float>();
+    }
+    color_bg = plane(layered, GRPG_NUM_CHANNELS, p_color_bg);
+    alpha_bg = plane(layered, 1, p_alpha_bg);
+    color_obj = plane(layered, GRPG_NUM_CHANNELS, p_color_obj);
+    alpha_obj = plane(layered, 1, p_alpha_obj);
+    radii = torch::empty({P}, like.options().dtype(torch::kInt32));
+    p_radii = P > 0 ? radii.data_ptr<int>() : nullptr;
+    const auto byte_opts = like.options().dtype(torch::kByte);
+    geom = torch::empty({0}, byte_opts);
+    binning = torch::empty({0}, byte_opts);
+    img = torch::empty({0}, byte_opts);
+  }
+  // rasterize_gaussians (rasterize_points.cu:35-124)
+  auto flat(const int n) const { return std::make_tuple(n, color, depth, alpha, semantic, radii, geom, binning, img); }
+  auto composed(const int n) const { return std::make_tuple(n, color, depth, alpha, radii, geom, binning, img); }
+  auto layers(const int n) const {
+    return std::make_tuple(n, color, depth, alpha, radii, color_bg, alpha_bg, color_obj, alpha_obj);
+  }
+  FrameResult frame(const int n, const torch::Tensor& rgb8) const {
+    return std::make_tuple(n, rgb8, color, depth, alpha, radii, color_bg, alpha_bg, color_obj, alpha_obj);
+  }
+};
+
+// What a backward call gets back from its forward -- radii and the three blobs -- and the upstream gradients of
+// the planes.
+struct SavedState {
+  const float *dcolor, *ddepth, *dalpha, *dsemantic = nullptr;
+  int* radii;
+  char *geom, *binning, *img;
+  torch::Tensor keep[8];
+  SavedState(const torch::Tensor& like, const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_depth,
+             const torch::Tensor& dL_dout_alpha, const torch::Tensor* dL_dout_semantic, const torch::Tensor& radii_in,
+             const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer) {
+    dcolor = fptr(dL_dout_color, like, "dL_dout_color", keep[0]);
+    ddepth = fptr(dL_dout_depth, like, "dL_dout_depth", keep[1]);
+    dalpha = fptr(dL_dout_alpha, like, "dL_dout_alpha", keep[2]);
+    if (dL_dout_semantic) dsemantic = fptr(*dL_dout_semantic, like, "dL_dout_semantic", keep[3]);
+    TORCH_CHECK(radii_in.scalar_type() == torch::kInt32 && radii_in.device() == like.device(),
+                "radii must be int32 on the device");
+    radii = (keep[4] = radii_in.contiguous()).data_ptr<int>();
+    geom = reinterpret_cast<char*>((keep[5] = geomBuffer.contiguous()).data_ptr());
+    binning = reinterpret_cast<char*>((keep[6] = binningBuffer.contiguous()).data_ptr());
+    img = reinterpret_cast<char*>((keep[7] = imageBuffer.contiguous()).data_ptr());
+  }
+};
+
+// One forward call of the C ABI on the current stream.  The call blocks once on the stream (num_rendered
+// read-back): let other Python threads drive their own streams meanwhile.  The blob callbacks only touch ATen,
+// never Python objects.
+template <class Call>
+int run(const char* what, Call&& call) {
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  int rendered;
+  {
+    pybind11::gil_scoped_release nogil;
+    rendered = call((void*)stream);
+  }
+  if (rendered < 0) raise_abi_error(what, rendered);
+  return rendered;
+}
+
 }  // namespace
 
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
@@ -70,74 +242,30 @@ RasterizeGaussiansImpl(const unsigned flags, int* ticket /* non-NULL: deferred f
                    const int image_height, const int image_width, const torch::Tensor& sh,
                    const int degree, const torch::Tensor& campos, const bool prefiltered,
                    const bool debug) {
-  if (means3D.ndimension() != 2 || means3D.size(1) != 3) {
-    AT_ERROR("means3D must have dimensions (num_points, 3)");   // rasterize_points.cu:58-60
-  }
-  require_device(means3D);
-  TORCH_CHECK(means3D.scalar_type() == torch::kFloat32, "means3D must be float32");
+  check_means3D(means3D);
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D.device());
-  const int P = means3D.size(0);
   const int H = image_height, W = image_width;
   TORCH_CHECK(semantics.dim() == 2, "semantics must be [P,S]");
   const int S = semantics.size(1);
-
-  auto float_opts = means3D.options().dtype(torch::kFloat32);
-  // every element of these planes is written by the library: no zero-fill pass needed
-  torch::Tensor out_color = torch::empty({GRPG_NUM_CHANNELS, H, W}, float_opts);
-  torch::Tensor out_depth = torch::empty({1, H, W}, float_opts);
-  torch::Tensor out_alpha = torch::empty({1, H, W}, float_opts);
-  torch::Tensor out_semantic = torch::empty({S, H, W}, float_opts);
-  torch::Tensor radii = torch::empty({P}, means3D.options().dtype(torch::kInt32));
-  auto byte_opts = means3D.options().dtype(torch::kByte);
-  torch::Tensor geomBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor binningBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor imgBuffer = torch::empty({0}, byte_opts);
-
-  int M = 0;
-  if (sh.size(0) != 0) M = sh.size(1);   // rasterize_points.cu:88-92
-
-  torch::Tensor k_bg, k_means, k_sh, k_col, k_sem, k_op, k_sc, k_rot, k_cov, k_view, k_proj, k_cam;
-  const float* p_bg = fptr(background, means3D, "background", k_bg);
-  const float* p_means = fptr(means3D, means3D, "means3D", k_means);
-  const float* p_sh = fptr(sh, means3D, "sh", k_sh);
-  const float* p_col = fptr(colors, means3D, "colors_precomp", k_col);
-  const float* p_sem = fptr(semantics, means3D, "semantics", k_sem);
-  const float* p_op = fptr(opacity, means3D, "opacities", k_op);
-  const float* p_sc = fptr(scales, means3D, "scales", k_sc);
-  const float* p_rot = fptr(rotations, means3D, "rotations", k_rot);
-  const float* p_cov = fptr(cov3D_precomp, means3D, "cov3D_precomp", k_cov);
-  const float* p_view = fptr(viewmatrix, means3D, "viewmatrix", k_view);
-  const float* p_proj = fptr(projmatrix, means3D, "projmatrix", k_proj);
-  const float* p_cam = fptr(campos, means3D, "campos", k_cam);
-  TORCH_CHECK(p_bg && p_view && p_proj && p_cam, "bg/viewmatrix/projmatrix/campos must be non-empty");
-
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  float* p_out_color = out_color.data_ptr<float>();
-  float* p_out_depth = out_depth.data_ptr<float>();
-  float* p_out_alpha = out_alpha.data_ptr<float>();
-  float* p_out_sem = S > 0 ? out_semantic.data_ptr<float>() : nullptr;
-  int* p_radii = P > 0 ? radii.data_ptr<int>() : nullptr;
-  int rendered;
-  {
-    // The call blocks once on the stream (num_rendered read-back): let other Python threads drive
-    // their own streams meanwhile.  The blob callbacks only touch ATen, never Python objects.
-    pybind11::gil_scoped_release nogil;
+  CameraPtrs cam(means3D, background, nullptr);
+  const FlatModelPtrs g = flat_model_ptrs(means3D, sh, colors, &semantics, opacity, scales, rotations, cov3D_precomp);
+  cam.pose(means3D, viewmatrix, projmatrix, campos);
+  cam.require(LayerBg::kIfLayered, false);
+  ForwardOutputs o(means3D, g.P, H, W, S, true, false);
+  const int rendered = run("grpg_forward", [&](void* stream) {
     if (ticket)
-      rendered = grpg_forward_deferred(
-          resize_blob, &geomBuffer, resize_blob, &binningBuffer, resize_blob, &imgBuffer, P, degree,
-          M, S, p_bg, W, H, p_means, p_sh, p_col, p_sem, p_op, p_sc, scale_modifier, p_rot, p_cov,
-          p_view, p_proj, p_cam, tan_fovx, tan_fovy, prefiltered ? 1 : 0, p_out_color, p_out_depth,
-          p_out_alpha, p_out_sem, p_radii, debug ? 1 : 0, (void*)stream, flags, ticket);
-    else
-      rendered = grpg_forward_flags(
-          resize_blob, &geomBuffer, resize_blob, &binningBuffer, resize_blob, &imgBuffer, P, degree,
-          M, S, p_bg, W, H, p_means, p_sh, p_col, p_sem, p_op, p_sc, scale_modifier, p_rot, p_cov,
-          p_view, p_proj, p_cam, tan_fovx, tan_fovy, prefiltered ? 1 : 0, p_out_color, p_out_depth,
-          p_out_alpha, p_out_sem, p_radii, debug ? 1 : 0, (void*)stream, flags);
-  }
-  if (rendered < 0) raise_abi_error("grpg_forward", rendered);
-  return std::make_tuple(rendered, out_color, out_depth, out_alpha, out_semantic, radii,
-                         geomBuffer, binningBuffer, imgBuffer);
+      return grpg_forward_deferred(
+          resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, g.P, degree, g.M, S, cam.bg, W, H,
+          g.means, g.sh, g.colors, g.semantics, g.opacity, g.scales, scale_modifier, g.rotations, g.cov3D, cam.view,
+          cam.proj, cam.pos, tan_fovx, tan_fovy, prefiltered ? 1 : 0, o.p_color, o.p_depth, o.p_alpha, o.p_semantic,
+          o.p_radii, debug ? 1 : 0, stream, flags, ticket);
+    return grpg_forward_flags(
+        resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, g.P, degree, g.M, S, cam.bg, W, H,
+        g.means, g.sh, g.colors, g.semantics, g.opacity, g.scales, scale_modifier, g.rotations, g.cov3D, cam.view,
+        cam.proj, cam.pos, tan_fovx, tan_fovy, prefiltered ? 1 : 0, o.p_color, o.p_depth, o.p_alpha, o.p_semantic,
+        o.p_radii, debug ? 1 : 0, stream, flags);
+  });
+  return o.flat(rendered);
 }
 
 #define GRPG_RASTERIZE_ARGS                                                                        \
@@ -180,55 +308,24 @@ RasterizeGaussiansLayers(const torch::Tensor& background, const torch::Tensor& l
                          const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
                          const int image_height, const int image_width, const torch::Tensor& sh,
                          const int degree, const torch::Tensor& campos, const bool debug) {
-  if (means3D.ndimension() != 2 || means3D.size(1) != 3) AT_ERROR("means3D must have dimensions (num_points, 3)");
-  require_device(means3D);
-  TORCH_CHECK(means3D.scalar_type() == torch::kFloat32, "means3D must be float32");
+  check_means3D(means3D);
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D.device());
-  const int P = means3D.size(0);
   const int H = image_height, W = image_width;
-  TORCH_CHECK(layer_class.numel() == P && layer_class.device() == means3D.device() &&
-                  (layer_class.scalar_type() == torch::kUInt8 || layer_class.scalar_type() == torch::kBool),
-              "layer_class must be a uint8 / bool tensor of P elements on the device of means3D");
-  const torch::Tensor k_cls = layer_class.contiguous();
-  auto fo = means3D.options().dtype(torch::kFloat32);
-  torch::Tensor out_color = torch::empty({GRPG_NUM_CHANNELS, H, W}, fo), out_depth = torch::empty({1, H, W}, fo);
-  torch::Tensor out_alpha = torch::empty({1, H, W}, fo);
-  torch::Tensor color_bg = torch::empty({GRPG_NUM_CHANNELS, H, W}, fo), alpha_bg = torch::empty({1, H, W}, fo);
-  torch::Tensor color_obj = torch::empty({GRPG_NUM_CHANNELS, H, W}, fo), alpha_obj = torch::empty({1, H, W}, fo);
-  torch::Tensor radii = torch::empty({P}, means3D.options().dtype(torch::kInt32));
-  auto byte_opts = means3D.options().dtype(torch::kByte);
-  torch::Tensor geomBuffer = torch::empty({0}, byte_opts), binningBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor imgBuffer = torch::empty({0}, byte_opts);
-  int M = 0;
-  if (sh.size(0) != 0) M = sh.size(1);
-  torch::Tensor k_bg, k_lbg, k_means, k_sh, k_col, k_op, k_sc, k_rot, k_cov, k_view, k_proj, k_cam;
-  const float* p_bg = fptr(background, means3D, "background", k_bg);
-  const float* p_lbg = fptr(layer_background, means3D, "layer_background", k_lbg);
-  const float* p_means = fptr(means3D, means3D, "means3D", k_means);
-  const float* p_sh = fptr(sh, means3D, "sh", k_sh);
-  const float* p_col = fptr(colors, means3D, "colors_precomp", k_col);
-  const float* p_op = fptr(opacity, means3D, "opacities", k_op);
-  const float* p_sc = fptr(scales, means3D, "scales", k_sc);
-  const float* p_rot = fptr(rotations, means3D, "rotations", k_rot);
-  const float* p_cov = fptr(cov3D_precomp, means3D, "cov3D_precomp", k_cov);
-  const float* p_view = fptr(viewmatrix, means3D, "viewmatrix", k_view);
-  const float* p_proj = fptr(projmatrix, means3D, "projmatrix", k_proj);
-  const float* p_cam = fptr(campos, means3D, "campos", k_cam);
-  TORCH_CHECK(p_bg && p_lbg && p_view && p_proj && p_cam, "bg/layer_bg/viewmatrix/projmatrix/campos must be non-empty");
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int rendered;
-  {
-    pybind11::gil_scoped_release nogil;
-    rendered = grpg_forward_layers(
-        resize_blob, &geomBuffer, resize_blob, &binningBuffer, resize_blob, &imgBuffer, P, degree, M, p_bg, W, H,
-        p_means, p_sh, p_col, p_op, p_sc, scale_modifier, p_rot, p_cov, p_view, p_proj, p_cam, tan_fovx, tan_fovy,
-        P > 0 ? (const unsigned char*)k_cls.data_ptr() : nullptr, p_lbg, out_color.data_ptr<float>(),
-        out_depth.data_ptr<float>(), out_alpha.data_ptr<float>(), color_bg.data_ptr<float>(),
-        alpha_bg.data_ptr<float>(), color_obj.data_ptr<float>(), alpha_obj.data_ptr<float>(),
-        P > 0 ? radii.data_ptr<int>() : nullptr, debug ? 1 : 0, (void*)stream);
-  }
-  if (rendered < 0) raise_abi_error("grpg_forward_layers", rendered);
-  return std::make_tuple(rendered, out_color, out_depth, out_alpha, radii, color_bg, alpha_bg, color_obj, alpha_obj);
+  torch::Tensor k_cls;
+  const unsigned char* p_cls = layer_class_ptr(layer_class, means3D, k_cls);
+  CameraPtrs cam(means3D, background, &layer_background);
+  const FlatModelPtrs g = flat_model_ptrs(means3D, sh, colors, nullptr, opacity, scales, rotations, cov3D_precomp);
+  cam.pose(means3D, viewmatrix, projmatrix, campos);
+  cam.require(LayerBg::kAlways, true);
+  ForwardOutputs o(means3D, g.P, H, W, c10::nullopt, true, true);
+  const int rendered = run("grpg_forward_layers", [&](void* stream) {
+    return grpg_forward_layers(
+        resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, g.P, degree, g.M, cam.bg, W, H, g.means,
+        g.sh, g.colors, g.opacity, g.scales, scale_modifier, g.rotations, g.cov3D, cam.view, cam.proj, cam.pos,
+        tan_fovx, tan_fovy, p_cls, cam.layer_bg, o.p_color, o.p_depth, o.p_alpha, o.p_color_bg, o.p_alpha_bg,
+        o.p_color_obj, o.p_alpha_obj, o.p_radii, debug ? 1 : 0, stream);
+  });
+  return o.layers(rendered);
 }
 
 // ---- the frame epilogue (grpg_forward_frame / grpg_forward_composed_frame, ABI 6; host destination: ABI 7) ----
@@ -276,11 +373,7 @@ static void make_epilogue(EpilogueArgs& a, const torch::Tensor& like, const torc
     a.rgb8 = torch::empty({0}, like.options().dtype(torch::kByte));
   }
 }
-
-// returns (num_rendered, rgb8, color, depth, alpha, radii, color_bg, alpha_bg, color_obj, alpha_obj); tensors that
-// were not asked for are empty
-typedef std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
-                   torch::Tensor, torch::Tensor, torch::Tensor> FrameResult;
+static const char* const kFrameAsksForNothing = "forward_frame: ask for the float planes, the rgb8 frame, or both";
 
 FrameResult RasterizeGaussiansFrame(
     const torch::Tensor& background, const torch::Tensor& layer_background, const torch::Tensor& layer_class,
@@ -291,70 +384,28 @@ FrameResult RasterizeGaussiansFrame(
     const torch::Tensor& sh, const int degree, const torch::Tensor& campos, const bool debug,
     const torch::Tensor& sky_cube, const torch::Tensor& ray_matrix, const float sky_fill, const bool clamp,
     const bool want_planes, const bool want_rgb8, const bool truncate, const c10::optional<torch::Tensor>& out_rgb8) {
-  if (means3D.ndimension() != 2 || means3D.size(1) != 3) AT_ERROR("means3D must have dimensions (num_points, 3)");
-  require_device(means3D);
-  TORCH_CHECK(means3D.scalar_type() == torch::kFloat32, "means3D must be float32");
-  TORCH_CHECK(want_planes || want_rgb8, "forward_frame: ask for the float planes, the rgb8 frame, or both");
+  check_means3D(means3D);
+  TORCH_CHECK(want_planes || want_rgb8, kFrameAsksForNothing);
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D.device());
-  const int P = means3D.size(0);
   const int H = image_height, W = image_width;
   const bool layered = layer_class.defined() && layer_class.numel() != 0;
   torch::Tensor k_cls;
-  if (layered) {
-    TORCH_CHECK(layer_class.numel() == P && layer_class.device() == means3D.device() &&
-                    (layer_class.scalar_type() == torch::kUInt8 || layer_class.scalar_type() == torch::kBool),
-                "layer_class must be a uint8 / bool tensor of P elements on the device of means3D");
-    k_cls = layer_class.contiguous();
-  }
-  auto fo = means3D.options().dtype(torch::kFloat32);
-  auto none = [&]() { return torch::empty({0}, fo); };
-  torch::Tensor out_color = want_planes ? torch::empty({GRPG_NUM_CHANNELS, H, W}, fo) : none();
-  torch::Tensor out_depth = want_planes ? torch::empty({1, H, W}, fo) : none();
-  torch::Tensor out_alpha = want_planes ? torch::empty({1, H, W}, fo) : none();
-  torch::Tensor color_bg = layered ? torch::empty({GRPG_NUM_CHANNELS, H, W}, fo) : none();
-  torch::Tensor alpha_bg = layered ? torch::empty({1, H, W}, fo) : none();
-  torch::Tensor color_obj = layered ? torch::empty({GRPG_NUM_CHANNELS, H, W}, fo) : none();
-  torch::Tensor alpha_obj = layered ? torch::empty({1, H, W}, fo) : none();
-  torch::Tensor radii = torch::empty({P}, means3D.options().dtype(torch::kInt32));
-  auto byte_opts = means3D.options().dtype(torch::kByte);
-  torch::Tensor geomBuffer = torch::empty({0}, byte_opts), binningBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor imgBuffer = torch::empty({0}, byte_opts);
-  int M = 0;
-  if (sh.size(0) != 0) M = sh.size(1);
-  torch::Tensor k_bg, k_lbg, k_means, k_sh, k_col, k_op, k_sc, k_rot, k_cov, k_view, k_proj, k_cam;
-  const float* p_bg = fptr(background, means3D, "background", k_bg);
-  const float* p_lbg = fptr(layer_background, means3D, "layer_background", k_lbg);
-  const float* p_means = fptr(means3D, means3D, "means3D", k_means);
-  const float* p_sh = fptr(sh, means3D, "sh", k_sh);
-  const float* p_col = fptr(colors, means3D, "colors_precomp", k_col);
-  const float* p_op = fptr(opacity, means3D, "opacities", k_op);
-  const float* p_sc = fptr(scales, means3D, "scales", k_sc);
-  const float* p_rot = fptr(rotations, means3D, "rotations", k_rot);
-  const float* p_cov = fptr(cov3D_precomp, means3D, "cov3D_precomp", k_cov);
-  const float* p_view = fptr(viewmatrix, means3D, "viewmatrix", k_view);
-  const float* p_proj = fptr(projmatrix, means3D, "projmatrix", k_proj);
-  const float* p_cam = fptr(campos, means3D, "campos", k_cam);
-  TORCH_CHECK(p_bg && p_view && p_proj && p_cam, "bg/viewmatrix/projmatrix/campos must be non-empty");
-  TORCH_CHECK(!layered || p_lbg, "layer_background must be non-empty in a layered frame");
+  const unsigned char* p_cls = layered ? layer_class_ptr(layer_class, means3D, k_cls) : nullptr;
+  CameraPtrs cam(means3D, background, &layer_background);
+  const FlatModelPtrs g = flat_model_ptrs(means3D, sh, colors, nullptr, opacity, scales, rotations, cov3D_precomp);
+  cam.pose(means3D, viewmatrix, projmatrix, campos);
+  cam.require(LayerBg::kIfLayered, layered);
   EpilogueArgs ea;
   make_epilogue(ea, means3D, sky_cube, ray_matrix, sky_fill, clamp, want_rgb8, truncate, out_rgb8, H, W);
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int rendered;
-  {
-    pybind11::gil_scoped_release nogil;
-    rendered = grpg_forward_frame(
-        resize_blob, &geomBuffer, resize_blob, &binningBuffer, resize_blob, &imgBuffer, P, degree, M, p_bg, W, H,
-        p_means, p_sh, p_col, p_op, p_sc, scale_modifier, p_rot, p_cov, p_view, p_proj, p_cam, tan_fovx, tan_fovy,
-        (layered && P > 0) ? (const unsigned char*)k_cls.data_ptr() : nullptr, p_lbg,
-        want_planes ? out_color.data_ptr<float>() : nullptr, want_planes ? out_depth.data_ptr<float>() : nullptr,
-        want_planes ? out_alpha.data_ptr<float>() : nullptr, layered ? color_bg.data_ptr<float>() : nullptr,
-        layered ? alpha_bg.data_ptr<float>() : nullptr, layered ? color_obj.data_ptr<float>() : nullptr,
-        layered ? alpha_obj.data_ptr<float>() : nullptr, P > 0 ? radii.data_ptr<int>() : nullptr, debug ? 1 : 0,
-        (void*)stream, &ea.e);
-  }
-  if (rendered < 0) raise_abi_error("grpg_forward_frame", rendered);
-  return std::make_tuple(rendered, ea.rgb8, out_color, out_depth, out_alpha, radii, color_bg, alpha_bg, color_obj,
-                         alpha_obj);
+  ForwardOutputs o(means3D, g.P, H, W, c10::nullopt, want_planes, layered);
+  const int rendered = run("grpg_forward_frame", [&](void* stream) {
+    return grpg_forward_frame(
+        resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, g.P, degree, g.M, cam.bg, W, H, g.means,
+        g.sh, g.colors, g.opacity, g.scales, scale_modifier, g.rotations, g.cov3D, cam.view, cam.proj, cam.pos,
+        tan_fovx, tan_fovy, p_cls, cam.layer_bg, o.p_color, o.p_depth, o.p_alpha, o.p_color_bg, o.p_alpha_bg,
+        o.p_color_obj, o.p_alpha_obj, o.p_radii, debug ? 1 : 0, stream, &ea.e);
+  });
+  return o.frame(rendered, ea.rgb8);
 }
 
 // (ok, num_rendered): ok = 1 valid, 0 the frame must be rendered again, -1 not ready (wait = false)
@@ -429,34 +480,24 @@ RasterizeGaussiansBackwardImpl(const torch::Tensor& background, const torch::Ten
   torch::Tensor dL_dsemantic = torch::zeros({P, S}, o);
 
   if (P != 0) {
-    torch::Tensor k[16];
-    const float* p_bg = fptr(background, means3D, "background", k[0]);
-    const float* p_means = fptr(means3D, means3D, "means3D", k[1]);
-    const float* p_sh = fptr(sh, means3D, "sh", k[2]);
-    const float* p_col = fptr(colors, means3D, "colors_precomp", k[3]);
-    const float* p_sem = fptr(semantics, means3D, "semantics", k[4]);
-    const float* p_alpha = fptr(alphas, means3D, "alphas", k[5]);
-    const float* p_sc = fptr(scales, means3D, "scales", k[6]);
-    const float* p_rot = fptr(rotations, means3D, "rotations", k[7]);
-    const float* p_cov = fptr(cov3D_precomp, means3D, "cov3D_precomp", k[8]);
-    const float* p_view = fptr(viewmatrix, means3D, "viewmatrix", k[9]);
-    const float* p_proj = fptr(projmatrix, means3D, "projmatrix", k[10]);
-    const float* p_cam = fptr(campos, means3D, "campos", k[11]);
-    const float* g_col = fptr(dL_dout_color, means3D, "dL_dout_color", k[12]);
-    const float* g_dep = fptr(dL_dout_depth, means3D, "dL_dout_depth", k[13]);
-    const float* g_alp = fptr(dL_dout_alpha, means3D, "dL_dout_alpha", k[14]);
-    const float* g_sem = fptr(dL_dout_semantic, means3D, "dL_dout_semantic", k[15]);
-    TORCH_CHECK(radii.scalar_type() == torch::kInt32 && radii.device() == means3D.device(),
-                "radii must be int32 on the device");
-    torch::Tensor radii_c = radii.contiguous();
-    torch::Tensor gb = geomBuffer.contiguous(), bb = binningBuffer.contiguous(),
-                  ib = imageBuffer.contiguous();
+    CameraPtrs cam(means3D, background, nullptr);
+    torch::Tensor k[8];
+    const float* p_means = fptr(means3D, means3D, "means3D", k[0]);
+    const float* p_sh = fptr(sh, means3D, "sh", k[1]);
+    const float* p_col = fptr(colors, means3D, "colors_precomp", k[2]);
+    const float* p_sem = fptr(semantics, means3D, "semantics", k[3]);
+    const float* p_alpha = fptr(alphas, means3D, "alphas", k[4]);
+    const float* p_sc = fptr(scales, means3D, "scales", k[5]);
+    const float* p_rot = fptr(rotations, means3D, "rotations", k[6]);
+    const float* p_cov = fptr(cov3D_precomp, means3D, "cov3D_precomp", k[7]);
+    cam.pose(means3D, viewmatrix, projmatrix, campos);
+    const SavedState sv(means3D, dL_dout_color, dL_dout_depth, dL_dout_alpha, &dL_dout_semantic, radii, geomBuffer,
+                        binningBuffer, imageBuffer);
     hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
     const int rc = grpg_backward(
-        P, degree, M, R, S, p_bg, W, H, p_means, p_sh, p_col, p_sem, p_alpha, p_sc, scale_modifier,
-        p_rot, p_cov, p_view, p_proj, p_cam, tan_fovx, tan_fovy, radii_c.data_ptr<int>(),
-        reinterpret_cast<char*>(gb.data_ptr()), reinterpret_cast<char*>(bb.data_ptr()),
-        reinterpret_cast<char*>(ib.data_ptr()), g_col, g_dep, g_alp, g_sem,
+        P, degree, M, R, S, cam.bg, W, H, p_means, p_sh, p_col, p_sem, p_alpha, p_sc, scale_modifier,
+        p_rot, p_cov, cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy, sv.radii, sv.geom, sv.binning, sv.img,
+        sv.dcolor, sv.ddepth, sv.dalpha, sv.dsemantic,
         dL_dmeans2D.data_ptr<float>(), /*dL_dconic=*/nullptr, dL_dopacity.data_ptr<float>(),
         want_colors ? dL_dcolors.data_ptr<float>() : nullptr, /*dL_ddepth=*/nullptr,
         dL_dmeans3D.data_ptr<float>(), want_cov ? dL_dcov3D.data_ptr<float>() : nullptr,
@@ -647,34 +688,17 @@ RasterizeGaussiansComposed(const torch::Tensor& background, const std::vector<to
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
   const int H = image_height, W = image_width;
-  auto float_opts = like.options().dtype(torch::kFloat32);
-  torch::Tensor out_color = torch::empty({GRPG_NUM_CHANNELS, H, W}, float_opts);
-  torch::Tensor out_depth = torch::empty({1, H, W}, float_opts);
-  torch::Tensor out_alpha = torch::empty({1, H, W}, float_opts);
-  torch::Tensor radii = torch::empty({pk.P}, like.options().dtype(torch::kInt32));
-  auto byte_opts = like.options().dtype(torch::kByte);
-  torch::Tensor geomBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor binningBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor imgBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor k_bg, k_view, k_proj, k_cam;
-  const float* p_bg = fptr(background, like, "background", k_bg);
-  const float* p_view = fptr(viewmatrix, like, "viewmatrix", k_view);
-  const float* p_proj = fptr(projmatrix, like, "projmatrix", k_proj);
-  const float* p_cam = fptr(campos, like, "campos", k_cam);
-  TORCH_CHECK(p_bg && p_view && p_proj && p_cam, "bg/viewmatrix/projmatrix/campos must be non-empty");
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int rendered;
-  {
-    pybind11::gil_scoped_release nogil;
-    rendered = grpg_forward_composed_flags(
-        resize_blob, &geomBuffer, resize_blob, &binningBuffer, resize_blob, &imgBuffer, pk.segs.data(),
-        (int)pk.segs.size(), degree, pk.M, p_bg, W, H, scale_modifier, p_view, p_proj, p_cam, tan_fovx,
-        tan_fovy, out_color.data_ptr<float>(), out_depth.data_ptr<float>(), out_alpha.data_ptr<float>(),
-        radii.data_ptr<int>(), debug ? 1 : 0, (void*)stream, for_backward ? 0u : GRPG_FORWARD_NO_BACKWARD);
-  }
-  if (rendered < 0) raise_abi_error("grpg_forward_composed", rendered);
-  return std::make_tuple(rendered, out_color, out_depth, out_alpha, radii, geomBuffer, binningBuffer,
-                         imgBuffer);
+  CameraPtrs cam(like, background, nullptr);
+  cam.pose(like, viewmatrix, projmatrix, campos);
+  cam.require(LayerBg::kIfLayered, false);
+  ForwardOutputs o(like, pk.P, H, W, c10::nullopt, true, false);
+  const int rendered = run("grpg_forward_composed", [&](void* stream) {
+    return grpg_forward_composed_flags(
+        resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, pk.segs.data(), (int)pk.segs.size(),
+        degree, pk.M, cam.bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy, o.p_color,
+        o.p_depth, o.p_alpha, o.p_radii, debug ? 1 : 0, stream, for_backward ? 0u : GRPG_FORWARD_NO_BACKWARD);
+  });
+  return o.composed(rendered);
 }
 
 // Composition + layered frame (grpg_forward_composed_layers): the reference's whole evaluation render of a frame --
@@ -700,44 +724,20 @@ RasterizeGaussiansComposedLayers(const torch::Tensor& background, const torch::T
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
   const int H = image_height, W = image_width;
-  const unsigned char* p_cls = nullptr;
   torch::Tensor k_cls;
-  if (object_model.numel() != 0) {
-    TORCH_CHECK(object_model.numel() == (int64_t)pk.segs.size() && !object_model.is_cuda() &&
-                    (object_model.scalar_type() == torch::kUInt8 || object_model.scalar_type() == torch::kBool),
-                "object_model must be a uint8 / bool HOST tensor with one element per model");
-    k_cls = object_model.contiguous();
-    p_cls = (const unsigned char*)k_cls.data_ptr();
-  }
-  auto fo = like.options().dtype(torch::kFloat32);
-  torch::Tensor out_color = torch::empty({GRPG_NUM_CHANNELS, H, W}, fo), out_depth = torch::empty({1, H, W}, fo);
-  torch::Tensor out_alpha = torch::empty({1, H, W}, fo);
-  torch::Tensor color_bg = torch::empty({GRPG_NUM_CHANNELS, H, W}, fo), alpha_bg = torch::empty({1, H, W}, fo);
-  torch::Tensor color_obj = torch::empty({GRPG_NUM_CHANNELS, H, W}, fo), alpha_obj = torch::empty({1, H, W}, fo);
-  torch::Tensor radii = torch::empty({pk.P}, like.options().dtype(torch::kInt32));
-  auto byte_opts = like.options().dtype(torch::kByte);
-  torch::Tensor geomBuffer = torch::empty({0}, byte_opts), binningBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor imgBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor k_bg, k_lbg, k_view, k_proj, k_cam;
-  const float* p_bg = fptr(background, like, "background", k_bg);
-  const float* p_lbg = fptr(layer_background, like, "layer_background", k_lbg);
-  const float* p_view = fptr(viewmatrix, like, "viewmatrix", k_view);
-  const float* p_proj = fptr(projmatrix, like, "projmatrix", k_proj);
-  const float* p_cam = fptr(campos, like, "campos", k_cam);
-  TORCH_CHECK(p_bg && p_lbg && p_view && p_proj && p_cam, "bg/layer_bg/viewmatrix/projmatrix/campos must be non-empty");
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int rendered;
-  {
-    pybind11::gil_scoped_release nogil;
-    rendered = grpg_forward_composed_layers(
-        resize_blob, &geomBuffer, resize_blob, &binningBuffer, resize_blob, &imgBuffer, pk.segs.data(),
-        (int)pk.segs.size(), p_cls, degree, pk.M, p_bg, p_lbg, W, H, scale_modifier, p_view, p_proj, p_cam, tan_fovx,
-        tan_fovy, out_color.data_ptr<float>(), out_depth.data_ptr<float>(), out_alpha.data_ptr<float>(),
-        color_bg.data_ptr<float>(), alpha_bg.data_ptr<float>(), color_obj.data_ptr<float>(),
-        alpha_obj.data_ptr<float>(), radii.data_ptr<int>(), debug ? 1 : 0, (void*)stream);
-  }
-  if (rendered < 0) raise_abi_error("grpg_forward_composed_layers", rendered);
-  return std::make_tuple(rendered, out_color, out_depth, out_alpha, radii, color_bg, alpha_bg, color_obj, alpha_obj);
+  const unsigned char* p_cls = object_model_ptr(object_model, pk.segs.size(), k_cls);
+  CameraPtrs cam(like, background, &layer_background);
+  cam.pose(like, viewmatrix, projmatrix, campos);
+  cam.require(LayerBg::kAlways, true);
+  ForwardOutputs o(like, pk.P, H, W, c10::nullopt, true, true);
+  const int rendered = run("grpg_forward_composed_layers", [&](void* stream) {
+    return grpg_forward_composed_layers(
+        resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, pk.segs.data(), (int)pk.segs.size(),
+        p_cls, degree, pk.M, cam.bg, cam.layer_bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx,
+        tan_fovy, o.p_color, o.p_depth, o.p_alpha, o.p_color_bg, o.p_alpha_bg, o.p_color_obj, o.p_alpha_obj,
+        o.p_radii, debug ? 1 : 0, stream);
+  });
+  return o.layers(rendered);
 }
 
 // The scene-graph frame as one call (grpg_forward_composed_frame): composition + op (+ layers) + sky + clamp + rgb8.
@@ -755,56 +755,24 @@ FrameResult RasterizeGaussiansComposedFrame(
   SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
-  TORCH_CHECK(want_planes || want_rgb8, "forward_frame: ask for the float planes, the rgb8 frame, or both");
+  TORCH_CHECK(want_planes || want_rgb8, kFrameAsksForNothing);
   const int H = image_height, W = image_width;
-  const unsigned char* p_cls = nullptr;
   torch::Tensor k_cls;
-  if (layered && object_model.numel() != 0) {
-    TORCH_CHECK(object_model.numel() == (int64_t)pk.segs.size() && !object_model.is_cuda() &&
-                    (object_model.scalar_type() == torch::kUInt8 || object_model.scalar_type() == torch::kBool),
-                "object_model must be a uint8 / bool HOST tensor with one element per model");
-    k_cls = object_model.contiguous();
-    p_cls = (const unsigned char*)k_cls.data_ptr();
-  }
-  auto fo = like.options().dtype(torch::kFloat32);
-  auto none = [&]() { return torch::empty({0}, fo); };
-  torch::Tensor out_color = want_planes ? torch::empty({GRPG_NUM_CHANNELS, H, W}, fo) : none();
-  torch::Tensor out_depth = want_planes ? torch::empty({1, H, W}, fo) : none();
-  torch::Tensor out_alpha = want_planes ? torch::empty({1, H, W}, fo) : none();
-  torch::Tensor color_bg = layered ? torch::empty({GRPG_NUM_CHANNELS, H, W}, fo) : none();
-  torch::Tensor alpha_bg = layered ? torch::empty({1, H, W}, fo) : none();
-  torch::Tensor color_obj = layered ? torch::empty({GRPG_NUM_CHANNELS, H, W}, fo) : none();
-  torch::Tensor alpha_obj = layered ? torch::empty({1, H, W}, fo) : none();
-  torch::Tensor radii = torch::empty({pk.P}, like.options().dtype(torch::kInt32));
-  auto byte_opts = like.options().dtype(torch::kByte);
-  torch::Tensor geomBuffer = torch::empty({0}, byte_opts), binningBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor imgBuffer = torch::empty({0}, byte_opts);
-  torch::Tensor k_bg, k_lbg, k_view, k_proj, k_cam;
-  const float* p_bg = fptr(background, like, "background", k_bg);
-  const float* p_lbg = fptr(layer_background, like, "layer_background", k_lbg);
-  const float* p_view = fptr(viewmatrix, like, "viewmatrix", k_view);
-  const float* p_proj = fptr(projmatrix, like, "projmatrix", k_proj);
-  const float* p_cam = fptr(campos, like, "campos", k_cam);
-  TORCH_CHECK(p_bg && p_view && p_proj && p_cam, "bg/viewmatrix/projmatrix/campos must be non-empty");
-  TORCH_CHECK(!layered || p_lbg, "layer_background must be non-empty in a layered frame");
+  const unsigned char* p_cls = layered ? object_model_ptr(object_model, pk.segs.size(), k_cls) : nullptr;
+  CameraPtrs cam(like, background, &layer_background);
+  cam.pose(like, viewmatrix, projmatrix, campos);
+  cam.require(LayerBg::kIfLayered, layered);
   EpilogueArgs ea;
   make_epilogue(ea, like, sky_cube, ray_matrix, sky_fill, clamp, want_rgb8, truncate, out_rgb8, H, W);
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int rendered;
-  {
-    pybind11::gil_scoped_release nogil;
-    rendered = grpg_forward_composed_frame(
-        resize_blob, &geomBuffer, resize_blob, &binningBuffer, resize_blob, &imgBuffer, pk.segs.data(),
-        (int)pk.segs.size(), p_cls, degree, pk.M, p_bg, p_lbg, W, H, scale_modifier, p_view, p_proj, p_cam, tan_fovx,
-        tan_fovy, want_planes ? out_color.data_ptr<float>() : nullptr,
-        want_planes ? out_depth.data_ptr<float>() : nullptr, want_planes ? out_alpha.data_ptr<float>() : nullptr,
-        layered ? color_bg.data_ptr<float>() : nullptr, layered ? alpha_bg.data_ptr<float>() : nullptr,
-        layered ? color_obj.data_ptr<float>() : nullptr, layered ? alpha_obj.data_ptr<float>() : nullptr,
-        radii.data_ptr<int>(), debug ? 1 : 0, (void*)stream, &ea.e);
-  }
-  if (rendered < 0) raise_abi_error("grpg_forward_composed_frame", rendered);
-  return std::make_tuple(rendered, ea.rgb8, out_color, out_depth, out_alpha, radii, color_bg, alpha_bg, color_obj,
-                         alpha_obj);
+  ForwardOutputs o(like, pk.P, H, W, c10::nullopt, want_planes, layered);
+  const int rendered = run("grpg_forward_composed_frame", [&](void* stream) {
+    return grpg_forward_composed_frame(
+        resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, pk.segs.data(), (int)pk.segs.size(),
+        p_cls, degree, pk.M, cam.bg, cam.layer_bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx,
+        tan_fovy, o.p_color, o.p_depth, o.p_alpha, o.p_color_bg, o.p_alpha_bg, o.p_color_obj, o.p_alpha_obj,
+        o.p_radii, debug ? 1 : 0, stream, &ea.e);
+  });
+  return o.frame(rendered, ea.rgb8);
 }
 
 // Training backward of the fused composition (grpg_backward_composed): gradients with respect to
@@ -846,25 +814,16 @@ RasterizeGaussiansComposedBackward(
   }
   torch::Tensor dL_dmeans2D = torch::empty({pk.P, 3}, o);
   torch::Tensor dL_dposes = torch::empty({(int64_t)n, 8}, o);
-  torch::Tensor k[7];
-  const float* p_bg = fptr(background, like, "background", k[0]);
-  const float* p_view = fptr(viewmatrix, like, "viewmatrix", k[1]);
-  const float* p_proj = fptr(projmatrix, like, "projmatrix", k[2]);
-  const float* p_cam = fptr(campos, like, "campos", k[3]);
-  const float* g_col = fptr(dL_dout_color, like, "dL_dout_color", k[4]);
-  const float* g_dep = fptr(dL_dout_depth, like, "dL_dout_depth", k[5]);
-  const float* g_alp = fptr(dL_dout_alpha, like, "dL_dout_alpha", k[6]);
+  CameraPtrs cam(like, background, nullptr);
+  cam.pose(like, viewmatrix, projmatrix, campos);
   torch::Tensor k_alpha;
   const float* p_alpha = fptr(alphas, like, "alphas", k_alpha);
-  TORCH_CHECK(radii.scalar_type() == torch::kInt32 && radii.device() == like.device(),
-              "radii must be int32 on the device");
-  torch::Tensor radii_c = radii.contiguous();
-  torch::Tensor gb = geomBuffer.contiguous(), bb = binningBuffer.contiguous(), ib = imageBuffer.contiguous();
+  const SavedState sv(like, dL_dout_color, dL_dout_depth, dL_dout_alpha, nullptr, radii, geomBuffer, binningBuffer,
+                      imageBuffer);
   hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   const int rc = grpg_backward_composed(
-      pk.segs.data(), gs.data(), (int)n, degree, pk.M, R, p_bg, W, H, scale_modifier, p_view, p_proj, p_cam,
-      tan_fovx, tan_fovy, radii_c.data_ptr<int>(), p_alpha, reinterpret_cast<char*>(gb.data_ptr()),
-      reinterpret_cast<char*>(bb.data_ptr()), reinterpret_cast<char*>(ib.data_ptr()), g_col, g_dep, g_alp,
+      pk.segs.data(), gs.data(), (int)n, degree, pk.M, R, cam.bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos,
+      tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img, sv.dcolor, sv.ddepth, sv.dalpha,
       dL_dmeans2D.data_ptr<float>(), dL_dposes.data_ptr<float>(), debug ? 1 : 0, (void*)stream);
   if (rc != GRPG_OK) raise_abi_error("grpg_backward_composed", rc);
   return std::make_tuple(g_xyz, g_scaling, g_rotation, g_opacity, g_fdc, g_frest, dL_dmeans2D, dL_dposes);
@@ -1409,3 +1368,4 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     if (grpg_set_binning_algorithm(alg) != GRPG_OK) raise_abi_error("grpg_set_binning_algorithm", -1);
   });
 }
+

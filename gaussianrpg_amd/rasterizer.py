@@ -26,6 +26,24 @@ def _snapshot(args):
     return tuple(a.cpu().clone() if isinstance(a, torch.Tensor) else a for a in args)
 
 
+def _call_debuggable(fn, call, dump_name, message):
+    """fn(*call); in debug mode (the last element of both argument tuples is rs.debug) a failing call leaves a
+    snapshot of its arguments behind, like the reference's wrapper (:86-96, :140-150)."""
+    if not call[-1]:
+        return fn(*call)
+    saved = _snapshot(call)
+    try:
+        return fn(*call)
+    except Exception:
+        torch.save(saved, dump_name)
+        print(message)
+        raise
+
+
+_FW_DUMP = ("snapshot_fw.dump", "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+_BW_DUMP = ("snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+
+
 class GaussianRasterizationSettings(NamedTuple):
     image_height: int
     image_width: int
@@ -41,6 +59,13 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
+def _forward_call(rs, means3D, sh, colors_precomp, semantics, opacities, scales, rotations, cov3Ds_precomp):
+    """The 20 arguments of _C.rasterize_gaussians / _eval / _eval_deferred, reference order (__init__.py:63-84)."""
+    return (rs.bg, means3D, colors_precomp, semantics, opacities, scales, rotations, rs.scale_modifier,
+            cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
+            rs.image_width, sh, rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """autograd bridge: forward -> _C.rasterize_gaussians (20 args, reference order
     __init__.py:63-84), backward -> _C.rasterize_gaussians_backward (26 args, :113-138)."""
@@ -49,20 +74,9 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, colors_precomp, semantics, opacities, scales, rotations,
                 cov3Ds_precomp, raster_settings):
         rs = raster_settings
-        call = (rs.bg, means3D, colors_precomp, semantics, opacities, scales, rotations,
-                rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
-                rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, rs.campos,
-                rs.prefiltered, rs.debug)
-        if rs.debug:
-            saved = _snapshot(call)
-            try:
-                out = _C.rasterize_gaussians(*call)
-            except Exception:
-                torch.save(saved, "snapshot_fw.dump")
-                print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                raise
-        else:
-            out = _C.rasterize_gaussians(*call)
+        call = _forward_call(rs, means3D, sh, colors_precomp, semantics, opacities, scales, rotations,
+                             cov3Ds_precomp)
+        out = _call_debuggable(_C.rasterize_gaussians, call, *_FW_DUMP)
         num_rendered, color, depth, alpha, semantic, radii, geom, binning, img = out
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
@@ -79,16 +93,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color,
                 grad_depth, grad_alpha, grad_semantic, sh, rs.sh_degree, rs.campos, geom,
                 ctx.num_rendered, binning, img, alpha, semantics, rs.debug)
-        if rs.debug:
-            saved = _snapshot(call)
-            try:
-                grads = _C.rasterize_gaussians_backward_lean(*call)
-            except Exception:
-                torch.save(saved, "snapshot_bw.dump")
-                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                raise
-        else:
-            grads = _C.rasterize_gaussians_backward_lean(*call)
+        grads = _call_debuggable(_C.rasterize_gaussians_backward_lean, call, *_BW_DUMP)
         (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations,
          g_semantics) = grads
         # one gradient per forward input, in forward-argument order (reference :152-163).
@@ -109,21 +114,9 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, semantics, opaciti
         # No gradient can ever be asked of this call (torch.no_grad(), or no input requires grad:
         # render.py / render_lite.py / the simulator).  Same outputs through the entry point that
         # skips what only the backward needs (n_contrib); nothing is saved for autograd.
-        rs = raster_settings
-        call = (rs.bg, means3D, colors_precomp, semantics, opacities, scales, rotations,
-                rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
-                rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, rs.campos,
-                rs.prefiltered, rs.debug)
-        if rs.debug:
-            saved = _snapshot(call)
-            try:
-                out = _C.rasterize_gaussians_eval(*call)
-            except Exception:
-                torch.save(saved, "snapshot_fw.dump")
-                print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                raise
-        else:
-            out = _C.rasterize_gaussians_eval(*call)
+        call = _forward_call(raster_settings, means3D, sh, colors_precomp, semantics, opacities, scales,
+                             rotations, cov3Ds_precomp)
+        out = _call_debuggable(_C.rasterize_gaussians_eval, call, *_FW_DUMP)
         num_rendered, color, depth, alpha, semantic, radii = out[:6]
         return color, radii, depth, alpha, semantic
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, semantics, opacities,
@@ -133,6 +126,54 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, semantics, opaciti
 def _empty():
     # the reference passes torch.Tensor([]) (an empty CPU tensor) for absent optionals (:207-217)
     return torch.Tensor([])
+
+
+def _or_empty(*optionals):
+    """The optionals with one empty tensor in place of every absent one."""
+    e = _empty()
+    return [e if t is None else t for t in optionals]
+
+
+def _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """The reference's two input checks (:199-203), its texts and spelling."""
+    if (shs is None) == (colors_precomp is None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    has_sr = scales is not None or rotations is not None
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            (has_sr and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+
+
+def _no_semantics(means3D):
+    return torch.zeros(means3D.shape[0], 0, dtype=torch.float32, device=means3D.device)
+
+
+def _white(device):
+    """Default background of the two layer planes: white, like the reference's white_background=True."""
+    return torch.ones(3, dtype=torch.float32, device=device)
+
+
+def _layers_result(out):
+    """The dict of forward_layers from the 9-tuple of _C.rasterize_gaussians_layers / _composed_layers."""
+    _, color, depth, alpha, radii, color_bg, alpha_bg, color_obj, alpha_obj = out
+    return {"color": color, "radii": radii, "depth": depth, "alpha": alpha,
+            "color_background": color_bg, "alpha_background": alpha_bg,
+            "color_object": color_obj, "alpha_object": alpha_obj}
+
+
+def _frame_result(out, rgb8, planes, layered):
+    """The dict of forward_frame from the 10-tuple of _C.rasterize_gaussians_frame / _composed_frame: only what
+    was asked for."""
+    n, frame, color, depth, alpha, radii, color_bg, alpha_bg, color_obj, alpha_obj = out
+    res = {"num_rendered": n, "radii": radii}
+    if rgb8:
+        res["rgb8"] = frame
+    if planes:
+        res.update(rgb=color, depth=depth, alpha=alpha)
+    if layered:
+        res.update(color_background=color_bg, alpha_background=alpha_bg, color_object=color_obj,
+                   alpha_object=alpha_obj)
+    return res
 
 
 class GaussianRasterizer(nn.Module):
@@ -149,19 +190,11 @@ class GaussianRasterizer(nn.Module):
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
                 rotations=None, cov3D_precomp=None, semantics=None):
         rs = self.raster_settings
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        has_sr = scales is not None or rotations is not None
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                (has_sr and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        shs = _empty() if shs is None else shs
-        colors_precomp = _empty() if colors_precomp is None else colors_precomp
-        scales = _empty() if scales is None else scales
-        rotations = _empty() if rotations is None else rotations
-        cov3D_precomp = _empty() if cov3D_precomp is None else cov3D_precomp
+        _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _or_empty(
+            shs, colors_precomp, scales, rotations, cov3D_precomp)
         if semantics is None:
-            semantics = torch.zeros(means3D.shape[0], 0, dtype=torch.float32, device=means3D.device)
+            semantics = _no_semantics(means3D)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, semantics, opacities,
                                    scales, rotations, cov3D_precomp, rs)
 
@@ -174,25 +207,14 @@ class GaussianRasterizer(nn.Module):
         with and must be rendered again (forward() does).  gaussianrpg_amd.trajectory.DeferredFrames
         wraps the bookkeeping."""
         rs = self.raster_settings
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        has_sr = scales is not None or rotations is not None
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                (has_sr and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        shs = _empty() if shs is None else shs
-        colors_precomp = _empty() if colors_precomp is None else colors_precomp
-        scales = _empty() if scales is None else scales
-        rotations = _empty() if rotations is None else rotations
-        cov3D_precomp = _empty() if cov3D_precomp is None else cov3D_precomp
+        _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _or_empty(
+            shs, colors_precomp, scales, rotations, cov3D_precomp)
         if semantics is None:
-            semantics = torch.zeros(means3D.shape[0], 0, dtype=torch.float32, device=means3D.device)
+            semantics = _no_semantics(means3D)
         with torch.no_grad():
-            ticket, color, depth, alpha, semantic, radii = _C.rasterize_gaussians_eval_deferred(
-                rs.bg, means3D, colors_precomp, semantics, opacities, scales, rotations,
-                rs.scale_modifier, cov3D_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
-                rs.tanfovy, rs.image_height, rs.image_width, shs, rs.sh_degree, rs.campos,
-                rs.prefiltered, rs.debug)
+            ticket, color, depth, alpha, semantic, radii = _C.rasterize_gaussians_eval_deferred(*_forward_call(
+                rs, means3D, shs, colors_precomp, semantics, opacities, scales, rotations, cov3D_precomp))
         return ticket, color, radii, depth, alpha, semantic
 
     def forward_layers(self, means3D, opacities, layer_class, shs=None, colors_precomp=None, scales=None,
@@ -205,28 +227,16 @@ class GaussianRasterizer(nn.Module):
         reference's white_background=True).  Returns a dict: color, radii, depth, alpha (the composition, as
         forward()), color_background, alpha_background, color_object, alpha_object."""
         rs = self.raster_settings
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        has_sr = scales is not None or rotations is not None
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                (has_sr and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        shs = _empty() if shs is None else shs
-        colors_precomp = _empty() if colors_precomp is None else colors_precomp
-        scales = _empty() if scales is None else scales
-        rotations = _empty() if rotations is None else rotations
-        cov3D_precomp = _empty() if cov3D_precomp is None else cov3D_precomp
+        _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _or_empty(
+            shs, colors_precomp, scales, rotations, cov3D_precomp)
         if layer_bg is None:
-            layer_bg = torch.ones(3, dtype=torch.float32, device=means3D.device)
+            layer_bg = _white(means3D.device)
         with torch.no_grad():
-            (_, color, depth, alpha, radii, color_bg, alpha_bg, color_obj,
-             alpha_obj) = _C.rasterize_gaussians_layers(
+            return _layers_result(_C.rasterize_gaussians_layers(
                 rs.bg, layer_bg, layer_class, means3D, colors_precomp, opacities, scales, rotations,
                 rs.scale_modifier, cov3D_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
-                rs.image_height, rs.image_width, shs, rs.sh_degree, rs.campos, rs.debug)
-        return {"color": color, "radii": radii, "depth": depth, "alpha": alpha,
-                "color_background": color_bg, "alpha_background": alpha_bg,
-                "color_object": color_obj, "alpha_object": alpha_obj}
+                rs.image_height, rs.image_width, shs, rs.sh_degree, rs.campos, rs.debug))
 
     def forward_frame(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                       cov3D_precomp=None, layer_class=None, layer_bg=None, sky_cube=None, ray_matrix=None,
@@ -243,42 +253,25 @@ class GaussianRasterizer(nn.Module):
         epilogue on the composition; planes=False: the float planes are not even written.  Bit-identical to the
         chain forward() / forward_layers() -> clamp -> SkyCubeMap.composite -> trajectory.pack_hwc."""
         rs = self.raster_settings
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        has_sr = scales is not None or rotations is not None
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                (has_sr and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        e = _empty()
-        dev = means3D.device
-        if layer_class is not None and layer_bg is None:
-            layer_bg = torch.ones(3, dtype=torch.float32, device=dev)
+        _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        layered = layer_class is not None
+        if layered and layer_bg is None:
+            layer_bg = _white(means3D.device)
+        (layer_bg, layer_class, colors_precomp, scales, rotations, cov3D_precomp, shs, sky_cube,
+         ray_matrix) = _or_empty(layer_bg, layer_class, colors_precomp, scales, rotations, cov3D_precomp, shs,
+                                 sky_cube, ray_matrix)
         with torch.no_grad():
-            (n, frame, color, depth, alpha, radii, color_bg, alpha_bg, color_obj,
-             alpha_obj) = _C.rasterize_gaussians_frame(
-                rs.bg, e if layer_bg is None else layer_bg, e if layer_class is None else layer_class, means3D,
-                e if colors_precomp is None else colors_precomp, opacities, e if scales is None else scales,
-                e if rotations is None else rotations, rs.scale_modifier,
-                e if cov3D_precomp is None else cov3D_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
-                rs.image_height, rs.image_width, e if shs is None else shs, rs.sh_degree, rs.campos, rs.debug,
-                e if sky_cube is None else sky_cube, e if ray_matrix is None else ray_matrix, float(sky_fill),
-                bool(clamp), bool(planes), bool(rgb8), bool(truncate), out)
-        res = {"num_rendered": n, "radii": radii}
-        if rgb8:
-            res["rgb8"] = frame
-        if planes:
-            res.update(rgb=color, depth=depth, alpha=alpha)
-        if layer_class is not None:
-            res.update(color_background=color_bg, alpha_background=alpha_bg, color_object=color_obj,
-                       alpha_object=alpha_obj)
-        return res
+            ret = _C.rasterize_gaussians_frame(
+                rs.bg, layer_bg, layer_class, means3D, colors_precomp, opacities, scales, rotations,
+                rs.scale_modifier, cov3D_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
+                rs.image_height, rs.image_width, shs, rs.sh_degree, rs.campos, rs.debug, sky_cube, ray_matrix,
+                float(sky_fill), bool(clamp), bool(planes), bool(rgb8), bool(truncate), out)
+        return _frame_result(ret, rgb8, planes, layered)
 
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):
         """(radii int32[P], means2D [P,2]) without colour/conic (reference :235-259)."""
         rs = self.raster_settings
-        scales = _empty() if scales is None else scales
-        rotations = _empty() if rotations is None else rotations
-        cov3D_precomp = _empty() if cov3D_precomp is None else cov3D_precomp
+        scales, rotations, cov3D_precomp = _or_empty(scales, rotations, cov3D_precomp)
         with torch.no_grad():
             return _C.rasterize_gaussians_filter(
                 means3D, scales, rotations, rs.scale_modifier, cov3D_precomp, rs.viewmatrix,
