@@ -127,62 +127,21 @@ def build_binding(force=False, verbose=False):
 
 
 # Test variants of the C-ABI library: the same sources with one translation unit recompiled under an
-# extra -D.  They live under build/variants/ (git-ignored like every built file, shipped to the GPU
-# box by gpurun), are loaded through ctypes by the one test that needs them and are never imported
-# by the package.
+# extra -D.  They live under build/variants/ (git-ignored like every built file), are loaded through
+# ctypes by the one test that needs them and are never imported by the package.
 VARIANTS = {
     # every producer / consumer hand-over of the render gives up at once: the timeout -> error path
     # (render_fwd.hip pc_fail, tests/test_gpu_pc_timeout.py)
     "pcspin0": {"render_fwd.hip": ["-DGRPG_PC_SPIN_LIMIT=0"]},
 }
-# experiment builds (not built by build_all): python -c "from gaussianrpg_amd import build; build.build_variant('dstrace')"
+# Instrumented builds of the stages DESIGN.md section 10 lists as open; outputs stay correct.  Not built by
+# build_all: python -c "from gaussianrpg_amd import build; build.build_variant('dstrace')"
+# (tests/test_build_variants.py holds every flag of both tables against the sources)
 EXPERIMENT_VARIANTS = {
     # phase timestamps of the depth sort's scatter passes (tools/ds_trace.py)
     "dstrace": {"sort.hip": ["-DGRPG_DS_TRACE"]},
-    # per-wave trace of the render (GRPG_RENDER_TRACE=<file>, tools/trace_render.py) and the loop
-    # counters / ablation switches of the blend backward (GRPG_BWD_STATS, GRPG_BWD_ABLATE)
-    "trace": {"render_fwd.hip": ["-DGRPG_TRACE"], "render_bwd.hip": ["-DGRPG_TRACE"]},
-    # render capped at 3 / 2 workgroups per CU by unused LDS (does a second stream's kernel co-reside?)
-    # num_rendered published by a launch of its own right behind preprocess instead of by the sort's first pass
-    "pubearly": {"api.hip": ["-DGRPG_PUBLISH_EARLY"]},
-    # the classic (256-thread, 21 KB of LDS) depth-sort passes for every P: does a small footprint overlap better?
-    "classicsort": {"api.hip": ["-DGRPG_FORCE_CLASSIC_SORT"]},
-    # 96 registers / 101 KB of LDS per sort workgroup: room for another stream's workgroup on the same CU
-    "sortlean": {"sort.hip": ["-DGRPG_SORT_LEAN"]},
-    # round 5: only the class-0 workgroups run (images are wrong): how long is the chain of the longest
-    # tiles with nothing beside it?  (+ the per-role trace of it, tools/trace_class0.py)
-    # round 5: the coarse emit behind the two-launch offsets scan again (what the fused emit is measured against)
-    "unfusedemit": {"api.hip": ["-DGRPG_UNFUSED_COARSE_EMIT"]},
-    "only0": {"render_fwd.hip": ["-DGRPG_RENDER_ONLY_CLASS0"]},
-    "no0": {"render_fwd.hip": ["-DGRPG_RENDER_NO_CLASS0"]},
-    "only0trace": {"render_fwd.hip": ["-DGRPG_RENDER_ONLY_CLASS0", "-DGRPG_TRACE"], "render_bwd.hip": ["-DGRPG_TRACE"]},
-    # the producer / consumer pairs from 4096 / 16384 entries instead of 8192
-    "pc4096": {"render_fwd.hip": ["-DGRPG_RENDER_PC_MIN=4096"], "api.hip": ["-DGRPG_RENDER_PC_MIN=4096"],
-               "hier_binning.hip": ["-DGRPG_RENDER_PC_MIN=4096"]},
-    "pc16384": {"render_fwd.hip": ["-DGRPG_RENDER_PC_MIN=16384"], "api.hip": ["-DGRPG_RENDER_PC_MIN=16384"],
-                "hier_binning.hip": ["-DGRPG_RENDER_PC_MIN=16384"]},
-    # round 6: the layered kernel allocated for 3 waves per SIMD (168 VGPRs, no scratch) instead of 4
-    # round 6 (wrong images): the layered walk without the object layer's state / without the background layer's
-    # round 6: one walk per layer for object tiles from 2048 / 8192 entries instead of 4096
-    "lpc2048": {"render_fwd.hip": ["-DGRPG_LAYERS_PC_MIN=2048"], "api.hip": ["-DGRPG_LAYERS_PC_MIN=2048"]},
-    "lpc8192": {"render_fwd.hip": ["-DGRPG_LAYERS_PC_MIN=8192"], "api.hip": ["-DGRPG_LAYERS_PC_MIN=8192"]},
-    "lay_noobj": {"render_fwd.hip": ["-DGRPG_LAYERS_ABLATE=1"]},
-    "lay_nobg": {"render_fwd.hip": ["-DGRPG_LAYERS_ABLATE=2"]},
-    "lay_none": {"render_fwd.hip": ["-DGRPG_LAYERS_ABLATE=3"]},
-    # round 6: per-workgroup life of the point-list fill (tools/fill_trace.py)
-    # round 6: the fill with every lane reading record 0 / 1 instead of its own (what does the gather cost?)
-    "fill_nogather": {"hier_binning.hip": ["-DGRPG_FILL_ABLATE=2"]},
+    # per-workgroup life of the point-list fill (tools/fill_trace.py)
     "filltrace": {"hier_binning.hip": ["-DGRPG_FILL_TRACE"]},
-    # round 6: 512-entry segments in the hierarchical binning (26 KB of LDS, 52 registers: four fill workgroups per CU)
-    "hbseg512": {"hier_binning.hip": ["-DGRPG_HB_SEG=512"]},
-    "layers3w": {"render_fwd.hip": ["-DGRPG_LAYERS_MIN_WAVES=3"]},
-    # round 6 (wrong host bytes): a drained frame whose drain workgroups exit at once -- what the blending waves' share
-    # of a host-destination frame costs (write-through staging stores, the arrival's wait and atomic)
-    "drainidle": {"render_fwd.hip": ["-DGRPG_DRAIN_IDLE"]},
-    # round 6: light / mid tiles of the backward by ONE wave at 4 pixels per lane (half the reductions there)
-    "bwdpx4": {"render_bwd.hip": ["-DGRPG_BWD_LIGHT_SPLIT=1"]},
-    "pad12": {"render_fwd.hip": ["-DGRPG_RENDER_LDS_PAD=12288"]},
-    "pad26": {"render_fwd.hip": ["-DGRPG_RENDER_LDS_PAD=26624"]},
 }
 
 

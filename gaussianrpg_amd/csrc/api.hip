@@ -254,13 +254,6 @@ std::atomic<int> g_binning_alg{[] {
   return (e && strcmp(e, "sort") == 0) ? GRPG_BINNING_ALG_SORT : GRPG_BINNING_ALG_HIER;
 }()};
 bool binning_is_hier() { return g_binning_alg.load() == GRPG_BINNING_ALG_HIER; }
-// -DGRPG_UNFUSED_COARSE_EMIT (experiment build `unfusedemit`): the coarse emit behind the two-launch offsets scan, as
-// before round 5 (still the path of grids beyond 255 x 255 tiles), for A/B runs on one box
-#ifdef GRPG_UNFUSED_COARSE_EMIT
-constexpr bool UNFUSED_COARSE_EMIT = true;
-#else
-constexpr bool UNFUSED_COARSE_EMIT = false;
-#endif
 
 int bits_for(uint32_t T) {  // smallest b with (1 << b) >= T, i.e. tile ids fit in b bits
   int b = 0;
@@ -826,11 +819,7 @@ struct Frame {
     // With the fat depth sort the sum rides in its first pass (one launch fewer; the count arrives
     // ~35 us later, still long before the host has enqueued the frame); the classic sort of very
     // large P: the separate one-workgroup launch right here.
-#ifdef GRPG_PUBLISH_EARLY   // experiment build: the count by its own launch right behind preprocess
-    const bool fold_publish = false;
-#else
     const bool fold_publish = fat_sort;
-#endif
     if (!fold_publish) {
       launch_publish_counts(stream, pre_counts, (uint32_t)((q.P + 255) / 256), pub_ptr, &gh->R_pre);
       HIP_TRY(hipEventRecord(pub_ev, stream));
@@ -935,7 +924,7 @@ struct Frame {
     tm.mark(2);
     // counts and rectangles already in depth order (from the sort's last pass): the emit scans the offsets it
     // needs itself from the block sums (binning.hip emit_coarse_fused_kernel); otherwise the two-launch scan
-    const bool fused_emit = rect_sorted_by_sort && emit_coarse_fused_ok(GL.nblocks_scan) && !UNFUSED_COARSE_EMIT;
+    const bool fused_emit = rect_sorted_by_sort && emit_coarse_fused_ok(GL.nblocks_scan);
     if (fused_emit)
       launch_offsets_reduce(stream, (uint32_t)q.P, &gh->V, tiles_sorted, block_sums, GL.nblocks_scan);
     else if (rect_sorted_by_sort)

@@ -149,11 +149,7 @@ constexpr int DS_WAVES = DS_THREADS / WAVE;       // 16
 constexpr int DS_BITS = 9;                        // three 9-bit passes over key - key_base (+ a fourth
 constexpr int DS_RADIX = 1 << DS_BITS;            // over the last 5 bits when the depth range needs it)
 constexpr int DS_PASSES = 4;
-#ifdef GRPG_FORCE_CLASSIC_SORT   // experiment build: the small-footprint classic passes for every P
-constexpr uint32_t DS_MAX_CHUNKS = 0;
-#else
 constexpr uint32_t DS_MAX_CHUNKS = 512;           // beyond (P > 4 M) the table sweep per workgroup grows
-#endif
                                                   // quadratically: classic three-kernel passes instead
 
 // One model of a composed scene as the kernels see it (device copy of grpg_model_segment).
@@ -311,13 +307,7 @@ inline ImgLayout img_layout(size_t T, size_t N) {
 //   shorter: one wave per tile (light).
 // A frame with semantic planes sends every non-empty tile down the heavy path (heavy_min = 1), whose
 // one-pixel-per-lane waves carry the extra accumulators.
-#ifndef GRPG_RENDER_PC_MIN      // experiment builds override the class boundaries
-#define GRPG_RENDER_PC_MIN 8192
-#endif
-#ifndef GRPG_RENDER_C1_MIN
-#define GRPG_RENDER_C1_MIN 2048
-#endif
-constexpr uint32_t RENDER_PC_MIN = GRPG_RENDER_PC_MIN, RENDER_C1_MIN = GRPG_RENDER_C1_MIN, RENDER_HEAVY_MIN = 256;
+constexpr uint32_t RENDER_PC_MIN = 8192, RENDER_C1_MIN = 2048, RENDER_HEAVY_MIN = 256;
 constexpr int RENDER_NSEM = 16;   // semantic channels fused into the main render launch
 static_assert(RENDER_HEAVY_MIN <= CK_LONG_MIN, "lists with blend checkpoints must take the heavy path");
 // A LAYERED frame (grpg_forward_layers) knows, per tile, whether its list holds an entry of an OBJECT-class
@@ -333,10 +323,9 @@ struct TileObjBits {
   int gx;
   __host__ __device__ bool tile(const uint32_t t) const { return flags[t] != 0; }
 };
-#ifndef GRPG_LAYERS_PC_MIN      // experiment builds: from how many entries a tile WITH object entries gets one walk
-#define GRPG_LAYERS_PC_MIN 4096 // per layer (render_fwd.hip LayerRoleOut) instead of three states on one wave
-#endif
-constexpr uint32_t LAYERS_PC_MIN = GRPG_LAYERS_PC_MIN;
+// from how many entries a tile WITH object entries gets one walk per layer (render_fwd.hip LayerRoleOut) instead of
+// three states on one wave
+constexpr uint32_t LAYERS_PC_MIN = 4096;
 struct TileClasses { uint32_t c0_min, c1_min, heavy_min; TileObjBits obj; uint32_t c0_obj_min; };
 inline TileClasses tile_classes(int S) {
   return TileClasses{RENDER_PC_MIN, RENDER_C1_MIN, S > 0 ? 1u : RENDER_HEAVY_MIN, TileObjBits{nullptr, 0}, RENDER_PC_MIN};

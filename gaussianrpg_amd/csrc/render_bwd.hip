@@ -30,10 +30,6 @@
 //     the Gaussian: 64-256x fewer atomic operations than the reference.  Summation order differs
 //     from the reference's (unspecified) atomic order, so gradients agree to rounding, not
 //     bitwise -- exactly as two runs of the reference differ from each other.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
 #include "blend_math.h"
 #include "common.h"
 
@@ -160,16 +156,9 @@ __device__ __forceinline__ void backward_rect(
     const float* __restrict__ alphas, const uint32_t* __restrict__ n_contrib,
     const float* __restrict__ dL_dpix, const float* __restrict__ dL_dpix_depth,
     const float* __restrict__ dL_dalphas, const float* __restrict__ dL_dpix_semantic,
-    float* __restrict__ grad_rec, float* __restrict__ dL_dsemantic, const int ablate_in,
-    unsigned long long* __restrict__ stats_in, const uint32_t seg_lo = 0u, const uint32_t seg_hi = 0u,
+    float* __restrict__ grad_rec, float* __restrict__ dL_dsemantic,
+    const uint32_t seg_lo = 0u, const uint32_t seg_hi = 0u,
     const float* __restrict__ ck_end = nullptr, const float* __restrict__ ck_final = nullptr) {
-#ifdef GRPG_TRACE   // experiment build: ablation switches and loop counters are live
-  const int ablate = ablate_in;
-  unsigned long long* const stats = stats_in;
-#else               // production: constants, so that the counters and the switches' masks cost nothing in the trip loop
-  constexpr int ablate = 0;
-  constexpr unsigned long long* stats = nullptr;
-#endif
   constexpr int SM = SMAX > 0 ? SMAX : 1;
   const int px = x0 + (lane & 15);
   const int py0 = y0 + (lane >> 4) * PX;
@@ -278,10 +267,6 @@ __device__ __forceinline__ void backward_rect(
     const uint32_t off = (uint32_t)(q * WAVE + lane);
     win[q] = off < in_hi - lo ? point_list[r_begin + in_hi - 1 - off] : 0u;
   }
-  const uint64_t ablate_m = (ablate & 4) ? 0ull : ~0ull;
-  uint32_t st_fill = 0, st_batches = 0, st_iters = 0, st_used = 0, st_rows = 0;   // GRPG_BWD_STATS
-  unsigned long long st_small = 0ull, st_lanes_sum = 0ull;
-  const unsigned long long st_t0 = stats ? __builtin_readcyclecounter() : 0ull;
   float4 la = make_float4(0, 0, 0, 0), lb = la, lc = la;   // current batch (records arrived)
   uint32_t lpos = 0, lid = 0, ncur = 0;
   for (;;) {
@@ -309,7 +294,6 @@ __device__ __forceinline__ void backward_rect(
         rcount += (uint32_t)__popcll(m);
       }
       in_hi = nxt;
-      st_fill++;
     }
     // the ring entries written by FILL are read by OTHER lanes in POP: keep the compiler from
     // reordering the LDS accesses across this point (costs no instruction)
@@ -378,8 +362,6 @@ __device__ __forceinline__ void backward_rect(
       }
     }
     __builtin_amdgcn_wave_barrier();
-    st_batches += ncur > 0 ? 1u : 0u;
-    st_iters += (uint32_t)cnt;
     const int cnt_u = __builtin_amdgcn_readfirstlane(cnt);   // loop control on the scalar unit
     for (int j = 0; j < cnt_u; j++) {
       const float4 a = my[j * BREC + 0];   // px, py, depth, opacity
@@ -401,7 +383,6 @@ __device__ __forceinline__ void backward_rect(
 #pragma unroll
       for (int cc = 0; cc < SM; cc++) g_s[cc] = 0.f;
       bool any = false;
-      uint64_t st_lanes = 0ull;   // GRPG_BWD_STATS: lanes that take the splat for some pixel
 #pragma unroll
       for (int k = 0; k < PX; k++) {
         const float dy = a.y - pyf[k];
@@ -412,12 +393,10 @@ __device__ __forceinline__ void backward_rect(
         // lane masks in SGPRs: the compares ARE ballots, the boolean algebra runs on the scalar unit
         const uint64_t valid_m = __builtin_amdgcn_ballot_w64(!(power2 > 0.0f)) &
                                  __builtin_amdgcn_ballot_w64(!(alpha < ALPHA_MIN)) &
-                                 __builtin_amdgcn_ballot_w64(pos < lastc[k]) & ablate_m;
+                                 __builtin_amdgcn_ballot_w64(pos < lastc[k]);
         if (valid_m == 0ull) continue;   // wave-uniform: no pixel of this row takes the splat
         const bool valid = __builtin_amdgcn_inverse_ballot_w64(valid_m);
         any = true;
-        st_rows++;
-        st_lanes |= valid_m;
         // Branch-free below: a lane that rejects the splat runs the same arithmetic with
         // alpha = G = 0, which leaves its T and accumulators unchanged (T / (1 - 0), acc + 0 * d)
         // and contributes exact zeros to every sum.
@@ -464,18 +443,11 @@ __device__ __forceinline__ void backward_rect(
         g_cyy = fmaf(tdy, dy, g_cyy);
       }
       if (!any) continue;         // wave-uniform: nobody in the tile used this splat
-      st_used++;
-      if (stats != nullptr) {
-        const int nl = (int)__popcll(st_lanes);
-        st_lanes_sum += (unsigned long long)nl;
-        st_small += nl <= 1 ? 1ull : (nl <= 4 ? (1ull << 20) : (nl <= 8 ? (1ull << 40) : 0ull));
-      }
-      if (ablate & 2) continue;   // experiment switch (GRPG_BWD_ABLATE): no reduction, no atomics
       {
         const float qv[12] = {g_mx, g_my, g_mabs, g_cxx, g_cxy, g_cyy, g_c[0], g_c[1], g_c[2], g_op,
                               g_c[3], 0.f};
         const float tot = wave_fold_12(qv, lane_odd, lane_hi2);
-        if (sc_lane && !(ablate & 1)) atomicAdd(sc_ptr + gid * (uint32_t)GRAD_STRIDE, tot * sc_scale);
+        if (sc_lane) atomicAdd(sc_ptr + gid * (uint32_t)GRAD_STRIDE, tot * sc_scale);
       }
       if (SMAX > 0) {
 #pragma unroll
@@ -490,20 +462,6 @@ __device__ __forceinline__ void backward_rect(
     __builtin_amdgcn_wave_barrier();
     la = na; lb = nb; lc = nc; lpos = npos; lid = nid; ncur = nn;
     if (ncur == 0 && in_hi == lo) break;   // ring empty (rcount == 0 here) and list exhausted
-  }
-  if (stats != nullptr && lane == 0) {   // experiment counters (GRPG_BWD_STATS=1), off in production
-    // one record of 8 words per wave, no atomics (same-address atomics would dominate the launch)
-    unsigned long long* r = stats + 8ull * ((unsigned long long)blockIdx.x * RB_WAVES + (threadIdx.x >> 6));
-    // wave kind: 1 quarter wave, 3 half-tile wave; + 4: a (tile, segment) item; above: the tile's list length
-    r[0] = (1ull + (PX == 1 ? 0ull : 2ull)) | (SEG ? 4ull : 0ull) | ((unsigned long long)(r_end - r_begin) << 8);
-    // list entries in reach of the wave (up to the deepest contributor) | the wave's share of the list
-    r[1] = (unsigned long long)(count - lo) | ((unsigned long long)(SEG ? seg_hi - seg_lo : r_end - r_begin) << 32);
-    r[2] = ((unsigned long long)st_fill << 32) | st_batches;
-    r[3] = st_iters;                          // survivors of the rectangle cull = loop trips
-    r[4] = st_used;                           // ... of which some pixel used (reduction + atomic)
-    r[5] = (unsigned long long)st_rows | (st_lanes_sum << 32);   // gradient blocks executed | accepting lanes, summed over the used trips
-    r[6] = __builtin_readcyclecounter() - st_t0;
-    r[7] = st_small;                          // used trips with 1 / 2-4 / 5-8 accepting lanes (20 bits each)
   }
 }
 
@@ -524,8 +482,7 @@ render_backward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restr
                        const float* __restrict__ dL_dpix, const float* __restrict__ dL_dpix_depth,
                        const float* __restrict__ dL_dalphas,
                        const float* __restrict__ dL_dpix_semantic, float* __restrict__ grad_rec,
-                       float* __restrict__ dL_dsemantic, const int ablate, const int wide_classes,
-                       unsigned long long* __restrict__ stats,
+                       float* __restrict__ dL_dsemantic, const int wide_classes,
                        const BlobHeader* __restrict__ bin_hdr, const uint32_t* __restrict__ ck_count,
                        const uint32_t* __restrict__ bwd_ctl, const uint32_t items_cap) {
   __shared__ float4 s_rec[RB_WAVES][WAVE * BREC];
@@ -554,7 +511,7 @@ render_backward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restr
     backward_rect<1, SMAX, true>(s_rec[wave], s_qid[wave], s_qpos[wave], lane, rb, re, tx * TILE,
                                  ty * TILE + wave * 4, 1u << (SUBTILE_SHIFT + wave), W, H, S, point_list,
                                  rec, semantics, bg, alphas, n_contrib, dL_dpix, dL_dpix_depth,
-                                 dL_dalphas, dL_dpix_semantic, grad_rec, dL_dsemantic, ablate, stats, lo,
+                                 dL_dalphas, dL_dpix_semantic, grad_rec, dL_dsemantic, lo,
                                  hi, k + 1u == n ? nullptr : rk, r0 + (size_t)(n - 1u) * 4 * CK_REC_FLOATS);
     return;
   }
@@ -588,8 +545,7 @@ render_backward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restr
 #define RB_CALL(PXV, YOFF, BITS)                                                                  \
   backward_rect<PXV, SMAX>(s_rec[wave], s_qid[wave], s_qpos[wave], lane, rb, re, tx * TILE, ty * TILE + (YOFF), (BITS), W, H, \
                            S, point_list, rec, semantics, bg, alphas, n_contrib, dL_dpix,          \
-                           dL_dpix_depth, dL_dalphas, dL_dpix_semantic, grad_rec, dL_dsemantic,     \
-                           ablate, stats)
+                           dL_dpix_depth, dL_dalphas, dL_dpix_semantic, grad_rec, dL_dsemantic)
   if (b < nheavy)
     RB_CALL(1, wave * 4, 1u << (SUBTILE_SHIFT + wave));
   else if (LIGHT_SPLIT == 2)
@@ -620,91 +576,23 @@ void launch_render_backward(hipStream_t s, const uint2* ranges, const uint32_t* 
   // reduction: 515 -> 489 us at config 5, 645 -> 573 us on the 2 M-Gaussian scene (quarter waves for
   // every heavy tile, or half tiles for lists of 2048 .. 4095 entries as well: slower).
   const int wide = 1;
-  int ablate = 0;
-  unsigned long long* stats = nullptr;
-#ifdef GRPG_TRACE   // experiment build: ablation switch and per-launch loop counters (synchronises)
-  // GRPG_BWD_ABLATE: 1 = no atomics, 2 = no reduction either, 4 = traversal + alpha only
-  static const int ablate_env = [] { const char* e = getenv("GRPG_BWD_ABLATE"); return e ? atoi(e) : 0; }();
-  ablate = ablate_env;
-  static const int want_stats = [] { const char* e = getenv("GRPG_BWD_STATS"); return e ? atoi(e) : 0; }();
-  static unsigned long long* stats_dev = nullptr;
-  static size_t stats_cap = 0;
-  const int grid_max = ntiles + ntiles / 2 + 1 + (int)ckpt_slots(R);
-  const size_t stats_words = 8ull * (size_t)grid_max * RB_WAVES;
-  if (want_stats) {
-    if (stats_words > stats_cap) {
-      if (stats_dev) (void)hipFree(stats_dev);
-      stats_dev = nullptr;
-      if (hipMalloc((void**)&stats_dev, stats_words * sizeof(unsigned long long)) != hipSuccess) return;
-      stats_cap = stats_words;
-    }
-    (void)hipMemsetAsync(stats_dev, 0, stats_words * sizeof(unsigned long long), s);
-    stats = stats_dev;
-  }
-#endif
 #define RB_ARGS                                                                                  \
   ranges, point_list, rec, semantics, S, W, H, gx, (uint32_t)ntiles, work, bg, alphas, n_contrib, \
-      dL_dpix, dL_dpix_depth, dL_dalphas, dL_dpix_semantic, grad_rec, dL_dsemantic, ablate, wide, stats, \
+      dL_dpix, dL_dpix_depth, dL_dalphas, dL_dpix_semantic, grad_rec, dL_dsemantic, wide, \
       bin_hdr, ck_count, bwd_ctl, items_cap
   // nheavy + ceil(2 nlight / 4) workgroups at most = ntiles + ntiles / 2 + 1; surplus ones exit at once.
   // Light tiles: two waves per tile at 2 pixels per lane: the kernel then fits 128 VGPRs = 4 waves per
   // SIMD (one wave at 4 pixels per lane / 160 VGPRs and an uncapped allocation measured within 1 %;
   // 96 VGPRs with 36 spilled: 8 % slower).
   const int grid = ntiles + ntiles / 2 + 1 + (int)items_cap;
-#ifndef GRPG_BWD_LIGHT_SPLIT   // experiment switch: 1 = one wave per light / mid tile at 4 pixels per lane
-#define GRPG_BWD_LIGHT_SPLIT 2
-#endif
   if (S <= 0) {
-    render_backward_kernel<0, GRPG_BWD_LIGHT_SPLIT, 4><<<grid, 256, 0, s>>>(RB_ARGS);
+    render_backward_kernel<0, 2, 4><<<grid, 256, 0, s>>>(RB_ARGS);
   } else if (S <= 4) {
     render_backward_kernel<4, 2><<<grid, 256, 0, s>>>(RB_ARGS);
   } else {
     render_backward_kernel<32, 1><<<ntiles, 256, 0, s>>>(RB_ARGS);   // S <= 32 (reference: 20)
   }
 #undef RB_ARGS
-#ifdef GRPG_TRACE
-  if (stats) {
-    std::vector<unsigned long long> h(stats_words);
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h.data(), stats_dev, stats_words * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    // Per tile class (by list length; how the launch walks it): tile instances, (wave, splat) reductions, and how
-    // many lanes accept per reduction -- VERDICT r5 item 4: what has to be sized is the NUMBER of reductions.
-    struct Cls { unsigned long long waves, inst4, reach, trips, used, rows, lanes, s1, s4, s8, cyc; };
-    Cls c[4] = {};
-    static const char* const cname[4] = {"<256 (2 half-tile waves)", "256-2047 (2 half-tile waves)",
-                                         "2048-4095 (4 quarter waves)", ">=4096 (4 quarter waves per segment)"};
-    unsigned long long cyc_max = 0, trips_of_longest = 0, reach_of_longest = 0;
-    for (size_t w = 0; w < stats_words / 8; w++) {
-      const unsigned long long* r = &h[8 * w];
-      if (!r[0]) continue;
-      const unsigned kind = (unsigned)(r[0] & 3ull);
-      const unsigned long long len = r[0] >> 8;
-      Cls& k = c[len < 256 ? 0 : (len < 2048 ? 1 : (len < 4096 ? 2 : 3))];
-      k.waves++;
-      // the wave's share of the list in quarter-instances: a quarter wave covers 1/4 of its entries' pixels, a
-      // half-tile wave 2/4
-      k.inst4 += (r[1] >> 32) * (kind == 1 ? 1ull : 2ull);
-      k.reach += r[1] & 0xFFFFFFFFull; k.trips += r[3]; k.used += r[4];
-      k.rows += r[5] & 0xFFFFFFFFull; k.lanes += r[5] >> 32; k.cyc += r[6];
-      k.s1 += r[7] & 0xFFFFFull; k.s4 += (r[7] >> 20) & 0xFFFFFull; k.s8 += (r[7] >> 40) & 0xFFFFFull;
-      if (r[6] > cyc_max) { cyc_max = r[6]; trips_of_longest = r[3]; reach_of_longest = r[1] & 0xFFFFFFFFull; }
-    }
-    unsigned long long tu = 0, ti = 0;
-    for (int i = 0; i < 4; i++) {
-      const double inst = (double)c[i].inst4 / 4.0;   // tile instances of the class
-      tu += c[i].used; ti += c[i].inst4;
-      fprintf(stderr, "[bwd stats] class %-38s waves %8llu  tile instances %10.0f  cull survivors (trips) %10llu  "
-                      "reductions %10llu = %.3f per instance  lanes per reduction %.2f  (1 lane: %.3f, 2-4: %.3f, 5-8: %.3f)  "
-                      "wave cycles %llu\n", cname[i], c[i].waves, inst, c[i].trips, c[i].used,
-              inst > 0 ? (double)c[i].used / inst : 0.0, c[i].used ? (double)c[i].lanes / (double)c[i].used : 0.0,
-              c[i].used ? (double)c[i].s1 / (double)c[i].used : 0.0, c[i].used ? (double)c[i].s4 / (double)c[i].used : 0.0,
-              c[i].used ? (double)c[i].s8 / (double)c[i].used : 0.0, c[i].cyc);
-    }
-    fprintf(stderr, "[bwd stats] all classes: reductions %llu, tile instances %.0f, %.3f per instance; longest wave %llu cycles "
-                    "(%llu trips, %llu entries in reach)\n", tu, (double)ti / 4.0, ti ? 4.0 * (double)tu / (double)ti : 0.0,
-            cyc_max, trips_of_longest, reach_of_longest);
-  }
-#endif
 }
 
 }  // namespace grpg

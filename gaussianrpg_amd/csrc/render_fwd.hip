@@ -33,17 +33,9 @@
 // The kernel is VALU-issue-bound (about 25 flop-equivalents per surviving pixel-splat pair), not
 // HBM-bound; its compulsory HBM traffic is 4 B (id) + 40 B (record fields) per tile instance
 // + 20 B per pixel.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
 #include "blend_math.h"
 #include "common.h"
 #include "sky_math.h"
-
-#ifndef GRPG_LAYERS_ABLATE
-#define GRPG_LAYERS_ABLATE 0
-#endif
 
 namespace grpg {
 
@@ -542,9 +534,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // the wave pairs' (pc_fail): a lost arrival is reported, not waited for.
 __device__ __forceinline__ void drain_units(const FrameEpi& e, const int W, const int H, const uint32_t wid,
                                             const uint32_t nd, const int lane, const PCErr err) {
-#ifdef GRPG_DRAIN_IDLE   // experiment build: nobody drains (the blending waves' share of the cost; wrong host bytes)
-  return;
-#endif
   const uint32_t gy = (uint32_t)(H + 15) >> 4, NU = (uint32_t)e.units_x * gy;
   const size_t pitch = (size_t)3 * W;
   // unit u belongs to wave u % nd, slot u / nd (< 64: the launch has >= NU / 64 drain waves); a wave's 64 counters
@@ -696,15 +685,12 @@ struct LayersOutT {
 };
 typedef LayersOutT<false> LayersOut;
 
-struct WaveTrace { uint32_t batches, survivors, blends, t_stage, t_loop; uint32_t it[4], cyc[4]; };
-
-template <int PX, int GPI, bool WRITE_AUX, bool TRACE = false, class Out = PlainOut>
+template <int PX, int GPI, bool WRITE_AUX, class Out = PlainOut>
 __device__ __forceinline__ void blend_rect(float4* __restrict__ my, const int lane,
                                            const uint32_t r_begin, const uint32_t r_end,
                                            const int x0, const int y0, const int W, const int H,
                                            const uint32_t* __restrict__ point_list,
-                                           const RecView rec, const Out& out,
-                                           WaveTrace* tr = nullptr, const int ablate = 0) {
+                                           const RecView rec, const Out& out) {
   const int px = x0 + (lane & 15);
   const int py0 = y0 + (lane >> 4) * PX;
   const float pxf = (float)px;
@@ -778,33 +764,22 @@ __device__ __forceinline__ void blend_rect(float4* __restrict__ my, const int la
     }
     if (base + 2 * WAVE + (uint32_t)lane < r_end)      // ids of the batch after that
       id_n2 = point_list[base + 2 * WAVE + lane];
-    const uint64_t tc0 = TRACE ? __builtin_readcyclecounter() : 0;
     const bool keep = ((uint32_t)lane < n) && live &&
                       !splat_misses_rect(a.x, a.y, b.x, b.y, b.z, a.w, rx0, rx1, ry0, ry1);
     const uint64_t mask = __ballot(keep);
     const int cnt = (int)__popcll(mask);
     if (keep)   // list positions are 1-based (n_contrib convention of the reference)
       store_slot(my, (int)__popcll(mask & lanemask_lt()), a, b, c, base - r_begin + 1 + (uint32_t)lane);
-    if (TRACE) { tr->batches++; tr->survivors += (uint32_t)cnt; }
     __builtin_amdgcn_wave_barrier();
 
-    const uint64_t tc1 = TRACE ? __builtin_readcyclecounter() : 0;
-    if (TRACE) tr->t_stage += (uint32_t)(tc1 - tc0);
     {
       // full groups of GPI survivors, then the remainder one by one: no dummy slots are evaluated
-      int j0 = (TRACE && (ablate & 1)) ? cnt : 0;
-      for (; j0 + GPI <= cnt; j0 += GPI) {
-        const bool blended = blend_group<PX, GPI, WRITE_AUX>(st, my, j0, pxf, py0);
-        if (TRACE && blended) tr->blends++;
-      }
+      int j0 = 0;
+      for (; j0 + GPI <= cnt; j0 += GPI) blend_group<PX, GPI, WRITE_AUX>(st, my, j0, pxf, py0);
       if (GPI > 1) {
-        for (; j0 < cnt; j0++) {
-          const bool blended = blend_group<PX, 1, WRITE_AUX>(st, my, j0, pxf, py0);
-          if (TRACE && blended) tr->blends++;
-        }
+        for (; j0 < cnt; j0++) blend_group<PX, 1, WRITE_AUX>(st, my, j0, pxf, py0);
       }
     }
-    if (TRACE) tr->t_loop += (uint32_t)(__builtin_readcyclecounter() - tc1);
     __builtin_amdgcn_wave_barrier();
   }
 
@@ -846,7 +821,7 @@ constexpr int FILL_Q = 4;            // list entries per lane per FILL step of t
 // written by the fill kernel a moment ago: HBM / Infinity Cache, 1 - 2 us).  With thousands of waves in
 // flight that is hidden; for ONE wave walking 8 k - 35 k entries -- a class-0 producer, or the quarter wave of
 // such a tile in a layered frame, which has no wave pairs -- those 126 steps are most of its life
-// (tools/trace_class0.py: 1.9 us per batch for 0.7 us of work).  Here a window is SUB sub-windows of 256
+// (per-role wave trace, DESIGN_EXPERIMENTS.md R5.1: 1.9 us per batch for 0.7 us of work).  Here a window is SUB sub-windows of 256
 // entries, requested together with 16-byte loads (lane l owns four consecutive entries) and consumed from
 // registers: one memory latency per SUB x 256 entries.  SUB = 8 for the producers (a wave of its own with
 // registers to spare), 4 for the layered frame's quarter waves.  (The ordinary quarter waves were measured on
@@ -1011,14 +986,14 @@ struct ClassFilter {
   uint32_t wmask = 0u, wval = 0u, id_and = 0xFFFFFFFFu;
 };
 
-template <bool TRACE, bool AUX = true, int NSEM = 0, class Out = PlainOut>
+template <bool AUX = true, int NSEM = 0, class Out = PlainOut>
 __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* __restrict__ qid,
                                             uint32_t* __restrict__ qpos, const int lane,
                                             const int quarter, const uint32_t r_begin,
                                             const uint32_t r_end, const int x0, const int y0,
                                             const int W, const int H,
                                             const uint32_t* __restrict__ point_list,
-                                            const RecView rec, const Out& out, WaveTrace* tr,
+                                            const RecView rec, const Out& out,
                                             CkptWriter ckw, const SemSrc sem = SemSrc{nullptr, 0, nullptr},
                                             float* __restrict__ out_semantic = nullptr,
                                             float* __restrict__ semrows = nullptr /* LDS: WAVE x SEM_ROW */,
@@ -1084,7 +1059,6 @@ __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* _
         count += (uint32_t)__popcll(m);
       }
       in_pos = nxt;
-      if (TRACE) tr->batches++;
     }
 
     // the ring entries written by FILL are read by OTHER lanes in POP: keep the compiler from
@@ -1105,7 +1079,6 @@ __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* _
 
     // ---- BLEND the previous batch while the gather is in flight ----
     if (ncur > 0) {
-      const uint64_t tc0 = TRACE ? __builtin_readcyclecounter() : 0;
       const bool keep = ((uint32_t)lane < ncur) &&
                         !splat_misses_rect(a.x, a.y, b.x, b.y, b.z, a.w, rx0, rx1, ry0, ry1);
       const uint64_t mask = __ballot(keep);
@@ -1123,27 +1096,11 @@ __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* _
         store_pair_half(my, cnt + lane, 0.f, 0.f, zq, 0.f, make_float4(0.f, 0.f, 0.f, 0.f), 0u);
         if (NSEM > 0) sem_stage(semrows, cnt + lane, sem.semantics, sem.S, 0u, false);
       }
-      if (TRACE) tr->survivors += (uint32_t)cnt;
       __builtin_amdgcn_wave_barrier();
-      const uint64_t tc1 = TRACE ? __builtin_readcyclecounter() : 0;
-      if (TRACE) tr->t_stage += (uint32_t)(tc1 - tc0);
       if (batch_safe) {
-        for (int j0 = 0; j0 < cnt; j0 += 4) {
-          const bool blended = blend_quad<AUX, NSEM, true>(st, my, j0, pxf, (float)py, &sa, semb, lane);
-          if (TRACE && blended) tr->blends++;
-        }
+        for (int j0 = 0; j0 < cnt; j0 += 4) blend_quad<AUX, NSEM, true>(st, my, j0, pxf, (float)py, &sa, semb, lane);
       } else {
-        for (int j0 = 0; j0 < cnt; j0 += 4) {
-          const bool blended = blend_quad<AUX, NSEM, false>(st, my, j0, pxf, (float)py, &sa, semb, lane);
-          if (TRACE && blended) tr->blends++;
-        }
-      }
-      if (TRACE) {
-        const uint64_t tc2 = __builtin_readcyclecounter();
-        tr->t_loop += (uint32_t)(tc2 - tc1);
-        const int na = (int)__popcll(alive);   // live pixels when this batch was culled
-        const int bk = na <= 2 ? 0 : (na <= 8 ? 1 : (na <= 24 ? 2 : 3));
-        tr->it[bk]++; tr->cyc[bk] += (uint32_t)(tc2 - tc0);
+        for (int j0 = 0; j0 < cnt; j0 += 4) blend_quad<AUX, NSEM, false>(st, my, j0, pxf, (float)py, &sa, semb, lane);
       }
       // every entry up to the batch's last ring entry is now blended, masked out or culled
       if (AUX) ckpt_batch_end(ckw, lane, st, (uint32_t)__builtin_amdgcn_readlane((int)pos, (int)ncur - 1));
@@ -1221,9 +1178,8 @@ __device__ __forceinline__ void pc_store(uint32_t* p, const uint32_t v) {
 // waits until ready() (false: the consumer stopped, or the hand-over timed out -- reported, see above)
 template <class Cond>
 __device__ __forceinline__ bool pc_wait(PCCtrl* __restrict__ ctl, const PCErr err, const int lane, const bool poll_stop,
-                                        Cond ready, WaveTrace* tr = nullptr /* experiment build: cycles waited */) {
+                                        Cond ready) {
   if (ready()) return true;
-  const uint64_t t0 = tr ? __builtin_readcyclecounter() : 0;
   uint32_t spins = 0;
   bool ok = true;
   while (!ready()) {
@@ -1231,12 +1187,11 @@ __device__ __forceinline__ bool pc_wait(PCCtrl* __restrict__ ctl, const PCErr er
     if (++spins > PC_SPIN_LIMIT) { pc_fail(err, lane); ok = false; break; }
     __builtin_amdgcn_s_sleep(1);
   }
-  if (tr) { tr->t_stage += (uint32_t)(__builtin_readcyclecounter() - t0); tr->blends++; }
   return ok;
 }
 
 // Round 5.  With nothing else on the chip the 96 class-0 tiles of the bench frame take 0.197 ms
-// (experiment build `only0pair`): that chain, not throughput, set the render launch's length.  Per-wave
+// (measured with those workgroups alone): that chain, not throughput, set the render launch's length.  Per-wave
 // traces of a three-stage split of the consumer (evaluator / blender waves, built and measured: no gain,
 // twice the wave slots -- DESIGN_EXPERIMENTS.md) showed BOTH halves of the pair within 10 % of each other:
 //   producer  1.9 us per batch for 0.7 us of work -- one list window and one record gather in flight
@@ -1254,7 +1209,7 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
                                             const int quarter, const uint32_t r_begin,
                                             const uint32_t r_end,
                                             const uint32_t* __restrict__ point_list,
-                                            const RecView rec, const PCErr err, WaveTrace* tr = nullptr,
+                                            const RecView rec, const PCErr err,
                                             const SemSrc sem = SemSrc{nullptr, 0, nullptr},
                                             float* __restrict__ semrows0 = nullptr /* LDS rows of buf0 / buf1 */,
                                             float* __restrict__ semrows1 = nullptr, const ClassFilter cf = ClassFilter{}) {
@@ -1282,7 +1237,6 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
       store_pair_half(my, cnt + lane, 0.f, 0.f, zq, 0.f, make_float4(0.f, 0.f, 0.f, 0.f), 0u);
       if (WITH_SEM) sem_stage(my == buf0 ? semrows0 : semrows1, cnt + lane, sem.semantics, sem.S, 0u, false);
     }
-    if (tr) { tr->batches++; tr->survivors += (uint32_t)cnt; }
     pc_store(&ctl->flag[cur], ((uint32_t)cnt + 1u) | (safe ? PC_SAFE : 0u));
     cur ^= 1;
   };
@@ -1324,7 +1278,7 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
       const bool safe0 = __ballot(k0 && !splat_power_never_positive(splat_q(b0.x, b0.y, b0.z))) == 0ull;
       const bool safe1 = __ballot(k1 && !splat_power_never_positive(splat_q(b1.x, b1.y, b1.z))) == 0ull;
       if (n0 + n1 > 0) {
-        if (!pc_wait(ctl, err, lane, true, buffer_free, tr)) return;
+        if (!pc_wait(ctl, err, lane, true, buffer_free)) return;
         float4* my = cur ? buf1 : buf0;
         if (n0 + n1 <= WAVE) {   // one batch (list order: the first half's survivors first)
           put(my, k0, m0, 0, a0, b0, c0, pos0, id0);
@@ -1333,7 +1287,7 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
         } else {                 // two batches
           put(my, k0, m0, 0, a0, b0, c0, pos0, id0);
           publish(my, n0, safe0);
-          if (!pc_wait(ctl, err, lane, true, buffer_free, tr)) return;
+          if (!pc_wait(ctl, err, lane, true, buffer_free)) return;
           my = cur ? buf1 : buf0;
           put(my, k1, m1, 0, a1, b1, c1, pos1, id1);
           publish(my, n1, safe1);
@@ -1345,7 +1299,7 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
     ncur = nn;
     if (ncur == 0 && ls.exhausted()) break;
   }
-  if (!pc_wait(ctl, err, lane, true, buffer_free, tr)) return;   // end-of-list marker
+  if (!pc_wait(ctl, err, lane, true, buffer_free)) return;   // end-of-list marker
   pc_store(&ctl->flag[cur], PC_DONE);
 }
 
@@ -1380,7 +1334,7 @@ __device__ __forceinline__ void pc_consumer(const float4* __restrict__ buf0,
                                             const Out& out, CkptWriter ckw,
                                             const uint32_t len, const PCErr err,
                                             const SemSrc sem = SemSrc{nullptr, 0, nullptr},
-                                            float* __restrict__ out_semantic = nullptr, WaveTrace* tr = nullptr,
+                                            float* __restrict__ out_semantic = nullptr,
                                             const float* __restrict__ semrows0 = nullptr,
                                             const float* __restrict__ semrows1 = nullptr,
                                             float* __restrict__ t_lo = nullptr /* LDS: 8 x WAVE floats each, for the */,
@@ -1398,10 +1352,9 @@ __device__ __forceinline__ void pc_consumer(const float4* __restrict__ buf0,
   if (~st.done[0] == 0ull) pc_store(&ctl->stop, 1u);   // nothing to do (quarter outside the image)
   else for (;;) {
     uint32_t f = 0;
-    if (!pc_wait(ctl, err, lane, false, [&]() { f = pc_load(&ctl->flag[cur]); return f != 0u; }, tr)) break;
+    if (!pc_wait(ctl, err, lane, false, [&]() { f = pc_load(&ctl->flag[cur]); return f != 0u; })) break;
     if (f == PC_DONE) break;
     const int cnt = (int)((f & (PC_SAFE - 1u)) - 1u);
-    if (tr) { tr->batches++; tr->survivors += (uint32_t)cnt; }
     const float4* my = cur ? buf1 : buf0;
     const SemSrc semb = {sem.semantics, sem.S, cur ? semrows1 : semrows0};
     if (f & PC_SAFE) pc_blend_batch<AUX, NSEM, true>(st, my, cnt, pxf, pyf, &sa, semb, lane);
@@ -1497,12 +1450,8 @@ __device__ __forceinline__ void blend_quad_layers(WavePix<1>& sa, WavePix<1>& sb
   const SemSrc nosem = {nullptr, 0, nullptr};
   SemAcc<0>* nosa = nullptr;
   blend_quad_tail<false, 0>(sa, cols, alpha, ok, nosa, nosem, j0, lane);
-#if !(GRPG_LAYERS_ABLATE & 2)   // experiment builds (wrong images): what does a state cost?
   if (anyb & ~sb.done[0]) blend_quad_tail<false, 0>(sb, cols, alpha, okb, nosa, nosem, j0, lane);
-#endif
-#if !(GRPG_LAYERS_ABLATE & 1)
   if (anyo & ~so.done[0]) blend_quad_tail<false, 0>(so, cols, alpha, oko, nosa, nosem, j0, lane);
-#endif
 }
 
 // the three states of a quarter wave and what the walk needs to know about them
@@ -1518,11 +1467,7 @@ struct Layers3 {
   // splat the composition has (same bits), the object layer none
   __device__ __forceinline__ void fork() { if (!forked) { b = a; forked = true; } }
   __device__ __forceinline__ uint64_t live_ab() const { return forked ? ~(a.done[0] & b.done[0]) : ~a.done[0]; }
-#if GRPG_LAYERS_ABLATE & 1   // experiment build (wrong images): the object layer never keeps a walk alive
-  __device__ __forceinline__ uint64_t live_all() const { return live_ab(); }
-#else
   __device__ __forceinline__ uint64_t live_all() const { return forked ? (live_ab() | ~o.done[0]) : ~outside; }
-#endif
   template <class Out>
   __device__ __forceinline__ void write(const Out& out, const int px, const int py, const int W, const int H) {
     if (!forked) b = a;
@@ -1664,6 +1609,7 @@ __device__ __forceinline__ ClassFilter layer_filter(const int role) {
 // A frame with semantic planes (NSEM > 0) carries 16 accumulator registers per lane (MFMA) and 4 KB of
 // staged rows per wave: 3 waves per SIMD / 3 workgroups per CU.
 constexpr int RENDER_MIN_WAVES = 4;
+constexpr int LAYERS_MIN_WAVES = 4;   // waves per SIMD the layered kernel is allocated for
 
 template <bool LAYERS, bool EPI> struct FrameOut { typedef PlainOutT<EPI> type; };
 template <bool EPI> struct FrameOut<true, EPI> { typedef LayersOutT<EPI> type; };
@@ -1678,12 +1624,9 @@ __device__ __forceinline__ LayersOutT<EPI> make_out(const PlainOutT<EPI>& p, con
 // neighbouring tiles are similarly long, contiguous eighths unbalance the XCDs), occupancy capped
 // with unused LDS, one splat per iteration in the light path, persistent waves.
 // LAYERS: a layered frame (above) -- the same launch structure, one state where the tile holds no object entry
-#ifndef GRPG_LAYERS_MIN_WAVES   // experiment builds: waves per SIMD the layered kernel is allocated for
-#define GRPG_LAYERS_MIN_WAVES 4
-#endif
 // EPI: the frame epilogue (FrameEpi above) behind the blend, evaluation frames only
-template <bool WRITE_AUX, int GPI_L, bool TRACE = false, int NSEM = 0, bool LAYERS = false, bool EPI = false>
-__global__ void __launch_bounds__(256, NSEM > 0 ? 3 : (LAYERS ? GRPG_LAYERS_MIN_WAVES : RENDER_MIN_WAVES))
+template <bool WRITE_AUX, int GPI_L, int NSEM = 0, bool LAYERS = false, bool EPI = false>
+__global__ void __launch_bounds__(256, NSEM > 0 ? 3 : (LAYERS ? LAYERS_MIN_WAVES : RENDER_MIN_WAVES))
 render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
                       const RecView rec, const int W, const int H, const int gx,
                       const uint32_t T, const uint32_t* __restrict__ work,
@@ -1692,10 +1635,9 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
                       float* __restrict__ out_alpha, uint32_t* __restrict__ n_contrib,
                       const uint32_t pc_slots, const CkptArgs ck, const PCErr pc_err,
                       const SemSrc sem, float* __restrict__ out_semantic,
-                      uint32_t* __restrict__ trace = nullptr, const int ablate = 0,
                       const LayerOut lo = LayerOut{nullptr, nullptr, nullptr, nullptr, nullptr},
                       const TileObjBits ob = TileObjBits{nullptr, 0}, const FrameEpi epi = FrameEpi{}) {
-  static_assert(!(LAYERS || EPI) || (!WRITE_AUX && NSEM == 0 && !TRACE), "layered frames / frame epilogue: evaluation only, no semantic planes");
+  static_assert(!(LAYERS || EPI) || (!WRITE_AUX && NSEM == 0), "layered frames / frame epilogue: evaluation only, no semantic planes");
   typedef typename FrameOut<LAYERS, EPI>::type Out;
   const Out out = make_out(PlainOutT<EPI>{bg, out_color, out_depth, out_alpha, n_contrib, W, H, epi}, lo, (Out*)nullptr);
   __shared__ float4 s_rec[RW_WAVES][WAVE * REC_F4];
@@ -1704,15 +1646,7 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
   __shared__ PCCtrl s_ctl[2];
   // staged semantic rows of the batch being blended: per heavy wave, or per batch buffer of the pairs
   __shared__ float s_sem[NSEM > 0 ? RW_WAVES : 1][NSEM > 0 ? WAVE * SEM_ROW : 4];
-#ifdef GRPG_RENDER_LDS_PAD   // experiment build: unused LDS that caps the workgroups per CU
-  __shared__ uint32_t s_pad[GRPG_RENDER_LDS_PAD / 4];
-  if (W < 0) s_pad[threadIdx.x] = (uint32_t)H;   // never true: keeps the array allocated
-  if (W < -1) out_color[0] = (float)s_pad[0];
-#endif
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  WaveTrace tr = {0, 0, 0, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
-  const uint64_t t_start = TRACE ? wall_clock64() : 0;
-  uint32_t tr_tile = 0xFFFFFFFFu, tr_len = 0;
   const uint32_t n0 = work[0], n1 = work[1], n2 = work[2], nlight = work[3];
   const uint32_t* lists = work + NUM_CLASSES;
   if (WRITE_AUX && ck.bin_hdr != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1740,12 +1674,6 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
       bx -= ndw;
     }
   }
-#ifdef GRPG_RENDER_ONLY_CLASS0   // experiment build: the class-0 tiles alone (their chain, nothing beside it)
-  if (bx >= pc_n) return;
-#endif
-#ifdef GRPG_RENDER_NO_CLASS0     // experiment build: everything BUT the class-0 tiles (the throughput part)
-  if (bx < pc_n) return;
-#endif
   if (bx < pc_n) {
     const uint32_t pc_ti = LAYERS ? bx / 6u : bx >> 1;
     uint32_t pc_sub = LAYERS ? bx - 6u * pc_ti : bx & 1u;
@@ -1764,9 +1692,9 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
           const CkptWriter nock = ckpt_writer(ck, tile, wave, rb, re);
           const SemSrc nosem = {nullptr, 0, nullptr};
 #define LAYER_HEAVY(R)                                                                                                \
-          blend_heavy<false, false, 0>(s_rec[wave], s_qid[wave], s_qpos[wave], lane, wave, rb, re, tx * TILE,         \
-                                       ty * TILE + wave * 4, W, H, point_list, rec, LayerRoleOut<R, Out>{out}, nullptr, \
-                                       nock, nosem, nullptr, nullptr, cf)
+          blend_heavy<false, 0>(s_rec[wave], s_qid[wave], s_qpos[wave], lane, wave, rb, re, tx * TILE,                \
+                                ty * TILE + wave * 4, W, H, point_list, rec, LayerRoleOut<R, Out>{out},              \
+                                nock, nosem, nullptr, nullptr, cf)
           if (pc_sub == 0u) LAYER_HEAVY(0); else if (pc_sub == 1u) LAYER_HEAVY(1); else LAYER_HEAVY(2);
 #undef LAYER_HEAVY
           return;
@@ -1786,7 +1714,6 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
       s_ctl[slot].box[2] = (float)y0; s_ctl[slot].box[3] = (float)(y0 + 3);
     }
     __syncthreads();   // the only workgroup barrier: all 4 waves of the workgroup take this branch
-    WaveTrace* const trp = TRACE ? &tr : nullptr;
     if constexpr (LAYERS) {
       if (role >= 0) {   // a layer's own wave pairs on a tile with object entries
         const SemSrc nosem = {nullptr, 0, nullptr};
@@ -1799,7 +1726,7 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
 #undef LAYER_CONSUMER
         } else {
           pc_producer<false>(s_rec[slot], s_rec[slot + 2], s_qid[wave], s_qpos[wave], &s_ctl[slot], lane, q, rb, re,
-                             point_list, rec, pc_err, nullptr, nosem, nullptr, nullptr, layer_filter(role));
+                             point_list, rec, pc_err, nosem, nullptr, nullptr, layer_filter(role));
         }
         return;
       }
@@ -1807,20 +1734,12 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
     if (wave < 2) {
       pc_consumer<WRITE_AUX, NSEM>(s_rec[slot], s_rec[slot + 2], &s_ctl[slot], lane, x0, y0, W, H, out,
                   ckpt_writer(ck, tile, q, rb, re), re - rb, pc_err, sem,
-                  out_semantic, trp, s_sem[NSEM > 0 ? slot : 0], s_sem[NSEM > 0 ? slot + 2 : 0],
+                  out_semantic, s_sem[NSEM > 0 ? slot : 0], s_sem[NSEM > 0 ? slot + 2 : 0],
                   reinterpret_cast<float*>(s_qid[wave]), reinterpret_cast<float*>(s_qpos[wave]));
       if (WRITE_AUX && q == 0) ckpt_publish_items(ck, lane, tile, re - rb);
     } else
       pc_producer<(NSEM > 0)>(s_rec[slot], s_rec[slot + 2], s_qid[wave], s_qpos[wave], &s_ctl[slot], lane, q,
-                  rb, re, point_list, rec, pc_err, trp, sem, s_sem[NSEM > 0 ? slot : 0], s_sem[NSEM > 0 ? slot + 2 : 0]);
-    if (TRACE && lane == 0) {   // class-0 roles: waves 0, 1 consumers, 2, 3 producers
-      // [0] tile | 0x40000000  [1] list length  [2] batches  [3] survivors  [4] waits
-      // [5] wave life (wall clock ticks)  [6] start  [7] wave | waiting cycles / 256 << 4
-      uint32_t* o = trace + ((size_t)blockIdx.x * RW_WAVES + wave) * 8;
-      o[0] = tile | 0x40000000u; o[1] = re - rb; o[2] = tr.batches; o[3] = tr.survivors; o[4] = tr.blends;
-      o[5] = (uint32_t)(wall_clock64() - t_start); o[6] = (uint32_t)(t_start & 0xFFFFFFFFu);
-      o[7] = (uint32_t)wave | ((tr.t_stage >> 8) << 4);
-    }
+                  rb, re, point_list, rec, pc_err, sem, s_sem[NSEM > 0 ? slot : 0], s_sem[NSEM > 0 ? slot + 2 : 0]);
     return;
   }
   // Dispatch order (longest processing time first): class 0, class 1, the LIGHT tiles, class 2.
@@ -1838,7 +1757,6 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
     const uint2 range = ranges[tile];
     const uint32_t rb = __builtin_amdgcn_readfirstlane(range.x);
     const uint32_t re = __builtin_amdgcn_readfirstlane(range.y);
-    tr_tile = tile; tr_len = re - rb;
     if constexpr (LAYERS) {
       if (ob.tile(tile)) {   // object entries in the list: three states (forked late)
         blend_heavy_layers(s_rec[wave], s_qid[wave], s_qpos[wave], lane, wave, rb, re, tx * TILE, ty * TILE + wave * 4,
@@ -1846,8 +1764,8 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
         return;
       }
     }
-    blend_heavy<TRACE, WRITE_AUX, NSEM>(s_rec[wave], s_qid[wave], s_qpos[wave], lane, wave, rb, re, tx * TILE,
-                       ty * TILE + wave * 4, W, H, point_list, rec, out, &tr, ckpt_writer(ck, tile, wave, rb, re),
+    blend_heavy<WRITE_AUX, NSEM>(s_rec[wave], s_qid[wave], s_qpos[wave], lane, wave, rb, re, tx * TILE,
+                       ty * TILE + wave * 4, W, H, point_list, rec, out, ckpt_writer(ck, tile, wave, rb, re),
                        sem, out_semantic, s_sem[NSEM > 0 ? wave : 0]);
     if (WRITE_AUX && wave == 0) ckpt_publish_items(ck, lane, tile, re - rb);
   } else {
@@ -1859,10 +1777,8 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
     const uint2 range = ranges[tile];
     const uint32_t rb = __builtin_amdgcn_readfirstlane(range.x);
     const uint32_t re = __builtin_amdgcn_readfirstlane(range.y);
-    tr_tile = tile | 0x80000000u; tr_len = re - rb;
     // (a layered frame: light tiles hold no object entry -- the tile scan sends the others down the heavy path)
-    blend_rect<4, GPI_L, WRITE_AUX, TRACE>(s_rec[wave], lane, rb, re, tx * TILE, ty * TILE, W, H,
-                                           point_list, rec, out, &tr, ablate);
+    blend_rect<4, GPI_L, WRITE_AUX>(s_rec[wave], lane, rb, re, tx * TILE, ty * TILE, W, H, point_list, rec, out);
     if (NSEM > 0) {
       // a semantic frame sends every non-empty tile down the heavy path (tile_classes): what arrives
       // here holds no splat at all -- its semantic planes are zero (they get no background)
@@ -1872,17 +1788,6 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
         if (px < W && py0 + k < H)
           for (int c = 0; c < sem.S && c < NSEM; c++) out_semantic[(size_t)c * HW + (size_t)(py0 + k) * W + px] = 0.f;
     }
-  }
-  if (TRACE && lane == 0) {   // per-wave trace record (experiment build -DGRPG_TRACE)
-    const uint64_t t_end = wall_clock64();
-    uint32_t* o = trace + ((size_t)blockIdx.x * RW_WAVES + wave) * 8;
-    o[0] = tr_tile; o[1] = tr_len; o[2] = tr.batches; o[3] = tr.survivors; o[4] = tr.blends;
-    o[5] = (uint32_t)(t_end - t_start); o[6] = (uint32_t)(t_start & 0xFFFFFFFFu);
-    o[7] = (uint32_t)wave | ((tr.t_stage >> 8) << 4);   // stage cycles / 256 in the upper bits
-    o[2] = tr.batches | 0u; o[4] = tr.blends;
-    trace[(size_t)gridDim.x * RW_WAVES * 8 + ((size_t)blockIdx.x * RW_WAVES + wave)] = tr.t_loop;
-    uint32_t* o2 = trace + (size_t)gridDim.x * RW_WAVES * 9 + ((size_t)blockIdx.x * RW_WAVES + wave) * 8;
-    for (int i = 0; i < 4; i++) { o2[i] = tr.it[i]; o2[4 + i] = tr.cyc[i]; }
   }
 }
 
@@ -1958,13 +1863,13 @@ void launch_render_layers(hipStream_t s, const uint2* ranges, uint32_t* point_li
   const SemSrc sem = {nullptr, 0, nullptr};
   if (epi) {
     const FrameEpi fe = make_frame_epi(epi, W, true);
-    render_forward_kernel<false, 2, false, 0, true, true><<<ntiles + pc_slots + fe.drain_wgs, 256, 0, s>>>(
+    render_forward_kernel<false, 2, 0, true, true><<<ntiles + pc_slots + fe.drain_wgs, 256, 0, s>>>(
         ranges, point_list, rec, W, H, gx, (uint32_t)ntiles, work, bg, out_color, out_depth, out_alpha, nullptr,
-        pc_slots, ck, pc_err, sem, nullptr, nullptr, 0, lo, cls.obj, fe);
+        pc_slots, ck, pc_err, sem, nullptr, lo, cls.obj, fe);
   } else
-    render_forward_kernel<false, 2, false, 0, true><<<ntiles + pc_slots, 256, 0, s>>>(
+    render_forward_kernel<false, 2, 0, true><<<ntiles + pc_slots, 256, 0, s>>>(
         ranges, point_list, rec, W, H, gx, (uint32_t)ntiles, work, bg, out_color, out_depth, out_alpha, nullptr,
-        pc_slots, ck, pc_err, sem, nullptr, nullptr, 0, lo, cls.obj);
+        pc_slots, ck, pc_err, sem, nullptr, lo, cls.obj);
 }
 
 // N-channel "semantic" planes (forward.cu:442-444): same traversal and the same accept/reject
@@ -2075,35 +1980,17 @@ void launch_render_forward(hipStream_t s, const uint2* ranges, const uint32_t* p
   // aux == false (no backward will follow): n_contrib is neither tracked nor written
 #define RF_ARGS ranges, point_list, rec, W, H, gx, (uint32_t)ntiles, work, bg, out_color, out_depth, \
                 out_alpha, n_contrib, pc_slots, ck, pc_err, sem, out_semantic
-#ifdef GRPG_TRACE   // experiment build: per-wave cycle counts and survivor statistics to a file
-  static const char* trace_path = getenv("GRPG_RENDER_TRACE");
-  if (trace_path && S == 0) {
-    uint32_t* d_trace = nullptr;
-    const size_t words = (size_t)(ntiles + pc_slots) * RW_WAVES * 17;
-    if (hipMalloc((void**)&d_trace, words * 4) == hipSuccess) {
-      (void)hipMemsetAsync(d_trace, 0xFF, words * 4, s);
-      render_forward_kernel<true, 1, true><<<ntiles + pc_slots, 256, 0, s>>>(
-          RF_ARGS, d_trace, getenv("GRPG_RENDER_ABLATE") ? atoi(getenv("GRPG_RENDER_ABLATE")) : 0);
-      std::vector<uint32_t> h(words);
-      (void)hipMemcpyAsync(h.data(), d_trace, words * 4, hipMemcpyDeviceToHost, s);
-      (void)hipStreamSynchronize(s);
-      if (FILE* f = fopen(trace_path, "wb")) { fwrite(h.data(), 4, words, f); fclose(f); }
-      (void)hipFree(d_trace);
-      return;
-    }
-  }
-#endif
   // the light (4 pixels per lane) path evaluates two splats per inner iteration (one: measured
   // slower); the heavy path always evaluates quads
   if (epi != nullptr && !aux && S == 0) {   // evaluation frame with the callers' epilogue fused in (grpg_forward_frame)
     const FrameEpi fe = make_frame_epi(epi, W, true);
-    render_forward_kernel<false, 2, false, 0, false, true><<<ntiles + pc_slots + fe.drain_wgs, 256, 0, s>>>(
-        RF_ARGS, nullptr, 0, LayerOut{nullptr, nullptr, nullptr, nullptr, nullptr}, TileObjBits{nullptr, 0}, fe);
+    render_forward_kernel<false, 2, 0, false, true><<<ntiles + pc_slots + fe.drain_wgs, 256, 0, s>>>(
+        RF_ARGS, LayerOut{nullptr, nullptr, nullptr, nullptr, nullptr}, TileObjBits{nullptr, 0}, fe);
   } else if (S > 0) {
     // semantic planes ride in the heavy path: up to RENDER_NSEM channels in this launch, the rest
     // (S > RENDER_NSEM) in the stand-alone kernel below
-    if (aux) render_forward_kernel<true, 2, false, RENDER_NSEM><<<ntiles + pc_slots, 256, 0, s>>>(RF_ARGS);
-    else render_forward_kernel<false, 2, false, RENDER_NSEM><<<ntiles + pc_slots, 256, 0, s>>>(RF_ARGS);
+    if (aux) render_forward_kernel<true, 2, RENDER_NSEM><<<ntiles + pc_slots, 256, 0, s>>>(RF_ARGS);
+    else render_forward_kernel<false, 2, RENDER_NSEM><<<ntiles + pc_slots, 256, 0, s>>>(RF_ARGS);
   } else {
     if (aux) render_forward_kernel<true, 2><<<ntiles + pc_slots, 256, 0, s>>>(RF_ARGS);
     else render_forward_kernel<false, 2><<<ntiles + pc_slots, 256, 0, s>>>(RF_ARGS);

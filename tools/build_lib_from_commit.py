@@ -1,7 +1,6 @@
-"""Build libgrpg_rasterizer_<name>.so from the csrc/ of another commit (with this tree's flags) for an A/B on one
-box under this tree's binding:  python tools/build_lib_from_commit.py <commit> <name>
-(tools/gpu_ab_variants.sh "<name>" LD_PRELOADs it).  Boxes of the pool differ by ~3 %: a delta is only trustworthy
-against the previous library on ONE box."""
+"""Build build/variants/libgrpg_rasterizer_<name>.so from the csrc/ of another commit (with this tree's flags), to be
+driven through the C ABI (ctypes) beside this tree's library:  python tools/build_lib_from_commit.py <commit> <name>
+Boxes of the pool differ by ~3 %: a delta is only trustworthy against the previous library on ONE box."""
 import os, shutil, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

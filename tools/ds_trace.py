@@ -1,14 +1,16 @@
 """Phase timing of the depth sort's scatter passes (experiment build -DGRPG_DS_TRACE).
-usage on the GPU box:  LD_PRELOAD=build/variants/libgrpg_rasterizer_dstrace.so python tools/ds_trace.py"""
+usage:  python -c "from gaussianrpg_amd import build; build.build_variant('dstrace')" && python tools/ds_trace.py
+The variant library is loaded with RTLD_GLOBAL before the package is imported, so the binding's calls
+resolve to it in this process; nothing is preloaded."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+lib = ctypes.CDLL(os.path.join(ROOT, "build", "variants", "libgrpg_rasterizer_dstrace.so"), mode=ctypes.RTLD_GLOBAL)
 import torch
 from gaussianrpg_amd import harness as hz
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 dev = torch.device("cuda:0")
 sc = hz.street_scene(2_000_000, seed=2, sh_degree=1).to(dev)
-lib = ctypes.CDLL(os.path.join(ROOT, "build", "variants", "libgrpg_rasterizer_dstrace.so"))
 names = ["start", "loads issued", "sweep done", "barrier", "digit bases", "ranked", "barrier", "staged", "written"]
 for k in range(4):
     cam = hz.trajectory_camera(k, device=dev)

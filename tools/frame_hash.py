@@ -1,5 +1,5 @@
 """Hashes of the planes of bench frames (evaluation and training-mode forward), for bit-for-bit comparisons of
-two library builds on one box:  python tools/frame_hash.py  vs  LD_PRELOAD=build/variants/lib..._X.so python tools/frame_hash.py"""
+two builds on one box: run it from each build's own checkout and compare the printed lines."""
 import hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

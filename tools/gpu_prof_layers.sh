@@ -1,10 +1,9 @@
 #!/bin/bash
-# kernel times of the layered frame: bash tools/gpu_prof_layers.sh <case> [variant]
+# kernel times of the layered frame: bash tools/gpu_prof_layers.sh <case>
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$ROOT/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-c=$1; v=${2:-}
-pre=""; [ -n "$v" ] && pre="$ROOT/build/variants/libgrpg_rasterizer_$v.so"
-LD_PRELOAD=$pre timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_layers_$c$v -o stats -- python $ROOT/tools/prof_layers.py $c 20 > /dev/null 2> $OUT/prof_layers_$c$v.err
+c=$1; v=""
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_layers_$c$v -o stats -- python $ROOT/tools/prof_layers.py $c 20 > /dev/null 2> $OUT/prof_layers_$c$v.err
 f=$(find $OUT/prof_layers_$c$v -name "*kernel_stats.csv" | head -1)
 python3 - "$f" "$c$v" <<'PY'
 import csv,sys
