@@ -45,6 +45,9 @@ HIP_UNITS = {
     # fused lidar / sky / object-alpha losses: the error plane bit-identical to PyTorch's float32
     # expression (no FMA contraction); integer atomics only
     "aux_loss.hip": ["-ffp-contract=off"],
+    # fused semantic cross-entropy: the backward recomputes the forward's softmax input bit for bit (no FMA
+    # contraction); no atomics, deterministic fixed-order reduction
+    "semantic_loss.hip": ["-ffp-contract=off"],
     # fused multi-tensor Adam step + densification statistics: one rounding per operation, in the order
     # written, on the vector and the scalar path alike (bit-identical across alignments)
     "optim.hip": ["-ffp-contract=off"],

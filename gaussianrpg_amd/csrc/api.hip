@@ -1867,6 +1867,64 @@ int grpg_aux_loss_backward(int height, int width, const float* depth, const floa
   return GRPG_OK;
 }
 
+// ---- fused semantic cross-entropy loss (semantic_loss.hip) ----
+size_t grpg_semantic_ce_workspace_bytes(int height, int width) {
+  if (height <= 0 || width <= 0 || (long long)height * width > 0x7FFFFFFFll) return 0;
+  return semantic_ce_workspace_bytes(height, width);
+}
+
+namespace {
+int semantic_ce_check(int S, int height, int width, const float* sem, const void* target, int target_bytes,
+                      int mode, const void* workspace) {
+  if (S < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: S must be at least 1");
+  if (height <= 0 || width <= 0)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: height and width must be positive");
+  if ((long long)height * width > 0x7FFFFFFFll)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: H*W must be < 2^31");
+  if (!sem || !target) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL sem / target");
+  if (mode != 0 && mode != 1)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: mode must be 0 (logits) or 1 (probabilities)");
+  if (target_bytes != 4 && target_bytes != 8)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: target_bytes must be 4 (int32) or 8 (int64)");
+  if (((uintptr_t)sem & 3) || ((uintptr_t)target & (uintptr_t)(target_bytes - 1)))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: sem must be 4-byte aligned, target aligned to its width");
+  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL workspace");
+  if ((uintptr_t)workspace & 15)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: workspace must be 16-byte aligned");
+  return GRPG_OK;
+}
+}  // namespace
+
+int grpg_semantic_ce_forward(int S, int height, int width, const float* sem, const void* target, int target_bytes,
+                             int mode, float* stats, unsigned char* labels, void* workspace, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (int rc = semantic_ce_check(S, height, width, sem, target, target_bytes, mode, workspace)) return rc;
+  if (!stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL stats");
+  if (((uintptr_t)stats & 3)) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: stats must be 4-byte aligned");
+  if (labels && S > 256)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: the uint8 label plane needs S <= 256");
+  launch_semantic_ce_forward((hipStream_t)hip_stream, S, height, width, sem, target, target_bytes, mode, stats,
+                             labels, (char*)workspace);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_semantic_ce_backward(int S, int height, int width, const float* sem, const void* target, int target_bytes,
+                              int mode, const float* grad_loss, const void* workspace, float* grad_sem,
+                              void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (int rc = semantic_ce_check(S, height, width, sem, target, target_bytes, mode, workspace)) return rc;
+  if (!grad_loss || !grad_sem) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL grad_loss / grad_sem");
+  if (((uintptr_t)grad_loss & 3) || ((uintptr_t)grad_sem & 3))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: grad_loss and grad_sem must be 4-byte aligned");
+  launch_semantic_ce_backward((hipStream_t)hip_stream, S, height, width, sem, target, target_bytes, mode, grad_loss,
+                              (const char*)workspace, grad_sem);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
 // ---- fused multi-tensor Adam step and densification statistics (optim.hip) ----
 namespace {
 // Both entries return without a host wait, so the pinned table an asynchronous copy reads must outlive the call: a

@@ -645,6 +645,15 @@ void launch_aux_loss_backward(hipStream_t st, int H, int W, const AuxPlanes& pla
                               float lam_lidar, float lam_sky, float lam_reg, const float* grad_stats,
                               const char* workspace, float* grad_depth, float* grad_acc, float* grad_acc_obj);
 
+// fused semantic cross-entropy loss (semantic_loss.hip).  sem [S,H,W] float32, target [H,W] int64 / int32
+// (target_bytes 8 / 4), mode 0 = logits, 1 = probabilities; labels NULL or uint8 [H,W] (S <= 256).
+size_t semantic_ce_workspace_bytes(int H, int W);
+void launch_semantic_ce_forward(hipStream_t st, int S, int H, int W, const float* sem, const void* target,
+                                int target_bytes, int mode, float* stats, unsigned char* labels, char* workspace);
+void launch_semantic_ce_backward(hipStream_t st, int S, int H, int W, const float* sem, const void* target,
+                                 int target_bytes, int mode, const float* grad_loss, const char* workspace,
+                                 float* grad_sem);
+
 // fused multi-tensor Adam step and densification statistics (optim.hip).  The device tables api.hip uploads.
 constexpr uint32_t ADAM_CHUNK = 4096;      // elements per unit of work; a chunk never straddles two segments
 struct AdamSegmentDev {

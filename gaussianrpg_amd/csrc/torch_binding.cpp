@@ -1205,6 +1205,91 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> AuxLossBackward(
   return std::make_tuple(gd, ga, go);
 }
 
+// Fused semantic cross-entropy loss (gaussianrpg_amd/loss.py).  semantic: contiguous float32 [S,H,W]; target:
+// contiguous int64 or int32 [H,W] on the same device; mode 0 = logits, 1 = probabilities (raw planes).
+// Returns (stats [4], workspace, labels uint8 [H,W] or empty); the workspace carries n_valid and the per-pixel
+// logsumexp to the backward.
+namespace {
+struct SemIn {
+  int S, H, W, target_bytes;
+};
+
+SemIn semantic_args(const char* fn, const torch::Tensor& semantic, const torch::Tensor& target, const int64_t mode) {
+  TORCH_CHECK(semantic.defined() && target.defined(), fn, ": undefined tensor");
+  TORCH_CHECK(semantic.is_cuda() && target.is_cuda(), fn,
+              ": semantic and target must live on a ROCm/HIP device (no CPU path)");
+  TORCH_CHECK(semantic.device() == target.device(), fn, ": semantic and target on different devices");
+  TORCH_CHECK(semantic.scalar_type() == torch::kFloat32 && semantic.dim() == 3 && semantic.is_contiguous(), fn,
+              ": semantic must be a contiguous float32 [S,H,W] tensor");
+  TORCH_CHECK((target.scalar_type() == torch::kInt64 || target.scalar_type() == torch::kInt32) &&
+                  target.dim() == 2 && target.is_contiguous(),
+              fn, ": target must be a contiguous int64 or int32 [H,W] tensor");
+  TORCH_CHECK(target.size(0) == semantic.size(1) && target.size(1) == semantic.size(2), fn,
+              ": target must have the H x W of semantic");
+  TORCH_CHECK(semantic.size(0) >= 1 && semantic.size(0) <= 0x7FFFFFFFll, fn, ": S must be at least 1");
+  const int64_t H = semantic.size(1), W = semantic.size(2);
+  TORCH_CHECK(H > 0 && W > 0 && H * W <= 0x7FFFFFFFll, fn, ": H and W must be positive with H*W < 2^31");
+  TORCH_CHECK(mode == 0 || mode == 1, fn, ": mode must be 0 (logits) or 1 (probabilities)");
+  return SemIn{(int)semantic.size(0), (int)H, (int)W, target.scalar_type() == torch::kInt64 ? 8 : 4};
+}
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> SemanticCeForward(
+    const torch::Tensor& semantic, const torch::Tensor& target, const int64_t mode, const bool want_labels) {
+  const SemIn in = semantic_args("semantic_ce_forward", semantic, target, mode);
+  TORCH_CHECK(!want_labels || in.S <= 256, "semantic_ce_forward: the uint8 label plane needs S <= 256");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(semantic.device());
+  auto fopts = torch::TensorOptions().dtype(torch::kFloat32).device(semantic.device());
+  torch::Tensor stats = torch::empty({4}, fopts);
+  const size_t ws_bytes = grpg_semantic_ce_workspace_bytes(in.H, in.W);
+  torch::Tensor ws = torch::empty({(long long)ws_bytes}, fopts.dtype(torch::kByte));
+  torch::Tensor labels = want_labels ? torch::empty({in.H, in.W}, fopts.dtype(torch::kByte))
+                                     : torch::empty({0}, fopts.dtype(torch::kByte));
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  int rc;
+  {
+    pybind11::gil_scoped_release nogil;
+    rc = grpg_semantic_ce_forward(in.S, in.H, in.W, semantic.data_ptr<float>(), target.data_ptr(), in.target_bytes,
+                                  (int)mode, stats.data_ptr<float>(),
+                                  want_labels ? labels.data_ptr<uint8_t>() : nullptr, ws.data_ptr(), (void*)stream);
+  }
+  if (rc != GRPG_OK) raise_abi_error("grpg_semantic_ce_forward", rc);
+  return std::make_tuple(stats, ws, labels);
+}
+
+// grad_stats: the upstream gradient of the stats vector (entry 0, the loss, is used).  grad_out: None, or a
+// contiguous float32 tensor of S*H*W elements to write into (every element is overwritten).
+torch::Tensor SemanticCeBackward(const torch::Tensor& semantic, const torch::Tensor& target, const int64_t mode,
+                                 const torch::Tensor& grad_stats, const torch::Tensor& ws,
+                                 const c10::optional<torch::Tensor>& grad_out) {
+  const SemIn in = semantic_args("semantic_ce_backward", semantic, target, mode);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(semantic.device());
+  TORCH_CHECK(ws.device() == semantic.device() && ws.scalar_type() == torch::kByte && ws.is_contiguous() &&
+                  (size_t)ws.numel() == grpg_semantic_ce_workspace_bytes(in.H, in.W),
+              "semantic_ce_backward: workspace does not match");
+  const torch::Tensor g = grad_stats.to(semantic.device(), torch::kFloat32).contiguous();
+  TORCH_CHECK(g.numel() >= 1, "semantic_ce_backward: grad_stats is empty");
+  torch::Tensor grad;
+  if (grad_out) {
+    grad = *grad_out;
+    TORCH_CHECK(grad.device() == semantic.device() && grad.scalar_type() == torch::kFloat32 &&
+                    grad.is_contiguous() && grad.numel() == semantic.numel(),
+                "semantic_ce_backward: grad_out must be a contiguous float32 tensor of S*H*W elements on the device");
+  } else {
+    grad = torch::empty_like(semantic);
+  }
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  int rc;
+  {
+    pybind11::gil_scoped_release nogil;
+    rc = grpg_semantic_ce_backward(in.S, in.H, in.W, semantic.data_ptr<float>(), target.data_ptr(), in.target_bytes,
+                                   (int)mode, g.data_ptr<float>(), ws.data_ptr(), grad.data_ptr<float>(),
+                                   (void*)stream);
+  }
+  if (rc != GRPG_OK) raise_abi_error("grpg_semantic_ce_backward", rc);
+  return grad;
+}
+
 // The tail of the training iteration (gaussianrpg_amd/optim.py): optimizer.step() of every tensor of every
 // optimizer in one launch, and the densification statistics of every model in one launch.
 namespace {
@@ -1320,6 +1405,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ssim_backward", &SsimBackward);
   m.def("aux_loss_forward", &AuxLossForward);    // (stats [9], workspace)
   m.def("aux_loss_backward", &AuxLossBackward);
+  m.def("semantic_ce_forward", &SemanticCeForward);    // (stats [4], workspace, labels)
+  m.def("semantic_ce_backward", &SemanticCeBackward, pybind11::arg("semantic"), pybind11::arg("target"),
+        pybind11::arg("mode"), pybind11::arg("grad_stats"), pybind11::arg("workspace"),
+        pybind11::arg("grad_out") = pybind11::none());
   m.def("adam_step", &AdamStep);            // in place: params, exp_avgs, exp_avg_sqs
   m.def("densify_stats", &DensifyStats);    // in place: accum, denom, max_radii2D
   m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);

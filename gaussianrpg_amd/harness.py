@@ -339,15 +339,31 @@ def simulator_frame(scene: Scene, cam: CameraTensors, sky=None, K=None, w2c=None
 def train_loss(render_pkg: dict, gt_image: torch.Tensor, lidar_depth: Optional[torch.Tensor] = None,
                sky_mask: Optional[torch.Tensor] = None, lambda_l1: float = 1.0,
                lambda_depth_lidar: float = 0.1, lambda_sky: float = 0.05, *, lambda_dssim: float = 0.0,
-               mask: Optional[torch.Tensor] = None, fused_aux: bool = False) -> torch.Tensor:
+               mask: Optional[torch.Tensor] = None, fused_aux: bool = False,
+               gt_semantic: Optional[torch.Tensor] = None, lambda_semantic: float = 0.0,
+               semantic_mode: str = "logits") -> torch.Tensor:
     """The loss mix of train.py:110-127,164-176 that reaches the op's four outputs: L1 on rgb
     (loss_utils.l1_loss), the sky term on acc, the lidar term on depth / (acc + 1e-10) keeping the
-    smallest 95 % of the errors.  (SSIM, semantic and the regularisers do not change which output
+    smallest 95 % of the errors.  (SSIM and the regularisers do not change which output
     gradients are non-zero.)  lambda_dssim > 0 or a mask: the rgb term is the reference's full
     train.py:118 mix (1 - lambda_dssim) * lambda_l1 * L1 + lambda_dssim * (1 - SSIM), computed by the
     fused kernels of gaussianrpg_amd.loss; the defaults keep the plain L1 term.  fused_aux=True: the sky and
     lidar terms come from the fused kernels of gaussianrpg_amd.loss.aux_loss (no host sync; the lidar guard is
-    the reference's torch.nonzero(depth_mask).any()); the default keeps the PyTorch terms."""
+    the reference's torch.nonzero(depth_mask).any()); the default keeps the PyTorch terms.
+    lambda_semantic > 0 with gt_semantic given and S > 0 planes in render_pkg['semantic']: the semantic term of
+    train.py:129-143, lambda_semantic * gaussianrpg_amd.loss.semantic_loss (fused, no host sync; semantic_mode
+    'probabilities' takes the raw planes); the defaults leave the result as it is without these keywords."""
+    loss = _train_loss_base(render_pkg, gt_image, lidar_depth, sky_mask, lambda_l1, lambda_depth_lidar, lambda_sky,
+                            lambda_dssim, mask, fused_aux)
+    semantic = render_pkg.get("semantic")
+    if lambda_semantic > 0 and gt_semantic is not None and semantic is not None and semantic.numel() > 0:
+        from .loss import semantic_loss
+        loss = loss + lambda_semantic * semantic_loss(semantic, gt_semantic, mode=semantic_mode)
+    return loss
+
+
+def _train_loss_base(render_pkg, gt_image, lidar_depth, sky_mask, lambda_l1, lambda_depth_lidar, lambda_sky,
+                     lambda_dssim, mask, fused_aux):
     image, acc, depth = render_pkg["rgb"], render_pkg["acc"], render_pkg["depth"]
     if lambda_dssim == 0.0 and mask is None:
         loss = lambda_l1 * torch.abs(image - gt_image).mean()

@@ -32,13 +32,28 @@ masks of the same H x W:
 The lidar term keeps the reference's guard exactly, on the device: 0 with a zero gradient when no pixel is selected
 or only flat index 0 is; NaN with a zero gradient when one other pixel is.  Ties at the k-th smallest error share
 its weight evenly.  No host synchronisation in forward or backward.
+
+The semantic term of train.py (csrc/semantic_loss.hip), on float32 planes [S,H,W] or [1,S,H,W] and int64 (or int32)
+labels [H,W] or [1,H,W]:
+
+  semantic_loss(semantic, gt_semantic, mode='logits', ignore_index=-1)   == train.py:129-143 (semantic_loss)
+      F.cross_entropy(semantic[None], gt_semantic, ignore_index=-1, reduction='mean'), and 0 with a zero gradient
+      when every label is -1: the reference's torch.all(gt_semantic == -1) guard, evaluated on the device.
+      mode='probabilities' takes the RAW rendered planes and applies the normalise + log of
+      street_gaussian_renderer.py:248-256 itself, log(x / (sum_c x + 1e-8) + 1e-8): do not transform them first.
+  semantic_loss_stats(semantic, gt_semantic, mode='logits', ignore_index=-1)
+      without a gradient: a dict of device tensors, 'loss' (float32), 'n_valid', 'n_bad', 'n_correct' (exact int64)
+      and, for S <= 256, 'labels' (uint8 [H,W], the argmax channel, ties to the lowest).
+
+A label outside [-1, S) is counted in n_bad and ignored (PyTorch raises a device assert there).  Only
+ignore_index == -1 is provided.  No host synchronisation in forward or backward.
 """
 import torch
 
 from .rasterizer import _C
 
 __all__ = ["ssim", "l1_loss", "l1_ssim_loss", "aux_loss", "lidar_depth_loss", "sky_loss", "obj_acc_loss",
-           "lidar_selection"]
+           "lidar_selection", "semantic_loss", "semantic_loss_stats"]
 
 
 def _check(img1, img2, what=("img1", "img2")):
@@ -265,3 +280,87 @@ def lidar_selection(depth, acc, lidar_depth, mask=None):
         _, ws, _ = _aux_run(depth, acc, lidar_depth, mask, None, 1.0, None, None, 1.0, 0.0, 0.0)
     counts = ws[:32].view(torch.int64)
     return {"N": counts[0], "k": counts[1], "c_lt": counts[2], "c_eq": counts[3], "t": ws[32:36].view(torch.float32)[0]}
+
+
+# ---- semantic cross-entropy (csrc/semantic_loss.hip) ----
+
+_SEMANTIC_MODES = {"logits": 0, "probabilities": 1}
+
+
+class _SemanticLoss(torch.autograd.Function):
+    """[S,H,W] planes, [H,W] labels -> (stats [4]: loss, n_valid, n_bad, n_correct; workspace; labels)."""
+
+    @staticmethod
+    def forward(ctx, semantic, target, mode, want_labels):
+        stats, ws, labels = _C.semantic_ce_forward(semantic, target, mode, want_labels)
+        ctx.save_for_backward(semantic, target, ws)
+        ctx.mode = mode
+        ctx.mark_non_differentiable(ws, labels)
+        return stats, ws, labels
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_stats, _grad_ws, _grad_labels):
+        semantic, target, ws = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        if grad_stats is None:
+            grad_stats = torch.zeros(4, dtype=torch.float32, device=ws.device)
+        return _C.semantic_ce_backward(semantic, target, ctx.mode, grad_stats.contiguous(), ws), None, None, None
+
+
+def _semantic_run(semantic, gt_semantic, mode, ignore_index, want_labels):
+    if mode not in _SEMANTIC_MODES:
+        raise ValueError("gaussianrpg_amd.loss: mode must be 'logits' or 'probabilities' (got %r)" % (mode,))
+    if ignore_index != -1:
+        raise ValueError("gaussianrpg_amd.loss: only ignore_index == -1 is supported (got %r)" % (ignore_index,))
+    for t, n in ((semantic, "semantic"), (gt_semantic, "gt_semantic")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("gaussianrpg_amd.loss: %s must be a torch.Tensor" % n)
+    if semantic.dtype != torch.float32:
+        raise TypeError("gaussianrpg_amd.loss: semantic must be float32 (got %s)" % semantic.dtype)
+    if gt_semantic.dtype not in (torch.int64, torch.int32):
+        raise TypeError("gaussianrpg_amd.loss: gt_semantic must be int64 or int32 (got %s)" % gt_semantic.dtype)
+    if not (semantic.dim() == 3 or (semantic.dim() == 4 and semantic.shape[0] == 1)):
+        raise ValueError("gaussianrpg_amd.loss: semantic must be [S,H,W] or [1,S,H,W] (got %s)"
+                         % (tuple(semantic.shape),))
+    if not (gt_semantic.dim() == 2 or (gt_semantic.dim() == 3 and gt_semantic.shape[0] == 1)):
+        raise ValueError("gaussianrpg_amd.loss: gt_semantic must be [H,W] or [1,H,W] (got %s)"
+                         % (tuple(gt_semantic.shape),))
+    if tuple(semantic.shape[-2:]) != tuple(gt_semantic.shape[-2:]):
+        raise ValueError("gaussianrpg_amd.loss: semantic is %s, gt_semantic is %s"
+                         % (tuple(semantic.shape), tuple(gt_semantic.shape)))
+    if semantic.shape[-3] < 1 or semantic.shape[-2] < 1 or semantic.shape[-1] < 1:
+        raise ValueError("gaussianrpg_amd.loss: semantic must have S >= 1 planes of at least one pixel (got %s)"
+                         % (tuple(semantic.shape),))
+    if gt_semantic.requires_grad:
+        raise ValueError("gaussianrpg_amd.loss: gt_semantic requires a gradient; the fused loss differentiates only "
+                         "semantic")
+    for t, n in ((semantic, "semantic"), (gt_semantic, "gt_semantic")):
+        if not t.is_cuda:
+            raise RuntimeError("gaussianrpg_amd.loss: %s must live on a ROCm/HIP device (torch device 'cuda'); "
+                               "the fused loss is MI355X-native and has no CPU path" % n)
+    if semantic.device != gt_semantic.device:
+        raise ValueError("gaussianrpg_amd.loss: gt_semantic on %s, semantic on %s"
+                         % (gt_semantic.device, semantic.device))
+    sem = semantic.reshape(semantic.shape[-3:]).contiguous()
+    tgt = gt_semantic.reshape(gt_semantic.shape[-2:]).contiguous()
+    return _SemanticLoss.apply(sem, tgt, _SEMANTIC_MODES[mode], bool(want_labels) and sem.shape[0] <= 256)
+
+
+def semantic_loss(semantic, gt_semantic, mode="logits", ignore_index=-1):
+    """train.py:129-143: F.cross_entropy(semantic[None], gt_semantic, ignore_index=-1), 0 when every label is -1.
+    mode='probabilities': semantic holds the raw rendered planes; log(x / (sum_c x + 1e-8) + 1e-8) is applied here."""
+    return _semantic_run(semantic, gt_semantic, mode, ignore_index, False)[0][0]
+
+
+def semantic_loss_stats(semantic, gt_semantic, mode="logits", ignore_index=-1):
+    """The semantic term as the device computed it, without a gradient: a dict of device tensors, 'loss' (float32),
+    'n_valid', 'n_bad', 'n_correct' (exact int64) and, for S <= 256, 'labels' (uint8 [H,W], the argmax channel)."""
+    with torch.no_grad():
+        stats, ws, labels = _semantic_run(semantic, gt_semantic, mode, ignore_index, True)
+    counts = ws[:24].view(torch.int64)
+    out = {"loss": stats[0], "n_valid": counts[0], "n_bad": counts[1], "n_correct": counts[2]}
+    if labels.numel():
+        out["labels"] = labels
+    return out

@@ -701,6 +701,42 @@ GRPG_API int grpg_aux_loss_backward(int height, int width, const float* depth, c
                                     float* grad_acc_obj, void* hip_stream);
 
 /*
+ * Fused semantic cross-entropy loss (no counterpart in the extension; replaces the PyTorch code of train.py:129-143,
+ * F.cross_entropy(semantic[None], gt_semantic, ignore_index=-1, reduction='mean') behind its host-synchronising
+ * torch.all(gt_semantic == -1) guard, and with mode 1 the normalise-and-log step of
+ * street_gaussian_renderer.py:248-256 in front of it).
+ * sem: device fp32 [S,H,W], channel-major, contiguous, any 4-byte alignment; S >= 1 (S == 1 gives loss 0 and a
+ * zero gradient).  target: device [H,W] of int64 (target_bytes 8) or int32 (target_bytes 4), aligned to its width.
+ * mode: 0 = logits, x_c = sem_c; 1 = probabilities, sem holds the RAW rendered planes and
+ *   x_c = log(sem_c / (sum_c sem_c + 1e-8) + 1e-8)   (float32, the reference's operand order).
+ * A pixel is valid when 0 <= target < S and ignored when target == -1; any other target is bad: it is counted,
+ * treated as ignored and never used as an index (PyTorch raises a device assert there).
+ *   loss = mean over the valid pixels of (logsumexp_c x_c - x_target); 0 when no pixel is valid.
+ * grpg_semantic_ce_forward writes stats[4] (device fp32): [0] loss, [1] n_valid, [2] n_bad, [3] n_correct (valid
+ * pixels whose argmax equals the target; the counts are exact in fp32 below 2^24).  labels: NULL or device uint8
+ * [H,W] (needs S <= 256) that receives the argmax channel of every pixel, ties to the lowest channel.  workspace:
+ * device memory of grpg_semantic_ce_workspace_bytes(H, W) bytes, 16-byte aligned; it must be kept unchanged from a
+ * forward to its backward.  Its first 24 bytes hold n_valid, n_bad, n_correct as exact int64; the per-pixel
+ * logsumexp plane (fp32 [H,W]) follows the header.
+ * grpg_semantic_ce_backward: the same S, sizes, sem, target and mode as the forward; grad_loss (device fp32 scalar)
+ * is the upstream gradient g of the loss, read on the device together with n_valid (no host synchronisation);
+ * writes every element of grad_sem (device fp32 [S,H,W], 4-byte aligned):
+ * g * (softmax_c - [c == target]) / n_valid at a valid pixel, chained through the probabilities transform with
+ * mode 1; exactly 0 at ignored and bad pixels and everywhere when n_valid == 0.  The caller need not zero it.
+ * Both run asynchronously on hip_stream; identical calls give identical bits.  Purely additive exports:
+ * GRPG_ABI_VERSION stays 7.  grpg_semantic_ce_workspace_bytes is a pure size query (no device needed; 0 for bad
+ * sizes).  Returns GRPG_OK, GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT for S < 1, bad sizes, a
+ * NULL or misaligned pointer, an unknown mode or target width, or labels with S > 256.
+ */
+GRPG_API size_t grpg_semantic_ce_workspace_bytes(int height, int width);
+GRPG_API int grpg_semantic_ce_forward(int S, int height, int width, const float* sem, const void* target,
+                                      int target_bytes, int mode, float* stats, unsigned char* labels,
+                                      void* workspace, void* hip_stream);
+GRPG_API int grpg_semantic_ce_backward(int S, int height, int width, const float* sem, const void* target,
+                                       int target_bytes, int mode, const float* grad_loss,
+                                       const void* workspace, float* grad_sem, void* hip_stream);
+
+/*
  * The tail of the training iteration (no counterpart in the extension; replace the PyTorch code of
  * gaussian_model.py:316-317 optimizer.step() and street_gaussian_model.py:555-578 set_max_radii2D /
  * add_densification_stats).
