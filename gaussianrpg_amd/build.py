@@ -53,7 +53,7 @@ HIP_UNITS = {
     "optim.hip": ["-ffp-contract=off"],
     "api.hip": [],
 }
-HEADERS = ["common.h", "gaussian_math.h", "blend_math.h", "compose_math.h", os.path.join(ROOT, "include", "grpg_rasterizer.h")]
+HEADERS = ["common.h", "reduce.h", "gaussian_math.h", "blend_math.h", "compose_math.h", os.path.join(ROOT, "include", "grpg_rasterizer.h")]
 
 
 def _hipcc():

@@ -1808,18 +1808,20 @@ int grpg_ssim_backward(int B, int C, int height, int width, const float* img1, c
   return GRPG_OK;
 }
 
-size_t grpg_aux_loss_workspace_bytes(int height, int width) {
-  if (height <= 0 || width <= 0 || (long long)height * width > 0x7FFFFFFFll) return 0;
-  return aux_loss_workspace_bytes(height, width);
+namespace {
+// The H x W plane of the auxiliary and semantic entries.  what: the entry's prefix in the error text; NULL (the size
+// queries) leaves the error text alone.
+int loss_plane_check(const char* what, int height, int width) {
+  const bool sides = height > 0 && width > 0;
+  if (sides && (long long)height * width <= 0x7FFFFFFFll) return GRPG_OK;
+  if (what) g_last_error = std::string(what) + (sides ? ": H*W must be < 2^31" : ": height and width must be positive");
+  return GRPG_ERR_INVALID_ARGUMENT;
 }
 
-namespace {
 int aux_check(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
               const unsigned char* sky_mask, const float* acc_obj, const unsigned char* obj_bound,
               float lambda_depth_lidar, float lambda_sky, float lambda_reg, const void* workspace) {
-  if (height <= 0 || width <= 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: height and width must be positive");
-  if ((long long)height * width > 0x7FFFFFFFll)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: H*W must be < 2^31");
+  if (int rc = loss_plane_check("aux_loss", height, width)) return rc;
   if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: NULL workspace");
   if ((uintptr_t)workspace & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: workspace must be 16-byte aligned");
   if (lambda_depth_lidar > 0.f && lidar_depth && (!depth || !acc))
@@ -1830,6 +1832,10 @@ int aux_check(int height, int width, const float* depth, const float* acc, const
   return GRPG_OK;
 }
 }  // namespace
+
+size_t grpg_aux_loss_workspace_bytes(int height, int width) {
+  return loss_plane_check(nullptr, height, width) ? 0 : aux_loss_workspace_bytes(height, width);
+}
 
 int grpg_aux_loss_forward(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
                           const unsigned char* mask, const unsigned char* sky_mask, const float* acc_obj,
@@ -1869,18 +1875,14 @@ int grpg_aux_loss_backward(int height, int width, const float* depth, const floa
 
 // ---- fused semantic cross-entropy loss (semantic_loss.hip) ----
 size_t grpg_semantic_ce_workspace_bytes(int height, int width) {
-  if (height <= 0 || width <= 0 || (long long)height * width > 0x7FFFFFFFll) return 0;
-  return semantic_ce_workspace_bytes(height, width);
+  return loss_plane_check(nullptr, height, width) ? 0 : semantic_ce_workspace_bytes(height, width);
 }
 
 namespace {
 int semantic_ce_check(int S, int height, int width, const float* sem, const void* target, int target_bytes,
                       int mode, const void* workspace) {
   if (S < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: S must be at least 1");
-  if (height <= 0 || width <= 0)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: height and width must be positive");
-  if ((long long)height * width > 0x7FFFFFFFll)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: H*W must be < 2^31");
+  if (int rc = loss_plane_check("semantic_ce", height, width)) return rc;
   if (!sem || !target) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL sem / target");
   if (mode != 0 && mode != 1)
     return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: mode must be 0 (logits) or 1 (probabilities)");

@@ -42,6 +42,7 @@
 // [4] N, [5] k, [6] t (the k-th smallest error; 0 when k == 0), [7] c_lt, [8] c_eq.  The counts are
 // exact in float32 only below 2^24; the workspace header (AuxState) keeps them as exact integers.
 #include "common.h"
+#include "reduce.h"
 
 namespace grpg {
 
@@ -50,7 +51,6 @@ namespace {
 constexpr int AX_THREADS = 256;
 constexpr int AX_MAX_WG = 1024;              // forward / sum grid (grid-strided over 4-pixel quads)
 constexpr int AX_BINS = 2048;                // 11-bit digits
-constexpr int AX_REDUCE_THREADS = 1024;
 constexpr unsigned AX_NOSEL = 0xFFFFFFFFu;
 constexpr int AX_SHIFT[3] = {20, 9, 0};      // digit p covers key bits [AX_SHIFT[p], AX_SHIFT[p] + AX_BITS[p])
 constexpr int AX_BITS[3] = {11, 11, 9};
@@ -106,19 +106,6 @@ __device__ __forceinline__ float sky_val(const float acc, const unsigned char s)
 __device__ __forceinline__ float obj_val(const float acc_obj, const unsigned char b) {
   const float a = clamp_nan(acc_obj);
   return b ? -(a * logf(a) + (1.0f - a) * logf(1.0f - a)) : -logf(1.0f - a);
-}
-
-// sum over the lanes of the workgroup in a fixed order (float64); valid on thread 0
-__device__ __forceinline__ double block_sum_d(double v, double* s_red) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += s_red[w];
-  __syncthreads();
-  return t;
 }
 
 struct Quad {
@@ -183,6 +170,27 @@ __device__ __forceinline__ float lidar_diff(const float depth, const float acc, 
   return expected - lidar;
 }
 
+// the keys of quad q (cnt valid): one 16-byte access when the planes allow it
+__device__ __forceinline__ void load_keys(const AuxArgs& A, const unsigned int* keys, const int q,
+                                          const int cnt, unsigned (&key)[4]) {
+  if (A.vec && cnt == 4) {
+    const uint4 k4 = reinterpret_cast<const uint4*>(keys)[q];
+    key[0] = k4.x; key[1] = k4.y; key[2] = k4.z; key[3] = k4.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; j++) if (j < cnt) key[j] = keys[q * 4 + j];
+  }
+}
+__device__ __forceinline__ void store_keys(const AuxArgs& A, unsigned int* __restrict__ keys, const int q,
+                                           const int cnt, const unsigned (&key)[4]) {
+  if (A.vec && cnt == 4) {
+    reinterpret_cast<uint4*>(keys)[q] = make_uint4(key[0], key[1], key[2], key[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; j++) if (j < cnt) keys[q * 4 + j] = key[j];
+  }
+}
+
 // Forward elementwise pass: key plane, first-digit histogram, sky / obj partial sums.
 __global__ void __launch_bounds__(AX_THREADS)
 aux_forward_kernel(const AuxArgs A, const AuxWs ws) {
@@ -207,12 +215,7 @@ aux_forward_kernel(const AuxArgs A, const AuxWs ws) {
         }
       }
       if (q == 0) ws.st->sel0 = key[0] != AX_NOSEL ? 1u : 0u;
-      if (A.vec && cnt == 4) {
-        reinterpret_cast<uint4*>(ws.keys)[q] = make_uint4(key[0], key[1], key[2], key[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++) if (j < cnt) ws.keys[q * 4 + j] = key[j];
-      }
+      store_keys(A, ws.keys, q, cnt, key);
     }
     if (A.sky_on)
 #pragma unroll
@@ -226,8 +229,8 @@ aux_forward_kernel(const AuxArgs A, const AuxWs ws) {
     for (int i = threadIdx.x; i < AX_BINS; i += AX_THREADS)
       if (h[i]) atomicAdd(&ws.hist[i], h[i]);
   }
-  const double ts = block_sum_d(sum_sky, s_red);
-  const double to = block_sum_d(sum_obj, s_red);
+  const double ts = block_sum(sum_sky, s_red);
+  const double to = block_sum(sum_obj, s_red);
   if (threadIdx.x == 0) {
     ws.part[blockIdx.x] = ts;
     ws.part[A.nwg + blockIdx.x] = to;
@@ -248,13 +251,7 @@ aux_hist_kernel(const AuxArgs A, const AuxWs ws, const int p) {
   for (int q = blockIdx.x * AX_THREADS + threadIdx.x; q < nq; q += gridDim.x * AX_THREADS) {
     const int cnt = min(4, A.n - q * 4);
     unsigned key[4];
-    if (A.vec && cnt == 4) {
-      const uint4 k4 = reinterpret_cast<const uint4*>(ws.keys)[q];
-      key[0] = k4.x; key[1] = k4.y; key[2] = k4.z; key[3] = k4.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; j++) if (j < cnt) key[j] = ws.keys[q * 4 + j];
-    }
+    load_keys(A, ws.keys, q, cnt, key);
 #pragma unroll
     for (int j = 0; j < 4; j++) if (j < cnt)   // AX_NOSEL has bit 31 set and never matches a 31-bit prefix
       if ((key[j] >> hi_shift) == prefix) atomicAdd(&h[(key[j] >> shift) & dmask], 1u);
@@ -348,42 +345,22 @@ aux_lidar_sum_kernel(const AuxArgs A, const AuxWs ws) {
   for (int q = blockIdx.x * AX_THREADS + threadIdx.x; q < nq; q += A.nwg * AX_THREADS) {
     const int cnt = min(4, A.n - q * 4);
     unsigned key[4];
-    if (A.vec && cnt == 4) {
-      const uint4 k4 = reinterpret_cast<const uint4*>(ws.keys)[q];
-      key[0] = k4.x; key[1] = k4.y; key[2] = k4.z; key[3] = k4.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; j++) if (j < cnt) key[j] = ws.keys[q * 4 + j];
-    }
+    load_keys(A, ws.keys, q, cnt, key);
 #pragma unroll
     for (int j = 0; j < 4; j++) if (j < cnt)
       if (key[j] < tkey) sum += (double)__uint_as_float(key[j]);
   }
-  const double t = block_sum_d(sum, s_red);
+  const double t = block_sum(sum, s_red);
   if (threadIdx.x == 0) ws.part[2 * (size_t)A.nwg + blockIdx.x] = t;
 }
 
-__device__ double reduce_slots(const double* __restrict__ p, const int cnt, double* s_red) {
-  double v = 0.0;
-  for (int i = threadIdx.x; i < cnt; i += AX_REDUCE_THREADS) v += p[i];
-  s_red[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = AX_REDUCE_THREADS / 2; w >= 1; w >>= 1) {
-    if ((int)threadIdx.x < w) s_red[threadIdx.x] += s_red[threadIdx.x + w];
-    __syncthreads();
-  }
-  const double t = s_red[0];
-  __syncthreads();
-  return t;
-}
-
 // One workgroup: the slots in a fixed order -> stats[9]
-__global__ void __launch_bounds__(AX_REDUCE_THREADS)
+__global__ void __launch_bounds__(REDUCE_THREADS)
 aux_reduce_kernel(const AuxArgs A, const AuxWs ws, float* __restrict__ stats) {
-  __shared__ double s_red[AX_REDUCE_THREADS];
-  const double sky = A.sky_on ? reduce_slots(ws.part, A.nwg, s_red) : 0.0;
-  const double obj = A.obj_on ? reduce_slots(ws.part + A.nwg, A.nwg, s_red) : 0.0;
-  const double lt = A.lidar_on ? reduce_slots(ws.part + 2 * (size_t)A.nwg, A.nwg, s_red) : 0.0;
+  __shared__ double s_red[REDUCE_THREADS];
+  const double sky = A.sky_on ? slot_sum(ws.part, A.nwg, s_red) : 0.0;
+  const double obj = A.obj_on ? slot_sum(ws.part + A.nwg, A.nwg, s_red) : 0.0;
+  const double lt = A.lidar_on ? slot_sum(ws.part + 2 * (size_t)A.nwg, A.nwg, s_red) : 0.0;
   if (threadIdx.x != 0) return;
   float total = 0.0f, f_lidar = 0.0f, f_sky = 0.0f, f_obj = 0.0f;
   float N = 0.f, k = 0.f, t = 0.f, c_lt = 0.f, c_eq = 0.f;
@@ -504,24 +481,34 @@ AuxArgs make_args(const int H, const int W, const AuxPlanes& P, const float sky_
   return A;
 }
 
+// Workspace: header, histograms, partial slots, key plane, each from a 256-byte boundary
+struct AuxLayout {
+  size_t hist, part, keys, total;
+};
+AuxLayout aux_layout(const int n) {
+  AuxLayout L;
+  size_t o = AX_HDR;
+  auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
+  L.hist = take(3 * AX_BINS * sizeof(unsigned int));
+  L.part = take(3 * sizeof(double) * aux_grid(n));
+  L.keys = take((size_t)n * sizeof(unsigned int));
+  L.total = o;
+  return L;
+}
+
 AuxWs make_ws(char* base, const int n) {
+  const AuxLayout L = aux_layout(n);
   AuxWs w;
-  const int nwg = aux_grid(n);
   w.st = (AuxState*)base;
-  w.hist = (unsigned int*)(base + AX_HDR);
-  w.part = (double*)(base + AX_HDR + 3 * AX_BINS * sizeof(unsigned int));
-  w.keys = (unsigned int*)(base + align_up(AX_HDR + 3 * AX_BINS * sizeof(unsigned int) + 3 * sizeof(double) * nwg, 256));
+  w.hist = (unsigned int*)(base + L.hist);
+  w.part = (double*)(base + L.part);
+  w.keys = (unsigned int*)(base + L.keys);
   return w;
 }
 
 }  // namespace
 
-size_t aux_loss_workspace_bytes(const int H, const int W) {
-  const size_t n = (size_t)H * W;
-  const int nwg = aux_grid((int)n);
-  return align_up(AX_HDR + 3 * AX_BINS * sizeof(unsigned int) + 3 * sizeof(double) * nwg, 256) +
-         align_up(n * sizeof(unsigned int), 256);
-}
+size_t aux_loss_workspace_bytes(const int H, const int W) { return aux_layout(H * W).total; }
 
 void launch_aux_loss_forward(hipStream_t st, const int H, const int W, const AuxPlanes& planes,
                              const float sky_scale, const float lam_lidar, const float lam_sky,
@@ -538,7 +525,7 @@ void launch_aux_loss_forward(hipStream_t st, const int H, const int W, const Aux
     }
     aux_lidar_sum_kernel<<<A.nwg, AX_THREADS, 0, st>>>(A, ws);
   }
-  aux_reduce_kernel<<<1, AX_REDUCE_THREADS, 0, st>>>(A, ws, stats);
+  aux_reduce_kernel<<<1, REDUCE_THREADS, 0, st>>>(A, ws, stats);
 }
 
 void launch_aux_loss_backward(hipStream_t st, const int H, const int W, const AuxPlanes& planes,
@@ -547,8 +534,8 @@ void launch_aux_loss_backward(hipStream_t st, const int H, const int W, const Au
                               float* grad_depth, float* grad_acc, float* grad_acc_obj) {
   AuxArgs A = make_args(H, W, planes, sky_scale, lam_lidar, lam_sky, lam_reg);
   A.vec = A.vec && aligned(grad_depth, 16) && aligned(grad_acc, 16) && aligned(grad_acc_obj, 16);
-  const AuxState* state = (const AuxState*)workspace;
-  aux_backward_kernel<<<A.nwg, AX_THREADS, 0, st>>>(A, state, grad_stats, grad_depth, grad_acc, grad_acc_obj);
+  const AuxWs ws = make_ws(const_cast<char*>(workspace), A.n);
+  aux_backward_kernel<<<A.nwg, AX_THREADS, 0, st>>>(A, ws.st, grad_stats, grad_depth, grad_acc, grad_acc_obj);
 }
 
 }  // namespace grpg

@@ -39,15 +39,17 @@
 //
 // Bytes per pixel (S <= 32): forward 4 S + sizeof(target) + 4 (+ 1 with labels), backward 8 S + sizeof(target) + 4
 // (4 S + sizeof(target) for an ignored pixel).
+#include <type_traits>
+
 #include "common.h"
+#include "reduce.h"
 
 namespace grpg {
 
 namespace {
 
-constexpr int SC_THREADS = 256;
+constexpr int SCE_THREADS = 256;            // (SC_THREADS is the scan's, common.h)
 constexpr int SC_MAX_WG = 2048;              // 256 CUs x 8 resident workgroups of 4 waves; grid-strided beyond
-constexpr int SC_REDUCE_THREADS = 1024;
 constexpr size_t SC_HDR = 256;
 constexpr float SC_EPS = 1e-8f;
 
@@ -122,29 +124,15 @@ __device__ __forceinline__ float sc_x(const float r, const float D) {
   else return logf(r / D + SC_EPS);
 }
 
-// sum over the lanes of the workgroup in a fixed order; valid on thread 0
-template <class T>
-__device__ __forceinline__ T sc_block_sum(T v, T* s_red) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T t = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += s_red[w];
-  __syncthreads();
-  return t;
-}
-
 template <int CAP, int MODE>
-__global__ void __launch_bounds__(SC_THREADS)
+__global__ void __launch_bounds__(SCE_THREADS)
 semantic_ce_forward_kernel(const ScArgs A, const ScWs ws, unsigned char* __restrict__ labels) {
-  __shared__ double s_red_d[SC_THREADS / 64];
-  __shared__ unsigned int s_red_u[SC_THREADS / 64];
+  __shared__ double s_red_d[SCE_THREADS / 64];
+  __shared__ unsigned int s_red_u[SCE_THREADS / 64];
   double sum = 0.0;
   unsigned int n_valid = 0, n_bad = 0, n_correct = 0;
   // 64-bit loop counter: i + the grid stride may pass 2^31 for the largest planes
-  for (long long ii = blockIdx.x * SC_THREADS + threadIdx.x; ii < A.n; ii += A.nwg * SC_THREADS) {
+  for (long long ii = blockIdx.x * SCE_THREADS + threadIdx.x; ii < A.n; ii += A.nwg * SCE_THREADS) {
     const int i = (int)ii;
     const long long t = load_target(A, i);
     const bool valid = t >= 0 && t < (long long)A.S;
@@ -184,10 +172,10 @@ semantic_ce_forward_kernel(const ScArgs A, const ScWs ws, unsigned char* __restr
       n_bad++;
     }
   }
-  const double ts = sc_block_sum(sum, s_red_d);
-  const unsigned int tv = sc_block_sum(n_valid, s_red_u);
-  const unsigned int tb = sc_block_sum(n_bad, s_red_u);
-  const unsigned int tk = sc_block_sum(n_correct, s_red_u);
+  const double ts = block_sum(sum, s_red_d);
+  const unsigned int tv = block_sum(n_valid, s_red_u);
+  const unsigned int tb = block_sum(n_bad, s_red_u);
+  const unsigned int tk = block_sum(n_correct, s_red_u);
   if (threadIdx.x == 0) {
     ws.part[blockIdx.x] = ts;
     ws.cnt[blockIdx.x] = tv;
@@ -196,34 +184,21 @@ semantic_ce_forward_kernel(const ScArgs A, const ScWs ws, unsigned char* __restr
   }
 }
 
-template <class T>
-__device__ T sc_reduce_slots(const T v, T* s_red) {
-  s_red[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = SC_REDUCE_THREADS / 2; w >= 1; w >>= 1) {
-    if ((int)threadIdx.x < w) s_red[threadIdx.x] += s_red[threadIdx.x + w];
-    __syncthreads();
-  }
-  const T t = s_red[0];
-  __syncthreads();
-  return t;
-}
-
 // One workgroup: the slots in a fixed order -> stats[4] and the workspace header
-__global__ void __launch_bounds__(SC_REDUCE_THREADS)
+__global__ void __launch_bounds__(REDUCE_THREADS)
 semantic_ce_reduce_kernel(const int nwg, const ScWs ws, float* __restrict__ stats) {
-  __shared__ double s_d[SC_REDUCE_THREADS];
-  __shared__ unsigned long long s_u[SC_REDUCE_THREADS];
+  __shared__ double s_d[REDUCE_THREADS];
+  __shared__ unsigned long long s_u[REDUCE_THREADS];
   double sum = 0.0;
   unsigned long long c[3] = {0ull, 0ull, 0ull};
-  for (int i = threadIdx.x; i < nwg; i += SC_REDUCE_THREADS) {
+  for (int i = threadIdx.x; i < nwg; i += REDUCE_THREADS) {   // the counts widen while loading
     sum += ws.part[i];
 #pragma unroll
     for (int k = 0; k < 3; k++) c[k] += ws.cnt[k * SC_MAX_WG + i];
   }
-  sum = sc_reduce_slots(sum, s_d);
+  sum = slot_sum(sum, s_d);
 #pragma unroll
-  for (int k = 0; k < 3; k++) c[k] = sc_reduce_slots(c[k], s_u);
+  for (int k = 0; k < 3; k++) c[k] = slot_sum(c[k], s_u);
   if (threadIdx.x != 0) return;
   ws.st->n_valid = (long long)c[0];
   ws.st->n_bad = (long long)c[1];
@@ -236,13 +211,13 @@ semantic_ce_reduce_kernel(const int nwg, const ScWs ws, float* __restrict__ stat
 }
 
 template <int CAP, int MODE>
-__global__ void __launch_bounds__(SC_THREADS)
+__global__ void __launch_bounds__(SCE_THREADS)
 semantic_ce_backward_kernel(const ScArgs A, const ScState* __restrict__ st, const float* __restrict__ lse_plane,
                             const float* __restrict__ grad_loss, float* __restrict__ grad_sem) {
   const long long nv = st->n_valid;
   const float q = nv > 0 ? grad_loss[0] / (float)nv : 0.0f;
   const size_t n = (size_t)A.n;
-  for (long long ii = blockIdx.x * SC_THREADS + threadIdx.x; ii < A.n; ii += A.nwg * SC_THREADS) {
+  for (long long ii = blockIdx.x * SCE_THREADS + threadIdx.x; ii < A.n; ii += A.nwg * SCE_THREADS) {
     const int i = (int)ii;
     const long long t = load_target(A, i);
     float* g = grad_sem + i;
@@ -295,7 +270,7 @@ semantic_ce_backward_kernel(const ScArgs A, const ScState* __restrict__ st, cons
   }
 }
 
-int sc_grid(const int n) { return max(1, min(SC_MAX_WG, (n + SC_THREADS - 1) / SC_THREADS)); }
+int sc_grid(const int n) { return max(1, min(SC_MAX_WG, (n + SCE_THREADS - 1) / SCE_THREADS)); }
 
 constexpr size_t SC_PART_OFF = SC_HDR;
 constexpr size_t SC_CNT_OFF = SC_PART_OFF + sizeof(double) * SC_MAX_WG;
@@ -323,29 +298,19 @@ ScArgs make_args(const int S, const int H, const int W, const float* sem, const 
   return A;
 }
 
-// CAP: the smallest register array that holds S values; 0 = walk memory
-template <int MODE>
-void forward_dispatch(hipStream_t st, const ScArgs& A, const ScWs& ws, unsigned char* labels) {
-  if (A.S <= 4) semantic_ce_forward_kernel<4, MODE><<<A.nwg, SC_THREADS, 0, st>>>(A, ws, labels);
-  else if (A.S <= 8) semantic_ce_forward_kernel<8, MODE><<<A.nwg, SC_THREADS, 0, st>>>(A, ws, labels);
-  else if (A.S <= 16) semantic_ce_forward_kernel<16, MODE><<<A.nwg, SC_THREADS, 0, st>>>(A, ws, labels);
-  else if (A.S <= 32) semantic_ce_forward_kernel<32, MODE><<<A.nwg, SC_THREADS, 0, st>>>(A, ws, labels);
-  else semantic_ce_forward_kernel<0, MODE><<<A.nwg, SC_THREADS, 0, st>>>(A, ws, labels);
-}
-
-template <int MODE>
-void backward_dispatch(hipStream_t st, const ScArgs& A, const ScState* state, const float* lse,
-                       const float* grad_loss, float* grad_sem) {
-  if (A.S <= 4)
-    semantic_ce_backward_kernel<4, MODE><<<A.nwg, SC_THREADS, 0, st>>>(A, state, lse, grad_loss, grad_sem);
-  else if (A.S <= 8)
-    semantic_ce_backward_kernel<8, MODE><<<A.nwg, SC_THREADS, 0, st>>>(A, state, lse, grad_loss, grad_sem);
-  else if (A.S <= 16)
-    semantic_ce_backward_kernel<16, MODE><<<A.nwg, SC_THREADS, 0, st>>>(A, state, lse, grad_loss, grad_sem);
-  else if (A.S <= 32)
-    semantic_ce_backward_kernel<32, MODE><<<A.nwg, SC_THREADS, 0, st>>>(A, state, lse, grad_loss, grad_sem);
-  else
-    semantic_ce_backward_kernel<0, MODE><<<A.nwg, SC_THREADS, 0, st>>>(A, state, lse, grad_loss, grad_sem);
+// f(CAP, MODE) with both as compile-time constants.  CAP: the smallest register array that holds S values;
+// 0 = walk memory
+template <class F>
+void sc_dispatch(const int S, const int mode, F&& f) {
+  auto ladder = [&](auto m) {
+    if (S <= 4) f(std::integral_constant<int, 4>{}, m);
+    else if (S <= 8) f(std::integral_constant<int, 8>{}, m);
+    else if (S <= 16) f(std::integral_constant<int, 16>{}, m);
+    else if (S <= 32) f(std::integral_constant<int, 32>{}, m);
+    else f(std::integral_constant<int, 0>{}, m);
+  };
+  if (mode == 0) ladder(std::integral_constant<int, 0>{});
+  else ladder(std::integral_constant<int, 1>{});
 }
 
 }  // namespace
@@ -359,19 +324,22 @@ void launch_semantic_ce_forward(hipStream_t st, const int S, const int H, const 
                                 unsigned char* labels, char* workspace) {
   const ScArgs A = make_args(S, H, W, sem, target, target_bytes);
   const ScWs ws = make_ws(workspace);
-  if (mode == 0) forward_dispatch<0>(st, A, ws, labels);
-  else forward_dispatch<1>(st, A, ws, labels);
-  semantic_ce_reduce_kernel<<<1, SC_REDUCE_THREADS, 0, st>>>(A.nwg, ws, stats);
+  sc_dispatch(S, mode, [&](auto cap, auto m) {
+    semantic_ce_forward_kernel<decltype(cap)::value, decltype(m)::value>
+        <<<A.nwg, SCE_THREADS, 0, st>>>(A, ws, labels);
+  });
+  semantic_ce_reduce_kernel<<<1, REDUCE_THREADS, 0, st>>>(A.nwg, ws, stats);
 }
 
 void launch_semantic_ce_backward(hipStream_t st, const int S, const int H, const int W, const float* sem,
                                  const void* target, const int target_bytes, const int mode,
                                  const float* grad_loss, const char* workspace, float* grad_sem) {
   const ScArgs A = make_args(S, H, W, sem, target, target_bytes);
-  const ScState* state = (const ScState*)workspace;
-  const float* lse = (const float*)(workspace + SC_LSE_OFF);
-  if (mode == 0) backward_dispatch<0>(st, A, state, lse, grad_loss, grad_sem);
-  else backward_dispatch<1>(st, A, state, lse, grad_loss, grad_sem);
+  const ScWs ws = make_ws(const_cast<char*>(workspace));
+  sc_dispatch(S, mode, [&](auto cap, auto m) {
+    semantic_ce_backward_kernel<decltype(cap)::value, decltype(m)::value>
+        <<<A.nwg, SCE_THREADS, 0, st>>>(A, ws.st, ws.lse, grad_loss, grad_sem);
+  });
 }
 
 }  // namespace grpg

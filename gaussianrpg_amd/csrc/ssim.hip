@@ -24,6 +24,7 @@
 // runs over all B*C*H*W positions, the L1 mean over the selected elements only (all-false mask: NaN,
 // gradient 0); C1 = 0.01^2, C2 = 0.03^2; variances as E[x^2] - mu^2.
 #include "common.h"
+#include "reduce.h"
 
 namespace grpg {
 
@@ -35,7 +36,6 @@ constexpr int SS_IW = SS_TW + 2 * SS_R;         // 42: tile + halo
 constexpr int SS_IH = SS_TH + 2 * SS_R;         // 26
 constexpr int SS_THREADS = 256;
 constexpr int SS_PX = SS_TW * SS_TH / SS_THREADS;   // 2 output pixels per lane
-constexpr int SS_REDUCE_THREADS = 1024;
 
 // loss_utils.gaussian(11, 1.5): exp(-(x - 5)^2 / 4.5) normalised by its sum, in float32
 constexpr float SS_G[11] = {
@@ -57,20 +57,6 @@ __device__ __forceinline__ float mask_at(const unsigned char* __restrict__ mask,
                                          const int b, const int c, const size_t pix) {
   if (!mask) return 1.0f;
   return mask[(size_t)b * s.mask_bstride + (size_t)c * s.mask_cstride + pix] ? 1.0f : 0.0f;
-}
-
-// sum over the lanes of the workgroup, fixed order; valid on lane 0 of wave 0
-__device__ __forceinline__ double block_sum(float v, double* s_red) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) s_red[wave] = (double)v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += s_red[w];
-  __syncthreads();
-  return t;
 }
 
 __global__ void __launch_bounds__(SS_THREADS)
@@ -159,6 +145,7 @@ ssim_forward_kernel(const SsimShape s, const float* __restrict__ x1, const float
     }
   }
   const size_t nwg = (size_t)gridDim.x;
+  // the butterfly in float32, widened at the wave boundary (reduce.h)
   const double t_ssim = block_sum(sum_ssim, s_red);
   const double t_l1 = block_sum(sum_l1, s_red);
   const double t_cnt = block_sum(sum_cnt, s_red);
@@ -169,36 +156,21 @@ ssim_forward_kernel(const SsimShape s, const float* __restrict__ x1, const float
   }
 }
 
-__device__ double reduce_range(const double* __restrict__ p, const size_t lo, const size_t hi,
-                               double* s_red) {
-  double v = 0.0;
-  for (size_t i = lo + threadIdx.x; i < hi; i += SS_REDUCE_THREADS) v += p[i];
-  s_red[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = SS_REDUCE_THREADS / 2; w >= 1; w >>= 1) {
-    if ((int)threadIdx.x < w) s_red[threadIdx.x] += s_red[threadIdx.x + w];
-    __syncthreads();
-  }
-  const double t = s_red[0];
-  __syncthreads();
-  return t;
-}
-
 // one workgroup: the per-workgroup slots in a fixed order -> stats[0..3 + B]
-__global__ void __launch_bounds__(SS_REDUCE_THREADS)
+__global__ void __launch_bounds__(REDUCE_THREADS)
 ssim_reduce_kernel(const SsimShape s, const double* __restrict__ part, const float w_l1,
                    const float w_ssim, float* __restrict__ stats) {
-  __shared__ double s_red[SS_REDUCE_THREADS];
+  __shared__ double s_red[REDUCE_THREADS];
   const size_t per_image = (size_t)s.C * s.tiles_x * s.tiles_y;
   const size_t nwg = per_image * s.B;
   double tot_ssim = 0.0;
   for (int b = 0; b < s.B; b++) {
-    const double v = reduce_range(part, b * per_image, (b + 1) * per_image, s_red);
+    const double v = slot_sum(part + b * per_image, per_image, s_red);
     tot_ssim += v;
     if (threadIdx.x == 0) stats[4 + b] = (float)(v / ((double)s.C * (double)s.plane));
   }
-  const double l1 = reduce_range(part + nwg, 0, nwg, s_red);
-  const double cnt = reduce_range(part + 2 * nwg, 0, nwg, s_red);
+  const double l1 = slot_sum(part + nwg, nwg, s_red);
+  const double cnt = slot_sum(part + 2 * nwg, nwg, s_red);
   if (threadIdx.x == 0) {
     const double ssim = tot_ssim / ((double)s.B * (double)s.C * (double)s.plane);
     const float l1m = (float)(l1 / cnt);      // 0 / 0 = NaN for an all-false mask, as the reference
@@ -314,7 +286,7 @@ void launch_ssim_forward(hipStream_t st, const int B, const int C, const int H, 
   const int nwg = B * C * s.tiles_x * s.tiles_y;
   double* part = (double*)ws;
   ssim_forward_kernel<<<nwg, SS_THREADS, 0, st>>>(s, x1, x2, mask, part, saved);
-  ssim_reduce_kernel<<<1, SS_REDUCE_THREADS, 0, st>>>(s, part, w_l1, w_ssim, stats);
+  ssim_reduce_kernel<<<1, REDUCE_THREADS, 0, st>>>(s, part, w_l1, w_ssim, stats);
 }
 
 void launch_ssim_backward(hipStream_t st, const int B, const int C, const int H, const int W,

@@ -1060,66 +1060,91 @@ torch::Tensor distCUDA2(const torch::Tensor& points) {
   return means;
 }
 
+// ---- the pieces every loss binding is made of ----
+namespace {
+// One loss call of the C ABI, as run(): on the current stream, the GIL released (the C calls touch no Python object).
+template <class Call>
+void loss_call(const char* what, Call&& call) {
+  if (const int rc = run(what, call); rc != GRPG_OK) raise_abi_error(what, rc);
+}
+
+torch::Tensor loss_workspace(const size_t bytes, const torch::Device& dev) {
+  return torch::empty({(long long)bytes}, torch::TensorOptions().dtype(torch::kByte).device(dev));
+}
+
+// The upstream gradient of a stats vector as the kernels read it.  count: the elements it must have (0: at least one).
+torch::Tensor loss_grad_stats(const torch::Tensor& grad_stats, const torch::Device& dev, const int64_t count,
+                              const char* mismatch) {
+  torch::Tensor g = grad_stats.to(dev, torch::kFloat32).contiguous();
+  TORCH_CHECK(count ? g.numel() == count : g.numel() >= 1, mismatch);
+  return g;
+}
+
 // Fused SSIM + L1 loss (gaussianrpg_amd/loss.py).  img1 / img2: float32 [B,C,H,W] on one device (made contiguous
 // here); mask: empty or uint8 [1|B, 1|C, H, W].  Returns (stats [4 + B], saved partials [3,B,C,H,W] or empty).
-namespace {
-void ssim_args(const torch::Tensor& img1, const torch::Tensor& img2, const torch::Tensor& mask) {
+struct SsimIn {
+  torch::Tensor a, b, m;   // contiguous
+  int B, C, H, W;
+  const unsigned char* mask = nullptr;   // NULL: no mask
+  int mask_batch = 1, mask_channels = 1;
+};
+
+SsimIn ssim_args(const torch::Tensor& img1, const torch::Tensor& img2, const torch::Tensor& mask) {
   TORCH_CHECK(img1.is_cuda() && img2.is_cuda(), "ssim: images must live on a ROCm/HIP device (no CPU path)");
   TORCH_CHECK(img1.scalar_type() == torch::kFloat32 && img2.scalar_type() == torch::kFloat32,
               "ssim: images must be float32");
   TORCH_CHECK(img1.dim() == 4 && img1.sizes() == img2.sizes(), "ssim: images must be two [B,C,H,W] of one shape");
   TORCH_CHECK(img1.device() == img2.device(), "ssim: images on different devices");
+  SsimIn in;
+  in.a = img1.contiguous();
+  in.b = img2.contiguous();
+  in.B = in.a.size(0); in.C = in.a.size(1); in.H = in.a.size(2); in.W = in.a.size(3);
   if (mask.defined() && mask.numel() > 0) {
     TORCH_CHECK(mask.device() == img1.device() && mask.scalar_type() == torch::kUInt8 && mask.dim() == 4 &&
                     mask.size(2) == img1.size(2) && mask.size(3) == img1.size(3),
                 "ssim: mask must be uint8 [1|B, 1|C, H, W] on the images' device");
+    in.m = mask.contiguous();
+    in.mask = in.m.data_ptr<uint8_t>();
+    in.mask_batch = in.m.size(0);
+    in.mask_channels = in.m.size(1);
   }
+  return in;
 }
 }  // namespace
 
 std::tuple<torch::Tensor, torch::Tensor> SsimForward(const torch::Tensor& img1, const torch::Tensor& img2,
                                                      const torch::Tensor& mask, const double w_l1,
                                                      const double w_ssim, const bool save_partials) {
-  ssim_args(img1, img2, mask);
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(img1.device());
-  const torch::Tensor a = img1.contiguous(), b = img2.contiguous();
-  const bool has_mask = mask.defined() && mask.numel() > 0;
-  const torch::Tensor m = has_mask ? mask.contiguous() : mask;
-  const int B = a.size(0), C = a.size(1), H = a.size(2), W = a.size(3);
-  auto fopts = a.options();
-  torch::Tensor stats = torch::empty({4 + B}, fopts);
-  torch::Tensor saved = save_partials ? torch::empty({3, B, C, H, W}, fopts) : torch::empty({0}, fopts);
-  const size_t ws_bytes = grpg_ssim_workspace_bytes(B, C, H, W);
-  torch::Tensor ws = torch::empty({(long long)(ws_bytes > 0 ? ws_bytes : 8)}, a.options().dtype(torch::kByte));
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  const int rc = grpg_ssim_forward(B, C, H, W, a.data_ptr<float>(), b.data_ptr<float>(),
-                                   has_mask ? m.data_ptr<uint8_t>() : nullptr, has_mask ? m.size(0) : 1,
-                                   has_mask ? m.size(1) : 1, (float)w_l1, (float)w_ssim, stats.data_ptr<float>(),
-                                   save_partials ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (void*)stream);
-  if (rc != GRPG_OK) raise_abi_error("grpg_ssim_forward", rc);
+  const SsimIn in = ssim_args(img1, img2, mask);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.a.device());
+  auto fopts = in.a.options();
+  torch::Tensor stats = torch::empty({4 + in.B}, fopts);
+  torch::Tensor saved = save_partials ? torch::empty({3, in.B, in.C, in.H, in.W}, fopts) : torch::empty({0}, fopts);
+  const size_t ws_bytes = grpg_ssim_workspace_bytes(in.B, in.C, in.H, in.W);
+  torch::Tensor ws = loss_workspace(ws_bytes > 0 ? ws_bytes : 8, in.a.device());
+  loss_call("grpg_ssim_forward", [&](void* stream) {
+    return grpg_ssim_forward(in.B, in.C, in.H, in.W, in.a.data_ptr<float>(), in.b.data_ptr<float>(), in.mask,
+                             in.mask_batch, in.mask_channels, (float)w_l1, (float)w_ssim, stats.data_ptr<float>(),
+                             save_partials ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), stream);
+  });
   return std::make_tuple(stats, saved);
 }
 
 torch::Tensor SsimBackward(const torch::Tensor& img1, const torch::Tensor& img2, const torch::Tensor& mask,
                            const double w_l1, const double w_ssim, const torch::Tensor& stats,
                            const torch::Tensor& saved, const torch::Tensor& grad_stats) {
-  ssim_args(img1, img2, mask);
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(img1.device());
-  const torch::Tensor a = img1.contiguous(), b = img2.contiguous();
-  const bool has_mask = mask.defined() && mask.numel() > 0;
-  const torch::Tensor m = has_mask ? mask.contiguous() : mask;
-  const int B = a.size(0), C = a.size(1), H = a.size(2), W = a.size(3);
-  TORCH_CHECK(stats.numel() == 4 + B && saved.numel() == 3 * a.numel(), "ssim_backward: stats / saved do not match");
-  const torch::Tensor g = grad_stats.to(a.device(), torch::kFloat32).contiguous();
-  TORCH_CHECK(g.numel() == 4 + B, "ssim_backward: grad_stats must have 4 + B elements");
-  torch::Tensor grad = torch::empty_like(a);
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  const int rc = grpg_ssim_backward(B, C, H, W, a.data_ptr<float>(), b.data_ptr<float>(),
-                                    has_mask ? m.data_ptr<uint8_t>() : nullptr, has_mask ? m.size(0) : 1,
-                                    has_mask ? m.size(1) : 1, (float)w_l1, (float)w_ssim, stats.data_ptr<float>(),
-                                    saved.data_ptr<float>(), g.data_ptr<float>(), grad.data_ptr<float>(),
-                                    (void*)stream);
-  if (rc != GRPG_OK) raise_abi_error("grpg_ssim_backward", rc);
+  const SsimIn in = ssim_args(img1, img2, mask);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.a.device());
+  TORCH_CHECK(stats.numel() == 4 + in.B && saved.numel() == 3 * in.a.numel(),
+              "ssim_backward: stats / saved do not match");
+  const torch::Tensor g = loss_grad_stats(grad_stats, in.a.device(), 4 + in.B,
+                                          "ssim_backward: grad_stats must have 4 + B elements");
+  torch::Tensor grad = torch::empty_like(in.a);
+  loss_call("grpg_ssim_backward", [&](void* stream) {
+    return grpg_ssim_backward(in.B, in.C, in.H, in.W, in.a.data_ptr<float>(), in.b.data_ptr<float>(), in.mask,
+                              in.mask_batch, in.mask_channels, (float)w_l1, (float)w_ssim, stats.data_ptr<float>(),
+                              saved.data_ptr<float>(), g.data_ptr<float>(), grad.data_ptr<float>(), stream);
+  });
   return grad;
 }
 
@@ -1167,14 +1192,12 @@ std::tuple<torch::Tensor, torch::Tensor> AuxLossForward(
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.dev);
   auto fopts = torch::TensorOptions().dtype(torch::kFloat32).device(in.dev);
   torch::Tensor stats = torch::empty({9}, fopts);
-  const size_t ws_bytes = grpg_aux_loss_workspace_bytes(in.H, in.W);
-  torch::Tensor ws = torch::empty({(long long)ws_bytes}, fopts.dtype(torch::kByte));
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  const int rc = grpg_aux_loss_forward(in.H, in.W, aux_f(depth), aux_f(acc), aux_f(lidar), aux_u8(mask), aux_u8(sky),
-                                       aux_f(acc_obj), aux_u8(bound), (float)sky_scale, (float)lam_lidar,
-                                       (float)lam_sky, (float)lam_reg, stats.data_ptr<float>(), ws.data_ptr(),
-                                       (void*)stream);
-  if (rc != GRPG_OK) raise_abi_error("grpg_aux_loss_forward", rc);
+  torch::Tensor ws = loss_workspace(grpg_aux_loss_workspace_bytes(in.H, in.W), in.dev);
+  loss_call("grpg_aux_loss_forward", [&](void* stream) {
+    return grpg_aux_loss_forward(in.H, in.W, aux_f(depth), aux_f(acc), aux_f(lidar), aux_u8(mask), aux_u8(sky),
+                                 aux_f(acc_obj), aux_u8(bound), (float)sky_scale, (float)lam_lidar, (float)lam_sky,
+                                 (float)lam_reg, stats.data_ptr<float>(), ws.data_ptr(), stream);
+  });
   return std::make_tuple(stats, ws);
 }
 
@@ -1189,19 +1212,18 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> AuxLossBackward(
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.dev);
   TORCH_CHECK(ws.device() == in.dev && (size_t)ws.numel() == grpg_aux_loss_workspace_bytes(in.H, in.W),
               "aux_loss_backward: workspace does not match");
-  const torch::Tensor g = grad_stats.to(in.dev, torch::kFloat32).contiguous();
-  TORCH_CHECK(g.numel() == 9, "aux_loss_backward: grad_stats must have 9 elements");
+  const torch::Tensor g = loss_grad_stats(grad_stats, in.dev, 9, "aux_loss_backward: grad_stats must have 9 elements");
   auto fopts = torch::TensorOptions().dtype(torch::kFloat32).device(in.dev);
   auto plane = [&](bool want) { return want ? torch::empty({H * W}, fopts) : torch::empty({0}, fopts); };
   torch::Tensor gd = plane(want_depth), ga = plane(want_acc), go = plane(want_acc_obj);
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  const int rc = grpg_aux_loss_backward(in.H, in.W, aux_f(depth), aux_f(acc), aux_f(lidar), aux_u8(mask), aux_u8(sky),
-                                        aux_f(acc_obj), aux_u8(bound), (float)sky_scale, (float)lam_lidar,
-                                        (float)lam_sky, (float)lam_reg, g.data_ptr<float>(), ws.data_ptr(),
-                                        want_depth ? gd.data_ptr<float>() : nullptr,
-                                        want_acc ? ga.data_ptr<float>() : nullptr,
-                                        want_acc_obj ? go.data_ptr<float>() : nullptr, (void*)stream);
-  if (rc != GRPG_OK) raise_abi_error("grpg_aux_loss_backward", rc);
+  loss_call("grpg_aux_loss_backward", [&](void* stream) {
+    return grpg_aux_loss_backward(in.H, in.W, aux_f(depth), aux_f(acc), aux_f(lidar), aux_u8(mask), aux_u8(sky),
+                                  aux_f(acc_obj), aux_u8(bound), (float)sky_scale, (float)lam_lidar, (float)lam_sky,
+                                  (float)lam_reg, g.data_ptr<float>(), ws.data_ptr(),
+                                  want_depth ? gd.data_ptr<float>() : nullptr,
+                                  want_acc ? ga.data_ptr<float>() : nullptr,
+                                  want_acc_obj ? go.data_ptr<float>() : nullptr, stream);
+  });
   return std::make_tuple(gd, ga, go);
 }
 
@@ -1241,19 +1263,14 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> SemanticCeForward(
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(semantic.device());
   auto fopts = torch::TensorOptions().dtype(torch::kFloat32).device(semantic.device());
   torch::Tensor stats = torch::empty({4}, fopts);
-  const size_t ws_bytes = grpg_semantic_ce_workspace_bytes(in.H, in.W);
-  torch::Tensor ws = torch::empty({(long long)ws_bytes}, fopts.dtype(torch::kByte));
+  torch::Tensor ws = loss_workspace(grpg_semantic_ce_workspace_bytes(in.H, in.W), semantic.device());
   torch::Tensor labels = want_labels ? torch::empty({in.H, in.W}, fopts.dtype(torch::kByte))
                                      : torch::empty({0}, fopts.dtype(torch::kByte));
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int rc;
-  {
-    pybind11::gil_scoped_release nogil;
-    rc = grpg_semantic_ce_forward(in.S, in.H, in.W, semantic.data_ptr<float>(), target.data_ptr(), in.target_bytes,
-                                  (int)mode, stats.data_ptr<float>(),
-                                  want_labels ? labels.data_ptr<uint8_t>() : nullptr, ws.data_ptr(), (void*)stream);
-  }
-  if (rc != GRPG_OK) raise_abi_error("grpg_semantic_ce_forward", rc);
+  loss_call("grpg_semantic_ce_forward", [&](void* stream) {
+    return grpg_semantic_ce_forward(in.S, in.H, in.W, semantic.data_ptr<float>(), target.data_ptr(), in.target_bytes,
+                                    (int)mode, stats.data_ptr<float>(),
+                                    want_labels ? labels.data_ptr<uint8_t>() : nullptr, ws.data_ptr(), stream);
+  });
   return std::make_tuple(stats, ws, labels);
 }
 
@@ -1267,8 +1284,7 @@ torch::Tensor SemanticCeBackward(const torch::Tensor& semantic, const torch::Ten
   TORCH_CHECK(ws.device() == semantic.device() && ws.scalar_type() == torch::kByte && ws.is_contiguous() &&
                   (size_t)ws.numel() == grpg_semantic_ce_workspace_bytes(in.H, in.W),
               "semantic_ce_backward: workspace does not match");
-  const torch::Tensor g = grad_stats.to(semantic.device(), torch::kFloat32).contiguous();
-  TORCH_CHECK(g.numel() >= 1, "semantic_ce_backward: grad_stats is empty");
+  const torch::Tensor g = loss_grad_stats(grad_stats, semantic.device(), 0, "semantic_ce_backward: grad_stats is empty");
   torch::Tensor grad;
   if (grad_out) {
     grad = *grad_out;
@@ -1278,15 +1294,10 @@ torch::Tensor SemanticCeBackward(const torch::Tensor& semantic, const torch::Ten
   } else {
     grad = torch::empty_like(semantic);
   }
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int rc;
-  {
-    pybind11::gil_scoped_release nogil;
-    rc = grpg_semantic_ce_backward(in.S, in.H, in.W, semantic.data_ptr<float>(), target.data_ptr(), in.target_bytes,
-                                   (int)mode, g.data_ptr<float>(), ws.data_ptr(), grad.data_ptr<float>(),
-                                   (void*)stream);
-  }
-  if (rc != GRPG_OK) raise_abi_error("grpg_semantic_ce_backward", rc);
+  loss_call("grpg_semantic_ce_backward", [&](void* stream) {
+    return grpg_semantic_ce_backward(in.S, in.H, in.W, semantic.data_ptr<float>(), target.data_ptr(), in.target_bytes,
+                                     (int)mode, g.data_ptr<float>(), ws.data_ptr(), grad.data_ptr<float>(), stream);
+  });
   return grad;
 }
 

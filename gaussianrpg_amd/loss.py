@@ -56,12 +56,33 @@ __all__ = ["ssim", "l1_loss", "l1_ssim_loss", "aux_loss", "lidar_depth_loss", "s
            "lidar_selection", "semantic_loss", "semantic_loss_stats"]
 
 
+_FLOAT = ((torch.float32,), "float32")
+_MASK = ((torch.bool, torch.uint8), "a bool (or uint8) tensor")
+_LABEL = ((torch.int64, torch.int32), "int64 or int32")
+
+
+def _tensor_of(t, name, kind=None):
+    """t is a torch.Tensor, of one of the dtypes of kind = (dtypes, how the message names them)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("gaussianrpg_amd.loss: %s must be a torch.Tensor" % name)
+    if kind is not None and t.dtype not in kind[0]:
+        raise TypeError("gaussianrpg_amd.loss: %s must be %s (got %s)" % (name, kind[1], t.dtype))
+
+
+def _on_device(named, device, different):
+    """Every (name, tensor) of named lives on a ROCm device, and on this one; different(name, tensor) words the
+    complaint about another."""
+    for n, t in named:
+        if not t.is_cuda:
+            raise RuntimeError("gaussianrpg_amd.loss: %s must live on a ROCm/HIP device (torch device 'cuda'); "
+                               "the fused loss is MI355X-native and has no CPU path" % n)
+        if t.device != device:
+            raise ValueError("gaussianrpg_amd.loss: " + different(n, t))
+
+
 def _check(img1, img2, what=("img1", "img2")):
     for t, n in zip((img1, img2), what):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("gaussianrpg_amd.loss: %s must be a torch.Tensor" % n)
-        if t.dtype != torch.float32:
-            raise TypeError("gaussianrpg_amd.loss: %s must be float32 (got %s)" % (n, t.dtype))
+        _tensor_of(t, n, _FLOAT)
     if img1.shape != img2.shape:
         raise ValueError("gaussianrpg_amd.loss: %s and %s must have the same shape (got %s and %s)"
                          % (what[0], what[1], tuple(img1.shape), tuple(img2.shape)))
@@ -70,12 +91,7 @@ def _check(img1, img2, what=("img1", "img2")):
     if img2.requires_grad:
         raise ValueError("gaussianrpg_amd.loss: %s requires a gradient; the fused loss differentiates only %s "
                          "(the reference's ground truth never requires one)" % (what[1], what[0]))
-    for t, n in zip((img1, img2), what):
-        if not t.is_cuda:
-            raise RuntimeError("gaussianrpg_amd.loss: %s must live on a ROCm/HIP device (torch device 'cuda'); "
-                               "the fused loss is MI355X-native and has no CPU path" % n)
-    if img1.device != img2.device:
-        raise ValueError("gaussianrpg_amd.loss: images on different devices")
+    _on_device(zip(what, (img1, img2)), img1.device, lambda n, t: "images on different devices")
 
 
 def _as4(img):
@@ -86,7 +102,7 @@ def _mask4(mask, img, B, C, H, W):
     """mask broadcast like torch.where(mask, img, 0) -> uint8 [1|B, 1|C, H, W] (empty: no mask)."""
     if mask is None:
         return torch.empty(0, dtype=torch.uint8, device=img.device)
-    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in _MASK[0]:   # one message for both faults
         raise TypeError("gaussianrpg_amd.loss: mask must be a bool (or uint8) tensor")
     if mask.device != img.device:
         raise ValueError("gaussianrpg_amd.loss: mask must be on %s (got %s)" % (img.device, mask.device))
@@ -162,13 +178,7 @@ def _aux_plane(t, name, hw, mask=False):
     """None or a [H,W] / [1,H,W] device plane -> (flat contiguous tensor or None, hw)."""
     if t is None:
         return None, hw
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("gaussianrpg_amd.loss: %s must be a torch.Tensor" % name)
-    if mask:
-        if t.dtype not in (torch.bool, torch.uint8):
-            raise TypeError("gaussianrpg_amd.loss: %s must be a bool (or uint8) tensor (got %s)" % (name, t.dtype))
-    elif t.dtype != torch.float32:
-        raise TypeError("gaussianrpg_amd.loss: %s must be float32 (got %s)" % (name, t.dtype))
+    _tensor_of(t, name, _MASK if mask else _FLOAT)
     if not (t.dim() == 2 or (t.dim() == 3 and t.shape[0] == 1)):
         raise ValueError("gaussianrpg_amd.loss: %s must be [H,W] or [1,H,W] (got %s)" % (name, tuple(t.shape)))
     if hw is not None and tuple(t.shape[-2:]) != hw[:2]:
@@ -230,14 +240,8 @@ def _aux_run(depth, acc, lidar_depth, mask, sky_mask, sky_scale, acc_obj, obj_bo
         planes[name], hw = _aux_plane(t if on else None, name, hw, is_mask)
     if hw is None:
         raise ValueError("gaussianrpg_amd.loss: no auxiliary term is on (every lambda is 0 or its plane is missing)")
-    for name, t in planes.items():
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError("gaussianrpg_amd.loss: %s must live on a ROCm/HIP device (torch device 'cuda'); "
-                               "the fused loss is MI355X-native and has no CPU path" % name)
-        if t.device != hw[2]:
-            raise ValueError("gaussianrpg_amd.loss: %s on %s, another plane on %s" % (name, t.device, hw[2]))
+    _on_device([(name, t) for name, t in planes.items() if t is not None], hw[2],
+               lambda name, t: "%s on %s, another plane on %s" % (name, t.device, hw[2]))
     empty = torch.empty(0, device=hw[2])
     args = [planes[k] if planes[k] is not None else empty
             for k in ("depth", "acc", "acc_obj", "lidar_depth", "mask", "sky_mask", "obj_bound")]
@@ -314,13 +318,10 @@ def _semantic_run(semantic, gt_semantic, mode, ignore_index, want_labels):
         raise ValueError("gaussianrpg_amd.loss: mode must be 'logits' or 'probabilities' (got %r)" % (mode,))
     if ignore_index != -1:
         raise ValueError("gaussianrpg_amd.loss: only ignore_index == -1 is supported (got %r)" % (ignore_index,))
-    for t, n in ((semantic, "semantic"), (gt_semantic, "gt_semantic")):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("gaussianrpg_amd.loss: %s must be a torch.Tensor" % n)
-    if semantic.dtype != torch.float32:
-        raise TypeError("gaussianrpg_amd.loss: semantic must be float32 (got %s)" % semantic.dtype)
-    if gt_semantic.dtype not in (torch.int64, torch.int32):
-        raise TypeError("gaussianrpg_amd.loss: gt_semantic must be int64 or int32 (got %s)" % gt_semantic.dtype)
+    _tensor_of(semantic, "semantic")
+    _tensor_of(gt_semantic, "gt_semantic")
+    _tensor_of(semantic, "semantic", _FLOAT)
+    _tensor_of(gt_semantic, "gt_semantic", _LABEL)
     if not (semantic.dim() == 3 or (semantic.dim() == 4 and semantic.shape[0] == 1)):
         raise ValueError("gaussianrpg_amd.loss: semantic must be [S,H,W] or [1,S,H,W] (got %s)"
                          % (tuple(semantic.shape),))
@@ -336,13 +337,8 @@ def _semantic_run(semantic, gt_semantic, mode, ignore_index, want_labels):
     if gt_semantic.requires_grad:
         raise ValueError("gaussianrpg_amd.loss: gt_semantic requires a gradient; the fused loss differentiates only "
                          "semantic")
-    for t, n in ((semantic, "semantic"), (gt_semantic, "gt_semantic")):
-        if not t.is_cuda:
-            raise RuntimeError("gaussianrpg_amd.loss: %s must live on a ROCm/HIP device (torch device 'cuda'); "
-                               "the fused loss is MI355X-native and has no CPU path" % n)
-    if semantic.device != gt_semantic.device:
-        raise ValueError("gaussianrpg_amd.loss: gt_semantic on %s, semantic on %s"
-                         % (gt_semantic.device, semantic.device))
+    _on_device((("semantic", semantic), ("gt_semantic", gt_semantic)), semantic.device,
+               lambda n, t: "gt_semantic on %s, semantic on %s" % (t.device, semantic.device))
     sem = semantic.reshape(semantic.shape[-3:]).contiguous()
     tgt = gt_semantic.reshape(gt_semantic.shape[-2:]).contiguous()
     return _SemanticLoss.apply(sem, tgt, _SEMANTIC_MODES[mode], bool(want_labels) and sem.shape[0] <= 256)

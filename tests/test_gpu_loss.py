@@ -181,6 +181,33 @@ def test_deterministic(dev):
     assert torch.equal(outs[0][1], outs[1][1])
 
 
+# partial slots of the forward: B * C * ceil(W / 32) * ceil(H / 16); the one-workgroup reduce has 1024 threads
+EXACT_SHAPES = [
+    ("3slots", (3, 1, 1)),
+    ("18slots", (3, 37, 53)),
+    ("1083slots", (3, 304, 577)),        # some reduce threads add two slots
+    ("2166slots", (2, 3, 304, 577)),     # the per-image ranges start at a non-zero slot
+]
+
+
+@pytest.mark.parametrize("name,shape", EXACT_SHAPES, ids=[s[0] for s in EXACT_SHAPES])
+def test_exact_sums_through_the_reduction(dev, name, shape):
+    """Values from {0, 0.5} against zeros: every partial sum is exactly representable, so the masked L1 mean has
+    one right answer whatever the order of the additions, and a slot that is dropped or added twice shows."""
+    from gaussianrpg_amd import loss
+    g = torch.Generator(device="cpu").manual_seed(sum(shape))
+    x1 = (0.5 * torch.randint(0, 2, shape, generator=g).float()).to(dev)
+    x2 = torch.zeros_like(x1)
+    m = (torch.rand((1,) + shape[-2:], generator=g) > 0.3).to(dev)
+    assert bool(m.any())
+    want = ((x1 * m).double().sum() / m.expand_as(x1).sum()).float()
+    assert torch.equal(loss.l1_loss(x1, x2, m), want)
+    if len(shape) == 4:
+        per_image = loss.ssim(x1, x2, size_average=False, mask=m)
+        for b in range(shape[0]):
+            assert torch.equal(per_image[b], loss.ssim(x1[b], x2[b], mask=m))
+
+
 def test_harness_train_loss_default_unchanged(dev):
     a, b = _imgs((3, 48, 64), 4, dev)
     pkg = {"rgb": a, "acc": torch.rand(1, 48, 64, device=dev), "depth": torch.rand(1, 48, 64, device=dev)}

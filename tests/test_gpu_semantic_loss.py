@@ -127,8 +127,9 @@ def test_single_valid_pixel(dev, mode):
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("S,H,W", [(3, 37, 53), (19, 37, 53), (40, 37, 53), (15, 96, 200)])
+@pytest.mark.parametrize("S,H,W", [(3, 37, 53), (19, 37, 53), (40, 37, 53), (15, 96, 200), (3, 520, 520)])
 def test_counts_and_labels_are_exact(dev, S, H, W, mode):
+    """520x520: 1057 workgroups, so the first threads of the one-workgroup reduce add two slots each."""
     from gaussianrpg_amd import loss
     sem, gt = _inputs(S, H, W, mode, dev, seed=9)
     gt[3, 4], gt[H - 1, W - 1], gt[0, 0] = -7, S + 3, -(2 ** 40)       # bad labels: counted, ignored, no fault

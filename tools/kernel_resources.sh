@@ -14,6 +14,6 @@ for l in sys.stdin:
     if m and cur:
         d[m.group(1).strip()]=m.group(2)
         if m.group(1).strip().startswith('LDS Size'):
-            name=subprocess.run(['c++filt',cur],capture_output=True,text=True).stdout.strip().split('(')[0]
+            name=subprocess.run(['c++filt','-p',cur],capture_output=True,text=True).stdout.strip().replace('(anonymous namespace)::','')
             print('%-72s VGPR %3s AGPR %3s scratch %4s SGPR %3s occ %s LDS %s'%(name[-72:],d.get('VGPRs'),d.get('AGPRs'),d.get('ScratchSize [bytes/lane]'),d.get('TotalSGPRs'),d.get('Occupancy [waves/SIMD]'),d.get('LDS Size [bytes/block]')))
 "
