@@ -51,6 +51,9 @@ HIP_UNITS = {
     # fused multi-tensor Adam step + densification statistics: one rounding per operation, in the order
     # written, on the vector and the scalar path alike (bit-identical across alignments)
     "optim.hip": ["-ffp-contract=off"],
+    # feature planes of a composed frame: compose_one() must give the bits the composed preprocess sees (no FMA
+    # contraction); no atomics, deterministic fixed-order reduction of the pose gradient
+    "features.hip": ["-ffp-contract=off"],
     "api.hip": [],
 }
 HEADERS = ["common.h", "reduce.h", "gaussian_math.h", "blend_math.h", "compose_math.h", os.path.join(ROOT, "include", "grpg_rasterizer.h")]

@@ -22,9 +22,11 @@ returns the gradients with respect to the RAW parameters (``_xyz``, ``_scaling``
 sigmoid / normalize, the Fourier DC sum, the rigid transform and the quaternion product runs inside
 the preprocess backward kernel.  ``means2D`` (zeros ``[P,3]`` requiring grad, as
 street_gaussian_renderer.py:157-162 creates it) receives the densification statistic.  The flip
-augmentation of rigid actors (street_gaussian_model.py:286-293) is ``ModelParams.flip``.  Not fused
-(stay in the caller's PyTorch): the semantic concatenation (:420-435) and pose-correction modules
--- a corrected pose is simply an ``obj_rot`` / ``obj_trans`` tensor with a graph behind it.
+augmentation of rigid actors (street_gaussian_model.py:286-293) is ``ModelParams.flip``.  Feature planes --
+the semantic concatenation (:420-435) and the normals (:463-484) -- ride through
+``ComposedRasterizer.forward_features``; ``forward`` itself renders none.  Not fused (stay in the caller's
+PyTorch): pose-correction modules -- a corrected pose is simply an ``obj_rot`` / ``obj_trans`` tensor with a
+graph behind it.
 """
 import math
 from typing import List, NamedTuple, Optional, Sequence
@@ -174,6 +176,178 @@ def compose(models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]])
     return _C.compose(*lists, pose_t, idft_t)
 
 
+def _pose_tensors(poses):
+    return [t for p in poses if p is not None for t in (p.obj_rot, p.obj_trans) if isinstance(t, torch.Tensor)]
+
+
+def _pose_graph(poses, pose_tensors):
+    """poses as [n,4] / [n,3] tensors that keep their graph (rows of static models: constants)"""
+    if not pose_tensors:
+        return None, None
+    one = torch.tensor([1.0, 0.0, 0.0, 0.0])
+    zero3 = torch.zeros(3)
+    dev = pose_tensors[0].device
+    as_t = lambda v, d: v.to(dev).float() if isinstance(v, torch.Tensor) else \
+        torch.tensor([float(x) for x in v], device=dev)   # noqa: E731
+    pose_rot = torch.stack([one.to(dev) if p is None else as_t(p.obj_rot, dev) for p in poses])
+    pose_trans = torch.stack([zero3.to(dev) if p is None else as_t(p.obj_trans, dev) for p in poses])
+    return pose_rot, pose_trans
+
+
+_NO_SEMANTIC = torch.empty(0)
+
+
+def _semantic_list(models, semantics):
+    """One [N_i,S] float32 device tensor per model (None -> an empty tensor: zeros); S.  No fallback: a CPU
+    tensor, another dtype or disagreeing S is an error."""
+    if semantics is None:
+        return [], 0
+    if len(semantics) != len(models):
+        raise ValueError("one semantic tensor (or None) per model")
+    out, S = [], None
+    for i, (m, t) in enumerate(zip(models, semantics)):
+        if t is None:
+            out.append(_NO_SEMANTIC)
+            continue
+        if not t.is_cuda:
+            raise RuntimeError("gaussianrpg_amd: semantics of model %d must live on the device: there is no CPU path" % i)
+        if t.dtype != torch.float32:
+            raise TypeError("semantics of model %d must be float32, got %s" % (i, t.dtype))
+        if t.dim() != 2 or t.shape[0] != m.xyz.shape[0]:
+            raise ValueError("semantics of model %d must be [N,S]" % i)
+        if S is not None and t.shape[1] != S:
+            raise ValueError("all models must carry the same number of semantic channels (%d and %d)" % (S, t.shape[1]))
+        S = int(t.shape[1])
+        out.append(t)
+    if S is None:
+        return [], 0
+    return out, S
+
+
+def _check_models(models):
+    for i, m in enumerate(models):
+        for name, t in zip(ModelParams._fields[:6], m[:6]):
+            if not t.is_cuda:
+                raise RuntimeError("gaussianrpg_amd: %s of model %d must live on the device: there is no CPU path" % (name, i))
+            if t.dtype != torch.float32:
+                raise TypeError("%s of model %d must be float32, got %s" % (name, i, t.dtype))
+
+
+class _ComposeFeatures(torch.autograd.Function):
+    """compose_features with a graph: backward = _C.compose_features_backward (C ABI grpg_compose_features_backward)."""
+
+    @staticmethod
+    def forward(ctx, nm, pose_t, idft_t, flips, normals, campos, pose_rot, S, *flat):
+        lists = [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
+        sems = list(flat[6 * nm:])
+        ctx.nm, ctx.pose_t, ctx.idft_t, ctx.flips, ctx.normals, ctx.campos, ctx.S = nm, pose_t, idft_t, flips, normals, campos, S
+        ctx.pose_dev = None if pose_rot is None else pose_rot.device
+        ctx.save_for_backward(*flat[:6 * nm])
+        return _C.compose_features(*lists, flips, pose_t, idft_t, sems, normals, campos)
+
+    @staticmethod
+    def backward(ctx, g_features):
+        nm = ctx.nm
+        flat = ctx.saved_tensors
+        lists = [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
+        need = ctx.needs_input_grad
+        want_sem = [bool(n) for n in need[8 + 6 * nm:]] or [False] * nm
+        g_rot, g_sem, g_poses = _C.compose_features_backward(
+            *lists, ctx.flips, ctx.pose_t, ctx.idft_t, ctx.S, want_sem, ctx.normals, ctx.campos, g_features.contiguous())
+        grads = [None] * (6 * nm)
+        for i in range(nm):
+            if need[8 + 2 * nm + i] and ctx.normals:
+                grads[2 * nm + i] = g_rot[i]
+        sem_grads = [g if (n and g.numel()) else None for g, n in zip(g_sem, need[8 + 6 * nm:])]
+        g_pose_rot = g_poses[:, 0:4].to(ctx.pose_dev) if need[6] else None
+        return (None, None, None, None, None, None, g_pose_rot, None) + tuple(grads) + tuple(sem_grads)
+
+
+def compose_features(models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]], semantics=None,
+                     normals: bool = False, campos=None):
+    """The feature array of a composed frame alone, ``[P,F]`` with ``F = 3 * normals + S``: the normals first
+    (``GaussianModel.get_normals``, gaussian_model.py:256-269, on the world rotations / scales / means ``compose``
+    returns; for actors ``R_obj n_local`` with the sign taken in the world frame), then the models' semantic arrays
+    (``semantics``: one ``[N_i,S]`` tensor or None -- zeros -- per model; street_gaussian_model.py:420-435), computed
+    by the HIP code ``ComposedRasterizer.forward_features`` uses.  Differentiable with respect to the raw rotations,
+    tensor-valued ``obj_rot`` and the semantic arrays (none through the axis choice, the sign, the means or the
+    scales, like the reference)."""
+    _check_models(models)
+    sems, S = _semantic_list(models, semantics)
+    if normals and campos is None:
+        raise ValueError("normals=True needs campos (the camera centre the normals are turned towards)")
+    lists, pose_t, idft_t = _pack(models, poses)
+    dev = models[0].xyz.device
+    campos = _NO_SEMANTIC if campos is None else campos.detach().to(device=dev, dtype=torch.float32).reshape(-1)
+    normals = bool(normals)
+    rot_tensors = [p.obj_rot for p in poses if p is not None and isinstance(p.obj_rot, torch.Tensor)]
+    train = torch.is_grad_enabled() and any(
+        t.requires_grad for t in (lists[2] if normals else []) + (rot_tensors if normals else []) + list(sems))
+    if not train:
+        with torch.no_grad():
+            return _C.compose_features(*lists, pose_t, idft_t, sems, normals, campos)
+    pose_rot, _ = _pose_graph(poses, rot_tensors)
+    flat = [t for per_field in lists[:6] for t in per_field]
+    return _ComposeFeatures.apply(len(models), pose_t, idft_t, lists[6], normals, campos, pose_rot, S, *flat, *sems)
+
+
+def gaussian_normals(scaling, rotation, xyz, campos):
+    """Drop-in for ``GaussianModel.get_normals(camera)`` (gaussian_model.py:256-269) on one static model: the raw
+    ``_scaling`` / ``_rotation`` / ``_xyz`` and ``camera.camera_center`` -> ``[N,3]``."""
+    n = xyz.shape[0]
+    dc = xyz.new_zeros(n, 1, 3)   # (colour and opacity take no part)
+    m = ModelParams(xyz, scaling, rotation, xyz.new_zeros(n, 1), dc, xyz.new_zeros(n, 0, 3))
+    return compose_features([m], [None], None, True, campos)
+
+
+class _ComposedRasterizeFeatures(torch.autograd.Function):
+    """Training path of forward_features: forward = _C.rasterize_gaussians_composed_features(for_backward=True),
+    backward = _C.rasterize_gaussians_composed_features_backward (C ABI grpg_backward_composed_features)."""
+
+    @staticmethod
+    def forward(ctx, owner, rs, nm, pose_t, idft_t, flips, normals, S, pose_rot, pose_trans, means2D, *flat):
+        lists = [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
+        sems = list(flat[6 * nm:])
+        num_rendered, color, depth, alpha, features, radii, geom, binning, img, blob = \
+            _C.rasterize_gaussians_composed_features(
+                rs.bg, *lists, flips, pose_t, idft_t, sems, normals, rs.scale_modifier, rs.viewmatrix, rs.projmatrix,
+                rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.sh_degree, rs.campos, rs.debug, True)
+        ctx.rs, ctx.nm, ctx.num_rendered, ctx.normals, ctx.S = rs, nm, num_rendered, normals, S
+        owner.num_rendered = num_rendered
+        ctx.pose_t, ctx.idft_t, ctx.flips = pose_t, idft_t, flips
+        ctx.pose_dev = (None if pose_rot is None else pose_rot.device,
+                        None if pose_trans is None else pose_trans.device)
+        ctx.save_for_backward(radii, alpha, geom, binning, img, blob, *flat[:6 * nm])
+        ctx.mark_non_differentiable(radii)
+        return color, radii, depth, alpha, features
+
+    @staticmethod
+    def backward(ctx, g_color, g_radii, g_depth, g_alpha, g_features):
+        rs, nm = ctx.rs, ctx.nm
+        radii, alpha, geom, binning, img, blob = ctx.saved_tensors[:6]
+        flat = ctx.saved_tensors[6:]
+        lists = [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
+        zeros = lambda t: torch.zeros_like(t)   # noqa: E731  (an output the loss does not touch)
+        need = ctx.needs_input_grad
+        F = 3 * int(ctx.normals) + ctx.S
+        H, W = alpha.shape[-2], alpha.shape[-1]
+        want_sem = [bool(n) for n in need[11 + 6 * nm:]] or [False] * nm
+        gx, gs, gr, go, gdc, gfr, gsem, g_means2D, g_poses = _C.rasterize_gaussians_composed_features_backward(
+            rs.bg, *lists, ctx.flips, ctx.pose_t, ctx.idft_t, ctx.S, want_sem, ctx.normals, rs.scale_modifier,
+            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.sh_degree, rs.campos, radii, alpha, geom,
+            ctx.num_rendered, binning, img, blob,
+            g_color if g_color is not None else zeros(alpha).expand(3, -1, -1).contiguous(),
+            g_depth if g_depth is not None else zeros(alpha),
+            g_alpha if g_alpha is not None else zeros(alpha),
+            g_features if g_features is not None else alpha.new_zeros(F, H, W), rs.debug)
+        g_rot = g_poses[:, 0:4].to(ctx.pose_dev[0]) if need[8] else None
+        g_trans = g_poses[:, 4:7].to(ctx.pose_dev[1]) if need[9] else None
+        grads = [g for per_field in (gx, gs, gr, go, gdc, gfr) for g in per_field]
+        flat_grads = tuple(g if n else None for g, n in zip(grads, need[11:11 + 6 * nm]))
+        sem_grads = tuple(g if (n and g.numel()) else None for g, n in zip(gsem, need[11 + 6 * nm:]))
+        return (None,) * 8 + (g_rot, g_trans, g_means2D if need[10] else None) + flat_grads + sem_grads
+
+
 class _ComposedRasterize(torch.autograd.Function):
     """Training path: forward = _C.rasterize_gaussians_composed(for_backward=True), backward =
     _C.rasterize_gaussians_composed_backward (C ABI grpg_backward_composed)."""
@@ -299,3 +473,34 @@ class ComposedRasterizer(nn.Module):
             pose_trans = torch.stack([zero3.to(dev) if p is None else as_t(p.obj_trans, dev) for p in poses])
         return _ComposedRasterize.apply(self, rs, len(models), pose_t, idft_t, flips, pose_rot, pose_trans,
                                         means2D, *flat)
+
+    def forward_features(self, models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]], semantics=None,
+                         normals: bool = False, means2D=None):
+        """``forward`` with ``F = 3 * normals + S`` feature planes (C ABI ``grpg_forward_composed_features`` /
+        ``grpg_backward_composed_features``): returns ``(color, radii, depth, alpha, features [F,H,W])``, the normal
+        planes first, then the semantic ones -- the order of street_gaussian_renderer.py:205-215.  ``semantics``: one
+        ``[N_i,S]`` tensor, or None (zeros), per model.  The planes are raw: ``F.normalize(dim=0)`` of the normals and
+        the ``probabilities`` transform of the semantics stay with the caller (``semantic_loss(mode=...)`` takes raw
+        planes).  Differentiable like ``forward``, and with respect to the semantic arrays; the normals' gradient
+        reaches the raw rotations and tensor-valued ``obj_rot``.  A backward needs F <= 32; the forward takes any F."""
+        rs = self.raster_settings
+        _check_models(models)
+        sems, S = _semantic_list(models, semantics)
+        normals = bool(normals)
+        lists, pose_t, idft_t = _pack(models, poses)
+        flips = lists[6]
+        flat = [t for per_field in lists[:6] for t in per_field]
+        pose_tensors = _pose_tensors(poses)
+        train = torch.is_grad_enabled() and any(
+            t.requires_grad for t in flat + pose_tensors + list(sems) + ([means2D] if means2D is not None else []))
+        if not train:
+            with torch.no_grad():
+                num_rendered, color, depth, alpha, features, radii = _C.rasterize_gaussians_composed_features(
+                    rs.bg, *lists, pose_t, idft_t, sems, normals, rs.scale_modifier, rs.viewmatrix, rs.projmatrix,
+                    rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.sh_degree, rs.campos, rs.debug,
+                    False)[:6]
+            self.num_rendered = num_rendered
+            return color, radii, depth, alpha, features
+        pose_rot, pose_trans = _pose_graph(poses, pose_tensors)
+        return _ComposedRasterizeFeatures.apply(self, rs, len(models), pose_t, idft_t, flips, normals, S, pose_rot,
+                                                pose_trans, means2D, *flat, *sems)

@@ -26,6 +26,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <functional>
 #include <vector>
 
 #include "../../include/grpg_rasterizer.h"
@@ -504,6 +505,7 @@ namespace {
 // Pinned staging for the composed forward's segment table (thread-local; the frame's one host wait
 // guarantees the previous upload has been consumed before the buffer is reused).
 thread_local SegmentDev* g_seg_staging = nullptr;
+thread_local FeatureSegDev* g_feat_staging = nullptr;   // ... and for its feature table (grpg_forward_composed_features)
 
 // grpg_backward_composed returns without a host wait, so the pinned tables its asynchronous copies
 // read must outlive the call: a ring of slots, each guarded by an event recorded behind its copies
@@ -511,6 +513,7 @@ thread_local SegmentDev* g_seg_staging = nullptr;
 struct BwdStagingSlot {
   SegmentDev* segs = nullptr;
   grpg_model_segment_grad* grads = nullptr;
+  FeatureSegDev* feats = nullptr;   // (grpg_backward_composed_features)
   hipEvent_t ev = nullptr;
   bool used = false;
 };
@@ -523,6 +526,7 @@ BwdStagingSlot* bwd_staging_acquire() {
   if (!b.segs) {
     if (hipHostMalloc((void**)&b.segs, sizeof(SegmentDev) * MAX_SEGMENTS, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc((void**)&b.grads, sizeof(grpg_model_segment_grad) * MAX_SEGMENTS, hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void**)&b.feats, sizeof(FeatureSegDev) * MAX_SEGMENTS, hipHostMallocDefault) != hipSuccess ||
         hipEventCreateWithFlags(&b.ev, hipEventDisableTiming) != hipSuccess)
       return nullptr;
   }
@@ -569,6 +573,11 @@ struct FrameRequest {
   int* radii = nullptr;
   const grpg_model_segment* segs = nullptr;
   int nseg = 0;
+  // grpg_forward_composed_features: the segments' semantic arrays (host array of device pointers, or NULL), the
+  // channel split S = 3 * feat_normals + feat_S, and the blob whose head is the [P,S] array `semantics` points at
+  const float* const* seg_semantic = nullptr;
+  int feat_S = 0, feat_normals = 0;
+  char* feat_blob = nullptr;
   DeferSlot* defer = nullptr;           // grpg_forward_deferred: the slot the frame's count is published to
   const LayerArgs* layers = nullptr;    // a layered frame
   const FrameEpilogue* epi = nullptr;   // grpg_forward_frame: sky composite / clamp / bytes behind the blend
@@ -598,9 +607,12 @@ int validate(const FrameRequest& q) {
       return fail(GRPG_ERR_INVALID_ARGUMENT, "need shs (M>0) or colors_precomp");
     if (!q.colors_precomp && (q.D < 0 || q.D > 3 || (q.D + 1) * (q.D + 1) > q.M))
       return fail(GRPG_ERR_INVALID_ARGUMENT, "SH degree needs (D+1)^2 <= M, D <= 3");
-    if (q.S > 0 && (!q.semantics || !q.out_semantic))
-      return fail(GRPG_ERR_INVALID_ARGUMENT, "semantics/out_semantic NULL with S>0");
   }
+  // (a composed frame's feature array is the head of its feature blob: grpg_forward_composed_features)
+  if (q.P > 0 && q.S > 0 && (!q.semantics || !q.out_semantic))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantics/out_semantic NULL with S>0");
+  if (q.segs != nullptr && q.S > 0 && (q.layers || q.defer))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "feature planes of a composed frame: not in a layered or deferred frame");
   return GRPG_OK;
 }
 
@@ -793,6 +805,20 @@ struct Frame {
     return GRPG_OK;
   }
 
+  // composed frame with feature planes -- the feature table like the segment table, then the producer kernel
+  int stage_features(const SegmentDev* seg_dev) {
+    if (!g_feat_staging)
+      HIP_TRY(hipHostMalloc((void**)&g_feat_staging, sizeof(FeatureSegDev) * MAX_SEGMENTS, hipHostMallocDefault));
+    for (int i = 0; i < q.nseg; i++)
+      g_feat_staging[i] = FeatureSegDev{q.seg_semantic ? q.seg_semantic[i] : nullptr, nullptr, nullptr, nullptr};
+    const FeatLayout FL = feat_layout((size_t)q.P, (size_t)q.S);
+    FeatureSegDev* fdev = (FeatureSegDev*)(q.feat_blob + FL.table);
+    HIP_TRY(hipMemcpyAsync(fdev, g_feat_staging, sizeof(FeatureSegDev) * (size_t)q.nseg, hipMemcpyHostToDevice, stream));
+    launch_compose_features(stream, q.P, seg_dev, fdev, q.nseg, q.feat_S, q.feat_normals, q.cam_pos,
+                            (float*)(q.feat_blob + FL.features));
+    return GRPG_OK;
+  }
+
   // Everything that does not depend on the binning capacities: frame init, preprocess, the count's publish, the
   // depth sort.  (A frame without a carved blob -- bin all zero -- initialises the other two blobs only.)
   int enqueue_head() {
@@ -811,6 +837,9 @@ struct Frame {
       if (int rc = stage_segments(seg_dev)) return rc;
       launch_preprocess_composed(stream, q.P, q.D, q.M, seg_dev, q.nseg, q.scale_modifier, cam, radii_int, rec_w,
                                  key_a, tiles, rects, fat_sort ? ds_table : nullptr, pre_counts, marks);
+      if (q.S > 0) {   // the frame's feature planes: [P,S] from the models' own arrays (features.hip)
+        if (int rc = stage_features(seg_dev)) return rc;
+      }
     }
     // num_rendered (and the coarse pair count) as sums of the per-Gaussian counts: in the pinned
     // word ~70 us into the frame, with an event behind it.  The host looks at it only after the
@@ -1445,14 +1474,17 @@ int grpg_forward_composed(grpg_alloc_fn geometry_alloc, void* geometry_user,
                                      GRPG_FORWARD_NO_BACKWARD);
 }
 
-int grpg_backward_composed(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
-                           int num_segments, int D, int M, int R, const float* background, int width,
-                           int height, float scale_modifier, const float* viewmatrix,
-                           const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                           const int* radii, const float* alphas, char* geom_buffer, char* binning_buffer,
-                           char* image_buffer, const float* dL_dpix, const float* dL_dpix_depth,
-                           const float* dL_dalphas, float* dL_dmean2D, float* dL_dposes, int debug,
-                           void* hip_stream) {
+// Shared body of grpg_backward_composed (F = 0) and grpg_backward_composed_features: the blend backward over the
+// frame's F feature channels, then the composed preprocess backward.
+static int backward_composed_impl(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
+                                  int num_segments, int D, int M, int R, const float* background, int width,
+                                  int height, float scale_modifier, const float* viewmatrix,
+                                  const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                                  const int* radii, const float* alphas, char* geom_buffer, char* binning_buffer,
+                                  char* image_buffer, const float* dL_dpix, const float* dL_dpix_depth,
+                                  const float* dL_dalphas, float* dL_dmean2D, float* dL_dposes, int debug,
+                                  void* hip_stream, const float* features, int F, const float* dL_dpix_features,
+                                  float* dL_dfeatures) {
   g_last_error.clear();
   if (int rc = ensure_device()) return rc;
   long long Pll = 0;
@@ -1501,9 +1533,9 @@ int grpg_backward_composed(const grpg_model_segment* segments, const grpg_model_
   HIP_TRY(hipMemsetAsync(grad_rec, 0, (size_t)P * GRAD_STRIDE * sizeof(float), stream));
   BwdTimingRecord* const btr = bwd_timing_begin(stream);
   BwdTimingGuard btg(btr);
-  launch_render_backward(stream, ranges, point_list, rec, nullptr, 0, width, height, cam.gx, cam.gy,
+  launch_render_backward(stream, ranges, point_list, rec, features, F, width, height, cam.gx, cam.gy,
                          background, alphas, n_contrib, (const uint32_t*)(image_buffer + IL.work), dL_dpix,
-                         dL_dpix_depth, dL_dalphas, nullptr, grad_rec, nullptr,
+                         dL_dpix_depth, dL_dalphas, dL_dpix_features, grad_rec, dL_dfeatures,
                          (const BlobHeader*)binning_buffer, (const uint32_t*)(image_buffer + IL.ck_count),
                          (const uint32_t*)(image_buffer + IL.bwd_ctl), (uint32_t)R);
   STAGE_CHECK("render backward");
@@ -1515,6 +1547,189 @@ int grpg_backward_composed(const grpg_model_segment* segments, const grpg_model_
   btg.done = true;
   STAGE_CHECK("preprocess backward (composed)");
   return GRPG_OK;
+}
+
+int grpg_backward_composed(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
+                           int num_segments, int D, int M, int R, const float* background, int width,
+                           int height, float scale_modifier, const float* viewmatrix,
+                           const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                           const int* radii, const float* alphas, char* geom_buffer, char* binning_buffer,
+                           char* image_buffer, const float* dL_dpix, const float* dL_dpix_depth,
+                           const float* dL_dalphas, float* dL_dmean2D, float* dL_dposes, int debug,
+                           void* hip_stream) {
+  return backward_composed_impl(segments, grads, num_segments, D, M, R, background, width, height, scale_modifier,
+                                viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, alphas, geom_buffer,
+                                binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dmean2D,
+                                dL_dposes, debug, hip_stream, nullptr, 0, nullptr, nullptr);
+}
+
+// the channel split of a composed frame's feature planes: S >= 0, normals 0 / 1 -> F
+static int check_feature_split(int S, int normals, int* F) {
+  if (S < 0 || (normals != 0 && normals != 1))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "feature planes: S must be >= 0 and normals 0 or 1");
+  *F = 3 * normals + S;
+  return GRPG_OK;
+}
+
+int grpg_forward_composed_features(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_fn binning_alloc,
+                                   void* binning_user, grpg_alloc_fn image_alloc, void* image_user,
+                                   grpg_alloc_fn feature_alloc, void* feature_user,
+                                   const grpg_model_segment* segments, int num_segments,
+                                   const float* const* seg_semantic, int S, int normals, int D, int M,
+                                   const float* background, int width, int height, float scale_modifier,
+                                   const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                                   float tan_fovx, float tan_fovy, float* out_color, float* out_depth,
+                                   float* out_alpha, float* out_features, int* radii, int debug, void* hip_stream,
+                                   unsigned flags) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  long long P = 0;
+  if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
+  int F = 0;
+  if (int rc = check_feature_split(S, normals, &F)) return rc;
+  if (!feature_alloc) return fail(GRPG_ERR_INVALID_ARGUMENT, "buffer allocators must not be NULL");
+  if (F > 0 && !out_features) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantics/out_semantic NULL with S>0");
+  if (normals && !cam_pos) return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL camera/background/output pointer");
+  const FeatLayout FL = feat_layout((size_t)P, (size_t)F);
+  char* blob = feature_alloc(FL.total, feature_user);
+  if (!blob) return fail(GRPG_ERR_ALLOC, "feature buffer allocation failed");
+  FrameRequest q;
+  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
+  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
+  q.segs = segments; q.nseg = num_segments; q.P = (int)P; q.D = D; q.M = M; q.background = background;
+  q.width = width; q.height = height; q.scale_modifier = scale_modifier; q.viewmatrix = viewmatrix;
+  q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy;
+  q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha; q.radii = radii; q.debug = debug;
+  q.stream = (hipStream_t)hip_stream; q.flags = flags;
+  q.seg_semantic = seg_semantic; q.feat_S = S; q.feat_normals = normals; q.feat_blob = blob;
+  q.S = F; q.semantics = (const float*)(blob + FL.features); q.out_semantic = out_features;
+  return forward_impl(q);
+}
+
+int grpg_backward_composed_features(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
+                                    int num_segments, float* const* seg_dL_dsemantic, int S, int normals, int D,
+                                    int M, int R, const float* background, int width, int height,
+                                    float scale_modifier, const float* viewmatrix, const float* projmatrix,
+                                    const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                                    const float* alphas, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                    char* feature_buffer, const float* dL_dpix, const float* dL_dpix_depth,
+                                    const float* dL_dalphas, const float* dL_dpix_features, float* dL_dfeatures,
+                                    float* dL_dmean2D, float* dL_dposes, int debug, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  int F = 0;
+  if (int rc = check_feature_split(S, normals, &F)) return rc;
+  if (F > GRPG_MAX_SEMANTIC_BACKWARD)   // the blend backward carries the channels in registers
+    return fail(GRPG_ERR_INVALID_ARGUMENT,
+                "backward supports at most 32 semantic channels (the reference: 20, config.h:16)");
+  if (F > 0 && (!feature_buffer || !dL_dpix_features || !dL_dfeatures))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL semantic pointer with S>0");
+  const float* features = F > 0 ? (const float*)(feature_buffer + feat_layout(0, 0).features) : nullptr;
+  if (int rc = backward_composed_impl(segments, grads, num_segments, D, M, R, background, width, height,
+                                      scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                                      alphas, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth,
+                                      dL_dalphas, dL_dmean2D, dL_dposes, debug, hip_stream, features, F,
+                                      dL_dpix_features, dL_dfeatures))
+    return rc;
+  if (F == 0) return GRPG_OK;
+  // the feature gradient back to the models, behind the preprocess backward on the same stream (it ADDS to the
+  // rotation and pose gradients that one has written)
+  hipStream_t stream = (hipStream_t)hip_stream;
+  long long P = 0;
+  for (int i = 0; i < num_segments; i++) P += segments[i].count;
+  BwdStagingSlot* stg = bwd_staging_acquire();
+  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
+  for (int i = 0; i < num_segments; i++)
+    stg->feats[i] = FeatureSegDev{nullptr, seg_dL_dsemantic ? seg_dL_dsemantic[i] : nullptr, grads[i].rotation, nullptr};
+  const FeatLayout FL = feat_layout((size_t)P, (size_t)F);
+  FeatureSegDev* fdev = (FeatureSegDev*)(feature_buffer + FL.table);
+  HIP_TRY(hipMemcpyAsync(fdev, stg->feats, sizeof(FeatureSegDev) * (size_t)num_segments, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(stg->ev, stream));
+  const GeomLayout GL = geom_layout((size_t)P);
+  launch_compose_features_backward(stream, (int)P, (const SegmentDev*)(geom_buffer + GL.seg_table), fdev,
+                                   num_segments, S, normals, campos, dL_dfeatures,
+                                   (float*)(feature_buffer + FL.partials), FL.nslots, dL_dposes);
+  STAGE_CHECK("feature backward");
+  return GRPG_OK;
+}
+
+// the arguments the two stand-alone feature entries share
+static int check_feature_call(const grpg_model_segment* segments, int num_segments, int S, int normals,
+                              const float* cam_pos, long long* P, int* F) {
+  if (int rc = check_segments(segments, num_segments, 1, P)) return rc;
+  if (int rc = check_feature_split(S, normals, F)) return rc;
+  if (normals && !cam_pos) return fail(GRPG_ERR_INVALID_ARGUMENT, "normals need cam_pos");
+  return GRPG_OK;
+}
+
+// Stand-alone feature calls: the two tables (and the backward's slots) travel through a temporary device buffer,
+// like grpg_compose's.
+static int feature_call(const grpg_model_segment* segments, int num_segments, const float* const* seg_semantic,
+                        float* const* seg_dL_dsemantic, float* const* seg_dL_drotation, long long P, int F,
+                        hipStream_t stream, const char* what,
+                        const std::function<void(const SegmentDev*, const FeatureSegDev*, float*, uint32_t)>& launch) {
+  const size_t n = (size_t)num_segments;
+  std::vector<SegmentDev> host(n);
+  std::vector<FeatureSegDev> fhost(n);
+  uint32_t start = 0;
+  for (size_t i = 0; i < n; i++) {
+    fill_segment(host[i], segments[i], start, nullptr);
+    start += (uint32_t)segments[i].count;
+    fhost[i] = FeatureSegDev{seg_semantic ? seg_semantic[i] : nullptr, seg_dL_dsemantic ? seg_dL_dsemantic[i] : nullptr,
+                             seg_dL_drotation ? seg_dL_drotation[i] : nullptr, nullptr};
+  }
+  const FeatLayout FL = feat_layout((size_t)P, 0);   // (no feature array: the caller's)
+  const size_t seg_bytes = (sizeof(SegmentDev) * n + 255) / 256 * 256;
+  char* dev = nullptr;
+  HIP_TRY(hipMalloc((void**)&dev, seg_bytes + FL.total));
+  hipError_t e = hipMemcpyAsync(dev, host.data(), sizeof(SegmentDev) * n, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(dev + seg_bytes + FL.table, fhost.data(), sizeof(FeatureSegDev) * n, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);   // pageable sources: the copies must finish before they die
+  if (e == hipSuccess) {
+    launch((const SegmentDev*)dev, (const FeatureSegDev*)(dev + seg_bytes + FL.table),
+           (float*)(dev + seg_bytes + FL.partials), FL.nslots);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  }
+  (void)hipFree(dev);
+  if (e != hipSuccess) return fail(GRPG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  return GRPG_OK;
+}
+
+int grpg_compose_features(const grpg_model_segment* segments, int num_segments, const float* const* seg_semantic,
+                          int S, int normals, const float* cam_pos, float* features, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  long long P = 0;
+  int F = 0;
+  if (int rc = check_feature_call(segments, num_segments, S, normals, cam_pos, &P, &F)) return rc;
+  if (F == 0) return GRPG_OK;
+  if (!features) return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL output pointer");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  return feature_call(segments, num_segments, seg_semantic, nullptr, nullptr, P, F, stream, "grpg_compose_features",
+                      [&](const SegmentDev* sd, const FeatureSegDev* fd, float*, uint32_t) {
+                        launch_compose_features(stream, (int)P, sd, fd, num_segments, S, normals, cam_pos, features);
+                      });
+}
+
+int grpg_compose_features_backward(const grpg_model_segment* segments, int num_segments, int S, int normals,
+                                   const float* cam_pos, const float* dL_dfeatures, float* const* seg_dL_dsemantic,
+                                   float* const* seg_dL_drotation, float* dL_dposes, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  long long P = 0;
+  int F = 0;
+  if (int rc = check_feature_call(segments, num_segments, S, normals, cam_pos, &P, &F)) return rc;
+  if (F == 0) return GRPG_OK;
+  if (!dL_dfeatures || (normals && !dL_dposes)) return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL gradient pointer");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  return feature_call(segments, num_segments, nullptr, seg_dL_dsemantic, seg_dL_drotation, P, F, stream,
+                      "grpg_compose_features_backward",
+                      [&](const SegmentDev* sd, const FeatureSegDev* fd, float* partials, uint32_t nslots) {
+                        launch_compose_features_backward(stream, (int)P, sd, fd, num_segments, S, normals, cam_pos,
+                                                         dL_dfeatures, partials, nslots, dL_dposes);
+                      });
 }
 
 int grpg_compose(const grpg_model_segment* segments, int num_segments, int M, float* means3D,

@@ -618,6 +618,40 @@ void launch_sky_backward(hipStream_t st, const float* cube, int res, const float
 size_t knn_workspace_bytes(int P);
 void launch_knn(hipStream_t s, int P, const float* points, float* mean_dists, char* workspace);
 
+// Feature planes of a composed frame (features.hip): F = 3 * normals + S channels per Gaussian, normals first.
+// One row per segment, next to its SegmentDev row: the model's semantic array and where its gradients go.
+struct FeatureSegDev {
+  const float* semantic;   // [count,S] or NULL (zeros)
+  float* dL_dsemantic;     // [count,S], written; NULL: not wanted
+  float* dL_drotation;     // [count,4] raw-rotation gradient, ADDED to; NULL: not wanted
+  const void* pad;
+};
+constexpr int FEATURE_THREADS = 256;
+// The feature blob of grpg_forward_composed_features: the flat [P,F] array the blend reads, the segments' feature
+// table, and the slots of the backward's pose sum -- one per (workgroup, segment) pair, slot = workgroup + segment
+// (both ascend together, so the slots of one segment are contiguous), for each of the 4 quaternion components.
+struct FeatLayout {
+  size_t features, table, partials, total;
+  uint32_t nslots;
+};
+inline FeatLayout feat_layout(size_t P, size_t F) {
+  FeatLayout L;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
+  L.features = take(P * F * 4);
+  L.table = take((size_t)MAX_SEGMENTS * sizeof(FeatureSegDev));
+  L.nslots = (uint32_t)((P + FEATURE_THREADS - 1) / FEATURE_THREADS) + (uint32_t)MAX_SEGMENTS;
+  L.partials = take((size_t)4 * L.nslots * 4);
+  L.total = o;
+  return L;
+}
+void launch_compose_features(hipStream_t st, int P, const SegmentDev* segs, const FeatureSegDev* fsegs, int nseg, int S,
+                             int normals, const float* campos, float* features);
+// partials: float[4][nslots], nslots >= ceil(P / FEATURE_THREADS) + nseg (untouched when normals == 0)
+void launch_compose_features_backward(hipStream_t st, int P, const SegmentDev* segs, const FeatureSegDev* fsegs,
+                                      int nseg, int S, int normals, const float* campos, const float* dL_dfeatures,
+                                      float* partials, uint32_t nslots, float* dL_dposes);
+
 // fused SSIM + L1 loss (ssim.hip)
 size_t ssim_workspace_bytes(int B, int C, int H, int W);
 void launch_ssim_forward(hipStream_t st, int B, int C, int H, int W, const float* x1, const float* x2,

@@ -89,6 +89,48 @@ __device__ __forceinline__ Activated compose_one(const SegmentDev& sg, const uin
   return a;
 }
 
+// Backward of compose_one()'s rotation: gq = dL/dq of the world quaternion q (a.q of compose_one) -> dL/d(raw
+// _rotation) of Gaussian j, through  raw r -> n = r / |r| -> [flip] ql -> [actor: p = a (x) ql -> q = p / |p|].  For a
+// rigid segment pa[0..4) receives this Gaussian's share of dL/da, a = obj_rot as given (the product path; the path
+// through R(a / |a|) of the means is not this function's); pa is left alone otherwise.  Shared by the composed
+// preprocess backward and the feature backward (features.hip): the same operations in the same order.
+__device__ __forceinline__ float4 rotation_chain_backward(const SegmentDev& sg, const uint32_t j, const float4 q,
+                                                          const float4 gq, float* pa) {
+  const bool flip = sg.flip != nullptr && sg.flip[j] != 0;
+  const float4 rq = load_quat(sg.rotation, (int)j);
+  const float rn = fmaxf(sqrtf(rq.x * rq.x + rq.y * rq.y + rq.z * rq.z + rq.w * rq.w), 1e-12f);
+  const float4 qn_ = make_float4(rq.x / rn, rq.y / rn, rq.z / rn, rq.w / rn);
+  const float4 ql = flip ? make_float4(-qn_.z, qn_.w, qn_.x, -qn_.y) : qn_;   // as in compose_one
+  float4 gql = gq;   // dL/dq of the quaternion the op used
+  if (sg.rigid) {
+    const float aw = sg.rot[0], ax = sg.rot[1], ay = sg.rot[2], az = sg.rot[3];
+    const float ow = aw * ql.x - ax * ql.y - ay * ql.z - az * ql.w;
+    const float ox = aw * ql.y + ax * ql.x + ay * ql.w - az * ql.z;
+    const float oy = aw * ql.z - ax * ql.w + ay * ql.x + az * ql.y;
+    const float oz = aw * ql.w + ax * ql.z - ay * ql.y + az * ql.x;
+    const float pn = fmaxf(sqrtf(ow * ow + ox * ox + oy * oy + oz * oz), 1e-12f);
+    // through q = p / |p|
+    const float along = q.x * gql.x + q.y * gql.y + q.z * gql.z + q.w * gql.w;
+    const float ipn = 1.0f / pn;
+    const float gw = (gql.x - q.x * along) * ipn, gx = (gql.y - q.y * along) * ipn,
+                gy = (gql.z - q.z * along) * ipn, gz = (gql.w - q.w * along) * ipn;
+    // through the Hamilton product (general_utils.py:220-238): p = a (x) b, b = ql
+    gql = make_float4(aw * gw + ax * gx + ay * gy + az * gz, -ax * gw + aw * gx + az * gy - ay * gz,
+                      -ay * gw - az * gx + aw * gy + ax * gz, -az * gw + ay * gx - ax * gy + aw * gz);
+    pa[0] = ql.x * gw + ql.y * gx + ql.z * gy + ql.w * gz;
+    pa[1] = -ql.y * gw + ql.x * gx - ql.w * gy + ql.z * gz;
+    pa[2] = -ql.z * gw + ql.w * gx + ql.x * gy - ql.y * gz;
+    pa[3] = -ql.w * gw - ql.z * gx + ql.y * gy + ql.x * gz;
+  }
+  // back through the flip's signed permutation ql = (-n.y', n.z', n.w', -n.x') of the normalised
+  // local quaternion n = (w, x, y, z): dL/dn = (g_y, -g_z, -g_w, g_x) in (w, x, y, z) order
+  const float4 gn = flip ? make_float4(gql.z, -gql.w, -gql.x, gql.y) : gql;
+  const float along = qn_.x * gn.x + qn_.y * gn.y + qn_.z * gn.z + qn_.w * gn.w;
+  const float irn = 1.0f / rn;
+  return make_float4((gn.x - qn_.x * along) * irn, (gn.y - qn_.y * along) * irn, (gn.z - qn_.z * along) * irn,
+                     (gn.w - qn_.w * along) * irn);
+}
+
 // All M coefficients of Gaussian j of a segment into sh[3*M] (DC first, then _features_rest).
 __device__ __forceinline__ void compose_features(const SegmentDev& sg, const uint32_t j,
                                                  const Activated& a, const int M, float* sh) {

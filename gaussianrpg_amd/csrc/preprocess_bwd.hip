@@ -382,43 +382,10 @@ __device__ __forceinline__ void composed_backward_one(
       go.fdc[((size_t)j * F + c) * 3 + 2] = dsh[2] * sg.idft[c];
     }
     for (int e = 0; e < 3 * (Mc - 1); e++) go.frest[(size_t)j * (Mc - 1) * 3 + e] = dsh[3 + e];
-    // ---- rotation: raw r -> ql = r / |r| [-> p = a (x) ql -> q = p / |p|] ----
+    // ---- rotation: raw r -> ql = r / |r| [-> p = a (x) ql -> q = p / |p|] (compose_math.h) ----
     const bool flip = sg.flip != nullptr && sg.flip[j] != 0;
-    const float4 rq = load_quat(sg.rotation, (int)j);
-    const float rn = fmaxf(sqrtf(rq.x * rq.x + rq.y * rq.y + rq.z * rq.z + rq.w * rq.w), 1e-12f);
-    const float4 qn_ = make_float4(rq.x / rn, rq.y / rn, rq.z / rn, rq.w / rn);
-    const float4 ql = flip ? make_float4(-qn_.z, qn_.w, qn_.x, -qn_.y) : qn_;   // as in compose_one
-    float4 gql = make_float4(dr[0], dr[1], dr[2], dr[3]);   // dL/dq of the quaternion the op used
-    if (sg.rigid) {
-      const float aw = sg.rot[0], ax = sg.rot[1], ay = sg.rot[2], az = sg.rot[3];
-      const float ow = aw * ql.x - ax * ql.y - ay * ql.z - az * ql.w;
-      const float ox = aw * ql.y + ax * ql.x + ay * ql.w - az * ql.z;
-      const float oy = aw * ql.z - ax * ql.w + ay * ql.x + az * ql.y;
-      const float oz = aw * ql.w + ax * ql.z - ay * ql.y + az * ql.x;
-      const float pn = fmaxf(sqrtf(ow * ow + ox * ox + oy * oy + oz * oz), 1e-12f);
-      // through q = p / |p| (a.q is that q)
-      const float along = a.q.x * gql.x + a.q.y * gql.y + a.q.z * gql.z + a.q.w * gql.w;
-      const float ipn = 1.0f / pn;
-      const float gw = (gql.x - a.q.x * along) * ipn, gx = (gql.y - a.q.y * along) * ipn,
-                  gy = (gql.z - a.q.z * along) * ipn, gz = (gql.w - a.q.w * along) * ipn;
-      // through the Hamilton product (general_utils.py:220-238): p = a (x) b, b = ql
-      gql = make_float4(aw * gw + ax * gx + ay * gy + az * gz, -ax * gw + aw * gx + az * gy - ay * gz,
-                        -ay * gw - az * gx + aw * gy + ax * gz, -az * gw + ay * gx - ax * gy + aw * gz);
-      pv[12] = ql.x * gw + ql.y * gx + ql.z * gy + ql.w * gz;
-      pv[13] = -ql.y * gw + ql.x * gx - ql.w * gy + ql.z * gz;
-      pv[14] = -ql.z * gw + ql.w * gx + ql.x * gy - ql.y * gz;
-      pv[15] = -ql.w * gw - ql.z * gx + ql.y * gy + ql.x * gz;
-    }
-    {
-      // back through the flip's signed permutation ql = (-n.y', n.z', n.w', -n.x') of the normalised
-      // local quaternion n = (w, x, y, z): dL/dn = (g_y, -g_z, -g_w, g_x) in (w, x, y, z) order
-      const float4 gn = flip ? make_float4(gql.z, -gql.w, -gql.x, gql.y) : gql;
-      const float along = qn_.x * gn.x + qn_.y * gn.y + qn_.z * gn.z + qn_.w * gn.w;
-      const float irn = 1.0f / rn;
-      reinterpret_cast<float4*>(go.rotation)[j] =
-          make_float4((gn.x - qn_.x * along) * irn, (gn.y - qn_.y * along) * irn, (gn.z - qn_.z * along) * irn,
-                      (gn.w - qn_.w * along) * irn);
-    }
+    reinterpret_cast<float4*>(go.rotation)[j] =
+        rotation_chain_backward(sg, j, a.q, make_float4(dr[0], dr[1], dr[2], dr[3]), pv + 12);
     // ---- mean: world == local, or m = R(a / |a|) x + t ----
     if (sg.rigid) {
       const float x = sg.xyz[3 * j], y = flip ? -sg.xyz[3 * j + 1] : sg.xyz[3 * j + 1], z = sg.xyz[3 * j + 2];

@@ -829,6 +829,200 @@ RasterizeGaussiansComposedBackward(
   return std::make_tuple(g_xyz, g_scaling, g_rotation, g_opacity, g_fdc, g_frest, dL_dmeans2D, dL_dposes);
 }
 
+// ---- feature planes of a composed frame (grpg_*_features): F = 3 * normals + S channels, normals first ----
+namespace {
+
+// The models' semantic arrays: one [N_i,S] float32 device tensor per model, or an empty one (zeros); S is what the
+// non-empty ones agree on.  No semantics at all: an empty list.
+struct SemanticPack {
+  std::vector<const float*> ptrs;
+  std::vector<torch::Tensor> keep;
+  int S = 0;
+};
+SemanticPack pack_semantics(const std::vector<torch::Tensor>& semantics, const std::vector<torch::Tensor>& xyz) {
+  SemanticPack sp;
+  const size_t n = xyz.size();
+  TORCH_CHECK(semantics.empty() || semantics.size() == n, "one semantic tensor (or an empty one) per model");
+  sp.ptrs.assign(n, nullptr);
+  sp.keep.resize(n);
+  bool have = false;
+  for (size_t i = 0; i < semantics.size(); i++) {
+    const torch::Tensor& t = semantics[i];
+    if (t.numel() == 0 && !(t.dim() == 2 && t.size(0) == xyz[i].size(0))) continue;   // "no semantics for this model"
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == xyz[i].size(0), "model ", i, ": semantics must be [N,S]");
+    TORCH_CHECK(!have || t.size(1) == sp.S, "all models must carry the same number of semantic channels (model ", i,
+                " has ", t.size(1), ", an earlier one ", sp.S, ")");
+    sp.S = t.size(1);
+    have = true;
+    sp.ptrs[i] = fptr(t, xyz[0], "semantics", sp.keep[i]);
+  }
+  return sp;
+}
+
+}  // namespace
+
+// composed.compose_features: [P,F]
+torch::Tensor ComposeFeatures(const std::vector<torch::Tensor>& xyz, const std::vector<torch::Tensor>& scaling,
+                              const std::vector<torch::Tensor>& rotation, const std::vector<torch::Tensor>& opacity,
+                              const std::vector<torch::Tensor>& features_dc,
+                              const std::vector<torch::Tensor>& features_rest, const std::vector<torch::Tensor>& flip,
+                              const torch::Tensor& poses, const torch::Tensor& idft,
+                              const std::vector<torch::Tensor>& semantics, const bool normals,
+                              const torch::Tensor& campos) {
+  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  const torch::Tensor& like = xyz[0];
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
+  const SemanticPack sp = pack_semantics(semantics, xyz);
+  torch::Tensor k_pos;
+  const float* p_pos = fptr(campos, like, "campos", k_pos);
+  TORCH_CHECK(!normals || (p_pos && campos.numel() == 3), "normals need campos (3 floats on the device)");
+  torch::Tensor features = torch::empty({pk.P, (int64_t)(3 * (normals ? 1 : 0) + sp.S)}, like.options().dtype(torch::kFloat32));
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int rc = grpg_compose_features(pk.segs.data(), (int)pk.segs.size(), sp.ptrs.data(), sp.S, normals ? 1 : 0, p_pos,
+                                       features.numel() ? features.data_ptr<float>() : nullptr, (void*)stream);
+  if (rc != GRPG_OK) raise_abi_error("grpg_compose_features", rc);
+  return features;
+}
+
+// its backward: (dL/d raw rotation per model, dL/d semantic per model ([N_i,S]; empty where want_semantic[i] is
+// false), dL_dposes [n,8] with the product path's share in [:, 0:4])
+std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>, torch::Tensor>
+ComposeFeaturesBackward(const std::vector<torch::Tensor>& xyz, const std::vector<torch::Tensor>& scaling,
+                        const std::vector<torch::Tensor>& rotation, const std::vector<torch::Tensor>& opacity,
+                        const std::vector<torch::Tensor>& features_dc, const std::vector<torch::Tensor>& features_rest,
+                        const std::vector<torch::Tensor>& flip, const torch::Tensor& poses, const torch::Tensor& idft,
+                        const int S, const std::vector<bool>& want_semantic, const bool normals,
+                        const torch::Tensor& campos, const torch::Tensor& dL_dfeatures) {
+  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  const torch::Tensor& like = xyz[0];
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
+  const size_t n = xyz.size();
+  const int64_t F = 3 * (normals ? 1 : 0) + S;
+  TORCH_CHECK(want_semantic.size() == n, "one want_semantic flag per model");
+  TORCH_CHECK(dL_dfeatures.dim() == 2 && dL_dfeatures.size(0) == pk.P && dL_dfeatures.size(1) == F,
+              "dL_dfeatures must be [P,F]");
+  torch::Tensor k_pos, k_g;
+  const float* p_pos = fptr(campos, like, "campos", k_pos);
+  const float* p_g = fptr(dL_dfeatures, like, "dL_dfeatures", k_g);
+  TORCH_CHECK(!normals || (p_pos && campos.numel() == 3), "normals need campos (3 floats on the device)");
+  auto o = like.options().dtype(torch::kFloat32);
+  std::vector<torch::Tensor> g_rot(n), g_sem(n);
+  std::vector<float*> p_rot(n, nullptr), p_sem(n, nullptr);
+  for (size_t i = 0; i < n; i++) {
+    g_rot[i] = torch::zeros(rotation[i].sizes(), o);   // added to
+    if (normals) p_rot[i] = g_rot[i].data_ptr<float>();
+    g_sem[i] = want_semantic[i] && S > 0 ? torch::empty({xyz[i].size(0), (int64_t)S}, o) : torch::empty({0}, o);
+    if (g_sem[i].numel()) p_sem[i] = g_sem[i].data_ptr<float>();
+  }
+  torch::Tensor dL_dposes = torch::zeros({(int64_t)n, 8}, o);
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int rc = grpg_compose_features_backward(pk.segs.data(), (int)n, S, normals ? 1 : 0, p_pos, p_g, p_sem.data(),
+                                                p_rot.data(), dL_dposes.data_ptr<float>(), (void*)stream);
+  if (rc != GRPG_OK) raise_abi_error("grpg_compose_features_backward", rc);
+  return std::make_tuple(g_rot, g_sem, dL_dposes);
+}
+
+// ComposedRasterizer.forward_features: rasterize_gaussians_composed + the feature planes [F,H,W] and the fourth blob.
+// returns (num_rendered, color, depth, alpha, features, radii, geom, binning, img, feature blob)
+std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor, torch::Tensor>
+RasterizeGaussiansComposedFeatures(const torch::Tensor& background, const std::vector<torch::Tensor>& xyz,
+                                   const std::vector<torch::Tensor>& scaling,
+                                   const std::vector<torch::Tensor>& rotation,
+                                   const std::vector<torch::Tensor>& opacity,
+                                   const std::vector<torch::Tensor>& features_dc,
+                                   const std::vector<torch::Tensor>& features_rest,
+                                   const std::vector<torch::Tensor>& flip, const torch::Tensor& poses,
+                                   const torch::Tensor& idft, const std::vector<torch::Tensor>& semantics,
+                                   const bool normals, const float scale_modifier, const torch::Tensor& viewmatrix,
+                                   const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                                   const int image_height, const int image_width, const int degree,
+                                   const torch::Tensor& campos, const bool debug, const bool for_backward) {
+  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  const torch::Tensor& like = xyz[0];
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
+  const SemanticPack sp = pack_semantics(semantics, xyz);
+  const int H = image_height, W = image_width, F = 3 * (normals ? 1 : 0) + sp.S;
+  CameraPtrs cam(like, background, nullptr);
+  cam.pose(like, viewmatrix, projmatrix, campos);
+  cam.require(LayerBg::kIfLayered, false);
+  ForwardOutputs o(like, pk.P, H, W, F, true, false);
+  torch::Tensor feat_blob = torch::empty({0}, like.options().dtype(torch::kByte));
+  const int rendered = run("grpg_forward_composed_features", [&](void* stream) {
+    return grpg_forward_composed_features(
+        resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, resize_blob, &feat_blob, pk.segs.data(),
+        (int)pk.segs.size(), sp.ptrs.data(), sp.S, normals ? 1 : 0, degree, pk.M, cam.bg, W, H, scale_modifier,
+        cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy, o.p_color, o.p_depth, o.p_alpha, o.p_semantic, o.p_radii,
+        debug ? 1 : 0, stream, for_backward ? 0u : GRPG_FORWARD_NO_BACKWARD);
+  });
+  return std::make_tuple(rendered, o.color, o.depth, o.alpha, o.semantic, o.radii, o.geom, o.binning, o.img, feat_blob);
+}
+
+// its backward (grpg_backward_composed_features): rasterize_gaussians_composed_backward's tuple with the semantic
+// gradients ([N_i,S] per model; empty where want_semantic[i] is false) in front of dL_dmeans2D
+std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
+           std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
+           std::vector<torch::Tensor>, torch::Tensor, torch::Tensor>
+RasterizeGaussiansComposedFeaturesBackward(
+    const torch::Tensor& background, const std::vector<torch::Tensor>& xyz,
+    const std::vector<torch::Tensor>& scaling, const std::vector<torch::Tensor>& rotation,
+    const std::vector<torch::Tensor>& opacity, const std::vector<torch::Tensor>& features_dc,
+    const std::vector<torch::Tensor>& features_rest, const std::vector<torch::Tensor>& flip,
+    const torch::Tensor& poses, const torch::Tensor& idft, const int S, const std::vector<bool>& want_semantic,
+    const bool normals, const float scale_modifier, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
+    const float tan_fovx, const float tan_fovy, const int degree, const torch::Tensor& campos,
+    const torch::Tensor& radii, const torch::Tensor& alphas, const torch::Tensor& geomBuffer, const int R,
+    const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const torch::Tensor& featureBuffer,
+    const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_depth, const torch::Tensor& dL_dout_alpha,
+    const torch::Tensor& dL_dout_features, const bool debug) {
+  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  const torch::Tensor& like = xyz[0];
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
+  const int H = dL_dout_color.size(1), W = dL_dout_color.size(2);
+  const size_t n = xyz.size();
+  const int64_t F = 3 * (normals ? 1 : 0) + S;
+  TORCH_CHECK(want_semantic.size() == n, "one want_semantic flag per model");
+  TORCH_CHECK(dL_dout_features.numel() == F * H * W, "dL_dout_features must be [F,H,W]");
+  auto o = like.options().dtype(torch::kFloat32);
+  std::vector<torch::Tensor> g_xyz(n), g_scaling(n), g_rotation(n), g_opacity(n), g_fdc(n), g_frest(n), g_sem(n);
+  std::vector<grpg_model_segment_grad> gs(n);
+  std::vector<float*> p_sem(n, nullptr);
+  for (size_t i = 0; i < n; i++) {   // every element is written by the kernels: no zero-fill
+    g_xyz[i] = torch::empty(xyz[i].sizes(), o);
+    g_scaling[i] = torch::empty(scaling[i].sizes(), o);
+    g_rotation[i] = torch::empty(rotation[i].sizes(), o);
+    g_opacity[i] = torch::empty(opacity[i].sizes(), o);
+    g_fdc[i] = torch::empty(features_dc[i].sizes(), o);
+    g_frest[i] = torch::empty(features_rest[i].sizes(), o);
+    gs[i] = grpg_model_segment_grad{g_xyz[i].data_ptr<float>(), g_scaling[i].data_ptr<float>(),
+                                    g_rotation[i].data_ptr<float>(), g_opacity[i].data_ptr<float>(),
+                                    g_fdc[i].data_ptr<float>(),
+                                    g_frest[i].numel() ? g_frest[i].data_ptr<float>() : nullptr};
+    g_sem[i] = want_semantic[i] && S > 0 ? torch::empty({xyz[i].size(0), (int64_t)S}, o) : torch::empty({0}, o);
+    if (g_sem[i].numel()) p_sem[i] = g_sem[i].data_ptr<float>();
+  }
+  torch::Tensor dL_dmeans2D = torch::empty({pk.P, 3}, o);
+  torch::Tensor dL_dposes = torch::empty({(int64_t)n, 8}, o);
+  torch::Tensor dL_dfeatures = torch::zeros({pk.P, F}, o);   // the blend backward accumulates into it
+  CameraPtrs cam(like, background, nullptr);
+  cam.pose(like, viewmatrix, projmatrix, campos);
+  torch::Tensor k_alpha, k_blob;
+  const float* p_alpha = fptr(alphas, like, "alphas", k_alpha);
+  const SavedState sv(like, dL_dout_color, dL_dout_depth, dL_dout_alpha, &dL_dout_features, radii, geomBuffer,
+                      binningBuffer, imageBuffer);
+  TORCH_CHECK(featureBuffer.scalar_type() == torch::kByte && featureBuffer.device() == like.device(),
+              "the feature blob must be the forward's byte tensor");
+  char* p_blob = reinterpret_cast<char*>((k_blob = featureBuffer.contiguous()).data_ptr());
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int rc = grpg_backward_composed_features(
+      pk.segs.data(), gs.data(), (int)n, p_sem.data(), S, normals ? 1 : 0, degree, pk.M, R, cam.bg, W, H,
+      scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img,
+      p_blob, sv.dcolor, sv.ddepth, sv.dalpha, sv.dsemantic, F > 0 ? dL_dfeatures.data_ptr<float>() : nullptr,
+      dL_dmeans2D.data_ptr<float>(), dL_dposes.data_ptr<float>(), debug ? 1 : 0, (void*)stream);
+  if (rc != GRPG_OK) raise_abi_error("grpg_backward_composed_features", rc);
+  return std::make_tuple(g_xyz, g_scaling, g_rotation, g_opacity, g_fdc, g_frest, g_sem, dL_dmeans2D, dL_dposes);
+}
+
 // (means3D [P,3], scales [P,3], rotations [P,4], opacity [P,1], shs [P,M,3]): what the reference's
 // get_xyz / get_scaling / get_rotation / get_opacity / get_features return for the same models
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
@@ -1440,6 +1634,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rasterize_gaussians_frame", &RasterizeGaussiansFrame);
   m.def("rasterize_gaussians_composed_frame", &RasterizeGaussiansComposedFrame);
   m.def("compose", &Compose);
+  m.def("compose_features", &ComposeFeatures);
+  m.def("compose_features_backward", &ComposeFeaturesBackward);
+  m.def("rasterize_gaussians_composed_features", &RasterizeGaussiansComposedFeatures);
+  m.def("rasterize_gaussians_composed_features_backward", &RasterizeGaussiansComposedFeaturesBackward);
   m.def("sky_composite", &SkyComposite, pybind11::arg("cube"), pybind11::arg("ray_matrix"),
         pybind11::arg("fill"), pybind11::arg("clamp_out"), pybind11::arg("rgb"), pybind11::arg("acc"),
         pybind11::arg("height"), pybind11::arg("width"), pybind11::arg("want_sky"),

@@ -290,8 +290,9 @@ GRPG_API int grpg_frame_status(int ticket, int wait, int* num_rendered);
  * arrays and the per-frame actor poses instead and does that arithmetic inside preprocess; the
  * concatenated tensors never exist.  S = 0.  Training: grpg_forward_composed_flags(flags = 0) +
  * grpg_backward_composed return the gradients with respect to the RAW parameters and the poses
- * (round 3; the semantic concatenation of street_gaussian_model.py:420-435 and pose-correction
- * modules stay in the caller's PyTorch; the flip augmentation :286-293 is the segment's `flip` mask).
+ * (round 3; pose-correction modules stay in the caller's PyTorch; the flip augmentation :286-293 is
+ * the segment's `flip` mask; the semantic concatenation of street_gaussian_model.py:420-435 and the
+ * normals: grpg_forward_composed_features below).
  *
  * A segment describes one model, in the order the reference concatenates them (background first,
  * then the visible actors, street_gaussian_model.py:232-262).  All pointers are device pointers to
@@ -409,6 +410,77 @@ GRPG_API int grpg_backward_composed(const grpg_model_segment* segments,
 GRPG_API int grpg_compose(const grpg_model_segment* segments, int num_segments, int M,
                  float* means3D, float* scales, float* rotations, float* opacities, float* shs,
                  void* hip_stream);
+
+/*
+ * Feature planes of a composed frame (additive; ABI 7 unchanged, grpg_model_segment and every entry point above as
+ * they were).  A composed frame carries F = 3 * normals + S feature channels through the blend, forward and backward:
+ * the normals first, then the semantic channels -- the order in which the reference's renderer concatenates them
+ * (lib/models/street_gaussian_renderer.py:205-215).  The flat [P,F] array the blend reads by Gaussian id is produced
+ * on the device from per-model arrays (csrc/features.hip); the per-segment pointers travel as HOST arrays of
+ * num_segments device pointers, parallel to `segments`:
+ *   seg_semantic[i]      [count_i,S] fp32, copied bit for bit; NULL (or a NULL array) = zeros --
+ *                        StreetGaussianModel.get_semantic, street_gaussian_model.py:420-435
+ *   normals != 0         GaussianModel.get_normals (lib/models/gaussian_model.py:256-269) on the values the composed
+ *                        preprocess forms: the column of quaternion_to_matrix(world rotation) that belongs to the
+ *                        smallest activated scale (ties: the lowest index), negated unless it faces cam_pos (device
+ *                        float[3]; a Gaussian at the camera centre is negated, as torch.where does with a NaN).  For
+ *                        an actor: R_obj n_local at unit length, the sign taken in the world frame (what
+ *                        street_gaussian_model.py:463-484 intends).
+ * The planes are raw: F.normalize(dim=0) of the normals and the `probabilities` transform of the semantics stay
+ * with the caller (grpg_semantic_ce_forward takes raw planes).
+ */
+
+/* The producer alone: features [P,F] device fp32, every element written.  Synchronises with the stream (the tables
+ * travel through a temporary device buffer, like grpg_compose's). */
+GRPG_API int grpg_compose_features(const grpg_model_segment* segments, int num_segments,
+                 const float* const* seg_semantic, int S, int normals, const float* cam_pos,
+                 float* features, void* hip_stream);
+
+/* Its backward alone, given dL_dfeatures [P,F].  seg_dL_dsemantic[i] [count_i,S] is WRITTEN.  The normal channels'
+ * gradient -- chained through R[:,k], the normalisations, the quaternion product and the flip; none through k, the
+ * sign, the means or the scales, like the reference -- is ADDED to seg_dL_drotation[i] [count_i,4] (the gradient of
+ * the RAW _rotation) and to dL_dposes[i][0:4] (device [num_segments][8], as in grpg_backward_composed): hand in
+ * zeros, or what grpg_backward_composed wrote.  A NULL array or entry: not wanted.  No atomics: the rotation gradient
+ * one thread per row, the pose gradient per-workgroup partial sums added in a fixed order, so given dL_dfeatures
+ * identical calls give identical bits (dL_dfeatures itself, when it comes from the blend backward's float atomics,
+ * is not bit-reproducible). */
+GRPG_API int grpg_compose_features_backward(const grpg_model_segment* segments, int num_segments, int S,
+                 int normals, const float* cam_pos, const float* dL_dfeatures,
+                 float* const* seg_dL_dsemantic, float* const* seg_dL_drotation, float* dL_dposes,
+                 void* hip_stream);
+
+/* grpg_forward_composed_flags with feature planes: out_features [F,H,W] is rendered like grpg_forward's
+ * out_semantic from the [P,F] array, which lives at the head of a fourth blob (feature_alloc; it also holds the
+ * segments' feature table and the backward's partial sums: keep it for grpg_backward_composed_features).  Any F;
+ * F == 0 is grpg_forward_composed_flags.  Layered frames, deferred frames and the frame epilogue stay S = 0. */
+GRPG_API int grpg_forward_composed_features(grpg_alloc_fn geometry_alloc, void* geometry_user,
+                 grpg_alloc_fn binning_alloc, void* binning_user,
+                 grpg_alloc_fn image_alloc, void* image_user,
+                 grpg_alloc_fn feature_alloc, void* feature_user,
+                 const grpg_model_segment* segments, int num_segments,
+                 const float* const* seg_semantic, int S, int normals, int D, int M,
+                 const float* background, int width, int height, float scale_modifier,
+                 const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                 float tan_fovx, float tan_fovy,
+                 float* out_color, float* out_depth, float* out_alpha, float* out_features, int* radii,
+                 int debug, void* hip_stream, unsigned flags);
+
+/* grpg_backward_composed with feature planes: the blend backward with F channels (dL_dpix_features [F,H,W];
+ * dL_dfeatures [P,F] is scratch that must arrive ZERO-FILLED -- the dL_dsemantic contract of grpg_backward -- and
+ * holds the gradient of the flat feature array afterwards), the composed preprocess backward, then the feature
+ * backward on the same stream: seg_dL_dsemantic[i] is written, the normals' share is added to grads[i].rotation and
+ * dL_dposes.  feature_buffer: the forward's fourth blob.  F > GRPG_MAX_SEMANTIC_BACKWARD is refused like
+ * grpg_backward refuses S. */
+GRPG_API int grpg_backward_composed_features(const grpg_model_segment* segments,
+                 const grpg_model_segment_grad* grads, int num_segments,
+                 float* const* seg_dL_dsemantic, int S, int normals, int D, int M, int R,
+                 const float* background, int width, int height, float scale_modifier,
+                 const float* viewmatrix, const float* projmatrix, const float* campos,
+                 float tan_fovx, float tan_fovy, const int* radii, const float* alphas,
+                 char* geom_buffer, char* binning_buffer, char* image_buffer, char* feature_buffer,
+                 const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dalphas,
+                 const float* dL_dpix_features, float* dL_dfeatures,
+                 float* dL_dmean2D, float* dL_dposes, int debug, void* hip_stream);
 
 /*
  * Sky cube map without nvdiffrast (additive).  Replaces
