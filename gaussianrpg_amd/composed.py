@@ -197,6 +197,11 @@ def _pose_graph(poses, pose_tensors):
 _NO_SEMANTIC = torch.empty(0)
 
 
+def _split(flat, nm):
+    """The head of a Function's flat tensor arguments -> the six per-field lists of nm tensors (_model_lists' order)."""
+    return [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
+
+
 def _semantic_list(models, semantics):
     """One [N_i,S] float32 device tensor per model (None -> an empty tensor: zeros); S.  No fallback: a CPU
     tensor, another dtype or disagreeing S is an error."""
@@ -238,7 +243,7 @@ class _ComposeFeatures(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, nm, pose_t, idft_t, flips, normals, campos, pose_rot, S, *flat):
-        lists = [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
+        lists = _split(flat, nm)
         sems = list(flat[6 * nm:])
         ctx.nm, ctx.pose_t, ctx.idft_t, ctx.flips, ctx.normals, ctx.campos, ctx.S = nm, pose_t, idft_t, flips, normals, campos, S
         ctx.pose_dev = None if pose_rot is None else pose_rot.device
@@ -248,8 +253,7 @@ class _ComposeFeatures(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_features):
         nm = ctx.nm
-        flat = ctx.saved_tensors
-        lists = [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
+        lists = _split(ctx.saved_tensors, nm)
         need = ctx.needs_input_grad
         want_sem = [bool(n) for n in need[8 + 6 * nm:]] or [False] * nm
         g_rot, g_sem, g_poses = _C.compose_features_backward(
@@ -300,20 +304,31 @@ def gaussian_normals(scaling, rotation, xyz, campos):
     return compose_features([m], [None], None, True, campos)
 
 
-class _ComposedRasterizeFeatures(torch.autograd.Function):
-    """Training path of forward_features: forward = _C.rasterize_gaussians_composed_features(for_backward=True),
-    backward = _C.rasterize_gaussians_composed_features_backward (C ABI grpg_backward_composed_features)."""
+def _rasterize(rs, lists, pose_t, idft_t, sems, normals, S, for_backward):
+    """One composed forward: _C.rasterize_gaussians_composed for a frame without feature planes (F = 3 * normals + S
+    = 0), _C.rasterize_gaussians_composed_features otherwise -> the latter's tuple (num_rendered, color, depth, alpha,
+    features [F,H,W], radii, geom, binning, img, feature blob)."""
+    camera = (rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
+              rs.image_width, rs.sh_degree, rs.campos, rs.debug, for_backward)
+    if not normals and S == 0:
+        num_rendered, color, depth, alpha, radii, geom, binning, img = _C.rasterize_gaussians_composed(
+            rs.bg, *lists, pose_t, idft_t, *camera)
+        features = alpha.new_empty(0, rs.image_height, rs.image_width)
+        return num_rendered, color, depth, alpha, features, radii, geom, binning, img, _NO_SEMANTIC
+    return _C.rasterize_gaussians_composed_features(rs.bg, *lists, pose_t, idft_t, sems, normals, *camera)
+
+
+class _ComposedRasterize(torch.autograd.Function):
+    """Training path of forward (F = 0) and forward_features: forward = _rasterize(for_backward=True), backward =
+    _C.rasterize_gaussians_composed_backward (C ABI grpg_backward_composed at F = 0, grpg_backward_composed_features
+    otherwise)."""
 
     @staticmethod
     def forward(ctx, owner, rs, nm, pose_t, idft_t, flips, normals, S, pose_rot, pose_trans, means2D, *flat):
-        lists = [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
-        sems = list(flat[6 * nm:])
-        num_rendered, color, depth, alpha, features, radii, geom, binning, img, blob = \
-            _C.rasterize_gaussians_composed_features(
-                rs.bg, *lists, flips, pose_t, idft_t, sems, normals, rs.scale_modifier, rs.viewmatrix, rs.projmatrix,
-                rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.sh_degree, rs.campos, rs.debug, True)
+        num_rendered, color, depth, alpha, features, radii, geom, binning, img, blob = _rasterize(
+            rs, _split(flat, nm) + [flips], pose_t, idft_t, list(flat[6 * nm:]), normals, S, True)
         ctx.rs, ctx.nm, ctx.num_rendered, ctx.normals, ctx.S = rs, nm, num_rendered, normals, S
-        owner.num_rendered = num_rendered
+        owner.num_rendered = num_rendered   # like the evaluation branch of ComposedRasterizer._render
         ctx.pose_t, ctx.idft_t, ctx.flips = pose_t, idft_t, flips
         ctx.pose_dev = (None if pose_rot is None else pose_rot.device,
                         None if pose_trans is None else pose_trans.device)
@@ -325,67 +340,27 @@ class _ComposedRasterizeFeatures(torch.autograd.Function):
     def backward(ctx, g_color, g_radii, g_depth, g_alpha, g_features):
         rs, nm = ctx.rs, ctx.nm
         radii, alpha, geom, binning, img, blob = ctx.saved_tensors[:6]
-        flat = ctx.saved_tensors[6:]
-        lists = [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
-        zeros = lambda t: torch.zeros_like(t)   # noqa: E731  (an output the loss does not touch)
+        # forward's arguments: 8 without a gradient, pose_rot, pose_trans, means2D, 6 * nm parameters, the semantics
         need = ctx.needs_input_grad
+        need_params, need_sem = need[11:11 + 6 * nm], need[11 + 6 * nm:]
         F = 3 * int(ctx.normals) + ctx.S
-        H, W = alpha.shape[-2], alpha.shape[-1]
-        want_sem = [bool(n) for n in need[11 + 6 * nm:]] or [False] * nm
-        gx, gs, gr, go, gdc, gfr, gsem, g_means2D, g_poses = _C.rasterize_gaussians_composed_features_backward(
-            rs.bg, *lists, ctx.flips, ctx.pose_t, ctx.idft_t, ctx.S, want_sem, ctx.normals, rs.scale_modifier,
-            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.sh_degree, rs.campos, radii, alpha, geom,
-            ctx.num_rendered, binning, img, blob,
-            g_color if g_color is not None else zeros(alpha).expand(3, -1, -1).contiguous(),
-            g_depth if g_depth is not None else zeros(alpha),
-            g_alpha if g_alpha is not None else zeros(alpha),
-            g_features if g_features is not None else alpha.new_zeros(F, H, W), rs.debug)
+        zeros = lambda *shape: alpha.new_zeros(*shape, *alpha.shape[-2:])   # noqa: E731  (an output the loss does not touch)
+        if F == 0:
+            g_features = _NO_SEMANTIC
+        *g_params, g_sem, g_means2D, g_poses = _C.rasterize_gaussians_composed_backward(
+            rs.bg, *_split(ctx.saved_tensors[6:], nm), ctx.flips, ctx.pose_t, ctx.idft_t, ctx.S,
+            [bool(n) for n in need_sem] or [False] * nm, ctx.normals, rs.scale_modifier, rs.viewmatrix, rs.projmatrix,
+            rs.tanfovx, rs.tanfovy, rs.sh_degree, rs.campos, radii, alpha, geom, ctx.num_rendered, binning, img, blob,
+            g_color if g_color is not None else zeros(3),
+            g_depth if g_depth is not None else zeros(1),
+            g_alpha if g_alpha is not None else zeros(1),
+            g_features if g_features is not None else zeros(F), rs.debug)
         g_rot = g_poses[:, 0:4].to(ctx.pose_dev[0]) if need[8] else None
         g_trans = g_poses[:, 4:7].to(ctx.pose_dev[1]) if need[9] else None
-        grads = [g for per_field in (gx, gs, gr, go, gdc, gfr) for g in per_field]
-        flat_grads = tuple(g if n else None for g, n in zip(grads, need[11:11 + 6 * nm]))
-        sem_grads = tuple(g if (n and g.numel()) else None for g, n in zip(gsem, need[11 + 6 * nm:]))
+        grads = [g for per_field in g_params for g in per_field]
+        flat_grads = tuple(g if n else None for g, n in zip(grads, need_params))
+        sem_grads = tuple(g if (n and g.numel()) else None for g, n in zip(g_sem, need_sem))
         return (None,) * 8 + (g_rot, g_trans, g_means2D if need[10] else None) + flat_grads + sem_grads
-
-
-class _ComposedRasterize(torch.autograd.Function):
-    """Training path: forward = _C.rasterize_gaussians_composed(for_backward=True), backward =
-    _C.rasterize_gaussians_composed_backward (C ABI grpg_backward_composed)."""
-
-    @staticmethod
-    def forward(ctx, owner, rs, nm, pose_t, idft_t, flips, pose_rot, pose_trans, means2D, *flat):
-        lists = [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
-        num_rendered, color, depth, alpha, radii, geom, binning, img = _C.rasterize_gaussians_composed(
-            rs.bg, *lists, flips, pose_t, idft_t, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
-            rs.tanfovy, rs.image_height, rs.image_width, rs.sh_degree, rs.campos, rs.debug, True)
-        ctx.rs, ctx.nm, ctx.num_rendered = rs, nm, num_rendered
-        owner.num_rendered = num_rendered   # like the evaluation branch of ComposedRasterizer.forward
-        ctx.pose_t, ctx.idft_t, ctx.flips = pose_t, idft_t, flips
-        ctx.pose_dev = (None if pose_rot is None else pose_rot.device,
-                        None if pose_trans is None else pose_trans.device)
-        ctx.save_for_backward(radii, alpha, geom, binning, img, *flat)
-        ctx.mark_non_differentiable(radii)
-        return color, radii, depth, alpha
-
-    @staticmethod
-    def backward(ctx, g_color, g_radii, g_depth, g_alpha):
-        rs, nm = ctx.rs, ctx.nm
-        radii, alpha, geom, binning, img = ctx.saved_tensors[:5]
-        flat = ctx.saved_tensors[5:]
-        lists = [list(flat[f * nm:(f + 1) * nm]) for f in range(6)]
-        zeros = lambda t: torch.zeros_like(t)   # noqa: E731  (an output the loss does not touch)
-        gx, gs, gr, go, gdc, gfr, g_means2D, g_poses = _C.rasterize_gaussians_composed_backward(
-            rs.bg, *lists, ctx.flips, ctx.pose_t, ctx.idft_t, rs.scale_modifier, rs.viewmatrix, rs.projmatrix,
-            rs.tanfovx, rs.tanfovy, rs.sh_degree, rs.campos, radii, alpha, geom, ctx.num_rendered,
-            binning, img, g_color if g_color is not None else zeros(alpha).expand(3, -1, -1).contiguous(),
-            g_depth if g_depth is not None else zeros(alpha),
-            g_alpha if g_alpha is not None else zeros(alpha), rs.debug)
-        need = ctx.needs_input_grad
-        g_rot = g_poses[:, 0:4].to(ctx.pose_dev[0]) if need[6] else None
-        g_trans = g_poses[:, 4:7].to(ctx.pose_dev[1]) if need[7] else None
-        grads = [g for per_field in (gx, gs, gr, go, gdc, gfr) for g in per_field]
-        flat_grads = tuple(g if n else None for g, n in zip(grads, need[9:]))
-        return (None, None, None, None, None, None, g_rot, g_trans, g_means2D if need[8] else None) + flat_grads
 
 
 class ComposedRasterizer(nn.Module):
@@ -445,34 +420,27 @@ class ComposedRasterizer(nn.Module):
         self.num_rendered = ret[0]
         return _frame_result(ret, rgb8, planes, layers)
 
-    def forward(self, models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]], means2D=None):
+    def _render(self, models, poses, semantics, normals, means2D):
+        """forward (no feature planes) and forward_features -> (color, radii, depth, alpha, features [F,H,W])"""
         rs = self.raster_settings
+        sems, S = _semantic_list(models, semantics)
         lists, pose_t, idft_t = _pack(models, poses)
-        flips = lists[6]
         flat = [t for per_field in lists[:6] for t in per_field]
-        pose_tensors = [t for p in poses if p is not None for t in (p.obj_rot, p.obj_trans)
-                        if isinstance(t, torch.Tensor)]
+        pose_tensors = _pose_tensors(poses)
         train = torch.is_grad_enabled() and any(
-            t.requires_grad for t in flat + pose_tensors + ([means2D] if means2D is not None else []))
+            t.requires_grad for t in flat + pose_tensors + list(sems) + ([means2D] if means2D is not None else []))
         if not train:
             with torch.no_grad():
-                num_rendered, color, depth, alpha, radii, geom, binning, img = _C.rasterize_gaussians_composed(
-                    rs.bg, *lists, pose_t, idft_t, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
-                    rs.tanfovy, rs.image_height, rs.image_width, rs.sh_degree, rs.campos, rs.debug)
+                num_rendered, color, depth, alpha, features, radii = _rasterize(
+                    rs, lists, pose_t, idft_t, sems, normals, S, False)[:6]
             self.num_rendered = num_rendered
-            return color, radii, depth, alpha
-        # poses as [n,4] / [n,3] tensors that keep their graph (rows of static models: constants)
-        pose_rot = pose_trans = None
-        if pose_tensors:
-            one = torch.tensor([1.0, 0.0, 0.0, 0.0])
-            zero3 = torch.zeros(3)
-            dev = pose_tensors[0].device
-            as_t = lambda v, d: v.to(dev).float() if isinstance(v, torch.Tensor) else \
-                torch.tensor([float(x) for x in v], device=dev)   # noqa: E731
-            pose_rot = torch.stack([one.to(dev) if p is None else as_t(p.obj_rot, dev) for p in poses])
-            pose_trans = torch.stack([zero3.to(dev) if p is None else as_t(p.obj_trans, dev) for p in poses])
-        return _ComposedRasterize.apply(self, rs, len(models), pose_t, idft_t, flips, pose_rot, pose_trans,
-                                        means2D, *flat)
+            return color, radii, depth, alpha, features
+        pose_rot, pose_trans = _pose_graph(poses, pose_tensors)
+        return _ComposedRasterize.apply(self, rs, len(models), pose_t, idft_t, lists[6], normals, S, pose_rot,
+                                        pose_trans, means2D, *flat, *sems)
+
+    def forward(self, models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]], means2D=None):
+        return self._render(models, poses, None, False, means2D)[:4]
 
     def forward_features(self, models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]], semantics=None,
                          normals: bool = False, means2D=None):
@@ -483,24 +451,5 @@ class ComposedRasterizer(nn.Module):
         the ``probabilities`` transform of the semantics stay with the caller (``semantic_loss(mode=...)`` takes raw
         planes).  Differentiable like ``forward``, and with respect to the semantic arrays; the normals' gradient
         reaches the raw rotations and tensor-valued ``obj_rot``.  A backward needs F <= 32; the forward takes any F."""
-        rs = self.raster_settings
         _check_models(models)
-        sems, S = _semantic_list(models, semantics)
-        normals = bool(normals)
-        lists, pose_t, idft_t = _pack(models, poses)
-        flips = lists[6]
-        flat = [t for per_field in lists[:6] for t in per_field]
-        pose_tensors = _pose_tensors(poses)
-        train = torch.is_grad_enabled() and any(
-            t.requires_grad for t in flat + pose_tensors + list(sems) + ([means2D] if means2D is not None else []))
-        if not train:
-            with torch.no_grad():
-                num_rendered, color, depth, alpha, features, radii = _C.rasterize_gaussians_composed_features(
-                    rs.bg, *lists, pose_t, idft_t, sems, normals, rs.scale_modifier, rs.viewmatrix, rs.projmatrix,
-                    rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.sh_degree, rs.campos, rs.debug,
-                    False)[:6]
-            self.num_rendered = num_rendered
-            return color, radii, depth, alpha, features
-        pose_rot, pose_trans = _pose_graph(poses, pose_tensors)
-        return _ComposedRasterizeFeatures.apply(self, rs, len(models), pose_t, idft_t, flips, normals, S, pose_rot,
-                                                pose_trans, means2D, *flat, *sems)
+        return self._render(models, poses, semantics, bool(normals), means2D)

@@ -395,6 +395,14 @@ int geom_check_backward(const void* ptr, int P, hipStream_t stream) {
   remember_geom(ptr, P, true);
   return GRPG_OK;
 }
+// what every backward settles about its state before it looks at its other arguments: the geometry blob, then the
+// asynchronous failures of the thread's earlier frames
+int check_backward_state(const void* geom_buffer, int P, hipStream_t stream) {
+  if (int rc = geom_check_backward(geom_buffer, P, stream)) return rc;
+  for (auto& hw : g_host_words)
+    if (int rc = check_async_error(&hw)) return rc;
+  return GRPG_OK;
+}
 
 CameraArgs make_camera(const float* view, const float* proj, const float* campos, int W, int H,
                        float tan_fovx, float tan_fovy) {
@@ -408,6 +416,48 @@ CameraArgs make_camera(const float* view, const float* proj, const float* campos
   c.focal_x = W / (2.0f * tan_fovx);
   return c;
 }
+
+// The first half of every backward (grpg_backward, grpg_backward_composed*): the camera and the blob layouts of the
+// frame, then -- run() -- the blend backward into the cleared gradient records.  The caller owns it: the preprocess
+// backward takes cam / GL / rec / grad_rec from it, marks btr once more (2) and sets btg.done.
+struct BlendBackward {
+  const int P;
+  const CameraArgs cam;
+  const GeomLayout GL;
+  const ImgLayout IL;
+  char *const geom_buffer, *const binning_buffer, *const image_buffer;
+  const RecView rec;
+  float* const grad_rec;   // per-Gaussian gradient records (one 64-byte line each) in the tail of the geometry blob
+  BwdTimingRecord* btr = nullptr;
+  BwdTimingGuard btg{nullptr};
+
+  BlendBackward(int P_, int width, int height, const float* viewmatrix, const float* projmatrix, const float* campos,
+                float tan_fovx, float tan_fovy, char* geom_buffer_, char* binning_buffer_, char* image_buffer_)
+      : P(P_), cam(make_camera(viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy)),
+        GL(geom_layout((size_t)P_)), IL(img_layout((size_t)cam.gx * (size_t)cam.gy, (size_t)width * height)),
+        geom_buffer(geom_buffer_), binning_buffer(binning_buffer_), image_buffer(image_buffer_),
+        rec{(const float4*)(geom_buffer_ + GL.rec)}, grad_rec((float*)(geom_buffer_ + GL.grad_rec)) {}
+
+  // features [P,F] / dL_dpix_features [F,H,W] / dL_dfeatures [P,F] (accumulated into): NULL at F == 0
+  int run(hipStream_t stream, int debug, int R, const float* background, const float* alphas, const float* features,
+          int F, const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dalphas,
+          const float* dL_dpix_features, float* dL_dfeatures) {
+    // the point list is the first array of the binning blob whatever capacity it was carved for
+    const uint32_t* point_list = (const uint32_t*)(binning_buffer + bin_layout(0).val_a);
+    const uint2* ranges = (const uint2*)(image_buffer + IL.ranges);
+    const uint32_t* n_contrib = (const uint32_t*)(image_buffer + IL.n_contrib);
+    HIP_TRY(hipMemsetAsync(grad_rec, 0, (size_t)P * GRAD_STRIDE * sizeof(float), stream));
+    btg.r = btr = bwd_timing_begin(stream);
+    launch_render_backward(stream, ranges, point_list, rec, features, F, cam.W, cam.H, cam.gx, cam.gy, background,
+                           alphas, n_contrib, (const uint32_t*)(image_buffer + IL.work), dL_dpix, dL_dpix_depth,
+                           dL_dalphas, dL_dpix_features, grad_rec, dL_dfeatures, (const BlobHeader*)binning_buffer,
+                           (const uint32_t*)(image_buffer + IL.ck_count),
+                           (const uint32_t*)(image_buffer + IL.bwd_ctl), (uint32_t)R);
+    STAGE_CHECK("render backward");
+    bwd_timing_mark(btr, 1, stream);
+    return GRPG_OK;
+  }
+};
 
 }  // namespace
 
@@ -535,18 +585,6 @@ BwdStagingSlot* bwd_staging_acquire() {
   return &b;
 }
 
-// one row of the device segment table; pad1: the model's class bit in a layered composed forward, else NULL
-void fill_segment(SegmentDev& d, const grpg_model_segment& g, uint32_t start, const void* pad1) {
-  d.xyz = g.xyz; d.scaling = g.scaling; d.rotation = g.rotation; d.opacity = g.opacity;
-  d.fdc = g.features_dc; d.frest = g.features_rest; d.flip = g.flip; d.pad1 = pad1;
-  d.start = start; d.count = (uint32_t)g.count;
-  d.fourier_dim = g.fourier_dim; d.rigid = g.rigid;
-  for (int k = 0; k < 4; k++) d.rot[k] = g.obj_rot[k];
-  for (int k = 0; k < 3; k++) d.trans[k] = g.obj_trans[k];
-  d.pad0 = 0.f;
-  for (int k = 0; k < MAX_FOURIER; k++) d.idft[k] = g.idft[k];
-}
-
 // grpg_forward_layers: the class of every Gaussian and the two extra plane pairs
 struct LayerArgs {
   const unsigned char* segment_class;   // composed frames: [num_segments] HOST bytes (NULL: the segment's rigid flag)
@@ -554,6 +592,26 @@ struct LayerArgs {
   const float* layer_background;
   float* out_color_bg; float* out_alpha_bg; float* out_color_obj; float* out_alpha_obj;
 };
+
+// The device segment table of a composed model: one row per segment, `start` running over the counts.  layers: the
+// layered frame whose class bit (pad1: 1 = object layer) the rows carry, NULL: none.
+void fill_segments(SegmentDev* dst, const grpg_model_segment* segs, int nseg, const LayerArgs* layers) {
+  uint32_t start = 0;
+  for (int i = 0; i < nseg; i++) {
+    const grpg_model_segment& g = segs[i];
+    SegmentDev& d = dst[i];
+    const bool obj = layers && (layers->segment_class ? layers->segment_class[i] != 0 : g.rigid != 0);
+    d.xyz = g.xyz; d.scaling = g.scaling; d.rotation = g.rotation; d.opacity = g.opacity;
+    d.fdc = g.features_dc; d.frest = g.features_rest; d.flip = g.flip; d.pad1 = (const void*)(uintptr_t)(obj ? 1u : 0u);
+    d.start = start; d.count = (uint32_t)g.count;
+    d.fourier_dim = g.fourier_dim; d.rigid = g.rigid;
+    for (int k = 0; k < 4; k++) d.rot[k] = g.obj_rot[k];
+    for (int k = 0; k < 3; k++) d.trans[k] = g.obj_trans[k];
+    d.pad0 = 0.f;
+    for (int k = 0; k < MAX_FOURIER; k++) d.idft[k] = g.idft[k];
+    start += (uint32_t)g.count;
+  }
+}
 
 // One forward frame as an entry point hands it to forward_impl.  Every extern "C" forward fills the fields it has;
 // the rest stay zero / NULL.  segs == NULL: flat input tensors (grpg_forward); segs: per-model raw parameters
@@ -584,6 +642,34 @@ struct FrameRequest {
   // an evaluation frame (GRPG_FORWARD_NO_BACKWARD: no backward can follow) is not a training frame
   bool training() const { return (flags & GRPG_FORWARD_NO_BACKWARD) == 0u; }
 };
+
+// The three groups of fields every entry point fills alike; what is an entry's own (S and the semantic arrays, layers,
+// epilogue, deferred slot, feature split) it states itself.
+void set_allocators(FrameRequest& q, grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_alloc_fn binning_alloc,
+                    void* binning_user, grpg_alloc_fn image_alloc, void* image_user) {
+  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
+  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
+}
+void set_camera(FrameRequest& q, const float* background, int width, int height, float scale_modifier,
+                const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                float tan_fovy, float* out_color, float* out_depth, float* out_alpha, int* radii, int debug,
+                void* hip_stream, unsigned flags) {
+  q.background = background; q.width = width; q.height = height; q.scale_modifier = scale_modifier;
+  q.viewmatrix = viewmatrix; q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx;
+  q.tan_fovy = tan_fovy; q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha;
+  q.radii = radii; q.debug = debug; q.stream = (hipStream_t)hip_stream; q.flags = flags;
+}
+// the model: flat tensors ...
+void set_model(FrameRequest& q, int P, int D, int M, const float* means3D, const float* shs,
+               const float* colors_precomp, const float* opacities, const float* scales, const float* rotations,
+               const float* cov3D_precomp) {
+  q.P = P; q.D = D; q.M = M; q.means3D = means3D; q.shs = shs; q.colors_precomp = colors_precomp;
+  q.opacities = opacities; q.scales = scales; q.rotations = rotations; q.cov3D_precomp = cov3D_precomp;
+}
+// ... or the checked segments of a composition (P: check_composed_model's)
+void set_model(FrameRequest& q, const grpg_model_segment* segments, int num_segments, long long P, int D, int M) {
+  q.segs = segments; q.nseg = num_segments; q.P = (int)P; q.D = D; q.M = M;
+}
 
 // the argument checks of every forward, behind ensure_device
 int validate(const FrameRequest& q) {
@@ -793,13 +879,7 @@ struct Frame {
   int stage_segments(SegmentDev* seg_dev) {
     if (!g_seg_staging)
       HIP_TRY(hipHostMalloc((void**)&g_seg_staging, sizeof(SegmentDev) * MAX_SEGMENTS, hipHostMallocDefault));
-    uint32_t start = 0;
-    for (int i = 0; i < q.nseg; i++) {
-      const grpg_model_segment& g = q.segs[i];
-      const bool obj = layers && (layers->segment_class ? layers->segment_class[i] != 0 : g.rigid != 0);
-      fill_segment(g_seg_staging[i], g, start, (const void*)(uintptr_t)(obj ? 1u : 0u));
-      start += (uint32_t)g.count;
-    }
+    fill_segments(g_seg_staging, q.segs, q.nseg, layers);
     HIP_TRY(hipMemcpyAsync(seg_dev, g_seg_staging, sizeof(SegmentDev) * (size_t)q.nseg,
                            hipMemcpyHostToDevice, stream));
     return GRPG_OK;
@@ -1248,15 +1328,11 @@ int grpg_forward_flags(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_a
                        void* hip_stream, unsigned flags) {
   (void)prefiltered;
   FrameRequest q;
-  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
-  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
-  q.P = P; q.D = D; q.M = M; q.S = S; q.background = background; q.width = width; q.height = height;
-  q.means3D = means3D; q.shs = shs; q.colors_precomp = colors_precomp; q.semantics = semantics;
-  q.opacities = opacities; q.scales = scales; q.scale_modifier = scale_modifier; q.rotations = rotations;
-  q.cov3D_precomp = cov3D_precomp; q.viewmatrix = viewmatrix; q.projmatrix = projmatrix; q.cam_pos = cam_pos;
-  q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy; q.out_color = out_color; q.out_depth = out_depth;
-  q.out_alpha = out_alpha; q.out_semantic = out_semantic; q.radii = radii; q.debug = debug;
-  q.stream = (hipStream_t)hip_stream; q.flags = flags;
+  set_allocators(q, geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user);
+  set_model(q, P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp);
+  set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+             out_color, out_depth, out_alpha, radii, debug, hip_stream, flags);
+  q.S = S; q.semantics = semantics; q.out_semantic = out_semantic;
   return forward_impl(q);
 }
 
@@ -1274,14 +1350,10 @@ int grpg_forward_layers(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_
   const LayerArgs la = {nullptr, layer_class, layer_background, out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj};
   FrameRequest q;
   if (int rc = check_layers(la, P, true, false, &q.layers)) return rc;
-  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
-  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
-  q.P = P; q.D = D; q.M = M; q.background = background; q.width = width; q.height = height;
-  q.means3D = means3D; q.shs = shs; q.colors_precomp = colors_precomp; q.opacities = opacities;
-  q.scales = scales; q.scale_modifier = scale_modifier; q.rotations = rotations; q.cov3D_precomp = cov3D_precomp;
-  q.viewmatrix = viewmatrix; q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx;
-  q.tan_fovy = tan_fovy; q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha;
-  q.radii = radii; q.debug = debug; q.stream = (hipStream_t)hip_stream; q.flags = GRPG_FORWARD_NO_BACKWARD;
+  set_allocators(q, geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user);
+  set_model(q, P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp);
+  set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+             out_color, out_depth, out_alpha, radii, debug, hip_stream, GRPG_FORWARD_NO_BACKWARD);
   return forward_impl(q);
 }
 
@@ -1302,15 +1374,11 @@ int grpg_forward_deferred(grpg_alloc_fn geometry_alloc, void* geometry_user, grp
   DeferSlot* d = defer_acquire(ticket);
   if (!d) return fail(GRPG_ERR_HIP, "pinned status words / event allocation failed");
   FrameRequest q;
-  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
-  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
-  q.P = P; q.D = D; q.M = M; q.S = S; q.background = background; q.width = width; q.height = height;
-  q.means3D = means3D; q.shs = shs; q.colors_precomp = colors_precomp; q.semantics = semantics;
-  q.opacities = opacities; q.scales = scales; q.scale_modifier = scale_modifier; q.rotations = rotations;
-  q.cov3D_precomp = cov3D_precomp; q.viewmatrix = viewmatrix; q.projmatrix = projmatrix; q.cam_pos = cam_pos;
-  q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy; q.out_color = out_color; q.out_depth = out_depth;
-  q.out_alpha = out_alpha; q.out_semantic = out_semantic; q.radii = radii; q.debug = debug;
-  q.stream = (hipStream_t)hip_stream; q.flags = flags; q.defer = d;
+  set_allocators(q, geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user);
+  set_model(q, P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp);
+  set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+             out_color, out_depth, out_alpha, radii, debug, hip_stream, flags);
+  q.S = S; q.semantics = semantics; q.out_semantic = out_semantic; q.defer = d;
   const int rc = forward_impl(q);
   if (rc < 0) { d->state = 2; d->result = rc; return rc; }
   return GRPG_OK;
@@ -1346,13 +1414,10 @@ int grpg_forward_composed_flags(grpg_alloc_fn geometry_alloc, void* geometry_use
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
   FrameRequest q;
-  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
-  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
-  q.segs = segments; q.nseg = num_segments; q.P = (int)P; q.D = D; q.M = M; q.background = background;
-  q.width = width; q.height = height; q.scale_modifier = scale_modifier; q.viewmatrix = viewmatrix;
-  q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy;
-  q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha; q.radii = radii; q.debug = debug;
-  q.stream = (hipStream_t)hip_stream; q.flags = flags;
+  set_allocators(q, geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user);
+  set_model(q, segments, num_segments, P, D, M);
+  set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+             out_color, out_depth, out_alpha, radii, debug, hip_stream, flags);
   return forward_impl(q);
 }
 
@@ -1374,13 +1439,10 @@ int grpg_forward_composed_layers(grpg_alloc_fn geometry_alloc, void* geometry_us
   const LayerArgs la = {segment_class, nullptr, layer_background, out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj};
   FrameRequest q;
   if (int rc = check_layers(la, P, false, false, &q.layers)) return rc;
-  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
-  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
-  q.segs = segments; q.nseg = num_segments; q.P = (int)P; q.D = D; q.M = M; q.background = background;
-  q.width = width; q.height = height; q.scale_modifier = scale_modifier; q.viewmatrix = viewmatrix;
-  q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy;
-  q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha; q.radii = radii; q.debug = debug;
-  q.stream = (hipStream_t)hip_stream; q.flags = GRPG_FORWARD_NO_BACKWARD;
+  set_allocators(q, geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user);
+  set_model(q, segments, num_segments, P, D, M);
+  set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+             out_color, out_depth, out_alpha, radii, debug, hip_stream, GRPG_FORWARD_NO_BACKWARD);
   return forward_impl(q);
 }
 
@@ -1416,14 +1478,10 @@ int grpg_forward_frame(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_a
     if (int rc = resolve_epilogue(epilogue, out_color && out_depth && out_alpha, &fe)) return rc;
     q.epi = &fe;
   }
-  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
-  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
-  q.P = P; q.D = D; q.M = M; q.background = background; q.width = width; q.height = height;
-  q.means3D = means3D; q.shs = shs; q.colors_precomp = colors_precomp; q.opacities = opacities;
-  q.scales = scales; q.scale_modifier = scale_modifier; q.rotations = rotations; q.cov3D_precomp = cov3D_precomp;
-  q.viewmatrix = viewmatrix; q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx;
-  q.tan_fovy = tan_fovy; q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha;
-  q.radii = radii; q.debug = debug; q.stream = (hipStream_t)hip_stream; q.flags = GRPG_FORWARD_NO_BACKWARD;
+  set_allocators(q, geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user);
+  set_model(q, P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp);
+  set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+             out_color, out_depth, out_alpha, radii, debug, hip_stream, GRPG_FORWARD_NO_BACKWARD);
   return forward_impl(q);
 }
 
@@ -1449,13 +1507,10 @@ int grpg_forward_composed_frame(grpg_alloc_fn geometry_alloc, void* geometry_use
     if (int rc = resolve_epilogue(epilogue, out_color && out_depth && out_alpha, &fe)) return rc;
     q.epi = &fe;
   }
-  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
-  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
-  q.segs = segments; q.nseg = num_segments; q.P = (int)P; q.D = D; q.M = M; q.background = background;
-  q.width = width; q.height = height; q.scale_modifier = scale_modifier; q.viewmatrix = viewmatrix;
-  q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy;
-  q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha; q.radii = radii; q.debug = debug;
-  q.stream = (hipStream_t)hip_stream; q.flags = GRPG_FORWARD_NO_BACKWARD;
+  set_allocators(q, geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user);
+  set_model(q, segments, num_segments, P, D, M);
+  set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+             out_color, out_depth, out_alpha, radii, debug, hip_stream, GRPG_FORWARD_NO_BACKWARD);
   return forward_impl(q);
 }
 
@@ -1492,9 +1547,7 @@ static int backward_composed_impl(const grpg_model_segment* segments, const grpg
   const int P = (int)Pll;
   if (!grads || !geom_buffer || !binning_buffer || !image_buffer)
     return fail(GRPG_ERR_BAD_BUFFER, "NULL gradient table / state buffer");
-  if (int rc = geom_check_backward(geom_buffer, P, (hipStream_t)hip_stream)) return rc;
-  for (auto& hw : g_host_words)
-    if (int rc = check_async_error(&hw)) return rc;
+  if (int rc = check_backward_state(geom_buffer, P, (hipStream_t)hip_stream)) return rc;
   if (!dL_dpix || !dL_dpix_depth || !dL_dalphas || !alphas || !dL_dmean2D || !dL_dposes || !radii ||
       !background || !viewmatrix || !projmatrix || !campos)
     return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL pointer");
@@ -1504,47 +1557,29 @@ static int backward_composed_impl(const grpg_model_segment* segments, const grpg
       return fail(GRPG_ERR_INVALID_ARGUMENT, "segment gradient with a NULL array");
   }
   hipStream_t stream = (hipStream_t)hip_stream;
-  const CameraArgs cam = make_camera(viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy);
-  const uint32_t T = (uint32_t)cam.gx * (uint32_t)cam.gy;
-  const GeomLayout GL = geom_layout((size_t)P);
-  const ImgLayout IL = img_layout(T, (size_t)width * height);
-  const RecView rec = {(const float4*)(geom_buffer + GL.rec)};
-  const uint32_t* point_list = (const uint32_t*)(binning_buffer + bin_layout(0).val_a);
-  const uint2* ranges = (const uint2*)(image_buffer + IL.ranges);
-  const uint32_t* n_contrib = (const uint32_t*)(image_buffer + IL.n_contrib);
+  BlendBackward bb(P, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, geom_buffer, binning_buffer,
+                   image_buffer);
   // tables: the segments (as in the forward; re-uploaded: the caller may hand over other arrays of
   // the same values) and the six output pointers per segment, through pinned staging
   BwdStagingSlot* stg = bwd_staging_acquire();
   if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
-  uint32_t start = 0;
-  for (int i = 0; i < num_segments; i++) {
-    fill_segment(stg->segs[i], segments[i], start, nullptr);
-    start += (uint32_t)segments[i].count;
-    stg->grads[i] = grads[i];
-  }
-  SegmentDev* seg_dev = (SegmentDev*)(geom_buffer + GL.seg_table);
-  void* seg_grad_dev = (void*)(geom_buffer + GL.seg_grad_table);
+  fill_segments(stg->segs, segments, num_segments, nullptr);
+  for (int i = 0; i < num_segments; i++) stg->grads[i] = grads[i];
+  SegmentDev* seg_dev = (SegmentDev*)(geom_buffer + bb.GL.seg_table);
+  void* seg_grad_dev = (void*)(geom_buffer + bb.GL.seg_grad_table);
   HIP_TRY(hipMemcpyAsync(seg_dev, stg->segs, sizeof(SegmentDev) * (size_t)num_segments,
                          hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(seg_grad_dev, stg->grads, sizeof(grpg_model_segment_grad) * (size_t)num_segments,
                          hipMemcpyHostToDevice, stream));
   HIP_TRY(hipEventRecord(stg->ev, stream));
-  float* grad_rec = (float*)(geom_buffer + GL.grad_rec);
-  HIP_TRY(hipMemsetAsync(grad_rec, 0, (size_t)P * GRAD_STRIDE * sizeof(float), stream));
-  BwdTimingRecord* const btr = bwd_timing_begin(stream);
-  BwdTimingGuard btg(btr);
-  launch_render_backward(stream, ranges, point_list, rec, features, F, width, height, cam.gx, cam.gy,
-                         background, alphas, n_contrib, (const uint32_t*)(image_buffer + IL.work), dL_dpix,
-                         dL_dpix_depth, dL_dalphas, dL_dpix_features, grad_rec, dL_dfeatures,
-                         (const BlobHeader*)binning_buffer, (const uint32_t*)(image_buffer + IL.ck_count),
-                         (const uint32_t*)(image_buffer + IL.bwd_ctl), (uint32_t)R);
-  STAGE_CHECK("render backward");
-  bwd_timing_mark(btr, 1, stream);
-  launch_preprocess_backward_composed(stream, P, D, M, seg_dev, seg_grad_dev, num_segments, radii, rec,
-                                      scale_modifier, cam, grad_rec, dL_dmean2D,
-                                      (float*)(geom_buffer + GL.pose_acc), dL_dposes);
-  bwd_timing_mark(btr, 2, stream);
-  btg.done = true;
+  if (int rc = bb.run(stream, debug, R, background, alphas, features, F, dL_dpix, dL_dpix_depth, dL_dalphas,
+                      dL_dpix_features, dL_dfeatures))
+    return rc;
+  launch_preprocess_backward_composed(stream, P, D, M, seg_dev, seg_grad_dev, num_segments, radii, bb.rec,
+                                      scale_modifier, bb.cam, bb.grad_rec, dL_dmean2D,
+                                      (float*)(geom_buffer + bb.GL.pose_acc), dL_dposes);
+  bwd_timing_mark(bb.btr, 2, stream);
+  bb.btg.done = true;
   STAGE_CHECK("preprocess backward (composed)");
   return GRPG_OK;
 }
@@ -1594,13 +1629,10 @@ int grpg_forward_composed_features(grpg_alloc_fn geometry_alloc, void* geometry_
   char* blob = feature_alloc(FL.total, feature_user);
   if (!blob) return fail(GRPG_ERR_ALLOC, "feature buffer allocation failed");
   FrameRequest q;
-  q.geometry_alloc = geometry_alloc; q.geometry_user = geometry_user; q.binning_alloc = binning_alloc;
-  q.binning_user = binning_user; q.image_alloc = image_alloc; q.image_user = image_user;
-  q.segs = segments; q.nseg = num_segments; q.P = (int)P; q.D = D; q.M = M; q.background = background;
-  q.width = width; q.height = height; q.scale_modifier = scale_modifier; q.viewmatrix = viewmatrix;
-  q.projmatrix = projmatrix; q.cam_pos = cam_pos; q.tan_fovx = tan_fovx; q.tan_fovy = tan_fovy;
-  q.out_color = out_color; q.out_depth = out_depth; q.out_alpha = out_alpha; q.radii = radii; q.debug = debug;
-  q.stream = (hipStream_t)hip_stream; q.flags = flags;
+  set_allocators(q, geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user);
+  set_model(q, segments, num_segments, P, D, M);
+  set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+             out_color, out_depth, out_alpha, radii, debug, hip_stream, flags);
   q.seg_semantic = seg_semantic; q.feat_S = S; q.feat_normals = normals; q.feat_blob = blob;
   q.S = F; q.semantics = (const float*)(blob + FL.features); q.out_semantic = out_features;
   return forward_impl(q);
@@ -1662,33 +1694,33 @@ static int check_feature_call(const grpg_model_segment* segments, int num_segmen
   return GRPG_OK;
 }
 
-// Stand-alone feature calls: the two tables (and the backward's slots) travel through a temporary device buffer,
-// like grpg_compose's.
-static int feature_call(const grpg_model_segment* segments, int num_segments, const float* const* seg_semantic,
-                        float* const* seg_dL_dsemantic, float* const* seg_dL_drotation, long long P, int F,
-                        hipStream_t stream, const char* what,
-                        const std::function<void(const SegmentDev*, const FeatureSegDev*, float*, uint32_t)>& launch) {
+// Stand-alone calls (grpg_compose, grpg_compose_features and its backward): the segment table -- and, with `feats`,
+// the feature table of the three per-segment arrays (each may be NULL) and the backward's slots -- travel through a
+// temporary device buffer.
+typedef std::function<void(const SegmentDev*, const FeatureSegDev*, float*, uint32_t)> TempTableLaunch;
+static int temp_table_call(const grpg_model_segment* segments, int num_segments, bool feats,
+                           const float* const* seg_semantic, float* const* seg_dL_dsemantic,
+                           float* const* seg_dL_drotation, long long P, hipStream_t stream, const char* what,
+                           const TempTableLaunch& launch) {
   const size_t n = (size_t)num_segments;
   std::vector<SegmentDev> host(n);
-  std::vector<FeatureSegDev> fhost(n);
-  uint32_t start = 0;
-  for (size_t i = 0; i < n; i++) {
-    fill_segment(host[i], segments[i], start, nullptr);
-    start += (uint32_t)segments[i].count;
+  fill_segments(host.data(), segments, num_segments, nullptr);
+  std::vector<FeatureSegDev> fhost(feats ? n : 0);
+  for (size_t i = 0; i < fhost.size(); i++)
     fhost[i] = FeatureSegDev{seg_semantic ? seg_semantic[i] : nullptr, seg_dL_dsemantic ? seg_dL_dsemantic[i] : nullptr,
                              seg_dL_drotation ? seg_dL_drotation[i] : nullptr, nullptr};
-  }
-  const FeatLayout FL = feat_layout((size_t)P, 0);   // (no feature array: the caller's)
+  const FeatLayout FL = feats ? feat_layout((size_t)P, 0) : FeatLayout{};   // (no feature array: the caller's)
   const size_t seg_bytes = (sizeof(SegmentDev) * n + 255) / 256 * 256;
   char* dev = nullptr;
   HIP_TRY(hipMalloc((void**)&dev, seg_bytes + FL.total));
+  char* const fdev = dev + seg_bytes;
   hipError_t e = hipMemcpyAsync(dev, host.data(), sizeof(SegmentDev) * n, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(dev + seg_bytes + FL.table, fhost.data(), sizeof(FeatureSegDev) * n, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess && feats)
+    e = hipMemcpyAsync(fdev + FL.table, fhost.data(), sizeof(FeatureSegDev) * n, hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);   // pageable sources: the copies must finish before they die
   if (e == hipSuccess) {
-    launch((const SegmentDev*)dev, (const FeatureSegDev*)(dev + seg_bytes + FL.table),
-           (float*)(dev + seg_bytes + FL.partials), FL.nslots);
+    launch((const SegmentDev*)dev, feats ? (const FeatureSegDev*)(fdev + FL.table) : nullptr,
+           feats ? (float*)(fdev + FL.partials) : nullptr, FL.nslots);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
   }
@@ -1707,10 +1739,10 @@ int grpg_compose_features(const grpg_model_segment* segments, int num_segments, 
   if (F == 0) return GRPG_OK;
   if (!features) return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL output pointer");
   hipStream_t stream = (hipStream_t)hip_stream;
-  return feature_call(segments, num_segments, seg_semantic, nullptr, nullptr, P, F, stream, "grpg_compose_features",
-                      [&](const SegmentDev* sd, const FeatureSegDev* fd, float*, uint32_t) {
-                        launch_compose_features(stream, (int)P, sd, fd, num_segments, S, normals, cam_pos, features);
-                      });
+  return temp_table_call(segments, num_segments, true, seg_semantic, nullptr, nullptr, P, stream, "grpg_compose_features",
+                         [&](const SegmentDev* sd, const FeatureSegDev* fd, float*, uint32_t) {
+                           launch_compose_features(stream, (int)P, sd, fd, num_segments, S, normals, cam_pos, features);
+                         });
 }
 
 int grpg_compose_features_backward(const grpg_model_segment* segments, int num_segments, int S, int normals,
@@ -1724,12 +1756,12 @@ int grpg_compose_features_backward(const grpg_model_segment* segments, int num_s
   if (F == 0) return GRPG_OK;
   if (!dL_dfeatures || (normals && !dL_dposes)) return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL gradient pointer");
   hipStream_t stream = (hipStream_t)hip_stream;
-  return feature_call(segments, num_segments, nullptr, seg_dL_dsemantic, seg_dL_drotation, P, F, stream,
-                      "grpg_compose_features_backward",
-                      [&](const SegmentDev* sd, const FeatureSegDev* fd, float* partials, uint32_t nslots) {
-                        launch_compose_features_backward(stream, (int)P, sd, fd, num_segments, S, normals, cam_pos,
-                                                         dL_dfeatures, partials, nslots, dL_dposes);
-                      });
+  return temp_table_call(segments, num_segments, true, nullptr, seg_dL_dsemantic, seg_dL_drotation, P, stream,
+                         "grpg_compose_features_backward",
+                         [&](const SegmentDev* sd, const FeatureSegDev* fd, float* partials, uint32_t nslots) {
+                           launch_compose_features_backward(stream, (int)P, sd, fd, num_segments, S, normals, cam_pos,
+                                                            dL_dfeatures, partials, nslots, dL_dposes);
+                         });
 }
 
 int grpg_compose(const grpg_model_segment* segments, int num_segments, int M, float* means3D,
@@ -1742,26 +1774,10 @@ int grpg_compose(const grpg_model_segment* segments, int num_segments, int M, fl
   if (!means3D || !scales || !rotations || !opacities || !shs)
     return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL output pointer");
   hipStream_t stream = (hipStream_t)hip_stream;
-  // standalone call: the table travels through a temporary device buffer (stream-ordered free)
-  std::vector<SegmentDev> host((size_t)num_segments);
-  uint32_t start = 0;
-  for (int i = 0; i < num_segments; i++) {
-    fill_segment(host[(size_t)i], segments[i], start, nullptr);
-    start += (uint32_t)segments[i].count;
-  }
-  SegmentDev* dev_tab = nullptr;
-  HIP_TRY(hipMalloc((void**)&dev_tab, sizeof(SegmentDev) * host.size()));
-  hipError_t e = hipMemcpyAsync(dev_tab, host.data(), sizeof(SegmentDev) * host.size(),
-                                hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);   // pageable source: copy must finish before `host` dies
-  if (e == hipSuccess) {
-    launch_compose(stream, (int)P, M, dev_tab, num_segments, means3D, scales, rotations, opacities, shs);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  }
-  (void)hipFree(dev_tab);
-  if (e != hipSuccess) return fail(GRPG_ERR_HIP, std::string("grpg_compose: ") + hipGetErrorString(e));
-  return GRPG_OK;
+  return temp_table_call(segments, num_segments, false, nullptr, nullptr, nullptr, P, stream, "grpg_compose",
+                         [&](const SegmentDev* sd, const FeatureSegDev*, float*, uint32_t) {
+                           launch_compose(stream, (int)P, M, sd, num_segments, means3D, scales, rotations, opacities, shs);
+                         });
 }
 
 int grpg_backward(int P, int D, int M, int R, int S, const float* background, int width,
@@ -1781,9 +1797,7 @@ int grpg_backward(int P, int D, int M, int R, int S, const float* background, in
   if (P <= 0) return GRPG_OK;
   if (!geom_buffer || !binning_buffer || !image_buffer)
     return fail(GRPG_ERR_BAD_BUFFER, "NULL state buffer");
-  if (int rc = geom_check_backward(geom_buffer, P, (hipStream_t)hip_stream)) return rc;
-  for (auto& hw : g_host_words)
-    if (int rc = check_async_error(&hw)) return rc;
+  if (int rc = check_backward_state(geom_buffer, P, (hipStream_t)hip_stream)) return rc;
   // dL_dconic / dL_ddepth (pure intermediates of the reference's binding) and dL_dcolor / dL_dcov3D
   // (gradients of the OPTIONAL inputs colors_precomp / cov3D_precomp) may be NULL: not written then
   if (!dL_dpix || !dL_dpix_depth || !dL_dalphas || !alphas || !dL_dmean2D || !dL_dopacity || !dL_dmean3D)
@@ -1803,10 +1817,8 @@ int grpg_backward(int P, int D, int M, int R, int S, const float* background, in
     return fail(GRPG_ERR_INVALID_ARGUMENT,
                 "backward supports at most 32 semantic channels (the reference: 20, config.h:16)");
   hipStream_t stream = (hipStream_t)hip_stream;
-  const CameraArgs cam = make_camera(viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy);
-  const uint32_t T = (uint32_t)cam.gx * (uint32_t)cam.gy;
-  const GeomLayout GL = geom_layout((size_t)P);
-  const ImgLayout IL = img_layout(T, (size_t)width * height);
+  BlendBackward bb(P, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, geom_buffer, binning_buffer,
+                   image_buffer);
   if (debug) {  // validate the blobs (costs a sync; only in debug mode, like the reference's checks)
     BlobHeader h[3];
     HIP_TRY(hipMemcpyAsync(&h[0], geom_buffer, sizeof(BlobHeader), hipMemcpyDeviceToHost, stream));
@@ -1822,34 +1834,17 @@ int grpg_backward(int P, int D, int M, int R, int S, const float* background, in
     if (h[2].pc_timeout != 0u)
       return fail(GRPG_ERR_HIP, "the forward of this frame reported a producer/consumer timeout: its image is invalid");
   }
-  const RecView rec = {(const float4*)(geom_buffer + GL.rec)};
-  const int* radii_int = radii ? radii : (const int*)(geom_buffer + GL.radii);
-  // the point list is the first array of the binning blob whatever capacity it was carved for
-  const uint32_t* point_list = (const uint32_t*)(binning_buffer + bin_layout(0).val_a);
-  const uint2* ranges = (const uint2*)(image_buffer + IL.ranges);
-  const uint32_t* n_contrib = (const uint32_t*)(image_buffer + IL.n_contrib);
-
-  // per-Gaussian gradient records (one 64-byte line each) in the tail of the geometry blob: cleared,
-  // accumulated by the blend backward, fanned out into the caller's arrays by the preprocess backward
-  float* grad_rec = (float*)(geom_buffer + GL.grad_rec);
-  HIP_TRY(hipMemsetAsync(grad_rec, 0, (size_t)P * GRAD_STRIDE * sizeof(float), stream));
-  BwdTimingRecord* const btr = bwd_timing_begin(stream);
-  BwdTimingGuard btg(btr);
-  launch_render_backward(stream, ranges, point_list, rec, semantics, S, width, height, cam.gx,
-                         cam.gy, background, alphas, n_contrib,
-                         (const uint32_t*)(image_buffer + IL.work), dL_dpix, dL_dpix_depth, dL_dalphas,
-                         dL_dpix_semantic, grad_rec, dL_dsemantic, (const BlobHeader*)binning_buffer,
-                         (const uint32_t*)(image_buffer + IL.ck_count),
-                         (const uint32_t*)(image_buffer + IL.bwd_ctl), (uint32_t)R);
-  STAGE_CHECK("render backward");
-  bwd_timing_mark(btr, 1, stream);
+  const int* radii_int = radii ? radii : (const int*)(geom_buffer + bb.GL.radii);
+  if (int rc = bb.run(stream, debug, R, background, alphas, semantics, S, dL_dpix, dL_dpix_depth, dL_dalphas,
+                      dL_dpix_semantic, dL_dsemantic))
+    return rc;
   launch_preprocess_backward(stream, P, D, M, means3D, radii_int, colors_precomp ? nullptr : shs,
-                             rec, cov3D_precomp ? nullptr : scales, rotations, scale_modifier,
-                             cov3D_precomp, cam, grad_rec, dL_dmean2D, dL_dconic, dL_dopacity,
+                             bb.rec, cov3D_precomp ? nullptr : scales, rotations, scale_modifier,
+                             cov3D_precomp, bb.cam, bb.grad_rec, dL_dmean2D, dL_dconic, dL_dopacity,
                              dL_dmean3D, dL_dcolor, dL_ddepth, dL_dcov3D,
                              colors_precomp ? nullptr : dL_dsh, dL_dscale, dL_drot);
-  bwd_timing_mark(btr, 2, stream);
-  btg.done = true;
+  bwd_timing_mark(bb.btr, 2, stream);
+  bb.btg.done = true;
   STAGE_CHECK("preprocess backward");
   return GRPG_OK;
 }

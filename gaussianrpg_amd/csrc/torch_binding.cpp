@@ -535,6 +535,15 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
            torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 RasterizeGaussiansBackwardLean(GRPG_BWD_PARAMS) { return RasterizeGaussiansBackwardImpl(GRPG_BWD_ARGS, false); }
 
+// the model bundle of the composed family (below): per model one tensor of each raw parameter, the flip masks, and
+// the two host tables
+#define GRPG_MODEL_PARAMS                                                                                 \
+  const std::vector<torch::Tensor> &xyz, const std::vector<torch::Tensor> &scaling,                         \
+      const std::vector<torch::Tensor> &rotation, const std::vector<torch::Tensor> &opacity,                \
+      const std::vector<torch::Tensor> &features_dc, const std::vector<torch::Tensor> &features_rest,       \
+      const std::vector<torch::Tensor> &flip, const torch::Tensor &poses, const torch::Tensor &idft
+#define GRPG_MODEL_ARGS xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft
+
 torch::Tensor markVisible(torch::Tensor& means3D, torch::Tensor& viewmatrix,
                           torch::Tensor& projmatrix) {
   require_device(means3D);
@@ -602,13 +611,7 @@ struct SegmentPack {
   int M = 0;
 };
 
-SegmentPack pack_segments(const std::vector<torch::Tensor>& xyz, const std::vector<torch::Tensor>& scaling,
-                          const std::vector<torch::Tensor>& rotation,
-                          const std::vector<torch::Tensor>& opacity,
-                          const std::vector<torch::Tensor>& features_dc,
-                          const std::vector<torch::Tensor>& features_rest,
-                          const std::vector<torch::Tensor>& flip,
-                          const torch::Tensor& poses, const torch::Tensor& idft) {
+SegmentPack pack_segments(GRPG_MODEL_PARAMS) {
   const size_t n = xyz.size();
   TORCH_CHECK(flip.size() == n, "one flip mask (or an empty tensor) per model");
   TORCH_CHECK(n > 0 && n <= GRPG_MAX_SEGMENTS, "need 1..", GRPG_MAX_SEGMENTS, " models");
@@ -672,19 +675,12 @@ SegmentPack pack_segments(const std::vector<torch::Tensor>& xyz, const std::vect
 
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
            torch::Tensor, torch::Tensor>
-RasterizeGaussiansComposed(const torch::Tensor& background, const std::vector<torch::Tensor>& xyz,
-                           const std::vector<torch::Tensor>& scaling,
-                           const std::vector<torch::Tensor>& rotation,
-                           const std::vector<torch::Tensor>& opacity,
-                           const std::vector<torch::Tensor>& features_dc,
-                           const std::vector<torch::Tensor>& features_rest,
-                           const std::vector<torch::Tensor>& flip,
-                           const torch::Tensor& poses, const torch::Tensor& idft,
+RasterizeGaussiansComposed(const torch::Tensor& background, GRPG_MODEL_PARAMS,
                            const float scale_modifier, const torch::Tensor& viewmatrix,
                            const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
                            const int image_height, const int image_width, const int degree,
                            const torch::Tensor& campos, const bool debug, const bool for_backward) {
-  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
   const int H = image_height, W = image_width;
@@ -708,19 +704,12 @@ RasterizeGaussiansComposed(const torch::Tensor& background, const std::vector<to
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
            torch::Tensor, torch::Tensor>
 RasterizeGaussiansComposedLayers(const torch::Tensor& background, const torch::Tensor& layer_background,
-                                 const torch::Tensor& object_model, const std::vector<torch::Tensor>& xyz,
-                                 const std::vector<torch::Tensor>& scaling,
-                                 const std::vector<torch::Tensor>& rotation,
-                                 const std::vector<torch::Tensor>& opacity,
-                                 const std::vector<torch::Tensor>& features_dc,
-                                 const std::vector<torch::Tensor>& features_rest,
-                                 const std::vector<torch::Tensor>& flip, const torch::Tensor& poses,
-                                 const torch::Tensor& idft, const float scale_modifier,
+                                 const torch::Tensor& object_model, GRPG_MODEL_PARAMS, const float scale_modifier,
                                  const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
                                  const float tan_fovx, const float tan_fovy, const int image_height,
                                  const int image_width, const int degree, const torch::Tensor& campos,
                                  const bool debug) {
-  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
   const int H = image_height, W = image_width;
@@ -743,16 +732,13 @@ RasterizeGaussiansComposedLayers(const torch::Tensor& background, const torch::T
 // The scene-graph frame as one call (grpg_forward_composed_frame): composition + op (+ layers) + sky + clamp + rgb8.
 FrameResult RasterizeGaussiansComposedFrame(
     const torch::Tensor& background, const torch::Tensor& layer_background, const torch::Tensor& object_model,
-    const bool layered, const std::vector<torch::Tensor>& xyz, const std::vector<torch::Tensor>& scaling,
-    const std::vector<torch::Tensor>& rotation, const std::vector<torch::Tensor>& opacity,
-    const std::vector<torch::Tensor>& features_dc, const std::vector<torch::Tensor>& features_rest,
-    const std::vector<torch::Tensor>& flip, const torch::Tensor& poses, const torch::Tensor& idft,
+    const bool layered, GRPG_MODEL_PARAMS,
     const float scale_modifier, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
     const float tan_fovx, const float tan_fovy, const int image_height, const int image_width, const int degree,
     const torch::Tensor& campos, const bool debug, const torch::Tensor& sky_cube, const torch::Tensor& ray_matrix,
     const float sky_fill, const bool clamp, const bool want_planes, const bool want_rgb8, const bool truncate,
     const c10::optional<torch::Tensor>& out_rgb8) {
-  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
   TORCH_CHECK(want_planes || want_rgb8, kFrameAsksForNothing);
@@ -773,60 +759,6 @@ FrameResult RasterizeGaussiansComposedFrame(
         o.p_radii, debug ? 1 : 0, stream, &ea.e);
   });
   return o.frame(rendered, ea.rgb8);
-}
-
-// Training backward of the fused composition (grpg_backward_composed): gradients with respect to
-// every model's RAW parameter tensors, means2D [P,3] (densification statistic) and the poses [n,8].
-std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
-           std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
-           torch::Tensor, torch::Tensor>
-RasterizeGaussiansComposedBackward(
-    const torch::Tensor& background, const std::vector<torch::Tensor>& xyz,
-    const std::vector<torch::Tensor>& scaling, const std::vector<torch::Tensor>& rotation,
-    const std::vector<torch::Tensor>& opacity, const std::vector<torch::Tensor>& features_dc,
-    const std::vector<torch::Tensor>& features_rest, const std::vector<torch::Tensor>& flip,
-    const torch::Tensor& poses, const torch::Tensor& idft,
-    const float scale_modifier, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
-    const float tan_fovx, const float tan_fovy, const int degree, const torch::Tensor& campos,
-    const torch::Tensor& radii, const torch::Tensor& alphas, const torch::Tensor& geomBuffer, const int R,
-    const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
-    const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_depth,
-    const torch::Tensor& dL_dout_alpha, const bool debug) {
-  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
-  const torch::Tensor& like = xyz[0];
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
-  const int H = dL_dout_color.size(1), W = dL_dout_color.size(2);
-  const size_t n = xyz.size();
-  auto o = like.options().dtype(torch::kFloat32);
-  std::vector<torch::Tensor> g_xyz(n), g_scaling(n), g_rotation(n), g_opacity(n), g_fdc(n), g_frest(n);
-  std::vector<grpg_model_segment_grad> gs(n);
-  for (size_t i = 0; i < n; i++) {   // every element is written by the kernel: no zero-fill
-    g_xyz[i] = torch::empty(xyz[i].sizes(), o);
-    g_scaling[i] = torch::empty(scaling[i].sizes(), o);
-    g_rotation[i] = torch::empty(rotation[i].sizes(), o);
-    g_opacity[i] = torch::empty(opacity[i].sizes(), o);
-    g_fdc[i] = torch::empty(features_dc[i].sizes(), o);
-    g_frest[i] = torch::empty(features_rest[i].sizes(), o);
-    gs[i] = grpg_model_segment_grad{g_xyz[i].data_ptr<float>(), g_scaling[i].data_ptr<float>(),
-                                    g_rotation[i].data_ptr<float>(), g_opacity[i].data_ptr<float>(),
-                                    g_fdc[i].data_ptr<float>(),
-                                    g_frest[i].numel() ? g_frest[i].data_ptr<float>() : nullptr};
-  }
-  torch::Tensor dL_dmeans2D = torch::empty({pk.P, 3}, o);
-  torch::Tensor dL_dposes = torch::empty({(int64_t)n, 8}, o);
-  CameraPtrs cam(like, background, nullptr);
-  cam.pose(like, viewmatrix, projmatrix, campos);
-  torch::Tensor k_alpha;
-  const float* p_alpha = fptr(alphas, like, "alphas", k_alpha);
-  const SavedState sv(like, dL_dout_color, dL_dout_depth, dL_dout_alpha, nullptr, radii, geomBuffer, binningBuffer,
-                      imageBuffer);
-  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  const int rc = grpg_backward_composed(
-      pk.segs.data(), gs.data(), (int)n, degree, pk.M, R, cam.bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos,
-      tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img, sv.dcolor, sv.ddepth, sv.dalpha,
-      dL_dmeans2D.data_ptr<float>(), dL_dposes.data_ptr<float>(), debug ? 1 : 0, (void*)stream);
-  if (rc != GRPG_OK) raise_abi_error("grpg_backward_composed", rc);
-  return std::make_tuple(g_xyz, g_scaling, g_rotation, g_opacity, g_fdc, g_frest, dL_dmeans2D, dL_dposes);
 }
 
 // ---- feature planes of a composed frame (grpg_*_features): F = 3 * normals + S channels, normals first ----
@@ -859,17 +791,46 @@ SemanticPack pack_semantics(const std::vector<torch::Tensor>& semantics, const s
   return sp;
 }
 
+// The semantic gradients a backward writes: [N_i,S] for the models that want one (want_semantic[i] and S > 0), an
+// empty tensor and a NULL pointer for the others.  Every element is written by the kernel: no zero-fill.
+struct SemanticGrads {
+  std::vector<torch::Tensor> grads;
+  std::vector<float*> ptrs;
+  SemanticGrads(const std::vector<torch::Tensor>& xyz, const int S, const std::vector<bool>& want_semantic,
+                const torch::TensorOptions& o)
+      : grads(xyz.size(), torch::empty({0}, o)), ptrs(xyz.size(), nullptr) {
+    TORCH_CHECK(want_semantic.size() == xyz.size(), "one want_semantic flag per model");
+    for (size_t i = 0; i < xyz.size(); i++)
+      if (want_semantic[i] && S > 0)
+        ptrs[i] = (grads[i] = torch::empty({xyz[i].size(0), (int64_t)S}, o)).data_ptr<float>();
+  }
+};
+
+// The raw-parameter gradients of a frame backward: per model six tensors shaped like the parameters (xyz, scaling,
+// rotation, opacity, features_dc, features_rest) and the table of their pointers the C ABI takes.  Every element is
+// written by the kernels: no zero-fill.
+struct ModelGrads {
+  std::vector<torch::Tensor> g[6];
+  std::vector<grpg_model_segment_grad> table;
+  ModelGrads(const std::vector<torch::Tensor>* const (&params)[6], const torch::TensorOptions& o)
+      : table(params[0]->size()) {
+    for (int f = 0; f < 6; f++)
+      for (const torch::Tensor& t : *params[f]) g[f].push_back(torch::empty(t.sizes(), o));
+    for (size_t i = 0; i < table.size(); i++)
+      table[i] = grpg_model_segment_grad{g[0][i].data_ptr<float>(), g[1][i].data_ptr<float>(),
+                                         g[2][i].data_ptr<float>(), g[3][i].data_ptr<float>(),
+                                         g[4][i].data_ptr<float>(),
+                                         g[5][i].numel() ? g[5][i].data_ptr<float>() : nullptr};
+  }
+};
+
 }  // namespace
 
 // composed.compose_features: [P,F]
-torch::Tensor ComposeFeatures(const std::vector<torch::Tensor>& xyz, const std::vector<torch::Tensor>& scaling,
-                              const std::vector<torch::Tensor>& rotation, const std::vector<torch::Tensor>& opacity,
-                              const std::vector<torch::Tensor>& features_dc,
-                              const std::vector<torch::Tensor>& features_rest, const std::vector<torch::Tensor>& flip,
-                              const torch::Tensor& poses, const torch::Tensor& idft,
+torch::Tensor ComposeFeatures(GRPG_MODEL_PARAMS,
                               const std::vector<torch::Tensor>& semantics, const bool normals,
                               const torch::Tensor& campos) {
-  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
   const SemanticPack sp = pack_semantics(semantics, xyz);
@@ -887,58 +848,47 @@ torch::Tensor ComposeFeatures(const std::vector<torch::Tensor>& xyz, const std::
 // its backward: (dL/d raw rotation per model, dL/d semantic per model ([N_i,S]; empty where want_semantic[i] is
 // false), dL_dposes [n,8] with the product path's share in [:, 0:4])
 std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>, torch::Tensor>
-ComposeFeaturesBackward(const std::vector<torch::Tensor>& xyz, const std::vector<torch::Tensor>& scaling,
-                        const std::vector<torch::Tensor>& rotation, const std::vector<torch::Tensor>& opacity,
-                        const std::vector<torch::Tensor>& features_dc, const std::vector<torch::Tensor>& features_rest,
-                        const std::vector<torch::Tensor>& flip, const torch::Tensor& poses, const torch::Tensor& idft,
+ComposeFeaturesBackward(GRPG_MODEL_PARAMS,
                         const int S, const std::vector<bool>& want_semantic, const bool normals,
                         const torch::Tensor& campos, const torch::Tensor& dL_dfeatures) {
-  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
   const size_t n = xyz.size();
   const int64_t F = 3 * (normals ? 1 : 0) + S;
-  TORCH_CHECK(want_semantic.size() == n, "one want_semantic flag per model");
+  auto o = like.options().dtype(torch::kFloat32);
+  SemanticGrads sem(xyz, S, want_semantic, o);
   TORCH_CHECK(dL_dfeatures.dim() == 2 && dL_dfeatures.size(0) == pk.P && dL_dfeatures.size(1) == F,
               "dL_dfeatures must be [P,F]");
   torch::Tensor k_pos, k_g;
   const float* p_pos = fptr(campos, like, "campos", k_pos);
   const float* p_g = fptr(dL_dfeatures, like, "dL_dfeatures", k_g);
   TORCH_CHECK(!normals || (p_pos && campos.numel() == 3), "normals need campos (3 floats on the device)");
-  auto o = like.options().dtype(torch::kFloat32);
-  std::vector<torch::Tensor> g_rot(n), g_sem(n);
-  std::vector<float*> p_rot(n, nullptr), p_sem(n, nullptr);
+  std::vector<torch::Tensor> g_rot(n);
+  std::vector<float*> p_rot(n, nullptr);
   for (size_t i = 0; i < n; i++) {
     g_rot[i] = torch::zeros(rotation[i].sizes(), o);   // added to
     if (normals) p_rot[i] = g_rot[i].data_ptr<float>();
-    g_sem[i] = want_semantic[i] && S > 0 ? torch::empty({xyz[i].size(0), (int64_t)S}, o) : torch::empty({0}, o);
-    if (g_sem[i].numel()) p_sem[i] = g_sem[i].data_ptr<float>();
   }
   torch::Tensor dL_dposes = torch::zeros({(int64_t)n, 8}, o);
   hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  const int rc = grpg_compose_features_backward(pk.segs.data(), (int)n, S, normals ? 1 : 0, p_pos, p_g, p_sem.data(),
+  const int rc = grpg_compose_features_backward(pk.segs.data(), (int)n, S, normals ? 1 : 0, p_pos, p_g, sem.ptrs.data(),
                                                 p_rot.data(), dL_dposes.data_ptr<float>(), (void*)stream);
   if (rc != GRPG_OK) raise_abi_error("grpg_compose_features_backward", rc);
-  return std::make_tuple(g_rot, g_sem, dL_dposes);
+  return std::make_tuple(g_rot, sem.grads, dL_dposes);
 }
 
 // ComposedRasterizer.forward_features: rasterize_gaussians_composed + the feature planes [F,H,W] and the fourth blob.
 // returns (num_rendered, color, depth, alpha, features, radii, geom, binning, img, feature blob)
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
            torch::Tensor, torch::Tensor, torch::Tensor>
-RasterizeGaussiansComposedFeatures(const torch::Tensor& background, const std::vector<torch::Tensor>& xyz,
-                                   const std::vector<torch::Tensor>& scaling,
-                                   const std::vector<torch::Tensor>& rotation,
-                                   const std::vector<torch::Tensor>& opacity,
-                                   const std::vector<torch::Tensor>& features_dc,
-                                   const std::vector<torch::Tensor>& features_rest,
-                                   const std::vector<torch::Tensor>& flip, const torch::Tensor& poses,
-                                   const torch::Tensor& idft, const std::vector<torch::Tensor>& semantics,
+RasterizeGaussiansComposedFeatures(const torch::Tensor& background, GRPG_MODEL_PARAMS,
+                                   const std::vector<torch::Tensor>& semantics,
                                    const bool normals, const float scale_modifier, const torch::Tensor& viewmatrix,
                                    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
                                    const int image_height, const int image_width, const int degree,
                                    const torch::Tensor& campos, const bool debug, const bool for_backward) {
-  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
   const SemanticPack sp = pack_semantics(semantics, xyz);
@@ -958,79 +908,67 @@ RasterizeGaussiansComposedFeatures(const torch::Tensor& background, const std::v
   return std::make_tuple(rendered, o.color, o.depth, o.alpha, o.semantic, o.radii, o.geom, o.binning, o.img, feat_blob);
 }
 
-// its backward (grpg_backward_composed_features): rasterize_gaussians_composed_backward's tuple with the semantic
-// gradients ([N_i,S] per model; empty where want_semantic[i] is false) in front of dL_dmeans2D
+// The training backward of rasterize_gaussians_composed and _composed_features (grpg_backward_composed at F = 0, where
+// the feature blob and dL_dout_features are not looked at; grpg_backward_composed_features otherwise): gradients with
+// respect to every model's RAW parameter tensors, the semantic arrays ([N_i,S] per model; empty where
+// want_semantic[i] is false), means2D [P,3] (densification statistic) and the poses [n,8].
 std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
            std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
            std::vector<torch::Tensor>, torch::Tensor, torch::Tensor>
-RasterizeGaussiansComposedFeaturesBackward(
-    const torch::Tensor& background, const std::vector<torch::Tensor>& xyz,
-    const std::vector<torch::Tensor>& scaling, const std::vector<torch::Tensor>& rotation,
-    const std::vector<torch::Tensor>& opacity, const std::vector<torch::Tensor>& features_dc,
-    const std::vector<torch::Tensor>& features_rest, const std::vector<torch::Tensor>& flip,
-    const torch::Tensor& poses, const torch::Tensor& idft, const int S, const std::vector<bool>& want_semantic,
+RasterizeGaussiansComposedBackward(
+    const torch::Tensor& background, GRPG_MODEL_PARAMS, const int S, const std::vector<bool>& want_semantic,
     const bool normals, const float scale_modifier, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
     const float tan_fovx, const float tan_fovy, const int degree, const torch::Tensor& campos,
     const torch::Tensor& radii, const torch::Tensor& alphas, const torch::Tensor& geomBuffer, const int R,
     const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const torch::Tensor& featureBuffer,
     const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_depth, const torch::Tensor& dL_dout_alpha,
     const torch::Tensor& dL_dout_features, const bool debug) {
-  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+  SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
   const int H = dL_dout_color.size(1), W = dL_dout_color.size(2);
-  const size_t n = xyz.size();
+  const int n = (int)xyz.size();
   const int64_t F = 3 * (normals ? 1 : 0) + S;
-  TORCH_CHECK(want_semantic.size() == n, "one want_semantic flag per model");
-  TORCH_CHECK(dL_dout_features.numel() == F * H * W, "dL_dout_features must be [F,H,W]");
   auto o = like.options().dtype(torch::kFloat32);
-  std::vector<torch::Tensor> g_xyz(n), g_scaling(n), g_rotation(n), g_opacity(n), g_fdc(n), g_frest(n), g_sem(n);
-  std::vector<grpg_model_segment_grad> gs(n);
-  std::vector<float*> p_sem(n, nullptr);
-  for (size_t i = 0; i < n; i++) {   // every element is written by the kernels: no zero-fill
-    g_xyz[i] = torch::empty(xyz[i].sizes(), o);
-    g_scaling[i] = torch::empty(scaling[i].sizes(), o);
-    g_rotation[i] = torch::empty(rotation[i].sizes(), o);
-    g_opacity[i] = torch::empty(opacity[i].sizes(), o);
-    g_fdc[i] = torch::empty(features_dc[i].sizes(), o);
-    g_frest[i] = torch::empty(features_rest[i].sizes(), o);
-    gs[i] = grpg_model_segment_grad{g_xyz[i].data_ptr<float>(), g_scaling[i].data_ptr<float>(),
-                                    g_rotation[i].data_ptr<float>(), g_opacity[i].data_ptr<float>(),
-                                    g_fdc[i].data_ptr<float>(),
-                                    g_frest[i].numel() ? g_frest[i].data_ptr<float>() : nullptr};
-    g_sem[i] = want_semantic[i] && S > 0 ? torch::empty({xyz[i].size(0), (int64_t)S}, o) : torch::empty({0}, o);
-    if (g_sem[i].numel()) p_sem[i] = g_sem[i].data_ptr<float>();
-  }
+  SemanticGrads sem(xyz, S, want_semantic, o);
+  TORCH_CHECK(dL_dout_features.numel() == F * H * W, "dL_dout_features must be [F,H,W]");
+  ModelGrads mg({&xyz, &scaling, &rotation, &opacity, &features_dc, &features_rest}, o);
   torch::Tensor dL_dmeans2D = torch::empty({pk.P, 3}, o);
   torch::Tensor dL_dposes = torch::empty({(int64_t)n, 8}, o);
-  torch::Tensor dL_dfeatures = torch::zeros({pk.P, F}, o);   // the blend backward accumulates into it
   CameraPtrs cam(like, background, nullptr);
   cam.pose(like, viewmatrix, projmatrix, campos);
-  torch::Tensor k_alpha, k_blob;
+  torch::Tensor k_alpha;
   const float* p_alpha = fptr(alphas, like, "alphas", k_alpha);
   const SavedState sv(like, dL_dout_color, dL_dout_depth, dL_dout_alpha, &dL_dout_features, radii, geomBuffer,
                       binningBuffer, imageBuffer);
-  TORCH_CHECK(featureBuffer.scalar_type() == torch::kByte && featureBuffer.device() == like.device(),
-              "the feature blob must be the forward's byte tensor");
-  char* p_blob = reinterpret_cast<char*>((k_blob = featureBuffer.contiguous()).data_ptr());
   hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  const int rc = grpg_backward_composed_features(
-      pk.segs.data(), gs.data(), (int)n, p_sem.data(), S, normals ? 1 : 0, degree, pk.M, R, cam.bg, W, H,
-      scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img,
-      p_blob, sv.dcolor, sv.ddepth, sv.dalpha, sv.dsemantic, F > 0 ? dL_dfeatures.data_ptr<float>() : nullptr,
-      dL_dmeans2D.data_ptr<float>(), dL_dposes.data_ptr<float>(), debug ? 1 : 0, (void*)stream);
-  if (rc != GRPG_OK) raise_abi_error("grpg_backward_composed_features", rc);
-  return std::make_tuple(g_xyz, g_scaling, g_rotation, g_opacity, g_fdc, g_frest, g_sem, dL_dmeans2D, dL_dposes);
+  if (F == 0) {
+    const int rc = grpg_backward_composed(
+        pk.segs.data(), mg.table.data(), n, degree, pk.M, R, cam.bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos,
+        tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img, sv.dcolor, sv.ddepth, sv.dalpha,
+        dL_dmeans2D.data_ptr<float>(), dL_dposes.data_ptr<float>(), debug ? 1 : 0, (void*)stream);
+    if (rc != GRPG_OK) raise_abi_error("grpg_backward_composed", rc);
+  } else {
+    torch::Tensor dL_dfeatures = torch::zeros({pk.P, F}, o);   // the blend backward accumulates into it
+    TORCH_CHECK(featureBuffer.scalar_type() == torch::kByte && featureBuffer.device() == like.device(),
+                "the feature blob must be the forward's byte tensor");
+    const torch::Tensor k_blob = featureBuffer.contiguous();
+    const int rc = grpg_backward_composed_features(
+        pk.segs.data(), mg.table.data(), n, sem.ptrs.data(), S, normals ? 1 : 0, degree, pk.M, R, cam.bg, W, H,
+        scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img,
+        reinterpret_cast<char*>(k_blob.data_ptr()), sv.dcolor, sv.ddepth, sv.dalpha, sv.dsemantic,
+        dL_dfeatures.data_ptr<float>(), dL_dmeans2D.data_ptr<float>(), dL_dposes.data_ptr<float>(), debug ? 1 : 0,
+        (void*)stream);
+    if (rc != GRPG_OK) raise_abi_error("grpg_backward_composed_features", rc);
+  }
+  return std::make_tuple(mg.g[0], mg.g[1], mg.g[2], mg.g[3], mg.g[4], mg.g[5], sem.grads, dL_dmeans2D, dL_dposes);
 }
 
 // (means3D [P,3], scales [P,3], rotations [P,4], opacity [P,1], shs [P,M,3]): what the reference's
 // get_xyz / get_scaling / get_rotation / get_opacity / get_features return for the same models
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
-Compose(const std::vector<torch::Tensor>& xyz, const std::vector<torch::Tensor>& scaling,
-        const std::vector<torch::Tensor>& rotation, const std::vector<torch::Tensor>& opacity,
-        const std::vector<torch::Tensor>& features_dc, const std::vector<torch::Tensor>& features_rest,
-        const std::vector<torch::Tensor>& flip, const torch::Tensor& poses, const torch::Tensor& idft) {
-  SegmentPack pk = pack_segments(xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft);
+Compose(GRPG_MODEL_PARAMS) {
+  SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
   auto o = like.options().dtype(torch::kFloat32);
@@ -1637,7 +1575,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("compose_features", &ComposeFeatures);
   m.def("compose_features_backward", &ComposeFeaturesBackward);
   m.def("rasterize_gaussians_composed_features", &RasterizeGaussiansComposedFeatures);
-  m.def("rasterize_gaussians_composed_features_backward", &RasterizeGaussiansComposedFeaturesBackward);
   m.def("sky_composite", &SkyComposite, pybind11::arg("cube"), pybind11::arg("ray_matrix"),
         pybind11::arg("fill"), pybind11::arg("clamp_out"), pybind11::arg("rgb"), pybind11::arg("acc"),
         pybind11::arg("height"), pybind11::arg("width"), pybind11::arg("want_sky"),

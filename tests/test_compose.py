@@ -251,13 +251,16 @@ def test_compose_matches_reference_quaternion_fixture():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("sh_degree", [1, 2])
-def test_fused_training_gradients_match_autograd_through_the_restatement(sh_degree):
+@pytest.mark.parametrize("sh_degree,via_features", [
+    pytest.param(1, False, id="1"), pytest.param(2, False, id="2"),
+    pytest.param(1, True, id="1-forward_features"), pytest.param(2, True, id="2-forward_features")])
+def test_fused_training_gradients_match_autograd_through_the_restatement(sh_degree, via_features):
     """Training through the fused composition (C ABI grpg_forward_composed_flags + grpg_backward_composed):
     gradients with respect to every model's RAW parameters, the actors' poses and means2D against
     torch.autograd through oracle/compose_torch.py (the restatement of the reference's getters,
     street_gaussian_model.py:296-453) followed by the classic op -- whose own backward is
-    oracle-checked in tests/test_gpu_backward.py."""
+    oracle-checked in tests/test_gpu_backward.py.  via_features: the same frame asked of forward_features without
+    any feature plane (F = 0), which takes the same two C entries."""
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
     from gaussianrpg_amd.composed import ActorPose, ComposedRasterizer
     from oracle import compose_torch as ct
@@ -289,7 +292,10 @@ def test_fused_training_gradients_match_autograd_through_the_restatement(sh_degr
 
     # fused
     ms, ps, m2d = leaves()
-    color, radii, depth, alpha = ComposedRasterizer(rs)(ms, ps, means2D=m2d)
+    if via_features:
+        color, radii, depth, alpha = ComposedRasterizer(rs).forward_features(ms, ps, None, False, means2D=m2d)[:4]
+    else:
+        color, radii, depth, alpha = ComposedRasterizer(rs)(ms, ps, means2D=m2d)
     assert color.requires_grad and int((radii > 0).sum()) > 5000
     nb = models[0].xyz.shape[0]
     assert int((radii[nb:] > 0).sum()) > 500, "the actors must be in view"

@@ -292,6 +292,62 @@ def test_full_backward(scene):
     assert measured[worst] <= 1e-3, (worst, measured[worst])
 
 
+def _three_models(scene):
+    """the background (300), the partly flipped actor (130) and the single-Gaussian actor; W = 200 is no multiple of
+    the 16-pixel tile"""
+    models, poses, cam, sems = scene
+    keep = (0, 1, 3)
+    return [models[i] for i in keep], [poses[i] for i in keep], cam, {S: [v[i] for i in keep] for S, v in sems.items()}
+
+
+def test_training_frame_without_feature_planes_is_forward(scene):
+    """forward_features without semantics and normals (F = 0), training: an empty [0,H,W] feature tensor, and the
+    frame of forward() on the same inputs -- every plane bit for bit (the forward is deterministic), the same count"""
+    from gaussianrpg_amd.composed import ComposedRasterizer
+    models, poses, cam, _ = _three_models(scene)
+    dev = torch.device("cuda:0")
+    rs = _settings(cam, dev)
+    ms = [_to(m, dev, grad=True) for m in models]
+    plain, feat = ComposedRasterizer(rs), ComposedRasterizer(rs)
+    c1, r1, d1, a1 = plain(ms, poses)
+    c2, r2, d2, a2, f2 = feat.forward_features(ms, poses, None, normals=False)
+    torch.cuda.synchronize()
+    assert c1.requires_grad and c2.requires_grad
+    assert f2.shape == (0, H, W)
+    assert int((r1 > 0).sum()) > 100, "the scene must be in view"
+    assert torch.equal(c2, c1) and torch.equal(d2, d1) and torch.equal(a2, a1) and torch.equal(r2, r1)
+    assert feat.num_rendered == plain.num_rendered and plain.num_rendered > 0
+
+
+@pytest.mark.parametrize("S,normals", [(0, False), (3, True)])
+def test_backward_of_a_loss_on_alpha_alone(scene, S, normals):
+    """only g_alpha reaches the backward (colour, depth and the feature planes arrive as None): every parameter, the
+    tensor-valued poses and means2D get a finite gradient of their own shape; of the semantic arrays, the one that
+    requires grad gets one and the one that does not gets None"""
+    from gaussianrpg_amd.composed import ActorPose, ComposedRasterizer
+    models, poses, cam, sems = _three_models(scene)
+    dev = torch.device("cuda:0")
+    rs = _settings(cam, dev)
+    ms = [_to(m, dev, grad=True) for m in models]
+    ps = [None if p is None else ActorPose(torch.tensor(p.obj_rot, device=dev, requires_grad=True),
+                                           torch.tensor(p.obj_trans, device=dev, requires_grad=True), p.fourier_time)
+          for p in poses]
+    m2d = torch.zeros(sum(m.xyz.shape[0] for m in ms), 3, device=dev, requires_grad=True)
+    # semantics: the background's requires grad, the first actor's does not, the single Gaussian has none
+    ss = None if S == 0 else [sems[S][0].to(dev).clone().requires_grad_(True), sems[S][1].to(dev).clone(), None]
+    out = ComposedRasterizer(rs).forward_features(ms, ps, ss, normals, means2D=m2d)
+    assert out[4].shape == (3 * normals + S, H, W)
+    out[3].sum().backward()
+    torch.cuda.synchronize()
+    leaves = [t for m in ms for t in m[:6]] + [t for p in ps if p is not None for t in (p.obj_rot, p.obj_trans)] + [m2d]
+    for t in leaves:
+        assert t.grad is not None and t.grad.shape == t.shape and bool(torch.isfinite(t.grad).all())
+    assert float(ms[0].opacity.grad.abs().max()) > 0 and float(ms[1].xyz.grad.abs().max()) > 0
+    if ss is not None:
+        assert ss[0].grad is not None and ss[0].grad.shape == ss[0].shape and bool(torch.isfinite(ss[0].grad).all())
+        assert ss[1].grad is None
+
+
 def test_backward_above_32_channels_is_refused(scene):
     """F = 33: the forward works, a backward is refused with the message of grpg_backward, the next call succeeds"""
     from gaussianrpg_amd.composed import ComposedRasterizer
