@@ -48,6 +48,11 @@ HIP_UNITS = {
     # fused semantic cross-entropy: the backward recomputes the forward's softmax input bit for bit (no FMA
     # contraction); no atomics, deterministic fixed-order reduction
     "semantic_loss.hip": ["-ffp-contract=off"],
+    # fused mono-normal loss, scale-flatten / opacity-sparse regularisers and PSNR: each backward recomputes its
+    # forward bit for bit (no FMA contraction); no atomics, deterministic fixed-order reduction
+    "normal_loss.hip": ["-ffp-contract=off"],
+    "reg_loss.hip": ["-ffp-contract=off"],
+    "metrics.hip": ["-ffp-contract=off"],
     # fused multi-tensor Adam step + densification statistics: one rounding per operation, in the order
     # written, on the vector and the scalar path alike (bit-identical across alignments)
     "optim.hip": ["-ffp-contract=off"],

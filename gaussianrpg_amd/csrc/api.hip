@@ -2278,6 +2278,199 @@ int grpg_densify_stats(int P, const float* grad_xyz, const int* radii, const grp
   return GRPG_OK;
 }
 
+// ---- fused mono-normal loss (normal_loss.hip) ----
+size_t grpg_normal_loss_workspace_bytes(int height, int width) {
+  return loss_plane_check(nullptr, height, width) ? 0 : normal_loss_workspace_bytes(height, width);
+}
+
+namespace {
+int normal_loss_check(int height, int width, const float* normals, const float* mono_normal, const float* rotation,
+                      int top_rows, const void* workspace) {
+  if (int rc = loss_plane_check("normal_loss", height, width)) return rc;
+  if (top_rows < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: top_rows must not be negative");
+  if (!normals || !mono_normal || !rotation)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: NULL normals / mono_normal / rotation");
+  if (((uintptr_t)normals | (uintptr_t)mono_normal | (uintptr_t)rotation) & 3)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: normals, mono_normal and rotation must be 4-byte aligned");
+  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: NULL workspace");
+  if ((uintptr_t)workspace & 15)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: workspace must be 16-byte aligned");
+  return GRPG_OK;
+}
+}  // namespace
+
+int grpg_normal_loss_forward(int height, int width, const float* normals, const float* mono_normal,
+                             const float* rotation, int rot_row_stride, int rot_col_stride, const unsigned char* mask,
+                             const unsigned char* sky_mask, int normalize, int top_rows, float* stats,
+                             void* workspace, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (int rc = normal_loss_check(height, width, normals, mono_normal, rotation, top_rows, workspace)) return rc;
+  if (!stats || ((uintptr_t)stats & 3))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: stats must be a 4-byte aligned pointer");
+  const NormalPlanes planes{normals, mono_normal, rotation, rot_row_stride, rot_col_stride, mask, sky_mask};
+  launch_normal_loss_forward((hipStream_t)hip_stream, height, width, planes, normalize ? 1 : 0, top_rows, stats,
+                             (char*)workspace);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_normal_loss_backward(int height, int width, const float* normals, const float* mono_normal,
+                              const float* rotation, int rot_row_stride, int rot_col_stride, const unsigned char* mask,
+                              const unsigned char* sky_mask, int normalize, int top_rows, const float* grad_stats,
+                              const void* workspace, float* grad_normals, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (int rc = normal_loss_check(height, width, normals, mono_normal, rotation, top_rows, workspace)) return rc;
+  if (!grad_stats || !grad_normals || (((uintptr_t)grad_stats | (uintptr_t)grad_normals) & 3))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: grad_stats and grad_normals must be 4-byte aligned pointers");
+  const NormalPlanes planes{normals, mono_normal, rotation, rot_row_stride, rot_col_stride, mask, sky_mask};
+  launch_normal_loss_backward((hipStream_t)hip_stream, height, width, planes, normalize ? 1 : 0, top_rows, grad_stats,
+                              (const char*)workspace, grad_normals);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+// ---- fused scale-flatten / opacity-sparse regularisers (reg_loss.hip) ----
+size_t grpg_reg_loss_workspace_bytes(int num_segments) {
+  return num_segments < 0 ? 0 : reg_loss_workspace_bytes(num_segments);
+}
+
+namespace {
+// Checks every argument, then uploads the live segments into table slot `which` of the workspace through the pinned
+// ring and fills args / table.  Nothing is queued before the last check has passed.
+int reg_loss_prepare(const float* scaling, long long n_scaling, int scale_activated, const grpg_reg_segment* segments,
+                     int num_segments, int opacity_activated, const int* radii, long long n_radii, float lam_scale,
+                     float lam_opacity, void* workspace, const bool backward, const bool want_scale, int which,
+                     hipStream_t stream, RegLossArgs& R, const RegSegDev*& table) {
+  R = RegLossArgs{};
+  R.scale_on = lam_scale > 0.f && (!backward || want_scale);
+  R.opacity_on = lam_opacity > 0.f;
+  R.scale_activated = scale_activated ? 1 : 0;
+  R.opacity_activated = opacity_activated ? 1 : 0;
+  R.lam_scale = lam_scale;
+  R.lam_opacity = lam_opacity;
+  table = nullptr;
+  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: NULL workspace");
+  if ((uintptr_t)workspace & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: workspace must be 16-byte aligned");
+  if (num_segments < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: negative segment count");
+  if (R.scale_on) {
+    if (n_scaling < 0 || n_scaling > 0x7FFFFFFFll / 3)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: n_scaling must be in [0, (2^31 - 1) / 3]");
+    if (n_scaling > 0 && !scaling) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: NULL scaling with n_scaling > 0");
+    if ((uintptr_t)scaling & 3) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: scaling must be 4-byte aligned");
+    R.n_scaling = n_scaling;
+    R.scaling = scaling;
+  }
+  if (!R.opacity_on) return GRPG_OK;
+  if (num_segments > 0 && !segments) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: NULL segment table");
+  long long total = 0;
+  int live = 0;
+  bool any_grad = false;
+  for (int i = 0; i < num_segments; i++) {
+    const grpg_reg_segment& g = segments[i];
+    if (g.n < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: segment with negative n");
+    if (g.n == 0) continue;
+    if (!g.opacity) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: segment with a NULL opacity array and n > 0");
+    if (((uintptr_t)g.opacity | (uintptr_t)g.grad_opacity) & 3)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: opacity arrays must be 4-byte aligned");
+    total += g.n;
+    if (total > 0x7FFFFFFFll) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: more than 2^31 - 1 Gaussians");
+    any_grad = any_grad || g.grad_opacity != nullptr;
+    live++;
+  }
+  if (n_radii != total)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: the length of radii must be the sum of the segments' n");
+  if (total > 0 && (!radii || ((uintptr_t)radii & 3)))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: radii must be a 4-byte aligned pointer");
+  R.n_opacity = total;
+  R.radii = radii;
+  if (backward && !any_grad) {          // no opacity gradient is wanted: the term costs nothing
+    R.opacity_on = 0;
+    return GRPG_OK;
+  }
+  if (live == 0) return GRPG_OK;
+  const size_t bytes = sizeof(RegSegDev) * (size_t)live;
+  OptimStagingSlot* stg = optim_staging_acquire(bytes);
+  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
+  RegSegDev* host = (RegSegDev*)stg->host;
+  long long start = 0;
+  int k = 0;
+  for (int i = 0; i < num_segments; i++) {
+    const grpg_reg_segment& g = segments[i];
+    if (g.n == 0) continue;
+    host[k++] = RegSegDev{g.opacity, backward ? g.grad_opacity : nullptr, start, g.n};
+    start += g.n;
+  }
+  char* dev = (char*)workspace + reg_loss_table_offset(which, num_segments);
+  HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(stg->ev, stream));
+  R.num_live = live;
+  table = (const RegSegDev*)dev;
+  return GRPG_OK;
+}
+}  // namespace
+
+int grpg_reg_loss_forward(const float* scaling, long long n_scaling, int scale_activated,
+                          const grpg_reg_segment* segments, int num_segments, int opacity_activated, const int* radii,
+                          long long n_radii, float lambda_scale_flatten, float lambda_opacity_sparse, float* stats,
+                          void* workspace, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (!stats || ((uintptr_t)stats & 3))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: stats must be a 4-byte aligned pointer");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  RegLossArgs R;
+  const RegSegDev* table;
+  if (int rc = reg_loss_prepare(scaling, n_scaling, scale_activated, segments, num_segments, opacity_activated, radii,
+                                n_radii, lambda_scale_flatten, lambda_opacity_sparse, workspace, false, true, 0,
+                                stream, R, table))
+    return rc;
+  launch_reg_loss_forward(stream, R, table, stats, (char*)workspace);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_reg_loss_backward(const float* scaling, long long n_scaling, int scale_activated,
+                           const grpg_reg_segment* segments, int num_segments, int opacity_activated, const int* radii,
+                           long long n_radii, float lambda_scale_flatten, float lambda_opacity_sparse,
+                           const float* grad_stats, void* workspace, float* grad_scaling, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (!grad_stats || (((uintptr_t)grad_stats | (uintptr_t)grad_scaling) & 3))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: grad_stats and grad_scaling must be 4-byte aligned pointers");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  RegLossArgs R;
+  const RegSegDev* table;
+  if (int rc = reg_loss_prepare(scaling, n_scaling, scale_activated, segments, num_segments, opacity_activated, radii,
+                                n_radii, lambda_scale_flatten, lambda_opacity_sparse, workspace, true,
+                                grad_scaling != nullptr, 1, stream, R, table))
+    return rc;
+  if (!R.scale_on && !R.opacity_on) return GRPG_OK;
+  launch_reg_loss_backward(stream, R, table, grad_stats, (const char*)workspace, R.scale_on ? grad_scaling : nullptr);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+// ---- PSNR (metrics.hip) ----
+size_t grpg_psnr_workspace_bytes(void) { return psnr_workspace_bytes(); }
+
+int grpg_psnr_forward(int C, int height, int width, const float* img1, const float* img2, const unsigned char* mask,
+                      float* stats, void* workspace, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (C < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: C must be at least 1");
+  if (int rc = loss_plane_check("psnr", height, width)) return rc;
+  if (!img1 || !img2 || !stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: NULL img1 / img2 / stats");
+  if (((uintptr_t)img1 | (uintptr_t)img2 | (uintptr_t)stats) & 3)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: img1, img2 and stats must be 4-byte aligned");
+  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: NULL workspace");
+  if ((uintptr_t)workspace & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: workspace must be 16-byte aligned");
+  launch_psnr_forward((hipStream_t)hip_stream, C, height, width, img1, img2, mask, stats, (char*)workspace);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
 int grpg_debug_export(int P, int R, int width, int height, const char* geom_buffer,
                       const char* binning_buffer, const char* image_buffer, uint64_t* keys_sorted,
                       uint32_t* point_list, uint32_t* ranges, uint32_t* n_contrib, float* means2D,

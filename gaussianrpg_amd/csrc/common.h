@@ -688,6 +688,52 @@ void launch_semantic_ce_backward(hipStream_t st, int S, int H, int W, const floa
                                  int target_bytes, int mode, const float* grad_loss, const char* workspace,
                                  float* grad_sem);
 
+// fused mono-normal loss (normal_loss.hip).  normals / mono [3,H,W] float32; rot: the 3x3 rotation read through its
+// row and column element strides; mask / sky uint8 [H,W] or NULL.
+struct NormalPlanes {
+  const float* normals;
+  const float* mono;
+  const float* rot;
+  int rot_row_stride, rot_col_stride;
+  const unsigned char* mask;
+  const unsigned char* sky;
+};
+size_t normal_loss_workspace_bytes(int H, int W);
+void launch_normal_loss_forward(hipStream_t st, int H, int W, const NormalPlanes& planes, int normalize, int top_rows,
+                                float* stats, char* workspace);
+void launch_normal_loss_backward(hipStream_t st, int H, int W, const NormalPlanes& planes, int normalize,
+                                 int top_rows, const float* grad_stats, const char* workspace, float* grad_normals);
+
+// fused scale-flatten / opacity-sparse regularisers (reg_loss.hip).  The device segment table api.hip uploads into the
+// workspace: slot 0 by the forward, slot 1 (with the gradient pointers) by the backward.
+struct RegSegDev {
+  const float* x;                          // the model's raw opacity [n]
+  float* grad;                             // its gradient [n], or NULL (forward; not wanted)
+  long long start;                         // first flat index of the composed order
+  long long n;                             // > 0
+};
+struct RegLossArgs {
+  int scale_on, opacity_on;
+  int scale_activated, opacity_activated;
+  long long n_scaling;                     // N of scaling [N,3]
+  long long n_opacity;                     // sum of the segments' n = the length of radii
+  int num_live;                            // segments with n > 0 in the device table
+  float lam_scale, lam_opacity;
+  const float* scaling;
+  const int* radii;
+};
+size_t reg_loss_workspace_bytes(int num_segments);
+size_t reg_loss_table_offset(int which, int num_segments);
+void launch_reg_loss_forward(hipStream_t st, const RegLossArgs& args, const RegSegDev* segs, float* stats,
+                             char* workspace);
+void launch_reg_loss_backward(hipStream_t st, const RegLossArgs& args, const RegSegDev* segs, const float* grad_stats,
+                              const char* workspace, float* grad_scaling);
+
+// PSNR (metrics.hip).  img1 / img2 [C,H,W] float32, mask uint8 [H,W] or NULL; stats [2]: psnr, mse.
+size_t psnr_workspace_bytes();
+void launch_psnr_forward(hipStream_t st, int C, int H, int W, const float* img1, const float* img2,
+                         const unsigned char* mask, float* stats, char* workspace);
+
 // fused multi-tensor Adam step and densification statistics (optim.hip).  The device tables api.hip uploads.
 constexpr uint32_t ADAM_CHUNK = 4096;      // elements per unit of work; a chunk never straddles two segments
 struct AdamSegmentDev {

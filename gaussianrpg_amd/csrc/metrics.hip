@@ -1,0 +1,78 @@
+// PSNR for gfx950: the reference's loss_utils.psnr (loss_utils.py:61-78), which train.py:258-262 evaluates up to
+// three times per iteration through a boolean gather,
+//   mse = mean((img1[mask] - img2[mask]) ** 2),   psnr = 20 log10(1 / sqrt(mse))
+// in one pass with no host synchronisation.  No gradient is provided: the reference calls it under torch.no_grad().
+//
+// Layout: img1 and img2 are float32 [C,H,W], channel-major; mask is uint8 [H,W] or NULL.  One thread owns one pixel
+// (lanes run along the flat pixel index): every channel load is one contiguous 256-byte row per wave at any 4-byte
+// alignment.  The differences are taken and squared in float64 (exact for float32 inputs up to the final rounding
+// of the sum), summed per workgroup into fixed slots, and one workgroup adds the slots in a fixed order: identical
+// calls give identical bits; no atomics.
+// Stats (float32 [2]): [0] psnr, [1] mse.  An empty selection gives NaN in both; identical images give mse 0 and
+// psnr +inf.  Bytes per selected pixel: 8 C + 1 with a mask.
+#include "common.h"
+#include "reduce.h"
+
+namespace grpg {
+
+namespace {
+
+constexpr int PS_THREADS = 256;
+constexpr int PS_MAX_WG = 2048;
+constexpr size_t PS_CNT_OFF = sizeof(double) * PS_MAX_WG;
+
+__global__ void __launch_bounds__(PS_THREADS)
+psnr_forward_kernel(const int C, const int n, const int nwg, const float* __restrict__ a, const float* __restrict__ b,
+                    const unsigned char* __restrict__ mask, double* __restrict__ part, unsigned int* __restrict__ cnt) {
+  __shared__ double s_red_d[PS_THREADS / 64];
+  __shared__ unsigned int s_red_u[PS_THREADS / 64];
+  double sum = 0.0;
+  unsigned int sel = 0;
+  for (long long ii = blockIdx.x * PS_THREADS + threadIdx.x; ii < n; ii += nwg * PS_THREADS) {
+    const int i = (int)ii;
+    if (mask && !mask[i]) continue;
+    for (int c = 0; c < C; c++) {
+      const size_t at = (size_t)c * (size_t)n + i;
+      const double d = (double)a[at] - (double)b[at];
+      sum += d * d;
+    }
+    sel++;
+  }
+  const double ts = block_sum(sum, s_red_d);
+  const unsigned int tn = block_sum(sel, s_red_u);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = ts;
+    cnt[blockIdx.x] = tn;
+  }
+}
+
+__global__ void __launch_bounds__(REDUCE_THREADS)
+psnr_reduce_kernel(const int C, const int nwg, const double* __restrict__ part, const unsigned int* __restrict__ cnt,
+                   float* __restrict__ stats) {
+  __shared__ double s_d[REDUCE_THREADS];
+  __shared__ unsigned long long s_u[REDUCE_THREADS];
+  const double sum = slot_sum(part, nwg, s_d);
+  unsigned long long c = 0;
+  for (int i = threadIdx.x; i < nwg; i += REDUCE_THREADS) c += cnt[i];
+  c = slot_sum(c, s_u);
+  if (threadIdx.x != 0) return;
+  const double mse = sum / ((double)c * (double)C);   // 0 / 0 = NaN for an empty selection
+  stats[0] = (float)(20.0 * log10(1.0 / sqrt(mse)));
+  stats[1] = (float)mse;
+}
+
+}  // namespace
+
+size_t psnr_workspace_bytes() { return PS_CNT_OFF + sizeof(unsigned int) * PS_MAX_WG; }
+
+void launch_psnr_forward(hipStream_t st, const int C, const int H, const int W, const float* img1, const float* img2,
+                         const unsigned char* mask, float* stats, char* workspace) {
+  const int n = H * W;
+  const int nwg = max(1, min(PS_MAX_WG, (n + PS_THREADS - 1) / PS_THREADS));
+  double* part = (double*)workspace;
+  unsigned int* cnt = (unsigned int*)(workspace + PS_CNT_OFF);
+  psnr_forward_kernel<<<nwg, PS_THREADS, 0, st>>>(C, n, nwg, img1, img2, mask, part, cnt);
+  psnr_reduce_kernel<<<1, REDUCE_THREADS, 0, st>>>(C, nwg, part, cnt, stats);
+}
+
+}  // namespace grpg

@@ -1,5 +1,5 @@
 // The fixed-order sums behind "identical calls give identical bits" of the fused losses (ssim.hip, aux_loss.hip,
-// semantic_loss.hip); device code only.  A loss kernel sums its lanes with block_sum into one slot per workgroup; a
+// semantic_loss.hip, normal_loss.hip, reg_loss.hip, metrics.hip); device code only.  A loss kernel sums its lanes with block_sum into one slot per workgroup; a
 // launch of one workgroup of REDUCE_THREADS then adds the slots with slot_sum.  No atomics.
 #pragma once
 #include <hip/hip_runtime.h>

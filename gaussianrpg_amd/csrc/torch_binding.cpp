@@ -1433,6 +1433,205 @@ torch::Tensor SemanticCeBackward(const torch::Tensor& semantic, const torch::Ten
   return grad;
 }
 
+// Fused mono-normal loss (gaussianrpg_amd/loss.py).  normals / mono: contiguous float32 [3,H,W]; wvt: the camera's
+// float32 [4,4] (or [3,3]) device tensor, any strides (read on the device); mask / sky: empty or contiguous uint8 of
+// H*W elements.  Returns (stats [4], workspace).
+namespace {
+struct NormalIn {
+  int H, W, rs, cs;
+  const unsigned char *mask, *sky;
+};
+
+NormalIn normal_args(const char* fn, const torch::Tensor& normals, const torch::Tensor& mono, const torch::Tensor& wvt,
+                     const torch::Tensor& mask, const torch::Tensor& sky, const int64_t top_rows) {
+  TORCH_CHECK(normals.defined() && mono.defined() && wvt.defined(), fn, ": undefined tensor");
+  TORCH_CHECK(normals.is_cuda() && mono.is_cuda() && wvt.is_cuda(), fn,
+              ": normals, mono_normal and world_view_transform must live on a ROCm/HIP device (no CPU path)");
+  TORCH_CHECK(normals.device() == mono.device() && normals.device() == wvt.device(), fn, ": tensors on different devices");
+  TORCH_CHECK(normals.scalar_type() == torch::kFloat32 && normals.dim() == 3 && normals.size(0) == 3 &&
+                  normals.is_contiguous(), fn, ": normals must be a contiguous float32 [3,H,W] tensor");
+  TORCH_CHECK(mono.scalar_type() == torch::kFloat32 && mono.is_contiguous() && mono.sizes() == normals.sizes(), fn,
+              ": mono_normal must be a contiguous float32 tensor of the shape of normals");
+  TORCH_CHECK(wvt.scalar_type() == torch::kFloat32 && wvt.dim() == 2 && wvt.size(0) >= 3 && wvt.size(1) >= 3, fn,
+              ": world_view_transform must be a float32 [4,4] tensor");
+  const int64_t H = normals.size(1), W = normals.size(2);
+  TORCH_CHECK(H > 0 && W > 0 && H * W <= 0x7FFFFFFFll, fn, ": H and W must be positive with H*W < 2^31");
+  TORCH_CHECK(top_rows >= 0 && top_rows <= 0x7FFFFFFFll, fn, ": top_rows must not be negative");
+  NormalIn in{(int)H, (int)W, (int)wvt.stride(0), (int)wvt.stride(1), nullptr, nullptr};
+  auto plane = [&](const torch::Tensor& m, const char* what) -> const unsigned char* {
+    if (!m.defined() || m.numel() == 0) return nullptr;
+    TORCH_CHECK(m.is_cuda() && m.device() == normals.device() && m.scalar_type() == torch::kUInt8 &&
+                    m.is_contiguous() && m.numel() == H * W,
+                fn, ": ", what, " must be a contiguous uint8 plane of H*W elements on the device of normals");
+    return m.data_ptr<uint8_t>();
+  };
+  in.mask = plane(mask, "mask");
+  in.sky = plane(sky, "sky_mask");
+  return in;
+}
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor> NormalLossForward(const torch::Tensor& normals, const torch::Tensor& mono,
+                                                           const torch::Tensor& wvt, const torch::Tensor& mask,
+                                                           const torch::Tensor& sky, const bool normalize,
+                                                           const int64_t top_rows) {
+  const NormalIn in = normal_args("normal_loss_forward", normals, mono, wvt, mask, sky, top_rows);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(normals.device());
+  torch::Tensor stats = torch::empty({4}, torch::TensorOptions().dtype(torch::kFloat32).device(normals.device()));
+  torch::Tensor ws = loss_workspace(grpg_normal_loss_workspace_bytes(in.H, in.W), normals.device());
+  loss_call("grpg_normal_loss_forward", [&](void* stream) {
+    return grpg_normal_loss_forward(in.H, in.W, normals.data_ptr<float>(), mono.data_ptr<float>(),
+                                    wvt.data_ptr<float>(), in.rs, in.cs, in.mask, in.sky, normalize ? 1 : 0,
+                                    (int)top_rows, stats.data_ptr<float>(), ws.data_ptr(), stream);
+  });
+  return std::make_tuple(stats, ws);
+}
+
+torch::Tensor NormalLossBackward(const torch::Tensor& normals, const torch::Tensor& mono, const torch::Tensor& wvt,
+                                 const torch::Tensor& mask, const torch::Tensor& sky, const bool normalize,
+                                 const int64_t top_rows, const torch::Tensor& grad_stats, const torch::Tensor& ws) {
+  const NormalIn in = normal_args("normal_loss_backward", normals, mono, wvt, mask, sky, top_rows);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(normals.device());
+  TORCH_CHECK(ws.device() == normals.device() && ws.scalar_type() == torch::kByte && ws.is_contiguous() &&
+                  (size_t)ws.numel() == grpg_normal_loss_workspace_bytes(in.H, in.W),
+              "normal_loss_backward: workspace does not match");
+  const torch::Tensor g = loss_grad_stats(grad_stats, normals.device(), 4,
+                                          "normal_loss_backward: grad_stats must have 4 elements");
+  torch::Tensor grad = torch::empty_like(normals);
+  loss_call("grpg_normal_loss_backward", [&](void* stream) {
+    return grpg_normal_loss_backward(in.H, in.W, normals.data_ptr<float>(), mono.data_ptr<float>(),
+                                     wvt.data_ptr<float>(), in.rs, in.cs, in.mask, in.sky, normalize ? 1 : 0,
+                                     (int)top_rows, g.data_ptr<float>(), ws.data_ptr(), grad.data_ptr<float>(), stream);
+  });
+  return grad;
+}
+
+// Fused scale-flatten / opacity-sparse regularisers (gaussianrpg_amd/loss.py).  scaling: empty (term off) or a
+// contiguous float32 [N,3]; opacities: one contiguous float32 [N_i,1] or [N_i] tensor per model; radii: contiguous
+// int32 of sum N_i elements.  A term is on when its lambda is > 0.  Returns (stats [4], workspace).
+namespace {
+struct RegIn {
+  torch::Device dev = torch::kCPU;
+  const float* scaling = nullptr;
+  int64_t n_scaling = 0, total = 0;
+  std::vector<grpg_reg_segment> segs;
+  const int* radii = nullptr;
+};
+
+RegIn reg_args(const char* fn, const torch::Tensor& scaling, const std::vector<torch::Tensor>& opacities,
+               const torch::Tensor& radii, const double lam_scale, const double lam_opacity) {
+  RegIn in;
+  bool any = false;
+  auto on_device = [&](const torch::Tensor& t, const char* what) {
+    TORCH_CHECK(t.defined(), fn, ": undefined ", what);
+    TORCH_CHECK(t.is_cuda(), fn, ": ", what, " must live on a ROCm/HIP device (no CPU path)");
+    TORCH_CHECK(!any || t.device() == in.dev, fn, ": tensors on different devices");
+    in.dev = t.device();
+    any = true;
+  };
+  if (lam_scale > 0) {
+    on_device(scaling, "scaling");
+    TORCH_CHECK(scaling.scalar_type() == torch::kFloat32 && scaling.dim() == 2 && scaling.size(1) == 3 &&
+                    scaling.is_contiguous(), fn, ": scaling must be a contiguous float32 [N,3] tensor");
+    in.n_scaling = scaling.size(0);
+    in.scaling = in.n_scaling ? scaling.data_ptr<float>() : nullptr;
+  }
+  if (lam_opacity > 0) {
+    on_device(radii, "radii");
+    TORCH_CHECK(radii.scalar_type() == torch::kInt32 && radii.dim() == 1 && radii.is_contiguous(), fn,
+                ": radii must be a contiguous int32 [sum N_i] tensor");
+    for (const torch::Tensor& t : opacities) {
+      on_device(t, "opacity");
+      TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.is_contiguous() &&
+                      (t.dim() == 1 || (t.dim() == 2 && t.size(1) == 1)),
+                  fn, ": every opacity tensor must be a contiguous float32 [N_i,1] or [N_i]");
+      in.segs.push_back(grpg_reg_segment{t.numel() ? t.data_ptr<float>() : nullptr, nullptr, t.numel()});
+      in.total += t.numel();
+    }
+    TORCH_CHECK(radii.numel() == in.total, fn, ": radii has ", radii.numel(), " elements, the opacities ", in.total);
+    in.radii = in.total ? radii.data_ptr<int>() : nullptr;
+  }
+  TORCH_CHECK(any, fn, ": no term is on");
+  return in;
+}
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor> RegLossForward(const torch::Tensor& scaling, const bool scale_activated,
+                                                        const std::vector<torch::Tensor>& opacities,
+                                                        const bool opacity_activated, const torch::Tensor& radii,
+                                                        const double lam_scale, const double lam_opacity) {
+  RegIn in = reg_args("reg_loss_forward", scaling, opacities, radii, lam_scale, lam_opacity);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.dev);
+  torch::Tensor stats = torch::empty({4}, torch::TensorOptions().dtype(torch::kFloat32).device(in.dev));
+  torch::Tensor ws = loss_workspace(grpg_reg_loss_workspace_bytes((int)in.segs.size()), in.dev);
+  loss_call("grpg_reg_loss_forward", [&](void* stream) {
+    return grpg_reg_loss_forward(in.scaling, in.n_scaling, scale_activated ? 1 : 0, in.segs.data(), (int)in.segs.size(),
+                                 opacity_activated ? 1 : 0, in.radii, in.total, (float)lam_scale, (float)lam_opacity,
+                                 stats.data_ptr<float>(), ws.data_ptr(), stream);
+  });
+  return std::make_tuple(stats, ws);
+}
+
+// Returns (grad_scaling: the shape of scaling, or empty when not wanted; one gradient per opacity tensor, of its
+// shape, or empty where want_opacity[i] is false).
+std::tuple<torch::Tensor, std::vector<torch::Tensor>> RegLossBackward(
+    const torch::Tensor& scaling, const bool scale_activated, const std::vector<torch::Tensor>& opacities,
+    const bool opacity_activated, const torch::Tensor& radii, const double lam_scale, const double lam_opacity,
+    const torch::Tensor& grad_stats, const torch::Tensor& ws, const bool want_scale,
+    const std::vector<bool>& want_opacity) {
+  RegIn in = reg_args("reg_loss_backward", scaling, opacities, radii, lam_scale, lam_opacity);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.dev);
+  TORCH_CHECK(ws.device() == in.dev && ws.scalar_type() == torch::kByte && ws.is_contiguous() &&
+                  (size_t)ws.numel() == grpg_reg_loss_workspace_bytes((int)in.segs.size()),
+              "reg_loss_backward: workspace does not match");
+  TORCH_CHECK(lam_opacity <= 0 || want_opacity.size() == opacities.size(),
+              "reg_loss_backward: one want_opacity flag per opacity tensor");
+  const torch::Tensor g = loss_grad_stats(grad_stats, in.dev, 4, "reg_loss_backward: grad_stats must have 4 elements");
+  auto fopts = torch::TensorOptions().dtype(torch::kFloat32).device(in.dev);
+  torch::Tensor gs = (want_scale && lam_scale > 0) ? torch::empty_like(scaling) : torch::empty({0}, fopts);
+  std::vector<torch::Tensor> go;
+  for (size_t i = 0; i < in.segs.size(); i++) {
+    go.push_back(want_opacity[i] ? torch::empty_like(opacities[i]) : torch::empty({0}, fopts));
+    if (want_opacity[i] && in.segs[i].n) in.segs[i].grad_opacity = go[i].data_ptr<float>();
+  }
+  loss_call("grpg_reg_loss_backward", [&](void* stream) {
+    return grpg_reg_loss_backward(in.scaling, in.n_scaling, scale_activated ? 1 : 0, in.segs.data(),
+                                  (int)in.segs.size(), opacity_activated ? 1 : 0, in.radii, in.total, (float)lam_scale,
+                                  (float)lam_opacity, g.data_ptr<float>(), ws.data_ptr(),
+                                  gs.numel() ? gs.data_ptr<float>() : nullptr, stream);
+  });
+  return std::make_tuple(gs, go);
+}
+
+// PSNR (gaussianrpg_amd/loss.py).  img1 / img2: contiguous float32 [C,H,W]; mask: empty or contiguous uint8 of H*W
+// elements.  Returns stats [2]: psnr, mse.
+torch::Tensor PsnrForward(const torch::Tensor& img1, const torch::Tensor& img2, const torch::Tensor& mask) {
+  TORCH_CHECK(img1.defined() && img2.defined(), "psnr: undefined tensor");
+  TORCH_CHECK(img1.is_cuda() && img2.is_cuda(), "psnr: images must live on a ROCm/HIP device (no CPU path)");
+  TORCH_CHECK(img1.device() == img2.device(), "psnr: images on different devices");
+  TORCH_CHECK(img1.scalar_type() == torch::kFloat32 && img2.scalar_type() == torch::kFloat32 && img1.dim() == 3 &&
+                  img1.sizes() == img2.sizes() && img1.is_contiguous() && img2.is_contiguous(),
+              "psnr: images must be two contiguous float32 [C,H,W] tensors of one shape");
+  const int64_t C = img1.size(0), H = img1.size(1), W = img1.size(2);
+  TORCH_CHECK(C >= 1 && C <= 0x7FFFFFFFll && H > 0 && W > 0 && H * W <= 0x7FFFFFFFll,
+              "psnr: C, H and W must be positive with H*W < 2^31");
+  const unsigned char* pm = nullptr;
+  if (mask.defined() && mask.numel() > 0) {
+    TORCH_CHECK(mask.is_cuda() && mask.device() == img1.device() && mask.scalar_type() == torch::kUInt8 &&
+                    mask.is_contiguous() && mask.numel() == H * W,
+                "psnr: mask must be a contiguous uint8 plane of H*W elements on the images' device");
+    pm = mask.data_ptr<uint8_t>();
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(img1.device());
+  torch::Tensor stats = torch::empty({2}, torch::TensorOptions().dtype(torch::kFloat32).device(img1.device()));
+  torch::Tensor ws = loss_workspace(grpg_psnr_workspace_bytes(), img1.device());
+  loss_call("grpg_psnr_forward", [&](void* stream) {
+    return grpg_psnr_forward((int)C, (int)H, (int)W, img1.data_ptr<float>(), img2.data_ptr<float>(), pm,
+                             stats.data_ptr<float>(), ws.data_ptr(), stream);
+  });
+  return stats;
+}
+
 // The tail of the training iteration (gaussianrpg_amd/optim.py): optimizer.step() of every tensor of every
 // optimizer in one launch, and the densification statistics of every model in one launch.
 namespace {
@@ -1552,6 +1751,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("semantic_ce_backward", &SemanticCeBackward, pybind11::arg("semantic"), pybind11::arg("target"),
         pybind11::arg("mode"), pybind11::arg("grad_stats"), pybind11::arg("workspace"),
         pybind11::arg("grad_out") = pybind11::none());
+  m.def("normal_loss_forward", &NormalLossForward);    // (stats [4], workspace)
+  m.def("normal_loss_backward", &NormalLossBackward);
+  m.def("reg_loss_forward", &RegLossForward);          // (stats [4], workspace)
+  m.def("reg_loss_backward", &RegLossBackward);        // (grad_scaling, [grad_opacity per model])
+  m.def("psnr_forward", &PsnrForward);                 // stats [2]: psnr, mse
   m.def("adam_step", &AdamStep);            // in place: params, exp_avgs, exp_avg_sqs
   m.def("densify_stats", &DensifyStats);    // in place: accum, denom, max_radii2D
   m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);

@@ -341,7 +341,10 @@ def train_loss(render_pkg: dict, gt_image: torch.Tensor, lidar_depth: Optional[t
                lambda_depth_lidar: float = 0.1, lambda_sky: float = 0.05, *, lambda_dssim: float = 0.0,
                mask: Optional[torch.Tensor] = None, fused_aux: bool = False,
                gt_semantic: Optional[torch.Tensor] = None, lambda_semantic: float = 0.0,
-               semantic_mode: str = "logits") -> torch.Tensor:
+               semantic_mode: str = "logits", mono_normal: Optional[torch.Tensor] = None,
+               world_view_transform: Optional[torch.Tensor] = None, lambda_normal_mono: float = 0.0,
+               scaling: Optional[torch.Tensor] = None, opacities=None, lambda_scale_flatten: float = 0.0,
+               lambda_opacity_sparse: float = 0.0) -> torch.Tensor:
     """The loss mix of train.py:110-127,164-176 that reaches the op's four outputs: L1 on rgb
     (loss_utils.l1_loss), the sky term on acc, the lidar term on depth / (acc + 1e-10) keeping the
     smallest 95 % of the errors.  (SSIM and the regularisers do not change which output
@@ -352,13 +355,31 @@ def train_loss(render_pkg: dict, gt_image: torch.Tensor, lidar_depth: Optional[t
     the reference's torch.nonzero(depth_mask).any()); the default keeps the PyTorch terms.
     lambda_semantic > 0 with gt_semantic given and S > 0 planes in render_pkg['semantic']: the semantic term of
     train.py:129-143, lambda_semantic * gaussianrpg_amd.loss.semantic_loss (fused, no host sync; semantic_mode
-    'probabilities' takes the raw planes); the defaults leave the result as it is without these keywords."""
+    'probabilities' takes the raw planes); the defaults leave the result as it is without these keywords.
+    lambda_normal_mono > 0 with mono_normal and world_view_transform given and render_pkg['normals'] present (the RAW
+    [3,H,W] planes, feature[:3] of forward_features; the kernel normalises them): the mono-normal term of
+    train.py:206-225, lambda_normal_mono * gaussianrpg_amd.loss.normal_loss with this call's mask and sky_mask.
+    lambda_scale_flatten > 0 with scaling (the background model's raw _scaling), lambda_opacity_sparse > 0 with
+    opacities (every model's raw _opacity, in composed order) and render_pkg['radii']: the regularisers of
+    train.py:190-204 from gaussianrpg_amd.loss.gaussian_reg_loss.  All fused, no host sync; the defaults leave the
+    result bit for bit as it is without these keywords."""
     loss = _train_loss_base(render_pkg, gt_image, lidar_depth, sky_mask, lambda_l1, lambda_depth_lidar, lambda_sky,
                             lambda_dssim, mask, fused_aux)
     semantic = render_pkg.get("semantic")
     if lambda_semantic > 0 and gt_semantic is not None and semantic is not None and semantic.numel() > 0:
         from .loss import semantic_loss
         loss = loss + lambda_semantic * semantic_loss(semantic, gt_semantic, mode=semantic_mode)
+    normals = render_pkg.get("normals")
+    if lambda_normal_mono > 0 and mono_normal is not None and world_view_transform is not None and normals is not None:
+        from .loss import normal_loss
+        loss = loss + lambda_normal_mono * normal_loss(normals, mono_normal, world_view_transform, mask, sky_mask)
+    scale_on = lambda_scale_flatten > 0 and scaling is not None
+    opacity_on = lambda_opacity_sparse > 0 and opacities is not None and render_pkg.get("radii") is not None
+    if scale_on or opacity_on:
+        from .loss import gaussian_reg_loss
+        loss = loss + gaussian_reg_loss(scaling=scaling, opacities=opacities, radii=render_pkg.get("radii"),
+                                        lambda_scale_flatten=lambda_scale_flatten,
+                                        lambda_opacity_sparse=lambda_opacity_sparse)[0]
     return loss
 
 

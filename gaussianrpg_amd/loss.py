@@ -47,18 +47,53 @@ labels [H,W] or [1,H,W]:
 
 A label outside [-1, S) is counted in n_bad and ignored (PyTorch raises a device assert there).  Only
 ignore_index == -1 is provided.  No host synchronisation in forward or backward.
+
+The mono-normal term of train.py (csrc/normal_loss.hip), on float32 planes [3,H,W]:
+
+  normal_loss(normals, mono_normal, world_view_transform, mask=None, sky_mask=None, *, normalize=True, top_rows=50)
+      == train.py:206-225 (normal_l1_loss + normal_cos_loss).  normalize=True takes the RAW planes (feature[:3] of
+      forward_features) and applies the renderer's F.normalize(dim=0) itself; normalize=False takes
+      render_pkg['normals'] as the reference holds it.  The rotation world_view_transform[:3,:3] is read on the device.
+      With a sky mask the selection is mask & ~sky_mask minus the first top_rows rows; without one it is mask alone
+      (squeezed: the reference's un-squeezed index raises for H > 1); without either, every pixel.
+  normal_loss_terms(...same...)
+      without a gradient: a dict of device tensors, 'normal_l1_loss', 'normal_cos_loss' (float32) and 'n_selected'
+      (exact int64).
+
+The per-Gaussian regularisers of train.py (csrc/reg_loss.hip):
+
+  scale_flatten_loss(scaling, activated=False)             == gaussians.background.scale_flatten_loss()
+      scaling: the raw _scaling, float32 [N,3] (exp is applied here); activated=True: get_scaling, used as given.
+  opacity_sparse_loss(opacities, radii, activated=False)   == train.py:197-203
+      opacities: one float32 [N_i,1] (or [N_i]) tensor or a list of them, each model's raw _opacity in composed
+      order (the sigmoid is applied here; the get_opacity concatenation never runs); radii: int32 [sum N_i], the
+      visibility filter is radii > 0, taken on the device.
+  gaussian_reg_loss(*, scaling=None, opacities=None, radii=None, lambda_scale_flatten=0.0, lambda_opacity_sparse=0.0)
+      == lambda_scale_flatten * scale_flatten + lambda_opacity_sparse * opacity_sparse in one forward and one
+      backward launch chain; returns (loss, terms), terms a dict of detached device scalars under
+      'scale_flatten_loss' / 'opacity_sparse_loss' for the terms that are on.  A lambda of 0 or a missing input turns
+      its term off (not evaluated, no gradient).
+
+  psnr(img1, img2, mask=None)                               == loss_utils.psnr (csrc/metrics.hip)
+      float32 [C,H,W] images, a [1,H,W] or [H,W] mask selecting pixels; a detached device scalar.  NO gradient is
+      provided (the reference calls it under torch.no_grad()).
+
+An empty selection (no pixel, no visible Gaussian, N == 0) gives NaN with an exactly-zero gradient, as mean() of an
+empty gather does.  No host synchronisation in any forward or backward, no atomics.
 """
 import torch
 
 from .rasterizer import _C
 
 __all__ = ["ssim", "l1_loss", "l1_ssim_loss", "aux_loss", "lidar_depth_loss", "sky_loss", "obj_acc_loss",
-           "lidar_selection", "semantic_loss", "semantic_loss_stats"]
+           "lidar_selection", "semantic_loss", "semantic_loss_stats", "normal_loss", "normal_loss_terms",
+           "scale_flatten_loss", "opacity_sparse_loss", "gaussian_reg_loss", "psnr"]
 
 
 _FLOAT = ((torch.float32,), "float32")
 _MASK = ((torch.bool, torch.uint8), "a bool (or uint8) tensor")
 _LABEL = ((torch.int64, torch.int32), "int64 or int32")
+_RADII = ((torch.int32,), "int32")
 
 
 def _tensor_of(t, name, kind=None):
@@ -360,3 +395,184 @@ def semantic_loss_stats(semantic, gt_semantic, mode="logits", ignore_index=-1):
     if labels.numel():
         out["labels"] = labels
     return out
+
+
+# ---- mono-normal term (csrc/normal_loss.hip) ----
+
+class _NormalLoss(torch.autograd.Function):
+    """[3,H,W] planes -> (stats [4]: loss, normal_l1_loss, normal_cos_loss, n; workspace)."""
+
+    @staticmethod
+    def forward(ctx, normals, mono, wvt, mask, sky, normalize, top_rows):
+        stats, ws = _C.normal_loss_forward(normals, mono, wvt, mask, sky, normalize, top_rows)
+        ctx.save_for_backward(normals, mono, wvt, mask, sky, ws)
+        ctx.cfg = (normalize, top_rows)
+        ctx.mark_non_differentiable(ws)
+        return stats, ws
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_stats, _grad_ws):
+        normals, mono, wvt, mask, sky, ws = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        if grad_stats is None:
+            grad_stats = torch.zeros(4, dtype=torch.float32, device=ws.device)
+        g = _C.normal_loss_backward(normals, mono, wvt, mask, sky, *ctx.cfg, grad_stats.contiguous(), ws)
+        return (g,) + (None,) * 6
+
+
+def _normal_run(normals, mono_normal, world_view_transform, mask, sky_mask, normalize, top_rows):
+    for t, n in ((normals, "normals"), (mono_normal, "mono_normal"), (world_view_transform, "world_view_transform")):
+        _tensor_of(t, n)
+    for t, n in ((normals, "normals"), (mono_normal, "mono_normal"), (world_view_transform, "world_view_transform")):
+        _tensor_of(t, n, _FLOAT)
+    if normals.dim() != 3 or normals.shape[0] != 3 or normals.shape[1] < 1 or normals.shape[2] < 1:
+        raise ValueError("gaussianrpg_amd.loss: normals must be [3,H,W] (got %s)" % (tuple(normals.shape),))
+    if mono_normal.shape != normals.shape:
+        raise ValueError("gaussianrpg_amd.loss: normals is %s, mono_normal is %s"
+                         % (tuple(normals.shape), tuple(mono_normal.shape)))
+    if tuple(world_view_transform.shape) != (4, 4):
+        raise ValueError("gaussianrpg_amd.loss: world_view_transform must be [4,4] (got %s)"
+                         % (tuple(world_view_transform.shape),))
+    if mono_normal.requires_grad:
+        raise ValueError("gaussianrpg_amd.loss: mono_normal requires a gradient; the fused loss differentiates only "
+                         "normals")
+    if int(top_rows) < 0:
+        raise ValueError("gaussianrpg_amd.loss: top_rows must not be negative (got %r)" % (top_rows,))
+    dev = normals.device
+    hw = (int(normals.shape[1]), int(normals.shape[2]), dev)
+    mk, _ = _aux_plane(mask, "mask", hw, True)
+    sk, _ = _aux_plane(sky_mask, "sky_mask", hw, True)
+    named = [("normals", normals), ("mono_normal", mono_normal), ("world_view_transform", world_view_transform)]
+    named += [(n, t) for n, t in (("mask", mk), ("sky_mask", sk)) if t is not None]
+    _on_device(named, dev, lambda n, t: "%s on %s, normals on %s" % (n, t.device, dev))
+    empty = torch.empty(0, dtype=torch.uint8, device=dev)
+    return _NormalLoss.apply(normals.contiguous(), mono_normal.contiguous(), world_view_transform.detach(),
+                             empty if mk is None else mk, empty if sk is None else sk, bool(normalize), int(top_rows))
+
+
+def normal_loss(normals, mono_normal, world_view_transform, mask=None, sky_mask=None, *, normalize=True, top_rows=50):
+    """train.py:206-225: normal_l1_loss + normal_cos_loss over the selected pixels, a device scalar with a gradient for
+    ``normals``.  normalize=True: normals are the raw planes and x / max(|x|, 1e-12) is applied here."""
+    return _normal_run(normals, mono_normal, world_view_transform, mask, sky_mask, normalize, top_rows)[0][0]
+
+
+def normal_loss_terms(normals, mono_normal, world_view_transform, mask=None, sky_mask=None, *, normalize=True,
+                      top_rows=50):
+    """The normal term as the device computed it, without a gradient: a dict of device tensors, 'normal_l1_loss',
+    'normal_cos_loss' (float32) and 'n_selected' (exact int64)."""
+    with torch.no_grad():
+        stats, ws = _normal_run(normals, mono_normal, world_view_transform, mask, sky_mask, normalize, top_rows)
+    return {"normal_l1_loss": stats[1], "normal_cos_loss": stats[2], "n_selected": ws[:8].view(torch.int64)[0]}
+
+
+# ---- scale-flatten and opacity-sparse regularisers (csrc/reg_loss.hip) ----
+
+class _RegLoss(torch.autograd.Function):
+    """scaling [N,3], opacities [N_i,1]..., radii -> (stats [4]: total, scale_flatten, opacity_sparse, n_visible;
+    workspace)."""
+
+    @staticmethod
+    def forward(ctx, cfg, radii, scaling, *opacities):
+        lam_s, lam_o, act_s, act_o = cfg
+        stats, ws = _C.reg_loss_forward(scaling, act_s, list(opacities), act_o, radii, lam_s, lam_o)
+        ctx.save_for_backward(radii, scaling, ws, *opacities)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(ws)
+        return stats, ws
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_stats, _grad_ws):
+        radii, scaling, ws, *opacities = ctx.saved_tensors
+        lam_s, lam_o, act_s, act_o = ctx.cfg
+        want_s = bool(ctx.needs_input_grad[2]) and lam_s > 0
+        want_o = [bool(w) and lam_o > 0 for w in ctx.needs_input_grad[3:]]
+        if not (want_s or any(want_o)):
+            return (None,) * (3 + len(opacities))
+        if grad_stats is None:
+            grad_stats = torch.zeros(4, dtype=torch.float32, device=ws.device)
+        gs, go = _C.reg_loss_backward(scaling, act_s, list(opacities), act_o, radii, lam_s, lam_o,
+                                      grad_stats.contiguous(), ws, want_s, want_o)
+        return (None, None, gs if want_s else None) + tuple(g if w else None for g, w in zip(go, want_o))
+
+
+def _reg_run(scaling, scale_activated, opacities, radii, opacity_activated, lambda_scale_flatten,
+             lambda_opacity_sparse):
+    lam_s, lam_o = float(lambda_scale_flatten), float(lambda_opacity_sparse)
+    scale_on = lam_s > 0 and scaling is not None
+    opacity_on = lam_o > 0 and opacities is not None and radii is not None
+    if not (scale_on or opacity_on):
+        raise ValueError("gaussianrpg_amd.loss: no regulariser is on (every lambda is 0 or its input is missing)")
+    named = []
+    if scale_on:
+        _tensor_of(scaling, "scaling", _FLOAT)
+        if scaling.dim() != 2 or scaling.shape[1] != 3:
+            raise ValueError("gaussianrpg_amd.loss: scaling must be [N,3] (got %s)" % (tuple(scaling.shape),))
+        named.append(("scaling", scaling))
+    ops = []
+    if opacity_on:
+        ops = [opacities] if isinstance(opacities, torch.Tensor) else list(opacities)
+        for i, t in enumerate(ops):
+            _tensor_of(t, "opacities[%d]" % i, _FLOAT)
+            if not (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1)):
+                raise ValueError("gaussianrpg_amd.loss: opacities[%d] must be [N,1] or [N] (got %s)"
+                                 % (i, tuple(t.shape)))
+            named.append(("opacities[%d]" % i, t))
+        _tensor_of(radii, "radii", _RADII)
+        total = sum(int(t.shape[0]) for t in ops)
+        if radii.dim() != 1 or int(radii.shape[0]) != total:
+            raise ValueError("gaussianrpg_amd.loss: radii is %s, the opacities hold %d Gaussians"
+                             % (tuple(radii.shape), total))
+        named.append(("radii", radii))
+    dev = named[0][1].device
+    _on_device(named, dev, lambda n, t: "%s on %s, %s on %s" % (n, t.device, named[0][0], dev))
+    s = scaling.contiguous() if scale_on else torch.empty(0, device=dev)
+    r = radii.contiguous() if opacity_on else torch.empty(0, dtype=torch.int32, device=dev)
+    stats, _ = _RegLoss.apply((lam_s if scale_on else 0.0, lam_o if opacity_on else 0.0, bool(scale_activated),
+                               bool(opacity_activated)), r, s, *[t.contiguous() for t in ops])
+    return stats, (scale_on, opacity_on)
+
+
+def scale_flatten_loss(scaling, activated=False):
+    """gaussian_model.py:271-280: mean|s1| + mean|s2/s3 + s3/s2 - 2| over the stably sorted, clamped scales of every
+    Gaussian.  scaling: the raw _scaling [N,3] (exp applied here); activated=True: get_scaling."""
+    return _reg_run(scaling, activated, None, None, False, 1.0, 0.0)[0][1]
+
+
+def opacity_sparse_loss(opacities, radii, activated=False):
+    """train.py:197-203: mean over the visible Gaussians (radii > 0) of -(o log o + (1 - o) log(1 - o)),
+    o = clamp(sigmoid(x), 1e-6, 1 - 1e-6).  opacities: one raw _opacity tensor or a list, one per model."""
+    return _reg_run(None, False, opacities, radii, activated, 0.0, 1.0)[0][2]
+
+
+def gaussian_reg_loss(*, scaling=None, opacities=None, radii=None, lambda_scale_flatten=0.0,
+                      lambda_opacity_sparse=0.0):
+    """lambda_scale_flatten * scale_flatten + lambda_opacity_sparse * opacity_sparse (train.py:190-204).
+    Returns (loss, terms); terms holds detached device scalars of the terms that are on."""
+    stats, on = _reg_run(scaling, False, opacities, radii, False, lambda_scale_flatten, lambda_opacity_sparse)
+    terms = {name: stats[i].detach() for i, name, flag in
+             ((1, "scale_flatten_loss", on[0]), (2, "opacity_sparse_loss", on[1])) if flag}
+    return stats[0], terms
+
+
+# ---- PSNR (csrc/metrics.hip) ----
+
+def psnr(img1, img2, mask=None):
+    """loss_utils.psnr: 20 log10(1 / sqrt(mse)), mse the mean of (img1 - img2)^2 over the selected elements; NaN for
+    an empty selection, inf for identical images.  A detached device scalar: no gradient is provided."""
+    for t, n in ((img1, "img1"), (img2, "img2")):
+        _tensor_of(t, n)
+    for t, n in ((img1, "img1"), (img2, "img2")):
+        _tensor_of(t, n, _FLOAT)
+    if img1.dim() != 3 or img1.shape != img2.shape or img1.numel() == 0:
+        raise ValueError("gaussianrpg_amd.loss: psnr takes two [C,H,W] images of one shape (got %s and %s)"
+                         % (tuple(img1.shape), tuple(img2.shape)))
+    dev = img1.device
+    mk, _ = _aux_plane(mask, "mask", (int(img1.shape[1]), int(img1.shape[2]), dev), True)
+    _on_device([("img1", img1), ("img2", img2)] + ([("mask", mk)] if mk is not None else []), dev,
+               lambda n, t: "%s on %s, img1 on %s" % (n, t.device, dev))
+    with torch.no_grad():
+        return _C.psnr_forward(img1.detach().contiguous(), img2.detach().contiguous(),
+                               torch.empty(0, dtype=torch.uint8, device=dev) if mk is None else mk)[0]

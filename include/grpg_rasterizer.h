@@ -809,6 +809,100 @@ GRPG_API int grpg_semantic_ce_backward(int S, int height, int width, const float
                                        const void* workspace, float* grad_sem, void* hip_stream);
 
 /*
+ * Fused mono-normal loss (no counterpart in the extension; replaces the PyTorch code of train.py:206-225 and, with
+ * normalize != 0, the F.normalize(normals, dim=0) of street_gaussian_renderer.py:245-246 in front of it).
+ * normals / mono_normal: device fp32 [3,H,W], channel-major, contiguous, any 4-byte alignment.  rotation: device
+ * fp32, the camera's R = world_view_transform[:3,:3]; element (j,k) is read at rotation[j * rot_row_stride +
+ * k * rot_col_stride] on the device (no host copy; a contiguous [4,4] matrix has strides 4 and 1).  mask / sky_mask:
+ * NULL or device uint8 [H,W].  Selected pixels: with sky_mask, (mask) && !sky_mask && row >= top_rows; without,
+ * (mask) alone and no row cut; a NULL mask selects everything.  The reference indexes with an un-squeezed [1,H,W]
+ * mask when sky_mask is None, which raises for H > 1; the squeezed mask is taken here.
+ * Per selected pixel, fp32: n = normals / max(|normals|_2, 1e-12) (normals itself with normalize == 0),
+ * gt = mono_normal @ R^T, l1 += sum_c |n_c - gt_c|, cos += 1 - sum_c n_c gt_c.
+ * grpg_normal_loss_forward writes stats[4] (device fp32): [0] loss = [1] + [2], [1] normal_l1_loss = l1 / (3 n),
+ * [2] normal_cos_loss = cos / n, [3] n.  n == 0 gives NaN in [0..2], as mean() of an empty gather does.  workspace:
+ * device memory of grpg_normal_loss_workspace_bytes(H, W) bytes, 16-byte aligned, kept unchanged from a forward to
+ * its backward; its first 8 bytes hold n as an exact int64.
+ * grpg_normal_loss_backward: the same arguments as the forward; grad_stats (device fp32 [4], entries 0..2 are used)
+ * is read on the device together with n (no host synchronisation); writes every element of grad_normals (device
+ * fp32 [3,H,W]): dn_c = (g0 + g1) sign(n_c - gt_c) / (3 n) - (g0 + g2) gt_c / n with sign(0) = 0, chained through the
+ * normalise as dx = (dn - n (n . dn)) / |x| where |x| >= 1e-12 and dx = dn / 1e-12 below it (torch's clamp_min);
+ * exactly 0 at unselected pixels and everywhere when n == 0.
+ * Both run asynchronously on hip_stream; no atomics: identical calls give identical bits.  Purely additive exports:
+ * GRPG_ABI_VERSION stays 7.  The size query needs no device (0 for bad sizes).  Returns GRPG_OK, GRPG_ERR_NO_DEVICE
+ * without a device, GRPG_ERR_INVALID_ARGUMENT for bad sizes, a negative top_rows or a NULL or misaligned pointer.
+ */
+GRPG_API size_t grpg_normal_loss_workspace_bytes(int height, int width);
+GRPG_API int grpg_normal_loss_forward(int height, int width, const float* normals, const float* mono_normal,
+                                      const float* rotation, int rot_row_stride, int rot_col_stride,
+                                      const unsigned char* mask, const unsigned char* sky_mask, int normalize,
+                                      int top_rows, float* stats, void* workspace, void* hip_stream);
+GRPG_API int grpg_normal_loss_backward(int height, int width, const float* normals, const float* mono_normal,
+                                       const float* rotation, int rot_row_stride, int rot_col_stride,
+                                       const unsigned char* mask, const unsigned char* sky_mask, int normalize,
+                                       int top_rows, const float* grad_stats, const void* workspace,
+                                       float* grad_normals, void* hip_stream);
+
+/*
+ * Fused per-Gaussian regularisers (no counterpart in the extension; replace the PyTorch code of train.py:190-194 with
+ * gaussian_model.py:271-280, the scale-flatten term, and of train.py:196-204, the opacity-sparse term).
+ * A term is on when its lambda is > 0.
+ * Scale flatten: scaling is device fp32 [n_scaling,3], the raw _scaling (exp is applied here; scale_activated != 0:
+ * used as given).  Per Gaussian the three values are sorted ascending (stable: equal values keep index order),
+ * s1 = clamp(s1, 0, 30), s2 = clamp(s2, 1e-5, 30), s3 = clamp(s3, 1e-5, 30), term = |s1| + |s2/s3 + s3/s2 - 2|,
+ * the second part evaluated as (s2 - s3)^2 / (s2 s3), the same value without the cancellation;
+ * scale_flatten_loss = mean of the terms (NaN for n_scaling == 0).
+ * Opacity sparse: segments is a HOST array, one entry per model in composed order: opacity, the model's raw _opacity
+ * (device fp32 [n]; the sigmoid is applied here; opacity_activated != 0: used as given), and grad_opacity (backward
+ * only).  radii: device int32 [n_radii], n_radii == the sum of the segments' n; Gaussian j is visible when
+ * radii[j] > 0.  Per visible Gaussian o = clamp(sigmoid(x), 1e-6, 1 - 1e-6), term = -(o log o + (1-o) log(1-o));
+ * opacity_sparse_loss = mean over the visible ones (NaN when none is).  Segments with n == 0 are accepted.
+ * grpg_reg_loss_forward writes stats[4] (device fp32): [0] lambda_scale_flatten * [1] + lambda_opacity_sparse * [2]
+ * over the terms that are on, [1] scale_flatten_loss, [2] opacity_sparse_loss, [3] n_visible.  workspace: device memory
+ * of grpg_reg_loss_workspace_bytes(num_segments) bytes, 16-byte aligned, kept from a forward to its backward; its first
+ * 8 bytes hold n_visible as an exact int64, and it holds the device copies of the segment table, uploaded
+ * asynchronously on hip_stream from pinned staging (the ring of grpg_adam_step: no host synchronisation).
+ * grpg_reg_loss_backward: the same arguments; grad_stats (device fp32 [4], entries 0..2 are used); writes every
+ * element of grad_scaling (device fp32 [n_scaling,3]; NULL: not wanted) and of every segment's grad_opacity (device
+ * fp32 [n]; NULL: not wanted), exact zeros for invisible Gaussians and for clamped values: through the permutation, the
+ * clamps (passing where min <= x <= max), the abs (sign(0) = 0), the exp and the sigmoid.  It writes its own
+ * segment table into the workspace and nothing else of it.
+ * One forward launch plus a one-workgroup fixed-order reduce, one backward launch over all models; no atomics:
+ * identical calls give identical bits.  Purely additive exports: GRPG_ABI_VERSION stays 7.  The size query needs no
+ * device (0 for a negative count).  Returns GRPG_OK, GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT
+ * for a negative count, n_radii != sum n, more than 2^31 - 1 Gaussians, a NULL array with n > 0 or a misaligned
+ * pointer (checked before anything is queued).
+ */
+typedef struct grpg_reg_segment {
+  const float* opacity;
+  float* grad_opacity;
+  long long n;
+} grpg_reg_segment;
+GRPG_API size_t grpg_reg_loss_workspace_bytes(int num_segments);
+GRPG_API int grpg_reg_loss_forward(const float* scaling, long long n_scaling, int scale_activated,
+                                   const grpg_reg_segment* segments, int num_segments, int opacity_activated,
+                                   const int* radii, long long n_radii, float lambda_scale_flatten,
+                                   float lambda_opacity_sparse, float* stats, void* workspace, void* hip_stream);
+GRPG_API int grpg_reg_loss_backward(const float* scaling, long long n_scaling, int scale_activated,
+                                    const grpg_reg_segment* segments, int num_segments, int opacity_activated,
+                                    const int* radii, long long n_radii, float lambda_scale_flatten,
+                                    float lambda_opacity_sparse, const float* grad_stats, void* workspace,
+                                    float* grad_scaling, void* hip_stream);
+
+/*
+ * PSNR (no counterpart in the extension; replaces loss_utils.py:61-78, which train.py:258-262 evaluates through a
+ * boolean gather).  img1 / img2: device fp32 [C,H,W], contiguous, any 4-byte alignment; mask: NULL or device uint8
+ * [H,W] selecting pixels.  Writes stats[2] (device fp32): [0] 20 log10(1 / sqrt(mse)), [1] mse = the mean of
+ * (img1 - img2)^2 over the selected elements, accumulated in fp64.  An empty selection gives NaN, identical images
+ * +inf.  No gradient is provided.  workspace: grpg_psnr_workspace_bytes() bytes of device memory, 16-byte aligned.
+ * One pass plus a one-workgroup fixed-order reduce on hip_stream; identical calls give identical bits.  Errors as
+ * the entries above.
+ */
+GRPG_API size_t grpg_psnr_workspace_bytes(void);
+GRPG_API int grpg_psnr_forward(int C, int height, int width, const float* img1, const float* img2,
+                               const unsigned char* mask, float* stats, void* workspace, void* hip_stream);
+
+/*
  * The tail of the training iteration (no counterpart in the extension; replace the PyTorch code of
  * gaussian_model.py:316-317 optimizer.step() and street_gaussian_model.py:555-578 set_max_radii2D /
  * add_densification_stats).
