@@ -75,14 +75,14 @@ def test_seamless_lookup_is_continuous_across_edges():
     assert np.abs(got - ref).max() < 6e-3
 
 
-def _camera(Wd, Hd, yaw=0.3, pitch=-0.25):
+def _camera(Wd, Hd, yaw=0.3, pitch=-0.25, focal=0.55):
     cy, sy, cp, sp = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch)
     Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
     Rx = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]])
     w2c = torch.eye(4)
     w2c[:3, :3] = torch.tensor(Rx @ Ry, dtype=torch.float32)
     w2c[:3, 3] = torch.tensor([0.3, -1.2, 2.0])
-    K = torch.tensor([[0.55 * Wd, 0.0, Wd / 2.0], [0.0, 0.55 * Wd, Hd / 2.0], [0.0, 0.0, 1.0]])
+    K = torch.tensor([[focal * Wd, 0.0, Wd / 2.0], [0.0, focal * Wd, Hd / 2.0], [0.0, 0.0, 1.0]])
     return K, w2c
 
 
