@@ -153,6 +153,9 @@ EXPERIMENT_VARIANTS = {
     "dstrace": {"sort.hip": ["-DGRPG_DS_TRACE"]},
     # per-workgroup life of the point-list fill (tools/fill_trace.py)
     "filltrace": {"hier_binning.hip": ["-DGRPG_FILL_TRACE"]},
+    # the render's rectangle cull: batches with a full / a shrunk live box and what the cull removes in each,
+    # per path of the launch (tools/cull_count.py)
+    "cullcount": {"render_fwd.hip": ["-DGRPG_CULL_COUNT"]},
 }
 
 

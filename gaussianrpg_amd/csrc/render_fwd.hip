@@ -24,7 +24,9 @@
 //     entry whose mask concerns the wave.  The reference bins by the 3-sigma bounding SQUARE, so
 //     about 2/3 of the (quarter, entry) pairs are dead.
 //   * Surviving records are culled once more against the bounding box of the wave's still-LIVE
-//     pixels (shrinks as pixels saturate), compacted with ballot + popcount into the wave's
+//     pixels (shrinks as pixels saturate; while it is the wave's whole rectangle the mask has
+//     answered the question already and the cull is skipped: box_is_full), compacted with
+//     ballot + popcount into the wave's
 //     private LDS slice, and only those are evaluated, G at a time (independent alpha chains for
 //     ILP, then the in-order blend).  Decisions per pixel are unchanged: both culls only remove
 //     splats that every pixel of the rectangle would reject.
@@ -99,6 +101,52 @@ __device__ __forceinline__ MaskBox mask_box(const uint64_t m) {
   b.c0 = (int)__builtin_ctz(cols);
   b.c1 = 31 - (int)__builtin_clz(cols);
   return b;
+}
+// The live box is still the wave's whole 16 x ROWS rectangle (wave-uniform).  Then the rectangle cull asks what the
+// fill already answered when it set the entry's quarter bit -- does the alpha >= 1 / 255 ellipse reach this
+// rectangle? (blend_math.h quarter_reach_mask; a light wave's rectangle is the four quarters together) -- and a record
+// is only ever loaded for an entry whose bit is set: the cull is skipped (keep_entry).  Measured on the bench frame
+// (tools/cull_count.py): 80 % of the batches run with a full box, and the cull removed 0.01 entries per such batch.
+// Exact either way: the cull only removes splats that every live pixel rejects.
+__device__ __forceinline__ bool box_is_full(const int c0, const int c1, const int r0, const int r1, const int rows) {
+  return c0 == 0 && c1 == 15 && r0 == 0 && r1 == rows - 1;
+}
+
+// Experiment build -DGRPG_CULL_COUNT (build.py EXPERIMENT_VARIANTS "cullcount", tools/cull_count.py): how many
+// batches run with a full and with a shrunk live box, and how many entries the rectangle cull removes in each --
+// per path of the launch.  The cull runs on every batch in this build (that is what is counted); frames are unchanged.
+enum CullPath { CULL_LIGHT = 0, CULL_QUARTER = 1, CULL_PRODUCER = 2 };
+#ifdef GRPG_CULL_COUNT
+constexpr bool CULL_COUNTED = true;
+__device__ unsigned long long g_cull_count[3][4];   // [path][batches full, batches shrunk, culled full, culled shrunk]
+struct CullCount {   // per wave (wave-uniform values), added once at the wave's end
+  uint32_t bf = 0u, bs = 0u, cf = 0u, cs = 0u;
+  __device__ __forceinline__ void batch(const bool full, const uint64_t in_m, const uint64_t keep_m) {
+    const uint32_t culled = (uint32_t)__popcll(in_m & ~keep_m);
+    bf += full ? 1u : 0u; bs += full ? 0u : 1u;
+    cf += full ? culled : 0u; cs += full ? 0u : culled;
+  }
+  __device__ __forceinline__ void flush(const CullPath p, const int lane) const {
+    if (lane < 4) {
+      const uint32_t v = lane == 0 ? bf : lane == 1 ? bs : lane == 2 ? cf : cs;
+      if (v != 0u) (void)__hip_atomic_fetch_add(&g_cull_count[p][lane], (unsigned long long)v, __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_AGENT);   // result unused: no return value
+    }
+  }
+};
+#else
+constexpr bool CULL_COUNTED = false;
+struct CullCount {
+  __device__ __forceinline__ void batch(const bool, const uint64_t, const uint64_t) {}
+  __device__ __forceinline__ void flush(const CullPath, const int) const {}
+};
+#endif
+
+// Does entry `in` (a lane's record of the batch) stay in the batch?  full: box_is_full, a scalar branch.
+__device__ __forceinline__ bool keep_entry(const bool in, const bool full, const float4 a, const float4 b,
+                                           const float rx0, const float rx1, const float ry0, const float ry1) {
+  if (full && !CULL_COUNTED) return in;
+  return in && !splat_misses_rect(a.x, a.y, b.x, b.y, b.z, a.w, rx0, rx1, ry0, ry1);
 }
 
 template <int PX>
@@ -198,10 +246,12 @@ __device__ __forceinline__ float blend_one(WavePix<PX>& s, const int k, const ui
 // LDS slot of a compacted survivor, light path (REC_F4 = 3 float4):
 //   [0] gx, gy, opacity, list position   [1] A, B, C (pre-scaled conic, blend_math.h), -
 //   [2] r, g, b, depth
+// POS = false (evaluation frames: nothing reads n_contrib or checkpoints): no list position is computed or stored.
+template <bool POS = true>
 __device__ __forceinline__ void store_slot(float4* __restrict__ my, const int slot, const float4 a,
                                            const float4 b, const float4 c, const uint32_t pos) {
   const SplatQ q = splat_q(b.x, b.y, b.z);
-  my[slot * REC_F4 + 0] = make_float4(a.x, a.y, a.w, __uint_as_float(pos));
+  my[slot * REC_F4 + 0] = make_float4(a.x, a.y, a.w, POS ? __uint_as_float(pos) : 0.f);
   my[slot * REC_F4 + 1] = make_float4(q.A, q.B, q.C, 0.f);
   my[slot * REC_F4 + 2] = make_float4(b.w, c.x, c.y, a.z);
 }
@@ -284,8 +334,11 @@ __device__ __forceinline__ bool blend_group(WavePix<PX>& s, const float4* __rest
 // per packed instruction.  LDS block of a pair (PAIR_F4 = 6 float4, same 48 B per splat):
 //   [0] gx0 gx1 gy0 gy1   [1] A0 A1 B0 B1   [2] C0 C1 op0 op1
 //   [3] r0 g0 b0 depth0   [4] r1 g1 b1 depth1   [5] pos0 pos1 - -
+// POS = false (evaluation frames): the position words are neither written nor read -- they would travel FILL ->
+// ring -> POP -> pair block for nothing, and the compiler cannot drop LDS traffic another lane might read.
 constexpr int PAIR_F4 = 2 * REC_F4;
 
+template <bool POS = true>
 __device__ __forceinline__ void store_pair_half(float4* __restrict__ my, const int slot,
                                                 const float gx, const float gy, const SplatQ q,
                                                 const float op, const float4 col, const uint32_t pos) {
@@ -293,7 +346,7 @@ __device__ __forceinline__ void store_pair_half(float4* __restrict__ my, const i
   float* f = reinterpret_cast<float*>(blk) + (slot & 1);
   f[0] = gx; f[2] = gy; f[4] = q.A; f[6] = q.B; f[8] = q.C; f[10] = op;
   blk[3 + (slot & 1)] = col;
-  f[20] = __uint_as_float(pos);
+  if (POS) f[20] = __uint_as_float(pos);
 }
 
 // The accept half of a quad: alpha and the lanes that take the splat, for the four slots of blk
@@ -700,12 +753,16 @@ __device__ __forceinline__ void blend_rect(float4* __restrict__ my, const int la
   uint64_t prev_alive = ~0ull;
 
   WavePix<PX> st;
+  uint64_t outside = 0ull;
 #pragma unroll
   for (int k = 0; k < PX; k++) {
     st.T[k] = 1.0f; st.CrCg[k] = (v2f){0.f, 0.f}; st.CbD[k] = (v2f){0.f, 0.f};
     st.last[k] = 0;
     st.done[k] = lanes(!(px < W && (py0 + k) < H));
+    outside |= st.done[k];
   }
+  bool box_full = outside == 0ull;   // (a wave with pixels outside the image recomputes its box in the first batch)
+  CullCount cc;
 
   // Software pipeline over batches of 64 list entries: while batch i is blended, the records of
   // batch i+1 and the ids of batch i+2 are in flight (the id -> record gather is a dependent pair
@@ -751,6 +808,7 @@ __device__ __forceinline__ void blend_rect(float4* __restrict__ my, const int la
         }
       }
       rx0 = (float)(x0 + c0); rx1 = (float)(x0 + c1); ry0 = (float)(y0 + r0); ry1 = (float)(y0 + r1);
+      box_full = box_is_full(c0, c1, r0, r1, 4 * PX);
     }
     const uint32_t n = min((uint32_t)WAVE, r_end - base);
     const float4 a = a_n, b = b_n, c = c_n;
@@ -764,12 +822,13 @@ __device__ __forceinline__ void blend_rect(float4* __restrict__ my, const int la
     }
     if (base + 2 * WAVE + (uint32_t)lane < r_end)      // ids of the batch after that
       id_n2 = point_list[base + 2 * WAVE + lane];
-    const bool keep = ((uint32_t)lane < n) && live &&
-                      !splat_misses_rect(a.x, a.y, b.x, b.y, b.z, a.w, rx0, rx1, ry0, ry1);
+    const bool in = ((uint32_t)lane < n) && live;
+    const bool keep = keep_entry(in, box_full, a, b, rx0, rx1, ry0, ry1);
     const uint64_t mask = __ballot(keep);
     const int cnt = (int)__popcll(mask);
+    if (CULL_COUNTED) cc.batch(box_full, __ballot(in), mask);
     if (keep)   // list positions are 1-based (n_contrib convention of the reference)
-      store_slot(my, (int)__popcll(mask & lanemask_lt()), a, b, c, base - r_begin + 1 + (uint32_t)lane);
+      store_slot<WRITE_AUX>(my, (int)__popcll(mask & lanemask_lt()), a, b, c, base - r_begin + 1 + (uint32_t)lane);
     __builtin_amdgcn_wave_barrier();
 
     {
@@ -782,6 +841,7 @@ __device__ __forceinline__ void blend_rect(float4* __restrict__ my, const int la
     }
     __builtin_amdgcn_wave_barrier();
   }
+  cc.flush(CULL_LIGHT, lane);
 
   uint32_t npix = 0u;
 #pragma unroll
@@ -867,6 +927,7 @@ struct ListStream {
   // list order: lane-major, then the lane's four entries.
   // wmask / wval: an entry must additionally satisfy (entry & wmask) == wval -- a layered frame's "objects only"
   // (LAYER_BIT, LAYER_BIT) and "no objects" (LAYER_BIT, 0) phases; (0, 0) keeps everything.
+  template <bool POS>
   __device__ __forceinline__ void append(const uint4 v, const uint32_t e0, uint32_t* __restrict__ qid,
                                          uint32_t* __restrict__ qpos, const uint32_t bit, const uint32_t head,
                                          uint32_t& count, const uint64_t lt, const uint32_t wmask,
@@ -879,27 +940,29 @@ struct ListStream {
     uint32_t sl = head + count + (uint32_t)__popcll(m0 & lt) + (uint32_t)__popcll(m1 & lt) +
                   (uint32_t)__popcll(m2 & lt) + (uint32_t)__popcll(m3 & lt);
     const uint32_t p0 = e0 - r_begin + 1u;   // 1-based position in the tile's list
-    if (k0) { qid[sl & (QCAP - 1)] = v.x & ID_MASK; qpos[sl & (QCAP - 1)] = p0; sl++; }
-    if (k1) { qid[sl & (QCAP - 1)] = v.y & ID_MASK; qpos[sl & (QCAP - 1)] = p0 + 1u; sl++; }
-    if (k2) { qid[sl & (QCAP - 1)] = v.z & ID_MASK; qpos[sl & (QCAP - 1)] = p0 + 2u; sl++; }
-    if (k3) { qid[sl & (QCAP - 1)] = v.w & ID_MASK; qpos[sl & (QCAP - 1)] = p0 + 3u; }
+    if (k0) { qid[sl & (QCAP - 1)] = v.x & ID_MASK; if (POS) qpos[sl & (QCAP - 1)] = p0; sl++; }
+    if (k1) { qid[sl & (QCAP - 1)] = v.y & ID_MASK; if (POS) qpos[sl & (QCAP - 1)] = p0 + 1u; sl++; }
+    if (k2) { qid[sl & (QCAP - 1)] = v.z & ID_MASK; if (POS) qpos[sl & (QCAP - 1)] = p0 + 2u; sl++; }
+    if (k3) { qid[sl & (QCAP - 1)] = v.w & ID_MASK; if (POS) qpos[sl & (QCAP - 1)] = p0 + 3u; }
     count += (uint32_t)__popcll(m0) + (uint32_t)__popcll(m1) + (uint32_t)__popcll(m2) + (uint32_t)__popcll(m3);
   }
   // one FILL step: the next sub-window (256 entries); count is the ring's fill state, which must leave
   // room for 256 entries.  q is wave-uniform: scalar branches, each naming its register.
+  // POS = false: the ring carries ids only (evaluation frames, see store_pair_half).
+  template <bool POS>
   __device__ __forceinline__ void fill(uint32_t* __restrict__ qid, uint32_t* __restrict__ qpos, const uint32_t bit,
                                        const uint32_t head, uint32_t& count, const int lane, const uint64_t lt,
                                        const uint32_t wmask = 0u, const uint32_t wval = 0u) {
     const uint32_t e0 = wpos + 256u * q + 4u * (uint32_t)lane;
     switch (q) {
-      case 0u: append(c0, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
-      case 1u: append(c1, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
-      case 2u: append(c2, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
-      case 3u: append(c3, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
-      case 4u: append(c4, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
-      case 5u: append(c5, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
-      case 6u: append(c6, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
-      default: append(c7, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
+      case 0u: append<POS>(c0, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
+      case 1u: append<POS>(c1, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
+      case 2u: append<POS>(c2, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
+      case 3u: append<POS>(c3, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
+      case 4u: append<POS>(c4, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
+      case 5u: append<POS>(c5, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
+      case 6u: append<POS>(c6, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
+      default: append<POS>(c7, e0, qid, qpos, bit, head, count, lt, wmask, wval); break;
     }
     if (++q == (uint32_t)SUB) { q = 0; wpos += SPAN; if (wpos < r_end) refill(lane); }
   }
@@ -1013,6 +1076,8 @@ __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* _
   st.T[0] = 1.0f; st.CrCg[0] = (v2f){0.f, 0.f}; st.CbD[0] = (v2f){0.f, 0.f};
   st.last[0] = 0;
   st.done[0] = lanes(!(px < W && py < H));
+  bool box_full = st.done[0] == 0ull;   // (see blend_rect)
+  CullCount cc;
 
   uint32_t in_pos = r_begin;   // next unread list entry          (wave-uniform)
   uint32_t head = 0, count = 0;   // ring state                   (wave-uniform)
@@ -1033,6 +1098,7 @@ __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* _
       prev_alive = alive;
       const MaskBox b = mask_box(alive);
       rx0 = (float)(x0 + b.c0); rx1 = (float)(x0 + b.c1); ry0 = (float)(y0 + b.r0); ry1 = (float)(y0 + b.r1);
+      box_full = box_is_full(b.c0, b.c1, b.r0, b.r1, 4);
     }
 
     // ---- FILL ----
@@ -1054,7 +1120,7 @@ __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* _
         if (keep) {
           const uint32_t slot = (head + count + (uint32_t)__popcll(m & lt)) & (QCAP - 1);
           qid[slot] = v[q] & ID_MASK;
-          qpos[slot] = i - r_begin + 1;   // 1-based position in the tile's list
+          if (AUX) qpos[slot] = i - r_begin + 1;   // 1-based position in the tile's list
         }
         count += (uint32_t)__popcll(m);
       }
@@ -1071,7 +1137,7 @@ __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* _
     if ((uint32_t)lane < nn) {
       const uint32_t slot = (head + lane) & (QCAP - 1);
       id_n = qid[slot] & cf.id_and;
-      pos_n = qpos[slot];
+      if (AUX) pos_n = qpos[slot];
       rec.load(id_n, a_n, b_n, c_n);
     }
     head = (head + nn) & (QCAP - 1);
@@ -1079,21 +1145,21 @@ __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* _
 
     // ---- BLEND the previous batch while the gather is in flight ----
     if (ncur > 0) {
-      const bool keep = ((uint32_t)lane < ncur) &&
-                        !splat_misses_rect(a.x, a.y, b.x, b.y, b.z, a.w, rx0, rx1, ry0, ry1);
+      const bool keep = keep_entry((uint32_t)lane < ncur, box_full, a, b, rx0, rx1, ry0, ry1);
       const uint64_t mask = __ballot(keep);
       const int cnt = (int)__popcll(mask);
+      if (CULL_COUNTED) cc.batch(box_full, __ballot((uint32_t)lane < ncur), mask);
       const SplatQ sq = splat_q(b.x, b.y, b.z);
       // wave-uniform: no survivor of this batch can produce power > 0 (all but pathological conics)
       const bool batch_safe = __ballot(keep && !splat_power_never_positive(sq)) == 0ull;
       if (keep) {
-        store_pair_half(my, (int)__popcll(mask & lt), a.x, a.y, sq, a.w,
-                        make_float4(b.w, c.x, c.y, a.z), pos);
+        store_pair_half<AUX>(my, (int)__popcll(mask & lt), a.x, a.y, sq, a.w,
+                             make_float4(b.w, c.x, c.y, a.z), pos);
         if (NSEM > 0) sem_stage(semrows, (int)__popcll(mask & lt), sem.semantics, sem.S, idc, true);
       }
       if (lane < ((4 - (cnt & 3)) & 3)) {   // neutral pads up to a multiple of 4 (opacity 0)
         const SplatQ zq = {0.f, 0.f, 0.f};
-        store_pair_half(my, cnt + lane, 0.f, 0.f, zq, 0.f, make_float4(0.f, 0.f, 0.f, 0.f), 0u);
+        store_pair_half<AUX>(my, cnt + lane, 0.f, 0.f, zq, 0.f, make_float4(0.f, 0.f, 0.f, 0.f), 0u);
         if (NSEM > 0) sem_stage(semrows, cnt + lane, sem.semantics, sem.S, 0u, false);
       }
       __builtin_amdgcn_wave_barrier();
@@ -1110,6 +1176,7 @@ __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* _
     if (ncur == 0 && in_pos >= r_end) break;   // ring empty (count == 0 here) and list exhausted
   }
   if (AUX) ckpt_finish(ckw, lane, st, r_end - r_begin);
+  cc.flush(CULL_QUARTER, lane);
 
   if (px < W && py < H) out.template pixel<AUX>(px, py, st.T[0], st.CrCg[0], st.CbD[0], st.last[0]);
   out.arrive(x0, y0, wave_pixels_inside(px < W && py < H));
@@ -1138,6 +1205,8 @@ __device__ __forceinline__ void blend_heavy(float4* __restrict__ my, uint32_t* _
 //                         producer may read a stale or half-updated box: boxes only shrink, so any
 //                         mix of old and new bounds is a superset of the current box (the cull
 //                         stays conservative, results are unchanged).
+//   full                  the box is still the whole quarter (box_is_full): the producer skips the cull.  Only ever
+//                         goes from 1 to 0, and a stale 1 keeps more than the box would: conservative as well.
 // Same arithmetic in the same order as blend_heavy: bit-identical images.
 // Spin loops are bounded (PC_SPIN_LIMIT): a protocol error ends the wave instead of hanging -- and
 // is REPORTED: the wave raises pc_timeout in the image blob's header and the calling thread's sticky
@@ -1163,7 +1232,7 @@ __device__ __forceinline__ void pc_fail(const PCErr err, const int lane) {
 struct PCCtrl {
   uint32_t flag[2];
   uint32_t stop;
-  uint32_t pad;
+  uint32_t full;
   float box[4];
 };
 
@@ -1202,7 +1271,8 @@ __device__ __forceinline__ bool pc_wait(PCCtrl* __restrict__ ctl, const PCErr er
 // per iteration and publishes them as ONE batch when their survivors fit a buffer, the consumer keeps a
 // quad's geometry one quad ahead in registers and requests its colours before the accept arithmetic,
 // and the live box comes from the lane mask's bits (mask_box).
-template <bool WITH_SEM = false>
+// AUX = false (evaluation frames): no list positions through the ring and the pair blocks (store_pair_half).
+template <bool WITH_SEM = false, bool AUX = true>
 __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* __restrict__ buf1,
                                             uint32_t* __restrict__ qid, uint32_t* __restrict__ qpos,
                                             PCCtrl* __restrict__ ctl, const int lane,
@@ -1225,8 +1295,8 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
   const auto put = [&](float4* __restrict__ my, const bool keep, const uint64_t mask, const int base,
                        const float4 a, const float4 b, const float4 c, const uint32_t pos, const uint32_t idc) {
     if (keep) {
-      store_pair_half(my, base + (int)__popcll(mask & lt), a.x, a.y, splat_q(b.x, b.y, b.z), a.w,
-                      make_float4(b.w, c.x, c.y, a.z), pos);
+      store_pair_half<AUX>(my, base + (int)__popcll(mask & lt), a.x, a.y, splat_q(b.x, b.y, b.z), a.w,
+                           make_float4(b.w, c.x, c.y, a.z), pos);
       if (WITH_SEM) sem_stage(my == buf0 ? semrows0 : semrows1, base + (int)__popcll(mask & lt), sem.semantics, sem.S, idc, true);
     }
   };
@@ -1234,17 +1304,18 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
   const auto publish = [&](float4* __restrict__ my, const int cnt, const bool safe) {
     if (lane < ((4 - (cnt & 3)) & 3)) {
       const SplatQ zq = {0.f, 0.f, 0.f};
-      store_pair_half(my, cnt + lane, 0.f, 0.f, zq, 0.f, make_float4(0.f, 0.f, 0.f, 0.f), 0u);
+      store_pair_half<AUX>(my, cnt + lane, 0.f, 0.f, zq, 0.f, make_float4(0.f, 0.f, 0.f, 0.f), 0u);
       if (WITH_SEM) sem_stage(my == buf0 ? semrows0 : semrows1, cnt + lane, sem.semantics, sem.S, 0u, false);
     }
     pc_store(&ctl->flag[cur], ((uint32_t)cnt + 1u) | (safe ? PC_SAFE : 0u));
     cur ^= 1;
   };
   const auto buffer_free = [&]() { return pc_load(&ctl->flag[cur]) == 0u; };
+  CullCount cc;
   for (;;) {
-    if (pc_load(&ctl->stop) != 0u) return;
+    if (pc_load(&ctl->stop) != 0u) { cc.flush(CULL_PRODUCER, lane); return; }
     // ---- FILL: until two batches are queued (ring: < 128 + 256 entries <= QCAP) ----
-    while (count < 2u * WAVE && !ls.exhausted()) ls.fill(qid, qpos, bit, head, count, lane, lt, cf.wmask, cf.wval);
+    while (count < 2u * WAVE && !ls.exhausted()) ls.fill<AUX>(qid, qpos, bit, head, count, lane, lt, cf.wmask, cf.wval);
     // the ring entries written by FILL are read by OTHER lanes in POP: keep the compiler from
     // reordering the LDS accesses across this point (costs no instruction)
     __builtin_amdgcn_wave_barrier();
@@ -1255,30 +1326,33 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
     if ((uint32_t)lane < nn) {
       const uint32_t slot = (head + lane) & (QCAP - 1);
       id0n = qid[slot] & cf.id_and;
-      pos0n = qpos[slot];
+      if (AUX) pos0n = qpos[slot];
       rec.load(id0n, a0n, b0n, c0n);
     }
     if ((uint32_t)lane + WAVE < nn) {
       const uint32_t slot = (head + WAVE + lane) & (QCAP - 1);
       id1n = qid[slot] & cf.id_and;
-      pos1n = qpos[slot];
+      if (AUX) pos1n = qpos[slot];
       rec.load(id1n, a1n, b1n, c1n);
     }
     head = (head + nn) & (QCAP - 1);
     count -= nn;
     // ---- the previous iteration's records: cull against the consumer's live box, compact, publish ----
     if (ncur > 0) {
+      const bool box_full = __builtin_amdgcn_readfirstlane((int)ctl->full) != 0;
       const float rx0 = ctl->box[0], rx1 = ctl->box[1], ry0 = ctl->box[2], ry1 = ctl->box[3];
-      const bool k0 = ((uint32_t)lane < ncur) &&
-                      !splat_misses_rect(a0.x, a0.y, b0.x, b0.y, b0.z, a0.w, rx0, rx1, ry0, ry1);
-      const bool k1 = ((uint32_t)lane + WAVE < ncur) &&
-                      !splat_misses_rect(a1.x, a1.y, b1.x, b1.y, b1.z, a1.w, rx0, rx1, ry0, ry1);
+      const bool k0 = keep_entry((uint32_t)lane < ncur, box_full, a0, b0, rx0, rx1, ry0, ry1);
+      const bool k1 = keep_entry((uint32_t)lane + WAVE < ncur, box_full, a1, b1, rx0, rx1, ry0, ry1);
       const uint64_t m0 = __ballot(k0), m1 = __ballot(k1);
       const int n0 = (int)__popcll(m0), n1 = (int)__popcll(m1);
+      if (CULL_COUNTED) {   // (two batches of 64 per iteration)
+        cc.batch(box_full, __ballot((uint32_t)lane < ncur), m0);
+        if (ncur > (uint32_t)WAVE) cc.batch(box_full, __ballot((uint32_t)lane + WAVE < ncur), m1);
+      }
       const bool safe0 = __ballot(k0 && !splat_power_never_positive(splat_q(b0.x, b0.y, b0.z))) == 0ull;
       const bool safe1 = __ballot(k1 && !splat_power_never_positive(splat_q(b1.x, b1.y, b1.z))) == 0ull;
       if (n0 + n1 > 0) {
-        if (!pc_wait(ctl, err, lane, true, buffer_free)) return;
+        if (!pc_wait(ctl, err, lane, true, buffer_free)) { cc.flush(CULL_PRODUCER, lane); return; }
         float4* my = cur ? buf1 : buf0;
         if (n0 + n1 <= WAVE) {   // one batch (list order: the first half's survivors first)
           put(my, k0, m0, 0, a0, b0, c0, pos0, id0);
@@ -1287,7 +1361,7 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
         } else {                 // two batches
           put(my, k0, m0, 0, a0, b0, c0, pos0, id0);
           publish(my, n0, safe0);
-          if (!pc_wait(ctl, err, lane, true, buffer_free)) return;
+          if (!pc_wait(ctl, err, lane, true, buffer_free)) { cc.flush(CULL_PRODUCER, lane); return; }
           my = cur ? buf1 : buf0;
           put(my, k1, m1, 0, a1, b1, c1, pos1, id1);
           publish(my, n1, safe1);
@@ -1299,6 +1373,7 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
     ncur = nn;
     if (ncur == 0 && ls.exhausted()) break;
   }
+  cc.flush(CULL_PRODUCER, lane);
   if (!pc_wait(ctl, err, lane, true, buffer_free)) return;   // end-of-list marker
   pc_store(&ctl->flag[cur], PC_DONE);
 }
@@ -1374,6 +1449,7 @@ __device__ __forceinline__ void pc_consumer(const float4* __restrict__ buf0,
       if (lane == 0) {
         ctl->box[0] = (float)(x0 + b.c0); ctl->box[1] = (float)(x0 + b.c1);
         ctl->box[2] = (float)(y0 + b.r0); ctl->box[3] = (float)(y0 + b.r1);
+        if (!box_is_full(b.c0, b.c1, b.r0, b.r1, 4)) ctl->full = 0u;
       }
     }
   }
@@ -1500,7 +1576,7 @@ __device__ __forceinline__ void blend_heavy_layers(float4* __restrict__ my, uint
   ListStream<4> ls;
   ls.open(point_list, r_begin, r_end, lane);
   float4 a = make_float4(0, 0, 0, 0), b = a, c = a;
-  uint32_t pos = 0, idc = 0, ncur = 0;
+  uint32_t idc = 0, ncur = 0;   // (no list positions: a layered frame is an evaluation frame)
 
   for (;;) {
     const uint64_t live_ab = L.live_ab();
@@ -1519,16 +1595,15 @@ __device__ __forceinline__ void blend_heavy_layers(float4* __restrict__ my, uint
     }
     // ---- FILL (the ring entry keeps the class bit: ID_MASK covers bit 27) ----
     while (count < (uint32_t)WAVE && !ls.exhausted())
-      ls.fill(qid, qpos, bit, head, count, lane, lt, need_ab ? 0u : LAYER_BIT, need_ab ? 0u : LAYER_BIT);
+      ls.fill<false>(qid, qpos, bit, head, count, lane, lt, need_ab ? 0u : LAYER_BIT, need_ab ? 0u : LAYER_BIT);
     __builtin_amdgcn_wave_barrier();
     // ---- POP ----
     const uint32_t nn = min(count, (uint32_t)WAVE);
     float4 a_n = make_float4(0, 0, 0, 0), b_n = a_n, c_n = a_n;
-    uint32_t pos_n = 0, id_n = 0;
+    uint32_t id_n = 0;
     if ((uint32_t)lane < nn) {
       const uint32_t slot = (head + lane) & (QCAP - 1);
       id_n = qid[slot];
-      pos_n = qpos[slot];
       rec.load(id_n & LAYER_ID_MASK, a_n, b_n, c_n);
     }
     head = (head + nn) & (QCAP - 1);
@@ -1544,12 +1619,12 @@ __device__ __forceinline__ void blend_heavy_layers(float4* __restrict__ my, uint
       if (__ballot(keep && is_obj) != 0ull) L.fork();
       if (keep) {
         const int slot = (int)__popcll(mask & lt);
-        store_pair_half(my, slot, a.x, a.y, splat_q(b.x, b.y, b.z), a.w, make_float4(b.w, c.x, c.y, a.z), pos);
+        store_pair_half<false>(my, slot, a.x, a.y, splat_q(b.x, b.y, b.z), a.w, make_float4(b.w, c.x, c.y, a.z), 0u);
         store_slot_class(my, slot, is_obj ? 1u : 0u);
       }
       if (lane < ((4 - (cnt & 3)) & 3)) {   // neutral pads up to a multiple of 4 (opacity 0)
         const SplatQ zq = {0.f, 0.f, 0.f};
-        store_pair_half(my, cnt + lane, 0.f, 0.f, zq, 0.f, make_float4(0.f, 0.f, 0.f, 0.f), 0u);
+        store_pair_half<false>(my, cnt + lane, 0.f, 0.f, zq, 0.f, make_float4(0.f, 0.f, 0.f, 0.f), 0u);
         store_slot_class(my, cnt + lane, 0u);
       }
       __builtin_amdgcn_wave_barrier();
@@ -1560,7 +1635,7 @@ __device__ __forceinline__ void blend_heavy_layers(float4* __restrict__ my, uint
       }
       __builtin_amdgcn_wave_barrier();
     }
-    a = a_n; b = b_n; c = c_n; pos = pos_n; idc = id_n; ncur = nn;
+    a = a_n; b = b_n; c = c_n; idc = id_n; ncur = nn;
     if (ncur == 0 && ls.exhausted()) break;
   }
   L.write(out, px, py, W, H);
@@ -1709,7 +1784,8 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
     const int q = (int)pc_sub * 2 + slot;                        // quarter of the tile
     const int x0 = tx * TILE, y0 = ty * TILE + q * 4;
     if (wave < 2 && lane == 0) {   // the consumer initialises its quarter's control block
-      s_ctl[slot].flag[0] = 0u; s_ctl[slot].flag[1] = 0u; s_ctl[slot].stop = 0u; s_ctl[slot].pad = 0u;
+      s_ctl[slot].flag[0] = 0u; s_ctl[slot].flag[1] = 0u; s_ctl[slot].stop = 0u;
+      s_ctl[slot].full = (x0 + 15 < W && y0 + 3 < H) ? 1u : 0u;   // no pixel outside the image (see blend_rect)
       s_ctl[slot].box[0] = (float)x0; s_ctl[slot].box[1] = (float)(x0 + 15);
       s_ctl[slot].box[2] = (float)y0; s_ctl[slot].box[3] = (float)(y0 + 3);
     }
@@ -1725,7 +1801,7 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
           if (role == 0) LAYER_CONSUMER(0); else if (role == 1) LAYER_CONSUMER(1); else LAYER_CONSUMER(2);
 #undef LAYER_CONSUMER
         } else {
-          pc_producer<false>(s_rec[slot], s_rec[slot + 2], s_qid[wave], s_qpos[wave], &s_ctl[slot], lane, q, rb, re,
+          pc_producer<false, false>(s_rec[slot], s_rec[slot + 2], s_qid[wave], s_qpos[wave], &s_ctl[slot], lane, q, rb, re,
                              point_list, rec, pc_err, nosem, nullptr, nullptr, layer_filter(role));
         }
         return;
@@ -1738,7 +1814,7 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
                   reinterpret_cast<float*>(s_qid[wave]), reinterpret_cast<float*>(s_qpos[wave]));
       if (WRITE_AUX && q == 0) ckpt_publish_items(ck, lane, tile, re - rb);
     } else
-      pc_producer<(NSEM > 0)>(s_rec[slot], s_rec[slot + 2], s_qid[wave], s_qpos[wave], &s_ctl[slot], lane, q,
+      pc_producer<(NSEM > 0), WRITE_AUX>(s_rec[slot], s_rec[slot + 2], s_qid[wave], s_qpos[wave], &s_ctl[slot], lane, q,
                   rb, re, point_list, rec, pc_err, sem, s_sem[NSEM > 0 ? slot : 0], s_sem[NSEM > 0 ? slot + 2 : 0]);
     return;
   }
@@ -2013,3 +2089,16 @@ void launch_render_semantic(hipStream_t s, const uint2* ranges, const uint32_t* 
 }
 
 }  // namespace grpg
+
+#ifdef GRPG_CULL_COUNT
+// out[3][4] (CullPath x CullCount's four words), summed over every render launch since the last reset
+extern "C" __attribute__((visibility("default"))) int grpg_debug_cull_count(unsigned long long* out, int reset) {
+  int rc = (int)hipDeviceSynchronize();
+  if (rc == 0) rc = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(grpg::g_cull_count), sizeof(grpg::g_cull_count));
+  if (rc == 0 && reset) {
+    const unsigned long long zero[3][4] = {};
+    rc = (int)hipMemcpyToSymbol(HIP_SYMBOL(grpg::g_cull_count), zero, sizeof(zero));
+  }
+  return rc;
+}
+#endif
