@@ -61,6 +61,10 @@ HIP_UNITS = {
     "features.hip": ["-ffp-contract=off"],
     "api.hip": [],
 }
+# units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept
+# next to the object as <unit>.remarks: the render launch's occupancy is a budget the sources promise
+# (render_fwd.hip render_min_waves; tests/test_render_resources.py reads the file)
+REMARK_UNITS = ("render_fwd.hip",)
 HEADERS = ["common.h", "reduce.h", "gaussian_math.h", "blend_math.h", "compose_math.h", os.path.join(ROOT, "include", "grpg_rasterizer.h")]
 
 
@@ -78,11 +82,38 @@ def _newer(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
-def _run(cmd):
+def _run(cmd, keep=None):
+    """keep: file that receives the command's output (the compiler's remarks)"""
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if p.returncode != 0:
         raise RuntimeError("command failed: %s\n%s" % (" ".join(cmd), p.stdout))
+    if keep:
+        with open(keep, "w") as f:
+            f.write(p.stdout)
     return p.stdout
+
+
+def remarks_path(unit):
+    return os.path.join(OBJ, unit.replace(".hip", ".remarks"))
+
+
+def kernel_resources(unit="render_fwd.hip"):
+    """{mangled kernel name: {"vgprs", "agprs", "sgprs", "scratch", "occupancy", "lds"}} as hipcc reported them when
+    build_native() last compiled `unit` (one of REMARK_UNITS)."""
+    import re
+    keys = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch",
+            "Occupancy [waves/SIMD]": "occupancy", "LDS Size [bytes/block]": "lds"}
+    out, cur = {}, None
+    with open(remarks_path(unit)) as f:
+        for line in f:
+            m = re.search(r"remark:\s+([A-Za-z][^:]*): (\S+)", line)
+            if not m:
+                continue
+            if m.group(1) == "Function Name":
+                cur = out.setdefault(m.group(2), {})
+            elif cur is not None and m.group(1) in keys:
+                cur[keys[m.group(1)]] = int(m.group(2))
+    return out
 
 
 def build_native(force=False, verbose=False):
@@ -96,15 +127,17 @@ def build_native(force=False, verbose=False):
         src = os.path.join(CSRC, unit)
         obj = os.path.join(OBJ, unit.replace(".hip", ".o"))
         objs.append(obj)
-        if force or _newer(obj, [src] + hdrs + [os.path.abspath(__file__)]):
-            jobs.append([hipcc, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC",
-                         "-fvisibility=hidden", "-Wall", "-Wno-unused-function"] + extra +
-                        os.environ.get("GRPG_EXTRA_HIPCC_FLAGS", "").split() +   # experiments (-D...)
-                        ["-c", src, "-o", obj])
+        keep = remarks_path(unit) if unit in REMARK_UNITS else None
+        if force or _newer(obj, [src] + hdrs + [os.path.abspath(__file__)]) or (keep and not os.path.exists(keep)):
+            jobs.append(([hipcc, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC",
+                          "-fvisibility=hidden", "-Wall", "-Wno-unused-function"] + extra +
+                         (["-Rpass-analysis=kernel-resource-usage"] if keep else []) +
+                         os.environ.get("GRPG_EXTRA_HIPCC_FLAGS", "").split() +   # experiments (-D...)
+                         ["-c", src, "-o", obj], keep))
     if jobs:
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
-            for out in ex.map(_run, jobs):
-                if verbose and out.strip():
+            for (_, keep), out in zip(jobs, ex.map(lambda j: _run(*j), jobs)):
+                if verbose and out.strip() and not keep:
                     print(out)
     if force or jobs or _newer(LIB_PATH, objs):
         _run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB_PATH] + objs +

@@ -884,7 +884,8 @@ constexpr int FILL_Q = 4;            // list entries per lane per FILL step of t
 // (per-role wave trace, DESIGN_EXPERIMENTS.md R5.1: 1.9 us per batch for 0.7 us of work).  Here a window is SUB sub-windows of 256
 // entries, requested together with 16-byte loads (lane l owns four consecutive entries) and consumed from
 // registers: one memory latency per SUB x 256 entries.  SUB = 8 for the producers (a wave of its own with
-// registers to spare), 4 for the layered frame's quarter waves.  (The ordinary quarter waves were measured on
+// registers to spare; 4 in the plain evaluation frame, whose kernel is allocated for five waves per SIMD:
+// pc_list_sub), 4 for the layered frame's quarter waves.  (The ordinary quarter waves were measured on
 // it too: render 0.2095-0.2112 vs 0.2074-0.2104 ms on one box -- the bulk of the launch is bound by the
 // vector ALUs, they keep their 256-entry windows.)
 // ------------------------------------------------------------------------------------------
@@ -1272,7 +1273,7 @@ __device__ __forceinline__ bool pc_wait(PCCtrl* __restrict__ ctl, const PCErr er
 // quad's geometry one quad ahead in registers and requests its colours before the accept arithmetic,
 // and the live box comes from the lane mask's bits (mask_box).
 // AUX = false (evaluation frames): no list positions through the ring and the pair blocks (store_pair_half).
-template <bool WITH_SEM = false, bool AUX = true>
+template <bool WITH_SEM = false, bool AUX = true, int SUB = 8>
 __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* __restrict__ buf1,
                                             uint32_t* __restrict__ qid, uint32_t* __restrict__ qpos,
                                             PCCtrl* __restrict__ ctl, const int lane,
@@ -1286,7 +1287,7 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
   const uint32_t bit = 1u << (SUBTILE_SHIFT + quarter);
   const uint64_t lt = lanemask_lt();
   uint32_t head = 0, count = 0;
-  ListStream<8> ls;
+  ListStream<SUB> ls;
   ls.open(point_list, r_begin, r_end, lane);
   float4 a0 = make_float4(0, 0, 0, 0), b0 = a0, c0 = a0, a1 = a0, b1 = a0, c1 = a0;
   uint32_t pos0 = 0, id0 = 0, pos1 = 0, id1 = 0, ncur = 0;
@@ -1304,7 +1305,11 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
   const auto publish = [&](float4* __restrict__ my, const int cnt, const bool safe) {
     if (lane < ((4 - (cnt & 3)) & 3)) {
       const SplatQ zq = {0.f, 0.f, 0.f};
-      store_pair_half<AUX>(my, cnt + lane, 0.f, 0.f, zq, 0.f, make_float4(0.f, 0.f, 0.f, 0.f), 0u);
+      // the pad's colour: a zero the compiler cannot hoist out of the loop as FOUR registers held (and, at 96
+      // VGPRs, spilled: the kernel's only scratch) for the sake of one 16-byte store per batch
+      float z = 0.f;
+      if (SUB < 8) asm volatile("" : "+v"(z));
+      store_pair_half<AUX>(my, cnt + lane, 0.f, 0.f, zq, 0.f, make_float4(z, z, z, z), 0u);
       if (WITH_SEM) sem_stage(my == buf0 ? semrows0 : semrows1, cnt + lane, sem.semantics, sem.S, 0u, false);
     }
     pc_store(&ctl->flag[cur], ((uint32_t)cnt + 1u) | (safe ? PC_SAFE : 0u));
@@ -1315,7 +1320,7 @@ __device__ __forceinline__ void pc_producer(float4* __restrict__ buf0, float4* _
   for (;;) {
     if (pc_load(&ctl->stop) != 0u) { cc.flush(CULL_PRODUCER, lane); return; }
     // ---- FILL: until two batches are queued (ring: < 128 + 256 entries <= QCAP) ----
-    while (count < 2u * WAVE && !ls.exhausted()) ls.fill<AUX>(qid, qpos, bit, head, count, lane, lt, cf.wmask, cf.wval);
+    while (count < 2u * WAVE && !ls.exhausted()) ls.template fill<AUX>(qid, qpos, bit, head, count, lane, lt, cf.wmask, cf.wval);
     // the ring entries written by FILL are read by OTHER lanes in POP: keep the compiler from
     // reordering the LDS accesses across this point (costs no instruction)
     __builtin_amdgcn_wave_barrier();
@@ -1678,13 +1683,29 @@ __device__ __forceinline__ ClassFilter layer_filter(const int role) {
   return cf;
 }
 
-// waves per SIMD the register allocator must fit.  4 (128 VGPRs, no spills in the 4-pixel light path,
-// 112 KB of LDS per CU so that the other stream's sort workgroups can co-reside) measured slightly
-// ahead of 5 (96 VGPRs, 136 B of scratch per lane): 0.327 vs 0.333 ms, 1640 vs 1600 frames/s.
-// A frame with semantic planes (NSEM > 0) carries 16 accumulator registers per lane (MFMA) and 4 KB of
-// staged rows per wave: 3 waves per SIMD / 3 workgroups per CU.
+// Waves per SIMD the register allocator must fit, PER INSTANTIATION (hipcc's own figures are kept by the build:
+// build/obj/render_fwd.remarks, table in DESIGN.md section 5, tests/test_render_resources.py):
+//   plain evaluation frame (WRITE_AUX = false, NSEM = 0, no layers, no epilogue): 5 waves, 96 VGPRs, no scratch.
+//     Its quarter waves (90 VGPRs; 80 % of the bench frame's wave-time) and the pairs' consumer (88) fit five
+//     waves as they stand; the two side paths that pinned them at four are built smaller for this instantiation:
+//     the light path blends one splat per iteration (GPI_L = 1: 94 instead of 118 VGPRs, same products in the same
+//     order) and the producer reads the list in windows of 4 x 256 entries (pc_list_sub; 118 -> 98, the allocator
+//     closes the last two).  Five workgroups are 103 KB of a CU's LDS.
+//   frame epilogue (EPI): 4 waves (123 VGPRs) -- forced to five it spills 16 B per lane, and a five-wave kernel
+//     with scratch is a loss that was measured (round 2: 0.333 against 0.327 ms);
+//   training frame (WRITE_AUX): 4 waves (127 VGPRs), layered frames 4;
+//   semantic planes (NSEM > 0): 16 accumulator registers per lane (MFMA) and 4 KB of staged rows per wave: 3 waves
+//     per SIMD / 3 workgroups per CU.
 constexpr int RENDER_MIN_WAVES = 4;
+constexpr int RENDER_EVAL_MIN_WAVES = 5;
 constexpr int LAYERS_MIN_WAVES = 4;   // waves per SIMD the layered kernel is allocated for
+template <bool WRITE_AUX, int NSEM, bool LAYERS, bool EPI>
+constexpr int render_min_waves() {
+  return NSEM > 0 ? 3 : (LAYERS ? LAYERS_MIN_WAVES : ((WRITE_AUX || EPI) ? RENDER_MIN_WAVES : RENDER_EVAL_MIN_WAVES));
+}
+// sub-windows of 256 entries per register window of the pairs' producer (ListStream): 8 where the budget allows
+template <bool WRITE_AUX, int NSEM, bool LAYERS, bool EPI>
+constexpr int pc_list_sub() { return render_min_waves<WRITE_AUX, NSEM, LAYERS, EPI>() >= 5 ? 4 : 8; }
 
 template <bool LAYERS, bool EPI> struct FrameOut { typedef PlainOutT<EPI> type; };
 template <bool EPI> struct FrameOut<true, EPI> { typedef LayersOutT<EPI> type; };
@@ -1697,11 +1718,12 @@ __device__ __forceinline__ LayersOutT<EPI> make_out(const PlainOutT<EPI>& p, con
 
 // Measured and removed: XCD-contiguous work assignment (0.248 vs 0.232 ms:
 // neighbouring tiles are similarly long, contiguous eighths unbalance the XCDs), occupancy capped
-// with unused LDS, one splat per iteration in the light path, persistent waves.
+// with unused LDS, persistent waves; one splat per iteration in the light path (GPI_L = 1) bought nothing at four
+// waves per SIMD and is what lets the plain evaluation frame run at five (render_min_waves above).
 // LAYERS: a layered frame (above) -- the same launch structure, one state where the tile holds no object entry
 // EPI: the frame epilogue (FrameEpi above) behind the blend, evaluation frames only
 template <bool WRITE_AUX, int GPI_L, int NSEM = 0, bool LAYERS = false, bool EPI = false>
-__global__ void __launch_bounds__(256, NSEM > 0 ? 3 : (LAYERS ? LAYERS_MIN_WAVES : RENDER_MIN_WAVES))
+__global__ void __launch_bounds__(256, (render_min_waves<WRITE_AUX, NSEM, LAYERS, EPI>()))
 render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
                       const RecView rec, const int W, const int H, const int gx,
                       const uint32_t T, const uint32_t* __restrict__ work,
@@ -1814,7 +1836,7 @@ render_forward_kernel(const uint2* __restrict__ ranges, const uint32_t* __restri
                   reinterpret_cast<float*>(s_qid[wave]), reinterpret_cast<float*>(s_qpos[wave]));
       if (WRITE_AUX && q == 0) ckpt_publish_items(ck, lane, tile, re - rb);
     } else
-      pc_producer<(NSEM > 0), WRITE_AUX>(s_rec[slot], s_rec[slot + 2], s_qid[wave], s_qpos[wave], &s_ctl[slot], lane, q,
+      pc_producer<(NSEM > 0), WRITE_AUX, pc_list_sub<WRITE_AUX, NSEM, LAYERS, EPI>()>(s_rec[slot], s_rec[slot + 2], s_qid[wave], s_qpos[wave], &s_ctl[slot], lane, q,
                   rb, re, point_list, rec, pc_err, sem, s_sem[NSEM > 0 ? slot : 0], s_sem[NSEM > 0 ? slot + 2 : 0]);
     return;
   }
@@ -2069,7 +2091,7 @@ void launch_render_forward(hipStream_t s, const uint2* ranges, const uint32_t* p
     else render_forward_kernel<false, 2, RENDER_NSEM><<<ntiles + pc_slots, 256, 0, s>>>(RF_ARGS);
   } else {
     if (aux) render_forward_kernel<true, 2><<<ntiles + pc_slots, 256, 0, s>>>(RF_ARGS);
-    else render_forward_kernel<false, 2><<<ntiles + pc_slots, 256, 0, s>>>(RF_ARGS);
+    else render_forward_kernel<false, 1><<<ntiles + pc_slots, 256, 0, s>>>(RF_ARGS);
   }
 #undef RF_ARGS
 }
