@@ -36,6 +36,8 @@ HIP_UNITS = {
     # arithmetic: a v_pk_fma_f32 occupies the gfx950 VALU 1.8x as long as a v_fma_f32
     # (tools/ubench/valu_rate.hip), so pairs only add moves
     "render_bwd.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
+    # object-alpha plane of a training frame and its backward: the blend's arithmetic, the same atomics
+    "object_alpha.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
     # bit-identical to oracle/knn_oracle.py: one rounding per operation
     "knn.hip": ["-ffp-contract=off"],
     # hardware float atomics for the cube-map gradient

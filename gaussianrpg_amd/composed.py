@@ -338,29 +338,104 @@ class _ComposedRasterize(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_color, g_radii, g_depth, g_alpha, g_features):
-        rs, nm = ctx.rs, ctx.nm
-        radii, alpha, geom, binning, img, blob = ctx.saved_tensors[:6]
         # forward's arguments: 8 without a gradient, pose_rot, pose_trans, means2D, 6 * nm parameters, the semantics
-        need = ctx.needs_input_grad
-        need_params, need_sem = need[11:11 + 6 * nm], need[11 + 6 * nm:]
-        F = 3 * int(ctx.normals) + ctx.S
-        zeros = lambda *shape: alpha.new_zeros(*shape, *alpha.shape[-2:])   # noqa: E731  (an output the loss does not touch)
-        if F == 0:
-            g_features = _NO_SEMANTIC
-        *g_params, g_sem, g_means2D, g_poses = _C.rasterize_gaussians_composed_backward(
-            rs.bg, *_split(ctx.saved_tensors[6:], nm), ctx.flips, ctx.pose_t, ctx.idft_t, ctx.S,
+        return (None,) * 8 + _composed_backward(ctx, 11, ctx.saved_tensors[:6], ctx.saved_tensors[6:], g_color, g_depth,
+                                                g_alpha, g_features)
+
+
+def _composed_backward(ctx, first, state, params, g_color, g_depth, g_alpha, g_features, objects=None):
+    """The one backward call of a composed training frame -> (g_pose_rot, g_pose_trans, g_means2D, parameter
+    gradients..., semantic gradients...).  forward's arguments: pose_rot, pose_trans, means2D at 8, 9, 10, the
+    6 * nm parameters from `first`, then the semantics.  objects: (alpha_object, workspace, g_alpha_object) of
+    forward_objects -- the object-alpha plane's gradient rides along (C ABI grpg_backward_composed_objects)."""
+    rs, nm = ctx.rs, ctx.nm
+    radii, alpha, geom, binning, img, blob = state
+    need = ctx.needs_input_grad
+    need_params, need_sem = need[first:first + 6 * nm], need[first + 6 * nm:]
+    F = 3 * int(ctx.normals) + ctx.S
+    zeros = lambda *shape: alpha.new_zeros(*shape, *alpha.shape[-2:])   # noqa: E731  (an output the loss does not touch)
+    if F == 0:
+        g_features = _NO_SEMANTIC
+    args = (rs.bg, *_split(params, nm), ctx.flips, ctx.pose_t, ctx.idft_t, ctx.S,
             [bool(n) for n in need_sem] or [False] * nm, ctx.normals, rs.scale_modifier, rs.viewmatrix, rs.projmatrix,
             rs.tanfovx, rs.tanfovy, rs.sh_degree, rs.campos, radii, alpha, geom, ctx.num_rendered, binning, img, blob,
             g_color if g_color is not None else zeros(3),
             g_depth if g_depth is not None else zeros(1),
             g_alpha if g_alpha is not None else zeros(1),
-            g_features if g_features is not None else zeros(F), rs.debug)
-        g_rot = g_poses[:, 0:4].to(ctx.pose_dev[0]) if need[8] else None
-        g_trans = g_poses[:, 4:7].to(ctx.pose_dev[1]) if need[9] else None
-        grads = [g for per_field in g_params for g in per_field]
-        flat_grads = tuple(g if n else None for g, n in zip(grads, need_params))
-        sem_grads = tuple(g if (n and g.numel()) else None for g, n in zip(g_sem, need_sem))
-        return (None,) * 8 + (g_rot, g_trans, g_means2D if need[10] else None) + flat_grads + sem_grads
+            g_features if g_features is not None else zeros(F))
+    if objects is None:
+        out = _C.rasterize_gaussians_composed_backward(*args, rs.debug)
+    else:
+        out = _C.rasterize_gaussians_composed_objects_backward(*args, *objects, rs.debug)
+    *g_params, g_sem, g_means2D, g_poses = out
+    g_rot = g_poses[:, 0:4].to(ctx.pose_dev[0]) if need[8] else None
+    g_trans = g_poses[:, 4:7].to(ctx.pose_dev[1]) if need[9] else None
+    grads = [g for per_field in g_params for g in per_field]
+    flat_grads = tuple(g if n else None for g, n in zip(grads, need_params))
+    sem_grads = tuple(g if (n and g.numel()) else None for g, n in zip(g_sem, need_sem))
+    return (g_rot, g_trans, g_means2D if need[10] else None) + flat_grads + sem_grads
+
+
+_NO_CLASS = torch.empty(0, dtype=torch.uint8)
+_CLASS_CACHE = {}   # (counts, flags, device) -> uint8 [P] on the device; the last set of models only
+
+
+def _layer_class(models, flags, device):
+    """uint8 [P] on the device, 1 = the Gaussian's model is an object: built once per set of models (their counts and
+    flags), not per frame."""
+    counts = tuple(int(m.xyz.shape[0]) for m in models)
+    key = (counts, tuple(flags), str(device))
+    t = _CLASS_CACHE.get(key)
+    if t is None:
+        _CLASS_CACHE.clear()
+        host = torch.repeat_interleave(torch.tensor(flags, dtype=torch.uint8), torch.tensor(counts))
+        t = _CLASS_CACHE[key] = host.to(device)
+    return t
+
+
+def _objects_frame(owner, rs, nm, pose_t, idft_t, flips, normals, S, layer_class, any_object, flat):
+    """The composed TRAINING forward and the object-alpha forward on its blobs -> ((color, radii, depth, alpha,
+    features, alpha_object), (geom, binning, img, feature blob, workspace))."""
+    num_rendered, color, depth, alpha, features, radii, geom, binning, img, blob = _rasterize(
+        rs, _split(flat, nm) + [flips], pose_t, idft_t, list(flat[6 * nm:]), normals, S, True)
+    owner.num_rendered = num_rendered
+    if any_object:
+        alpha_object, workspace = _C.object_alpha_forward(geom, binning, img, radii.shape[0], layer_class,
+                                                          rs.image_height, rs.image_width)
+    else:   # the plane is exactly zero and the backward the plain one
+        alpha_object, workspace = torch.zeros_like(alpha), _NO_CLASS
+    return (color, radii, depth, alpha, features, alpha_object), (geom, binning, img, blob, workspace)
+
+
+class _ComposedRasterizeObjects(torch.autograd.Function):
+    """Training path of forward_objects: forward = the composed training forward (_rasterize(for_backward=True))
+    followed by _C.object_alpha_forward on its blobs (C ABI grpg_object_alpha_forward); backward = ONE call,
+    grpg_backward_composed_objects -- or the plain composed backward when the loss does not touch alpha_object or
+    no model is an object."""
+
+    @staticmethod
+    def forward(ctx, owner, rs, nm, pose_t, idft_t, flips, normals, S, pose_rot, pose_trans, means2D, layer_class,
+                any_object, *flat):
+        outs, state = _objects_frame(owner, rs, nm, pose_t, idft_t, flips, normals, S, layer_class, any_object, flat)
+        ctx.rs, ctx.nm, ctx.num_rendered, ctx.normals, ctx.S, ctx.any_object = rs, nm, owner.num_rendered, normals, S, any_object
+        ctx.pose_t, ctx.idft_t, ctx.flips = pose_t, idft_t, flips
+        ctx.pose_dev = (None if pose_rot is None else pose_rot.device,
+                        None if pose_trans is None else pose_trans.device)
+        ctx.save_for_backward(outs[1], outs[3], *state, outs[5], *flat[:6 * nm])   # radii, alpha, ..., alpha_object
+        ctx.mark_non_differentiable(outs[1])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_color, g_radii, g_depth, g_alpha, g_features, g_alpha_object):
+        workspace, alpha_object = ctx.saved_tensors[6:8]
+        objects = None
+        if g_alpha_object is not None and ctx.any_object:
+            objects = (alpha_object, workspace, g_alpha_object)
+        # forward's arguments: 8 without a gradient, pose_rot, pose_trans, means2D, layer_class, any_object, then the
+        # 6 * nm parameters and the semantics
+        g = _composed_backward(ctx, 13, ctx.saved_tensors[:6], ctx.saved_tensors[8:], g_color, g_depth, g_alpha,
+                               g_features, objects)
+        return (None,) * 8 + g[:3] + (None, None) + g[3:]
 
 
 class ComposedRasterizer(nn.Module):
@@ -441,6 +516,46 @@ class ComposedRasterizer(nn.Module):
 
     def forward(self, models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]], means2D=None):
         return self._render(models, poses, None, False, means2D)[:4]
+
+    def forward_objects(self, models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]],
+                        object_models: Optional[Sequence[bool]] = None, semantics=None, normals: bool = False,
+                        means2D=None):
+        """``forward_features`` plus the object-alpha plane of the SAME frame: returns ``(color, radii, depth, alpha,
+        features, alpha_object)`` with ``alpha_object [1,H,W]`` = the ``alpha`` a ``forward`` over the object models
+        alone returns, bit for bit -- what train.py:145-158 renders a second time (``render_object``) to read
+        ``acc_obj`` for the object-alpha loss.  ``object_models``: one flag per model, default "every posed model
+        (actor) is an object", as in ``forward_layers``.  The plane is blended from the tile lists and projected
+        records the main render left behind (C ABI ``grpg_object_alpha_forward``), and its gradient joins the frame's
+        ONE backward call (``grpg_backward_composed_objects``) between the blend backward and the preprocess
+        backward: no second composition, preprocess, binning or preprocess backward.  A loss that does not touch
+        ``alpha_object``, or a frame without object models (the plane is exactly zero), takes the plain backward.
+        Under ``torch.no_grad()`` the same tuple is returned and no state is kept -- but the frame underneath is still a
+        TRAINING forward (gradient records carved, ``n_contrib`` and blend checkpoints written): the plane is blended
+        from a training frame's blobs only.  An evaluation loop that wants the object layer uses ``forward_layers``.
+
+        ``means2D.grad`` is the SUM of both planes' terms on the object rows -- as if one leaf had fed both renders
+        of the reference (which creates a leaf per render and reads the main render's for densification); rows of
+        background models see the main render's term only."""
+        if object_models is not None and len(object_models) != len(models):
+            raise ValueError("object_models: one flag per model (%d flags, %d models)" % (len(object_models), len(models)))
+        _check_models(models)
+        rs = self.raster_settings
+        sems, S = _semantic_list(models, semantics)
+        lists, pose_t, idft_t = _pack(models, poses)
+        flags = [p is not None for p in poses] if object_models is None else [bool(f) for f in object_models]
+        # default flags: the class comes from the frame's own segment table on the device
+        layer_class = _NO_CLASS if object_models is None else _layer_class(models, flags, models[0].xyz.device)
+        flat = [t for per_field in lists[:6] for t in per_field]
+        pose_tensors = _pose_tensors(poses)
+        train = torch.is_grad_enabled() and any(
+            t.requires_grad for t in flat + pose_tensors + list(sems) + ([means2D] if means2D is not None else []))
+        head = (rs, len(models), pose_t, idft_t, lists[6], bool(normals), S)
+        if not train:
+            with torch.no_grad():
+                return _objects_frame(self, *head, layer_class, any(flags), flat + list(sems))[0]
+        pose_rot, pose_trans = _pose_graph(poses, pose_tensors)
+        return _ComposedRasterizeObjects.apply(self, *head, pose_rot, pose_trans, means2D, layer_class, any(flags),
+                                               *flat, *sems)
 
     def forward_features(self, models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]], semantics=None,
                          normals: bool = False, means2D=None):

@@ -594,13 +594,15 @@ struct LayerArgs {
 };
 
 // The device segment table of a composed model: one row per segment, `start` running over the counts.  layers: the
-// layered frame whose class bit (pad1: 1 = object layer) the rows carry, NULL: none.
+// layered frame whose class bit (pad1: 1 = object layer) the rows carry, NULL: none -- the rows then carry the
+// default class, "actors are objects" (only a layered frame's preprocess looks at the bit; grpg_object_alpha_forward
+// reads it from a training frame's table).
 void fill_segments(SegmentDev* dst, const grpg_model_segment* segs, int nseg, const LayerArgs* layers) {
   uint32_t start = 0;
   for (int i = 0; i < nseg; i++) {
     const grpg_model_segment& g = segs[i];
     SegmentDev& d = dst[i];
-    const bool obj = layers && (layers->segment_class ? layers->segment_class[i] != 0 : g.rigid != 0);
+    const bool obj = (layers && layers->segment_class) ? layers->segment_class[i] != 0 : g.rigid != 0;
     d.xyz = g.xyz; d.scaling = g.scaling; d.rotation = g.rotation; d.opacity = g.opacity;
     d.fdc = g.features_dc; d.frest = g.features_rest; d.flip = g.flip; d.pad1 = (const void*)(uintptr_t)(obj ? 1u : 0u);
     d.start = start; d.count = (uint32_t)g.count;
@@ -1530,7 +1532,9 @@ int grpg_forward_composed(grpg_alloc_fn geometry_alloc, void* geometry_user,
 }
 
 // Shared body of grpg_backward_composed (F = 0) and grpg_backward_composed_features: the blend backward over the
-// frame's F feature channels, then the composed preprocess backward.
+// frame's F feature channels, then the composed preprocess backward.  obj (grpg_backward_composed_objects; NULL: none):
+// the object-alpha plane's gradient is added to the gradient records between the two.
+struct ObjectAlphaGrad { const float* alpha_object; char* workspace; const float* dL_dalpha_object; };
 static int backward_composed_impl(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
                                   int num_segments, int D, int M, int R, const float* background, int width,
                                   int height, float scale_modifier, const float* viewmatrix,
@@ -1539,7 +1543,7 @@ static int backward_composed_impl(const grpg_model_segment* segments, const grpg
                                   char* image_buffer, const float* dL_dpix, const float* dL_dpix_depth,
                                   const float* dL_dalphas, float* dL_dmean2D, float* dL_dposes, int debug,
                                   void* hip_stream, const float* features, int F, const float* dL_dpix_features,
-                                  float* dL_dfeatures) {
+                                  float* dL_dfeatures, const ObjectAlphaGrad* obj = nullptr) {
   g_last_error.clear();
   if (int rc = ensure_device()) return rc;
   long long Pll = 0;
@@ -1575,6 +1579,16 @@ static int backward_composed_impl(const grpg_model_segment* segments, const grpg
   if (int rc = bb.run(stream, debug, R, background, alphas, features, F, dL_dpix, dL_dpix_depth, dL_dalphas,
                       dL_dpix_features, dL_dfeatures))
     return rc;
+  if (obj) {
+    const ObjAlphaLayout OL = obj_alpha_layout((size_t)bb.cam.gx * (size_t)bb.cam.gy, (size_t)width * height);
+    launch_object_alpha_backward(stream, (const uint2*)(image_buffer + bb.IL.ranges),
+                                 (const uint32_t*)(binning_buffer + bin_layout(0).val_a), bb.rec,
+                                 (const unsigned char*)(geom_buffer + bb.GL.aux_c),
+                                 (const unsigned char*)(obj->workspace + OL.tile_flags), width, height, bb.cam.gx,
+                                 bb.cam.gy, obj->alpha_object, (const uint32_t*)(obj->workspace + OL.n_contrib),
+                                 obj->dL_dalpha_object, bb.grad_rec);
+    STAGE_CHECK("object-alpha backward");
+  }
   launch_preprocess_backward_composed(stream, P, D, M, seg_dev, seg_grad_dev, num_segments, radii, bb.rec,
                                       scale_modifier, bb.cam, bb.grad_rec, dL_dmean2D,
                                       (float*)(geom_buffer + bb.GL.pose_acc), dL_dposes);
@@ -1638,7 +1652,8 @@ int grpg_forward_composed_features(grpg_alloc_fn geometry_alloc, void* geometry_
   return forward_impl(q);
 }
 
-int grpg_backward_composed_features(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
+// grpg_backward_composed_features, and grpg_backward_composed_objects with the object-alpha plane's three arguments
+static int backward_composed_features_impl(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
                                     int num_segments, float* const* seg_dL_dsemantic, int S, int normals, int D,
                                     int M, int R, const float* background, int width, int height,
                                     float scale_modifier, const float* viewmatrix, const float* projmatrix,
@@ -1646,7 +1661,8 @@ int grpg_backward_composed_features(const grpg_model_segment* segments, const gr
                                     const float* alphas, char* geom_buffer, char* binning_buffer, char* image_buffer,
                                     char* feature_buffer, const float* dL_dpix, const float* dL_dpix_depth,
                                     const float* dL_dalphas, const float* dL_dpix_features, float* dL_dfeatures,
-                                    float* dL_dmean2D, float* dL_dposes, int debug, void* hip_stream) {
+                                    float* dL_dmean2D, float* dL_dposes, int debug, void* hip_stream,
+                                    const ObjectAlphaGrad* obj) {
   g_last_error.clear();
   if (int rc = ensure_device()) return rc;
   int F = 0;
@@ -1661,7 +1677,7 @@ int grpg_backward_composed_features(const grpg_model_segment* segments, const gr
                                       scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
                                       alphas, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth,
                                       dL_dalphas, dL_dmean2D, dL_dposes, debug, hip_stream, features, F,
-                                      dL_dpix_features, dL_dfeatures))
+                                      dL_dpix_features, dL_dfeatures, obj))
     return rc;
   if (F == 0) return GRPG_OK;
   // the feature gradient back to the models, behind the preprocess backward on the same stream (it ADDS to the
@@ -1683,6 +1699,88 @@ int grpg_backward_composed_features(const grpg_model_segment* segments, const gr
                                    (float*)(feature_buffer + FL.partials), FL.nslots, dL_dposes);
   STAGE_CHECK("feature backward");
   return GRPG_OK;
+}
+
+int grpg_backward_composed_features(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
+                                    int num_segments, float* const* seg_dL_dsemantic, int S, int normals, int D,
+                                    int M, int R, const float* background, int width, int height,
+                                    float scale_modifier, const float* viewmatrix, const float* projmatrix,
+                                    const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                                    const float* alphas, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                    char* feature_buffer, const float* dL_dpix, const float* dL_dpix_depth,
+                                    const float* dL_dalphas, const float* dL_dpix_features, float* dL_dfeatures,
+                                    float* dL_dmean2D, float* dL_dposes, int debug, void* hip_stream) {
+  return backward_composed_features_impl(segments, grads, num_segments, seg_dL_dsemantic, S, normals, D, M, R,
+                                         background, width, height, scale_modifier, viewmatrix, projmatrix, campos,
+                                         tan_fovx, tan_fovy, radii, alphas, geom_buffer, binning_buffer, image_buffer,
+                                         feature_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dpix_features,
+                                         dL_dfeatures, dL_dmean2D, dL_dposes, debug, hip_stream, nullptr);
+}
+
+size_t grpg_object_alpha_workspace_bytes(int width, int height) {
+  if (width <= 0 || height <= 0) return 0;
+  const size_t gx = ((size_t)width + TILE - 1) / TILE, gy = ((size_t)height + TILE - 1) / TILE;
+  return obj_alpha_layout(gx * gy, (size_t)width * (size_t)height).total;
+}
+
+int grpg_object_alpha_forward(int P, int width, int height, const unsigned char* layer_class, char* geom_buffer,
+                              char* binning_buffer, char* image_buffer, float* out_alpha_object, char* workspace,
+                              void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (P < 0 || width <= 0 || height <= 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "negative size");
+  if (!out_alpha_object || !workspace || ((uintptr_t)workspace & 3u) != 0u)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL pointer (or a workspace that is not 4-byte aligned)");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const int debug = 0;
+  const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
+  const size_t N = (size_t)width * (size_t)height;
+  const ObjAlphaLayout OL = obj_alpha_layout((size_t)gx * (size_t)gy, N);
+  if (P == 0) {   // a frame without Gaussians: the plane and its n_contrib are zero, no tile is flagged
+    HIP_TRY(hipMemsetAsync(out_alpha_object, 0, N * sizeof(float), stream));
+    HIP_TRY(hipMemsetAsync(workspace, 0, OL.total, stream));
+    return GRPG_OK;
+  }
+  if (!geom_buffer || !binning_buffer || !image_buffer)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL state buffer");
+  // a training forward's blobs only: the backward adds to the gradient records an evaluation blob lacks, and the
+  // class array lives in the geometry blob (the depth sort's third payload array, idle once the forward is through)
+  if (int rc = check_backward_state(geom_buffer, P, stream)) return rc;
+  const GeomLayout GL = geom_layout((size_t)P);
+  const ImgLayout IL = img_layout((size_t)gx * (size_t)gy, N);
+  HIP_TRY(hipMemsetAsync(workspace + OL.tile_flags, 0, (size_t)gx * (size_t)gy, stream));
+  launch_object_alpha_forward(stream, P, layer_class, (const SegmentDev*)(geom_buffer + GL.seg_table),
+                              (const uint2*)(image_buffer + IL.ranges),
+                              (const uint32_t*)(binning_buffer + bin_layout(0).val_a),
+                              RecView{(const float4*)(geom_buffer + GL.rec)},
+                              (const uint32_t*)(geom_buffer + GL.tiles), width, height, gx, gy,
+                              (unsigned char*)(geom_buffer + GL.aux_c), out_alpha_object,
+                              (uint32_t*)(workspace + OL.n_contrib), (unsigned char*)(workspace + OL.tile_flags));
+  STAGE_CHECK("object-alpha forward");
+  return GRPG_OK;
+}
+
+int grpg_backward_composed_objects(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
+                                   int num_segments, float* const* seg_dL_dsemantic, int S, int normals, int D,
+                                   int M, int R, const float* background, int width, int height,
+                                   float scale_modifier, const float* viewmatrix, const float* projmatrix,
+                                   const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                                   const float* alphas, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                   char* feature_buffer, const float* dL_dpix, const float* dL_dpix_depth,
+                                   const float* dL_dalphas, const float* dL_dpix_features, float* dL_dfeatures,
+                                   float* dL_dmean2D, float* dL_dposes, const float* alpha_object, char* workspace,
+                                   const float* dL_dalpha_object, int debug, void* hip_stream) {
+  g_last_error.clear();
+  if (int rc = ensure_device()) return rc;
+  if (!alpha_object || !workspace || !dL_dalpha_object || ((uintptr_t)workspace & 3u) != 0u || width <= 0 ||
+      height <= 0)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "object-alpha backward: NULL pointer, misaligned workspace or bad size");
+  const ObjectAlphaGrad obj = {alpha_object, workspace, dL_dalpha_object};
+  return backward_composed_features_impl(segments, grads, num_segments, seg_dL_dsemantic, S, normals, D, M, R,
+                                         background, width, height, scale_modifier, viewmatrix, projmatrix, campos,
+                                         tan_fovx, tan_fovy, radii, alphas, geom_buffer, binning_buffer, image_buffer,
+                                         feature_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dpix_features,
+                                         dL_dfeatures, dL_dmean2D, dL_dposes, debug, hip_stream, &obj);
 }
 
 // the arguments the two stand-alone feature entries share

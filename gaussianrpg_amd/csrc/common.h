@@ -556,6 +556,27 @@ void launch_preprocess_backward_composed(hipStream_t s, int P, int D, int M, con
                                          float* pose_acc /* [nseg][POSE_ACC_FLOATS] scratch */,
                                          float* dL_dposes /* [nseg][8] */);
 
+// Object-alpha plane of a training frame (object_alpha.hip).  The workspace of grpg_object_alpha_forward: the plane's
+// n_contrib [N] and one flag byte per tile (1 = an object Gaussian's rectangle touches it), kept for the backward.
+struct ObjAlphaLayout { size_t n_contrib, tile_flags, total; };
+inline ObjAlphaLayout obj_alpha_layout(size_t T, size_t N) {
+  ObjAlphaLayout L;
+  L.n_contrib = 0;
+  L.tile_flags = align_up(N * 4, 256);
+  L.total = L.tile_flags + align_up(T, 256);
+  return L;
+}
+// cls [P]: written (the class array both kernels read); tile_flags zeroed by the caller
+void launch_object_alpha_forward(hipStream_t s, int P, const unsigned char* layer_class /* [P] or NULL: segs */,
+                                 const SegmentDev* segs, const uint2* ranges, const uint32_t* point_list,
+                                 const RecView rec, const uint32_t* tiles /* [P] per-Gaussian tile counts, 0 = culled */,
+                                 int W, int H, int gx, int gy, unsigned char* cls, float* out_alpha, uint32_t* n_contrib_obj, unsigned char* tile_flags);
+// adds to grad_rec: between the blend backward and the preprocess backward of the same frame
+void launch_object_alpha_backward(hipStream_t s, const uint2* ranges, const uint32_t* point_list, const RecView rec,
+                                  const unsigned char* cls, const unsigned char* tile_flags, int W, int H, int gx,
+                                  int gy, const float* alpha_object, const uint32_t* n_contrib_obj,
+                                  const float* dL_dalpha_object, float* grad_rec);
+
 void launch_frame_init(hipStream_t s, char* geom, char* bin /* may be NULL */, char* img, uint32_t P,
                        uint32_t V_init, uint32_t Rcap, uint32_t W, uint32_t H, uint32_t S,
                        uint2* ranges /* zeroed, may be NULL */, uint32_t T,

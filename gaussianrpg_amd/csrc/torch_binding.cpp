@@ -912,17 +912,19 @@ RasterizeGaussiansComposedFeatures(const torch::Tensor& background, GRPG_MODEL_P
 // the feature blob and dL_dout_features are not looked at; grpg_backward_composed_features otherwise): gradients with
 // respect to every model's RAW parameter tensors, the semantic arrays ([N_i,S] per model; empty where
 // want_semantic[i] is false), means2D [P,3] (densification statistic) and the poses [n,8].
-std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
-           std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
-           std::vector<torch::Tensor>, torch::Tensor, torch::Tensor>
-RasterizeGaussiansComposedBackward(
+typedef std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
+                   std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
+                   std::vector<torch::Tensor>, torch::Tensor, torch::Tensor> ComposedGrads;
+// objects (rasterize_gaussians_composed_objects_backward; NULL: none): {alpha_object, workspace, dL_dout_alpha_object}
+// of ComposedRasterizer.forward_objects -- grpg_backward_composed_objects at any F
+static ComposedGrads ComposedBackwardImpl(
     const torch::Tensor& background, GRPG_MODEL_PARAMS, const int S, const std::vector<bool>& want_semantic,
     const bool normals, const float scale_modifier, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
     const float tan_fovx, const float tan_fovy, const int degree, const torch::Tensor& campos,
     const torch::Tensor& radii, const torch::Tensor& alphas, const torch::Tensor& geomBuffer, const int R,
     const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const torch::Tensor& featureBuffer,
     const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_depth, const torch::Tensor& dL_dout_alpha,
-    const torch::Tensor& dL_dout_features, const bool debug) {
+    const torch::Tensor& dL_dout_features, const bool debug, const torch::Tensor* const (*objects)[3]) {
   SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
@@ -942,7 +944,32 @@ RasterizeGaussiansComposedBackward(
   const SavedState sv(like, dL_dout_color, dL_dout_depth, dL_dout_alpha, &dL_dout_features, radii, geomBuffer,
                       binningBuffer, imageBuffer);
   hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  if (F == 0) {
+  if (objects) {
+    const torch::Tensor &alpha_object = *(*objects)[0], &workspace = *(*objects)[1], &dL_dobj = *(*objects)[2];
+    TORCH_CHECK(alpha_object.numel() == (int64_t)H * W && dL_dobj.numel() == (int64_t)H * W,
+                "alpha_object and its gradient must be [1,H,W]");
+    TORCH_CHECK(workspace.scalar_type() == torch::kByte && workspace.device() == like.device() &&
+                    (size_t)workspace.numel() >= grpg_object_alpha_workspace_bytes(W, H),
+                "the object-alpha workspace must be the forward's byte tensor");
+    torch::Tensor k_obj, k_dobj, k_blob;
+    const float* p_obj = fptr(alpha_object, like, "alpha_object", k_obj);
+    const float* p_dobj = fptr(dL_dobj, like, "dL_dout_alpha_object", k_dobj);
+    const torch::Tensor k_ws = workspace.contiguous();
+    torch::Tensor dL_dfeatures = torch::zeros({F > 0 ? pk.P : 0, F}, o);   // the blend backward accumulates into it
+    char* p_blob = nullptr;
+    if (F > 0) {
+      TORCH_CHECK(featureBuffer.scalar_type() == torch::kByte && featureBuffer.device() == like.device(),
+                  "the feature blob must be the forward's byte tensor");
+      p_blob = reinterpret_cast<char*>((k_blob = featureBuffer.contiguous()).data_ptr());
+    }
+    const int rc = grpg_backward_composed_objects(
+        pk.segs.data(), mg.table.data(), n, sem.ptrs.data(), S, normals ? 1 : 0, degree, pk.M, R, cam.bg, W, H,
+        scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img,
+        p_blob, sv.dcolor, sv.ddepth, sv.dalpha, sv.dsemantic, F > 0 ? dL_dfeatures.data_ptr<float>() : nullptr,
+        dL_dmeans2D.data_ptr<float>(), dL_dposes.data_ptr<float>(), p_obj, reinterpret_cast<char*>(k_ws.data_ptr()),
+        p_dobj, debug ? 1 : 0, (void*)stream);
+    if (rc != GRPG_OK) raise_abi_error("grpg_backward_composed_objects", rc);
+  } else if (F == 0) {
     const int rc = grpg_backward_composed(
         pk.segs.data(), mg.table.data(), n, degree, pk.M, R, cam.bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos,
         tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img, sv.dcolor, sv.ddepth, sv.dalpha,
@@ -962,6 +989,68 @@ RasterizeGaussiansComposedBackward(
     if (rc != GRPG_OK) raise_abi_error("grpg_backward_composed_features", rc);
   }
   return std::make_tuple(mg.g[0], mg.g[1], mg.g[2], mg.g[3], mg.g[4], mg.g[5], sem.grads, dL_dmeans2D, dL_dposes);
+}
+
+#define GRPG_COMPOSED_BACKWARD_PARAMS                                                                                \
+  const torch::Tensor &background, GRPG_MODEL_PARAMS, const int S, const std::vector<bool>&want_semantic,            \
+      const bool normals, const float scale_modifier, const torch::Tensor &viewmatrix,                               \
+      const torch::Tensor &projmatrix, const float tan_fovx, const float tan_fovy, const int degree,                 \
+      const torch::Tensor &campos, const torch::Tensor &radii, const torch::Tensor &alphas,                          \
+      const torch::Tensor &geomBuffer, const int R, const torch::Tensor &binningBuffer,                              \
+      const torch::Tensor &imageBuffer, const torch::Tensor &featureBuffer, const torch::Tensor &dL_dout_color,      \
+      const torch::Tensor &dL_dout_depth, const torch::Tensor &dL_dout_alpha, const torch::Tensor &dL_dout_features
+#define GRPG_COMPOSED_BACKWARD_ARGS                                                                                  \
+  background, GRPG_MODEL_ARGS, S, want_semantic, normals, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, \
+      degree, campos, radii, alphas, geomBuffer, R, binningBuffer, imageBuffer, featureBuffer, dL_dout_color,        \
+      dL_dout_depth, dL_dout_alpha, dL_dout_features
+
+ComposedGrads RasterizeGaussiansComposedBackward(GRPG_COMPOSED_BACKWARD_PARAMS, const bool debug) {
+  return ComposedBackwardImpl(GRPG_COMPOSED_BACKWARD_ARGS, debug, nullptr);
+}
+
+// ComposedRasterizer.forward_objects' backward: the same call with the object-alpha plane's gradient riding along
+ComposedGrads RasterizeGaussiansComposedObjectsBackward(GRPG_COMPOSED_BACKWARD_PARAMS,
+                                                        const torch::Tensor& alpha_object,
+                                                        const torch::Tensor& workspace,
+                                                        const torch::Tensor& dL_dout_alpha_object, const bool debug) {
+  const torch::Tensor* const objects[3] = {&alpha_object, &workspace, &dL_dout_alpha_object};
+  return ComposedBackwardImpl(GRPG_COMPOSED_BACKWARD_ARGS, debug, &objects);
+}
+
+// The object-alpha plane of a TRAINING frame (grpg_object_alpha_forward on the blobs its forward left behind).
+// layer_class: uint8 / bool [P] on the device, != 0 = object; empty: a composed frame's segment table decides
+// (actors = objects).  returns (alpha_object [1,H,W], workspace)
+std::tuple<torch::Tensor, torch::Tensor> ObjectAlphaForward(const torch::Tensor& geomBuffer,
+                                                            const torch::Tensor& binningBuffer,
+                                                            const torch::Tensor& imageBuffer, const int64_t P,
+                                                            const torch::Tensor& layer_class, const int image_height,
+                                                            const int image_width) {
+  const torch::Tensor& like = geomBuffer;
+  require_device(like);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
+  const int H = image_height, W = image_width;
+  TORCH_CHECK(H > 0 && W > 0 && P >= 0, "image size must be positive, P not negative");
+  for (const torch::Tensor* t : {&geomBuffer, &binningBuffer, &imageBuffer})
+    TORCH_CHECK(t->scalar_type() == torch::kByte && t->device() == like.device() && t->is_contiguous(),
+                "the state buffers must be the forward's byte tensors");
+  torch::Tensor k_cls;
+  const unsigned char* p_cls = nullptr;
+  if (layer_class.numel() != 0) {
+    TORCH_CHECK(layer_class.numel() == P && layer_class.device() == like.device() &&
+                    (layer_class.scalar_type() == torch::kUInt8 || layer_class.scalar_type() == torch::kBool),
+                "layer_class must be a uint8 / bool tensor of P elements on the device of the frame");
+    p_cls = (const unsigned char*)(k_cls = layer_class.contiguous()).data_ptr();
+  }
+  torch::Tensor alpha_object = torch::empty({1, H, W}, like.options().dtype(torch::kFloat32));
+  torch::Tensor workspace =
+      torch::empty({(int64_t)grpg_object_alpha_workspace_bytes(W, H)}, like.options().dtype(torch::kByte));
+  run("grpg_object_alpha_forward", [&](void* stream) {
+    return grpg_object_alpha_forward((int)P, W, H, p_cls, reinterpret_cast<char*>(geomBuffer.data_ptr()),
+                                     reinterpret_cast<char*>(binningBuffer.data_ptr()),
+                                     reinterpret_cast<char*>(imageBuffer.data_ptr()), alpha_object.data_ptr<float>(),
+                                     reinterpret_cast<char*>(workspace.data_ptr()), stream);
+  });
+  return std::make_tuple(alpha_object, workspace);
 }
 
 // (means3D [P,3], scales [P,3], rotations [P,4], opacity [P,1], shs [P,M,3]): what the reference's
@@ -1772,6 +1861,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("image_height"), pybind11::arg("image_width"), pybind11::arg("degree"),
         pybind11::arg("campos"), pybind11::arg("debug"), pybind11::arg("for_backward") = false);
   m.def("rasterize_gaussians_composed_backward", &RasterizeGaussiansComposedBackward);
+  m.def("rasterize_gaussians_composed_objects_backward", &RasterizeGaussiansComposedObjectsBackward);
+  m.def("object_alpha_forward", &ObjectAlphaForward);   // (alpha_object [1,H,W], workspace)
   m.def("rasterize_gaussians_composed_layers", &RasterizeGaussiansComposedLayers);
   m.def("rasterize_gaussians_frame", &RasterizeGaussiansFrame);
   m.def("rasterize_gaussians_composed_frame", &RasterizeGaussiansComposedFrame);

@@ -483,6 +483,50 @@ GRPG_API int grpg_backward_composed_features(const grpg_model_segment* segments,
                  float* dL_dmean2D, float* dL_dposes, int debug, void* hip_stream);
 
 /*
+ * Object-alpha plane of a TRAINING frame, and its backward inside the frame's own backward (additive; ABI 7
+ * unchanged).  Replaces the second render of the reference's training iteration (train.py:145-158, render_object:
+ * a whole forward and backward of the op over the object models, read for acc_obj alone): the plane is blended from
+ * the tile ranges, point list and projected records the frame's forward left in its three blobs.
+ *   alpha_object = 1 - T_obj   [H,W], bit for bit the out_alpha of a forward over the object Gaussians alone
+ *   d alpha_object / d alpha_i = T_obj,final / (1 - alpha_i)   for every splat that contributed
+ * grpg_object_alpha_workspace_bytes: size of `workspace` (the plane's per-pixel contributor count and one flag byte
+ * per tile, kept for the backward); a pure size query, no device needed, 0 for width or height <= 0.
+ * grpg_object_alpha_forward: any training forward's blobs (grpg_forward / grpg_forward_flags without
+ * GRPG_FORWARD_NO_BACKWARD, grpg_forward_composed_flags(0), grpg_forward_composed_features(flags 0)), same P, width,
+ * height and stream order.  layer_class: device uint8 [P], != 0 = object Gaussian; NULL (composed frames only): the
+ * class of a Gaussian is its model's in the frame's segment table -- `rigid`, actors are objects, as with
+ * grpg_forward_composed_layers' segment_class == NULL.  The blobs do not record whether a frame was composed: with
+ * NULL on a FLAT frame the table's bytes are whatever the blob held, the classes (and the plane) are meaningless --
+ * reads and writes stay inside the blobs, but nothing can refuse the call; pass layer_class there.  The class array the kernels read is kept in the geometry blob
+ * (an array of the depth sort that is idle once the forward is through).  out_alpha_object [H,W] and the workspace
+ * are written in full; P == 0 writes zeros and looks at no blob.  Deterministic: plain stores, no atomics.
+ * grpg_backward_composed_objects: grpg_backward_composed_features (at any F, F == 0 included) with the plane's
+ * gradient dL_dalpha_object [H,W] riding along: between the blend backward and the preprocess backward its share is
+ * added to the frame's gradient records (mean2D with the |x| + |y| statistic, conic, opacity), so the raw-parameter,
+ * pose and dL_dmean2D outputs are the gradients of both planes' losses.  alpha_object and workspace as
+ * grpg_object_alpha_forward left them for the same blobs.
+ * Returns GRPG_OK, GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT for a NULL pointer, a workspace
+ * that is not 4-byte aligned or sizes <= 0 (P < 0), GRPG_ERR_BAD_BUFFER for an evaluation frame's geometry blob
+ * (as grpg_backward).
+ */
+GRPG_API size_t grpg_object_alpha_workspace_bytes(int width, int height);
+GRPG_API int grpg_object_alpha_forward(int P, int width, int height, const unsigned char* layer_class,
+                 char* geom_buffer, char* binning_buffer, char* image_buffer,
+                 float* out_alpha_object, char* workspace, void* hip_stream);
+GRPG_API int grpg_backward_composed_objects(const grpg_model_segment* segments,
+                 const grpg_model_segment_grad* grads, int num_segments,
+                 float* const* seg_dL_dsemantic, int S, int normals, int D, int M, int R,
+                 const float* background, int width, int height, float scale_modifier,
+                 const float* viewmatrix, const float* projmatrix, const float* campos,
+                 float tan_fovx, float tan_fovy, const int* radii, const float* alphas,
+                 char* geom_buffer, char* binning_buffer, char* image_buffer, char* feature_buffer,
+                 const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dalphas,
+                 const float* dL_dpix_features, float* dL_dfeatures,
+                 float* dL_dmean2D, float* dL_dposes,
+                 const float* alpha_object, char* workspace, const float* dL_dalpha_object,
+                 int debug, void* hip_stream);
+
+/*
  * Sky cube map without nvdiffrast (additive).  Replaces
  * SkyCubeMap.forward (lib/models/sky_cubemap.py:77-122: get_rays_torch + mask + dr.texture(...,
  * filter_mode='linear', boundary_mode='cube') + clamp) and the composite of
@@ -681,7 +725,9 @@ GRPG_API int grpg_set_stage_timing(int enabled);
 GRPG_API int grpg_get_stage_timing(float* stage_ms_sum, int* num_calls);
 /* While stage timing is enabled every grpg_backward / grpg_backward_composed on this thread records
  * three events as well: this call waits for them and returns the summed device time of the blend
- * backward (render_backward_kernel) and of the preprocess backward over *num_calls calls. */
+ * backward (render_backward_kernel) and of the preprocess backward over *num_calls calls.  In a
+ * grpg_backward_composed_objects call the object-alpha backward kernel runs between the two and its time is part
+ * of the preprocess figure. */
 GRPG_API int grpg_get_backward_timing(float* blend_ms_sum, float* preprocess_ms_sum, int* num_calls);
 
 /*
