@@ -7,6 +7,7 @@
 
 Both land next to this file.  ``python -m gaussianrpg_amd.build`` builds everything.
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -67,7 +68,11 @@ HIP_UNITS = {
 # next to the object as <unit>.remarks: the render launch's occupancy is a budget the sources promise
 # (render_fwd.hip render_min_waves; tests/test_render_resources.py reads the file)
 REMARK_UNITS = ("render_fwd.hip",)
-HEADERS = ["common.h", "reduce.h", "gaussian_math.h", "blend_math.h", "compose_math.h", os.path.join(ROOT, "include", "grpg_rasterizer.h")]
+
+
+def headers():
+    """The headers whose change makes every object stale: all of csrc/ and the public one."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "grpg_rasterizer.h")]
 
 
 def _hipcc():
@@ -93,6 +98,21 @@ def _run(cmd, keep=None):
         with open(keep, "w") as f:
             f.write(p.stdout)
     return p.stdout
+
+
+def compile_cmd(unit, extra, src_dir, obj):
+    """The hipcc command line of one translation unit: its HIP_UNITS flags, then `extra`."""
+    return [_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
+            "-Wno-unused-function"] + HIP_UNITS[unit] + list(extra) + ["-c", os.path.join(src_dir, unit), "-o", obj]
+
+
+def link_cmd(objs, out):
+    return [_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", out] + list(objs) + \
+           ["-Wl,--enable-new-dtags", "-Wl,-rpath,/opt/rocm/lib"]
+
+
+def _stale(obj, unit):
+    return _newer(obj, [os.path.join(CSRC, unit)] + headers() + [os.path.abspath(__file__)])
 
 
 def remarks_path(unit):
@@ -121,29 +141,23 @@ def kernel_resources(unit="render_fwd.hip"):
 def build_native(force=False, verbose=False):
     """hipcc -> libgrpg_rasterizer.so (gfx950 only)."""
     os.makedirs(OBJ, exist_ok=True)
-    hipcc = _hipcc()
-    hdrs = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS]
     jobs = []
     objs = []
-    for unit, extra in HIP_UNITS.items():
-        src = os.path.join(CSRC, unit)
+    for unit in HIP_UNITS:
         obj = os.path.join(OBJ, unit.replace(".hip", ".o"))
         objs.append(obj)
         keep = remarks_path(unit) if unit in REMARK_UNITS else None
-        if force or _newer(obj, [src] + hdrs + [os.path.abspath(__file__)]) or (keep and not os.path.exists(keep)):
-            jobs.append(([hipcc, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC",
-                          "-fvisibility=hidden", "-Wall", "-Wno-unused-function"] + extra +
-                         (["-Rpass-analysis=kernel-resource-usage"] if keep else []) +
-                         os.environ.get("GRPG_EXTRA_HIPCC_FLAGS", "").split() +   # experiments (-D...)
-                         ["-c", src, "-o", obj], keep))
+        if force or _stale(obj, unit) or (keep and not os.path.exists(keep)):
+            extra = (["-Rpass-analysis=kernel-resource-usage"] if keep else []) + \
+                    os.environ.get("GRPG_EXTRA_HIPCC_FLAGS", "").split()   # experiments (-D...)
+            jobs.append((compile_cmd(unit, extra, CSRC, obj), keep))
     if jobs:
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
             for (_, keep), out in zip(jobs, ex.map(lambda j: _run(*j), jobs)):
                 if verbose and out.strip() and not keep:
                     print(out)
     if force or jobs or _newer(LIB_PATH, objs):
-        _run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB_PATH] + objs +
-             ["-Wl,--enable-new-dtags", "-Wl,-rpath,/opt/rocm/lib"])
+        _run(link_cmd(objs, LIB_PATH))
     return LIB_PATH
 
 
@@ -202,27 +216,22 @@ def build_variant(name, force=False):
     """build/variants/libgrpg_rasterizer_<name>.so from the objects of build_native(), except the
     units VARIANTS[name] lists, which are recompiled with the extra flags."""
     build_native()
-    hipcc = _hipcc()
     spec = VARIANTS.get(name) or EXPERIMENT_VARIANTS[name]
     out = variant_path(name)
     vobj = os.path.join(ROOT, "build", "obj_" + name)
     os.makedirs(vobj, exist_ok=True)
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    hdrs = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS]
     objs = []
-    for unit, extra in HIP_UNITS.items():
+    for unit in HIP_UNITS:
         if unit not in spec:
             objs.append(os.path.join(OBJ, unit.replace(".hip", ".o")))
             continue
-        src = os.path.join(CSRC, unit)
         obj = os.path.join(vobj, unit.replace(".hip", ".o"))
         objs.append(obj)
-        if force or _newer(obj, [src] + hdrs + [os.path.abspath(__file__)]):
-            _run([hipcc, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
-                  "-Wall", "-Wno-unused-function"] + extra + spec[unit] + ["-c", src, "-o", obj])
+        if force or _stale(obj, unit):
+            _run(compile_cmd(unit, spec[unit], CSRC, obj))
     if force or _newer(out, objs):
-        _run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", out] + objs +
-             ["-Wl,--enable-new-dtags", "-Wl,-rpath,/opt/rocm/lib"])
+        _run(link_cmd(objs, out))
     return out
 
 

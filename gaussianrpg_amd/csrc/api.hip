@@ -14,6 +14,8 @@
 // mode: read the count first, then carve and enqueue the tail; capacity overflow: redo the tail,
 // like the reference's one blocking read (rasterizer_impl.cu:284).
 // There is no CPU fallback: without a usable HIP device every entry point fails.
+// Only the frame is here.  The entries of the self-contained ops (losses, PSNR, Adam, kNN, sky cube map) sit next to
+// their kernels; what they share with this file is declared in abi_util.h and defined below.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -30,13 +32,70 @@
 #include <vector>
 
 #include "../../include/grpg_rasterizer.h"
+#include "abi_util.h"
 #include "common.h"
 
 using namespace grpg;
 
+// ---- what every entry point shares, the leaf ops' in their own units included (abi_util.h).  Ahead of the unnamed
+// namespace, which stays ONE block up to the entries: hipcc numbers the lambdas of namespace-scope initializers per
+// block, and the first lambdas of two blocks (g_binning_mode's, g_binning_alg's) would share one name and one body. ----
+static thread_local std::string g_last_error;
+
+namespace grpg {
+
+int fail(int code, const std::string& msg) {
+  g_last_error = msg;
+  return code;
+}
+
+int ensure_device() {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0)
+    return fail(GRPG_ERR_NO_DEVICE,
+                "no usable HIP device (libgrpg_rasterizer has no CPU fallback by design)");
+  return GRPG_OK;
+}
+
+int begin_call() {
+  g_last_error.clear();
+  return ensure_device();
+}
+
+int loss_plane_check(const char* what, int height, int width) {
+  const bool sides = height > 0 && width > 0;
+  if (sides && (long long)height * width <= 0x7FFFFFFFll) return GRPG_OK;
+  if (what) g_last_error = std::string(what) + (sides ? ": H*W must be < 2^31" : ": height and width must be positive");
+  return GRPG_ERR_INVALID_ARGUMENT;
+}
+
+// the one pinned staging ring of optim.hip's and reg_loss.hip's entries (abi_util.h)
+constexpr int OPTIM_STAGING_SLOTS = 32;
+static thread_local OptimStagingSlot g_optim_staging[OPTIM_STAGING_SLOTS];
+static thread_local int g_optim_staging_next = 0;
+OptimStagingSlot* optim_staging_acquire(size_t bytes) {
+  OptimStagingSlot& b = g_optim_staging[g_optim_staging_next];
+  g_optim_staging_next = (g_optim_staging_next + 1) % OPTIM_STAGING_SLOTS;
+  if (!b.ev && hipEventCreateWithFlags(&b.ev, hipEventDisableTiming) != hipSuccess) return nullptr;
+  if (b.used) (void)hipEventSynchronize(b.ev);
+  if (b.bytes < bytes) {
+    if (b.host) (void)hipHostFree(b.host);
+    b.host = nullptr;
+    b.bytes = 0;
+    size_t cap = 4096;
+    while (cap < bytes) cap *= 2;
+    if (hipHostMalloc((void**)&b.host, cap, hipHostMallocDefault) != hipSuccess) return nullptr;
+    b.bytes = cap;
+  }
+  b.used = true;
+  return &b;
+}
+
+}  // namespace grpg
+
 namespace {
 
-thread_local std::string g_last_error;
 thread_local int g_timing_enabled = 0;   // 0 off, 1 all stages, 2 render stage only
 
 // ---- num_rendered hand-over: pinned, device-mapped host words + one event per (thread, device) ----
@@ -206,18 +265,6 @@ void update_hint(const CapKey& k, uint32_t R, uint32_t Rc, bool far) {
 // hundred chunks, quadratic beyond (P > 4 M: the classic three-kernel passes).
 bool depth_sort_is_fat(uint32_t nchunks_ds) { return nchunks_ds <= DS_MAX_CHUNKS; }
 
-int fail(int code, const std::string& msg) {
-  g_last_error = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess)                                                                    \
-      return fail(GRPG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
-  } while (0)
-
 // debug=true: synchronise and check after every stage, like CHECK_CUDA (auxiliary.h:166-173).
 #define STAGE_CHECK(name)                                                                    \
   do {                                                                                       \
@@ -237,15 +284,6 @@ int check_async_error(HostWord* hw) {
     return fail(GRPG_ERR_HIP, "render: a producer/consumer hand-over timed out in an earlier frame "
                               "of this thread (image blob header pc_timeout): that frame's image is invalid");
   }
-  return GRPG_OK;
-}
-
-int ensure_device() {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    return fail(GRPG_ERR_NO_DEVICE,
-                "no usable HIP device (libgrpg_rasterizer has no CPU fallback by design)");
   return GRPG_OK;
 }
 
@@ -534,8 +572,7 @@ int grpg_reset_capacity_hints(void) {
   return GRPG_OK;
 }
 int grpg_set_capacity_hint(int P, int width, int height, unsigned instances, unsigned coarse_pairs) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (P <= 0 || width <= 0 || height <= 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "bad shape");
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -1142,8 +1179,7 @@ struct Frame {
 // mode: read the count first, carve the blob for it, then enqueue the tail -- like the
 // reference's one blocking read (rasterizer_impl.cu:284), only much earlier in the frame.
 int forward_impl(const FrameRequest& q, bool force_pass3 = false) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (int rc = validate(q)) return rc;
   const CameraArgs cam = make_camera(q.viewmatrix, q.projmatrix, q.cam_pos, q.width, q.height, q.tan_fovx, q.tan_fovy);
   // an evaluation frame carves the geometry blob without the gradient records
@@ -1370,8 +1406,7 @@ int grpg_forward_deferred(grpg_alloc_fn geometry_alloc, void* geometry_user, grp
                           float* out_depth, float* out_alpha, float* out_semantic, int* radii, int debug,
                           void* hip_stream, unsigned flags, int* ticket) {
   (void)prefiltered;
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (!ticket) return fail(GRPG_ERR_INVALID_ARGUMENT, "ticket must not be NULL");
   DeferSlot* d = defer_acquire(ticket);
   if (!d) return fail(GRPG_ERR_HIP, "pinned status words / event allocation failed");
@@ -1411,8 +1446,7 @@ int grpg_forward_composed_flags(grpg_alloc_fn geometry_alloc, void* geometry_use
                                 const float* viewmatrix, const float* projmatrix, const float* cam_pos,
                                 float tan_fovx, float tan_fovy, float* out_color, float* out_depth,
                                 float* out_alpha, int* radii, int debug, void* hip_stream, unsigned flags) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
   FrameRequest q;
@@ -1434,8 +1468,7 @@ int grpg_forward_composed_layers(grpg_alloc_fn geometry_alloc, void* geometry_us
                                  float* out_depth, float* out_alpha, float* out_color_bg, float* out_alpha_bg,
                                  float* out_color_obj, float* out_alpha_obj, int* radii, int debug,
                                  void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
   const LayerArgs la = {segment_class, nullptr, layer_background, out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj};
@@ -1497,8 +1530,7 @@ int grpg_forward_composed_frame(grpg_alloc_fn geometry_alloc, void* geometry_use
                                 float* out_alpha, float* out_color_bg, float* out_alpha_bg, float* out_color_obj,
                                 float* out_alpha_obj, int* radii, int debug, void* hip_stream,
                                 const grpg_frame_epilogue* epilogue) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
   const LayerArgs la = {segment_class, nullptr, layer_background, out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj};
@@ -1544,8 +1576,7 @@ static int backward_composed_impl(const grpg_model_segment* segments, const grpg
                                   const float* dL_dalphas, float* dL_dmean2D, float* dL_dposes, int debug,
                                   void* hip_stream, const float* features, int F, const float* dL_dpix_features,
                                   float* dL_dfeatures, const ObjectAlphaGrad* obj = nullptr) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   long long Pll = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &Pll)) return rc;
   const int P = (int)Pll;
@@ -1630,8 +1661,7 @@ int grpg_forward_composed_features(grpg_alloc_fn geometry_alloc, void* geometry_
                                    float tan_fovx, float tan_fovy, float* out_color, float* out_depth,
                                    float* out_alpha, float* out_features, int* radii, int debug, void* hip_stream,
                                    unsigned flags) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
   int F = 0;
@@ -1663,8 +1693,7 @@ static int backward_composed_features_impl(const grpg_model_segment* segments, c
                                     const float* dL_dalphas, const float* dL_dpix_features, float* dL_dfeatures,
                                     float* dL_dmean2D, float* dL_dposes, int debug, void* hip_stream,
                                     const ObjectAlphaGrad* obj) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   int F = 0;
   if (int rc = check_feature_split(S, normals, &F)) return rc;
   if (F > GRPG_MAX_SEMANTIC_BACKWARD)   // the blend backward carries the channels in registers
@@ -1726,8 +1755,7 @@ size_t grpg_object_alpha_workspace_bytes(int width, int height) {
 int grpg_object_alpha_forward(int P, int width, int height, const unsigned char* layer_class, char* geom_buffer,
                               char* binning_buffer, char* image_buffer, float* out_alpha_object, char* workspace,
                               void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (P < 0 || width <= 0 || height <= 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "negative size");
   if (!out_alpha_object || !workspace || ((uintptr_t)workspace & 3u) != 0u)
     return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL pointer (or a workspace that is not 4-byte aligned)");
@@ -1770,8 +1798,7 @@ int grpg_backward_composed_objects(const grpg_model_segment* segments, const grp
                                    const float* dL_dalphas, const float* dL_dpix_features, float* dL_dfeatures,
                                    float* dL_dmean2D, float* dL_dposes, const float* alpha_object, char* workspace,
                                    const float* dL_dalpha_object, int debug, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (!alpha_object || !workspace || !dL_dalpha_object || ((uintptr_t)workspace & 3u) != 0u || width <= 0 ||
       height <= 0)
     return fail(GRPG_ERR_INVALID_ARGUMENT, "object-alpha backward: NULL pointer, misaligned workspace or bad size");
@@ -1829,8 +1856,7 @@ static int temp_table_call(const grpg_model_segment* segments, int num_segments,
 
 int grpg_compose_features(const grpg_model_segment* segments, int num_segments, const float* const* seg_semantic,
                           int S, int normals, const float* cam_pos, float* features, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   long long P = 0;
   int F = 0;
   if (int rc = check_feature_call(segments, num_segments, S, normals, cam_pos, &P, &F)) return rc;
@@ -1846,8 +1872,7 @@ int grpg_compose_features(const grpg_model_segment* segments, int num_segments, 
 int grpg_compose_features_backward(const grpg_model_segment* segments, int num_segments, int S, int normals,
                                    const float* cam_pos, const float* dL_dfeatures, float* const* seg_dL_dsemantic,
                                    float* const* seg_dL_drotation, float* dL_dposes, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   long long P = 0;
   int F = 0;
   if (int rc = check_feature_call(segments, num_segments, S, normals, cam_pos, &P, &F)) return rc;
@@ -1864,8 +1889,7 @@ int grpg_compose_features_backward(const grpg_model_segment* segments, int num_s
 
 int grpg_compose(const grpg_model_segment* segments, int num_segments, int M, float* means3D,
                  float* scales, float* rotations, float* opacities, float* shs, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_segments(segments, num_segments, M, &P)) return rc;
   if (M < 1 || M > 16) return fail(GRPG_ERR_INVALID_ARGUMENT, "M must be in 1..16");
@@ -1890,8 +1914,7 @@ int grpg_backward(int P, int D, int M, int R, int S, const float* background, in
                   float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D,
                   float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                   float* dL_dsemantic, int debug, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (P <= 0) return GRPG_OK;
   if (!geom_buffer || !binning_buffer || !image_buffer)
     return fail(GRPG_ERR_BAD_BUFFER, "NULL state buffer");
@@ -1950,8 +1973,7 @@ int grpg_backward(int P, int D, int M, int R, int S, const float* background, in
 int grpg_mark_visible(int P, const float* means3D, const float* viewmatrix,
                       const float* projmatrix, unsigned char* present, void* hip_stream) {
   (void)projmatrix;
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (P < 0 || (P > 0 && (!means3D || !viewmatrix || !present)))
     return fail(GRPG_ERR_INVALID_ARGUMENT, "bad argument");
   launch_mark_visible((hipStream_t)hip_stream, P, means3D, viewmatrix, present);
@@ -1965,8 +1987,7 @@ int grpg_visible_filter(int P, int M, int width, int height, const float* means3
                         const float* projmatrix, float tan_fovx, float tan_fovy, int prefiltered,
                         int* radii, float* means2D, int debug, void* hip_stream) {
   (void)M; (void)prefiltered;
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (P < 0 || width <= 0 || height <= 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "bad size");
   if (P == 0) return GRPG_OK;
   if (!means3D || !viewmatrix || !projmatrix || !radii || !means2D ||
@@ -1981,8 +2002,7 @@ int grpg_visible_filter(int P, int M, int width, int height, const float* means3
 }
 
 int grpg_pack_rgb_u8(const float* src, unsigned char* dst, size_t n, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (n > 0 && (!src || !dst)) return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL pointer");
   if (((uintptr_t)src & 15) || ((uintptr_t)dst & 3))
     return fail(GRPG_ERR_INVALID_ARGUMENT, "src must be 16-byte and dst 4-byte aligned");
@@ -1993,8 +2013,7 @@ int grpg_pack_rgb_u8(const float* src, unsigned char* dst, size_t n, void* hip_s
 
 int grpg_pack_rgb_u8_hwc(const float* src_chw, unsigned char* dst_hwc, int height, int width,
                          int truncate, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (height < 0 || width < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "negative size");
   const size_t npix = (size_t)height * (size_t)width;
   if (npix > 0 && (!src_chw || !dst_hwc)) return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL pointer");
@@ -2005,577 +2024,12 @@ int grpg_pack_rgb_u8_hwc(const float* src_chw, unsigned char* dst_hwc, int heigh
   return GRPG_OK;
 }
 
-int grpg_sky_composite_ex(const float* cube, int res, const float* ray_matrix, int ray_matrix_on_device,
-                          float fill, int clamp_out, int width, int height, const float* rgb_in,
-                          const float* acc, const unsigned char* mask, const float* jitter,
-                          float* rgb_out, float* sky_out, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (!cube || !ray_matrix || res <= 0 || width <= 0 || height <= 0)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "bad cube / ray matrix / size");
-  if ((rgb_in == nullptr) != (rgb_out == nullptr))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "rgb_in and rgb_out go together");
-  if (!rgb_out && !sky_out) return fail(GRPG_ERR_INVALID_ARGUMENT, "nothing to write");
-  launch_sky_composite((hipStream_t)hip_stream, cube, res, ray_matrix, ray_matrix_on_device, fill,
-                       clamp_out, width, height, rgb_in, acc, mask, jitter, rgb_out, sky_out);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-int grpg_sky_composite(const float* cube, int res, const float* ray_matrix, float fill,
-                       int clamp_out, int width, int height, const float* rgb_in, const float* acc,
-                       float* rgb_out, float* sky_out, void* hip_stream) {
-  return grpg_sky_composite_ex(cube, res, ray_matrix, 0, fill, clamp_out, width, height, rgb_in, acc,
-                               nullptr, nullptr, rgb_out, sky_out, hip_stream);
-}
-
-int grpg_sky_backward_ex(const float* cube, int res, const float* ray_matrix, int ray_matrix_on_device,
-                         float fill, int width, int height, const float* acc, const unsigned char* mask,
-                         const float* jitter, const float* grad_rgb, float* grad_cube, float* grad_acc,
-                         void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (!cube || !ray_matrix || !grad_rgb || res <= 0 || width <= 0 || height <= 0)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "bad cube / ray matrix / gradient / size");
-  launch_sky_backward((hipStream_t)hip_stream, cube, res, ray_matrix, ray_matrix_on_device, fill, width,
-                      height, acc, mask, jitter, grad_rgb, grad_cube, grad_acc);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-int grpg_sky_backward(const float* cube, int res, const float* ray_matrix, float fill, int width,
-                      int height, const float* acc, const float* grad_rgb, float* grad_cube,
-                      float* grad_acc, void* hip_stream) {
-  return grpg_sky_backward_ex(cube, res, ray_matrix, 0, fill, width, height, acc, nullptr, nullptr,
-                              grad_rgb, grad_cube, grad_acc, hip_stream);
-}
-
-size_t grpg_knn_workspace_bytes(int P) { return knn_workspace_bytes(P); }
-
-int grpg_knn_mean_dist2(int P, const float* points, float* mean_dists,
-                        grpg_alloc_fn workspace_alloc, void* workspace_user, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (P < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "negative size");
-  if (P == 0) return GRPG_OK;
-  if (!points || !mean_dists) return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL pointer");
-  if (!workspace_alloc) return fail(GRPG_ERR_INVALID_ARGUMENT, "workspace allocator must not be NULL");
-  char* ws = workspace_alloc(knn_workspace_bytes(P), workspace_user);
-  if (!ws) return fail(GRPG_ERR_ALLOC, "knn workspace allocation failed");
-  if ((uintptr_t)ws & 255) return fail(GRPG_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
-  launch_knn((hipStream_t)hip_stream, P, points, mean_dists, ws);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-size_t grpg_ssim_workspace_bytes(int B, int C, int height, int width) {
-  if (B <= 0 || C <= 0 || height <= 0 || width <= 0) return 0;
-  return ssim_workspace_bytes(B, C, height, width);
-}
-
-namespace {
-int ssim_check(int B, int C, int height, int width, const float* img1, const float* img2,
-               const unsigned char* mask, int mask_batch, int mask_channels) {
-  if (B <= 0 || C <= 0 || height <= 0 || width <= 0)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: B, C, height and width must be positive");
-  if ((long long)B * C * height * width > 0x7FFFFFFFll)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: B*C*H*W must be < 2^31");
-  if (!img1 || !img2) return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: NULL image pointer");
-  if (mask && ((mask_batch != 1 && mask_batch != B) || (mask_channels != 1 && mask_channels != C)))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: the mask must have 1 or B images of 1 or C channels");
-  return GRPG_OK;
-}
-}  // namespace
-
-int grpg_ssim_forward(int B, int C, int height, int width, const float* img1, const float* img2,
-                      const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
-                      float w_ssim, float* stats, float* saved, void* workspace, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (int rc = ssim_check(B, C, height, width, img1, img2, mask, mask_batch, mask_channels)) return rc;
-  if (!stats || !workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: NULL stats / workspace");
-  if ((uintptr_t)workspace & 7) return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: workspace must be 8-byte aligned");
-  launch_ssim_forward((hipStream_t)hip_stream, B, C, height, width, img1, img2, mask, mask_batch,
-                      mask_channels, w_l1, w_ssim, stats, saved, (char*)workspace);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-int grpg_ssim_backward(int B, int C, int height, int width, const float* img1, const float* img2,
-                       const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
-                       float w_ssim, const float* stats, const float* saved, const float* grad_stats,
-                       float* grad_img1, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (int rc = ssim_check(B, C, height, width, img1, img2, mask, mask_batch, mask_channels)) return rc;
-  if (!stats || !saved || !grad_stats || !grad_img1)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: NULL stats / saved partials / gradient pointer");
-  launch_ssim_backward((hipStream_t)hip_stream, B, C, height, width, img1, img2, mask, mask_batch,
-                       mask_channels, w_l1, w_ssim, stats, saved, grad_stats, grad_img1);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-namespace {
-// The H x W plane of the auxiliary and semantic entries.  what: the entry's prefix in the error text; NULL (the size
-// queries) leaves the error text alone.
-int loss_plane_check(const char* what, int height, int width) {
-  const bool sides = height > 0 && width > 0;
-  if (sides && (long long)height * width <= 0x7FFFFFFFll) return GRPG_OK;
-  if (what) g_last_error = std::string(what) + (sides ? ": H*W must be < 2^31" : ": height and width must be positive");
-  return GRPG_ERR_INVALID_ARGUMENT;
-}
-
-int aux_check(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
-              const unsigned char* sky_mask, const float* acc_obj, const unsigned char* obj_bound,
-              float lambda_depth_lidar, float lambda_sky, float lambda_reg, const void* workspace) {
-  if (int rc = loss_plane_check("aux_loss", height, width)) return rc;
-  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: NULL workspace");
-  if ((uintptr_t)workspace & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: workspace must be 16-byte aligned");
-  if (lambda_depth_lidar > 0.f && lidar_depth && (!depth || !acc))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: the lidar term needs depth and acc");
-  if (lambda_sky > 0.f && sky_mask && !acc) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: the sky term needs acc");
-  if (lambda_reg > 0.f && obj_bound && !acc_obj)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: the object term needs acc_obj");
-  return GRPG_OK;
-}
-}  // namespace
-
-size_t grpg_aux_loss_workspace_bytes(int height, int width) {
-  return loss_plane_check(nullptr, height, width) ? 0 : aux_loss_workspace_bytes(height, width);
-}
-
-int grpg_aux_loss_forward(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
-                          const unsigned char* mask, const unsigned char* sky_mask, const float* acc_obj,
-                          const unsigned char* obj_bound, float sky_scale, float lambda_depth_lidar,
-                          float lambda_sky, float lambda_reg, float* stats, void* workspace, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (int rc = aux_check(height, width, depth, acc, lidar_depth, sky_mask, acc_obj, obj_bound, lambda_depth_lidar,
-                         lambda_sky, lambda_reg, workspace))
-    return rc;
-  if (!stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: NULL stats");
-  const AuxPlanes planes{depth, acc, lidar_depth, mask, sky_mask, acc_obj, obj_bound};
-  launch_aux_loss_forward((hipStream_t)hip_stream, height, width, planes, sky_scale, lambda_depth_lidar,
-                          lambda_sky, lambda_reg, stats, (char*)workspace);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-int grpg_aux_loss_backward(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
-                           const unsigned char* mask, const unsigned char* sky_mask, const float* acc_obj,
-                           const unsigned char* obj_bound, float sky_scale, float lambda_depth_lidar,
-                           float lambda_sky, float lambda_reg, const float* grad_stats, const void* workspace,
-                           float* grad_depth, float* grad_acc, float* grad_acc_obj, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (int rc = aux_check(height, width, depth, acc, lidar_depth, sky_mask, acc_obj, obj_bound, lambda_depth_lidar,
-                         lambda_sky, lambda_reg, workspace))
-    return rc;
-  if (!grad_stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: NULL grad_stats");
-  const AuxPlanes planes{depth, acc, lidar_depth, mask, sky_mask, acc_obj, obj_bound};
-  launch_aux_loss_backward((hipStream_t)hip_stream, height, width, planes, sky_scale, lambda_depth_lidar,
-                           lambda_sky, lambda_reg, grad_stats, (const char*)workspace, grad_depth, grad_acc,
-                           grad_acc_obj);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-// ---- fused semantic cross-entropy loss (semantic_loss.hip) ----
-size_t grpg_semantic_ce_workspace_bytes(int height, int width) {
-  return loss_plane_check(nullptr, height, width) ? 0 : semantic_ce_workspace_bytes(height, width);
-}
-
-namespace {
-int semantic_ce_check(int S, int height, int width, const float* sem, const void* target, int target_bytes,
-                      int mode, const void* workspace) {
-  if (S < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: S must be at least 1");
-  if (int rc = loss_plane_check("semantic_ce", height, width)) return rc;
-  if (!sem || !target) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL sem / target");
-  if (mode != 0 && mode != 1)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: mode must be 0 (logits) or 1 (probabilities)");
-  if (target_bytes != 4 && target_bytes != 8)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: target_bytes must be 4 (int32) or 8 (int64)");
-  if (((uintptr_t)sem & 3) || ((uintptr_t)target & (uintptr_t)(target_bytes - 1)))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: sem must be 4-byte aligned, target aligned to its width");
-  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL workspace");
-  if ((uintptr_t)workspace & 15)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: workspace must be 16-byte aligned");
-  return GRPG_OK;
-}
-}  // namespace
-
-int grpg_semantic_ce_forward(int S, int height, int width, const float* sem, const void* target, int target_bytes,
-                             int mode, float* stats, unsigned char* labels, void* workspace, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (int rc = semantic_ce_check(S, height, width, sem, target, target_bytes, mode, workspace)) return rc;
-  if (!stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL stats");
-  if (((uintptr_t)stats & 3)) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: stats must be 4-byte aligned");
-  if (labels && S > 256)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: the uint8 label plane needs S <= 256");
-  launch_semantic_ce_forward((hipStream_t)hip_stream, S, height, width, sem, target, target_bytes, mode, stats,
-                             labels, (char*)workspace);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-int grpg_semantic_ce_backward(int S, int height, int width, const float* sem, const void* target, int target_bytes,
-                              int mode, const float* grad_loss, const void* workspace, float* grad_sem,
-                              void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (int rc = semantic_ce_check(S, height, width, sem, target, target_bytes, mode, workspace)) return rc;
-  if (!grad_loss || !grad_sem) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL grad_loss / grad_sem");
-  if (((uintptr_t)grad_loss & 3) || ((uintptr_t)grad_sem & 3))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: grad_loss and grad_sem must be 4-byte aligned");
-  launch_semantic_ce_backward((hipStream_t)hip_stream, S, height, width, sem, target, target_bytes, mode, grad_loss,
-                              (const char*)workspace, grad_sem);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-// ---- fused multi-tensor Adam step and densification statistics (optim.hip) ----
-namespace {
-// Both entries return without a host wait, so the pinned table an asynchronous copy reads must outlive the call: a
-// ring of growable slots, each guarded by an event recorded behind its copy.  A slot comes round again 32 calls
-// later (16 iterations of a trainer that makes both calls); the host waits for the device only when it has run
-// that far ahead of it.
-struct OptimStagingSlot {
-  char* host = nullptr;
-  size_t bytes = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-};
-constexpr int OPTIM_STAGING_SLOTS = 32;
-static_assert(sizeof(DensifyRangeDev) == 32, "the header documents 32 bytes per range");
-thread_local OptimStagingSlot g_optim_staging[OPTIM_STAGING_SLOTS];
-thread_local int g_optim_staging_next = 0;
-OptimStagingSlot* optim_staging_acquire(size_t bytes) {
-  OptimStagingSlot& b = g_optim_staging[g_optim_staging_next];
-  g_optim_staging_next = (g_optim_staging_next + 1) % OPTIM_STAGING_SLOTS;
-  if (!b.ev && hipEventCreateWithFlags(&b.ev, hipEventDisableTiming) != hipSuccess) return nullptr;
-  if (b.used) (void)hipEventSynchronize(b.ev);
-  if (b.bytes < bytes) {
-    if (b.host) (void)hipHostFree(b.host);
-    b.host = nullptr;
-    b.bytes = 0;
-    size_t cap = 4096;
-    while (cap < bytes) cap *= 2;
-    if (hipHostMalloc((void**)&b.host, cap, hipHostMallocDefault) != hipSuccess) return nullptr;
-    b.bytes = cap;
-  }
-  b.used = true;
-  return &b;
-}
-}  // namespace
-
-size_t grpg_adam_workspace_bytes(int num_segments) {
-  if (num_segments <= 0) return 0;
-  return sizeof(AdamSegmentDev) * (size_t)num_segments;
-}
-
-int grpg_adam_step(const grpg_adam_segment* segments, int num_segments, grpg_alloc_fn table_alloc,
-                   void* table_user, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (num_segments < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: negative segment count");
-  if (num_segments == 0) return GRPG_OK;
-  if (!segments) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: NULL segment table");
-  if (!table_alloc) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: NULL table allocator");
-  int live = 0;
-  unsigned long long chunks = 0;
-  for (int i = 0; i < num_segments; i++) {
-    const grpg_adam_segment& g = segments[i];
-    if (g.n < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: segment with negative n");
-    if (g.n == 0) continue;
-    if (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq)
-      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: segment with a NULL array and n > 0");
-    if (((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 3)
-      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: arrays must be 4-byte aligned");
-    if (!std::isfinite(g.bc2_sqrt) || !(g.bc2_sqrt > 0.f))
-      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: bc2_sqrt must be finite and positive");
-    if (!std::isfinite(g.step_size) || !std::isfinite(g.beta2) || !std::isfinite(g.one_minus_beta1) ||
-        !std::isfinite(g.one_minus_beta2) || !std::isfinite(g.eps))
-      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: non-finite coefficient");
-    live++;
-    chunks += ((unsigned long long)g.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
-  }
-  if (live == 0) return GRPG_OK;              // nothing but empty tensors: no launch
-  if (chunks > 0xFFFFFFFFull) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: more than 2^32 chunks of 4096 elements");
-  hipStream_t stream = (hipStream_t)hip_stream;
-  const size_t bytes = sizeof(AdamSegmentDev) * (size_t)live;
-  OptimStagingSlot* stg = optim_staging_acquire(bytes);
-  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
-  AdamSegmentDev* host = (AdamSegmentDev*)stg->host;
-  uint32_t first = 0;
-  int k = 0;
-  for (int i = 0; i < num_segments; i++) {
-    const grpg_adam_segment& g = segments[i];
-    if (g.n == 0) continue;
-    AdamSegmentDev& d = host[k++];
-    d.param = g.param; d.grad = g.grad; d.exp_avg = g.exp_avg; d.exp_avg_sq = g.exp_avg_sq;
-    d.n = (unsigned long long)g.n;
-    d.step_size = g.step_size; d.bc2_sqrt = g.bc2_sqrt; d.beta2 = g.beta2;
-    d.one_minus_beta1 = g.one_minus_beta1; d.one_minus_beta2 = g.one_minus_beta2; d.eps = g.eps;
-    d.first_chunk = first;
-    d.vec = (((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15) == 0;
-    first += (uint32_t)((d.n + ADAM_CHUNK - 1) / ADAM_CHUNK);
-  }
-  char* dev = table_alloc(grpg_adam_workspace_bytes(num_segments), table_user);
-  if (!dev) return fail(GRPG_ERR_ALLOC, "adam_step: the table allocator returned NULL");
-  if ((uintptr_t)dev & 7) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: the table must be 8-byte aligned");
-  HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipEventRecord(stg->ev, stream));
-  launch_adam_step(stream, (const AdamSegmentDev*)dev, live, first);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-int grpg_densify_stats(int P, const float* grad_xyz, const int* radii, const grpg_range* ranges, int num_ranges,
-                       float* const* accum, float* const* denom, float* const* max_radii,
-                       grpg_alloc_fn table_alloc, void* table_user, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (P < 0 || num_ranges < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: negative count");
-  if (P == 0 || num_ranges == 0) return GRPG_OK;
-  if (!grad_xyz || !radii) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: NULL grad_xyz / radii");
-  if (!ranges || !accum || !denom || !max_radii)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: NULL range table");
-  if (!table_alloc) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: NULL table allocator");
-  int live = 0, prev_end = 0;
-  for (int i = 0; i < num_ranges; i++) {
-    const grpg_range& r = ranges[i];
-    if (r.start < prev_end || r.end < r.start || r.end > P)
-      return fail(GRPG_ERR_INVALID_ARGUMENT,
-                  "densify_stats: ranges must be half-open [start, end), ascending, disjoint and within [0, P)");
-    prev_end = r.end;
-    if (r.end == r.start) continue;
-    if (!accum[i] || !denom[i] || !max_radii[i])
-      return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: non-empty range with a NULL array");
-    live++;
-  }
-  if (live == 0) return GRPG_OK;
-  hipStream_t stream = (hipStream_t)hip_stream;
-  const size_t bytes = sizeof(DensifyRangeDev) * (size_t)live;
-  OptimStagingSlot* stg = optim_staging_acquire(bytes);
-  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
-  DensifyRangeDev* host = (DensifyRangeDev*)stg->host;
-  int k = 0;
-  for (int i = 0; i < num_ranges; i++) {
-    if (ranges[i].end == ranges[i].start) continue;
-    host[k++] = DensifyRangeDev{accum[i], denom[i], max_radii[i], ranges[i].start, ranges[i].end};
-  }
-  char* dev = table_alloc(sizeof(DensifyRangeDev) * (size_t)num_ranges, table_user);
-  if (!dev) return fail(GRPG_ERR_ALLOC, "densify_stats: the table allocator returned NULL");
-  if ((uintptr_t)dev & 7) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: the table must be 8-byte aligned");
-  HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipEventRecord(stg->ev, stream));
-  launch_densify_stats(stream, P, grad_xyz, radii, (const DensifyRangeDev*)dev, live);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-// ---- fused mono-normal loss (normal_loss.hip) ----
-size_t grpg_normal_loss_workspace_bytes(int height, int width) {
-  return loss_plane_check(nullptr, height, width) ? 0 : normal_loss_workspace_bytes(height, width);
-}
-
-namespace {
-int normal_loss_check(int height, int width, const float* normals, const float* mono_normal, const float* rotation,
-                      int top_rows, const void* workspace) {
-  if (int rc = loss_plane_check("normal_loss", height, width)) return rc;
-  if (top_rows < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: top_rows must not be negative");
-  if (!normals || !mono_normal || !rotation)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: NULL normals / mono_normal / rotation");
-  if (((uintptr_t)normals | (uintptr_t)mono_normal | (uintptr_t)rotation) & 3)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: normals, mono_normal and rotation must be 4-byte aligned");
-  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: NULL workspace");
-  if ((uintptr_t)workspace & 15)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: workspace must be 16-byte aligned");
-  return GRPG_OK;
-}
-}  // namespace
-
-int grpg_normal_loss_forward(int height, int width, const float* normals, const float* mono_normal,
-                             const float* rotation, int rot_row_stride, int rot_col_stride, const unsigned char* mask,
-                             const unsigned char* sky_mask, int normalize, int top_rows, float* stats,
-                             void* workspace, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (int rc = normal_loss_check(height, width, normals, mono_normal, rotation, top_rows, workspace)) return rc;
-  if (!stats || ((uintptr_t)stats & 3))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: stats must be a 4-byte aligned pointer");
-  const NormalPlanes planes{normals, mono_normal, rotation, rot_row_stride, rot_col_stride, mask, sky_mask};
-  launch_normal_loss_forward((hipStream_t)hip_stream, height, width, planes, normalize ? 1 : 0, top_rows, stats,
-                             (char*)workspace);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-int grpg_normal_loss_backward(int height, int width, const float* normals, const float* mono_normal,
-                              const float* rotation, int rot_row_stride, int rot_col_stride, const unsigned char* mask,
-                              const unsigned char* sky_mask, int normalize, int top_rows, const float* grad_stats,
-                              const void* workspace, float* grad_normals, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (int rc = normal_loss_check(height, width, normals, mono_normal, rotation, top_rows, workspace)) return rc;
-  if (!grad_stats || !grad_normals || (((uintptr_t)grad_stats | (uintptr_t)grad_normals) & 3))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: grad_stats and grad_normals must be 4-byte aligned pointers");
-  const NormalPlanes planes{normals, mono_normal, rotation, rot_row_stride, rot_col_stride, mask, sky_mask};
-  launch_normal_loss_backward((hipStream_t)hip_stream, height, width, planes, normalize ? 1 : 0, top_rows, grad_stats,
-                              (const char*)workspace, grad_normals);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-// ---- fused scale-flatten / opacity-sparse regularisers (reg_loss.hip) ----
-size_t grpg_reg_loss_workspace_bytes(int num_segments) {
-  return num_segments < 0 ? 0 : reg_loss_workspace_bytes(num_segments);
-}
-
-namespace {
-// Checks every argument, then uploads the live segments into table slot `which` of the workspace through the pinned
-// ring and fills args / table.  Nothing is queued before the last check has passed.
-int reg_loss_prepare(const float* scaling, long long n_scaling, int scale_activated, const grpg_reg_segment* segments,
-                     int num_segments, int opacity_activated, const int* radii, long long n_radii, float lam_scale,
-                     float lam_opacity, void* workspace, const bool backward, const bool want_scale, int which,
-                     hipStream_t stream, RegLossArgs& R, const RegSegDev*& table) {
-  R = RegLossArgs{};
-  R.scale_on = lam_scale > 0.f && (!backward || want_scale);
-  R.opacity_on = lam_opacity > 0.f;
-  R.scale_activated = scale_activated ? 1 : 0;
-  R.opacity_activated = opacity_activated ? 1 : 0;
-  R.lam_scale = lam_scale;
-  R.lam_opacity = lam_opacity;
-  table = nullptr;
-  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: NULL workspace");
-  if ((uintptr_t)workspace & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: workspace must be 16-byte aligned");
-  if (num_segments < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: negative segment count");
-  if (R.scale_on) {
-    if (n_scaling < 0 || n_scaling > 0x7FFFFFFFll / 3)
-      return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: n_scaling must be in [0, (2^31 - 1) / 3]");
-    if (n_scaling > 0 && !scaling) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: NULL scaling with n_scaling > 0");
-    if ((uintptr_t)scaling & 3) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: scaling must be 4-byte aligned");
-    R.n_scaling = n_scaling;
-    R.scaling = scaling;
-  }
-  if (!R.opacity_on) return GRPG_OK;
-  if (num_segments > 0 && !segments) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: NULL segment table");
-  long long total = 0;
-  int live = 0;
-  bool any_grad = false;
-  for (int i = 0; i < num_segments; i++) {
-    const grpg_reg_segment& g = segments[i];
-    if (g.n < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: segment with negative n");
-    if (g.n == 0) continue;
-    if (!g.opacity) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: segment with a NULL opacity array and n > 0");
-    if (((uintptr_t)g.opacity | (uintptr_t)g.grad_opacity) & 3)
-      return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: opacity arrays must be 4-byte aligned");
-    total += g.n;
-    if (total > 0x7FFFFFFFll) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: more than 2^31 - 1 Gaussians");
-    any_grad = any_grad || g.grad_opacity != nullptr;
-    live++;
-  }
-  if (n_radii != total)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: the length of radii must be the sum of the segments' n");
-  if (total > 0 && (!radii || ((uintptr_t)radii & 3)))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: radii must be a 4-byte aligned pointer");
-  R.n_opacity = total;
-  R.radii = radii;
-  if (backward && !any_grad) {          // no opacity gradient is wanted: the term costs nothing
-    R.opacity_on = 0;
-    return GRPG_OK;
-  }
-  if (live == 0) return GRPG_OK;
-  const size_t bytes = sizeof(RegSegDev) * (size_t)live;
-  OptimStagingSlot* stg = optim_staging_acquire(bytes);
-  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
-  RegSegDev* host = (RegSegDev*)stg->host;
-  long long start = 0;
-  int k = 0;
-  for (int i = 0; i < num_segments; i++) {
-    const grpg_reg_segment& g = segments[i];
-    if (g.n == 0) continue;
-    host[k++] = RegSegDev{g.opacity, backward ? g.grad_opacity : nullptr, start, g.n};
-    start += g.n;
-  }
-  char* dev = (char*)workspace + reg_loss_table_offset(which, num_segments);
-  HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipEventRecord(stg->ev, stream));
-  R.num_live = live;
-  table = (const RegSegDev*)dev;
-  return GRPG_OK;
-}
-}  // namespace
-
-int grpg_reg_loss_forward(const float* scaling, long long n_scaling, int scale_activated,
-                          const grpg_reg_segment* segments, int num_segments, int opacity_activated, const int* radii,
-                          long long n_radii, float lambda_scale_flatten, float lambda_opacity_sparse, float* stats,
-                          void* workspace, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (!stats || ((uintptr_t)stats & 3))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: stats must be a 4-byte aligned pointer");
-  hipStream_t stream = (hipStream_t)hip_stream;
-  RegLossArgs R;
-  const RegSegDev* table;
-  if (int rc = reg_loss_prepare(scaling, n_scaling, scale_activated, segments, num_segments, opacity_activated, radii,
-                                n_radii, lambda_scale_flatten, lambda_opacity_sparse, workspace, false, true, 0,
-                                stream, R, table))
-    return rc;
-  launch_reg_loss_forward(stream, R, table, stats, (char*)workspace);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-int grpg_reg_loss_backward(const float* scaling, long long n_scaling, int scale_activated,
-                           const grpg_reg_segment* segments, int num_segments, int opacity_activated, const int* radii,
-                           long long n_radii, float lambda_scale_flatten, float lambda_opacity_sparse,
-                           const float* grad_stats, void* workspace, float* grad_scaling, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (!grad_stats || (((uintptr_t)grad_stats | (uintptr_t)grad_scaling) & 3))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: grad_stats and grad_scaling must be 4-byte aligned pointers");
-  hipStream_t stream = (hipStream_t)hip_stream;
-  RegLossArgs R;
-  const RegSegDev* table;
-  if (int rc = reg_loss_prepare(scaling, n_scaling, scale_activated, segments, num_segments, opacity_activated, radii,
-                                n_radii, lambda_scale_flatten, lambda_opacity_sparse, workspace, true,
-                                grad_scaling != nullptr, 1, stream, R, table))
-    return rc;
-  if (!R.scale_on && !R.opacity_on) return GRPG_OK;
-  launch_reg_loss_backward(stream, R, table, grad_stats, (const char*)workspace, R.scale_on ? grad_scaling : nullptr);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
-// ---- PSNR (metrics.hip) ----
-size_t grpg_psnr_workspace_bytes(void) { return psnr_workspace_bytes(); }
-
-int grpg_psnr_forward(int C, int height, int width, const float* img1, const float* img2, const unsigned char* mask,
-                      float* stats, void* workspace, void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
-  if (C < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: C must be at least 1");
-  if (int rc = loss_plane_check("psnr", height, width)) return rc;
-  if (!img1 || !img2 || !stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: NULL img1 / img2 / stats");
-  if (((uintptr_t)img1 | (uintptr_t)img2 | (uintptr_t)stats) & 3)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: img1, img2 and stats must be 4-byte aligned");
-  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: NULL workspace");
-  if ((uintptr_t)workspace & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: workspace must be 16-byte aligned");
-  launch_psnr_forward((hipStream_t)hip_stream, C, height, width, img1, img2, mask, stats, (char*)workspace);
-  HIP_TRY(hipGetLastError());
-  return GRPG_OK;
-}
-
 int grpg_debug_export(int P, int R, int width, int height, const char* geom_buffer,
                       const char* binning_buffer, const char* image_buffer, uint64_t* keys_sorted,
                       uint32_t* point_list, uint32_t* ranges, uint32_t* n_contrib, float* means2D,
                       float* depths, float* conic_opacity, float* rgb, uint32_t* tiles_touched,
                       void* hip_stream) {
-  g_last_error.clear();
-  if (int rc = ensure_device()) return rc;
+  if (int rc = begin_call()) return rc;
   if (P < 0 || R < 0 || !geom_buffer || !binning_buffer || !image_buffer)
     return fail(GRPG_ERR_INVALID_ARGUMENT, "bad argument");
   hipStream_t stream = (hipStream_t)hip_stream;

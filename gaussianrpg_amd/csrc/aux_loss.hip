@@ -41,6 +41,7 @@
 // Stats vector (float32 [9]): [0] total, [1] lidar term, [2] sky term (after sky_scale), [3] obj term,
 // [4] N, [5] k, [6] t (the k-th smallest error; 0 when k == 0), [7] c_lt, [8] c_eq.  The counts are
 // exact in float32 only below 2^24; the workspace header (AuxState) keeps them as exact integers.
+#include "abi_util.h"
 #include "common.h"
 #include "reduce.h"
 
@@ -459,6 +460,17 @@ int aux_grid(const int n) {
 
 bool aligned(const void* p, const uintptr_t a) { return p == nullptr || ((uintptr_t)p & (a - 1)) == 0; }
 
+// The entries' planes, H*W each, NULL when absent.
+struct AuxPlanes {
+  const float* depth;
+  const float* acc;
+  const float* lidar;
+  const unsigned char* mask;
+  const unsigned char* sky;
+  const float* acc_obj;
+  const unsigned char* bound;
+};
+
 AuxArgs make_args(const int H, const int W, const AuxPlanes& P, const float sky_scale,
                   const float lam_lidar, const float lam_sky, const float lam_reg) {
   AuxArgs A;
@@ -506,15 +518,46 @@ AuxWs make_ws(char* base, const int n) {
   return w;
 }
 
+int aux_check(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
+              const unsigned char* sky_mask, const float* acc_obj, const unsigned char* obj_bound,
+              float lambda_depth_lidar, float lambda_sky, float lambda_reg, const void* workspace) {
+  if (int rc = loss_plane_check("aux_loss", height, width)) return rc;
+  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: NULL workspace");
+  if ((uintptr_t)workspace & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: workspace must be 16-byte aligned");
+  if (lambda_depth_lidar > 0.f && lidar_depth && (!depth || !acc))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: the lidar term needs depth and acc");
+  if (lambda_sky > 0.f && sky_mask && !acc) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: the sky term needs acc");
+  if (lambda_reg > 0.f && obj_bound && !acc_obj)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: the object term needs acc_obj");
+  return GRPG_OK;
+}
+
 }  // namespace
 
-size_t aux_loss_workspace_bytes(const int H, const int W) { return aux_layout(H * W).total; }
+}  // namespace grpg
 
-void launch_aux_loss_forward(hipStream_t st, const int H, const int W, const AuxPlanes& planes,
-                             const float sky_scale, const float lam_lidar, const float lam_sky,
-                             const float lam_reg, float* stats, char* workspace) {
-  const AuxArgs A = make_args(H, W, planes, sky_scale, lam_lidar, lam_sky, lam_reg);
-  const AuxWs ws = make_ws(workspace, A.n);
+using namespace grpg;
+
+// ---- C ABI (include/grpg_rasterizer.h) ----
+extern "C" {
+
+size_t grpg_aux_loss_workspace_bytes(int height, int width) {
+  return loss_plane_check(nullptr, height, width) ? 0 : aux_layout(height * width).total;
+}
+
+int grpg_aux_loss_forward(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
+                          const unsigned char* mask, const unsigned char* sky_mask, const float* acc_obj,
+                          const unsigned char* obj_bound, float sky_scale, float lambda_depth_lidar,
+                          float lambda_sky, float lambda_reg, float* stats, void* workspace, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (int rc = aux_check(height, width, depth, acc, lidar_depth, sky_mask, acc_obj, obj_bound, lambda_depth_lidar,
+                         lambda_sky, lambda_reg, workspace))
+    return rc;
+  if (!stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: NULL stats");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const AuxPlanes planes{depth, acc, lidar_depth, mask, sky_mask, acc_obj, obj_bound};
+  const AuxArgs A = make_args(height, width, planes, sky_scale, lambda_depth_lidar, lambda_sky, lambda_reg);
+  const AuxWs ws = make_ws((char*)workspace, A.n);
   if (A.lidar_on) (void)hipMemsetAsync(ws.hist, 0, 3 * AX_BINS * sizeof(unsigned int), st);
   aux_forward_kernel<<<A.nwg, AX_THREADS, 0, st>>>(A, ws);
   if (A.lidar_on) {
@@ -526,16 +569,28 @@ void launch_aux_loss_forward(hipStream_t st, const int H, const int W, const Aux
     aux_lidar_sum_kernel<<<A.nwg, AX_THREADS, 0, st>>>(A, ws);
   }
   aux_reduce_kernel<<<1, REDUCE_THREADS, 0, st>>>(A, ws, stats);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
 }
 
-void launch_aux_loss_backward(hipStream_t st, const int H, const int W, const AuxPlanes& planes,
-                              const float sky_scale, const float lam_lidar, const float lam_sky,
-                              const float lam_reg, const float* grad_stats, const char* workspace,
-                              float* grad_depth, float* grad_acc, float* grad_acc_obj) {
-  AuxArgs A = make_args(H, W, planes, sky_scale, lam_lidar, lam_sky, lam_reg);
+int grpg_aux_loss_backward(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
+                           const unsigned char* mask, const unsigned char* sky_mask, const float* acc_obj,
+                           const unsigned char* obj_bound, float sky_scale, float lambda_depth_lidar,
+                           float lambda_sky, float lambda_reg, const float* grad_stats, const void* workspace,
+                           float* grad_depth, float* grad_acc, float* grad_acc_obj, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (int rc = aux_check(height, width, depth, acc, lidar_depth, sky_mask, acc_obj, obj_bound, lambda_depth_lidar,
+                         lambda_sky, lambda_reg, workspace))
+    return rc;
+  if (!grad_stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "aux_loss: NULL grad_stats");
+  const AuxPlanes planes{depth, acc, lidar_depth, mask, sky_mask, acc_obj, obj_bound};
+  AuxArgs A = make_args(height, width, planes, sky_scale, lambda_depth_lidar, lambda_sky, lambda_reg);
   A.vec = A.vec && aligned(grad_depth, 16) && aligned(grad_acc, 16) && aligned(grad_acc_obj, 16);
-  const AuxWs ws = make_ws(const_cast<char*>(workspace), A.n);
-  aux_backward_kernel<<<A.nwg, AX_THREADS, 0, st>>>(A, ws.st, grad_stats, grad_depth, grad_acc, grad_acc_obj);
+  const AuxWs ws = make_ws((char*)const_cast<void*>(workspace), A.n);
+  aux_backward_kernel<<<A.nwg, AX_THREADS, 0, (hipStream_t)hip_stream>>>(A, ws.st, grad_stats, grad_depth, grad_acc,
+                                                                          grad_acc_obj);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
 }
 
-}  // namespace grpg
+}  // extern "C"

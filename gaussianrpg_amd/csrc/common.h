@@ -627,18 +627,6 @@ __device__ __forceinline__ void get_rect(float px, float py, int max_radius, int
 }
 #endif
 
-// sky cube map (sky.hip)
-void launch_sky_composite(hipStream_t st, const float* cube, int res, const float* m9, int m_on_device,
-                          float fill, int clamp_out, int W, int H, const float* rgb_in, const float* acc,
-                          const unsigned char* mask, const float* jitter, float* rgb_out, float* sky_out);
-void launch_sky_backward(hipStream_t st, const float* cube, int res, const float* m9, int m_on_device,
-                         float fill, int W, int H, const float* acc, const unsigned char* mask,
-                         const float* jitter, const float* grad_rgb, float* grad_cube, float* grad_acc);
-
-// distCUDA2 (knn.hip): mean squared distance to the 3 nearest other points.
-size_t knn_workspace_bytes(int P);
-void launch_knn(hipStream_t s, int P, const float* points, float* mean_dists, char* workspace);
-
 // Feature planes of a composed frame (features.hip): F = 3 * normals + S channels per Gaussian, normals first.
 // One row per segment, next to its SegmentDev row: the model's semantic array and where its gradients go.
 struct FeatureSegDev {
@@ -672,109 +660,5 @@ void launch_compose_features(hipStream_t st, int P, const SegmentDev* segs, cons
 void launch_compose_features_backward(hipStream_t st, int P, const SegmentDev* segs, const FeatureSegDev* fsegs,
                                       int nseg, int S, int normals, const float* campos, const float* dL_dfeatures,
                                       float* partials, uint32_t nslots, float* dL_dposes);
-
-// fused SSIM + L1 loss (ssim.hip)
-size_t ssim_workspace_bytes(int B, int C, int H, int W);
-void launch_ssim_forward(hipStream_t st, int B, int C, int H, int W, const float* x1, const float* x2,
-                         const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
-                         float w_ssim, float* stats, float* saved, char* workspace);
-void launch_ssim_backward(hipStream_t st, int B, int C, int H, int W, const float* x1, const float* x2,
-                          const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
-                          float w_ssim, const float* stats, const float* saved, const float* grad_stats,
-                          float* grad_x1);
-
-// fused lidar-depth / sky / object-alpha losses (aux_loss.hip).  Planes H*W, NULL when absent.
-struct AuxPlanes {
-  const float* depth;
-  const float* acc;
-  const float* lidar;
-  const unsigned char* mask;
-  const unsigned char* sky;
-  const float* acc_obj;
-  const unsigned char* bound;
-};
-size_t aux_loss_workspace_bytes(int H, int W);
-void launch_aux_loss_forward(hipStream_t st, int H, int W, const AuxPlanes& planes, float sky_scale,
-                             float lam_lidar, float lam_sky, float lam_reg, float* stats, char* workspace);
-void launch_aux_loss_backward(hipStream_t st, int H, int W, const AuxPlanes& planes, float sky_scale,
-                              float lam_lidar, float lam_sky, float lam_reg, const float* grad_stats,
-                              const char* workspace, float* grad_depth, float* grad_acc, float* grad_acc_obj);
-
-// fused semantic cross-entropy loss (semantic_loss.hip).  sem [S,H,W] float32, target [H,W] int64 / int32
-// (target_bytes 8 / 4), mode 0 = logits, 1 = probabilities; labels NULL or uint8 [H,W] (S <= 256).
-size_t semantic_ce_workspace_bytes(int H, int W);
-void launch_semantic_ce_forward(hipStream_t st, int S, int H, int W, const float* sem, const void* target,
-                                int target_bytes, int mode, float* stats, unsigned char* labels, char* workspace);
-void launch_semantic_ce_backward(hipStream_t st, int S, int H, int W, const float* sem, const void* target,
-                                 int target_bytes, int mode, const float* grad_loss, const char* workspace,
-                                 float* grad_sem);
-
-// fused mono-normal loss (normal_loss.hip).  normals / mono [3,H,W] float32; rot: the 3x3 rotation read through its
-// row and column element strides; mask / sky uint8 [H,W] or NULL.
-struct NormalPlanes {
-  const float* normals;
-  const float* mono;
-  const float* rot;
-  int rot_row_stride, rot_col_stride;
-  const unsigned char* mask;
-  const unsigned char* sky;
-};
-size_t normal_loss_workspace_bytes(int H, int W);
-void launch_normal_loss_forward(hipStream_t st, int H, int W, const NormalPlanes& planes, int normalize, int top_rows,
-                                float* stats, char* workspace);
-void launch_normal_loss_backward(hipStream_t st, int H, int W, const NormalPlanes& planes, int normalize,
-                                 int top_rows, const float* grad_stats, const char* workspace, float* grad_normals);
-
-// fused scale-flatten / opacity-sparse regularisers (reg_loss.hip).  The device segment table api.hip uploads into the
-// workspace: slot 0 by the forward, slot 1 (with the gradient pointers) by the backward.
-struct RegSegDev {
-  const float* x;                          // the model's raw opacity [n]
-  float* grad;                             // its gradient [n], or NULL (forward; not wanted)
-  long long start;                         // first flat index of the composed order
-  long long n;                             // > 0
-};
-struct RegLossArgs {
-  int scale_on, opacity_on;
-  int scale_activated, opacity_activated;
-  long long n_scaling;                     // N of scaling [N,3]
-  long long n_opacity;                     // sum of the segments' n = the length of radii
-  int num_live;                            // segments with n > 0 in the device table
-  float lam_scale, lam_opacity;
-  const float* scaling;
-  const int* radii;
-};
-size_t reg_loss_workspace_bytes(int num_segments);
-size_t reg_loss_table_offset(int which, int num_segments);
-void launch_reg_loss_forward(hipStream_t st, const RegLossArgs& args, const RegSegDev* segs, float* stats,
-                             char* workspace);
-void launch_reg_loss_backward(hipStream_t st, const RegLossArgs& args, const RegSegDev* segs, const float* grad_stats,
-                              const char* workspace, float* grad_scaling);
-
-// PSNR (metrics.hip).  img1 / img2 [C,H,W] float32, mask uint8 [H,W] or NULL; stats [2]: psnr, mse.
-size_t psnr_workspace_bytes();
-void launch_psnr_forward(hipStream_t st, int C, int H, int W, const float* img1, const float* img2,
-                         const unsigned char* mask, float* stats, char* workspace);
-
-// fused multi-tensor Adam step and densification statistics (optim.hip).  The device tables api.hip uploads.
-constexpr uint32_t ADAM_CHUNK = 4096;      // elements per unit of work; a chunk never straddles two segments
-struct AdamSegmentDev {
-  float* param;
-  const float* grad;
-  float* exp_avg;
-  float* exp_avg_sq;
-  unsigned long long n;                    // elements (> 0)
-  float step_size, bc2_sqrt, beta2, one_minus_beta1, one_minus_beta2, eps;
-  uint32_t first_chunk;                    // chunks of the segments before this one
-  uint32_t vec;                            // all four arrays 16-byte aligned: 16-byte loads and stores
-};
-struct DensifyRangeDev {
-  float* accum;                            // [n, 2]
-  float* denom;                            // [n]
-  float* max_radii;                        // [n]
-  int start, end;                          // half-open range of the composed frame, n = end - start > 0
-};
-void launch_adam_step(hipStream_t st, const AdamSegmentDev* table, int num_segments, uint32_t total_chunks);
-void launch_densify_stats(hipStream_t st, int P, const float* grad_xyz, const int* radii,
-                          const DensifyRangeDev* ranges, int num_ranges);
 
 }  // namespace grpg

@@ -20,6 +20,7 @@
 // so the result is bit-identical to oracle/knn_oracle.py.
 #include <cfloat>
 
+#include "abi_util.h"
 #include "common.h"
 
 namespace grpg {
@@ -257,7 +258,7 @@ knn_search_kernel(const int P, const float4* __restrict__ spts, const float* __r
   if (live) out[__float_as_uint(q.w)] = (best[0] + best[1] + best[2]) / 3.0f;
 }
 
-size_t knn_workspace_bytes(const int P) {
+static size_t knn_workspace_bytes(const int P) {
   const size_t n = (size_t)(P > 0 ? P : 1);
   const size_t nchunks = (n + RS_CHUNK - 1) / RS_CHUNK;
   const size_t nboxes = (n + KNN_BOX - 1) / KNN_BOX;
@@ -270,8 +271,26 @@ size_t knn_workspace_bytes(const int P) {
   return o;
 }
 
-void launch_knn(hipStream_t s, const int P, const float* points, float* mean_dists, char* ws) {
-  if (P <= 0) return;
+}  // namespace grpg
+
+using namespace grpg;
+
+// ---- C ABI (include/grpg_rasterizer.h) ----
+extern "C" {
+
+size_t grpg_knn_workspace_bytes(int P) { return knn_workspace_bytes(P); }
+
+int grpg_knn_mean_dist2(int P, const float* points, float* mean_dists,
+                        grpg_alloc_fn workspace_alloc, void* workspace_user, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (P < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "negative size");
+  if (P == 0) return GRPG_OK;
+  if (!points || !mean_dists) return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL pointer");
+  if (!workspace_alloc) return fail(GRPG_ERR_INVALID_ARGUMENT, "workspace allocator must not be NULL");
+  char* ws = workspace_alloc(knn_workspace_bytes(P), workspace_user);
+  if (!ws) return fail(GRPG_ERR_ALLOC, "knn workspace allocation failed");
+  if ((uintptr_t)ws & 255) return fail(GRPG_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)hip_stream;
   const size_t n = (size_t)P;
   const size_t nchunks = (n + RS_CHUNK - 1) / RS_CHUNK;
   const int nboxes = (int)((n + KNN_BOX - 1) / KNN_BOX);
@@ -298,6 +317,8 @@ void launch_knn(hipStream_t s, const int P, const float* points, float* mean_dis
   knn_gather_boxes_kernel<<<nboxes, 256, 0, s>>>(P, points, order, spts, boxes);
   knn_search_kernel<<<(P + KNN_TILE - 1) / KNN_TILE, KNN_TILE, 0, s>>>(P, spts, boxes, nboxes,
                                                                       mean_dists);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
 }
 
-}  // namespace grpg
+}  // extern "C"

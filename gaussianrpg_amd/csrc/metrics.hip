@@ -10,6 +10,7 @@
 // calls give identical bits; no atomics.
 // Stats (float32 [2]): [0] psnr, [1] mse.  An empty selection gives NaN in both; identical images give mse 0 and
 // psnr +inf.  Bytes per selected pixel: 8 C + 1 with a mask.
+#include "abi_util.h"
 #include "common.h"
 #include "reduce.h"
 
@@ -63,16 +64,34 @@ psnr_reduce_kernel(const int C, const int nwg, const double* __restrict__ part, 
 
 }  // namespace
 
-size_t psnr_workspace_bytes() { return PS_CNT_OFF + sizeof(unsigned int) * PS_MAX_WG; }
+}  // namespace grpg
 
-void launch_psnr_forward(hipStream_t st, const int C, const int H, const int W, const float* img1, const float* img2,
-                         const unsigned char* mask, float* stats, char* workspace) {
-  const int n = H * W;
+using namespace grpg;
+
+// ---- C ABI (include/grpg_rasterizer.h) ----
+extern "C" {
+
+size_t grpg_psnr_workspace_bytes(void) { return PS_CNT_OFF + sizeof(unsigned int) * PS_MAX_WG; }
+
+int grpg_psnr_forward(int C, int height, int width, const float* img1, const float* img2, const unsigned char* mask,
+                      float* stats, void* workspace, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (C < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: C must be at least 1");
+  if (int rc = loss_plane_check("psnr", height, width)) return rc;
+  if (!img1 || !img2 || !stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: NULL img1 / img2 / stats");
+  if (((uintptr_t)img1 | (uintptr_t)img2 | (uintptr_t)stats) & 3)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: img1, img2 and stats must be 4-byte aligned");
+  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: NULL workspace");
+  if ((uintptr_t)workspace & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "psnr: workspace must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int n = height * width;
   const int nwg = max(1, min(PS_MAX_WG, (n + PS_THREADS - 1) / PS_THREADS));
   double* part = (double*)workspace;
-  unsigned int* cnt = (unsigned int*)(workspace + PS_CNT_OFF);
+  unsigned int* cnt = (unsigned int*)((char*)workspace + PS_CNT_OFF);
   psnr_forward_kernel<<<nwg, PS_THREADS, 0, st>>>(C, n, nwg, img1, img2, mask, part, cnt);
   psnr_reduce_kernel<<<1, REDUCE_THREADS, 0, st>>>(C, nwg, part, cnt, stats);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
 }
 
-}  // namespace grpg
+}  // extern "C"

@@ -33,6 +33,7 @@
 //
 // Bytes per pixel: forward 24 + masks (1 each) at a selected pixel, the masks alone otherwise; backward 36 + masks
 // at a selected pixel, 12 + masks otherwise.
+#include "abi_util.h"
 #include "common.h"
 #include "reduce.h"
 
@@ -221,6 +222,17 @@ NlWs make_ws(char* base) {
   return w;
 }
 
+// The entries' planes.  normals / mono [3,H,W] float32; rot: the 3x3 rotation read through its row and column
+// element strides; mask / sky uint8 [H,W] or NULL.
+struct NormalPlanes {
+  const float* normals;
+  const float* mono;
+  const float* rot;
+  int rot_row_stride, rot_col_stride;
+  const unsigned char* mask;
+  const unsigned char* sky;
+};
+
 NlArgs make_args(const int H, const int W, const NormalPlanes& P, const int normalize, const int top_rows) {
   NlArgs A;
   A.n = H * W;
@@ -238,24 +250,65 @@ NlArgs make_args(const int H, const int W, const NormalPlanes& P, const int norm
   return A;
 }
 
+int normal_loss_check(int height, int width, const float* normals, const float* mono_normal, const float* rotation,
+                      int top_rows, const void* workspace) {
+  if (int rc = loss_plane_check("normal_loss", height, width)) return rc;
+  if (top_rows < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: top_rows must not be negative");
+  if (!normals || !mono_normal || !rotation)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: NULL normals / mono_normal / rotation");
+  if (((uintptr_t)normals | (uintptr_t)mono_normal | (uintptr_t)rotation) & 3)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: normals, mono_normal and rotation must be 4-byte aligned");
+  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: NULL workspace");
+  if ((uintptr_t)workspace & 15)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: workspace must be 16-byte aligned");
+  return GRPG_OK;
+}
+
 }  // namespace
 
-size_t normal_loss_workspace_bytes(const int H, const int W) { return NL_END; }
+}  // namespace grpg
 
-void launch_normal_loss_forward(hipStream_t st, const int H, const int W, const NormalPlanes& planes,
-                                const int normalize, const int top_rows, float* stats, char* workspace) {
-  const NlArgs A = make_args(H, W, planes, normalize, top_rows);
-  const NlWs ws = make_ws(workspace);
+using namespace grpg;
+
+// ---- C ABI (include/grpg_rasterizer.h) ----
+extern "C" {
+
+size_t grpg_normal_loss_workspace_bytes(int height, int width) {
+  return loss_plane_check(nullptr, height, width) ? 0 : NL_END;
+}
+
+int grpg_normal_loss_forward(int height, int width, const float* normals, const float* mono_normal,
+                             const float* rotation, int rot_row_stride, int rot_col_stride, const unsigned char* mask,
+                             const unsigned char* sky_mask, int normalize, int top_rows, float* stats,
+                             void* workspace, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (int rc = normal_loss_check(height, width, normals, mono_normal, rotation, top_rows, workspace)) return rc;
+  if (!stats || ((uintptr_t)stats & 3))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: stats must be a 4-byte aligned pointer");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const NormalPlanes planes{normals, mono_normal, rotation, rot_row_stride, rot_col_stride, mask, sky_mask};
+  const NlArgs A = make_args(height, width, planes, normalize ? 1 : 0, top_rows);
+  const NlWs ws = make_ws((char*)workspace);
   normal_forward_kernel<<<A.nwg, NL_THREADS, 0, st>>>(A, ws);
   normal_reduce_kernel<<<1, REDUCE_THREADS, 0, st>>>(A.nwg, ws, stats);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
 }
 
-void launch_normal_loss_backward(hipStream_t st, const int H, const int W, const NormalPlanes& planes,
-                                 const int normalize, const int top_rows, const float* grad_stats,
-                                 const char* workspace, float* grad_normals) {
-  const NlArgs A = make_args(H, W, planes, normalize, top_rows);
-  const NlWs ws = make_ws(const_cast<char*>(workspace));
-  normal_backward_kernel<<<A.nwg, NL_THREADS, 0, st>>>(A, ws.st, grad_stats, grad_normals);
+int grpg_normal_loss_backward(int height, int width, const float* normals, const float* mono_normal,
+                              const float* rotation, int rot_row_stride, int rot_col_stride, const unsigned char* mask,
+                              const unsigned char* sky_mask, int normalize, int top_rows, const float* grad_stats,
+                              const void* workspace, float* grad_normals, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (int rc = normal_loss_check(height, width, normals, mono_normal, rotation, top_rows, workspace)) return rc;
+  if (!grad_stats || !grad_normals || (((uintptr_t)grad_stats | (uintptr_t)grad_normals) & 3))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "normal_loss: grad_stats and grad_normals must be 4-byte aligned pointers");
+  const NormalPlanes planes{normals, mono_normal, rotation, rot_row_stride, rot_col_stride, mask, sky_mask};
+  const NlArgs A = make_args(height, width, planes, normalize ? 1 : 0, top_rows);
+  const NlWs ws = make_ws((char*)const_cast<void*>(workspace));
+  normal_backward_kernel<<<A.nwg, NL_THREADS, 0, (hipStream_t)hip_stream>>>(A, ws.st, grad_stats, grad_normals);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
 }
 
-}  // namespace grpg
+}  // extern "C"

@@ -3,7 +3,7 @@
 // adam_step_kernel: the step of torch.optim.Adam (amsgrad = False, weight_decay = 0, maximize = False) over EVERY
 // tensor of EVERY optimizer in one launch.  One pass over the data: read p, g, m, v; write p, m, v (28 B per
 // element), where the foreach path of torch.optim.Adam makes ~10 launches per optimizer, each a pass of its own.
-// The tensors are described by a device table of segments; the work is cut into chunks of ADAM_CHUNK elements
+// The tensors are described by a device table of segments; the work is cut into chunks of ADAM_CHUNK_ELEMS elements
 // that never straddle a segment, and the table carries for each segment the index of its first chunk, so that
 // a workgroup finds the segment of chunk c by a binary search over <= log2(segments) table entries (L2 hits).
 // The grid is capped at ADAM_MAX_WGS workgroups which stride over the chunks.
@@ -15,9 +15,31 @@
 // for sqrt(x*x + y*y) is derived for that, and the Adam arithmetic is then the same on every path of the kernel,
 // vector or scalar, which the bit-identity tests rely on).  No atomics, no inter-workgroup communication:
 // identical calls give identical bits.
+#include <cmath>
+
+#include "abi_util.h"
 #include "common.h"
 
 namespace grpg {
+
+// The device tables the entries upload.  Outside the unnamed namespace: the kernels' symbol names carry them.
+struct AdamSegmentDev {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  unsigned long long n;                    // elements (> 0)
+  float step_size, bc2_sqrt, beta2, one_minus_beta1, one_minus_beta2, eps;
+  uint32_t first_chunk;                    // chunks of the segments before this one
+  uint32_t vec;                            // all four arrays 16-byte aligned: 16-byte loads and stores
+};
+struct DensifyRangeDev {
+  float* accum;                            // [n, 2]
+  float* denom;                            // [n]
+  float* max_radii;                        // [n]
+  int start, end;                          // half-open range of the composed frame, n = end - start > 0
+};
+static_assert(sizeof(DensifyRangeDev) == 32, "the header documents 32 bytes per range");
 
 namespace {
 
@@ -29,8 +51,9 @@ constexpr int ADAM_THREADS = 256;
 #define GRPG_ADAM_MAX_WGS 2048   // 256 CUs x 8 resident workgroups
 #endif
 constexpr int ADAM_UNROLL = GRPG_ADAM_UNROLL;                       // float4 per thread and chunk
-constexpr uint32_t ADAM_CHUNK_ELEMS = ADAM_THREADS * 4 * ADAM_UNROLL;   // 4096 elements = 16 KB per array
-static_assert(ADAM_CHUNK_ELEMS == ADAM_CHUNK, "common.h ADAM_CHUNK is what api.hip cuts the segments by");
+// elements per unit of work (4096 = 16 KB per array); a chunk never straddles two segments
+constexpr uint32_t ADAM_CHUNK_ELEMS = ADAM_THREADS * 4 * ADAM_UNROLL;
+static_assert(ADAM_CHUNK_ELEMS == 4096, "grpg_adam_step's error text names the chunk size");
 
 // The table's pointers are loaded from memory, so the compiler cannot know their address space and would emit
 // flat_load / flat_store; they are device global memory by the entry's contract.
@@ -145,18 +168,120 @@ densify_stats_kernel(const int P, const float* __restrict__ grad_xyz, const int*
 
 }  // namespace
 
-void launch_adam_step(hipStream_t st, const AdamSegmentDev* table, int num_segments, uint32_t total_chunks) {
-  if (num_segments <= 0 || total_chunks == 0) return;
-  const uint32_t grid = total_chunks < (uint32_t)GRPG_ADAM_MAX_WGS ? total_chunks : (uint32_t)GRPG_ADAM_MAX_WGS;
-  hipLaunchKernelGGL(adam_step_kernel, dim3(grid), dim3(ADAM_THREADS), 0, st, table, num_segments, total_chunks);
-}
-
-void launch_densify_stats(hipStream_t st, int P, const float* grad_xyz, const int* radii,
-                          const DensifyRangeDev* ranges, int num_ranges) {
-  if (P <= 0 || num_ranges <= 0) return;
-  const int grid = (P + DENSIFY_THREADS - 1) / DENSIFY_THREADS;
-  hipLaunchKernelGGL(densify_stats_kernel, dim3(grid), dim3(DENSIFY_THREADS), 0, st, P, grad_xyz, radii, ranges,
-                     num_ranges);
-}
-
 }  // namespace grpg
+
+using namespace grpg;
+
+// ---- C ABI (include/grpg_rasterizer.h).  Both entries return without a host wait: their tables go through the
+// pinned staging ring of abi_util.h. ----
+extern "C" {
+
+size_t grpg_adam_workspace_bytes(int num_segments) {
+  if (num_segments <= 0) return 0;
+  return sizeof(AdamSegmentDev) * (size_t)num_segments;
+}
+
+int grpg_adam_step(const grpg_adam_segment* segments, int num_segments, grpg_alloc_fn table_alloc,
+                   void* table_user, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (num_segments < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: negative segment count");
+  if (num_segments == 0) return GRPG_OK;
+  if (!segments) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: NULL segment table");
+  if (!table_alloc) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: NULL table allocator");
+  int live = 0;
+  unsigned long long chunks = 0;
+  for (int i = 0; i < num_segments; i++) {
+    const grpg_adam_segment& g = segments[i];
+    if (g.n < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: segment with negative n");
+    if (g.n == 0) continue;
+    if (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: segment with a NULL array and n > 0");
+    if (((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 3)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: arrays must be 4-byte aligned");
+    if (!std::isfinite(g.bc2_sqrt) || !(g.bc2_sqrt > 0.f))
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: bc2_sqrt must be finite and positive");
+    if (!std::isfinite(g.step_size) || !std::isfinite(g.beta2) || !std::isfinite(g.one_minus_beta1) ||
+        !std::isfinite(g.one_minus_beta2) || !std::isfinite(g.eps))
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: non-finite coefficient");
+    live++;
+    chunks += ((unsigned long long)g.n + ADAM_CHUNK_ELEMS - 1) / ADAM_CHUNK_ELEMS;
+  }
+  if (live == 0) return GRPG_OK;              // nothing but empty tensors: no launch
+  if (chunks > 0xFFFFFFFFull) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: more than 2^32 chunks of 4096 elements");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const size_t bytes = sizeof(AdamSegmentDev) * (size_t)live;
+  OptimStagingSlot* stg = optim_staging_acquire(bytes);
+  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
+  AdamSegmentDev* host = (AdamSegmentDev*)stg->host;
+  uint32_t first = 0;
+  int k = 0;
+  for (int i = 0; i < num_segments; i++) {
+    const grpg_adam_segment& g = segments[i];
+    if (g.n == 0) continue;
+    AdamSegmentDev& d = host[k++];
+    d.param = g.param; d.grad = g.grad; d.exp_avg = g.exp_avg; d.exp_avg_sq = g.exp_avg_sq;
+    d.n = (unsigned long long)g.n;
+    d.step_size = g.step_size; d.bc2_sqrt = g.bc2_sqrt; d.beta2 = g.beta2;
+    d.one_minus_beta1 = g.one_minus_beta1; d.one_minus_beta2 = g.one_minus_beta2; d.eps = g.eps;
+    d.first_chunk = first;
+    d.vec = (((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15) == 0;
+    first += (uint32_t)((d.n + ADAM_CHUNK_ELEMS - 1) / ADAM_CHUNK_ELEMS);
+  }
+  char* dev = table_alloc(grpg_adam_workspace_bytes(num_segments), table_user);
+  if (!dev) return fail(GRPG_ERR_ALLOC, "adam_step: the table allocator returned NULL");
+  if ((uintptr_t)dev & 7) return fail(GRPG_ERR_INVALID_ARGUMENT, "adam_step: the table must be 8-byte aligned");
+  HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(stg->ev, stream));
+  const uint32_t grid = first < (uint32_t)GRPG_ADAM_MAX_WGS ? first : (uint32_t)GRPG_ADAM_MAX_WGS;
+  hipLaunchKernelGGL(adam_step_kernel, dim3(grid), dim3(ADAM_THREADS), 0, stream, (const AdamSegmentDev*)dev, live,
+                     first);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_densify_stats(int P, const float* grad_xyz, const int* radii, const grpg_range* ranges, int num_ranges,
+                       float* const* accum, float* const* denom, float* const* max_radii,
+                       grpg_alloc_fn table_alloc, void* table_user, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (P < 0 || num_ranges < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: negative count");
+  if (P == 0 || num_ranges == 0) return GRPG_OK;
+  if (!grad_xyz || !radii) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: NULL grad_xyz / radii");
+  if (!ranges || !accum || !denom || !max_radii)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: NULL range table");
+  if (!table_alloc) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: NULL table allocator");
+  int live = 0, prev_end = 0;
+  for (int i = 0; i < num_ranges; i++) {
+    const grpg_range& r = ranges[i];
+    if (r.start < prev_end || r.end < r.start || r.end > P)
+      return fail(GRPG_ERR_INVALID_ARGUMENT,
+                  "densify_stats: ranges must be half-open [start, end), ascending, disjoint and within [0, P)");
+    prev_end = r.end;
+    if (r.end == r.start) continue;
+    if (!accum[i] || !denom[i] || !max_radii[i])
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: non-empty range with a NULL array");
+    live++;
+  }
+  if (live == 0) return GRPG_OK;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const size_t bytes = sizeof(DensifyRangeDev) * (size_t)live;
+  OptimStagingSlot* stg = optim_staging_acquire(bytes);
+  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
+  DensifyRangeDev* host = (DensifyRangeDev*)stg->host;
+  int k = 0;
+  for (int i = 0; i < num_ranges; i++) {
+    if (ranges[i].end == ranges[i].start) continue;
+    host[k++] = DensifyRangeDev{accum[i], denom[i], max_radii[i], ranges[i].start, ranges[i].end};
+  }
+  char* dev = table_alloc(sizeof(DensifyRangeDev) * (size_t)num_ranges, table_user);
+  if (!dev) return fail(GRPG_ERR_ALLOC, "densify_stats: the table allocator returned NULL");
+  if ((uintptr_t)dev & 7) return fail(GRPG_ERR_INVALID_ARGUMENT, "densify_stats: the table must be 8-byte aligned");
+  HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(stg->ev, stream));
+  const int grid = (P + DENSIFY_THREADS - 1) / DENSIFY_THREADS;
+  hipLaunchKernelGGL(densify_stats_kernel, dim3(grid), dim3(DENSIFY_THREADS), 0, stream, P, grad_xyz, radii,
+                     (const DensifyRangeDev*)dev, live);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+}  // extern "C"

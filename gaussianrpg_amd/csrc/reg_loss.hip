@@ -39,6 +39,7 @@
 // Every element of every gradient array that is asked for is written.
 //
 // Bytes per Gaussian: scale 12 forward, 24 backward; opacity 8 forward (4 when invisible), 12 backward (8).
+#include "abi_util.h"
 #include "common.h"
 #include "reduce.h"
 
@@ -63,6 +64,15 @@ struct RgWs {
   RgState* st;
   double* part;           // [2][RG_MAX_WG] scale, opacity
   unsigned int* cnt;      // [RG_MAX_WG] visible
+};
+
+// One row of the device segment table the entries upload into the workspace: slot 0 by the forward, slot 1 (with the
+// gradient pointers) by the backward.
+struct RegSegDev {
+  const float* x;                          // the model's raw opacity [n]
+  float* grad;                             // its gradient [n], or NULL (forward; not wanted)
+  long long start;                         // first flat index of the composed order
+  long long n;                             // > 0
 };
 
 struct RgArgs {
@@ -251,6 +261,18 @@ RgWs make_ws(char* base) {
   return w;
 }
 
+// What reg_loss_prepare makes of an entry's arguments
+struct RegLossArgs {
+  int scale_on, opacity_on;
+  int scale_activated, opacity_activated;
+  long long n_scaling;                     // N of scaling [N,3]
+  long long n_opacity;                     // sum of the segments' n = the length of radii
+  int num_live;                            // segments with n > 0 in the device table
+  float lam_scale, lam_opacity;
+  const float* scaling;
+  const int* radii;
+};
+
 RgArgs make_args(const RegLossArgs& R, const RegSegDev* segs) {
   RgArgs A;
   A.scale_on = R.scale_on;
@@ -271,27 +293,138 @@ RgArgs make_args(const RegLossArgs& R, const RegSegDev* segs) {
   return A;
 }
 
-}  // namespace
-
+// byte offset of table slot `which` (0 forward, 1 backward; 2: the end of the workspace)
 size_t reg_loss_table_offset(const int which, const int num_segments) {
   return RG_TABLE_OFF + (size_t)which * align_up(sizeof(RegSegDev) * (size_t)(num_segments > 0 ? num_segments : 1), 256);
 }
 
-size_t reg_loss_workspace_bytes(const int num_segments) { return reg_loss_table_offset(2, num_segments); }
-
-void launch_reg_loss_forward(hipStream_t st, const RegLossArgs& R, const RegSegDev* segs, float* stats,
-                             char* workspace) {
-  const RgArgs A = make_args(R, segs);
-  const RgWs ws = make_ws(workspace);
-  reg_forward_kernel<<<A.nwg, RG_THREADS, 0, st>>>(A, ws);
-  reg_reduce_kernel<<<1, REDUCE_THREADS, 0, st>>>(A, ws, stats);
+// Checks every argument, then uploads the live segments into table slot `which` of the workspace through the pinned
+// ring and fills args / table.  Nothing is queued before the last check has passed.
+int reg_loss_prepare(const float* scaling, long long n_scaling, int scale_activated, const grpg_reg_segment* segments,
+                     int num_segments, int opacity_activated, const int* radii, long long n_radii, float lam_scale,
+                     float lam_opacity, void* workspace, const bool backward, const bool want_scale, int which,
+                     hipStream_t stream, RegLossArgs& R, const RegSegDev*& table) {
+  R = RegLossArgs{};
+  R.scale_on = lam_scale > 0.f && (!backward || want_scale);
+  R.opacity_on = lam_opacity > 0.f;
+  R.scale_activated = scale_activated ? 1 : 0;
+  R.opacity_activated = opacity_activated ? 1 : 0;
+  R.lam_scale = lam_scale;
+  R.lam_opacity = lam_opacity;
+  table = nullptr;
+  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: NULL workspace");
+  if ((uintptr_t)workspace & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: workspace must be 16-byte aligned");
+  if (num_segments < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: negative segment count");
+  if (R.scale_on) {
+    if (n_scaling < 0 || n_scaling > 0x7FFFFFFFll / 3)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: n_scaling must be in [0, (2^31 - 1) / 3]");
+    if (n_scaling > 0 && !scaling) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: NULL scaling with n_scaling > 0");
+    if ((uintptr_t)scaling & 3) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: scaling must be 4-byte aligned");
+    R.n_scaling = n_scaling;
+    R.scaling = scaling;
+  }
+  if (!R.opacity_on) return GRPG_OK;
+  if (num_segments > 0 && !segments) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: NULL segment table");
+  long long total = 0;
+  int live = 0;
+  bool any_grad = false;
+  for (int i = 0; i < num_segments; i++) {
+    const grpg_reg_segment& g = segments[i];
+    if (g.n < 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: segment with negative n");
+    if (g.n == 0) continue;
+    if (!g.opacity) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: segment with a NULL opacity array and n > 0");
+    if (((uintptr_t)g.opacity | (uintptr_t)g.grad_opacity) & 3)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: opacity arrays must be 4-byte aligned");
+    total += g.n;
+    if (total > 0x7FFFFFFFll) return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: more than 2^31 - 1 Gaussians");
+    any_grad = any_grad || g.grad_opacity != nullptr;
+    live++;
+  }
+  if (n_radii != total)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: the length of radii must be the sum of the segments' n");
+  if (total > 0 && (!radii || ((uintptr_t)radii & 3)))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: radii must be a 4-byte aligned pointer");
+  R.n_opacity = total;
+  R.radii = radii;
+  if (backward && !any_grad) {          // no opacity gradient is wanted: the term costs nothing
+    R.opacity_on = 0;
+    return GRPG_OK;
+  }
+  if (live == 0) return GRPG_OK;
+  const size_t bytes = sizeof(RegSegDev) * (size_t)live;
+  OptimStagingSlot* stg = optim_staging_acquire(bytes);
+  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
+  RegSegDev* host = (RegSegDev*)stg->host;
+  long long start = 0;
+  int k = 0;
+  for (int i = 0; i < num_segments; i++) {
+    const grpg_reg_segment& g = segments[i];
+    if (g.n == 0) continue;
+    host[k++] = RegSegDev{g.opacity, backward ? g.grad_opacity : nullptr, start, g.n};
+    start += g.n;
+  }
+  char* dev = (char*)workspace + reg_loss_table_offset(which, num_segments);
+  HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(stg->ev, stream));
+  R.num_live = live;
+  table = (const RegSegDev*)dev;
+  return GRPG_OK;
 }
-
-void launch_reg_loss_backward(hipStream_t st, const RegLossArgs& R, const RegSegDev* segs, const float* grad_stats,
-                              const char* workspace, float* grad_scaling) {
-  const RgArgs A = make_args(R, segs);
-  const RgWs ws = make_ws(const_cast<char*>(workspace));
-  reg_backward_kernel<<<A.nwg, RG_THREADS, 0, st>>>(A, ws.st, grad_stats, grad_scaling);
-}
+}  // namespace
 
 }  // namespace grpg
+
+using namespace grpg;
+
+// ---- C ABI (include/grpg_rasterizer.h) ----
+extern "C" {
+
+size_t grpg_reg_loss_workspace_bytes(int num_segments) {
+  return num_segments < 0 ? 0 : reg_loss_table_offset(2, num_segments);
+}
+
+int grpg_reg_loss_forward(const float* scaling, long long n_scaling, int scale_activated,
+                          const grpg_reg_segment* segments, int num_segments, int opacity_activated, const int* radii,
+                          long long n_radii, float lambda_scale_flatten, float lambda_opacity_sparse, float* stats,
+                          void* workspace, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (!stats || ((uintptr_t)stats & 3))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: stats must be a 4-byte aligned pointer");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  RegLossArgs R;
+  const RegSegDev* table;
+  if (int rc = reg_loss_prepare(scaling, n_scaling, scale_activated, segments, num_segments, opacity_activated, radii,
+                                n_radii, lambda_scale_flatten, lambda_opacity_sparse, workspace, false, true, 0,
+                                stream, R, table))
+    return rc;
+  const RgArgs A = make_args(R, table);
+  const RgWs ws = make_ws((char*)workspace);
+  reg_forward_kernel<<<A.nwg, RG_THREADS, 0, stream>>>(A, ws);
+  reg_reduce_kernel<<<1, REDUCE_THREADS, 0, stream>>>(A, ws, stats);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_reg_loss_backward(const float* scaling, long long n_scaling, int scale_activated,
+                           const grpg_reg_segment* segments, int num_segments, int opacity_activated, const int* radii,
+                           long long n_radii, float lambda_scale_flatten, float lambda_opacity_sparse,
+                           const float* grad_stats, void* workspace, float* grad_scaling, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (!grad_stats || (((uintptr_t)grad_stats | (uintptr_t)grad_scaling) & 3))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "reg_loss: grad_stats and grad_scaling must be 4-byte aligned pointers");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  RegLossArgs R;
+  const RegSegDev* table;
+  if (int rc = reg_loss_prepare(scaling, n_scaling, scale_activated, segments, num_segments, opacity_activated, radii,
+                                n_radii, lambda_scale_flatten, lambda_opacity_sparse, workspace, true,
+                                grad_scaling != nullptr, 1, stream, R, table))
+    return rc;
+  if (!R.scale_on && !R.opacity_on) return GRPG_OK;
+  const RgArgs A = make_args(R, table);
+  const RgWs ws = make_ws((char*)workspace);
+  reg_backward_kernel<<<A.nwg, RG_THREADS, 0, stream>>>(A, ws.st, grad_stats, R.scale_on ? grad_scaling : nullptr);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+}  // extern "C"

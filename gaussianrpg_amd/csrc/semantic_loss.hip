@@ -41,6 +41,7 @@
 // (4 S + sizeof(target) for an ignored pixel).
 #include <type_traits>
 
+#include "abi_util.h"
 #include "common.h"
 #include "reduce.h"
 
@@ -313,33 +314,74 @@ void sc_dispatch(const int S, const int mode, F&& f) {
   else ladder(std::integral_constant<int, 1>{});
 }
 
-}  // namespace
-
-size_t semantic_ce_workspace_bytes(const int H, const int W) {
-  return SC_LSE_OFF + align_up((size_t)H * W * sizeof(float), 256);
+int semantic_ce_check(int S, int height, int width, const float* sem, const void* target, int target_bytes,
+                      int mode, const void* workspace) {
+  if (S < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: S must be at least 1");
+  if (int rc = loss_plane_check("semantic_ce", height, width)) return rc;
+  if (!sem || !target) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL sem / target");
+  if (mode != 0 && mode != 1)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: mode must be 0 (logits) or 1 (probabilities)");
+  if (target_bytes != 4 && target_bytes != 8)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: target_bytes must be 4 (int32) or 8 (int64)");
+  if (((uintptr_t)sem & 3) || ((uintptr_t)target & (uintptr_t)(target_bytes - 1)))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: sem must be 4-byte aligned, target aligned to its width");
+  if (!workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL workspace");
+  if ((uintptr_t)workspace & 15)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: workspace must be 16-byte aligned");
+  return GRPG_OK;
 }
 
-void launch_semantic_ce_forward(hipStream_t st, const int S, const int H, const int W, const float* sem,
-                                const void* target, const int target_bytes, const int mode, float* stats,
-                                unsigned char* labels, char* workspace) {
-  const ScArgs A = make_args(S, H, W, sem, target, target_bytes);
-  const ScWs ws = make_ws(workspace);
+}  // namespace
+
+}  // namespace grpg
+
+using namespace grpg;
+
+// ---- C ABI (include/grpg_rasterizer.h) ----
+extern "C" {
+
+size_t grpg_semantic_ce_workspace_bytes(int height, int width) {
+  if (loss_plane_check(nullptr, height, width)) return 0;
+  return SC_LSE_OFF + align_up((size_t)height * width * sizeof(float), 256);
+}
+
+int grpg_semantic_ce_forward(int S, int height, int width, const float* sem, const void* target, int target_bytes,
+                             int mode, float* stats, unsigned char* labels, void* workspace, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (int rc = semantic_ce_check(S, height, width, sem, target, target_bytes, mode, workspace)) return rc;
+  if (!stats) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL stats");
+  if (((uintptr_t)stats & 3)) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: stats must be 4-byte aligned");
+  if (labels && S > 256)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: the uint8 label plane needs S <= 256");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const ScArgs A = make_args(S, height, width, sem, target, target_bytes);
+  const ScWs ws = make_ws((char*)workspace);
   sc_dispatch(S, mode, [&](auto cap, auto m) {
     semantic_ce_forward_kernel<decltype(cap)::value, decltype(m)::value>
         <<<A.nwg, SCE_THREADS, 0, st>>>(A, ws, labels);
   });
   semantic_ce_reduce_kernel<<<1, REDUCE_THREADS, 0, st>>>(A.nwg, ws, stats);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
 }
 
-void launch_semantic_ce_backward(hipStream_t st, const int S, const int H, const int W, const float* sem,
-                                 const void* target, const int target_bytes, const int mode,
-                                 const float* grad_loss, const char* workspace, float* grad_sem) {
-  const ScArgs A = make_args(S, H, W, sem, target, target_bytes);
-  const ScWs ws = make_ws(const_cast<char*>(workspace));
+int grpg_semantic_ce_backward(int S, int height, int width, const float* sem, const void* target, int target_bytes,
+                              int mode, const float* grad_loss, const void* workspace, float* grad_sem,
+                              void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (int rc = semantic_ce_check(S, height, width, sem, target, target_bytes, mode, workspace)) return rc;
+  if (!grad_loss || !grad_sem) return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: NULL grad_loss / grad_sem");
+  if (((uintptr_t)grad_loss & 3) || ((uintptr_t)grad_sem & 3))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "semantic_ce: grad_loss and grad_sem must be 4-byte aligned");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const ScArgs A = make_args(S, height, width, sem, target, target_bytes);
+  const ScWs ws = make_ws((char*)const_cast<void*>(workspace));
   sc_dispatch(S, mode, [&](auto cap, auto m) {
     semantic_ce_backward_kernel<decltype(cap)::value, decltype(m)::value>
         <<<A.nwg, SCE_THREADS, 0, st>>>(A, ws.st, ws.lse, grad_loss, grad_sem);
   });
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
 }
 
-}  // namespace grpg
+}  // extern "C"

@@ -24,6 +24,7 @@
 //     across a CORNER has no texel: it is dropped and the other three weights are renormalised.
 // Backward (training the sky): d rgb / d cube scatters (1 - acc) * weight * dL/drgb into the up to
 // four texels, d rgb / d acc = -sky.
+#include "abi_util.h"
 #include "common.h"
 #include "sky_math.h"
 
@@ -103,20 +104,56 @@ static SkyArgs make_sky_args(const float* cube, int res, const float* m9, int m_
   return s;
 }
 
-void launch_sky_composite(hipStream_t st, const float* cube, int res, const float* m9, int m_on_device,
-                          float fill, int clamp_out, int W, int H, const float* rgb_in, const float* acc,
-                          const unsigned char* mask, const float* jitter, float* rgb_out, float* sky_out) {
-  const SkyArgs s = make_sky_args(cube, res, m9, m_on_device, fill, clamp_out, mask, jitter);
-  const dim3 grid((W + 63) / 64, (H + 3) / 4);
-  sky_composite_kernel<<<grid, 256, 0, st>>>(s, W, H, rgb_in, acc, rgb_out, sky_out);
-}
-
-void launch_sky_backward(hipStream_t st, const float* cube, int res, const float* m9, int m_on_device,
-                         float fill, int W, int H, const float* acc, const unsigned char* mask,
-                         const float* jitter, const float* grad_rgb, float* grad_cube, float* grad_acc) {
-  const SkyArgs s = make_sky_args(cube, res, m9, m_on_device, fill, 0, mask, jitter);
-  const dim3 grid((W + 63) / 64, (H + 3) / 4);
-  sky_backward_kernel<<<grid, 256, 0, st>>>(s, W, H, acc, grad_rgb, grad_cube, grad_acc);
-}
-
 }  // namespace grpg
+
+using namespace grpg;
+
+// ---- C ABI (include/grpg_rasterizer.h) ----
+extern "C" {
+
+int grpg_sky_composite_ex(const float* cube, int res, const float* ray_matrix, int ray_matrix_on_device,
+                          float fill, int clamp_out, int width, int height, const float* rgb_in,
+                          const float* acc, const unsigned char* mask, const float* jitter,
+                          float* rgb_out, float* sky_out, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (!cube || !ray_matrix || res <= 0 || width <= 0 || height <= 0)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "bad cube / ray matrix / size");
+  if ((rgb_in == nullptr) != (rgb_out == nullptr))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "rgb_in and rgb_out go together");
+  if (!rgb_out && !sky_out) return fail(GRPG_ERR_INVALID_ARGUMENT, "nothing to write");
+  const SkyArgs s = make_sky_args(cube, res, ray_matrix, ray_matrix_on_device, fill, clamp_out, mask, jitter);
+  const dim3 grid((width + 63) / 64, (height + 3) / 4);
+  sky_composite_kernel<<<grid, 256, 0, (hipStream_t)hip_stream>>>(s, width, height, rgb_in, acc, rgb_out, sky_out);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_sky_composite(const float* cube, int res, const float* ray_matrix, float fill,
+                       int clamp_out, int width, int height, const float* rgb_in, const float* acc,
+                       float* rgb_out, float* sky_out, void* hip_stream) {
+  return grpg_sky_composite_ex(cube, res, ray_matrix, 0, fill, clamp_out, width, height, rgb_in, acc,
+                               nullptr, nullptr, rgb_out, sky_out, hip_stream);
+}
+
+int grpg_sky_backward_ex(const float* cube, int res, const float* ray_matrix, int ray_matrix_on_device,
+                         float fill, int width, int height, const float* acc, const unsigned char* mask,
+                         const float* jitter, const float* grad_rgb, float* grad_cube, float* grad_acc,
+                         void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (!cube || !ray_matrix || !grad_rgb || res <= 0 || width <= 0 || height <= 0)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "bad cube / ray matrix / gradient / size");
+  const SkyArgs s = make_sky_args(cube, res, ray_matrix, ray_matrix_on_device, fill, 0, mask, jitter);
+  const dim3 grid((width + 63) / 64, (height + 3) / 4);
+  sky_backward_kernel<<<grid, 256, 0, (hipStream_t)hip_stream>>>(s, width, height, acc, grad_rgb, grad_cube, grad_acc);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_sky_backward(const float* cube, int res, const float* ray_matrix, float fill, int width,
+                      int height, const float* acc, const float* grad_rgb, float* grad_cube,
+                      float* grad_acc, void* hip_stream) {
+  return grpg_sky_backward_ex(cube, res, ray_matrix, 0, fill, width, height, acc, nullptr, nullptr,
+                              grad_rgb, grad_cube, grad_acc, hip_stream);
+}
+
+}  // extern "C"

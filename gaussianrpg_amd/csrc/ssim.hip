@@ -23,6 +23,7 @@
 // Semantics of loss_utils kept exactly: the mask zeroes both images before any moment; the SSIM mean
 // runs over all B*C*H*W positions, the L1 mean over the selected elements only (all-false mask: NaN,
 // gradient 0); C1 = 0.01^2, C2 = 0.03^2; variances as E[x^2] - mu^2.
+#include "abi_util.h"
 #include "common.h"
 #include "reduce.h"
 
@@ -271,33 +272,64 @@ SsimShape make_shape(const int B, const int C, const int H, const int W, const i
   return s;
 }
 
+int ssim_check(int B, int C, int height, int width, const float* img1, const float* img2,
+               const unsigned char* mask, int mask_batch, int mask_channels) {
+  if (B <= 0 || C <= 0 || height <= 0 || width <= 0)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: B, C, height and width must be positive");
+  if ((long long)B * C * height * width > 0x7FFFFFFFll)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: B*C*H*W must be < 2^31");
+  if (!img1 || !img2) return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: NULL image pointer");
+  if (mask && ((mask_batch != 1 && mask_batch != B) || (mask_channels != 1 && mask_channels != C)))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: the mask must have 1 or B images of 1 or C channels");
+  return GRPG_OK;
+}
+
 }  // namespace
 
-size_t ssim_workspace_bytes(const int B, const int C, const int H, const int W) {
-  const SsimShape s = make_shape(B, C, H, W, 1, 1);
+}  // namespace grpg
+
+using namespace grpg;
+
+// ---- C ABI (include/grpg_rasterizer.h) ----
+extern "C" {
+
+size_t grpg_ssim_workspace_bytes(int B, int C, int height, int width) {
+  if (B <= 0 || C <= 0 || height <= 0 || width <= 0) return 0;
+  const SsimShape s = make_shape(B, C, height, width, 1, 1);
   return align_up(3 * sizeof(double) * (size_t)B * C * s.tiles_x * s.tiles_y, 256);
 }
 
-void launch_ssim_forward(hipStream_t st, const int B, const int C, const int H, const int W,
-                         const float* x1, const float* x2, const unsigned char* mask,
-                         const int mask_batch, const int mask_channels, const float w_l1,
-                         const float w_ssim, float* stats, float* saved, char* ws) {
-  const SsimShape s = make_shape(B, C, H, W, mask_batch, mask_channels);
+int grpg_ssim_forward(int B, int C, int height, int width, const float* img1, const float* img2,
+                      const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
+                      float w_ssim, float* stats, float* saved, void* workspace, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (int rc = ssim_check(B, C, height, width, img1, img2, mask, mask_batch, mask_channels)) return rc;
+  if (!stats || !workspace) return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: NULL stats / workspace");
+  if ((uintptr_t)workspace & 7) return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: workspace must be 8-byte aligned");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const SsimShape s = make_shape(B, C, height, width, mask_batch, mask_channels);
   const int nwg = B * C * s.tiles_x * s.tiles_y;
-  double* part = (double*)ws;
-  ssim_forward_kernel<<<nwg, SS_THREADS, 0, st>>>(s, x1, x2, mask, part, saved);
+  double* part = (double*)workspace;
+  ssim_forward_kernel<<<nwg, SS_THREADS, 0, st>>>(s, img1, img2, mask, part, saved);
   ssim_reduce_kernel<<<1, REDUCE_THREADS, 0, st>>>(s, part, w_l1, w_ssim, stats);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
 }
 
-void launch_ssim_backward(hipStream_t st, const int B, const int C, const int H, const int W,
-                          const float* x1, const float* x2, const unsigned char* mask,
-                          const int mask_batch, const int mask_channels, const float w_l1,
-                          const float w_ssim, const float* stats, const float* saved,
-                          const float* grad_stats, float* grad_x1) {
-  const SsimShape s = make_shape(B, C, H, W, mask_batch, mask_channels);
+int grpg_ssim_backward(int B, int C, int height, int width, const float* img1, const float* img2,
+                       const unsigned char* mask, int mask_batch, int mask_channels, float w_l1,
+                       float w_ssim, const float* stats, const float* saved, const float* grad_stats,
+                       float* grad_img1, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (int rc = ssim_check(B, C, height, width, img1, img2, mask, mask_batch, mask_channels)) return rc;
+  if (!stats || !saved || !grad_stats || !grad_img1)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "ssim: NULL stats / saved partials / gradient pointer");
+  const SsimShape s = make_shape(B, C, height, width, mask_batch, mask_channels);
   const int nwg = B * C * s.tiles_x * s.tiles_y;
-  ssim_backward_kernel<<<nwg, SS_THREADS, 0, st>>>(s, x1, x2, mask, saved, stats, grad_stats,
-                                                   w_l1, w_ssim, grad_x1);
+  ssim_backward_kernel<<<nwg, SS_THREADS, 0, (hipStream_t)hip_stream>>>(s, img1, img2, mask, saved, stats,
+                                                                         grad_stats, w_l1, w_ssim, grad_img1);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
 }
 
-}  // namespace grpg
+}  // extern "C"

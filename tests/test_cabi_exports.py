@@ -58,6 +58,18 @@ def test_abi_version_and_loud_failure_without_gpu(lib):
     assert lib.grpg_knn_workspace_bytes(1000) > 1000 * 24   # pure size query, no device needed
 
 
+def test_default_binning_algorithm_of_a_fresh_process(lib):
+    """Without GRPG_BINNING a fresh process bins hierarchically (include/grpg_rasterizer.h): the default comes from a
+    namespace-scope initializer of csrc/api.hip, which a size query cannot see going wrong."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k != "GRPG_BINNING"}
+    out = subprocess.run([sys.executable, "-c", "import ctypes, sys; "
+                          "print(ctypes.CDLL(sys.argv[1]).grpg_get_binning_algorithm())", LIB],
+                         env=env, capture_output=True, text=True, check=True).stdout.strip()
+    assert out == re.search(r"#define\s+GRPG_BINNING_ALG_HIER\s+(\d+)", open(HEADER).read()).group(1)
+
+
 def test_python_api_rejects_cpu_tensors():
     import torch
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer

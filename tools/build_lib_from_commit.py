@@ -10,19 +10,16 @@ commit, name = sys.argv[1], sys.argv[2]
 tmp = tempfile.mkdtemp(prefix="grpg_%s_" % name)
 subprocess.check_call("git archive %s gaussianrpg_amd/csrc include | tar -x -C %s" % (commit, tmp), shell=True, cwd=ROOT)
 src = os.path.join(tmp, "gaussianrpg_amd", "csrc")
-def cc(item):
-    u, extra = item
+def cc(u):
     if not os.path.exists(os.path.join(src, u)):
         return None
     o = os.path.join(tmp, u.replace(".hip", ".o"))
-    subprocess.check_call([b._hipcc(), "--offload-arch=" + b.ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
-                           "-Wno-unused-function"] + extra + ["-c", os.path.join(src, u), "-o", o])
+    subprocess.check_call(b.compile_cmd(u, [], src, o))
     return o
 with ThreadPoolExecutor(8) as ex:
-    objs = [o for o in ex.map(cc, b.HIP_UNITS.items()) if o]
+    objs = [o for o in ex.map(cc, b.HIP_UNITS) if o]
 out = b.variant_path(name)
 os.makedirs(os.path.dirname(out), exist_ok=True)
-subprocess.check_call([b._hipcc(), "--offload-arch=" + b.ARCH, "-shared", "-fPIC", "-o", out] + objs +
-                      ["-Wl,--enable-new-dtags", "-Wl,-rpath,/opt/rocm/lib"])
+subprocess.check_call(b.link_cmd(objs, out))
 shutil.rmtree(tmp)
 print(out)
