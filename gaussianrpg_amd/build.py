@@ -59,6 +59,9 @@ HIP_UNITS = {
     # fused multi-tensor Adam step + densification statistics: one rounding per operation, in the order
     # written, on the vector and the scalar path alike (bit-identical across alignments)
     "optim.hip": ["-ffp-contract=off"],
+    # fused densify-and-prune of all models: the apply pass recomputes a child's xyz / scaling with the bits the
+    # classification saw (no FMA contraction); no atomics
+    "densify.hip": ["-ffp-contract=off"],
     # feature planes of a composed frame: compose_one() must give the bits the composed preprocess sees (no FMA
     # contraction); no atomics, deterministic fixed-order reduction of the pose gradient
     "features.hip": ["-ffp-contract=off"],

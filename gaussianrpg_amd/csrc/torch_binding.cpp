@@ -1825,6 +1825,138 @@ void DensifyStats(const torch::Tensor& grad, const torch::Tensor& radii, const t
   }
 }
 
+// densify_and_prune of every model (gaussianrpg_amd/optim.py): plan (classify + scan, the call's one host wait), the
+// outputs from torch's allocator, apply.  params[m][t]: float32 [P_m, ...]; has_state[m][t] says whether
+// exp_avgs[m][t] / exp_avg_sqs[m][t] are the tensor's moments (otherwise they are ignored); special: CPU int64 [M,4]
+// = the indices of xyz, opacity, scaling, rotation; rules: CPU float64 [M,19] = grad_column, max_grad, percent_dense,
+// extent, min_opacity, prune_big, percent_big_ws, has_sphere, centre[3], radius, has_box, box_min[3], box_max[3].
+// Returns per model (params, exp_avgs, exp_avg_sqs, accum [n,2], denom [n,1], max_radii2D [n], src_index [n]) and the
+// counts as a CPU int64 [M,10] tensor (grpg_densify_counts).
+using DensifyModelOut = std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>, std::vector<torch::Tensor>,
+                                   torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>;
+std::tuple<std::vector<DensifyModelOut>, torch::Tensor> DensifyAndPrune(
+    const std::vector<std::vector<torch::Tensor>>& params, const std::vector<std::vector<torch::Tensor>>& exp_avgs,
+    const std::vector<std::vector<torch::Tensor>>& exp_avg_sqs, const std::vector<std::vector<int64_t>>& has_state,
+    const std::vector<torch::Tensor>& accum, const std::vector<torch::Tensor>& denom,
+    const std::vector<torch::Tensor>& split_noise, const std::vector<torch::Tensor>& box_noise,
+    const torch::Tensor& special, const torch::Tensor& rules) {
+  const size_t M = params.size();
+  TORCH_CHECK(exp_avgs.size() == M && exp_avg_sqs.size() == M && has_state.size() == M && accum.size() == M &&
+                  denom.size() == M && split_noise.size() == M && box_noise.size() == M,
+              "densify_and_prune: one entry per model in every list");
+  TORCH_CHECK(special.device().is_cpu() && special.scalar_type() == torch::kInt64 && special.is_contiguous() &&
+                  special.dim() == 2 && (size_t)special.size(0) == M && special.size(1) == 4,
+              "densify_and_prune: special must be a contiguous CPU int64 [models, 4] tensor");
+  TORCH_CHECK(rules.device().is_cpu() && rules.scalar_type() == torch::kFloat64 && rules.is_contiguous() &&
+                  rules.dim() == 2 && (size_t)rules.size(0) == M && rules.size(1) == 19,
+              "densify_and_prune: rules must be a contiguous CPU float64 [models, 19] tensor");
+  torch::Tensor counts = torch::zeros({(long long)M, 10}, torch::TensorOptions().dtype(torch::kInt64));
+  static_assert(sizeof(grpg_densify_counts) == 10 * sizeof(int64_t), "counts travel as an int64 [M,10] tensor");
+  std::vector<DensifyModelOut> result(M);
+  if (M == 0) return std::make_tuple(result, counts);
+  TORCH_CHECK(accum[0].defined() && accum[0].is_cuda(),
+              "densify_and_prune: tensors must live on a ROCm/HIP device (no CPU path)");
+  const torch::Device dev = accum[0].device();
+  std::vector<grpg_densify_model> models(M);
+  std::vector<long long> rows(M);
+  const int64_t* sp = special.data_ptr<int64_t>();
+  const double* ru = rules.data_ptr<double>();
+  for (size_t m = 0; m < M; m++) {
+    grpg_densify_model& g = models[m];
+    g = grpg_densify_model{};
+    const size_t T = params[m].size();
+    TORCH_CHECK(T >= 1 && T <= (size_t)GRPG_DENSIFY_MAX_TENSORS, "densify_and_prune: a model has 1 to ",
+                GRPG_DENSIFY_MAX_TENSORS, " tensors");
+    TORCH_CHECK(exp_avgs[m].size() == T && exp_avg_sqs[m].size() == T && has_state[m].size() == T,
+                "densify_and_prune: one moment pair and one has_state flag per tensor");
+    TORCH_CHECK(accum[m].defined() && accum[m].dim() == 2 && accum[m].size(1) == 2,
+                "densify_and_prune: xyz_gradient_accum must be [P,2]");
+    const int64_t P = accum[m].size(0);
+    g.P = rows[m] = P;
+    g.num_tensors = (int)T;
+    for (size_t t = 0; t < T; t++) {
+      const torch::Tensor& p = params[m][t];
+      TORCH_CHECK(p.defined() && p.dim() >= 1 && p.size(0) == P, "densify_and_prune: every tensor of a model has P rows");
+      int64_t w = 1;
+      for (int64_t k = 1; k < p.dim(); k++) w *= p.size(k);
+      TORCH_CHECK(w <= 0x7FFFFFFFll, "densify_and_prune: row too wide");
+      grpg_densify_tensor& D = g.tensors[t];
+      D.width = (int)w;
+      D.param = optim_f(p, dev, P * w, "densify_and_prune", "param");
+      if (has_state[m][t]) {
+        TORCH_CHECK(exp_avgs[m][t].defined() && exp_avgs[m][t].sizes() == p.sizes() &&
+                        exp_avg_sqs[m][t].defined() && exp_avg_sqs[m][t].sizes() == p.sizes(),
+                    "densify_and_prune: moments must have their parameter's shape");
+        D.exp_avg = optim_f(exp_avgs[m][t], dev, P * w, "densify_and_prune", "exp_avg");
+        D.exp_avg_sq = optim_f(exp_avg_sqs[m][t], dev, P * w, "densify_and_prune", "exp_avg_sq");
+      }
+    }
+    g.xyz_index = (int)sp[4 * m]; g.opacity_index = (int)sp[4 * m + 1];
+    g.scaling_index = (int)sp[4 * m + 2]; g.rotation_index = (int)sp[4 * m + 3];
+    g.xyz_gradient_accum = optim_f(accum[m], dev, 2 * P, "densify_and_prune", "xyz_gradient_accum");
+    g.denom = optim_f(denom[m], dev, P, "densify_and_prune", "denom");
+    g.split_noise = optim_f(split_noise[m], dev, 6 * P, "densify_and_prune", "split_noise");
+    const double* r = ru + 19 * m;
+    g.grad_column = (int)r[0]; g.max_grad = (float)r[1]; g.percent_dense = (float)r[2]; g.extent = (float)r[3];
+    g.min_opacity = (float)r[4]; g.prune_big = r[5] != 0.0; g.percent_big_ws = (float)r[6];
+    g.has_sphere = r[7] != 0.0;
+    for (int k = 0; k < 3; k++) {
+      g.sphere_center[k] = (float)r[8 + k];
+      g.box_min[k] = (float)r[13 + k];
+      g.box_max[k] = (float)r[16 + k];
+    }
+    g.sphere_radius = (float)r[11];
+    g.has_box = r[12] != 0.0;
+    if (g.has_box && g.prune_big)
+      g.box_noise = optim_f(box_noise[m], dev, 24 * P, "densify_and_prune", "box_noise");
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const auto bytes_opt = torch::TensorOptions().dtype(torch::kByte).device(dev);
+  const auto f_opt = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
+  torch::Tensor ws = loss_workspace(grpg_densify_workspace_bytes(rows.data(), (int)M), dev);
+  torch::Tensor table = torch::empty({0}, bytes_opt), table2 = torch::empty({0}, bytes_opt);
+  grpg_densify_counts* cnt = reinterpret_cast<grpg_densify_counts*>(counts.data_ptr<int64_t>());
+  loss_call("grpg_densify_plan", [&](void* stream) {
+    return grpg_densify_plan(models.data(), (int)M, ws.data_ptr(), cnt, resize_blob, &table, stream);
+  });
+  std::vector<grpg_densify_output> outs(M);
+  for (size_t m = 0; m < M; m++) {
+    grpg_densify_output& o = outs[m];
+    o = grpg_densify_output{};
+    const int64_t n = cnt[m].n_out;
+    TORCH_CHECK(n >= 0 && n <= 3 * rows[m], "densify_and_prune: the plan returned an impossible row count");
+    o.n_out = n;
+    auto& [np, nm, nv, na, nd, nr, ni] = result[m];
+    for (size_t t = 0; t < params[m].size(); t++) {
+      std::vector<int64_t> shape = params[m][t].sizes().vec();
+      shape[0] = n;
+      np.push_back(torch::empty(shape, f_opt));
+      nm.push_back(has_state[m][t] ? torch::empty(shape, f_opt) : torch::Tensor(torch::empty({0}, f_opt)));
+      nv.push_back(has_state[m][t] ? torch::empty(shape, f_opt) : torch::Tensor(torch::empty({0}, f_opt)));
+      const bool live = np.back().numel() > 0;
+      o.tensors[t].param = live ? np.back().data_ptr<float>() : nullptr;
+      if (has_state[m][t] && live) {
+        o.tensors[t].exp_avg = nm.back().data_ptr<float>();
+        o.tensors[t].exp_avg_sq = nv.back().data_ptr<float>();
+      }
+    }
+    na = torch::empty({n, 2}, f_opt);
+    nd = torch::empty({n, 1}, f_opt);
+    nr = torch::empty({n}, f_opt);
+    ni = torch::empty({n}, f_opt.dtype(torch::kInt32));
+    if (n > 0) {
+      o.xyz_gradient_accum = na.data_ptr<float>();
+      o.denom = nd.data_ptr<float>();
+      o.max_radii2D = nr.data_ptr<float>();
+      o.src_index = ni.data_ptr<int>();
+    }
+  }
+  loss_call("grpg_densify_apply", [&](void* stream) {
+    return grpg_densify_apply(models.data(), (int)M, ws.data_ptr(), outs.data(), resize_blob, &table2, stream);
+  });
+  return std::make_tuple(result, counts);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rasterize_gaussians", &RasterizeGaussians);
   m.def("rasterize_gaussians_eval", &RasterizeGaussiansEval);
@@ -1847,6 +1979,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("psnr_forward", &PsnrForward);                 // stats [2]: psnr, mse
   m.def("adam_step", &AdamStep);            // in place: params, exp_avgs, exp_avg_sqs
   m.def("densify_stats", &DensifyStats);    // in place: accum, denom, max_radii2D
+  m.def("densify_and_prune", &DensifyAndPrune);   // ([per model outputs], counts [M,10])
   m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);
   m.def("rasterize_gaussians_backward_lean", &RasterizeGaussiansBackwardLean);
   m.def("mark_visible", &markVisible);

@@ -459,3 +459,105 @@ def time_frames(render_one, num_frames: int, skip_first: int = 1) -> dict:
     n = len(kept)
     return {"frames": n, "mean_ms": sum(kept) / n, "median_ms": kept[n // 2],
             "p95_ms": kept[min(n - 1, int(0.95 * n))], "first_frame_ms": times[0]}
+
+
+def _unit_quat_matrix(r: torch.Tensor) -> torch.Tensor:
+    """[n,4] quaternions (real part first), normalised here -> [n,3,3]: lib/utils/general_utils.py:125-146."""
+    q = r / torch.sqrt((r * r).sum(dim=1, keepdim=True))
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    rows = (1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+            2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+            2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y))
+    return torch.stack(rows, dim=1).reshape(-1, 3, 3)
+
+
+def densify_and_prune_reference(tensors: dict, moments: dict, accum: torch.Tensor, denom: torch.Tensor, rule,
+                                split_noise: torch.Tensor, box_noise: Optional[torch.Tensor] = None) -> dict:
+    """The reference's ``densify_and_prune`` of ONE model as its PyTorch sequence, step for step -- clone
+    (``gaussian_model.py:494-520``), split with its prune of the parents (``:453-492``), then the model's own prune
+    (``gaussian_model.py:534-549``, ``gaussian_model_bkgd.py:90-110``, ``gaussian_model_actor.py:224-259``) -- with the
+    boolean-mask gathers and ``torch.cat`` of ``prune_optimizer`` / ``cat_optimizer`` (``:363-408``) applied to every
+    tensor and its two moments, and a ``.sum().item()`` wherever the reference reads a count.  The baseline of
+    tools/bench_densify.py and the CPU tests' second opinion; any device, any float dtype.
+
+    ``tensors``: {name: [P, ...]} with at least xyz, opacity, scaling, rotation; ``moments``: {name: (exp_avg,
+    exp_avg_sq)} for the tensors that have state; ``rule``: an object with ``optim.DensifyRule``'s fields.  The
+    reference draws ``torch.normal(0, std)`` where it needs a sample; here ``split_noise`` ``[P,2,3]`` and
+    ``box_noise`` ``[P,4,2,3]`` (slots: original, clone, child 0, child 1) hold the standard-normal draws, so every
+    row carries its source row and slot along.  Returns tensors, moments, the three fresh statistics, the scalars
+    and ``src_index``."""
+    t = dict(tensors)
+    mom = {k: tuple(v) for k, v in moments.items()}
+    dev, P = t["xyz"].device, t["xyz"].shape[0]
+    src = torch.arange(P, device=dev)
+    slot = torch.zeros(P, dtype=torch.long, device=dev)
+    scalars = {"points_total": P}
+
+    def keep(mask):
+        nonlocal src, slot
+        for k in t:
+            t[k] = t[k][mask]
+            if k in mom:
+                mom[k] = (mom[k][0][mask], mom[k][1][mask])
+        src, slot = src[mask], slot[mask]
+
+    def extend(new, new_src, new_slot):
+        nonlocal src, slot
+        for k in t:
+            if k in mom:
+                mom[k] = tuple(torch.cat((m, torch.zeros_like(new[k])), dim=0) for m in mom[k])
+            t[k] = torch.cat((t[k], new[k]), dim=0)
+        src, slot = torch.cat((src, new_src)), torch.cat((slot, new_slot))
+
+    def max_scale():
+        return torch.exp(t["scaling"]).max(dim=1).values
+
+    grads = accum[:, rule.grad_column:rule.grad_column + 1] / denom.reshape(-1, 1)
+    grads[grads.isnan()] = 0.0
+    dense = rule.percent_dense * rule.extent
+    # clone: small rows with a large gradient are appended once more
+    chosen = (torch.norm(grads, dim=-1) >= rule.max_grad) & (max_scale() <= dense)
+    scalars["points_clone"] = int(chosen.sum().item())
+    extend({k: v[chosen] for k, v in t.items()}, src[chosen], torch.ones_like(src[chosen]))
+    # split: large rows with a large gradient give two children each and go; the fresh clones have gradient 0
+    padded = torch.zeros(t["xyz"].shape[0], dtype=grads.dtype, device=dev)
+    padded[:P] = grads.squeeze(-1)
+    chosen = (padded >= rule.max_grad) & (max_scale() > dense)
+    count = int(chosen.sum().item())
+    scalars["points_split"] = count
+    stds = torch.exp(t["scaling"][chosen]).repeat(2, 1)
+    draws = torch.cat((split_noise[src[chosen], 0], split_noise[src[chosen], 1]), dim=0).to(stds.dtype)
+    rots = _unit_quat_matrix(t["rotation"][chosen]).repeat(2, 1, 1)
+    new = {k: v[chosen].repeat(2, *([1] * (v.dim() - 1))) for k, v in t.items()}
+    new["xyz"] = torch.bmm(rots, (draws * stds).unsqueeze(-1)).squeeze(-1) + t["xyz"][chosen].repeat(2, 1)
+    new["scaling"] = torch.log(stds / (0.8 * 2))
+    child_slot = torch.cat((torch.full((count,), 2, device=dev), torch.full((count,), 3, device=dev)))
+    extend(new, src[chosen].repeat(2), child_slot)
+    keep(~torch.cat((chosen, torch.zeros(2 * count, dtype=torch.bool, device=dev))))
+    # prune
+    prune = (torch.sigmoid(t["opacity"]) < rule.min_opacity).reshape(-1)
+    scalars["points_below_min_opacity"] = int(prune.sum().item())
+    scalars["points_big_ws"] = 0
+    if rule.prune_big:
+        big = max_scale() > rule.extent * rule.percent_big_ws
+        if rule.sphere_center is not None:
+            centre = torch.tensor(list(rule.sphere_center), dtype=t["xyz"].dtype, device=dev)
+            big[torch.linalg.norm(t["xyz"] - centre, dim=1) > 2 * rule.sphere_radius] = False
+        scalars["points_big_ws"] = int(big.sum().item())
+        prune = prune | big
+        if rule.box_min is not None:
+            lo = torch.tensor(list(rule.box_min), dtype=t["xyz"].dtype, device=dev)
+            hi = torch.tensor(list(rule.box_max), dtype=t["xyz"].dtype, device=dev)
+            samples = box_noise[src, slot].to(t["xyz"].dtype) * torch.exp(t["scaling"])[:, None, :]
+            rots = _unit_quat_matrix(torch.nn.functional.normalize(t["rotation"]))[:, None, :, :]
+            pts = torch.matmul(rots, samples.unsqueeze(-1)).squeeze(-1) + t["xyz"][:, None, :]
+            n = pts.shape[0]
+            inside = (pts >= lo).view(n, -1).all(dim=-1) & (pts <= hi).view(n, -1).all(dim=-1)
+            prune = prune | ~inside
+    scalars["points_pruned"] = int(prune.sum().item())
+    keep(~prune)
+    n = t["xyz"].shape[0]
+    kw = dict(dtype=t["xyz"].dtype, device=dev)
+    return {"tensors": t, "moments": mom, "xyz_gradient_accum": torch.zeros((n, 2), **kw),
+            "denom": torch.zeros((n, 1), **kw), "max_radii2D": torch.zeros(n, **kw), "scalars": scalars,
+            "src_index": src.to(torch.int32)}

@@ -1012,6 +1012,96 @@ GRPG_API int grpg_densify_stats(int P, const float* grad_xyz, const int* radii, 
                                 float* const* max_radii, grpg_alloc_fn table_alloc, void* table_user,
                                 void* hip_stream);
 
+/*
+ * densify_and_prune of every model in one call (replaces gaussians.densify_and_prune, train.py:285-291:
+ * gaussian_model.py:363-553, gaussian_model_bkgd.py:74-114, gaussian_model_actor.py:206-263): the reference's clone,
+ * split, prune of the split parents and prune, collapsed into one classification per row and one gather pass that
+ * carries the Adam moments along.  Two phases, because the caller allocates the outputs:
+ *
+ * grpg_densify_plan classifies every row of every model (one launch), scans the counts (one launch), copies the
+ * per-model counts to counts_host and waits for hip_stream ONCE -- the only host wait of the feature.
+ * grpg_densify_apply then queues one launch that writes the new arrays; it does not wait.
+ *
+ * Per row i of a model with P rows, float32:
+ *   g = accum[i, grad_column] / denom[i], NaN -> 0 (inf stays);  smax = max(exp(scaling[i, :]))
+ *   clone = g >= max_grad && smax <= percent_dense * extent;  split = g >= max_grad && smax > percent_dense * extent
+ * Candidate rows: the original, its clone (the same values) and the children c = 0, 1 of a split row,
+ *   xyz_c = R(q / |q|) (split_noise[i, c] * exp(scaling_i)) + xyz_i,  scaling_c = log(exp(scaling_i) / 1.6),
+ * every other tensor copied.  A candidate is pruned when sigmoid(opacity) < min_opacity; with prune_big when its own
+ * smax > extent * percent_big_ws (has_sphere: unless |xyz - sphere_center| > 2 sphere_radius); with prune_big and
+ * has_box when either sample R (box_noise[i, slot, j] * exp(scaling)) + xyz, j = 0, 1, of its noise slot (0 original,
+ * 1 clone, 2 child 0, 3 child 1) lies outside [box_min, box_max].  A split original never survives.
+ * Output rows: surviving originals, then clones, then children 0, then children 1, each ascending in i (the
+ * reference's order).  Moments (exp_avg, exp_avg_sq: both or neither per tensor) move with originals and are zero
+ * for every new row; the new xyz_gradient_accum [n_out,2], denom [n_out] and max_radii2D [n_out] are zeros;
+ * src_index [n_out] int32 is the source row of every output row.
+ *
+ * A model lists up to GRPG_DENSIFY_MAX_TENSORS device fp32 arrays [P, width] (any width >= 0, 4-byte aligned; 16-byte
+ * aligned arrays are read and written 16 bytes at a time) and says which of them are xyz (width 3), opacity (1),
+ * scaling (3) and rotation (4).  split_noise [P,2,3] and box_noise [P,4,2,3] (has_box && prune_big only) are the
+ * caller's standard-normal draws.  workspace: grpg_densify_workspace_bytes(P, num_models) bytes of device memory,
+ * 16-byte aligned, the SAME array and models in both phases.  table_alloc is asked once per phase for
+ * num_models * 768 bytes (8-byte aligned), with the lifetime rule of grpg_adam_step; the table is uploaded from the
+ * pinned staging ring of grpg_adam_step.  outputs[m] holds arrays of outputs[m].n_out = counts_host[m].n_out rows;
+ * a row beyond n_out is never written.  P == 0 and n_out == 0 are legal.  counts_host[m]: n_out, the rows of the four
+ * streams, points_clone / points_split (rows selected) and points_below_min_opacity / points_big_ws / points_pruned
+ * counted over the candidate rows, as the reference's masks are.  No atomics: identical calls give identical bits.
+ * Purely additive exports: GRPG_ABI_VERSION stays 7.  The size query needs no device (0 for bad sizes).  Returns
+ * GRPG_OK, GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT for a negative count, P > 2^29, a NULL
+ * array with P > 0 (n_out > 0), a misaligned array, max_grad <= 0 (the reference would split its own fresh clones)
+ * or a non-finite rule value -- all checked before anything is queued --, GRPG_ERR_ALLOC when table_alloc returns NULL.
+ */
+#define GRPG_DENSIFY_MAX_TENSORS 8
+typedef struct grpg_densify_tensor {
+  const float* param;
+  const float* exp_avg;      /* NULL (both): the optimizer has no state for this tensor yet */
+  const float* exp_avg_sq;
+  int width;                 /* floats per row */
+} grpg_densify_tensor;
+typedef struct grpg_densify_model {
+  long long P;
+  int num_tensors;
+  grpg_densify_tensor tensors[GRPG_DENSIFY_MAX_TENSORS];
+  int xyz_index, opacity_index, scaling_index, rotation_index;
+  const float* xyz_gradient_accum;   /* [P,2] */
+  const float* denom;                /* [P] */
+  const float* split_noise;          /* [P,2,3] */
+  const float* box_noise;            /* [P,4,2,3]; read with has_box && prune_big only */
+  int grad_column;                   /* 0, or 1: the AbsGS column */
+  float max_grad, percent_dense, extent, min_opacity;
+  int prune_big;
+  float percent_big_ws;
+  int has_sphere;
+  float sphere_center[3], sphere_radius;
+  int has_box;
+  float box_min[3], box_max[3];
+} grpg_densify_model;
+typedef struct grpg_densify_counts {
+  long long n_out;
+  long long stream[4];               /* surviving originals, clones, children 0, children 1 */
+  long long points_clone, points_split, points_below_min_opacity, points_big_ws, points_pruned;
+} grpg_densify_counts;
+typedef struct grpg_densify_out_tensor {
+  float* param;
+  float* exp_avg;
+  float* exp_avg_sq;
+} grpg_densify_out_tensor;
+typedef struct grpg_densify_output {
+  long long n_out;
+  grpg_densify_out_tensor tensors[GRPG_DENSIFY_MAX_TENSORS];
+  float* xyz_gradient_accum;         /* [n_out,2] */
+  float* denom;                      /* [n_out] */
+  float* max_radii2D;                /* [n_out] */
+  int* src_index;                    /* [n_out] */
+} grpg_densify_output;
+GRPG_API size_t grpg_densify_workspace_bytes(const long long* P, int num_models);   /* pure size query */
+GRPG_API int grpg_densify_plan(const grpg_densify_model* models, int num_models, void* workspace,
+                               grpg_densify_counts* counts_host, grpg_alloc_fn table_alloc, void* table_user,
+                               void* hip_stream);
+GRPG_API int grpg_densify_apply(const grpg_densify_model* models, int num_models, void* workspace,
+                                const grpg_densify_output* outputs, grpg_alloc_fn table_alloc, void* table_user,
+                                void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
