@@ -47,7 +47,8 @@ class ModelParams(NamedTuple):
     ``_features_rest [N,M-1,3]``.  ``flip`` (optional, bool ``[N]``): this iteration's flip mask of a
     rigid actor -- the training symmetry prior, ``torch.rand_like(xyz[:, 0]) < flip_prob``
     (street_gaussian_model.py:286-293); flipped Gaussians have their local y mirrored and their local
-    rotation pre-multiplied by the quaternion of diag(-1, 1, -1) (:57-61, :332, :360)."""
+    rotation pre-multiplied by the quaternion of diag(-1, 1, -1) (:57-61, :332, :360).  The mask of a static model
+    (pose ``None``) is ignored, in the forward and in the backward: the reference mirrors posed actors only."""
     xyz: torch.Tensor
     scaling: torch.Tensor
     rotation: torch.Tensor

@@ -641,7 +641,10 @@ void fill_segments(SegmentDev* dst, const grpg_model_segment* segs, int nseg, co
     SegmentDev& d = dst[i];
     const bool obj = (layers && layers->segment_class) ? layers->segment_class[i] != 0 : g.rigid != 0;
     d.xyz = g.xyz; d.scaling = g.scaling; d.rotation = g.rotation; d.opacity = g.opacity;
-    d.fdc = g.features_dc; d.frest = g.features_rest; d.flip = g.flip; d.pad1 = (const void*)(uintptr_t)(obj ? 1u : 0u);
+    // the symmetry prior mirrors posed actors only (street_gaussian_model.py:332,360 sit inside the per-actor loop):
+    // a static segment's mask is ignored, by the forward and by both backwards alike (they all read this table)
+    d.fdc = g.features_dc; d.frest = g.features_rest; d.flip = g.rigid ? g.flip : nullptr;
+    d.pad1 = (const void*)(uintptr_t)(obj ? 1u : 0u);
     d.start = start; d.count = (uint32_t)g.count;
     d.fourier_dim = g.fourier_dim; d.rigid = g.rigid;
     for (int k = 0; k < 4; k++) d.rot[k] = g.obj_rot[k];

@@ -319,7 +319,8 @@ typedef struct grpg_model_segment {
                                   (training symmetry prior of rigid actors, street_gaussian_model.py:
                                   286-293: local y mirrored, local rotation pre-multiplied by the
                                   quaternion of diag(-1,1,-1)); NULL = none (evaluation, flip_prob 0,
-                                  deformable actors) */
+                                  deformable actors).  Ignored when rigid == 0: the reference mirrors
+                                  posed actors only */
 } grpg_model_segment;
 
 /* Same outputs, blobs and return value as grpg_forward on the concatenation of the segments

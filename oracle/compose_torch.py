@@ -58,38 +58,51 @@ def idft(time, dim):
     return out
 
 
-def compose(models, poses):
+def compose(models, poses, dtype=None):
     """models: sequence with .xyz .scaling .rotation .opacity .features_dc .features_rest (CPU
     tensors); poses: None or (obj_rot[4], obj_trans[3], fourier_time) per model.
-    Returns (means3D, scales, rotations, opacity, shs) as the reference's getters would."""
+    Returns (means3D, scales, rotations, opacity, shs) as the reference's getters would.
+
+    dtype (default: float32 poses on the models' own dtype, as ever): the parameters, the poses, the flip
+    quaternion and all arithmetic in that dtype -- float64 is the truth of tests/compose_truth.py.  The IDFT row
+    stays the float32 values, cast up: those are the constants the kernel multiplies by.
+    obj_rot may be [n,4] and obj_trans [n,3] (one pose per Gaussian of the model): autograd then returns each
+    row's own contribution to the pose gradient."""
+    pdt = torch.float32 if dtype is None else dtype
+    c = (lambda t: t) if dtype is None else (lambda t: t.to(dtype))
     xyzs, scales, rots, opas, feats = [], [], [], [], []
     for m, p in zip(models, poses):
         n = m.xyz.shape[0]
-        scales.append(torch.exp(m.scaling))
-        opas.append(torch.sigmoid(m.opacity.reshape(n, 1)))
-        rot_local = torch.nn.functional.normalize(m.rotation)
-        xyz_local = m.xyz
+        xyz, fdc, frest = c(m.xyz), c(m.features_dc), c(m.features_rest)
+        scales.append(torch.exp(c(m.scaling)))
+        opas.append(torch.sigmoid(c(m.opacity).reshape(n, 1)))
+        rot_local = torch.nn.functional.normalize(c(m.rotation))
+        xyz_local = xyz
         flip = getattr(m, "flip", None)
         if flip is not None and p is not None:
             # street_gaussian_model.py:57-61 (flip_axis = 1, flip_matrix = quaternion of diag(-1,1,-1)
             # = (0,0,1,0)), :332 rotations_local[flip] = flip_matrix (x) rotations_local[flip],
             # :360 xyzs_local[flip, flip_axis] *= -1
-            fq = torch.tensor([0.0, 0.0, 1.0, 0.0], device=m.xyz.device).expand(n, 4)
+            fq = torch.tensor([0.0, 0.0, 1.0, 0.0], dtype=pdt, device=m.xyz.device).expand(n, 4)
             rot_local = torch.where(flip[:, None], quaternion_raw_multiply(fq, rot_local), rot_local)
-            xyz_local = torch.where(flip[:, None] & (torch.arange(3, device=m.xyz.device) == 1)[None], -m.xyz, m.xyz)
+            xyz_local = torch.where(flip[:, None] & (torch.arange(3, device=m.xyz.device) == 1)[None], -xyz, xyz)
         if p is None:
-            xyzs.append(m.xyz)
+            xyzs.append(xyz)
             rots.append(rot_local)
-            feats.append(torch.cat((m.features_dc, m.features_rest), dim=1))
+            feats.append(torch.cat((fdc, frest), dim=1))
         else:
             dev = m.xyz.device   # tensors keep their graph: autograd through the poses works (training)
-            obj_rot = torch.as_tensor(p[0], dtype=torch.float32).to(dev).reshape(1, 4).expand(n, -1)
-            obj_trans = torch.as_tensor(p[1], dtype=torch.float32).to(dev).reshape(1, 3).expand(n, -1)
+            obj_rot = torch.as_tensor(p[0], dtype=pdt).to(dev)
+            obj_trans = torch.as_tensor(p[1], dtype=pdt).to(dev)
+            if obj_rot.dim() < 2:
+                obj_rot = obj_rot.reshape(1, 4).expand(n, -1)
+            if obj_trans.dim() < 2:
+                obj_trans = obj_trans.reshape(1, 3).expand(n, -1)
             R = quaternion_to_matrix(obj_rot)
             xyzs.append(torch.einsum('bij, bj -> bi', R, xyz_local) + obj_trans)
             rots.append(torch.nn.functional.normalize(quaternion_raw_multiply(obj_rot, rot_local)))
-            base = idft(p[2], m.features_dc.shape[1])[0].to(m.xyz.device)
-            dc = torch.sum(m.features_dc * base[..., None], dim=1, keepdim=True)
-            feats.append(torch.cat([dc, m.features_rest], dim=1))
+            base = c(idft(p[2], m.features_dc.shape[1])[0].to(m.xyz.device))
+            dc = torch.sum(fdc * base[..., None], dim=1, keepdim=True)
+            feats.append(torch.cat([dc, frest], dim=1))
     return (torch.cat(xyzs, 0), torch.cat(scales, 0), torch.cat(rots, 0), torch.cat(opas, 0),
             torch.cat(feats, 0))

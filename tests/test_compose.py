@@ -203,6 +203,44 @@ def test_single_gaussian_actors():
 
 
 @pytest.mark.gpu
+def test_flip_mask_of_a_static_model_is_ignored_forward_and_backward():
+    """The reference mirrors posed actors only (street_gaussian_model.py:332,360 run inside the per-actor loop), and
+    so does oracle/compose_torch.compose: a flip mask on a static model changes nothing -- not the composition (bit for
+    bit), not the frame, and not the sign of dL/dy or the raw rotation's gradient in the training backward."""
+    from diff_gaussian_rasterization import GaussianRasterizationSettings
+    from gaussianrpg_amd.composed import ComposedRasterizer, compose
+    from oracle import compose_torch as ct
+    dev = torch.device("cuda:0")
+    models, poses = _scene_graph(1, nb=3000, actors=((300, 3),), seed=4)
+    mask = torch.rand(3000, generator=torch.Generator().manual_seed(8)) < 0.5
+    masked = [models[0]._replace(flip=mask), models[1]]
+    plain = compose([_to(m, dev) for m in models], poses)
+    got = compose([_to(m, dev) for m in masked], poses)
+    for a, b in zip(got, plain):
+        assert torch.equal(a, b)
+    ref = ct.compose(masked, [None if p is None else (p.obj_rot, p.obj_trans, p.fourier_time) for p in poses])
+    for a, b in zip(got, ref):
+        torch.testing.assert_close(a.cpu(), b, rtol=2e-6, atol=2e-6)
+    cam = hz.trajectory_camera(2, W=160, H=96, device=dev)
+    rs = GaussianRasterizationSettings(**hz.settings_kwargs(cam, 1))
+    g = torch.Generator().manual_seed(3)
+    gc = torch.randn(3, 96, 160, generator=g).to(dev)
+    grads, frames = [], []
+    for ms in (models, masked):
+        ms = [_to(m, dev, grad=True) for m in ms]
+        color, radii, depth, alpha = ComposedRasterizer(rs)(ms, poses)
+        ((color * gc).sum() + alpha.sum()).backward()
+        torch.cuda.synchronize()
+        frames.append((color.detach(), radii))
+        grads.append([ms[0].xyz.grad.cpu().double(), ms[0].rotation.grad.cpu().double()])
+    assert torch.equal(frames[0][0], frames[1][0]) and torch.equal(frames[0][1], frames[1][1])
+    seen = (frames[0][1][:3000] > 0).cpu() & mask
+    assert int(seen.sum()) > 50
+    for a, b in zip(*grads):      # two runs of one backward: float atomics' order apart, a mirrored row would be 2 apart
+        assert float(b[seen].norm()) > 0 and float((a[seen] - b[seen]).norm()) <= 1e-4 * float(b[seen].norm())
+
+
+@pytest.mark.gpu
 def test_composed_argument_errors():
     from gaussianrpg_amd.composed import ComposedRasterizer
     from diff_gaussian_rasterization import GaussianRasterizationSettings

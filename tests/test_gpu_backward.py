@@ -105,7 +105,11 @@ def _grad_close(name, got, ref, rel_l2=1e-3, elem_tol=2e-3, frac=0.995, exempt=N
 
 
 def _run(dev, sc, cam, bg, S=0, use_colors=False, use_cov=False, seed=0, miss_frac=STRICT_MISS_FRAC,
-         with_truth=False, with_arbiter=False):
+         with_truth=False, with_arbiter=False, scale_modifier=1.0):
+    """scale_modifier goes to the op and to the oracle alike.  The op reports dL/dscales with respect to the MODIFIED
+    scale (csrc/preprocess_bwd.hip header; backward.cu computeCov3D), and so does oracle.backward; float64 autograd
+    differentiates with respect to the scale it was handed, so where it arbitrates its dL/dscales is divided by the
+    modifier (tests/test_oracle_golden.py states the relation on the CPU)."""
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
     g = torch.Generator().manual_seed(100 + seed)
     P = sc.means3D.shape[0]
@@ -116,7 +120,7 @@ def _run(dev, sc, cam, bg, S=0, use_colors=False, use_cov=False, seed=0, miss_fr
     gd = 0.1 * torch.randn(1, H, W, generator=g)
     ga = torch.randn(1, H, W, generator=g)
     gs = torch.randn(S, H, W, generator=g)
-    okw = oracle_kwargs(cam, sc.sh_degree, bg=bg)
+    okw = oracle_kwargs(cam, sc.sh_degree, bg=bg, scale_modifier=scale_modifier)
     cov = None
     if use_cov:
         o0 = oracle.forward(sc.means3D, sc.opacity, shs=sc.shs, scales=sc.scales,
@@ -132,6 +136,8 @@ def _run(dev, sc, cam, bg, S=0, use_colors=False, use_cov=False, seed=0, miss_fr
     if with_truth:      # small draws only: float64 autograd through the pure-PyTorch splat
         from helpers import float64_truth_gradients
         tr = float64_truth_gradients(sc, okw, gc, gd, ga, gs, semantics=sem, colors=colors, cov=cov)
+        if tr.get("dL_dscales") is not None:
+            tr["dL_dscales"] = tr["dL_dscales"] / scale_modifier
     elif with_arbiter:  # any size: the blend stage's gradient in float64 from the exact final transmittance
         # (gs_oracle.c gso_render_backward_f64; agrees with the float64 autograd above to 1e-6, tests/test_oracle_golden.py)
         r64 = oracle.backward(o, gc, gd, ga, gs, blend_f64=True)
@@ -143,7 +149,7 @@ def _run(dev, sc, cam, bg, S=0, use_colors=False, use_cov=False, seed=0, miss_fr
     camd = hz.CameraTensors(H, W, cam.tanfovx, cam.tanfovy, cam.viewmatrix.to(dev),
                             cam.projmatrix.to(dev), cam.campos.to(dev))
     rast = GaussianRasterizer(GaussianRasterizationSettings(
-        **hz.settings_kwargs(camd, sc.sh_degree, bg=bg.to(dev))))
+        **hz.settings_kwargs(camd, sc.sh_degree, bg=bg.to(dev), scale_modifier=scale_modifier)))
     leaf = lambda t: t.to(dev).clone().requires_grad_(True)   # noqa: E731
     means, opac = leaf(sc.means3D), leaf(sc.opacity)
     means2D = torch.zeros(P, 3, device=dev, requires_grad=True)   # train mode, renderer :157-162
@@ -206,6 +212,14 @@ def test_backward_active_degree_below_max(dev):
     sc = hz.toy_scene(1500, seed=41, sh_degree=3, scale=0.1)._replace(sh_degree=1)
     assert sc.shs.shape[1] == 16
     _run(dev, sc, hz.trajectory_camera(0, W=112, H=80), torch.tensor([0.2, 0.3, 0.1]), seed=9)
+
+
+def test_backward_scale_modifier(dev):
+    """scale_modifier = 0.6 through the op and the oracle: every array, dL/dscales (taken at the modified scale) among
+    them, by the same bars as at 1.0; float64 autograd stands by as the arbiter."""
+    sc = hz.toy_scene(1500, seed=36, sh_degree=1, scale=0.15)
+    _run(dev, sc, hz.trajectory_camera(0, W=112, H=80), torch.tensor([0.3, 0.1, 0.6]), seed=13, with_truth=True,
+         scale_modifier=0.6)
 
 
 def test_backward_street(dev):

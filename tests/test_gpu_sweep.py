@@ -107,7 +107,7 @@ def test_backward_sweep(dev, seed):
          use_cov=bool(r.rand() < 0.3), seed=seed,
          # the dense draws reach the list lengths of test_backward_long_lists: its bar; where the
          # oracle's own T_final cancellation exceeds it, float64 autograd arbitrates (_grad_close)
-         miss_frac=STRICT_MISS_FRAC_LONG_LISTS, with_truth=True)
+         miss_frac=STRICT_MISS_FRAC_LONG_LISTS, with_truth=True, scale_modifier=d["scale_modifier"])
 
 
 ALT = {"sort_binning": dict(alg=0), "exact_mode": dict(mode=1), "overflow": dict(hint=True)}

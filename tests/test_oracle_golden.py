@@ -198,6 +198,31 @@ def test_oracle_backward_vs_fp64_autograd(S):
         assert err <= tol, (ko, err, same)
 
 
+def test_scale_modifier_gradient_is_taken_at_the_modified_scale():
+    """The op's dL/dscales is the derivative with respect to the MODIFIED scale modifier * s (backward.cu computeCov3D
+    differentiates Sigma = (S R)^T (S R) with S = diag(modifier * s) and stops there); oracle.backward restates that.
+    float64 autograd (helpers.float64_truth_gradients) differentiates with respect to s itself, so
+    oracle dL/dscales = truth dL/dscales / modifier, and every other array agrees as it stands.  The float64 blend
+    arbiter keeps the comparison at the float32 preprocess's rounding (2e-5, the bar of the test below)."""
+    from helpers import float64_truth_gradients
+    modifier = 0.6
+    sc = hz.toy_scene(400, seed=12, sh_degree=1, scale=0.15)
+    cam = hz.trajectory_camera(0, W=64, H=48)
+    g = torch.Generator().manual_seed(22)
+    H, W = cam.image_height, cam.image_width
+    gc, gd, ga = torch.randn(3, H, W, generator=g), 0.1 * torch.randn(1, H, W, generator=g), torch.randn(1, H, W, generator=g)
+    okw = oracle_kwargs(cam, sc.sh_degree, bg=torch.tensor([0.3, 0.1, 0.6]), scale_modifier=modifier)
+    o = oracle.forward(sc.means3D, sc.opacity, shs=sc.shs, scales=sc.scales, rotations=sc.rotations, **okw)
+    assert int((o["radii"] > 0).sum()) > 200
+    go = oracle.backward(o, gc, gd, ga, blend_f64=True)
+    truth = float64_truth_gradients(sc, okw, gc, gd, ga)
+    rel = lambda a, b: float(np.linalg.norm(np.asarray(a, np.float64).reshape(b.shape) - b) / np.linalg.norm(b))   # noqa: E731
+    assert rel(go["dL_dscales"], truth["dL_dscales"] / modifier) <= 2e-5
+    assert rel(go["dL_dscales"], truth["dL_dscales"]) > 0.3          # and not the derivative at the raw scale
+    for k in ("dL_dopacity", "dL_dsh", "dL_drotations"):
+        assert rel(go[k], truth[k]) <= 2e-5, k
+
+
 def test_oracle_f64_arbiter_vs_fp64_autograd():
     """oracle.backward(blend_f64=True) -- gs_oracle.c gso_render_backward_f64, the arbiter of HIP-vs-oracle
     disagreements at sizes float64 autograd does not reach (tests/test_gpu_smoke_script.py) -- against that very
