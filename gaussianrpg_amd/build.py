@@ -27,7 +27,10 @@ ARCH = "gfx950"
 # translation unit -> extra flags
 HIP_UNITS = {
     # bit-exact integer outputs need the oracle's arithmetic: no FMA contraction
-    "preprocess.hip": ["-ffp-contract=off"],
+    # no SLP packing: with contraction off the unit is separate fp32 multiplies and adds, which the vectorizer pairs
+    # into v_pk_mul_f32 / v_pk_add_f32 -- 4.15 SIMD cycles each against 2.25 for a plain one (tools/ubench/valu_rate.hip,
+    # DESIGN_EXPERIMENTS.md section 6), plus the moves that gather the pairs; same IEEE result per operation
+    "preprocess.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     "preprocess_bwd.hip": ["-ffp-contract=off"],
     "sort.hip": [],
     "binning.hip": [],
@@ -69,8 +72,9 @@ HIP_UNITS = {
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept
 # next to the object as <unit>.remarks: the render launch's occupancy is a budget the sources promise
-# (render_fwd.hip render_min_waves; tests/test_render_resources.py reads the file)
-REMARK_UNITS = ("render_fwd.hip",)
+# (render_fwd.hip render_min_waves; tests/test_render_resources.py reads the file), and so is
+# the eight waves per SIMD of the specialised preprocess instantiations (tests/test_preprocess_resources.py)
+REMARK_UNITS = ("render_fwd.hip", "preprocess.hip")
 
 
 def headers():

@@ -14,8 +14,17 @@
 // Memory: one thread per Gaussian, 256-thread workgroups.  Inputs arrive AoS ([P,3], [P,4],
 // [P,M,3]) straight from the caller's torch.cat; a wave's 64 lanes read 64 consecutive
 // records, so every cache line fetched is fully used.  Output is one 48-byte record per
-// visible Gaussian (common.h) + radii + depth key + tiles_touched.  The kernel is HBM-bound:
-// algorithmic bytes = P*(44+12M) read + 12 B (+48 B if visible) written per Gaussian.
+// visible Gaussian (common.h) + radii + depth key + tiles_touched.  Algorithmic bytes =
+// P*(44+12M) read + 12 B (+48 B if visible) written per Gaussian; the launch runs short of both
+// limits (5 TB/s, vector ALUs ~60 % busy, waves waiting on memory two thirds of their time), so
+// what it gets are fewer vector instructions and more waves in flight:
+//  * the unit is built with -fno-slp-vectorize (build.py): with contraction off its arithmetic is
+//    separate multiplies and adds, and paired into v_pk_mul_f32 / v_pk_add_f32 they take the VALU
+//    1.8x as long each and cost the moves that gather the pairs -- same IEEE result per operation;
+//  * the default frame takes an instantiation with every other caller's paths compiled out
+//    (preprocess_kernel<HOT>, preprocess_composed_kernel<M4, HOT>): <= 64 VGPRs without scratch,
+//    __launch_bounds__(256, 8) = the eight workgroups per CU its 18.5 KB of LDS were sized for.
+//    build/obj/preprocess.remarks keeps hipcc's report; tests/test_preprocess_resources.py reads it.
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -175,7 +184,14 @@ __device__ __forceinline__ void mark_object_tiles_wave(const LayerMarks lm, cons
   }
 }
 
-__global__ void __launch_bounds__(256)
+// HOT: the default hierarchical frame with the fat depth sort, as launch_preprocess found it -- scales and
+// rotations given (no cov3D_precomp), SH colours (no colors_precomp) on M == 4 coefficients, 16-byte aligned
+// inputs, no layer marks, rects / ds_table0 / pre_counts all present.  Those facts are compile-time constants
+// there and every path they exclude is compiled out: the instantiation fits 64 VGPRs without scratch, eight
+// waves per SIMD = the eight workgroups per CU the LDS was sized for.  Every other call takes HOT = false, the
+// kernel for any caller; both run the same expressions in the same order.
+template <bool HOT>
+__global__ void __launch_bounds__(256, HOT ? 8 : 1)
 preprocess_kernel(const int P, const int D, const int M, const float* __restrict__ means3D,
                   const float* __restrict__ scales, const float scale_modifier,
                   const float* __restrict__ rotations, const float* __restrict__ opacities,
@@ -189,7 +205,12 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
                   uint2* __restrict__ rects /* packed tile rectangles (hierarchical binning), or NULL */,
                   uint32_t* __restrict__ ds_table0 /* [chunk][DS_RADIX] pass-0 counts of the fat depth sort, or NULL */,
                   uint4* __restrict__ pre_counts /* [workgroups] (instances, coarse pairs, min key, max key) */,
-                  const int vec_ok /* means3D, scales, shs are 16-byte aligned */, const LayerMarks lm) {
+                  const int vec_ok_in /* means3D, scales, shs are 16-byte aligned */, const LayerMarks lm) {
+  const bool vec_ok = HOT || vec_ok_in != 0;
+  const bool has_scales = HOT || scales != nullptr;
+  const bool has_cov = !HOT && cov3D_precomp != nullptr;
+  const bool has_colors = !HOT && colors_precomp != nullptr;
+  const bool layered = !HOT && lm.tile_obj != nullptr;
   // The 64-byte records leave through LDS: every thread stages its record, then the workgroup
   // stores the 16 KB slab with consecutive lanes on consecutive 16-byte pieces (whole sectors, fully
   // coalesced; a lane-per-record store would touch 64 sectors per instruction).  Culled Gaussians
@@ -199,7 +220,8 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
   // loads.  Stage the workgroup's 256 x 12 B = 3 KB per array through LDS with 16-byte loads
   // instead (the slab of workgroup b starts at byte 3072*b, so it is 16-byte aligned).  The staging
   // area lives in the record slab's space (dead until the records are staged, a barrier in between):
-  // 18.5 KB of LDS per workgroup = 8 workgroups per CU instead of 6.
+  // 18.5 KB of LDS per workgroup leave room for 8 workgroups per CU instead of 6 (the HOT instantiation's
+  // registers allow 8 as well; the generic one's 80 allow 6).
   float* const s_mean = reinterpret_cast<float*>(s_out);
   float* const s_scale = s_mean + 256 * 3;
   const int base = blockIdx.x * 256;
@@ -209,13 +231,13 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
     if (vec_ok && t4 + 3 < nval) {
       reinterpret_cast<float4*>(s_mean)[threadIdx.x] =
           reinterpret_cast<const float4*>(means3D + (size_t)base * 3)[threadIdx.x];
-      if (scales != nullptr)
+      if (has_scales)
         reinterpret_cast<float4*>(s_scale)[threadIdx.x] =
             reinterpret_cast<const float4*>(scales + (size_t)base * 3)[threadIdx.x];
     } else if (t4 < nval) {
       for (int e = t4; e < min(t4 + 4, nval); e++) {
         s_mean[e] = means3D[(size_t)base * 3 + e];
-        if (scales != nullptr) s_scale[e] = scales[(size_t)base * 3 + e];
+        if (has_scales) s_scale[e] = scales[(size_t)base * 3 + e];
       }
     }
   }
@@ -234,7 +256,7 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
   float mx = 0.f, my = 0.f, mz = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f;
   if (idx < P) {
     mx = s_mean[3 * threadIdx.x]; my = s_mean[3 * threadIdx.x + 1]; mz = s_mean[3 * threadIdx.x + 2];
-    if (scales != nullptr) {
+    if (has_scales) {
       s0 = s_scale[3 * threadIdx.x]; s1 = s_scale[3 * threadIdx.x + 1]; s2 = s_scale[3 * threadIdx.x + 2];
     }
   }
@@ -243,19 +265,19 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
     // degree <= 1 (every shipped config): the 48 B of SH coefficients as three 16-byte loads, issued
     // BEFORE the projection arithmetic so that their latency hides behind it (a culled Gaussian's
     // coefficients are then loaded for nothing: + 7 % of the kernel's bytes)
-    const bool sh_fast = colors_precomp == nullptr && M == 4 && vec_ok;
+    const bool sh_fast = HOT || (!has_colors && M == 4 && vec_ok);
     float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0, q2 = q0;
     if (sh_fast) {
       const float4* sp = reinterpret_cast<const float4*>(shs + (size_t)idx * 12);
       q0 = sp[0]; q1 = sp[1]; q2 = sp[2];
     }
     const float opac = opacities[idx];
-    const bool q_early = cov3D_precomp == nullptr;   // the quaternion too: one 16-byte load in flight early
+    const bool q_early = !has_cov;   // the quaternion too: one 16-byte load in flight early
     const float4 quat = q_early ? load_quat(rotations, idx) : make_float4(1.f, 0.f, 0.f, 0.f);
     Projected o;
     const bool vis = project_and_bound(idx, mx, my, mz, s0, s1, s2, scale_modifier, rotations,
-                                       cov3D_precomp, view, proj, W, H, gx, gy, tan_fovx, tan_fovy,
-                                       focal_x, focal_y, o, q_early, quat);
+                                       has_cov ? cov3D_precomp : nullptr, view, proj, W, H, gx, gy,
+                                       tan_fovx, tan_fovy, focal_x, focal_y, o, q_early, quat);
     if (!vis) {
       radii[idx] = 0;
       tiles[idx] = 0;
@@ -263,7 +285,7 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
     } else {
       float rgb[3];
       uint32_t clamped = 0;
-      if (colors_precomp == nullptr) {
+      if (!has_colors) {
         const float dx = mx - campos[0];
         const float dy = my - campos[1];
         const float dz = mz - campos[2];
@@ -281,14 +303,14 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
       radii[idx] = o.radius;
       my_tiles = (uint32_t)(o.maxy - o.miny) * (uint32_t)(o.maxx - o.minx);
       tiles[idx] = my_tiles;
-      if (rects) {   // x and y tile ranges, half-open, 16 bits each (hier_binning.hip)
+      if (HOT || rects) {   // x and y tile ranges, half-open, 16 bits each (hier_binning.hip)
         const uint2 rc = make_uint2((uint32_t)o.minx | ((uint32_t)o.maxx << 16),
                                     (uint32_t)o.miny | ((uint32_t)o.maxy << 16));
         rects[idx] = rc;
         my_st = rect_super_tiles(rc.x, rc.y);
       }
       uint32_t cls_bit = 0u;   // layered frame: the class rides in the record (common.h REC_CLASS_BIT)
-      if (lm.tile_obj != nullptr && lm.layer_class[idx] != 0) {
+      if (layered && lm.layer_class[idx] != 0) {
         if (my_tiles <= (uint32_t)MARK_SMALL) mark_object_tiles(lm, o.minx, o.miny, o.maxx, o.maxy);
         else { mark_big = true; mark_rect = MarkRect{o.minx, o.miny, o.maxx, o.maxy}; }
         cls_bit = REC_CLASS_BIT;
@@ -300,13 +322,13 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
       r2 = make_float4(rgb[0], rgb[1], rgb[2], __uint_as_float(clamped));
     }
   }
-  if (lm.tile_obj != nullptr) mark_object_tiles_wave(lm, mark_big, mark_rect);
+  if (layered) mark_object_tiles_wave(lm, mark_big, mark_rect);
   s_out[REC_STRIDE * threadIdx.x + 0] = r0;
   s_out[REC_STRIDE * threadIdx.x + 1] = r1;
   s_out[REC_STRIDE * threadIdx.x + 2] = r2;
   s_out[REC_STRIDE * threadIdx.x + 3] = make_float4(0.f, 0.f, 0.f, 0.f);
   __syncthreads();   // also orders the zeroing of s_dh before the atomics below
-  if (ds_table0 != nullptr && my_key != CULLED_KEY) atomicAdd(&s_dh[my_key & (DS_RADIX - 1)], 1u);
+  if ((HOT || ds_table0 != nullptr) && my_key != CULLED_KEY) atomicAdd(&s_dh[my_key & (DS_RADIX - 1)], 1u);
   const int nrec4 = min(256, P - base) * REC_STRIDE;
   float4* dst = rec + (size_t)REC_STRIDE * base;
 #pragma unroll
@@ -315,7 +337,7 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
     // a culled Gaussian's record (radius bits 0) is never read: its sector is not written
     if (e < nrec4 && __float_as_int(s_out[e & ~(REC_STRIDE - 1)].w) != 0) dst[e] = s_out[e];
   }
-  if (ds_table0 != nullptr) {
+  if (HOT || ds_table0 != nullptr) {
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < DS_RADIX / 256; k++) {
@@ -324,7 +346,7 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
         atomicAdd(&ds_table0[(size_t)(blockIdx.x / (DS_CHUNK / 256)) * DS_RADIX + k * 256 + threadIdx.x], cnt);
     }
   }
-  if (pre_counts != nullptr) block_count_sums(my_tiles, my_st, my_key, pre_counts);
+  if (HOT || pre_counts != nullptr) block_count_sums(my_tiles, my_st, my_key, pre_counts);
 }
 
 __global__ void __launch_bounds__(256)
@@ -389,9 +411,10 @@ compose_kernel(const int P, const int M, const SegmentDev* __restrict__ segs, co
 // preprocess_kernel on composed inputs: same projection / EWA / SH / record code, the activated
 // per-Gaussian values come out of compose_one() instead of the flat tensors.  M4: four SH
 // coefficients per Gaussian (degree <= 1, every shipped config) stay in registers; the generic
-// variant stages up to 16 in a per-lane array.
-template <bool M4>
-__global__ void __launch_bounds__(256)
+// variant stages up to 16 in a per-lane array.  HOT (with M4): as in preprocess_kernel -- no layer
+// marks, rects / ds_table0 / pre_counts present; 64 VGPRs without scratch, eight waves per SIMD.
+template <bool M4, bool HOT>
+__global__ void __launch_bounds__(256, HOT ? 8 : 1)
 preprocess_composed_kernel(const int P, const int D, const int M,
                            const SegmentDev* __restrict__ segs, const int nseg,
                            const float scale_modifier, const float* __restrict__ view,
@@ -402,6 +425,8 @@ preprocess_composed_kernel(const int P, const int D, const int M,
                            uint32_t* __restrict__ depth_key, uint32_t* __restrict__ tiles,
                            uint2* __restrict__ rects, uint32_t* __restrict__ ds_table0,
                            uint4* __restrict__ pre_counts, const LayerMarks lm) {
+  static_assert(M4 || !HOT, "the specialised instantiation keeps its four SH coefficients in registers");
+  const bool layered = !HOT && lm.tile_obj != nullptr;
   __shared__ float4 s_out[256 * REC_STRIDE];
   __shared__ uint32_t s_dh[DS_RADIX];
 #pragma unroll
@@ -443,14 +468,14 @@ preprocess_composed_kernel(const int P, const int D, const int M,
       radii[idx] = o.radius;
       my_tiles = (uint32_t)(o.maxy - o.miny) * (uint32_t)(o.maxx - o.minx);
       tiles[idx] = my_tiles;
-      if (rects) {   // x and y tile ranges, half-open, 16 bits each (hier_binning.hip)
+      if (HOT || rects) {   // x and y tile ranges, half-open, 16 bits each (hier_binning.hip)
         const uint2 rc = make_uint2((uint32_t)o.minx | ((uint32_t)o.maxx << 16),
                                     (uint32_t)o.miny | ((uint32_t)o.maxy << 16));
         rects[idx] = rc;
         my_st = rect_super_tiles(rc.x, rc.y);
       }
       uint32_t cls_bit = 0u;   // layered frame: the class rides in the record (common.h REC_CLASS_BIT)
-      if (lm.tile_obj != nullptr && ((uint32_t)(uintptr_t)sg.pad1 & 1u)) {
+      if (layered && ((uint32_t)(uintptr_t)sg.pad1 & 1u)) {
         if (my_tiles <= (uint32_t)MARK_SMALL) mark_object_tiles(lm, o.minx, o.miny, o.maxx, o.maxy);
         else { mark_big = true; mark_rect = MarkRect{o.minx, o.miny, o.maxx, o.maxy}; }
         cls_bit = REC_CLASS_BIT;
@@ -462,13 +487,13 @@ preprocess_composed_kernel(const int P, const int D, const int M,
       r2 = make_float4(rgb[0], rgb[1], rgb[2], __uint_as_float(clamped));
     }
   }
-  if (lm.tile_obj != nullptr) mark_object_tiles_wave(lm, mark_big, mark_rect);
+  if (layered) mark_object_tiles_wave(lm, mark_big, mark_rect);
   s_out[REC_STRIDE * threadIdx.x + 0] = r0;
   s_out[REC_STRIDE * threadIdx.x + 1] = r1;
   s_out[REC_STRIDE * threadIdx.x + 2] = r2;
   s_out[REC_STRIDE * threadIdx.x + 3] = make_float4(0.f, 0.f, 0.f, 0.f);
   __syncthreads();
-  if (ds_table0 != nullptr && my_key != CULLED_KEY) atomicAdd(&s_dh[my_key & (DS_RADIX - 1)], 1u);
+  if ((HOT || ds_table0 != nullptr) && my_key != CULLED_KEY) atomicAdd(&s_dh[my_key & (DS_RADIX - 1)], 1u);
   const int nrec4 = min(256, P - base) * REC_STRIDE;
   float4* dst = rec + (size_t)REC_STRIDE * base;
 #pragma unroll
@@ -477,7 +502,7 @@ preprocess_composed_kernel(const int P, const int D, const int M,
     // a culled Gaussian's record (radius bits 0) is never read: its sector is not written
     if (e < nrec4 && __float_as_int(s_out[e & ~(REC_STRIDE - 1)].w) != 0) dst[e] = s_out[e];
   }
-  if (ds_table0 != nullptr) {
+  if (HOT || ds_table0 != nullptr) {
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < DS_RADIX / 256; k++) {
@@ -486,7 +511,7 @@ preprocess_composed_kernel(const int P, const int D, const int M,
         atomicAdd(&ds_table0[(size_t)(blockIdx.x / (DS_CHUNK / 256)) * DS_RADIX + k * 256 + threadIdx.x], cnt);
     }
   }
-  if (pre_counts != nullptr) block_count_sums(my_tiles, my_st, my_key, pre_counts);
+  if (HOT || pre_counts != nullptr) block_count_sums(my_tiles, my_st, my_key, pre_counts);
 }
 
 void launch_preprocess_composed(hipStream_t s, int P, int D, int M, const SegmentDev* segs, int nseg,
@@ -494,12 +519,14 @@ void launch_preprocess_composed(hipStream_t s, int P, int D, int M, const Segmen
                                 uint32_t* depth_key, uint32_t* tiles, uint2* rects,
                                 uint32_t* ds_table0, uint4* pre_counts, LayerMarks lm) {
   if (P <= 0) return;
-#define PC_LAUNCH(M4)                                                                           \
-  preprocess_composed_kernel<M4><<<(P + 255) / 256, 256, 0, s>>>(                                \
+#define PC_LAUNCH(M4, HOT)                                                                      \
+  preprocess_composed_kernel<M4, HOT><<<(P + 255) / 256, 256, 0, s>>>(                           \
       P, D, M, segs, nseg, scale_modifier, cam.view, cam.proj, cam.campos, cam.W, cam.H, cam.gx,  \
       cam.gy, cam.tan_fovx, cam.tan_fovy, cam.focal_x, cam.focal_y, radii, rec, depth_key, tiles, \
       rects, ds_table0, pre_counts, lm)
-  if (M == 4) PC_LAUNCH(true); else PC_LAUNCH(false);
+  const bool hot = M == 4 && lm.tile_obj == nullptr && rects != nullptr && ds_table0 != nullptr &&
+                   pre_counts != nullptr;
+  if (hot) PC_LAUNCH(true, true); else if (M == 4) PC_LAUNCH(true, false); else PC_LAUNCH(false, false);
 #undef PC_LAUNCH
 }
 
@@ -517,13 +544,19 @@ void launch_preprocess(hipStream_t s, int P, int D, int M, const float* means3D,
                        float4* rec, uint32_t* depth_key, uint32_t* tiles, uint2* rects,
                        uint32_t* ds_table0, uint4* pre_counts, LayerMarks lm) {
   if (P <= 0) return;
-  preprocess_kernel<<<(P + 255) / 256, 256, 0, s>>>(
-      P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, cov3D_precomp,
-      colors_precomp, cam.view, cam.proj, cam.campos, cam.W, cam.H, cam.gx, cam.gy, cam.tan_fovx,
-      cam.tan_fovy, cam.focal_x, cam.focal_y, radii, rec, depth_key, tiles, rects, ds_table0,
-      pre_counts, ((((uintptr_t)means3D | (uintptr_t)scales | (uintptr_t)shs) & 15) == 0) ? 1 : 0, lm);
+  const int vec_ok = ((((uintptr_t)means3D | (uintptr_t)scales | (uintptr_t)shs) & 15) == 0) ? 1 : 0;
+  // the default hierarchical frame with the fat depth sort: the specialised instantiation (preprocess_kernel<true>)
+  const bool hot = cov3D_precomp == nullptr && colors_precomp == nullptr && scales != nullptr && M == 4 && vec_ok &&
+                   lm.tile_obj == nullptr && rects != nullptr && ds_table0 != nullptr && pre_counts != nullptr;
+#define PP_LAUNCH(HOT)                                                                              \
+  preprocess_kernel<HOT><<<(P + 255) / 256, 256, 0, s>>>(                                            \
+      P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, cov3D_precomp,            \
+      colors_precomp, cam.view, cam.proj, cam.campos, cam.W, cam.H, cam.gx, cam.gy, cam.tan_fovx,    \
+      cam.tan_fovy, cam.focal_x, cam.focal_y, radii, rec, depth_key, tiles, rects, ds_table0,        \
+      pre_counts, vec_ok, lm)
+  if (hot) PP_LAUNCH(true); else PP_LAUNCH(false);
+#undef PP_LAUNCH
 }
-
 
 void launch_visible_filter(hipStream_t s, int P, const float* means3D, const float* scales,
                            float scale_modifier, const float* rotations,
