@@ -10,6 +10,7 @@ Layout:
   rasterizer.py   host-side mirror of the reference's Python operator interface
   harness.py      build-owned counterpart of the reference's callers (cameras, synthetic scenes)
   trajectory.py   frame-sharded multi-GPU trajectory rendering (one process per GPU, RCCL gather)
+  perception.py   the frame as the in-process detector's input: letterbox + CHW + / 255 in one launch
   build.py        in-tree build (hipcc for gfx950, g++ for the binding)
 
 Importing this package does not load native code; ``gaussianrpg_amd.rasterizer`` does, and fails

@@ -68,6 +68,9 @@ HIP_UNITS = {
     # feature planes of a composed frame: compose_one() must give the bits the composed preprocess sees (no FMA
     # contraction); no atomics, deterministic fixed-order reduction of the pose gradient
     "features.hip": ["-ffp-contract=off"],
+    # frame -> detector input: the quantisation of the float planes must give pack_hwc's bytes and the host's
+    # table arithmetic numpy's (no FMA contraction); q / 255 is a correctly rounded division, not a reciprocal
+    "letterbox.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "api.hip": [],
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept

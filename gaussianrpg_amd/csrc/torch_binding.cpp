@@ -1247,6 +1247,123 @@ torch::Tensor PackHWC(const torch::Tensor& color, const bool truncate) {
   return out;
 }
 
+// ---- frame -> detector input (gaussianrpg_amd/perception.py; csrc/letterbox.hip) ----
+
+// letterbox()'s arithmetic (utils/augmentations.py:121-151); host only.
+// Returns [new_h, new_w, top, bottom, left, right, h, w].
+std::vector<int> LetterboxGeometry(const int height, const int width, const int new_h_req, const int new_w_req,
+                                   const bool auto_pad, const bool scale_fill, const bool scaleup, const int stride) {
+  std::vector<int> g(8, 0);
+  const int rc = grpg_letterbox_geometry(height, width, new_h_req, new_w_req, auto_pad, scale_fill, scaleup, stride,
+                                         g.data());
+  if (rc != GRPG_OK) raise_abi_error("grpg_letterbox_geometry", rc);
+  return g;
+}
+
+// (x_table int32 [new_w,2], y_table int32 [new_h,2]) on the host; the entry format is in the C header.
+std::tuple<torch::Tensor, torch::Tensor> LetterboxTables(const int height, const int width, const int new_h,
+                                                         const int new_w) {
+  TORCH_CHECK(height > 0 && width > 0 && new_h > 0 && new_w > 0, "letterbox_tables: sizes must be positive");
+  torch::Tensor xt = torch::empty({new_w, 2}, torch::kInt32), yt = torch::empty({new_h, 2}, torch::kInt32);
+  const int rc = grpg_letterbox_tables(height, width, new_h, new_w, xt.data_ptr<int>(), yt.data_ptr<int>());
+  if (rc != GRPG_OK) raise_abi_error("grpg_letterbox_tables", rc);
+  return std::make_tuple(xt, yt);
+}
+
+namespace {
+// What the two letterbox bindings share.  The checks run in this order: the frame's dtype and shape (by the
+// caller), geometry, out's dtype / shape / layout, then the devices -- so a host tensor is told "no CPU path" only
+// when everything else about the call is right.
+struct LetterboxCall {
+  torch::Tensor out, xt, yt;
+  const int *p_xt = nullptr, *p_yt = nullptr;
+  bool half;
+
+  LetterboxCall(const torch::Tensor& frame, const int H, const int W, const std::vector<int>& g,
+                const c10::optional<torch::Tensor>& x_table, const c10::optional<torch::Tensor>& y_table,
+                const c10::optional<torch::Tensor>& out_opt, const bool out_half) : half(out_half) {
+    TORCH_CHECK(g.size() == 8, "letterbox: geometry must hold 8 ints (new_h, new_w, top, bottom, left, right, h, w)");
+    TORCH_CHECK(g[6] > 0 && g[7] > 0, "letterbox: geometry gives an empty output");
+    const int64_t h = g[6], w = g[7];
+    const auto dtype = half ? torch::kFloat16 : torch::kFloat32;
+    const bool given = out_opt.has_value() && out_opt->defined();
+    if (given) {
+      const torch::Tensor& o = *out_opt;
+      TORCH_CHECK(o.scalar_type() == dtype, "letterbox: out must be ", half ? "float16" : "float32", " (got ",
+                  o.scalar_type(), ")");
+      const bool shape3 = o.dim() == 3 && o.size(0) == 3 && o.size(1) == h && o.size(2) == w;
+      const bool shape4 = o.dim() == 4 && o.size(0) == 1 && o.size(1) == 3 && o.size(2) == h && o.size(3) == w;
+      TORCH_CHECK(shape3 || shape4, "letterbox: out must be [3,", h, ",", w, "] or [1,3,", h, ",", w, "] (got ",
+                  o.sizes(), ")");
+      TORCH_CHECK(o.is_contiguous(), "letterbox: out must be contiguous");
+    }
+    TORCH_CHECK(frame.is_contiguous(), "letterbox: frame must be contiguous");
+    TORCH_CHECK(frame.is_cuda(), "letterbox: frame must live on a ROCm/HIP device (torch device 'cuda'); "
+                                 "this op has no CPU path");
+    if (given) {
+      TORCH_CHECK(out_opt->device() == frame.device(), "letterbox: out must be on ", frame.device(), " (got ",
+                  out_opt->device(), ")");
+      out = *out_opt;
+    } else {
+      out = torch::empty({1, 3, h, w}, frame.options().dtype(dtype));
+    }
+    if (g[0] != H || g[1] != W) {   // a resize: the tables are needed
+      TORCH_CHECK(x_table.has_value() && x_table->defined() && y_table.has_value() && y_table->defined(),
+                  "letterbox: x_table and y_table are needed when the resized size differs from the frame's");
+      p_xt = table(*x_table, g[1], frame, "x_table", xt);
+      p_yt = table(*y_table, g[0], frame, "y_table", yt);
+    }
+  }
+
+  static const int* table(const torch::Tensor& t, const int64_t n, const torch::Tensor& frame, const char* name,
+                          torch::Tensor& keep) {
+    TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.dim() == 2 && t.size(0) == n && t.size(1) == 2 &&
+                    t.is_contiguous(), "letterbox: ", name, " must be a contiguous int32 [", n, ",2] tensor");
+    TORCH_CHECK(t.device() == frame.device(), "letterbox: ", name, " must be on ", frame.device(), " (got ",
+                t.device(), ")");
+    keep = t;
+    return t.data_ptr<int>();
+  }
+};
+}  // namespace
+
+// uint8 [H,W,3] device frame -> [1,3,h,w] (or `out`, returned as given)
+torch::Tensor LetterboxRgb8(const torch::Tensor& frame, const std::vector<int>& geometry,
+                            const c10::optional<torch::Tensor>& x_table, const c10::optional<torch::Tensor>& y_table,
+                            const bool reverse_channels, const c10::optional<torch::Tensor>& out, const bool half) {
+  TORCH_CHECK(frame.scalar_type() == torch::kUInt8, "letterbox_rgb8: frame must be uint8 (got ", frame.scalar_type(),
+              ")");
+  TORCH_CHECK(frame.dim() == 3 && frame.size(2) == 3 && frame.size(0) > 0 && frame.size(1) > 0,
+              "letterbox_rgb8: frame must be [H,W,3] (got ", frame.sizes(), ")");
+  const int H = frame.size(0), W = frame.size(1);
+  LetterboxCall c(frame, H, W, geometry, x_table, y_table, out, half);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(frame.device());
+  run("grpg_letterbox_rgb8", [&](void* stream) {
+    return grpg_letterbox_rgb8(frame.data_ptr<uint8_t>(), H, W, geometry.data(), c.p_xt, c.p_yt, reverse_channels,
+                               c.out.data_ptr(), half, stream);
+  });
+  return c.out;
+}
+
+// float32 [3,H,W] device planes -> the same, quantised on load as pack_hwc does
+torch::Tensor LetterboxPlanes(const torch::Tensor& frame, const std::vector<int>& geometry,
+                              const c10::optional<torch::Tensor>& x_table, const c10::optional<torch::Tensor>& y_table,
+                              const bool reverse_channels, const bool truncate,
+                              const c10::optional<torch::Tensor>& out, const bool half) {
+  TORCH_CHECK(frame.scalar_type() == torch::kFloat32, "letterbox_planes: frame must be float32 (got ",
+              frame.scalar_type(), ")");
+  TORCH_CHECK(frame.dim() == 3 && frame.size(0) == 3 && frame.size(1) > 0 && frame.size(2) > 0,
+              "letterbox_planes: frame must be [3,H,W] (got ", frame.sizes(), ")");
+  const int H = frame.size(1), W = frame.size(2);
+  LetterboxCall c(frame, H, W, geometry, x_table, y_table, out, half);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(frame.device());
+  run("grpg_letterbox_planes", [&](void* stream) {
+    return grpg_letterbox_planes(frame.data_ptr<float>(), H, W, geometry.data(), c.p_xt, c.p_yt, reverse_channels,
+                                 truncate, c.out.data_ptr(), half, stream);
+  });
+  return c.out;
+}
+
 std::tuple<std::vector<float>, int> StageTiming() {
   std::vector<float> ms(GRPG_NUM_STAGES, 0.f);
   int calls = 0;
@@ -2012,6 +2129,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("mask") = pybind11::none(), pybind11::arg("jitter") = pybind11::none());
   m.def("pack_u8", &PackU8, pybind11::arg("color"), pybind11::arg("out") = pybind11::none());
   m.def("pack_hwc", &PackHWC);
+  // frame -> detector input (perception.py)
+  m.def("letterbox_geometry", &LetterboxGeometry, pybind11::arg("height"), pybind11::arg("width"),
+        pybind11::arg("new_h_req"), pybind11::arg("new_w_req"), pybind11::arg("auto_pad") = true,
+        pybind11::arg("scale_fill") = false, pybind11::arg("scaleup") = true, pybind11::arg("stride") = 32);
+  m.def("letterbox_tables", &LetterboxTables);   // (x_table [new_w,2], y_table [new_h,2]), host int32
+  m.def("letterbox_rgb8", &LetterboxRgb8, pybind11::arg("frame"), pybind11::arg("geometry"),
+        pybind11::arg("x_table") = pybind11::none(), pybind11::arg("y_table") = pybind11::none(),
+        pybind11::arg("reverse_channels") = true, pybind11::arg("out") = pybind11::none(),
+        pybind11::arg("half") = false);
+  m.def("letterbox_planes", &LetterboxPlanes, pybind11::arg("frame"), pybind11::arg("geometry"),
+        pybind11::arg("x_table") = pybind11::none(), pybind11::arg("y_table") = pybind11::none(),
+        pybind11::arg("reverse_channels") = true, pybind11::arg("truncate") = true,
+        pybind11::arg("out") = pybind11::none(), pybind11::arg("half") = false);
   m.def("get_backward_timing", &BackwardTiming);   // (blend ms sum, preprocess ms sum, calls)
   m.def("set_stage_timing", [](int mode) { grpg_set_stage_timing(mode); });   // 0 off, 1 all, 2 render only
   m.def("stage_timing", &StageTiming);
