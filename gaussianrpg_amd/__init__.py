@@ -10,7 +10,8 @@ Layout:
   rasterizer.py   host-side mirror of the reference's Python operator interface
   harness.py      build-owned counterpart of the reference's callers (cameras, synthetic scenes)
   trajectory.py   frame-sharded multi-GPU trajectory rendering (one process per GPU, RCCL gather)
-  perception.py   the frame as the in-process detector's input: letterbox + CHW + / 255 in one launch
+  perception.py   the frame as the in-process detector's input: letterbox + CHW + / 255 in one launch;
+                  the detector's output as detections: NMS + the mapping back to the frame, no host wait
   build.py        in-tree build (hipcc for gfx950, g++ for the binding)
 
 Importing this package does not load native code; ``gaussianrpg_amd.rasterizer`` does, and fails

@@ -71,6 +71,9 @@ HIP_UNITS = {
     # frame -> detector input: the quantisation of the float planes must give pack_hwc's bytes and the host's
     # table arithmetic numpy's (no FMA contraction); q / 255 is a correctly rounded division, not a reciprocal
     "letterbox.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # detector output -> detections: every step of the IoU is one IEEE float32 operation as in the numpy restatement
+    # (areaA + areaB - inter and iw * ih must not fuse), the division correctly rounded; no atomics
+    "nms.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "api.hip": [],
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept

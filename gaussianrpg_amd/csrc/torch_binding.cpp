@@ -1364,6 +1364,69 @@ torch::Tensor LetterboxPlanes(const torch::Tensor& frame, const std::vector<int>
   return c.out;
 }
 
+// ---- detector output -> detections (gaussianrpg_amd/perception.py; csrc/nms.hip) ----
+
+// prediction float32 [bs,N,5+nc] on the device -> (det float32 [bs,max_det,6], count int32 [bs]), both written in
+// full, no host wait.  class_allow: uint8 [nc] on the device or None; frame_map: () or (h, w, H, W, pad_x, pad_y);
+// det_out / count_out: preallocated results, returned as given.
+std::tuple<torch::Tensor, torch::Tensor> NmsDetections(const torch::Tensor& prediction, const double conf_thres,
+                                                       const double iou_thres,
+                                                       const c10::optional<torch::Tensor>& class_allow,
+                                                       const bool agnostic, const int max_det, const int max_nms,
+                                                       const double max_wh, const std::vector<double>& frame_map,
+                                                       const c10::optional<torch::Tensor>& det_out,
+                                                       const c10::optional<torch::Tensor>& count_out) {
+  TORCH_CHECK(prediction.scalar_type() == torch::kFloat32, "nms_detections: prediction must be float32 (got ",
+              prediction.scalar_type(), ")");
+  TORCH_CHECK(prediction.dim() == 3 && prediction.size(0) > 0 && prediction.size(1) > 0 && prediction.size(2) >= 6,
+              "nms_detections: prediction must be [bs,N,5+nc] with nc >= 1 (got ", prediction.sizes(), ")");
+  TORCH_CHECK(prediction.is_contiguous(), "nms_detections: prediction must be contiguous");
+  const int64_t bs = prediction.size(0), N = prediction.size(1), nc = prediction.size(2) - 5;
+  TORCH_CHECK(bs * N < (int64_t(1) << 31), "nms_detections: bs * N must be below 2^31");
+  TORCH_CHECK(conf_thres >= 0.0 && conf_thres <= 1.0 && iou_thres >= 0.0 && iou_thres <= 1.0,
+              "nms_detections: conf_thres and iou_thres must lie in [0, 1]");
+  TORCH_CHECK(max_det >= 1 && max_det <= 1024, "nms_detections: max_det must lie in [1, 1024] (got ", max_det, ")");
+  TORCH_CHECK(max_nms >= 1, "nms_detections: max_nms must be positive");
+  TORCH_CHECK(frame_map.empty() || frame_map.size() == 6,
+              "nms_detections: frame_map must be empty or (h, w, H, W, pad_x, pad_y)");
+  const bool det_given = det_out.has_value() && det_out->defined();
+  const bool count_given = count_out.has_value() && count_out->defined();
+  if (det_given)
+    TORCH_CHECK(det_out->scalar_type() == torch::kFloat32 && det_out->dim() == 3 && det_out->size(0) == bs &&
+                    det_out->size(1) == max_det && det_out->size(2) == 6 && det_out->is_contiguous(),
+                "nms_detections: out det must be a contiguous float32 [", bs, ",", max_det, ",6] tensor");
+  if (count_given)
+    TORCH_CHECK(count_out->scalar_type() == torch::kInt32 && count_out->dim() == 1 && count_out->size(0) == bs &&
+                    count_out->is_contiguous(),
+                "nms_detections: out count must be a contiguous int32 [", bs, "] tensor");
+  TORCH_CHECK(prediction.is_cuda(), "nms_detections: prediction must live on a ROCm/HIP device (torch device "
+                                    "'cuda'); this op has no CPU path");
+  const unsigned char* allow = nullptr;
+  if (class_allow.has_value() && class_allow->defined()) {
+    const torch::Tensor& t = *class_allow;
+    TORCH_CHECK(t.scalar_type() == torch::kUInt8 && t.dim() == 1 && t.size(0) == nc && t.is_contiguous() &&
+                    t.device() == prediction.device(),
+                "nms_detections: class_allow must be a contiguous uint8 [", nc, "] tensor on ", prediction.device());
+    allow = t.data_ptr<uint8_t>();
+  }
+  if (det_given) TORCH_CHECK(det_out->device() == prediction.device(), "nms_detections: out det must be on ",
+                             prediction.device());
+  if (count_given) TORCH_CHECK(count_out->device() == prediction.device(), "nms_detections: out count must be on ",
+                               prediction.device());
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(prediction.device());
+  torch::Tensor det = det_given ? *det_out : torch::empty({bs, max_det, 6}, prediction.options());
+  torch::Tensor count = count_given ? *count_out : torch::empty({bs}, prediction.options().dtype(torch::kInt32));
+  const size_t bytes = grpg_nms_workspace_bytes((int)bs, (int)N);
+  torch::Tensor ws = torch::empty({(int64_t)bytes}, prediction.options().dtype(torch::kByte));
+  run("grpg_nms_detections", [&](void* stream) {
+    return grpg_nms_detections(prediction.data_ptr<float>(), (int)bs, (int)N, (int)nc, (float)conf_thres,
+                               (float)iou_thres, allow, agnostic, max_det, max_nms, (float)max_wh,
+                               frame_map.empty() ? nullptr : frame_map.data(), ws.data_ptr(), bytes,
+                               det.data_ptr<float>(), count.data_ptr<int>(), stream);
+  });
+  return std::make_tuple(det, count);
+}
+
 std::tuple<std::vector<float>, int> StageTiming() {
   std::vector<float> ms(GRPG_NUM_STAGES, 0.f);
   int calls = 0;
@@ -2142,6 +2205,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("x_table") = pybind11::none(), pybind11::arg("y_table") = pybind11::none(),
         pybind11::arg("reverse_channels") = true, pybind11::arg("truncate") = true,
         pybind11::arg("out") = pybind11::none(), pybind11::arg("half") = false);
+  // detector output -> detections (perception.py): (det [bs,max_det,6], count [bs])
+  m.def("nms_detections", &NmsDetections, pybind11::arg("prediction"), pybind11::arg("conf_thres") = 0.25,
+        pybind11::arg("iou_thres") = 0.45, pybind11::arg("class_allow") = pybind11::none(),
+        pybind11::arg("agnostic") = false, pybind11::arg("max_det") = 300, pybind11::arg("max_nms") = 30000,
+        pybind11::arg("max_wh") = 7680.0, pybind11::arg("frame_map") = std::vector<double>(),
+        pybind11::arg("det_out") = pybind11::none(), pybind11::arg("count_out") = pybind11::none());
+  m.def("nms_workspace_bytes", [](int bs, int N) { return grpg_nms_workspace_bytes(bs, N); });
   m.def("get_backward_timing", &BackwardTiming);   // (blend ms sum, preprocess ms sum, calls)
   m.def("set_stage_timing", [](int mode) { grpg_set_stage_timing(mode); });   // 0 off, 1 all, 2 render only
   m.def("stage_timing", &StageTiming);

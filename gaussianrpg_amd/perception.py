@@ -20,9 +20,15 @@ Known differences from the reference's cv2 calls: cv2.resize switches to area av
 wherever cv2 is installed).  With the reference's own configuration (``imgsz`` = image width) nothing is resized and
 the result is exact.
 
-Non-maximum suppression is not part of this module (the reference calls torchvision.ops.nms).
+The way back is here too: ``detections`` turns the detector's raw [bs,N,5+nc] head output into detections on the
+device -- the reference's ``non_max_suppression`` (utils/general.py:1005-1116, whose only NMS is torchvision.ops.nms)
+and, with a plan, ``scale_coords(...).round()`` (simulator.py:368) -- in one call without a host wait
+(csrc/nms.hip); ``non_max_suppression`` is the same under the reference's signature.  Three stated differences:
+equal confidences are ordered by ascending row (the reference's argsort leaves ties open), the frame mapping is a
+true float32 division (PyTorch's device kernels may multiply by a reciprocal; with the simulator's own plan the gain
+is 1 and they agree), and the prediction must be float32.
 """
-from typing import Optional, Tuple, Union
+from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -140,6 +146,105 @@ def detector_input(frame: torch.Tensor, plan: LetterboxPlan, *, reverse_channels
     else:
         res = _C.letterbox_rgb8(frame, plan.geometry, xt, yt, bool(reverse_channels), out, half)
     return res if out is None else out
+
+
+# ---- detector output -> detections ----
+
+MAX_WH = 7680        # non_max_suppression's max_wh: the per-class shift of the boxes (utils/general.py:1039)
+MAX_NMS = 30000      # its max_nms: candidates considered per image (utils/general.py:1040)
+MAX_DET_LIMIT = 1024  # the kept list of csrc/nms.hip lives in LDS
+
+_class_tables = {}
+
+
+def _class_table(classes: Sequence[int], nc: int, device: torch.device) -> torch.Tensor:
+    """uint8 [nc] on ``device``, 1 where the class is allowed; built once per (classes, nc, device)."""
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (tuple(int(c) for c in classes), int(nc), device)
+    if key not in _class_tables:
+        host = torch.zeros(nc, dtype=torch.uint8)
+        for c in key[0]:
+            if 0 <= c < nc:          # a class the head does not have can never match (the reference: no row equals it)
+                host[c] = 1
+        _class_tables[key] = host.to(device)
+    return _class_tables[key]
+
+
+def _check_nms_args(who: str, prediction, conf_thres, iou_thres, max_det, max_nms):
+    if not isinstance(prediction, torch.Tensor):
+        raise TypeError("%s: prediction must be a tensor (got %s)" % (who, type(prediction).__name__))
+    if prediction.dtype != torch.float32:
+        raise TypeError("%s: prediction must be float32 (got %s); a .half() detector forms obj * cls in half, which is "
+                        "a different contract: pass prediction.float() if that is what you mean" %
+                        (who, prediction.dtype))
+    if prediction.dim() != 3 or prediction.shape[2] < 6 or prediction.shape[0] < 1 or prediction.shape[1] < 1:
+        raise ValueError("%s: prediction must be [bs, N, 5 + nc] with bs, N, nc >= 1 (got %s)" %
+                         (who, list(prediction.shape)))
+    if not prediction.is_contiguous():
+        raise ValueError("%s: prediction must be contiguous (a copy of the head's output would hide its cost)" % who)
+    if prediction.shape[0] * prediction.shape[1] >= 2 ** 31:
+        raise ValueError("%s: bs * N must be below 2^31" % who)
+    if not 0.0 <= conf_thres <= 1.0:
+        raise ValueError("%s: invalid confidence threshold %r, valid values are between 0.0 and 1.0" % (who, conf_thres))
+    if not 0.0 <= iou_thres <= 1.0:
+        raise ValueError("%s: invalid IoU threshold %r, valid values are between 0.0 and 1.0" % (who, iou_thres))
+    if int(max_det) != max_det or not 1 <= max_det <= MAX_DET_LIMIT:
+        raise ValueError("%s: max_det must be an integer in [1, %d] (got %r)" % (who, MAX_DET_LIMIT, max_det))
+    if int(max_nms) != max_nms or max_nms < 1:
+        raise ValueError("%s: max_nms must be a positive integer (got %r)" % (who, max_nms))
+
+
+def frame_map(plan: LetterboxPlan) -> Tuple[float, float, float, float, float, float]:
+    """(h, w, H, W, pad_x, pad_y) of ``scale_coords((h, w), boxes, (H, W))`` with ``ratio_pad=None``
+    (utils/torch_utils.py:511-515), in double: the detector input's size, the frame's, and the pads."""
+    h, w = plan.out_shape
+    H, W = plan.height, plan.width
+    gain = min(h / H, w / W)
+    return (float(h), float(w), float(H), float(W), (w - W * gain) / 2, (h - H * gain) / 2)
+
+
+def detections(prediction: torch.Tensor, conf_thres: float = 0.25, iou_thres: float = 0.45,
+               classes: Optional[Sequence[int]] = None, agnostic: bool = False, max_det: int = 300, *,
+               max_nms: int = MAX_NMS, plan: Optional[LetterboxPlan] = None,
+               out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The detector's raw float32 [bs,N,5+nc] head output -> ``(det, count)`` on the device, on the current stream,
+    without a host wait: ``det`` float32 [bs,max_det,6] holds image b's detections as rows
+    ``x1, y1, x2, y2, conf, cls`` in descending confidence in its first ``count[b]`` rows and zeros below; ``count``
+    is int32 [bs].  The semantics are the reference's ``non_max_suppression`` (best class per row, class-shifted
+    greedy NMS as torchvision.ops.nms documents it), restated in tests/nms_truth.py and met bit for bit; equal
+    confidences are ordered by ascending row.  The prediction is not modified.
+
+    classes: keep only these class indices.  agnostic: one NMS over all classes.  max_det: 1..1024.
+    plan: a ``LetterboxPlan``; columns 0-3 then are ``scale_coords(plan.out_shape, boxes, frame size).round()``,
+    the boxes in the frame's pixels as simulator.py:368 computes them (a true float32 division by the gain).
+    out: ``(det, count)`` preallocated for this bs and max_det; every element is written, and they are returned."""
+    _check_nms_args("detections", prediction, conf_thres, iou_thres, max_det, max_nms)
+    nc = prediction.shape[2] - 5
+    table = None if classes is None else _class_table(classes, nc, prediction.device)
+    fmap = [] if plan is None else list(frame_map(plan))
+    det_out, count_out = (None, None) if out is None else out
+    det, count = _C.nms_detections(prediction, float(conf_thres), float(iou_thres), table, bool(agnostic),
+                                   int(max_det), int(max_nms), float(MAX_WH), fmap, det_out, count_out)
+    return (det, count) if out is None else (det_out, count_out)
+
+
+def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False,
+                        labels=(), max_det=300, nm=0):
+    """The reference's ``non_max_suppression`` (utils/general.py:1005-1116): same signature, same return -- a list of
+    one (n, 6) tensor ``xyxy, conf, cls`` per image -- through ``detections``.  It accepts the
+    ``(inference_out, loss_out)`` tuple of a model in validation mode.  One host wait, to read the counts.
+    Refused: ``multi_label=True``, ``labels``, ``nm > 0``, and what ``detections`` refuses."""
+    if multi_label:
+        raise ValueError("non_max_suppression: multi_label=True is not supported (best class per box only)")
+    if labels is not None and len(labels):
+        raise ValueError("non_max_suppression: a-priori labels (autolabelling) are not supported")
+    if nm:
+        raise ValueError("non_max_suppression: mask coefficients (nm > 0) are not supported")
+    if isinstance(prediction, (list, tuple)):
+        prediction = prediction[0]
+    det, count = detections(prediction, conf_thres, iou_thres, classes, agnostic, max_det)
+    return [det[b, :n] for b, n in enumerate(count.tolist())]
 
 
 # ---- host restatement: what stands in for cv2 on the reference's route through the host ----
