@@ -4,16 +4,25 @@ operation on float32 operands, which is what the kernels do (-ffp-contract=off, 
 
 It is written from the text of the reference's non_max_suppression (utils/general.py:1005-1116), its scale_coords /
 clip_coords (utils/torch_utils.py:501-547) and the documented rule of torchvision.ops.nms (greedy: walk the boxes in
-descending score, drop a box whose IoU with an already kept box exceeds the threshold).  The reference's own
-function cannot be imported here -- it needs torchvision, cv2 and pandas -- so there is NO golden recorded from it;
-tests/test_nms_host.py compares the greedy step with torchvision.ops.nms wherever torchvision imports.
+descending score, drop a box whose IoU with an already kept box exceeds the threshold).  The reference's modules
+cannot be imported here -- they need torchvision, cv2 and pandas -- but its FUNCTIONS run: tests/golden/ref_nms.json +
+.npz hold what non_max_suppression and scale_coords(...).round() themselves returned on CPU torch for 21 inputs
+(tests/golden/make_golden_nms.py cuts them out with ast; only torchvision.ops.nms is a stand-in there), and
+tests/test_nms_golden.py holds this restatement to those outputs bit for bit.  tests/test_nms_host.py compares the
+greedy step with torchvision.ops.nms wherever torchvision imports.
 
-Definitions this project adds where the reference leaves a choice open:
-  * equal confidences are ordered by ascending row (argsort(descending=True) leaves ties unspecified);
-  * equal best class scores give the lowest class;
-  * thresholds are compared as float32 values;
-  * the frame mapping divides by the gain (a true float32 division), clamps with comparisons (NaN stays NaN) and
-    rounds half to even.
+Where the reference's text leaves a choice open -- and what its recorded output says about it:
+  * equal confidences are ordered by ascending row (argsort(descending=True) leaves ties unspecified): this
+    project's definition; the golden's inputs have distinct confidences and say nothing about it;
+  * equal best class scores give the lowest class: likewise this project's definition;
+  * thresholds are compared as float32 values: CONFIRMED by the golden (a row at exactly float32(t) is dropped, its
+    successor kept, for t = 0.25 and for t = 0.3 where float32(0.3) > 0.3: CPU torch casts the Python threshold to
+    the tensor's type).  The IoU threshold likewise here; torchvision's CPU kernel compares the float IoU with the
+    threshold in double, which differs only for an IoU of exactly float32(t) when float32(t) > t -- for the
+    reference's 0.45 no float32 value tells the two apart;
+  * the frame mapping divides by the gain (a true float32 division) and rounds half to even: CONFIRMED by the
+    golden on CPU torch, gain 1 and gain 224/375 alike, with all four clamps binding; it clamps with comparisons,
+    NaN stays NaN: confirmed for the NaN box of nan_case(), whose NaN IoU is the stand-in's.
 """
 import numpy as np
 
@@ -220,4 +229,80 @@ def make_prediction(N, nc, n_cand, seed, size=(640, 640), clusters=None, jitter=
         p[b, rows, 4] = (0.5 + 0.5 * (rng.permutation(n) + 0.5) / max(n, 1)).astype(np.float32)
         if grid:
             p[b, :, :4] = np.round(p[b, :, :4] / grid) * grid
+    return p
+
+
+# ---- the inputs of tests/golden/ref_nms.* (make_golden_nms.py records the reference's own outputs for them) ----
+
+SIM = (1088, 1600, 1066, 1600)        # LetterboxPlan.for_simulator(1066, 1600): gain 1, 11 rows of border above
+RESIZE = (224, 640, 375, 1242)        # LetterboxPlan(375, 1242, 640)
+
+
+def frame_case(h, w, seed):
+    """400 candidates on a half-pixel grid over the (h, w) input, 40 each pushed beyond its right, top, left and
+    bottom side: all four clamps of the frame mapping bind, and mapped values land on halves."""
+    p = make_prediction(3000, 3, 400, seed=seed, size=(h, w), grid=0.5)
+    rows = np.nonzero(p[0, :, 4] > F(0.25))[0]
+    p[0, rows[:40], 0] += w
+    p[0, rows[40:80], 1] -= h
+    p[0, rows[80:120], 0] -= w
+    p[0, rows[120:160], 1] += h
+    return p
+
+
+def threshold_case(t, product):
+    """Rows at the confidence threshold t and one ulp above it, and one plainly above.  product=False: the
+    objectness is float32(t) / its successor, the class score 1.  product=True: objectness 0.5 and class score
+    2 * float32(t) / 2 * its successor, so obj * cls lands exactly there."""
+    ft = F(t)
+    up = np.nextafter(ft, F(1))
+    if product:
+        x = rows_of((0, 0, 10, 10, 0.5, F(2) * ft), (100, 0, 110, 10, 0.5, F(2) * up), (200, 0, 210, 10, 0.9, 1.0))
+        assert F(0.5) * x[0, 5] == ft and F(0.5) * x[1, 5] == up
+    else:
+        x = rows_of((0, 0, 10, 10, ft, 1.0), (100, 0, 110, 10, up, 1.0), (200, 0, 210, 10, 0.9, 1.0))
+        assert x[0, 4] == ft and x[1, 4] == up
+    return x[None]
+
+
+MAX_NMS_ISOLATED_Y = 2000.0
+
+
+def max_nms_case(seed=21):
+    """N = 32768, nc = 1, class score exactly 1 (conf = obj): 30 000 candidates in 56 well separated clusters, and
+    200 isolated candidates (centre y >= MAX_NMS_ISOLATED_Y) that hold the 200 LOWEST confidences -- beyond the
+    reference's max_nms = 30000 cut, so absent from its output although nothing overlaps them.  The confidences are
+    (20000 + rank) / 65536, exact in float32 and distinct."""
+    rng = np.random.RandomState(seed)
+    N, n_cl, n_iso = 32768, 30000, 200
+    p = np.zeros((1, N, 6), np.float32)
+    p[0, :, 0] = rng.uniform(0, 1200, N)
+    p[0, :, 1] = rng.uniform(0, 1000, N)
+    p[0, :, 2:4] = rng.uniform(8, 120, (N, 2))
+    p[0, :, 4] = rng.uniform(0.0, 0.2, N)
+    p[0, :, 5] = 1.0
+    rows = rng.permutation(N)[:n_cl + n_iso]
+    iso, cl = rows[:n_iso], rows[n_iso:]
+    k = np.arange(n_iso)
+    p[0, iso, 0] = 50.0 + 40.0 * (k % 25)
+    p[0, iso, 1] = MAX_NMS_ISOLATED_Y + 40.0 * (k // 25)
+    p[0, iso, 2:4] = 20.0
+    p[0, iso, 4] = ((20000 + rng.permutation(n_iso)) / 65536.0).astype(np.float32)
+    c = np.arange(56)
+    base = np.stack([100.0 + 150.0 * (c % 8), 100.0 + 150.0 * (c // 8), rng.uniform(60, 100, 56),
+                     rng.uniform(60, 100, 56)], axis=1)
+    which = rng.randint(0, 56, n_cl)
+    p[0, cl, :4] = (base[which] + rng.uniform(-3, 3, (n_cl, 4))).astype(np.float32)
+    p[0, cl, 4] = ((20000 + n_iso + rng.permutation(n_cl)) / 65536.0).astype(np.float32)
+    return p
+
+
+BUILDERS = {"make_prediction": make_prediction, "frame_case": frame_case, "threshold_case": threshold_case,
+            "max_nms_case": max_nms_case, "nan_case": lambda: nan_case()[None]}
+
+
+def build_input(builder, args):
+    """The float32 [bs, N, 5+nc] input a golden case names: BUILDERS[builder](**args)."""
+    p = BUILDERS[builder](**args)
+    assert p.dtype == np.float32 and p.ndim == 3 and p.flags["C_CONTIGUOUS"]
     return p

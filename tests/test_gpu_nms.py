@@ -1,5 +1,6 @@
 """GPU tests of the fused detector-output -> detections step (gaussianrpg_amd/perception.py, csrc/nms.hip): the whole
-``det`` array, zero rows included, and ``count`` bit for bit against the numpy restatement (tests/nms_truth.py)."""
+``det`` array, zero rows included, and ``count`` bit for bit against the numpy restatement (tests/nms_truth.py), and
+against what the reference's own functions returned (tests/golden/ref_nms.*, see tests/test_nms_golden.py)."""
 import ctypes
 import os
 
@@ -12,8 +13,7 @@ import nms_truth as nt
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = (1088, 1600, 1066, 1600)        # LetterboxPlan.for_simulator(1066, 1600): gain 1, 11 rows of border above
-RESIZE = (224, 640, 375, 1242)        # LetterboxPlan(375, 1242, 640)
+SIM, RESIZE = nt.SIM, nt.RESIZE
 
 
 @pytest.fixture(scope="module")
@@ -287,3 +287,38 @@ def test_c_abi_directly(dev):
     assert call(nc=0) == -1 and call(N=0) == -1 and call(bs=0) == -1
     assert call(bs=2, N=2 ** 30) == -1 and b"2^31" in lib.grpg_last_error()
     assert call(pred=None) == -1 and call(max_nms=0) == -1
+
+
+# ---- against the reference's own output (tests/golden/ref_nms.*), not through the restatement ----
+
+def _golden_cases():
+    from test_nms_golden import CASES
+    return CASES
+
+
+@pytest.mark.parametrize("case", _golden_cases(), ids=[c["name"] for c in _golden_cases()])
+def test_detections_equal_the_references_own_output(dev, case):
+    """perception.detections against what the reference's non_max_suppression (and, with a frame, its
+    scale_coords(...).round()) returned for the same input: the whole det array -- the golden's rows, then zeros --
+    and count, bit for bit; the prediction comes back unchanged.  Batches also through non_max_suppression's lists."""
+    from gaussianrpg_amd.perception import detections, non_max_suppression
+    from test_nms_golden import case_frame, case_input, golden_rows
+    p, frame, kw = case_input(case), case_frame(case), case["settings"]
+    bs, max_det = p.shape[0], kw.get("max_det", 300)
+    want = np.zeros((bs, max_det, 6), np.float32)
+    for b in range(bs):
+        rows = golden_rows(case, b, mapped=frame is not None)
+        assert len(rows) == case["counts"][b] <= max_det
+        want[b, :len(rows)] = rows
+    t = torch.from_numpy(p.copy()).to(dev)
+    det, count = detections(t, plan=None if frame is None else _plan(frame, dev), **kw)
+    assert tuple(det.shape) == (bs, max_det, 6) and det.is_contiguous()
+    _same(case["name"], det, count, want, np.asarray(case["counts"], np.int32))
+    assert np.array_equal(t.cpu().numpy().view(np.uint32), p.view(np.uint32)), "%s: the prediction changed" % case["name"]
+    if bs > 1:
+        out = non_max_suppression(t, **kw)
+        assert isinstance(out, list) and len(out) == bs
+        for b in range(bs):
+            got, ref = out[b].cpu().numpy(), golden_rows(case, b, mapped=False)
+            assert got.shape == ref.shape and got.dtype == np.float32, (b, got.shape, ref.shape)
+            assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), "%s: list %d differs" % (case["name"], b)
