@@ -196,6 +196,11 @@ def _run(dev, sc, cam, bg, S=0, use_colors=False, use_cov=False, seed=0, miss_fr
     # Gaussians that are culled get exactly zero gradient everywhere
     culled = (radii == 0)
     assert float(means.grad[culled].abs().max() if culled.any() else 0.0) == 0.0
+    # for callers that look closer (tests/test_gpu_list_boundaries.py): everything compared above, under the truth's names
+    n = lambda t: None if t is None or t.grad is None else t.grad.detach().cpu().numpy()   # noqa: E731
+    hip = dict(dL_dmeans3D=n(means), dL_dmeans2D_xy=n(means2D)[:, :2], dL_dopacity=n(opac), dL_dsh=n(shs), dL_dcolors=n(col),
+               dL_dscales=n(scales), dL_drotations=n(rots), dL_dcov3D=n(covd), dL_dsemantic=n(semd))
+    return dict(o=o, ref=ref, truth=tr, exempt=fed, hip=hip)
 
 
 @pytest.mark.parametrize("deg", [0, 1, 3])
@@ -256,23 +261,26 @@ def test_backward_long_lists_partial_tiles(dev):
          miss_frac=STRICT_MISS_FRAC_LONG_LISTS)
 
 
-def _long_list_gradients(dev, backward_twice=False, with_semantic_plane=False):
-    """Gradients of the 10-18 k-entry scene for a fixed loss; no oracle (used to compare schedules).
-    with_semantic_plane: one semantic channel the loss does not touch rides along -- same gradients,
-    but a semantic frame leaves no blend checkpoints, so the backward walks every list as one chain."""
+def _scene_gradients(dev, sc, cam, bg, planes, backward_twice=False, with_semantic_plane=False, colors=None):
+    """Gradients of a scene for a fixed loss sum(colour gc) + 0.1 sum(depth gd) + sum(alpha ga), planes = (gc, gd, ga);
+    no oracle (used to compare schedules).  with_semantic_plane: one semantic channel the loss does not touch rides
+    along -- same gradients, but a semantic frame leaves no blend checkpoints, so the backward walks every list as
+    one chain.  colors: colors_precomp in place of the SHs.  -> per backward [means3D, opacity, shs | colors, scales,
+    rotations, means2D] gradients."""
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
-    sc = hz.toy_scene(40000, seed=21, sh_degree=1, depth=6.0, spread=0.8, scale=0.015)
-    cam = hz.trajectory_camera(0, W=64, H=64, device=dev)
-    g = torch.Generator().manual_seed(5)
-    gc, gd, ga = (torch.randn(c, 64, 64, generator=g).to(dev) for c in (3, 1, 1))
-    rast = GaussianRasterizer(GaussianRasterizationSettings(
-        **hz.settings_kwargs(cam, 1, bg=torch.tensor([0.1, 0.4, 0.2], device=dev))))
+    camd = hz.CameraTensors(cam.image_height, cam.image_width, cam.tanfovx, cam.tanfovy, cam.viewmatrix.to(dev),
+                            cam.projmatrix.to(dev), cam.campos.to(dev))
+    gc, gd, ga = (p.to(dev) for p in planes)
+    rast = GaussianRasterizer(GaussianRasterizationSettings(**hz.settings_kwargs(camd, sc.sh_degree, bg=bg.to(dev))))
     leaves = [t.to(dev).clone().requires_grad_(True)
-              for t in (sc.means3D, sc.opacity, sc.shs, sc.scales, sc.rotations)]
+              for t in (sc.means3D, sc.opacity, sc.shs if colors is None else colors, sc.scales, sc.rotations)]
     means2D = torch.zeros(sc.means3D.shape[0], 3, device=dev, requires_grad=True)
-    sem = torch.rand(sc.means3D.shape[0], 1, generator=g).to(dev) if with_semantic_plane else None
+    sem = (torch.rand(sc.means3D.shape[0], 1, generator=torch.Generator().manual_seed(6)).to(dev)
+           if with_semantic_plane else None)
     color, radii, depth, alpha, _ = rast(means3D=leaves[0], means2D=means2D, opacities=leaves[1],
-                                         shs=leaves[2], scales=leaves[3], rotations=leaves[4], semantics=sem)
+                                         shs=leaves[2] if colors is None else None,
+                                         colors_precomp=None if colors is None else leaves[2],
+                                         scales=leaves[3], rotations=leaves[4], semantics=sem)
     loss = (color * gc).sum() + 0.1 * (depth * gd).sum() + (alpha * ga).sum()
     out = []
     for _ in range(2 if backward_twice else 1):
@@ -282,6 +290,15 @@ def _long_list_gradients(dev, backward_twice=False, with_semantic_plane=False):
         torch.cuda.synchronize()
         out.append([t.grad.detach().cpu().numpy().copy() for t in leaves + [means2D]])
     return out
+
+
+def _long_list_gradients(dev, backward_twice=False, with_semantic_plane=False):
+    """_scene_gradients of the 10-18 k-entry scene."""
+    sc = hz.toy_scene(40000, seed=21, sh_degree=1, depth=6.0, spread=0.8, scale=0.015)
+    g = torch.Generator().manual_seed(5)
+    planes = tuple(torch.randn(c, 64, 64, generator=g) for c in (3, 1, 1))
+    return _scene_gradients(dev, sc, hz.trajectory_camera(0, W=64, H=64), torch.tensor([0.1, 0.4, 0.2]), planes,
+                            backward_twice=backward_twice, with_semantic_plane=with_semantic_plane)
 
 
 def _rel_l2(a, b):
