@@ -12,6 +12,8 @@ Layout:
   trajectory.py   frame-sharded multi-GPU trajectory rendering (one process per GPU, RCCL gather)
   perception.py   the frame as the in-process detector's input: letterbox + CHW + / 255 in one launch;
                   the detector's output as detections: NMS + the mapping back to the frame, no host wait
+  tracks.py       tracklets + optimised corrections + timestamp + ego pose -> every actor's world pose in one
+                  launch, with backward to opt_trans / opt_rots (the step in front of composed.py)
   build.py        in-tree build (hipcc for gfx950, g++ for the binding)
 
 Importing this package does not load native code; ``gaussianrpg_amd.rasterizer`` does, and fails

@@ -74,6 +74,9 @@ HIP_UNITS = {
     # detector output -> detections: every step of the IoU is one IEEE float32 operation as in the numpy restatement
     # (areaA + areaB - inter and iw * ih must not fuse), the division correctly rounded; no atomics
     "nms.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # tracklets -> actor poses and back to opt_trans / opt_rots: every step the single float32 operation of the torch
+    # restatement (tests/tracks_truth.py), divisions and square roots correctly rounded; no atomics
+    "tracks.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "api.hip": [],
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept

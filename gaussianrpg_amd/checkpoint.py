@@ -18,7 +18,7 @@ This module reads both with numpy / torch only (``plyfile`` and ``lib.*`` are no
 ``composed.ModelParams`` -- the raw layout ``ComposedRasterizer`` consumes -- and can apply the
 reference's activations (gaussian_model.py:208-251) to hand the classic flat op a ``harness.Scene``.
 Actor poses are not part of either file (they come from the dataset's tracklets,
-R/lib/models/actor_pose.py); ``scene_from_models`` therefore renders static models as they are and
+R/lib/models/actor_pose.py; ``tracks.TrackedActorPoses`` computes them on the device); ``scene_from_models`` therefore renders static models as they are and
 actors only when the caller provides their poses.
 """
 import math

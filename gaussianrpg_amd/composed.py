@@ -14,6 +14,9 @@ concatenated tensors are never materialised.
     poses  = [None, ActorPose(obj_rot, obj_trans, fourier_time), ...]
     color, radii, depth, alpha = ComposedRasterizer(raster_settings)(models, poses)
 
+``poses`` may also be a ``PoseRows`` -- the frame's poses as two device tensors, what ``tracks.PoseBatch.frame``
+makes of the tracklets in one launch -- wherever the list form is accepted.
+
 Evaluation (``torch.no_grad()`` or nothing requires grad): forward only.  TRAINING (round 3): when
 any raw parameter tensor -- or an actor's ``obj_rot`` / ``obj_trans`` given as a tensor -- requires
 grad, the call goes through an autograd function whose backward (C ABI ``grpg_backward_composed``)
@@ -67,6 +70,38 @@ class ActorPose(NamedTuple):
     obj_rot: Sequence[float]
     obj_trans: Sequence[float]
     fourier_time: float = 0.0
+
+
+class PoseRows(NamedTuple):
+    """The poses of one frame as two tensors instead of a list of ``ActorPose``: ``rot [n,4]`` (w,x,y,z) and ``trans
+    [n,3]``, one row per model, on the device, ego pose applied -- what ``tracks.PoseBatch.frame`` returns.  ``posed``:
+    one flag per model, False = a static model (its row is ignored, like a ``None`` in the list form);
+    ``fourier_time``: one value per model.  Every entry point that takes the list form takes this one; the rows go to
+    the host in one copy and keep their graph in training, with no per-actor Python."""
+    rot: torch.Tensor
+    trans: torch.Tensor
+    posed: Sequence[bool]
+    fourier_time: Sequence[float]
+
+
+def _posed_flags(poses):
+    """one flag per model: the model has a pose (an actor)"""
+    return [bool(f) for f in poses.posed] if isinstance(poses, PoseRows) else [p is not None for p in poses]
+
+
+def _pack_rows(n_models, poses: PoseRows):
+    """pose_t [n,8] of a PoseRows: ONE host copy, made from the two tensors directly"""
+    n = len(poses.posed)
+    if n != n_models or len(poses.fourier_time) != n:
+        raise ValueError("one pose row, posed flag and fourier_time per model")
+    if tuple(poses.rot.shape) != (n, 4) or tuple(poses.trans.shape) != (n, 3):
+        raise ValueError("pose rows must be rot [%d,4] and trans [%d,3], got %s and %s"
+                         % (n, n, tuple(poses.rot.shape), tuple(poses.trans.shape)))
+    flag = torch.tensor([bool(f) for f in poses.posed]).view(n, 1)
+    host = torch.cat([poses.rot.detach().float(), poses.trans.detach().float()], 1).cpu()
+    pose_t = torch.cat([flag.float(), host], 1).masked_fill_(~flag, 0.0)   # a static model's row is zero, like _ZERO_ROW
+    times = [float(t) if f else 0.0 for t, f in zip(poses.fourier_time, poses.posed)]
+    return pose_t, times
 
 
 def idft_weights(time: float, dim: int) -> List[float]:
@@ -123,6 +158,10 @@ def _model_lists(models: Sequence[ModelParams]):
 
 
 def _pack(models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]]):
+    if isinstance(poses, PoseRows):
+        lists, dims = _model_lists(models)
+        pose_t, times = _pack_rows(len(models), poses)
+        return lists, pose_t, _idft_rows(times, dims)
     if len(models) != len(poses):
         raise ValueError("one pose entry (None for a static model) per model")
     lists, dims = _model_lists(models)
@@ -178,11 +217,15 @@ def compose(models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]])
 
 
 def _pose_tensors(poses):
+    if isinstance(poses, PoseRows):
+        return [poses.rot, poses.trans]
     return [t for p in poses if p is not None for t in (p.obj_rot, p.obj_trans) if isinstance(t, torch.Tensor)]
 
 
 def _pose_graph(poses, pose_tensors):
     """poses as [n,4] / [n,3] tensors that keep their graph (rows of static models: constants)"""
+    if isinstance(poses, PoseRows):   # as they are: a static model's row receives a zero gradient
+        return poses.rot.float(), poses.trans.float()
     if not pose_tensors:
         return None, None
     one = torch.tensor([1.0, 0.0, 0.0, 0.0])
@@ -285,7 +328,8 @@ def compose_features(models: Sequence[ModelParams], poses: Sequence[Optional[Act
     dev = models[0].xyz.device
     campos = _NO_SEMANTIC if campos is None else campos.detach().to(device=dev, dtype=torch.float32).reshape(-1)
     normals = bool(normals)
-    rot_tensors = [p.obj_rot for p in poses if p is not None and isinstance(p.obj_rot, torch.Tensor)]
+    rot_tensors = [poses.rot] if isinstance(poses, PoseRows) else \
+        [p.obj_rot for p in poses if p is not None and isinstance(p.obj_rot, torch.Tensor)]
     train = torch.is_grad_enabled() and any(
         t.requires_grad for t in (lists[2] if normals else []) + (rot_tensors if normals else []) + list(sems))
     if not train:
@@ -543,7 +587,7 @@ class ComposedRasterizer(nn.Module):
         rs = self.raster_settings
         sems, S = _semantic_list(models, semantics)
         lists, pose_t, idft_t = _pack(models, poses)
-        flags = [p is not None for p in poses] if object_models is None else [bool(f) for f in object_models]
+        flags = _posed_flags(poses) if object_models is None else [bool(f) for f in object_models]
         # default flags: the class comes from the frame's own segment table on the device
         layer_class = _NO_CLASS if object_models is None else _layer_class(models, flags, models[0].xyz.device)
         flat = [t for per_field in lists[:6] for t in per_field]

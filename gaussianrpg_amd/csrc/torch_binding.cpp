@@ -1427,6 +1427,140 @@ std::tuple<torch::Tensor, torch::Tensor> NmsDetections(const torch::Tensor& pred
   return std::make_tuple(det, count);
 }
 
+// ---- tracklets -> actor poses (gaussianrpg_amd/tracks.py; csrc/tracks.hip) ----
+
+namespace {
+// The static table as tracks.TrackTable keeps it: (stamps f64 [F], input_trans f32 [F,M,3], input_rots f32 [F,M,4],
+// entries i32 [E,2], entry_offsets i32 [A+1], start f64 [A], end f64 [A]) on the device, entry_offsets i32 [A+1] on the
+// host; and one call's per-query arguments.  Everything is checked here, before the device is needed.
+struct TrackCall {
+  grpg_track_table tb;
+  int64_t T;
+  const float* opt_trans = nullptr;
+  const float* opt_rots = nullptr;
+  const double* val = nullptr;
+
+  TrackCall(const char* what, const std::vector<torch::Tensor>& table, const torch::Tensor& timestamps,
+            const torch::Tensor& ego, const c10::optional<torch::Tensor>& opt_trans_t,
+            const c10::optional<torch::Tensor>& opt_rots_t, const c10::optional<torch::Tensor>& val_stamps) {
+    TORCH_CHECK(table.size() == 8, what, ": the table is (stamps, input_trans, input_rots, entries, entry_offsets, "
+                                         "start, end, entry_offsets on the host)");
+    const torch::Tensor &stamps = table[0], &itr = table[1], &irot = table[2], &entries = table[3], &offs = table[4],
+                        &start = table[5], &end = table[6], &offs_host = table[7];
+    auto is = [](const torch::Tensor& t, const torch::ScalarType ty) { return t.scalar_type() == ty && t.is_contiguous(); };
+    TORCH_CHECK(is(stamps, torch::kFloat64) && stamps.dim() == 1 && stamps.size(0) > 0, what,
+                ": stamps must be a contiguous float64 [F] tensor (float32 cannot tell neighbouring stamps apart)");
+    const int64_t F = stamps.size(0);
+    TORCH_CHECK(is(itr, torch::kFloat32) && itr.dim() == 3 && itr.size(0) == F && itr.size(1) > 0 && itr.size(2) == 3,
+                what, ": input_trans must be a contiguous float32 [F,M,3] tensor");
+    const int64_t M = itr.size(1);
+    TORCH_CHECK(is(irot, torch::kFloat32) && irot.dim() == 3 && irot.size(0) == F && irot.size(1) == M &&
+                    irot.size(2) == 4, what, ": input_rots must be a contiguous float32 [F,M,4] tensor");
+    TORCH_CHECK(is(entries, torch::kInt32) && entries.dim() == 2 && entries.size(1) == 2, what,
+                ": entries must be a contiguous int32 [E,2] tensor");
+    TORCH_CHECK(is(offs, torch::kInt32) && offs.dim() == 1 && offs.size(0) >= 2, what,
+                ": entry_offsets must be a contiguous int32 [A+1] tensor");
+    const int64_t A = offs.size(0) - 1;
+    TORCH_CHECK(is(start, torch::kFloat64) && is(end, torch::kFloat64) && start.dim() == 1 && end.dim() == 1 &&
+                    start.size(0) == A && end.size(0) == A, what, ": start / end must be contiguous float64 [A] tensors");
+    TORCH_CHECK(is(offs_host, torch::kInt32) && offs_host.dim() == 1 && offs_host.size(0) == A + 1 &&
+                    offs_host.device().is_cpu(), what, ": the host copy of entry_offsets must be an int32 [A+1] CPU tensor");
+    TORCH_CHECK(F * M <= (int64_t(1) << 27) && A <= 65536, what, ": F * M <= 2^27 and A <= 65536");
+    TORCH_CHECK(is(timestamps, torch::kFloat64) && timestamps.dim() == 1 && timestamps.size(0) > 0, what,
+                ": timestamps must be a contiguous float64 [T] tensor");
+    T = timestamps.size(0);
+    TORCH_CHECK(T * A <= (int64_t(1) << 24), what, ": T * A <= 2^24");
+    TORCH_CHECK(is(ego, torch::kFloat32) && ego.dim() == 3 && ego.size(0) == T && ego.size(1) == 4 && ego.size(2) == 4,
+                what, ": ego must be a contiguous float32 [T,4,4] tensor");
+    const bool has_t = opt_trans_t.has_value() && opt_trans_t->defined();
+    const bool has_r = opt_rots_t.has_value() && opt_rots_t->defined();
+    TORCH_CHECK(has_t == has_r, what, ": opt_trans and opt_rots come together or not at all");
+    const bool has_v = val_stamps.has_value() && val_stamps->defined();
+    TORCH_CHECK(!has_v || has_t, what, ": val_stamps needs opt_trans / opt_rots");
+    if (has_t) {
+      TORCH_CHECK(is(*opt_trans_t, torch::kFloat32) && opt_trans_t->sizes() == itr.sizes(),
+                  what, ": opt_trans must be a contiguous float32 [F,M,3] tensor");
+      TORCH_CHECK(is(*opt_rots_t, torch::kFloat32) && opt_rots_t->dim() == 3 && opt_rots_t->size(0) == F &&
+                      opt_rots_t->size(1) == M && opt_rots_t->size(2) == 1,
+                  what, ": opt_rots must be a contiguous float32 [F,M,1] tensor");
+    }
+    if (has_v)
+      TORCH_CHECK(is(*val_stamps, torch::kFloat64) && val_stamps->dim() == 3 && val_stamps->size(0) == T &&
+                      val_stamps->size(1) == A && val_stamps->size(2) == 2,
+                  what, ": val_stamps must be a contiguous float64 [T,A,2] tensor");
+    TORCH_CHECK(stamps.is_cuda(), what, ": the table must live on a ROCm/HIP device (torch device 'cuda'); this op "
+                                        "has no CPU path");
+    const torch::Device dev = stamps.device();
+    for (const torch::Tensor* t : {&itr, &irot, &entries, &offs, &start, &end, &timestamps, &ego})
+      TORCH_CHECK(t->device() == dev, what, ": every device tensor must be on ", dev);
+    if (has_t) {
+      TORCH_CHECK(opt_trans_t->device() == dev && opt_rots_t->device() == dev, what,
+                  ": opt_trans and opt_rots must be on ", dev);
+      opt_trans = opt_trans_t->data_ptr<float>();
+      opt_rots = opt_rots_t->data_ptr<float>();
+    }
+    if (has_v) {
+      TORCH_CHECK(val_stamps->device() == dev, what, ": val_stamps must be on ", dev);
+      val = val_stamps->data_ptr<double>();
+    }
+    tb.F = (int)F; tb.M = (int)M; tb.A = (int)A; tb.E = (int)entries.size(0);
+    tb.stamps = stamps.data_ptr<double>();
+    tb.input_trans = itr.data_ptr<float>();
+    tb.input_rots = irot.data_ptr<float>();
+    tb.entries = entries.data_ptr<int>();
+    tb.entry_offsets = offs.data_ptr<int>();
+    tb.start = start.data_ptr<double>();
+    tb.end = end.data_ptr<double>();
+    tb.entry_offsets_host = offs_host.data_ptr<int>();
+  }
+};
+}  // namespace
+
+// -> (rot f32 [T,A,4], trans f32 [T,A,3], active u8 [T,A], chosen i32 [T,A,4]); one launch, no host wait
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> TrackPosesForward(
+    const std::vector<torch::Tensor>& table, const torch::Tensor& timestamps, const torch::Tensor& ego,
+    const c10::optional<torch::Tensor>& opt_trans, const c10::optional<torch::Tensor>& opt_rots,
+    const c10::optional<torch::Tensor>& val_stamps) {
+  const char* what = "track_poses_forward";
+  const TrackCall c(what, table, timestamps, ego, opt_trans, opt_rots, val_stamps);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(ego.device());
+  const int64_t A = c.tb.A;
+  torch::Tensor rot = torch::empty({c.T, A, 4}, ego.options());
+  torch::Tensor trans = torch::empty({c.T, A, 3}, ego.options());
+  torch::Tensor active = torch::empty({c.T, A}, ego.options().dtype(torch::kUInt8));
+  torch::Tensor chosen = torch::empty({c.T, A, 4}, ego.options().dtype(torch::kInt32));
+  run("grpg_track_poses_forward", [&](void* stream) {
+    return grpg_track_poses_forward(&c.tb, (int)c.T, timestamps.data_ptr<double>(), ego.data_ptr<float>(), c.opt_trans,
+                                    c.opt_rots, c.val, rot.data_ptr<float>(), trans.data_ptr<float>(),
+                                    active.data_ptr<uint8_t>(), chosen.data_ptr<int>(), stream);
+  });
+  return std::make_tuple(rot, trans, active, chosen);
+}
+
+// -> (g_opt_trans f32 [F,M,3], g_opt_rots f32 [F,M,1]): dense, two views of one allocation; one memset, one launch
+std::tuple<torch::Tensor, torch::Tensor> TrackPosesBackward(
+    const std::vector<torch::Tensor>& table, const torch::Tensor& timestamps, const torch::Tensor& ego,
+    const torch::Tensor& opt_trans, const torch::Tensor& opt_rots, const c10::optional<torch::Tensor>& val_stamps,
+    const torch::Tensor& g_rot, const torch::Tensor& g_trans) {
+  const char* what = "track_poses_backward";
+  const TrackCall c(what, table, timestamps, ego, opt_trans, opt_rots, val_stamps);
+  const int64_t A = c.tb.A, F = c.tb.F, M = c.tb.M;
+  for (const auto& [g, n, name] : {std::make_tuple(&g_rot, int64_t(4), "g_rot"), std::make_tuple(&g_trans, int64_t(3), "g_trans")})
+    TORCH_CHECK(g->scalar_type() == torch::kFloat32 && g->is_contiguous() && g->dim() == 3 && g->size(0) == c.T &&
+                    g->size(1) == A && g->size(2) == n && g->device() == ego.device(),
+                what, ": ", name, " must be a contiguous float32 [T,A,", n, "] tensor on ", ego.device());
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(ego.device());
+  torch::Tensor both = torch::empty({F * M * 4}, ego.options());
+  torch::Tensor g_ot = both.narrow(0, 0, F * M * 3).view({F, M, 3});
+  torch::Tensor g_or = both.narrow(0, F * M * 3, F * M).view({F, M, 1});
+  run("grpg_track_poses_backward", [&](void* stream) {
+    return grpg_track_poses_backward(&c.tb, (int)c.T, timestamps.data_ptr<double>(), ego.data_ptr<float>(), c.opt_trans,
+                                     c.opt_rots, c.val, g_rot.data_ptr<float>(), g_trans.data_ptr<float>(),
+                                     g_ot.data_ptr<float>(), g_or.data_ptr<float>(), stream);
+  });
+  return std::make_tuple(g_ot, g_or);
+}
+
 std::tuple<std::vector<float>, int> StageTiming() {
   std::vector<float> ms(GRPG_NUM_STAGES, 0.f);
   int calls = 0;
@@ -2212,6 +2346,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("max_wh") = 7680.0, pybind11::arg("frame_map") = std::vector<double>(),
         pybind11::arg("det_out") = pybind11::none(), pybind11::arg("count_out") = pybind11::none());
   m.def("nms_workspace_bytes", [](int bs, int N) { return grpg_nms_workspace_bytes(bs, N); });
+  // tracklets -> actor poses (tracks.py): (rot [T,A,4], trans [T,A,3], active [T,A], chosen [T,A,4]) and the dense
+  // (g_opt_trans [F,M,3], g_opt_rots [F,M,1])
+  m.def("track_poses_forward", &TrackPosesForward, pybind11::arg("table"), pybind11::arg("timestamps"),
+        pybind11::arg("ego"), pybind11::arg("opt_trans") = pybind11::none(), pybind11::arg("opt_rots") = pybind11::none(),
+        pybind11::arg("val_stamps") = pybind11::none());
+  m.def("track_poses_backward", &TrackPosesBackward, pybind11::arg("table"), pybind11::arg("timestamps"),
+        pybind11::arg("ego"), pybind11::arg("opt_trans"), pybind11::arg("opt_rots"),
+        pybind11::arg("val_stamps"), pybind11::arg("g_rot"), pybind11::arg("g_trans"));
   m.def("get_backward_timing", &BackwardTiming);   // (blend ms sum, preprocess ms sum, calls)
   m.def("set_stage_timing", [](int mode) { grpg_set_stage_timing(mode); });   // 0 off, 1 all, 2 render only
   m.def("stage_timing", &StageTiming);

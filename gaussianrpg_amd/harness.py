@@ -464,6 +464,131 @@ def simulator_detections(prediction: torch.Tensor, plan, fused: bool = True, *, 
     return out
 
 
+def _quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """quaternion_raw_multiply (general_utils.py:220-238)"""
+    aw, ax, ay, az = torch.unbind(a, -1)
+    bw, bx, by, bz = torch.unbind(b, -1)
+    return torch.stack((aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                        aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw), -1)
+
+
+def _slerp(q0: torch.Tensor, q1: torch.Tensor, step: float) -> torch.Tensor:
+    """quaternion_slerp (general_utils.py:256-276) with roma.utils.unitquat_slerp(shortest_arc=True) written out as
+    DESIGN.md section 21 defines it (roma is not a dependency of this project)."""
+    q0 = torch.nn.functional.normalize(q0, dim=-1)
+    q1 = torch.nn.functional.normalize(q1, dim=-1)
+    s = torch.tensor(step, device=q0.device).float()
+    dot = (q0 * q1).sum(-1)
+    sigma = torch.where(dot < 0, -torch.ones_like(dot), torch.ones_like(dot))
+    c = dot.abs().clamp(max=1.0)
+    small = c > 1.0 - 1e-5
+    om = torch.acos(torch.where(small, torch.zeros_like(c), c))
+    a = torch.where(small, (1 - s) * (1 + (1 - (1 - s) * (1 - s)) * ((1 - c) / 3)), torch.sin((1 - s) * om) / torch.sin(om))
+    b = torch.where(small, s * (1 + (1 - s * s) * ((1 - c) / 3)), torch.sin(s * om) / torch.sin(om))
+    return a * q0 + (b * sigma) * q1
+
+
+def _matrix_to_quat(m: torch.Tensor) -> torch.Tensor:
+    """matrix_to_quaternion (general_utils.py:159-218) of one [3,3] matrix"""
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = torch.unbind(m.reshape(9), -1)
+    x = torch.stack([1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22], -1)
+    q_abs = torch.zeros_like(x)
+    q_abs[x > 0] = torch.sqrt(x[x > 0])
+    cand = torch.stack([torch.stack([q_abs[0] ** 2, m21 - m12, m02 - m20, m10 - m01], -1),
+                        torch.stack([m21 - m12, q_abs[1] ** 2, m10 + m01, m02 + m20], -1),
+                        torch.stack([m02 - m20, m10 + m01, q_abs[2] ** 2, m12 + m21], -1),
+                        torch.stack([m10 - m01, m20 + m02, m21 + m12, q_abs[3] ** 2], -1)], -2)
+    cand = cand / (2.0 * q_abs[..., None].max(torch.tensor(0.1, dtype=q_abs.dtype, device=q_abs.device)))
+    return cand[torch.nn.functional.one_hot(q_abs.argmax(-1), num_classes=4) > 0.5, :].reshape(4)
+
+
+def _actor_pose_unfused(actors, dev_table, a: int, timestamp: float, ego_pose: torch.Tensor, val):
+    """One actor's world pose the reference's way (actor_pose.py:83-179, street_gaussian_model.py:268-274): every
+    lookup brings the track's frame indices to the host, like find_closest_indices."""
+    table = actors.table
+    stamps, input_trans, input_rots, entries, offsets = dev_table[:5]
+    track_idx = entries[int(table.entry_offsets[a]):int(table.entry_offsets[a + 1])].long()
+
+    def closest(t):
+        frame_idx = track_idx[:, 0].cpu()                       # the reference's host wait
+        delta = np.abs(table.stamps[frame_idx.numpy()] - t)
+        i1, i2 = np.argsort(delta)[:2]
+        return track_idx[i1], track_idx[i2]
+
+    def translation(t):
+        ind1, ind2 = closest(t)
+        t1, t2 = table.stamps[ind1[0].cpu()], table.stamps[ind2[0].cpu()]
+        x1, x2 = input_trans[ind1[0], ind1[1]], input_trans[ind2[0], ind2[1]]
+        if actors.opt_track:
+            x1, x2 = x1 + actors.opt_trans[ind1[0], ind1[1]], x2 + actors.opt_trans[ind2[0], ind2[1]]
+        return (x1 * (t2 - t) + x2 * (t - t1)) / (t2 - t1)
+
+    def rotation(t):
+        ind1, ind2 = closest(t)
+        t1, t2 = table.stamps[ind1[0].cpu()], table.stamps[ind2[0].cpu()]
+        r1, r2 = input_rots[ind1[0], ind1[1]], input_rots[ind2[0], ind2[1]]
+        if actors.opt_track:
+            rs = []
+            for r, ind in ((r1, ind1), (r2, ind2)):
+                o = torch.zeros_like(r)
+                o[0] = torch.cos(actors.opt_rots[ind[0], ind[1]])
+                o[3] = torch.sin(actors.opt_rots[ind[0], ind[1]])
+                rs.append(_quat_mul(r.unsqueeze(0), o.unsqueeze(0)).squeeze(0))
+            r1, r2 = rs
+        return _slerp(r1, r2, (t - t1) / (t2 - t1))
+
+    if val is None:
+        rot, trans = rotation(timestamp), translation(timestamp)
+    else:
+        c1, c2 = val
+        rot = _slerp(rotation(c1), rotation(c2), (timestamp - c1) / (c2 - c1))
+        trans = (translation(c1) * (c2 - timestamp) + translation(c2) * (timestamp - c1)) / (c2 - c1)
+    q_e = _matrix_to_quat(ego_pose[:3, :3])
+    return (_quat_mul(q_e.unsqueeze(0), rot.unsqueeze(0)).squeeze(0), ego_pose[:3, :3] @ trans + ego_pose[:3, 3])
+
+
+def parse_camera_poses(actors, timestamp: float, ego_pose: torch.Tensor, num_gaussians, *, num_background: int = 0,
+                       visibility=None, is_val: bool = False, cam=None, fused: bool = True):
+    """The scene-graph part of ``StreetGaussianModel.parse_camera`` (street_gaussian_model.py:239-283) over a
+    ``tracks.TrackedActorPoses``: returns ``(visible, ranges, rot [n,4], trans [n,3])`` -- the indices of the actors
+    with ``start <= timestamp <= end`` (and ``visibility[a]``, when given), ``ranges`` = the reference's
+    ``graph_gaussian_range`` as ``{'background' | actor index: [first, last]}`` for ``num_gaussians[a]`` Gaussians
+    per actor behind ``num_background`` background ones, and the visible actors' world poses, one row each.
+      fused=True   ``actors.poses`` (one launch) and one gather of the visible rows
+      fused=False  the reference's per-actor PyTorch with its host waits, for tools/bench_tracks.py
+    The visible list and the ranges are host arithmetic either way."""
+    table = actors.table
+    A = table.shape[2]
+    visible = [a for a in range(A) if table.start[a] <= timestamp <= table.end[a]
+               and (visibility is None or visibility[a])]
+    ranges, idx = {}, 0
+    if num_background:
+        ranges['background'] = [0, num_background - 1]
+        idx = num_background
+    for a in visible:
+        ranges[a] = [idx, idx + int(num_gaussians[a]) - 1]
+        idx += int(num_gaussians[a])
+    if not visible:
+        return visible, ranges, ego_pose.new_zeros(0, 4), ego_pose.new_zeros(0, 3)
+    if fused:
+        batch = actors.poses(timestamp, ego_pose, is_val=is_val, cam=cam)
+        index = torch.tensor(visible, dtype=torch.long).to(ego_pose.device, non_blocking=True)
+        return visible, ranges, batch.rot[0].index_select(0, index), batch.trans[0].index_select(0, index)
+    from .tracks import closest_camera_timestamps
+    dev_table = table.tensors(ego_pose.device)
+    rots, trans = [], []
+    for a in visible:
+        val = None
+        if actors.opt_track and is_val:
+            c1, c2 = closest_camera_timestamps(actors.camera_timestamps[cam]['train_timestamps'], table.start[a],
+                                               table.end[a], timestamp)
+            val = None if c1 is None else (c1, c2)
+        r, t = _actor_pose_unfused(actors, dev_table, a, timestamp, ego_pose, val)
+        rots.append(r)
+        trans.append(t)
+    return visible, ranges, torch.stack(rots), torch.stack(trans)
+
+
 def train_loss(render_pkg: dict, gt_image: torch.Tensor, lidar_depth: Optional[torch.Tensor] = None,
                sky_mask: Optional[torch.Tensor] = None, lambda_l1: float = 1.0,
                lambda_depth_lidar: float = 0.1, lambda_sky: float = 0.05, *, lambda_dssim: float = 0.0,

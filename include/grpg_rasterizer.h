@@ -785,6 +785,67 @@ GRPG_API int grpg_nms_detections(const float* prediction, int bs, int N, int nc,
                                  float* det, int* count, void* hip_stream);
 
 /*
+ * Tracklets -> actor poses: ActorPose.get_tracking_rotation / get_tracking_translation (lib/models/actor_pose.py:83-179)
+ * and the ego product of StreetGaussianModel.parse_camera (lib/models/street_gaussian_model.py:268-274) for every actor
+ * and every query stamp in ONE launch, and the gradient at the poses carried on to opt_trans / opt_rots in one
+ * asynchronous memset and ONE launch.  No host wait, no atomics, identical bits from identical calls.
+ * tests/tracks_truth.py restates the contract in torch.
+ *
+ * grpg_track_table, built once per scene.  Device arrays: stamps float64 [F] (the tracklet timestamps; float32 cannot
+ * tell neighbouring Waymo stamps apart), input_trans float32 [F,M,3], input_rots float32 [F,M,4] (w,x,y,z), entries
+ * int32 [E,2] (per actor the (frame, column) pairs of argwhere(track_ids == track_id), row-major), entry_offsets int32
+ * [A+1], start / end float64 [A].  entry_offsets_host: the same offsets on the HOST, where the entries check them
+ * (every actor needs two entries; the reference asserts it).
+ *
+ * Per call: timestamps float64 [T] and ego float32 [T,4,4] on the device; opt_trans float32 [F,M,3] and opt_rots
+ * float32 [F,M,1] (both NULL: opt_track is off); val_stamps float64 [T,A,2] or NULL -- where both stamps of
+ * val_stamps[t,a] are finite the pose is evaluated at the two stamps and combined at timestamps[t]
+ * (actor_pose.py:124-136, :166-179), NaN means the plain path; it needs the opt_* pair.  Per (t, a):
+ *   1. the two entries with the smallest |stamps[frame] - t| in float64, ties to the lower list position
+ *      (argsort(delta)[:2]; not a bracketing search: the pair may lie on one side and then extrapolates);
+ *   2. trans = (x1 * w2 + x2 * w1) / d, x_i = input_trans_i (+ opt_trans_i), w2 = float(t2 - t), w1 = float(t - t1),
+ *      d = float(t2 - t1), each difference taken in float64;
+ *   3. r_i = input_rots_i (x) (cos th_i, 0, 0, sin th_i), th_i = opt_rots_i; both normalised (eps 1e-12); slerp at
+ *      s = float((t - t1) / (t2 - t1)): (sin((1 - s) W) q0 + sin(s W) sg q1) / sin W with sg = sign(q0 . q1),
+ *      c = min(|q0 . q1|, 1), W = acos(c); for c > 1 - 1e-5 the coefficients are k (1 + (1 - k^2) (1 - c) / 3) with
+ *      k = 1 - s and s.  This is roma.utils.unitquat_slerp(shortest_arc=True) in real arithmetic; its float32 bits
+ *      are not pinned;
+ *   4. q_e = matrix_to_quaternion(ego[:3,:3]) (general_utils.py:159-218), rot = q_e (x) rot (not normalised),
+ *      trans = ego[:3,:3] trans + ego[:3,3].
+ * Outputs, every element written: rot float32 [T,A,4], trans float32 [T,A,3], active uint8 [T,A]
+ * (start <= t <= end in float64; an inactive row is (1,0,0,0) / (0,0,0)), chosen int32 [T,A,4] (the list positions
+ * steps 1-3 used: two, or four on a validation frame; -1 where unused).
+ *
+ * grpg_track_poses_backward: g_rot [T,A,4], g_trans [T,A,3] -> g_opt_trans [F,M,3], g_opt_rots [F,M,1], DENSE and fully
+ * written (zero wherever no active query touched a cell, like autograd's gradient of the reference's indexing).  The
+ * two are one allocation of 4 F M floats (g_opt_rots == g_opt_trans + 3 F M): one memset.  One wave per actor walks
+ * its queries in order; cells of different actors are disjoint.  No gradient for stamps, ego pose or input tracklets.
+ *
+ * Purely additive exports: GRPG_ABI_VERSION stays 7.  Returns GRPG_OK, GRPG_ERR_NO_DEVICE without a device,
+ * GRPG_ERR_INVALID_ARGUMENT -- before anything is enqueued -- for a NULL or misaligned pointer, F, M < 1 or
+ * F * M > 2^27, A outside [1, 65536], T < 1 or T * A > 2^24, offsets that do not run from 0 to E, an actor with fewer
+ * than two entries, one of the opt_* pair missing, val_stamps without the pair.
+ */
+typedef struct grpg_track_table {
+  int F, M, A, E;
+  const double* stamps;
+  const float* input_trans;
+  const float* input_rots;
+  const int* entries;
+  const int* entry_offsets;
+  const double* start;
+  const double* end;
+  const int* entry_offsets_host;
+} grpg_track_table;
+GRPG_API int grpg_track_poses_forward(const grpg_track_table* table, int T, const double* timestamps, const float* ego,
+                                      const float* opt_trans, const float* opt_rots, const double* val_stamps,
+                                      float* rot, float* trans, unsigned char* active, int* chosen, void* hip_stream);
+GRPG_API int grpg_track_poses_backward(const grpg_track_table* table, int T, const double* timestamps,
+                                       const float* ego, const float* opt_trans, const float* opt_rots,
+                                       const double* val_stamps, const float* g_rot, const float* g_trans,
+                                       float* g_opt_trans, float* g_opt_rots, void* hip_stream);
+
+/*
  * Per-stage device timing, measured with HIP events recorded on the op's own stream (so it sees
  * the real kernel durations whatever stream torch calls "current").  While enabled, every
  * grpg_forward on this thread records GRPG_NUM_STAGES+1 events and returns without waiting;
