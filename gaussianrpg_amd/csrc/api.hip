@@ -293,6 +293,10 @@ std::atomic<int> g_binning_alg{[] {
   return (e && strcmp(e, "sort") == 0) ? GRPG_BINNING_ALG_SORT : GRPG_BINNING_ALG_HIER;
 }()};
 bool binning_is_hier() { return g_binning_alg.load() == GRPG_BINNING_ALG_HIER; }
+bool alpha_rect_enabled() {
+  static const bool on = [] { const char* v = getenv("GRPG_ALPHA_RECT"); return !(v && atoi(v) == 0); }();
+  return on;
+}
 
 int bits_for(uint32_t T) {  // smallest b with (1 << b) >= T, i.e. tile ids fit in b bits
   int b = 0;
@@ -803,6 +807,11 @@ struct Frame {
   // (sort.hip RectPayload); larger grids: the coarse scan gathers them by sorted id instead
   const bool rect_sorted_by_sort = hier && cam.gx <= 255 && cam.gy <= 255;
   uint2* const rects = hier ? (uint2*)(geom + GL.rects) : nullptr;
+  // An evaluation frame (no n_contrib, no checkpoints: nothing a backward or the oracle's lists are compared with)
+  // bins the 3-sigma rectangle cut to the alpha ellipse's box (preprocess.hip binned_rect): the device's instance
+  // total (gh->R) is then BELOW the published num_rendered, which stays the reference's sum -- an upper bound that
+  // still sizes every capacity.  GRPG_ALPHA_RECT=0 (experiments): the reference's rectangle.
+  const bool binned_rects = hier && !training && alpha_rect_enabled();
   // a training forward leaves blend checkpoints of its long tile lists behind the binning blob
   // (common.h CK_*; the backward starts its segments from them)
   const bool with_ckpt = training && q.S == 0;
@@ -812,7 +821,8 @@ struct Frame {
   const LayerArgs* const layers = q.layers;
   unsigned char* const tile_obj = layers ? (unsigned char*)(img + IL.ck_count) : nullptr;
   const uint32_t tile_obj_words = layers ? (T + 3u) / 4u : 0u;
-  const TileClasses frame_classes = layers ? tile_classes_layers(tile_obj, cam.gx) : tile_classes(q.S);
+  const TileClasses frame_classes = layers ? tile_classes_layers(tile_obj, cam.gx)
+                                           : (binned_rects ? tile_classes_binned(q.S) : tile_classes(q.S));
   const LayerMarks marks = {layers ? layers->layer_class : nullptr, tile_obj, cam.gx};
 
   const FrameEpilogue* epi = q.epi;     // the request's, or epi_drained
@@ -953,12 +963,12 @@ struct Frame {
     if (q.segs == nullptr) {
       launch_preprocess(stream, q.P, q.D, q.M, q.means3D, q.scales, q.scale_modifier, q.rotations, q.opacities,
                         q.shs, q.cov3D_precomp, q.colors_precomp, cam, radii_int, rec_w, key_a, tiles, rects,
-                        fat_sort ? ds_table : nullptr, pre_counts, marks);
+                        fat_sort ? ds_table : nullptr, pre_counts, marks, binned_rects);
     } else {
       SegmentDev* seg_dev = (SegmentDev*)(geom + GL.seg_table);
       if (int rc = stage_segments(seg_dev)) return rc;
       launch_preprocess_composed(stream, q.P, q.D, q.M, seg_dev, q.nseg, q.scale_modifier, cam, radii_int, rec_w,
-                                 key_a, tiles, rects, fat_sort ? ds_table : nullptr, pre_counts, marks);
+                                 key_a, tiles, rects, fat_sort ? ds_table : nullptr, pre_counts, marks, binned_rects);
       if (q.S > 0) {   // the frame's feature planes: [P,S] from the models' own arrays (features.hip)
         if (int rc = stage_features(seg_dev)) return rc;
       }
@@ -2044,11 +2054,19 @@ int grpg_debug_export(int P, int R, int width, int height, const char* geom_buff
   HIP_TRY(hipStreamSynchronize(stream));
   if (bh.magic != BIN_MAGIC || bh.Rcap < (uint32_t)R)
     return fail(GRPG_ERR_BAD_BUFFER, "binning buffer does not match this call");
+  // An evaluation frame of the hierarchical binning lists fewer instances than its num_rendered (binned rectangles,
+  // preprocess.hip): the point list holds what the tile scan counted (the geometry header's R), and the entries
+  // behind that were never written -- they must not be decoded as Gaussian ids.
+  BlobHeader gh;
+  HIP_TRY(hipMemcpyAsync(&gh, geom_buffer, sizeof(BlobHeader), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (gh.magic != GEOM_MAGIC) return fail(GRPG_ERR_BAD_BUFFER, "geometry buffer does not match this call");
+  const uint32_t R_listed = bh.hier && gh.R < (uint32_t)R ? gh.R : (uint32_t)R;
   // hierarchical blob: the header's Rc is the coarse capacity it was carved for
   const BinLayout BL = bh.hier ? bin_layout((size_t)bh.Rcap, (size_t)gx * gy, super_tiles(gx, gy), (size_t)bh.Rc)
                                : bin_layout((size_t)bh.Rcap);
   const ImgLayout IL = img_layout((size_t)gx * gy, (size_t)width * height);
-  launch_debug_export(stream, P, (uint32_t)R, width, height, gx, gy,
+  launch_debug_export(stream, P, R_listed, width, height, gx, gy,
                       RecView{(const float4*)(geom_buffer + GL.rec)},
                       (const uint32_t*)(geom_buffer + GL.tiles),
                       (const uint32_t*)(binning_buffer + BL.key_a),

@@ -153,22 +153,66 @@ struct QuarterPre {
   float b, ic, det, ct, xtop;   // conic b, 1/c, determinant, c t, abscissa of the upper extreme
   bool sane, transparent;
 };
-__device__ __forceinline__ QuarterPre quarter_pre(const float a, const float b, const float c,
-                                                  const float opacity) {
-  QuarterPre q;
+// The ellipse itself, shared by quarter_pre and alpha_box: the inflated t, Kahan's det, and the two verdicts
+struct AlphaEllipse {
+  float t, det;
+  bool sane, transparent;
+};
+__device__ __forceinline__ AlphaEllipse alpha_ellipse(const float a, const float b, const float c,
+                                                      const float opacity) {
+  AlphaEllipse e;
   float t = 2.0f * __logf(255.0f * opacity);
   t = t + 1e-4f * fabsf(t) + 2e-3f;
   const float p = b * b;
-  const float det = fmaf(a, c, -p) - fmaf(b, b, -p);
-  q.sane = (a > 0.0f) && (c > 0.0f) && (det > 0.0f) && (fabsf(t) < 3e38f) && (fabsf(det) < 3e38f);
+  e.det = fmaf(a, c, -p) - fmaf(b, b, -p);
+  e.t = t;
+  e.sane = (a > 0.0f) && (c > 0.0f) && (e.det > 0.0f) && (fabsf(t) < 3e38f) && (fabsf(e.det) < 3e38f);
+  // alpha <= opacity, so a splat below 1/255 never passes anywhere
+  e.transparent = opacity < (1.0f / 255.0f) * 0.999f;
+  return e;
+}
+// Bounding box of the ellipse: |ux| <= hx = sqrt(t c / det), |uy| <= hy = sqrt(t a / det), inflated like
+// strip_extent's y-extent -- so a tile column (row) outside it is one whose strip_extent comes out `empty` (whose
+// bands all miss [ylo, yup]): the box drops no tile in which a quarter bit could be set.  Tile column tx holds a
+// pixel of the box iff 16 tx <= px + hx and 16 tx + 15 >= px - hx: [lo, hi) below, rows alike.  keep_all (never
+// drop on doubt): a non-sane conic or a non-finite bound -- the caller keeps its own rectangle; a transparent
+// splat has no tile at all.
+struct AlphaBox {
+  int x0, x1, y0, y1;   // tile columns [x0, x1) and rows [y0, y1), not yet clamped to any grid
+  bool keep_all, transparent;
+};
+__device__ __forceinline__ AlphaBox alpha_box(const float px, const float py, const float a, const float b,
+                                              const float c, const float opacity) {
+  const AlphaEllipse e = alpha_ellipse(a, b, c, opacity);
+  const float s = e.t * __builtin_amdgcn_rcpf(e.det);
+  float hx = __builtin_amdgcn_sqrtf(fmaxf(s * c, 0.0f)), hy = __builtin_amdgcn_sqrtf(fmaxf(s * a, 0.0f));
+  hx += 1e-3f + 1e-5f * fabsf(hx);
+  hy += 1e-3f + 1e-5f * fabsf(hy);
+  const float fx0 = ceilf((px - hx - 15.0f) * 0.0625f), fx1 = floorf((px + hx) * 0.0625f);
+  const float fy0 = ceilf((py - hy - 15.0f) * 0.0625f), fy1 = floorf((py + hy) * 0.0625f);
+  AlphaBox o;
+  // (a NaN fails the comparison; beyond +-2^20 tiles no grid is reached and the int conversion stays exact)
+  const bool finite = fabsf(fx0) < 1048576.0f && fabsf(fx1) < 1048576.0f && fabsf(fy0) < 1048576.0f &&
+                      fabsf(fy1) < 1048576.0f;
+  o.keep_all = !e.sane || !finite;
+  o.transparent = e.transparent;
+  o.x0 = (int)fx0; o.x1 = (int)fx1 + 1;
+  o.y0 = (int)fy0; o.y1 = (int)fy1 + 1;
+  return o;
+}
+__device__ __forceinline__ QuarterPre quarter_pre(const float a, const float b, const float c,
+                                                  const float opacity) {
+  QuarterPre q;
+  const AlphaEllipse e = alpha_ellipse(a, b, c, opacity);
+  const float t = e.t, det = e.det;
+  q.sane = e.sane;
   const float ytop = __builtin_amdgcn_sqrtf(fmaxf(t * a * __builtin_amdgcn_rcpf(det), 0.0f));
   q.xtop = -(b * __builtin_amdgcn_rcpf(a)) * ytop;
   q.ct = c * t;
   q.ic = __builtin_amdgcn_rcpf(c);
   q.b = b;
   q.det = det;
-  // alpha <= opacity, so a splat below 1/255 never passes anywhere
-  q.transparent = opacity < (1.0f / 255.0f) * 0.999f;
+  q.transparent = e.transparent;
   return q;
 }
 // y-extent [ylo, yup] (relative to the centre) of the ellipse over the column strip starting at x0

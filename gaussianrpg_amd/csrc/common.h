@@ -330,6 +330,19 @@ struct TileClasses { uint32_t c0_min, c1_min, heavy_min; TileObjBits obj; uint32
 inline TileClasses tile_classes(int S) {
   return TileClasses{RENDER_PC_MIN, RENDER_C1_MIN, S > 0 ? 1u : RENDER_HEAVY_MIN, TileObjBits{nullptr, 0}, RENDER_PC_MIN};
 }
+// A plain EVALUATION frame of the hierarchical binning lists a splat only in the tiles its alpha ellipse's box reaches
+// (preprocess.hip binned_rect): 0.66-0.68 of the reference's entries on the bench drive, and every entry that left was
+// one the waves skipped by its quarter mask.  A list of n such entries is the work of n / 0.7 of the reference's, so
+// the class boundaries scale with it (11/16): the tiles keep the paths they were tuned on (with the reference's
+// boundaries the render launch came out 1-2 us longer than before the cut, profiles/alpha_rect_ab.txt).
+constexpr uint32_t BINNED_CLASS_NUM = 11, BINNED_CLASS_DEN = 16;
+inline TileClasses tile_classes_binned(int S) {
+  TileClasses c = tile_classes(S);
+  c.c0_min = c.c0_obj_min = RENDER_PC_MIN * BINNED_CLASS_NUM / BINNED_CLASS_DEN;
+  c.c1_min = RENDER_C1_MIN * BINNED_CLASS_NUM / BINNED_CLASS_DEN;
+  if (S == 0) c.heavy_min = RENDER_HEAVY_MIN * BINNED_CLASS_NUM / BINNED_CLASS_DEN;
+  return c;
+}
 // a LAYERED frame: the plain frame's classes (wave pairs for the longest tiles, quarter waves, light tiles); a
 // short tile WITH object entries takes the quarter-wave path (three states at four pixels per lane do not fit
 // the register file)
@@ -371,7 +384,9 @@ void launch_preprocess(hipStream_t s, int P, int D, int M, const float* means3D,
                        uint2* rects /* packed tile rectangles (hierarchical binning), or NULL */,
                        uint32_t* ds_table0 /* pass-0 counts of the fat depth sort, or NULL */,
                        uint4* pre_counts /* [ceil(P/256)] per-workgroup (instances, coarse pairs, min key, max key), or NULL */,
-                       LayerMarks lm = LayerMarks{nullptr, nullptr, 0} /* layered frame: object-tile bits */);
+                       LayerMarks lm = LayerMarks{nullptr, nullptr, 0} /* layered frame: object-tile bits */,
+                       bool binned = false /* a frame without backward state: rects (non-NULL) get the 3-sigma rectangle
+                                              cut to the alpha ellipse's box; Gaussians left without a tile are not sorted */);
 // sums pre_counts -> pinned host words [0] num_rendered, [1] coarse pairs; header words R_pre,
 // Rc_pre, key_base, key_far (sort.hip)
 void launch_publish_counts(hipStream_t s, const uint4* pre_counts, uint32_t nblocks,
@@ -380,7 +395,8 @@ void launch_publish_counts(hipStream_t s, const uint4* pre_counts, uint32_t nblo
 void launch_preprocess_composed(hipStream_t s, int P, int D, int M, const SegmentDev* segs, int nseg,
                                 float scale_modifier, const CameraArgs& cam, int* radii, float4* rec,
                                 uint32_t* depth_key, uint32_t* tiles, uint2* rects,
-                                uint32_t* ds_table0, uint4* pre_counts, LayerMarks lm = LayerMarks{nullptr, nullptr, 0});
+                                uint32_t* ds_table0, uint4* pre_counts, LayerMarks lm = LayerMarks{nullptr, nullptr, 0},
+                                bool binned = false /* as launch_preprocess */);
 void launch_compose(hipStream_t s, int P, int M, const SegmentDev* segs, int nseg, float* means3D,
                     float* scales, float* rotations, float* opacities, float* shs);
 void launch_visible_filter(hipStream_t s, int P, const float* means3D, const float* scales,

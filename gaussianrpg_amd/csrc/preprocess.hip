@@ -25,12 +25,16 @@
 //    (preprocess_kernel<HOT>, preprocess_composed_kernel<M4, HOT>): <= 64 VGPRs without scratch,
 //    __launch_bounds__(256, 8) = the eight workgroups per CU its 18.5 KB of LDS were sized for.
 //    build/obj/preprocess.remarks keeps hipcc's report; tests/test_preprocess_resources.py reads it.
+// An evaluation frame takes the *_binned_kernel twins (same bodies, BINNED = true): what goes into the binning is the
+// tile rectangle cut to the box of the splat's alpha >= 1/255 ellipse (binned_rect below) -- radii, tiles_touched and
+// num_rendered stay the reference's; HOT at 47 VGPRs, tests/test_preprocess_binned_resources.py.
 #include "common.h"
 
 #pragma clang fp contract(off)
 
 #include "gaussian_math.h"
 #include "compose_math.h"
+#include "blend_math.h"
 
 namespace grpg {
 
@@ -190,22 +194,45 @@ __device__ __forceinline__ void mark_object_tiles_wave(const LayerMarks lm, cons
 // there and every path they exclude is compiled out: the instantiation fits 64 VGPRs without scratch, eight
 // waves per SIMD = the eight workgroups per CU the LDS was sized for.  Every other call takes HOT = false, the
 // kernel for any caller; both run the same expressions in the same order.
-template <bool HOT>
-__global__ void __launch_bounds__(256, HOT ? 8 : 1)
-preprocess_kernel(const int P, const int D, const int M, const float* __restrict__ means3D,
-                  const float* __restrict__ scales, const float scale_modifier,
-                  const float* __restrict__ rotations, const float* __restrict__ opacities,
-                  const float* __restrict__ shs, const float* __restrict__ cov3D_precomp,
-                  const float* __restrict__ colors_precomp, const float* __restrict__ view,
-                  const float* __restrict__ proj, const float* __restrict__ campos, const int W,
-                  const int H, const int gx, const int gy, const float tan_fovx,
-                  const float tan_fovy, const float focal_x, const float focal_y,
-                  int* __restrict__ radii, float4* __restrict__ rec,
-                  uint32_t* __restrict__ depth_key, uint32_t* __restrict__ tiles,
-                  uint2* __restrict__ rects /* packed tile rectangles (hierarchical binning), or NULL */,
-                  uint32_t* __restrict__ ds_table0 /* [chunk][DS_RADIX] pass-0 counts of the fat depth sort, or NULL */,
-                  uint4* __restrict__ pre_counts /* [workgroups] (instances, coarse pairs, min key, max key) */,
-                  const int vec_ok_in /* means3D, scales, shs are 16-byte aligned */, const LayerMarks lm) {
+//
+// BINNED: a frame that leaves no backward state behind (evaluation, hierarchical binning).  radii, tiles and the
+// instance sum stay the reference's -- they are results of the call -- but the rectangle that goes into rects and
+// into the coarse pair count is binned_rect()'s, and a Gaussian it leaves no tile is not handed to the depth sort.
+// The two variants are kernels of their own (preprocess_kernel, preprocess_binned_kernel) over one body.
+#define PP_PARAMS                                                                                                  \
+  const int P, const int D, const int M, const float* __restrict__ means3D, const float* __restrict__ scales,      \
+      const float scale_modifier, const float* __restrict__ rotations, const float* __restrict__ opacities,        \
+      const float* __restrict__ shs, const float* __restrict__ cov3D_precomp,                                      \
+      const float* __restrict__ colors_precomp, const float* __restrict__ view, const float* __restrict__ proj,    \
+      const float* __restrict__ campos, const int W, const int H, const int gx, const int gy,                      \
+      const float tan_fovx, const float tan_fovy, const float focal_x, const float focal_y,                        \
+      int* __restrict__ radii, float4* __restrict__ rec, uint32_t* __restrict__ depth_key,                         \
+      uint32_t* __restrict__ tiles, uint2* __restrict__ rects, uint32_t* __restrict__ ds_table0,                   \
+      uint4* __restrict__ pre_counts, const int vec_ok_in, const LayerMarks lm
+#define PP_ARGS                                                                                                    \
+  P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, cov3D_precomp, colors_precomp, view, proj,  \
+      campos, W, H, gx, gy, tan_fovx, tan_fovy, focal_x, focal_y, radii, rec, depth_key, tiles, rects, ds_table0,  \
+      pre_counts, vec_ok_in, lm
+
+// The rectangle an evaluation frame bins: the reference's 3-sigma rectangle (o.minx .. o.maxy, kept in o) cut down
+// to the tiles the splat's alpha ellipse reaches (blend_math.h alpha_box: a pixel outside it cannot pass
+// alpha >= 1/255, the argument of the fill's quarter masks).  Returns false when no tile is left.
+struct TileRect { int minx, miny, maxx, maxy; };
+__device__ __forceinline__ bool binned_rect(const Projected& o, const float opacity, TileRect& r) {
+  r = TileRect{o.minx, o.miny, o.maxx, o.maxy};
+  const AlphaBox ab = alpha_box(o.px, o.py, o.conic[0], o.conic[1], o.conic[2], opacity);
+  if (!ab.keep_all) {
+    r.minx = max(r.minx, ab.x0); r.maxx = min(r.maxx, ab.x1);
+    r.miny = max(r.miny, ab.y0); r.maxy = min(r.maxy, ab.y1);
+  }
+  return !ab.transparent && r.maxx > r.minx && r.maxy > r.miny;
+}
+
+// rects: packed tile rectangles (hierarchical binning), or NULL; ds_table0: [chunk][DS_RADIX] pass-0 counts of the fat
+// depth sort, or NULL; pre_counts: [workgroups] (instances, coarse pairs, min key, max key); vec_ok_in: means3D,
+// scales, shs are 16-byte aligned
+template <bool HOT, bool BINNED>
+__device__ __forceinline__ void preprocess_body(PP_PARAMS) {
   const bool vec_ok = HOT || vec_ok_in != 0;
   const bool has_scales = HOT || scales != nullptr;
   const bool has_cov = !HOT && cov3D_precomp != nullptr;
@@ -264,7 +291,9 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
   if (idx < P) {
     // degree <= 1 (every shipped config): the 48 B of SH coefficients as three 16-byte loads, issued
     // BEFORE the projection arithmetic so that their latency hides behind it (a culled Gaussian's
-    // coefficients are then loaded for nothing: + 7 % of the kernel's bytes)
+    // coefficients are then loaded for nothing: + 7 % of the kernel's bytes.  Issuing them behind the
+    // near-plane test instead -- three multiply-adds on the mean -- was measured: the launch is latency-bound
+    // and got 3 % LONGER, 60.0 -> 61.7-62.0 us, profiles/alpha_rect_ab.txt)
     const bool sh_fast = HOT || (!has_colors && M == 4 && vec_ok);
     float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0, q2 = q0;
     if (sh_fast) {
@@ -278,11 +307,22 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
     const bool vis = project_and_bound(idx, mx, my, mz, s0, s1, s2, scale_modifier, rotations,
                                        has_cov ? cov3D_precomp : nullptr, view, proj, W, H, gx, gy,
                                        tan_fovx, tan_fovy, focal_x, focal_y, o, q_early, quat);
+    TileRect br = {0, 0, 0, 0};
+    const bool binned = vis && (BINNED ? binned_rect(o, opac, br) : true);
     if (!vis) {
       radii[idx] = 0;
       tiles[idx] = 0;
       depth_key[idx] = CULLED_KEY;
+    } else if (BINNED && !binned) {
+      // visible to the caller (radii, tiles, the instance sum), but no pixel can accept it: it leaves the binning
+      // here -- no depth key, no histogram count, no record (emit_coarse_fused_kernel relies on every sorted entry
+      // owning at least one slot)
+      radii[idx] = o.radius;
+      my_tiles = (uint32_t)(o.maxy - o.miny) * (uint32_t)(o.maxx - o.minx);
+      tiles[idx] = my_tiles;
+      depth_key[idx] = CULLED_KEY;
     } else {
+      if (!BINNED) br = TileRect{o.minx, o.miny, o.maxx, o.maxy};
       float rgb[3];
       uint32_t clamped = 0;
       if (!has_colors) {
@@ -304,15 +344,16 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
       my_tiles = (uint32_t)(o.maxy - o.miny) * (uint32_t)(o.maxx - o.minx);
       tiles[idx] = my_tiles;
       if (HOT || rects) {   // x and y tile ranges, half-open, 16 bits each (hier_binning.hip)
-        const uint2 rc = make_uint2((uint32_t)o.minx | ((uint32_t)o.maxx << 16),
-                                    (uint32_t)o.miny | ((uint32_t)o.maxy << 16));
+        const uint2 rc = make_uint2((uint32_t)br.minx | ((uint32_t)br.maxx << 16),
+                                    (uint32_t)br.miny | ((uint32_t)br.maxy << 16));
         rects[idx] = rc;
         my_st = rect_super_tiles(rc.x, rc.y);
       }
       uint32_t cls_bit = 0u;   // layered frame: the class rides in the record (common.h REC_CLASS_BIT)
-      if (layered && lm.layer_class[idx] != 0) {
-        if (my_tiles <= (uint32_t)MARK_SMALL) mark_object_tiles(lm, o.minx, o.miny, o.maxx, o.maxy);
-        else { mark_big = true; mark_rect = MarkRect{o.minx, o.miny, o.maxx, o.maxy}; }
+      if (layered && lm.layer_class[idx] != 0) {   // (the tiles the binning gives it: the same rectangle)
+        if ((uint32_t)(br.maxy - br.miny) * (uint32_t)(br.maxx - br.minx) <= (uint32_t)MARK_SMALL)
+          mark_object_tiles(lm, br.minx, br.miny, br.maxx, br.maxy);
+        else { mark_big = true; mark_rect = MarkRect{br.minx, br.miny, br.maxx, br.maxy}; }
         cls_bit = REC_CLASS_BIT;
       }
       depth_key[idx] = __float_as_uint(o.depth);
@@ -348,6 +389,16 @@ preprocess_kernel(const int P, const int D, const int M, const float* __restrict
   }
   if (HOT || pre_counts != nullptr) block_count_sums(my_tiles, my_st, my_key, pre_counts);
 }
+template <bool HOT>
+__global__ void __launch_bounds__(256, HOT ? 8 : 1) preprocess_kernel(PP_PARAMS) {
+  preprocess_body<HOT, false>(PP_ARGS);
+}
+template <bool HOT>
+__global__ void __launch_bounds__(256, HOT ? 8 : 1) preprocess_binned_kernel(PP_PARAMS) {
+  preprocess_body<HOT, true>(PP_ARGS);
+}
+#undef PP_PARAMS
+#undef PP_ARGS
 
 __global__ void __launch_bounds__(256)
 visible_filter_kernel(const int P, const float* __restrict__ means3D,
@@ -413,18 +464,20 @@ compose_kernel(const int P, const int M, const SegmentDev* __restrict__ segs, co
 // coefficients per Gaussian (degree <= 1, every shipped config) stay in registers; the generic
 // variant stages up to 16 in a per-lane array.  HOT (with M4): as in preprocess_kernel -- no layer
 // marks, rects / ds_table0 / pre_counts present; 64 VGPRs without scratch, eight waves per SIMD.
-template <bool M4, bool HOT>
-__global__ void __launch_bounds__(256, HOT ? 8 : 1)
-preprocess_composed_kernel(const int P, const int D, const int M,
-                           const SegmentDev* __restrict__ segs, const int nseg,
-                           const float scale_modifier, const float* __restrict__ view,
-                           const float* __restrict__ proj, const float* __restrict__ campos,
-                           const int W, const int H, const int gx, const int gy,
-                           const float tan_fovx, const float tan_fovy, const float focal_x,
-                           const float focal_y, int* __restrict__ radii, float4* __restrict__ rec,
-                           uint32_t* __restrict__ depth_key, uint32_t* __restrict__ tiles,
-                           uint2* __restrict__ rects, uint32_t* __restrict__ ds_table0,
-                           uint4* __restrict__ pre_counts, const LayerMarks lm) {
+// BINNED: as in preprocess_body (kernels preprocess_composed_kernel, preprocess_composed_binned_kernel).
+#define PC_PARAMS                                                                                                 \
+  const int P, const int D, const int M, const SegmentDev* __restrict__ segs, const int nseg,                     \
+      const float scale_modifier, const float* __restrict__ view, const float* __restrict__ proj,                 \
+      const float* __restrict__ campos, const int W, const int H, const int gx, const int gy,                     \
+      const float tan_fovx, const float tan_fovy, const float focal_x, const float focal_y,                       \
+      int* __restrict__ radii, float4* __restrict__ rec, uint32_t* __restrict__ depth_key,                        \
+      uint32_t* __restrict__ tiles, uint2* __restrict__ rects, uint32_t* __restrict__ ds_table0,                  \
+      uint4* __restrict__ pre_counts, const LayerMarks lm
+#define PC_ARGS                                                                                                   \
+  P, D, M, segs, nseg, scale_modifier, view, proj, campos, W, H, gx, gy, tan_fovx, tan_fovy, focal_x, focal_y,    \
+      radii, rec, depth_key, tiles, rects, ds_table0, pre_counts, lm
+template <bool M4, bool HOT, bool BINNED>
+__device__ __forceinline__ void preprocess_composed_body(PC_PARAMS) {
   static_assert(M4 || !HOT, "the specialised instantiation keeps its four SH coefficients in registers");
   const bool layered = !HOT && lm.tile_obj != nullptr;
   __shared__ float4 s_out[256 * REC_STRIDE];
@@ -445,11 +498,19 @@ preprocess_composed_kernel(const int P, const int D, const int M,
     const bool vis = project_and_bound(idx, a.mx, a.my, a.mz, a.s0, a.s1, a.s2, scale_modifier,
                                        nullptr, nullptr, view, proj, W, H, gx, gy, tan_fovx, tan_fovy,
                                        focal_x, focal_y, o, true, a.q);
+    TileRect br = {0, 0, 0, 0};
+    const bool binned = vis && (BINNED ? binned_rect(o, a.opacity, br) : true);
     if (!vis) {
       radii[idx] = 0;
       tiles[idx] = 0;
       depth_key[idx] = CULLED_KEY;
+    } else if (BINNED && !binned) {   // visible to the caller, out of the binning (preprocess_body)
+      radii[idx] = o.radius;
+      my_tiles = (uint32_t)(o.maxy - o.miny) * (uint32_t)(o.maxx - o.minx);
+      tiles[idx] = my_tiles;
+      depth_key[idx] = CULLED_KEY;
     } else {
+      if (!BINNED) br = TileRect{o.minx, o.miny, o.maxx, o.maxy};
       float rgb[3];
       uint32_t clamped = 0;
       const float dx = a.mx - campos[0];
@@ -469,15 +530,16 @@ preprocess_composed_kernel(const int P, const int D, const int M,
       my_tiles = (uint32_t)(o.maxy - o.miny) * (uint32_t)(o.maxx - o.minx);
       tiles[idx] = my_tiles;
       if (HOT || rects) {   // x and y tile ranges, half-open, 16 bits each (hier_binning.hip)
-        const uint2 rc = make_uint2((uint32_t)o.minx | ((uint32_t)o.maxx << 16),
-                                    (uint32_t)o.miny | ((uint32_t)o.maxy << 16));
+        const uint2 rc = make_uint2((uint32_t)br.minx | ((uint32_t)br.maxx << 16),
+                                    (uint32_t)br.miny | ((uint32_t)br.maxy << 16));
         rects[idx] = rc;
         my_st = rect_super_tiles(rc.x, rc.y);
       }
       uint32_t cls_bit = 0u;   // layered frame: the class rides in the record (common.h REC_CLASS_BIT)
-      if (layered && ((uint32_t)(uintptr_t)sg.pad1 & 1u)) {
-        if (my_tiles <= (uint32_t)MARK_SMALL) mark_object_tiles(lm, o.minx, o.miny, o.maxx, o.maxy);
-        else { mark_big = true; mark_rect = MarkRect{o.minx, o.miny, o.maxx, o.maxy}; }
+      if (layered && ((uint32_t)(uintptr_t)sg.pad1 & 1u)) {   // (the tiles the binning gives it: the same rectangle)
+        if ((uint32_t)(br.maxy - br.miny) * (uint32_t)(br.maxx - br.minx) <= (uint32_t)MARK_SMALL)
+          mark_object_tiles(lm, br.minx, br.miny, br.maxx, br.maxy);
+        else { mark_big = true; mark_rect = MarkRect{br.minx, br.miny, br.maxx, br.maxy}; }
         cls_bit = REC_CLASS_BIT;
       }
       depth_key[idx] = __float_as_uint(o.depth);
@@ -513,20 +575,38 @@ preprocess_composed_kernel(const int P, const int D, const int M,
   }
   if (HOT || pre_counts != nullptr) block_count_sums(my_tiles, my_st, my_key, pre_counts);
 }
+template <bool M4, bool HOT>
+__global__ void __launch_bounds__(256, HOT ? 8 : 1) preprocess_composed_kernel(PC_PARAMS) {
+  preprocess_composed_body<M4, HOT, false>(PC_ARGS);
+}
+template <bool M4, bool HOT>
+__global__ void __launch_bounds__(256, HOT ? 8 : 1) preprocess_composed_binned_kernel(PC_PARAMS) {
+  preprocess_composed_body<M4, HOT, true>(PC_ARGS);
+}
+#undef PC_PARAMS
+#undef PC_ARGS
 
 void launch_preprocess_composed(hipStream_t s, int P, int D, int M, const SegmentDev* segs, int nseg,
                                 float scale_modifier, const CameraArgs& cam, int* radii, float4* rec,
                                 uint32_t* depth_key, uint32_t* tiles, uint2* rects,
-                                uint32_t* ds_table0, uint4* pre_counts, LayerMarks lm) {
+                                uint32_t* ds_table0, uint4* pre_counts, LayerMarks lm, bool binned) {
   if (P <= 0) return;
-#define PC_LAUNCH(M4, HOT)                                                                      \
-  preprocess_composed_kernel<M4, HOT><<<(P + 255) / 256, 256, 0, s>>>(                           \
+#define PC_LAUNCH(KERNEL, M4, HOT)                                                              \
+  KERNEL<M4, HOT><<<(P + 255) / 256, 256, 0, s>>>(                                                \
       P, D, M, segs, nseg, scale_modifier, cam.view, cam.proj, cam.campos, cam.W, cam.H, cam.gx,  \
       cam.gy, cam.tan_fovx, cam.tan_fovy, cam.focal_x, cam.focal_y, radii, rec, depth_key, tiles, \
       rects, ds_table0, pre_counts, lm)
   const bool hot = M == 4 && lm.tile_obj == nullptr && rects != nullptr && ds_table0 != nullptr &&
                    pre_counts != nullptr;
-  if (hot) PC_LAUNCH(true, true); else if (M == 4) PC_LAUNCH(true, false); else PC_LAUNCH(false, false);
+  if (binned && rects != nullptr) {   // the binned rectangle lives in rects
+    if (hot) PC_LAUNCH(preprocess_composed_binned_kernel, true, true);
+    else if (M == 4) PC_LAUNCH(preprocess_composed_binned_kernel, true, false);
+    else PC_LAUNCH(preprocess_composed_binned_kernel, false, false);
+  } else {
+    if (hot) PC_LAUNCH(preprocess_composed_kernel, true, true);
+    else if (M == 4) PC_LAUNCH(preprocess_composed_kernel, true, false);
+    else PC_LAUNCH(preprocess_composed_kernel, false, false);
+  }
 #undef PC_LAUNCH
 }
 
@@ -542,19 +622,23 @@ void launch_preprocess(hipStream_t s, int P, int D, int M, const float* means3D,
                        const float* opacities, const float* shs, const float* cov3D_precomp,
                        const float* colors_precomp, const CameraArgs& cam, int* radii,
                        float4* rec, uint32_t* depth_key, uint32_t* tiles, uint2* rects,
-                       uint32_t* ds_table0, uint4* pre_counts, LayerMarks lm) {
+                       uint32_t* ds_table0, uint4* pre_counts, LayerMarks lm, bool binned) {
   if (P <= 0) return;
-  const int vec_ok = ((((uintptr_t)means3D | (uintptr_t)scales | (uintptr_t)shs) & 15) == 0) ? 1 : 0;
+  const int vec_ok =((((uintptr_t)means3D | (uintptr_t)scales | (uintptr_t)shs) & 15) == 0) ? 1 : 0;
   // the default hierarchical frame with the fat depth sort: the specialised instantiation (preprocess_kernel<true>)
   const bool hot = cov3D_precomp == nullptr && colors_precomp == nullptr && scales != nullptr && M == 4 && vec_ok &&
                    lm.tile_obj == nullptr && rects != nullptr && ds_table0 != nullptr && pre_counts != nullptr;
-#define PP_LAUNCH(HOT)                                                                              \
-  preprocess_kernel<HOT><<<(P + 255) / 256, 256, 0, s>>>(                                            \
+#define PP_LAUNCH(KERNEL, HOT)                                                                      \
+  KERNEL<HOT><<<(P + 255) / 256, 256, 0, s>>>(                                                       \
       P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, cov3D_precomp,            \
       colors_precomp, cam.view, cam.proj, cam.campos, cam.W, cam.H, cam.gx, cam.gy, cam.tan_fovx,    \
       cam.tan_fovy, cam.focal_x, cam.focal_y, radii, rec, depth_key, tiles, rects, ds_table0,        \
       pre_counts, vec_ok, lm)
-  if (hot) PP_LAUNCH(true); else PP_LAUNCH(false);
+  if (binned && rects != nullptr) {   // the binned rectangle lives in rects
+    if (hot) PP_LAUNCH(preprocess_binned_kernel, true); else PP_LAUNCH(preprocess_binned_kernel, false);
+  } else {
+    if (hot) PP_LAUNCH(preprocess_kernel, true); else PP_LAUNCH(preprocess_kernel, false);
+  }
 #undef PP_LAUNCH
 }
 

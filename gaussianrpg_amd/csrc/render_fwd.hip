@@ -2069,7 +2069,8 @@ void launch_render_forward(hipStream_t s, const uint2* ranges, const uint32_t* p
   if (ntiles <= 0) return;
   const CkptArgs ck = (aux && ckp) ? *ckp : CkptArgs{nullptr, nullptr, nullptr, nullptr, 0u, 0u};
   // work[0..3] were zeroed by frame_init_kernel (same stream, earlier in the frame)
-  const uint32_t pc_slots = render_pc_slots(R);
+  // (== render_pc_slots(R) for the classes of a training frame, whose backward derives the same number)
+  const uint32_t pc_slots = 2u * (uint32_t)((size_t)R / cls.c0_min + 1);
   // classified: the hierarchical binning's tile scan has already built the work lists
   if (!classified)
     classify_tiles_kernel<<<(ntiles + 255) / 256, 256, 0, s>>>((uint32_t)ntiles, ranges, cls, work);
