@@ -72,7 +72,8 @@ HIP_UNITS = {
     # table arithmetic numpy's (no FMA contraction); q / 255 is a correctly rounded division, not a reciprocal
     "letterbox.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # detector output -> detections: every step of the IoU is one IEEE float32 operation as in the numpy restatement
-    # (areaA + areaB - inter and iw * ih must not fuse), the division correctly rounded; no atomics
+    # (areaA + areaB - inter and iw * ih must not fuse), the division correctly rounded; no atomics.  The detector
+    # head's decode lives here too: its sigmoid divides, and xy / wh are one rounding per step
     "nms.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # tracklets -> actor poses and back to opt_trans / opt_rots: every step the single float32 operation of the torch
     # restatement (tests/tracks_truth.py), divisions and square roots correctly rounded; no atomics

@@ -25,6 +25,9 @@
 //     sentinel, at max_nms or at max_det keeps (a box kept later could only suppress boxes that fall beyond max_det
 //     as well).  The same workgroup zero-fills the rows from count on and writes the count: every element of det and
 //     count is stored on every call.
+// The walk reads a candidate's cx, cy, w, h from `pred` at NmsWalkArgs.stride floats per row: the prediction itself
+// here (stride 5 + nc), or the [bs, N, 4] box array that detect_candidates_kernel fills from the detector's conv
+// outputs (stride 4; second half of this file), in which case step 1 is that kernel and no prediction exists.
 #include <cmath>
 
 #include "abi_util.h"
@@ -43,7 +46,7 @@ constexpr int NMS_STAGE = NMS_WALK_THREADS;              // candidates staged pe
 
 struct NmsWalkArgs {
   int N;               // rows per image
-  int stride;          // 5 + nc floats per row
+  int stride;          // floats per row of the walk's box source: 5 + nc (the prediction) or 4 (the box array)
   uint32_t image_keys; // elements between two images' key / order arrays (N rounded up to 64)
   uint32_t limit;      // min(N, max_nms)
   int max_det;
@@ -222,6 +225,172 @@ nms_walk_kernel(const float* __restrict__ pred, const uint32_t* __restrict__ sor
   if (threadIdx.x == 0) count[image] = nkept;
 }
 
+// ---- detector head -> detections: the inference branch of Detect.forward (models/yolo.py:48-70) without pred ----
+//
+// The 1x1 convs leave nl tensors [bs, na * (5 + nc), ny, nx], channel-major: plane c of anchor a holds column c of the
+// ny * nx rows of that anchor, and row ((a * ny + y) * nx + x) of the level is cell y * nx + x of those planes.  64
+// neighbouring rows are 64 neighbouring cells, so one column of them is one coalesced 256-byte line (a wave that
+// straddles two anchors, two levels or two images reads two shorter lines).
+//  * detect_decode_kernel     the whole [bs, N, 5 + nc] tensor: a workgroup takes 64 rows, reads their columns plane by
+//    plane (one line per wave and column), decodes, turns the tile in LDS and stores the rows' bytes in address order.
+//  * detect_candidates_kernel one lane per row in row order reads only the row's objectness logit; a wave in which no
+//    lane has sigmoid(obj) > conf_thres branches past the rest (the branch on the wave's mask is the ballot).  The
+//    lanes that pass walk the nc class planes together -- each step one line across their cells -- and each keeps its
+//    own first maximum of sigmoid(obj) * sigmoid(cls_j) and a NaN flag: no cross-lane reduction in this orientation.
+//    A row that stays writes key and class as
+//    nms_candidates_kernel does, and its decoded cx, cy, w, h into a [bs, N, 4] box array that nms_walk_kernel reads
+//    with a row stride of 4; the rows of that array that are not candidates are never written and never read.
+// detect_value() is the arithmetic of both, so detections_from_heads(h) and detections(decode_heads(h)) give the same
+// bits: sigmoid = 1 / (1 + exp(-v)) with the correctly rounded divide, then every step one float32 operation in the
+// reference's order (-ffp-contract=off): xy = ((s * 2 - 0.5) + grid) * stride, wh = ((s * 2) * (s * 2)) * anchor.
+constexpr int DET_MAX_LEVELS = GRPG_DETECT_MAX_LEVELS;
+constexpr int DET_MAX_ANCHORS = GRPG_DETECT_MAX_ANCHORS;   // nl * na
+constexpr int DET_THREADS = 256;
+constexpr int DET_TILE_ROWS = WAVE;
+constexpr int DET_TILE_COLS = 128;                         // columns decoded per round: 33 KB of LDS
+constexpr int DET_BATCH = 8;                               // loads a lane issues before it waits for the first
+
+struct DetectLevel {
+  const float* head;   // [bs, na * (5 + nc), ny, nx]
+  uint32_t row0;       // the level's first row in an image
+  uint32_t cells;      // ny * nx
+  uint32_t nx;
+  float stride;
+};
+
+struct DetectArgs {
+  DetectLevel level[DET_MAX_LEVELS];
+  float anchor[DET_MAX_ANCHORS][2];   // [l * na + a]: width, height in pixels (Detect.anchor_grid)
+  int nl, na, nc;
+  uint32_t N, rows;                   // rows per image; bs * N
+};
+
+// Where a row lives: channel 0 of its anchor at its cell, the distance between two channels, and the row's constants.
+struct DetectRow {
+  const float* base;
+  size_t plane;
+  float gx, gy, stride, aw, ah;
+  uint32_t image, r;   // r: the row inside its image
+};
+
+__device__ __forceinline__ DetectRow detect_locate(const DetectArgs& g, const uint32_t row) {
+  DetectRow o;
+  o.image = row / g.N;
+  o.r = row - o.image * g.N;
+  // constant indices only: the levels stay in scalar registers and the lane selects
+  const float* head = g.level[0].head;
+  uint32_t row0 = 0, cells = g.level[0].cells, nx = g.level[0].nx;
+  float stride = g.level[0].stride;
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < DET_MAX_LEVELS; i++)
+    if (i < g.nl && o.r >= g.level[i].row0) {
+      head = g.level[i].head; row0 = g.level[i].row0; cells = g.level[i].cells; nx = g.level[i].nx;
+      stride = g.level[i].stride; l = i;
+    }
+  const uint32_t in_level = o.r - row0;
+  const uint32_t a = in_level / cells, cell = in_level - a * cells;
+  const uint32_t y = cell / nx, x = cell - y * nx;
+  const int la = l * g.na + (int)a;
+  float aw = g.anchor[0][0], ah = g.anchor[0][1];
+#pragma unroll
+  for (int i = 1; i < DET_MAX_ANCHORS; i++)
+    if (i == la) { aw = g.anchor[i][0]; ah = g.anchor[i][1]; }
+  o.plane = cells;
+  o.base = head + ((size_t)o.image * g.na + a) * (size_t)(g.nc + 5) * cells + cell;
+  o.gx = (float)x; o.gy = (float)y; o.stride = stride; o.aw = aw; o.ah = ah;
+  return o;
+}
+
+__device__ __forceinline__ float detect_sigmoid(const float v) { return 1.f / (1.f + expf(-v)); }
+
+// column `col` of a row from its logit v
+__device__ __forceinline__ float detect_value(const int col, const float v, const DetectRow& w) {
+  const float s = detect_sigmoid(v);
+  if (col >= 4) return s;
+  const float t = s * 2.f;
+  if (col < 2) return ((t - 0.5f) + (col == 0 ? w.gx : w.gy)) * w.stride;
+  return (t * t) * (col == 2 ? w.aw : w.ah);
+}
+
+__global__ void __launch_bounds__(DET_THREADS)
+detect_decode_kernel(const DetectArgs g, float* __restrict__ pred) {
+  __shared__ float tile[DET_TILE_ROWS][DET_TILE_COLS + 1];
+  const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+  const uint32_t tile_row0 = blockIdx.x * DET_TILE_ROWS;               // rows = bs * N < 2^31
+  const uint32_t nrows = min((uint32_t)DET_TILE_ROWS, g.rows - tile_row0);
+  const DetectRow w = detect_locate(g, min(tile_row0 + lane, g.rows - 1u));   // a lane past the end reads the last row
+  const int no = g.nc + 5;
+  for (int c0 = 0; c0 < no; c0 += DET_TILE_COLS) {
+    const int ncols = min(DET_TILE_COLS, no - c0);
+    // the column is the wave's: no divergence.  DET_BATCH lines are in flight before the first is decoded
+    for (int j0 = (int)wave; j0 < ncols; j0 += DET_BATCH * (DET_THREADS / WAVE)) {
+      float v[DET_BATCH];
+#pragma unroll
+      for (int k = 0; k < DET_BATCH; k++) {
+        const int j = j0 + k * (DET_THREADS / WAVE);
+        v[k] = j < ncols ? w.base[(size_t)(c0 + j) * w.plane] : 0.f;
+      }
+#pragma unroll
+      for (int k = 0; k < DET_BATCH; k++) {
+        const int j = j0 + k * (DET_THREADS / WAVE);
+        if (j < ncols) tile[lane][j] = detect_value(c0 + j, v[k], w);
+      }
+    }
+    __syncthreads();
+    // with ncols == no (5 + nc <= 128) the tile's rows are one run of bytes in pred
+    const uint32_t n = nrows * (uint32_t)ncols;
+    for (uint32_t e = threadIdx.x; e < n; e += DET_THREADS) {
+      const uint32_t r = e / (uint32_t)ncols, j = e - r * (uint32_t)ncols;
+      pred[(size_t)(tile_row0 + r) * no + c0 + j] = tile[r][j];
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(DET_THREADS)
+detect_candidates_kernel(const DetectArgs g, const uint32_t image_keys, const float conf_thres,
+                         const unsigned char* __restrict__ allow, uint32_t* __restrict__ keys,
+                         uint32_t* __restrict__ cls_out, float4* __restrict__ boxes) {
+  const uint32_t row = blockIdx.x * DET_THREADS + threadIdx.x;
+  const bool in = row < g.rows;
+  const DetectRow w = detect_locate(g, in ? row : g.rows - 1u);
+  const float obj = detect_value(4, w.base[4 * w.plane], w);
+  uint32_t key = NMS_SENTINEL, cls = 0;
+  if (in && obj > conf_thres) {                                        // NaN > x is false
+    const float* __restrict__ scores = w.base + 5 * w.plane;
+    float best = -INFINITY;
+    int best_j = 0;
+    bool nan = false;
+    // a class plane is one memory latency away: DET_BATCH lines are in flight before the first is used
+    for (int j0 = 0; j0 < g.nc; j0 += DET_BATCH) {
+      float v[DET_BATCH];
+#pragma unroll
+      for (int k = 0; k < DET_BATCH; k++) v[k] = j0 + k < g.nc ? scores[(size_t)(j0 + k) * w.plane] : 0.f;
+#pragma unroll
+      for (int k = 0; k < DET_BATCH; k++) {
+        const float c = obj * detect_value(5, v[k], w);
+        if (j0 + k < g.nc) {
+          nan |= c != c;
+          if (c > best) { best = c; best_j = j0 + k; }                 // ascending j: the first maximum stays
+        }
+      }
+    }
+    if (!nan && best > conf_thres && (!allow || allow[best_j] != 0)) {
+      key = ~__float_as_uint(best);
+      cls = (uint32_t)best_j;
+      boxes[(size_t)w.image * g.N + w.r] =
+          make_float4(detect_value(0, w.base[0], w), detect_value(1, w.base[w.plane], w),
+                      detect_value(2, w.base[2 * w.plane], w), detect_value(3, w.base[3 * w.plane], w));
+    }
+  }
+  if (in) {
+    const size_t at = (size_t)w.image * image_keys + w.r;
+    keys[at] = key;
+    cls_out[at] = cls;
+  }
+}
+
 // Layout of the workspace; every array starts on a 256-byte boundary, and so does every image's part of one.
 struct NmsLayout {
   size_t image_keys;   // elements per image
@@ -245,6 +414,106 @@ bool nms_layout(const int bs, const int N, NmsLayout& L) {
   L.totals = take(4 * RS_MAX_RADIX * 4);
   L.total = o;
   return true;
+}
+
+// What grpg_nms_detections and grpg_detect_detections check alike, and the walk's arguments; `stride` is the walk's
+// row stride in floats.  Returns GRPG_OK or the failure already filed.
+int nms_prepare(const std::string& pre, const int bs, const int N, const int stride, const float conf_thres,
+                const float iou_thres, const int agnostic, const int max_det, const int max_nms, const float max_wh,
+                const double* frame_map, const void* workspace, const size_t workspace_bytes, const size_t need,
+                const char* need_name, const uintptr_t words, const char* words_msg, const NmsLayout& L,
+                NmsWalkArgs& a) {
+  if (!(conf_thres >= 0.f && conf_thres <= 1.f) || !(iou_thres >= 0.f && iou_thres <= 1.f))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "conf_thres and iou_thres must lie in [0, 1]");
+  if (max_det < 1 || max_det > NMS_MAX_DET) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "max_det must lie in [1, 1024]");
+  if (max_nms < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "max_nms must be positive");
+  if (!(max_wh >= 0.f)) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "max_wh must not be negative");
+  if (workspace_bytes < need) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "workspace smaller than " + need_name);
+  if ((uintptr_t)workspace & 255) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "workspace must be 256-byte aligned");
+  if (words & 3) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + words_msg);   // the OR of the float / int pointers
+  a.N = N;
+  a.stride = stride;
+  a.image_keys = (uint32_t)L.image_keys;
+  a.limit = (uint32_t)(max_nms < N ? max_nms : N);
+  a.max_det = max_det;
+  a.agnostic = agnostic != 0;
+  a.iou_thres = iou_thres;
+  a.max_wh = max_wh;
+  a.map = frame_map != nullptr;
+  a.gain = 1.f; a.pad_x = a.pad_y = 0.f; a.frame_w = a.frame_h = 0.f;
+  if (frame_map) {
+    const double h = frame_map[0], w = frame_map[1], H = frame_map[2], W = frame_map[3];
+    if (!(h > 0 && w > 0 && H > 0 && W > 0)) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "frame_map sizes must be positive");
+    const double gh = h / H, gw = w / W;
+    a.gain = (float)(gh < gw ? gh : gw);      // scale_coords: gain = min(h / H, w / W), in double, then float32
+    a.pad_x = (float)frame_map[4];
+    a.pad_y = (float)frame_map[5];
+    a.frame_w = (float)W;
+    a.frame_h = (float)H;
+  }
+  return GRPG_OK;
+}
+
+// Steps 2 and 3 on the keys and classes a candidate pass left in key_a / cls: `boxes` is what the walk reads a
+// candidate's cx, cy, w, h from, a.stride floats apart.
+void nms_sort_and_walk(hipStream_t st, const int bs, const NmsLayout& L, char* ws, const float* boxes,
+                       const NmsWalkArgs& a, float* det, int* count) {
+  uint32_t* key_a = (uint32_t*)(ws + L.key_a);
+  uint32_t* key_b = (uint32_t*)(ws + L.key_b);
+  uint32_t* val_a = (uint32_t*)(ws + L.val_a);
+  uint32_t* val_b = (uint32_t*)(ws + L.val_b);
+  uint32_t* table = (uint32_t*)(ws + L.table);
+  uint32_t* totals = (uint32_t*)(ws + L.totals);
+  bool in_b = false;
+  for (int b = 0; b < bs; b++) {   // the same number of passes for every image: the result lands in the same pair
+    const size_t at = (size_t)b * L.image_keys;
+    in_b = radix_sort_pairs(st, (uint32_t)a.N, nullptr, key_a + at, val_a + at, key_b + at, val_b + at, true, 0, 32,
+                            table, totals, (uint32_t)L.nchunks, false);
+  }
+  nms_walk_kernel<<<bs, NMS_WALK_THREADS, 0, st>>>(boxes, in_b ? key_b : key_a, in_b ? val_b : val_a,
+                                               (const uint32_t*)(ws + L.cls), a, det, count);
+}
+
+// The geometry and the heads of a call -> the kernels' arguments and N.  Everything is checked on the host.
+int detect_prepare(const std::string& pre, const float* const* heads, const grpg_detect_geometry* geom, const int bs,
+                   DetectArgs& g, int& N) {
+  if (!heads || !geom) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "NULL heads / geometry");
+  if (geom->nl < 1 || geom->nl > DET_MAX_LEVELS || geom->na < 1 || geom->nl * (long long)geom->na > DET_MAX_ANCHORS)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "the geometry needs 1 <= nl <= 4, na >= 1 and nl * na <= 16");
+  if (geom->nc < 1 || bs < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "bs and nc must be positive");
+  // the kernels form 5 + nc and a head's na * (5 + nc) channels in int
+  if ((long long)geom->na * (5ll + geom->nc) >= (1ll << 31))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "na * (5 + nc) must be below 2^31");
+  long long rows = 0;
+  g = DetectArgs{};
+  for (int l = 0; l < geom->nl; l++) {
+    if (!heads[l] || ((uintptr_t)heads[l] & 3))
+      return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "every head must be a 4-byte aligned device pointer");
+    if (geom->ny[l] < 1 || geom->nx[l] < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "ny and nx must be positive");
+    if (!(geom->stride[l] > 0.f) || !std::isfinite(geom->stride[l]))
+      return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "strides must be positive and finite");
+    const long long cells = (long long)geom->ny[l] * geom->nx[l];
+    if (cells >= (1ll << 31) || rows + cells * geom->na >= (1ll << 31))
+      return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "bs * N must be below 2^31");
+    g.level[l].head = heads[l];
+    g.level[l].row0 = (uint32_t)rows;
+    g.level[l].cells = (uint32_t)cells;
+    g.level[l].nx = (uint32_t)geom->nx[l];
+    g.level[l].stride = geom->stride[l];
+    rows += cells * geom->na;
+    for (int k = 0; k < geom->na; k++)
+      for (int c = 0; c < 2; c++) {
+        const float v = geom->anchor_grid[l * geom->na + k][c];
+        if (!std::isfinite(v)) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "anchor_grid must be finite");
+        g.anchor[l * geom->na + k][c] = v;
+      }
+  }
+  if (rows * bs >= (1ll << 31)) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "bs * N must be below 2^31");
+  g.nl = geom->nl; g.na = geom->na; g.nc = geom->nc;
+  g.N = (uint32_t)rows;
+  g.rows = (uint32_t)(rows * bs);
+  N = (int)rows;
+  return GRPG_OK;
 }
 
 }  // namespace
@@ -272,59 +541,66 @@ int grpg_nms_detections(const float* prediction, int bs, int N, int nc, float co
   if (!nms_layout(bs, N, L)) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "bs * N must be below 2^31");
   if (!prediction || !workspace || !det || !count)
     return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "NULL prediction / workspace / det / count");
-  if (!(conf_thres >= 0.f && conf_thres <= 1.f) || !(iou_thres >= 0.f && iou_thres <= 1.f))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "conf_thres and iou_thres must lie in [0, 1]");
-  if (max_det < 1 || max_det > NMS_MAX_DET) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "max_det must lie in [1, 1024]");
-  if (max_nms < 1) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "max_nms must be positive");
-  if (!(max_wh >= 0.f)) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "max_wh must not be negative");
-  if (workspace_bytes < L.total) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "workspace smaller than grpg_nms_workspace_bytes");
-  if ((uintptr_t)workspace & 255) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "workspace must be 256-byte aligned");
-  if (((uintptr_t)prediction | (uintptr_t)det | (uintptr_t)count) & 3)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "prediction, det and count must be 4-byte aligned");
-
   NmsWalkArgs a;
-  a.N = N;
-  a.stride = 5 + nc;
-  a.image_keys = (uint32_t)L.image_keys;
-  a.limit = (uint32_t)(max_nms < N ? max_nms : N);
-  a.max_det = max_det;
-  a.agnostic = agnostic != 0;
-  a.iou_thres = iou_thres;
-  a.max_wh = max_wh;
-  a.map = frame_map != nullptr;
-  a.gain = 1.f; a.pad_x = a.pad_y = 0.f; a.frame_w = a.frame_h = 0.f;
-  if (frame_map) {
-    const double h = frame_map[0], w = frame_map[1], H = frame_map[2], W = frame_map[3];
-    if (!(h > 0 && w > 0 && H > 0 && W > 0)) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "frame_map sizes must be positive");
-    const double gh = h / H, gw = w / W;
-    a.gain = (float)(gh < gw ? gh : gw);      // scale_coords: gain = min(h / H, w / W), in double, then float32
-    a.pad_x = (float)frame_map[4];
-    a.pad_y = (float)frame_map[5];
-    a.frame_w = (float)W;
-    a.frame_h = (float)H;
-  }
+  if (int rc = nms_prepare(pre, bs, N, 5 + nc, conf_thres, iou_thres, agnostic, max_det, max_nms, max_wh, frame_map,
+                           workspace, workspace_bytes, L.total, "grpg_nms_workspace_bytes",
+                           (uintptr_t)prediction | (uintptr_t)det | (uintptr_t)count,
+                           "prediction, det and count must be 4-byte aligned", L, a))
+    return rc;
 
   char* ws = (char*)workspace;
-  uint32_t* key_a = (uint32_t*)(ws + L.key_a);
-  uint32_t* key_b = (uint32_t*)(ws + L.key_b);
-  uint32_t* val_a = (uint32_t*)(ws + L.val_a);
-  uint32_t* val_b = (uint32_t*)(ws + L.val_b);
-  uint32_t* cls = (uint32_t*)(ws + L.cls);
-  uint32_t* table = (uint32_t*)(ws + L.table);
-  uint32_t* totals = (uint32_t*)(ws + L.totals);
   hipStream_t st = (hipStream_t)hip_stream;
-
   const uint32_t rows = (uint32_t)((size_t)bs * N);
   nms_candidates_kernel<<<(rows + NMS_THREADS - 1) / NMS_THREADS, NMS_THREADS, 0, st>>>(
-      prediction, rows, (uint32_t)N, a.image_keys, nc, conf_thres, class_allow, key_a, cls);
-  bool in_b = false;
-  for (int b = 0; b < bs; b++) {   // the same number of passes for every image: the result lands in the same pair
-    const size_t at = (size_t)b * L.image_keys;
-    in_b = radix_sort_pairs(st, (uint32_t)N, nullptr, key_a + at, val_a + at, key_b + at, val_b + at, true, 0, 32,
-                            table, totals, (uint32_t)L.nchunks, false);
-  }
-  nms_walk_kernel<<<bs, NMS_WALK_THREADS, 0, st>>>(prediction, in_b ? key_b : key_a, in_b ? val_b : val_a, cls, a, det,
-                                               count);
+      prediction, rows, (uint32_t)N, a.image_keys, nc, conf_thres, class_allow, (uint32_t*)(ws + L.key_a),
+      (uint32_t*)(ws + L.cls));
+  nms_sort_and_walk(st, bs, L, ws, prediction, a, det, count);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+int grpg_detect_decode(const float* const* heads, const grpg_detect_geometry* geom, int bs, float* pred,
+                       void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  const std::string pre = "detect_decode: ";
+  DetectArgs g;
+  int N;
+  if (int rc = detect_prepare(pre, heads, geom, bs, g, N)) return rc;
+  if (!pred || ((uintptr_t)pred & 3)) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "pred must be a 4-byte aligned device pointer");
+  detect_decode_kernel<<<(g.rows + DET_TILE_ROWS - 1) / DET_TILE_ROWS, DET_THREADS, 0, (hipStream_t)hip_stream>>>(g, pred);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+size_t grpg_detect_workspace_bytes(int bs, int N) {
+  NmsLayout L;
+  return nms_layout(bs, N, L) ? L.total + align_up((size_t)bs * N * 16, 256) : 0;
+}
+
+int grpg_detect_detections(const float* const* heads, const grpg_detect_geometry* geom, int bs, float conf_thres,
+                           float iou_thres, const unsigned char* class_allow, int agnostic, int max_det, int max_nms,
+                           float max_wh, const double* frame_map, void* workspace, size_t workspace_bytes, float* det,
+                           int* count, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  const std::string pre = "detect_detections: ";
+  DetectArgs g;
+  int N;
+  if (int rc = detect_prepare(pre, heads, geom, bs, g, N)) return rc;
+  NmsLayout L;
+  if (!nms_layout(bs, N, L)) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "bs * N must be below 2^31");
+  if (!workspace || !det || !count) return fail(GRPG_ERR_INVALID_ARGUMENT, pre + "NULL workspace / det / count");
+  NmsWalkArgs a;
+  if (int rc = nms_prepare(pre, bs, N, 4, conf_thres, iou_thres, agnostic, max_det, max_nms, max_wh, frame_map, workspace,
+                           workspace_bytes, grpg_detect_workspace_bytes(bs, N), "grpg_detect_workspace_bytes",
+                           (uintptr_t)det | (uintptr_t)count, "det and count must be 4-byte aligned", L, a))
+    return rc;
+
+  char* ws = (char*)workspace;
+  hipStream_t st = (hipStream_t)hip_stream;
+  float4* boxes = (float4*)(ws + L.total);   // [bs, N, 4]; only a candidate's row is ever written or read
+  detect_candidates_kernel<<<(g.rows + DET_THREADS - 1) / DET_THREADS, DET_THREADS, 0, st>>>(
+      g, a.image_keys, conf_thres, class_allow, (uint32_t*)(ws + L.key_a), (uint32_t*)(ws + L.cls), boxes);
+  nms_sort_and_walk(st, bs, L, ws, (const float*)boxes, a, det, count);
   HIP_TRY(hipGetLastError());
   return GRPG_OK;
 }

@@ -1427,6 +1427,116 @@ std::tuple<torch::Tensor, torch::Tensor> NmsDetections(const torch::Tensor& pred
   return std::make_tuple(det, count);
 }
 
+// ---- detector head -> prediction / detections (gaussianrpg_amd/perception.py; csrc/nms.hip) ----
+
+namespace {
+// heads: the nl conv outputs float32 [bs, na*(5+nc), ny, nx]; anchor_grid: nl*na*2 pixels; stride: nl.  Everything is
+// checked here, before the device is needed.
+struct DetectCall {
+  grpg_detect_geometry geom;
+  std::vector<const float*> ptrs;
+  int64_t bs = 0, N = 0;
+
+  DetectCall(const char* what, const std::vector<torch::Tensor>& heads, const std::vector<double>& anchor_grid,
+             const std::vector<double>& stride, const int64_t na, const int64_t nc) {
+    const int64_t nl = (int64_t)stride.size();
+    TORCH_CHECK(nl >= 1 && nl <= GRPG_DETECT_MAX_LEVELS && na >= 1 && nl * na <= GRPG_DETECT_MAX_ANCHORS,
+                what, ": the geometry needs 1 <= nl <= 4, na >= 1 and nl * na <= 16 (got nl ", nl, ", na ", na, ")");
+    TORCH_CHECK(nc >= 1, what, ": nc must be positive");
+    TORCH_CHECK(nc < (int64_t(1) << 31) && na * (5 + nc) < (int64_t(1) << 31), what, ": na * (5 + nc) must be below 2^31");
+    TORCH_CHECK((int64_t)anchor_grid.size() == nl * na * 2, what, ": anchor_grid must hold nl * na * 2 values");
+    TORCH_CHECK((int64_t)heads.size() == nl, what, ": ", nl, " heads expected, one per level (got ", heads.size(), ")");
+    geom = grpg_detect_geometry{};
+    geom.nl = (int)nl; geom.na = (int)na; geom.nc = (int)nc;
+    for (int64_t i = 0; i < nl * na * 2; i++) geom.anchor_grid[i / 2][i % 2] = (float)anchor_grid[i];
+    for (int64_t l = 0; l < nl; l++) {
+      const torch::Tensor& h = heads[l];
+      TORCH_CHECK(h.scalar_type() == torch::kFloat32, what, ": head ", l, " must be float32 (got ", h.scalar_type(), ")");
+      TORCH_CHECK(h.dim() == 4 && h.size(0) >= 1 && h.size(2) >= 1 && h.size(3) >= 1 && h.size(1) == na * (5 + nc),
+                  what, ": head ", l, " must be [bs, na*(5+nc) = ", na * (5 + nc), ", ny, nx] (got ", h.sizes(), ")");
+      TORCH_CHECK(h.is_contiguous(), what, ": head ", l, " must be contiguous");
+      TORCH_CHECK(h.size(2) < (int64_t(1) << 31) && h.size(3) < (int64_t(1) << 31), what, ": bs * N must be below 2^31");
+      if (l == 0) bs = h.size(0);
+      TORCH_CHECK(h.size(0) == bs, what, ": every head must have the same bs (head 0 has ", bs, ", head ", l, " has ",
+                  h.size(0), ")");
+      TORCH_CHECK(h.device() == heads[0].device(), what, ": every head must be on ", heads[0].device());
+      geom.ny[l] = (int)h.size(2); geom.nx[l] = (int)h.size(3);
+      geom.stride[l] = (float)stride[l];
+      N += na * h.size(2) * h.size(3);
+      TORCH_CHECK(bs * N < (int64_t(1) << 31), what, ": bs * N must be below 2^31");
+    }
+    TORCH_CHECK(heads[0].is_cuda(), what, ": the heads must live on a ROCm/HIP device (torch device 'cuda'); this op "
+                                          "has no CPU path");
+    for (const torch::Tensor& h : heads) ptrs.push_back(h.data_ptr<float>());
+  }
+};
+}  // namespace
+
+torch::Tensor DetectDecode(const std::vector<torch::Tensor>& heads, const std::vector<double>& anchor_grid,
+                           const std::vector<double>& stride, const int64_t na, const int64_t nc,
+                           const c10::optional<torch::Tensor>& out) {
+  DetectCall c("detect_decode", heads, anchor_grid, stride, na, nc);
+  const bool given = out.has_value() && out->defined();
+  if (given)
+    TORCH_CHECK(out->scalar_type() == torch::kFloat32 && out->dim() == 3 && out->size(0) == c.bs && out->size(1) == c.N &&
+                    out->size(2) == 5 + nc && out->is_contiguous() && out->device() == heads[0].device(),
+                "detect_decode: out must be a contiguous float32 [", c.bs, ",", c.N, ",", 5 + nc, "] tensor on ",
+                heads[0].device());
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(heads[0].device());
+  torch::Tensor pred = given ? *out : torch::empty({c.bs, c.N, 5 + nc}, heads[0].options());
+  run("grpg_detect_decode", [&](void* stream) {
+    return grpg_detect_decode(c.ptrs.data(), &c.geom, (int)c.bs, pred.data_ptr<float>(), stream);
+  });
+  return pred;
+}
+
+std::tuple<torch::Tensor, torch::Tensor> DetectDetections(
+    const std::vector<torch::Tensor>& heads, const std::vector<double>& anchor_grid, const std::vector<double>& stride,
+    const int64_t na, const int64_t nc, const double conf_thres, const double iou_thres,
+    const c10::optional<torch::Tensor>& class_allow, const bool agnostic, const int max_det, const int max_nms,
+    const double max_wh, const std::vector<double>& frame_map, const c10::optional<torch::Tensor>& det_out,
+    const c10::optional<torch::Tensor>& count_out) {
+  DetectCall c("detect_detections", heads, anchor_grid, stride, na, nc);
+  const int64_t bs = c.bs;
+  const torch::Device device = heads[0].device();
+  TORCH_CHECK(conf_thres >= 0.0 && conf_thres <= 1.0 && iou_thres >= 0.0 && iou_thres <= 1.0,
+              "detect_detections: conf_thres and iou_thres must lie in [0, 1]");
+  TORCH_CHECK(max_det >= 1 && max_det <= 1024, "detect_detections: max_det must lie in [1, 1024] (got ", max_det, ")");
+  TORCH_CHECK(max_nms >= 1, "detect_detections: max_nms must be positive");
+  TORCH_CHECK(frame_map.empty() || frame_map.size() == 6,
+              "detect_detections: frame_map must be empty or (h, w, H, W, pad_x, pad_y)");
+  const bool det_given = det_out.has_value() && det_out->defined();
+  const bool count_given = count_out.has_value() && count_out->defined();
+  if (det_given)
+    TORCH_CHECK(det_out->scalar_type() == torch::kFloat32 && det_out->dim() == 3 && det_out->size(0) == bs &&
+                    det_out->size(1) == max_det && det_out->size(2) == 6 && det_out->is_contiguous() &&
+                    det_out->device() == device,
+                "detect_detections: out det must be a contiguous float32 [", bs, ",", max_det, ",6] tensor on ", device);
+  if (count_given)
+    TORCH_CHECK(count_out->scalar_type() == torch::kInt32 && count_out->dim() == 1 && count_out->size(0) == bs &&
+                    count_out->is_contiguous() && count_out->device() == device,
+                "detect_detections: out count must be a contiguous int32 [", bs, "] tensor on ", device);
+  const unsigned char* allow = nullptr;
+  if (class_allow.has_value() && class_allow->defined()) {
+    const torch::Tensor& t = *class_allow;
+    TORCH_CHECK(t.scalar_type() == torch::kUInt8 && t.dim() == 1 && t.size(0) == nc && t.is_contiguous() &&
+                    t.device() == device,
+                "detect_detections: class_allow must be a contiguous uint8 [", nc, "] tensor on ", device);
+    allow = t.data_ptr<uint8_t>();
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(device);
+  torch::Tensor det = det_given ? *det_out : torch::empty({bs, max_det, 6}, heads[0].options());
+  torch::Tensor count = count_given ? *count_out : torch::empty({bs}, heads[0].options().dtype(torch::kInt32));
+  const size_t bytes = grpg_detect_workspace_bytes((int)bs, (int)c.N);
+  torch::Tensor ws = torch::empty({(int64_t)bytes}, heads[0].options().dtype(torch::kByte));
+  run("grpg_detect_detections", [&](void* stream) {
+    return grpg_detect_detections(c.ptrs.data(), &c.geom, (int)bs, (float)conf_thres, (float)iou_thres, allow, agnostic,
+                                  max_det, max_nms, (float)max_wh, frame_map.empty() ? nullptr : frame_map.data(),
+                                  ws.data_ptr(), bytes, det.data_ptr<float>(), count.data_ptr<int>(), stream);
+  });
+  return std::make_tuple(det, count);
+}
+
 // ---- tracklets -> actor poses (gaussianrpg_amd/tracks.py; csrc/tracks.hip) ----
 
 namespace {
@@ -2346,6 +2456,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("max_wh") = 7680.0, pybind11::arg("frame_map") = std::vector<double>(),
         pybind11::arg("det_out") = pybind11::none(), pybind11::arg("count_out") = pybind11::none());
   m.def("nms_workspace_bytes", [](int bs, int N) { return grpg_nms_workspace_bytes(bs, N); });
+  // detector head -> prediction [bs,N,5+nc] / detections (perception.py)
+  m.def("detect_decode", &DetectDecode, pybind11::arg("heads"), pybind11::arg("anchor_grid"), pybind11::arg("stride"),
+        pybind11::arg("na"), pybind11::arg("nc"), pybind11::arg("out") = pybind11::none());
+  m.def("detect_detections", &DetectDetections, pybind11::arg("heads"), pybind11::arg("anchor_grid"),
+        pybind11::arg("stride"), pybind11::arg("na"), pybind11::arg("nc"), pybind11::arg("conf_thres") = 0.25,
+        pybind11::arg("iou_thres") = 0.45, pybind11::arg("class_allow") = pybind11::none(),
+        pybind11::arg("agnostic") = false, pybind11::arg("max_det") = 300, pybind11::arg("max_nms") = 30000,
+        pybind11::arg("max_wh") = 7680.0, pybind11::arg("frame_map") = std::vector<double>(),
+        pybind11::arg("det_out") = pybind11::none(), pybind11::arg("count_out") = pybind11::none());
+  m.def("detect_workspace_bytes", [](int bs, int N) { return grpg_detect_workspace_bytes(bs, N); });
   // tracklets -> actor poses (tracks.py): (rot [T,A,4], trans [T,A,3], active [T,A], chosen [T,A,4]) and the dense
   // (g_opt_trans [F,M,3], g_opt_rots [F,M,1])
   m.def("track_poses_forward", &TrackPosesForward, pybind11::arg("table"), pybind11::arg("timestamps"),

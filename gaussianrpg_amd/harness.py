@@ -464,6 +464,57 @@ def simulator_detections(prediction: torch.Tensor, plan, fused: bool = True, *, 
     return out
 
 
+def detect_inference_torch(heads, geom) -> torch.Tensor:
+    """The inference branch of the reference's ``Detect.forward`` after its convs (models/yolo.py:53-70, the
+    ``inplace`` form the simulator's detector runs), line by line in PyTorch on the heads' device: per level view /
+    permute / contiguous, sigmoid, the xy and wh slice assignments, and one cat.  geom: a ``DetectGeometry``.
+    Returns the [bs,N,5+nc] prediction; the heads are left alone.
+
+    As in the reference, nothing is built or uploaded per call: ``anchor_grid`` is a device buffer there
+    (yolo.py:44) and ``self.grid[i]`` is made once and kept while the level's shape stays (yolo.py:57-58).  Here both
+    are kept with ``geom``, per device; the first call on a device for a shape makes them."""
+    dev = heads[0].device
+    kept = geom.__dict__.setdefault("_torch_buffers", {})
+    if ("anchor_grid", dev) not in kept:
+        kept[("anchor_grid", dev)] = torch.from_numpy(geom.anchor_grid).to(dev).view(geom.nl, 1, geom.na, 1, 1, 2)
+    anchor_grid = kept[("anchor_grid", dev)]
+    z = []
+    with torch.no_grad():
+        for i, h in enumerate(heads):
+            bs, _, ny, nx = h.shape
+            x = h.view(bs, geom.na, geom.no, ny, nx).permute(0, 1, 3, 4, 2).contiguous()
+            if ("grid", dev, ny, nx) not in kept:          # _make_grid(nx, ny).to(device), yolo.py:72-75
+                yv, xv = torch.meshgrid([torch.arange(ny), torch.arange(nx)], indexing="ij")
+                kept[("grid", dev, ny, nx)] = torch.stack((xv, yv), 2).view((1, 1, ny, nx, 2)).float().to(dev)
+            grid = kept[("grid", dev, ny, nx)]
+            y = x.sigmoid()
+            y[..., 0:2] = (y[..., 0:2] * 2. - 0.5 + grid) * float(geom.stride[i])
+            y[..., 2:4] = (y[..., 2:4] * 2) ** 2 * anchor_grid[i]
+            z.append(y.view(bs, -1, geom.no))
+        return torch.cat(z, 1)
+
+
+def simulator_detections_from_heads(heads, geom, plan, fused: bool = True, *, conf_thres: float = 0.25,
+                                    iou_thres: float = 0.45, classes=None, agnostic: bool = False,
+                                    max_det: int = 10) -> list:
+    """``simulator_detections`` from the detector's nl conv outputs [bs, na*(5+nc), ny, nx] instead of its prediction:
+    what the simulator node does between its detector's last convolutions and its detections
+    (models/yolo.py:53-70, then simulator.py:349-368).  geom: the head's ``DetectGeometry``.
+      fused=False  ``detect_inference_torch`` -- the reference's lines in PyTorch on the device -- then
+                   ``simulator_detections(..., fused=False)``
+      fused=True   ``perception.detections_from_heads(..., plan=plan)``: the prediction never exists; one call, then
+                   one host wait to read the counts
+    Same detections either way, the confidences and the boxes before rounding to the last bits of the two sigmoids
+    (torch.sigmoid is not pinned bit for bit; tests/test_gpu_detect.py)."""
+    from . import perception
+    if fused:
+        det, count = perception.detections_from_heads(heads, geom, conf_thres, iou_thres, classes, agnostic, max_det,
+                                                      plan=plan)
+        return [det[b, :n] for b, n in enumerate(count.tolist())]
+    return simulator_detections(detect_inference_torch(heads, geom), plan, fused=False, conf_thres=conf_thres,
+                                iou_thres=iou_thres, classes=classes, agnostic=agnostic, max_det=max_det)
+
+
 def _quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """quaternion_raw_multiply (general_utils.py:220-238)"""
     aw, ax, ay, az = torch.unbind(a, -1)

@@ -27,6 +27,12 @@ and, with a plan, ``scale_coords(...).round()`` (simulator.py:368) -- in one cal
 equal confidences are ordered by ascending row (the reference's argsort leaves ties open), the frame mapping is a
 true float32 division (PyTorch's device kernels may multiply by a reciprocal; with the simulator's own plan the gain
 is 1 and they agree), and the prediction must be float32.
+
+Between the two stands the detector; of it, the inference branch of ``Detect.forward`` after the last convolutions
+(models/yolo.py:53-70) is here as well: ``decode_heads`` turns the nl conv outputs into the [bs,N,5+nc] prediction
+in one launch, and ``detections_from_heads`` goes from the conv outputs to the detections without the prediction
+(same bits as ``detections(decode_heads(...))``); a ``DetectGeometry`` holds the head's anchors and strides
+(INTEGRATION.md §21).
 """
 from typing import Optional, Sequence, Tuple, Union
 
@@ -185,6 +191,10 @@ def _check_nms_args(who: str, prediction, conf_thres, iou_thres, max_det, max_nm
         raise ValueError("%s: prediction must be contiguous (a copy of the head's output would hide its cost)" % who)
     if prediction.shape[0] * prediction.shape[1] >= 2 ** 31:
         raise ValueError("%s: bs * N must be below 2^31" % who)
+    _check_nms_settings(who, conf_thres, iou_thres, max_det, max_nms)
+
+
+def _check_nms_settings(who: str, conf_thres, iou_thres, max_det, max_nms):
     if not 0.0 <= conf_thres <= 1.0:
         raise ValueError("%s: invalid confidence threshold %r, valid values are between 0.0 and 1.0" % (who, conf_thres))
     if not 0.0 <= iou_thres <= 1.0:
@@ -245,6 +255,142 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
         prediction = prediction[0]
     det, count = detections(prediction, conf_thres, iou_thres, classes, agnostic, max_det)
     return [det[b, :n] for b, n in enumerate(count.tolist())]
+
+
+# ---- detector head -> prediction / detections ----
+
+DETECT_MAX_LEVELS = 4     # GRPG_DETECT_MAX_LEVELS
+DETECT_MAX_ANCHORS = 16   # GRPG_DETECT_MAX_ANCHORS: nl * na; the anchors travel as kernel arguments
+
+
+class DetectGeometry:
+    """The constants of the reference's ``Detect`` head (models/yolo.py:31-46), on the host:
+
+      anchor_grid  [nl, na, 2] anchor (width, height) in PIXELS -- ``Detect.anchor_grid``, not the stride-divided
+                   ``Detect.anchors``
+      stride       [nl]
+      nc           number of classes
+
+    1 <= nl <= 4, na >= 1, nl * na <= 16.  They travel to the kernels as launch arguments: there is no device table and
+    no per-call upload."""
+
+    def __init__(self, anchor_grid, stride, nc: int):
+        ag = np.asarray(anchor_grid.detach().cpu() if isinstance(anchor_grid, torch.Tensor) else anchor_grid,
+                        dtype=np.float32)
+        st = np.asarray(stride.detach().cpu() if isinstance(stride, torch.Tensor) else stride, dtype=np.float32)
+        if ag.ndim != 3 or ag.shape[2] != 2 or st.ndim != 1 or st.shape[0] != ag.shape[0]:
+            raise ValueError("DetectGeometry: anchor_grid must be [nl, na, 2] and stride [nl] (got %s and %s); "
+                             "Detect.anchor_grid is [nl,1,na,1,1,2]: use DetectGeometry.from_module" %
+                             (list(ag.shape), list(st.shape)))
+        nl, na = int(ag.shape[0]), int(ag.shape[1])
+        if not (1 <= nl <= DETECT_MAX_LEVELS and na >= 1 and nl * na <= DETECT_MAX_ANCHORS):
+            raise ValueError("DetectGeometry: needs 1 <= nl <= %d, na >= 1 and nl * na <= %d (got nl %d, na %d)" %
+                             (DETECT_MAX_LEVELS, DETECT_MAX_ANCHORS, nl, na))
+        if int(nc) != nc or nc < 1:
+            raise ValueError("DetectGeometry: nc must be a positive integer (got %r)" % (nc,))
+        if na * (5 + int(nc)) >= 2 ** 31:
+            raise ValueError("DetectGeometry: na * (5 + nc) must be below 2^31 (got %d * %d)" % (na, 5 + int(nc)))
+        if not (np.isfinite(ag).all() and np.isfinite(st).all() and (st > 0).all()):
+            raise ValueError("DetectGeometry: anchor_grid must be finite and stride positive and finite")
+        self.anchor_grid, self.stride = ag, st
+        self.nl, self.na, self.nc, self.no = nl, na, int(nc), int(nc) + 5
+        self._anchor_list = [float(v) for v in ag.reshape(-1)]
+        self._stride_list = [float(v) for v in st]
+
+    @classmethod
+    def from_module(cls, m) -> "DetectGeometry":
+        """From an object with ``anchor_grid``, ``stride``, ``nc``, ``na`` and ``nl`` (the reference's ``Detect``):
+        one host copy, here, and none per call."""
+        ag = m.anchor_grid
+        ag = ag.detach().cpu().numpy() if isinstance(ag, torch.Tensor) else np.asarray(ag)
+        return cls(np.asarray(ag, dtype=np.float32).reshape(int(m.nl), int(m.na), 2), m.stride, int(m.nc))
+
+    def rows(self, heads) -> int:
+        """N: the rows per image of these heads."""
+        return sum(self.na * int(h.shape[2]) * int(h.shape[3]) for h in heads)
+
+    def __repr__(self):
+        return "DetectGeometry(nl=%d, na=%d, nc=%d, stride=%s)" % (self.nl, self.na, self.nc, self._stride_list)
+
+
+def _check_heads(who: str, heads, geom) -> Tuple[int, int]:
+    """(bs, N) of the heads, or the error that says what to pass instead; touches no device."""
+    if not isinstance(geom, DetectGeometry):
+        raise TypeError("%s: geom must be a DetectGeometry (got %s); build one with DetectGeometry.from_module(detect)" %
+                        (who, type(geom).__name__))
+    if not isinstance(heads, (list, tuple)) or len(heads) != geom.nl:
+        raise ValueError("%s: heads must be the list of the %d conv outputs, one per level (got %s)" %
+                         (who, geom.nl, "%d" % len(heads) if isinstance(heads, (list, tuple)) else type(heads).__name__))
+    bs = N = 0
+    for l, h in enumerate(heads):
+        if not isinstance(h, torch.Tensor):
+            raise TypeError("%s: head %d must be a tensor (got %s)" % (who, l, type(h).__name__))
+        if h.dtype != torch.float32:
+            raise TypeError("%s: head %d must be float32 (got %s); a .half() detector forms its sigmoids and obj * cls "
+                            "in half, which is a different contract: pass head.float() if that is what you mean" %
+                            (who, l, h.dtype))
+        if h.dim() != 4 or h.shape[0] < 1 or h.shape[2] < 1 or h.shape[3] < 1:
+            raise ValueError("%s: head %d must be [bs, na*(5+nc), ny, nx] (got %s)" % (who, l, list(h.shape)))
+        if h.shape[1] != geom.na * geom.no:
+            raise ValueError("%s: head %d has %d channels, na * (5 + nc) = %d * %d = %d expected: pass the conv output "
+                             "itself, before Detect's view / permute" %
+                             (who, l, h.shape[1], geom.na, geom.no, geom.na * geom.no))
+        if l == 0:
+            bs = int(h.shape[0])
+        elif int(h.shape[0]) != bs:
+            raise ValueError("%s: every level must have the same bs (head 0 has %d, head %d has %d)" %
+                             (who, bs, l, h.shape[0]))
+        N += geom.na * int(h.shape[2]) * int(h.shape[3])
+    if bs * N >= 2 ** 31:
+        raise ValueError("%s: bs * N must be below 2^31 (got %d * %d): split the batch" % (who, bs, N))
+    for l, h in enumerate(heads):
+        if not h.is_contiguous():
+            raise ValueError("%s: head %d must be contiguous NCHW (the conv output as it is; a permuted or "
+                             "channels_last view would be copied, which hides its cost)" % (who, l))
+    for l, h in enumerate(heads):
+        if not h.is_cuda:
+            raise ValueError("%s: head %d is on %s; the heads must live on a ROCm/HIP device (torch device 'cuda'): "
+                             "this op has no CPU path" % (who, l, h.device))
+        if h.device != heads[0].device:
+            raise ValueError("%s: head %d is on %s, head 0 on %s" % (who, l, h.device, heads[0].device))
+    return bs, N
+
+
+def decode_heads(heads: Sequence[torch.Tensor], geom: DetectGeometry, *,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The inference branch of the reference's ``Detect.forward`` after its 1x1 convs (models/yolo.py:53-70: view /
+    permute / contiguous, sigmoid, the xy and wh slice assignments, cat over the levels) in ONE launch on the current
+    stream: the float32 [bs,N,5+nc] prediction ``detections`` takes.
+
+    heads: the nl conv outputs, float32 [bs, na*(5+nc), ny_l, nx_l], contiguous NCHW, on the device; only read.
+    Rows in the reference's order: levels in order, inside a level ``(a*ny + y)*nx + x``, images outermost.  Columns:
+    ``xy = ((s*2 - 0.5) + grid) * stride``, ``wh = (s*2)**2 * anchor``, columns 4+ ``s``, with s = 1/(1 + exp(-v)) and
+    every step one float32 operation in that order.  torch.sigmoid is not pinned bit for bit; the result lies as
+    close to the float64 value as the reference's own (tests/test_gpu_detect.py).
+    out: a preallocated contiguous float32 [bs,N,5+nc] tensor on the heads' device; every element is written."""
+    _check_heads("decode_heads", heads, geom)
+    res = _C.detect_decode(list(heads), geom._anchor_list, geom._stride_list, geom.na, geom.nc, out)
+    return res if out is None else out
+
+
+def detections_from_heads(heads: Sequence[torch.Tensor], geom: DetectGeometry, conf_thres: float = 0.25,
+                          iou_thres: float = 0.45, classes: Optional[Sequence[int]] = None, agnostic: bool = False,
+                          max_det: int = 300, *, max_nms: int = MAX_NMS, plan: Optional[LetterboxPlan] = None,
+                          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+                          ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``detections(decode_heads(heads, geom), ...)`` -- the same ``(det, count)``, bit for bit, every argument with
+    the same meaning -- without the prediction: the candidate pass reads every row's objectness logit from the heads
+    and the other 4 + nc planes only where a wave holds a row that passes; the rows that stay leave their decoded box
+    in the workspace, and the sort and the greedy walk of ``detections`` run on those.  No host wait."""
+    _check_nms_settings("detections_from_heads", conf_thres, iou_thres, max_det, max_nms)
+    _check_heads("detections_from_heads", heads, geom)
+    table = None if classes is None else _class_table(classes, geom.nc, heads[0].device)
+    fmap = [] if plan is None else list(frame_map(plan))
+    det_out, count_out = (None, None) if out is None else out
+    det, count = _C.detect_detections(list(heads), geom._anchor_list, geom._stride_list, geom.na, geom.nc,
+                                      float(conf_thres), float(iou_thres), table, bool(agnostic), int(max_det),
+                                      int(max_nms), float(MAX_WH), fmap, det_out, count_out)
+    return (det, count) if out is None else (det_out, count_out)
 
 
 # ---- host restatement: what stands in for cv2 on the reference's route through the host ----

@@ -785,6 +785,44 @@ GRPG_API int grpg_nms_detections(const float* prediction, int bs, int N, int nc,
                                  float* det, int* count, void* hip_stream);
 
 /*
+ * Detector head -> prediction / detections: the inference branch of Detect.forward (models/yolo.py:48-70) after its
+ * 1x1 convs, on the device, without a host wait and without atomics; identical bits from identical calls.
+ *
+ * grpg_detect_geometry (HOST; it travels to the kernels as launch arguments, there is no device table): nl levels
+ * (1..4) of na anchors each (nl * na <= 16), nc >= 1 classes (na * (5 + nc) < 2^31); per level the plane size
+ * ny x nx and the stride; anchor_grid [l * na + a] = the anchor's (width, height) in pixels -- Detect.anchor_grid,
+ * not the stride-divided Detect.anchors.
+ * heads: HOST array of nl DEVICE pointers, head l float32 [bs, na * (5 + nc), ny[l], nx[l]] contiguous (the conv
+ * output as it is); only read.  N = na * sum_l ny[l] * nx[l] rows per image, in the reference's order: levels in
+ * order, inside a level row (a * ny + y) * nx + x, images outermost.  With s = 1 / (1 + exp(-v)) (float32, the division
+ * correctly rounded) the columns of a row are, every step one float32 operation in this order,
+ *   cx = ((s0 * 2 - 0.5) + x) * stride      cy = ((s1 * 2 - 0.5) + y) * stride
+ *   w  = ((s2 * 2) * (s2 * 2)) * anchor_w   h  = ((s3 * 2) * (s3 * 2)) * anchor_h      columns 4 .. 4 + nc: s.
+ *
+ * grpg_detect_decode writes all of pred, float32 [bs, N, 5 + nc] on the device, in one launch.
+ * grpg_detect_detections is grpg_nms_detections on that prediction -- the same det and count, bit for bit, and the
+ * same meaning of every other argument -- without the prediction: a candidate pass reads every row's objectness logit
+ * and the other 4 + nc planes only where a wave holds a row with s(obj) > conf_thres; the rows that stay leave their
+ * decoded box in the workspace.  workspace: grpg_detect_workspace_bytes(bs, N) bytes on the device, 256-byte aligned;
+ * the size query needs no device and returns 0 for sizes the entry refuses (bs < 1, N < 1, bs * N >= 2^31).
+ */
+#define GRPG_DETECT_MAX_LEVELS 4
+#define GRPG_DETECT_MAX_ANCHORS 16
+typedef struct grpg_detect_geometry {
+  int nl, na, nc;
+  int ny[GRPG_DETECT_MAX_LEVELS], nx[GRPG_DETECT_MAX_LEVELS];
+  float stride[GRPG_DETECT_MAX_LEVELS];
+  float anchor_grid[GRPG_DETECT_MAX_ANCHORS][2];
+} grpg_detect_geometry;
+GRPG_API int grpg_detect_decode(const float* const* heads, const grpg_detect_geometry* geometry, int bs, float* pred,
+                                void* hip_stream);
+GRPG_API size_t grpg_detect_workspace_bytes(int bs, int N);
+GRPG_API int grpg_detect_detections(const float* const* heads, const grpg_detect_geometry* geometry, int bs,
+                                    float conf_thres, float iou_thres, const unsigned char* class_allow_dev,
+                                    int agnostic, int max_det, int max_nms, float max_wh, const double* frame_map,
+                                    void* workspace, size_t workspace_bytes, float* det, int* count, void* hip_stream);
+
+/*
  * Tracklets -> actor poses: ActorPose.get_tracking_rotation / get_tracking_translation (lib/models/actor_pose.py:83-179)
  * and the ego product of StreetGaussianModel.parse_camera (lib/models/street_gaussian_model.py:268-274) for every actor
  * and every query stamp in ONE launch, and the gradient at the poses carried on to opt_trans / opt_rots in one
