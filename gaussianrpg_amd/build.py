@@ -78,6 +78,8 @@ HIP_UNITS = {
     # tracklets -> actor poses and back to opt_trans / opt_rots: every step the single float32 operation of the torch
     # restatement (tests/tracks_truth.py), divisions and square roots correctly rounded; no atomics
     "tracks.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # actor poses from device memory into the segment table: loads and stores only, no arithmetic
+    "segment_pose.hip": [],
     "api.hip": [],
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept

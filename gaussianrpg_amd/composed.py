@@ -15,7 +15,9 @@ concatenated tensors are never materialised.
     color, radii, depth, alpha = ComposedRasterizer(raster_settings)(models, poses)
 
 ``poses`` may also be a ``PoseRows`` -- the frame's poses as two device tensors, what ``tracks.PoseBatch.frame``
-makes of the tracklets in one launch -- wherever the list form is accepted.
+makes of the tracklets in one launch -- wherever the list form is accepted, or a ``PoseTable`` -- the pose batch's own
+device rows and one row index per model, what ``tracks.PoseBatch.rows`` returns without a launch: the poses then never
+visit the host (C ABI ``grpg_bind_device_poses``), and the frame is bit for bit the one the other two forms give.
 
 Evaluation (``torch.no_grad()`` or nothing requires grad): forward only.  TRAINING (round 3): when
 any raw parameter tensor -- or an actor's ``obj_rot`` / ``obj_trans`` given as a tensor -- requires
@@ -84,9 +86,79 @@ class PoseRows(NamedTuple):
     fourier_time: Sequence[float]
 
 
+class PoseTable(NamedTuple):
+    """The poses of one frame left where ``TrackedActorPoses.poses`` wrote them: ``rot [A,4]`` (w,x,y,z) and ``trans
+    [A,3]`` on the device, one row per ACTOR of the track table (``PoseBatch.rot[t]`` / ``.trans[t]``, views), and
+    ``row``: per MODEL of the frame the row it takes its pose from, -1 for a model that takes none from the device.
+    ``posed`` / ``fourier_time``: one entry per model, as in ``PoseRows``.  ``host_pose`` (optional): per model None, or
+    ``(obj_rot, obj_trans)`` as floats for a posed model whose ``row`` is -1 -- an actor the host poses.  What
+    ``tracks.PoseBatch.rows`` returns; every entry point that takes the list form takes this one.  Nothing is copied to
+    the host: the library's segment table takes the rows from device memory behind its own upload, on the call's stream
+    (``grpg_bind_device_poses``), and in training the pose gradient comes back as dense ``[A,4]`` / ``[A,3]`` tensors,
+    zero for the actors the frame does not show."""
+    rot: torch.Tensor
+    trans: torch.Tensor
+    row: Sequence[int]
+    posed: Sequence[bool]
+    fourier_time: Sequence[float]
+    host_pose: Optional[Sequence] = None
+
+
 def _posed_flags(poses):
     """one flag per model: the model has a pose (an actor)"""
-    return [bool(f) for f in poses.posed] if isinstance(poses, PoseRows) else [p is not None for p in poses]
+    if isinstance(poses, (PoseRows, PoseTable)):
+        return [bool(f) for f in poses.posed]
+    return [p is not None for p in poses]
+
+
+def _pack_table(n_models, poses: PoseTable):
+    """The pose argument of a PoseTable, (pose_t [n,8] on the host, rot, trans, row int32 [n] on the host) -- what the
+    binding's `poses` takes in place of pose_t alone -- and the Fourier times.  pose_t holds the posed flag and zeros
+    (the host poses of `host_pose` where given); the device tensors are handed on as they are and never read."""
+    n = len(poses.posed)
+    if n != n_models or len(poses.fourier_time) != n or len(poses.row) != n:
+        raise ValueError("one row index, posed flag and fourier_time per model")
+    if poses.rot.dim() != 2 or poses.rot.shape[1] != 4 or tuple(poses.trans.shape) != (poses.rot.shape[0], 3):
+        raise ValueError("pose table must be rot [A,4] and trans [A,3], got %s and %s"
+                         % (tuple(poses.rot.shape), tuple(poses.trans.shape)))
+    if poses.rot.dtype != torch.float32 or poses.trans.dtype != torch.float32:
+        raise TypeError("pose table must be float32, got %s and %s" % (poses.rot.dtype, poses.trans.dtype))
+    A = int(poses.rot.shape[0])
+    rows = []
+    for i in range(n):
+        r, f = int(poses.row[i]), bool(poses.posed[i])
+        if r < -1 or r >= A:
+            raise ValueError("model %d: row %d is neither -1 nor one of the table's %d rows" % (i, r, A))
+        row = list(_ZERO_ROW)
+        if f:
+            row[0] = 1.0
+            if r < 0:
+                hp = None if poses.host_pose is None else poses.host_pose[i]
+                if hp is None:
+                    raise ValueError("model %d is posed, but has neither a table row nor a host pose" % i)
+                row[1:5] = [float(x) for x in hp[0]]
+                row[5:8] = [float(x) for x in hp[1]]
+        elif r >= 0:
+            raise ValueError("model %d is static, but names row %d of the pose table" % (i, r))
+        rows.append(row)
+    pose_t = torch.from_numpy(np.asarray(rows, dtype=np.float32).reshape(n, 8))
+    row_t = torch.from_numpy(np.asarray([int(r) for r in poses.row], dtype=np.int32).reshape(n))
+    times = [float(t) if f else 0.0 for t, f in zip(poses.fourier_time, poses.posed)]
+    return (pose_t, poses.rot.detach().contiguous(), poses.trans.detach().contiguous(), row_t), times
+
+
+def _scatter_pose_grads(pose_arg, g_poses, want_rot, want_trans):
+    """dL_dposes [n,8] of a PoseTable frame -> dense gradients of the table, ([A,4], [A,3]): zero for the actors the
+    frame does not show, summed for an actor it shows twice.  One memset and one index add per tensor."""
+    _, rot, _, row_t = pose_arg
+    sel = torch.nonzero(row_t >= 0).view(-1)          # host arithmetic on the host index list
+    dev = g_poses.device
+    src = g_poses.index_select(0, sel.to(dev, non_blocking=True))
+    to = row_t[sel].long().to(dev, non_blocking=True)
+    A = rot.shape[0]
+    g_rot = g_poses.new_zeros(A, 4).index_add_(0, to, src[:, 0:4]) if want_rot else None
+    g_trans = g_poses.new_zeros(A, 3).index_add_(0, to, src[:, 4:7]) if want_trans else None
+    return g_rot, g_trans
 
 
 def _pack_rows(n_models, poses: PoseRows):
@@ -162,6 +234,10 @@ def _pack(models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]]):
         lists, dims = _model_lists(models)
         pose_t, times = _pack_rows(len(models), poses)
         return lists, pose_t, _idft_rows(times, dims)
+    if isinstance(poses, PoseTable):   # pose_t: the tuple the binding takes in its place, device poses included
+        lists, dims = _model_lists(models)
+        pose_t, times = _pack_table(len(models), poses)
+        return lists, pose_t, _idft_rows(times, dims)
     if len(models) != len(poses):
         raise ValueError("one pose entry (None for a static model) per model")
     lists, dims = _model_lists(models)
@@ -217,7 +293,7 @@ def compose(models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]])
 
 
 def _pose_tensors(poses):
-    if isinstance(poses, PoseRows):
+    if isinstance(poses, (PoseRows, PoseTable)):
         return [poses.rot, poses.trans]
     return [t for p in poses if p is not None for t in (p.obj_rot, p.obj_trans) if isinstance(t, torch.Tensor)]
 
@@ -226,6 +302,8 @@ def _pose_graph(poses, pose_tensors):
     """poses as [n,4] / [n,3] tensors that keep their graph (rows of static models: constants)"""
     if isinstance(poses, PoseRows):   # as they are: a static model's row receives a zero gradient
         return poses.rot.float(), poses.trans.float()
+    if isinstance(poses, PoseTable):  # the table itself, [A,4] / [A,3]: the backward scatters into its shape
+        return poses.rot, poses.trans
     if not pose_tensors:
         return None, None
     one = torch.tensor([1.0, 0.0, 0.0, 0.0])
@@ -307,7 +385,10 @@ class _ComposeFeatures(torch.autograd.Function):
             if need[8 + 2 * nm + i] and ctx.normals:
                 grads[2 * nm + i] = g_rot[i]
         sem_grads = [g if (n and g.numel()) else None for g, n in zip(g_sem, need[8 + 6 * nm:])]
-        g_pose_rot = g_poses[:, 0:4].to(ctx.pose_dev) if need[6] else None
+        if isinstance(ctx.pose_t, tuple):   # a PoseTable: dense over the table's rows
+            g_pose_rot = _scatter_pose_grads(ctx.pose_t, g_poses, need[6], False)[0]
+        else:
+            g_pose_rot = g_poses[:, 0:4].to(ctx.pose_dev) if need[6] else None
         return (None, None, None, None, None, None, g_pose_rot, None) + tuple(grads) + tuple(sem_grads)
 
 
@@ -328,7 +409,7 @@ def compose_features(models: Sequence[ModelParams], poses: Sequence[Optional[Act
     dev = models[0].xyz.device
     campos = _NO_SEMANTIC if campos is None else campos.detach().to(device=dev, dtype=torch.float32).reshape(-1)
     normals = bool(normals)
-    rot_tensors = [poses.rot] if isinstance(poses, PoseRows) else \
+    rot_tensors = [poses.rot] if isinstance(poses, (PoseRows, PoseTable)) else \
         [p.obj_rot for p in poses if p is not None and isinstance(p.obj_rot, torch.Tensor)]
     train = torch.is_grad_enabled() and any(
         t.requires_grad for t in (lists[2] if normals else []) + (rot_tensors if normals else []) + list(sems))
@@ -413,8 +494,11 @@ def _composed_backward(ctx, first, state, params, g_color, g_depth, g_alpha, g_f
     else:
         out = _C.rasterize_gaussians_composed_objects_backward(*args, *objects, rs.debug)
     *g_params, g_sem, g_means2D, g_poses = out
-    g_rot = g_poses[:, 0:4].to(ctx.pose_dev[0]) if need[8] else None
-    g_trans = g_poses[:, 4:7].to(ctx.pose_dev[1]) if need[9] else None
+    if isinstance(ctx.pose_t, tuple):   # a PoseTable: dense over the table's rows
+        g_rot, g_trans = _scatter_pose_grads(ctx.pose_t, g_poses, need[8], need[9])
+    else:
+        g_rot = g_poses[:, 0:4].to(ctx.pose_dev[0]) if need[8] else None
+        g_trans = g_poses[:, 4:7].to(ctx.pose_dev[1]) if need[9] else None
     grads = [g for per_field in g_params for g in per_field]
     flat_grads = tuple(g if n else None for g, n in zip(grads, need_params))
     sem_grads = tuple(g if (n and g.numel()) else None for g, n in zip(g_sem, need_sem))

@@ -626,6 +626,41 @@ BwdStagingSlot* bwd_staging_acquire() {
   return &b;
 }
 
+// ---- device poses (grpg_bind_device_poses): a binding waits in g_pose_pending until the next entry point that takes
+// a grpg_model_segment* opens its PoseScope, which moves it into g_pose_cur for the length of that call -- through
+// nested entries (grpg_forward_composed -> _flags, the backward's shared bodies) and every table the call builds --
+// and drops it when the outermost scope closes, whatever the call returns.  Plain arrays: no destructor at thread exit.
+struct PoseBinding {
+  bool set = false, any = false;   // any: some row >= 0, i.e. the gather kernel has work
+  const float* rot = nullptr;
+  const float* trans = nullptr;
+  int n = 0;
+  int row[MAX_SEGMENTS];
+  void clear() { set = any = false; rot = trans = nullptr; n = 0; }
+};
+thread_local PoseBinding g_pose_pending, g_pose_cur;
+thread_local int g_pose_depth = 0;
+struct PoseScope {
+  PoseScope() {
+    if (g_pose_depth++ != 0) return;
+    g_pose_cur.clear();
+    if (g_pose_pending.set) {
+      g_pose_cur.set = true; g_pose_cur.any = g_pose_pending.any;
+      g_pose_cur.rot = g_pose_pending.rot; g_pose_cur.trans = g_pose_pending.trans; g_pose_cur.n = g_pose_pending.n;
+      memcpy(g_pose_cur.row, g_pose_pending.row, sizeof(int) * (size_t)g_pose_pending.n);
+    }
+    g_pose_pending.clear();
+  }
+  ~PoseScope() {
+    if (--g_pose_depth == 0) g_pose_cur.clear();
+  }
+};
+// behind the asynchronous copy of a table fill_segments built: the bound rows' poses, on the same stream
+void gather_device_poses(hipStream_t stream, SegmentDev* seg_dev, int nseg) {
+  if (g_pose_cur.set && g_pose_cur.any && g_pose_cur.n == nseg)
+    launch_segment_pose_gather(stream, seg_dev, nseg, g_pose_cur.rot, g_pose_cur.trans);
+}
+
 // grpg_forward_layers: the class of every Gaussian and the two extra plane pairs
 struct LayerArgs {
   const unsigned char* segment_class;   // composed frames: [num_segments] HOST bytes (NULL: the segment's rigid flag)
@@ -657,6 +692,14 @@ void fill_segments(SegmentDev* dst, const grpg_model_segment* segs, int nseg, co
     for (int k = 0; k < MAX_FOURIER; k++) d.idft[k] = g.idft[k];
     start += (uint32_t)g.count;
   }
+  // device poses: pose_row + 1 travels in the bits of the spare word, to the gather kernel behind the table's copy
+  // (gather_device_poses), which puts the word back to 0.f -- the hot kernels load the same 144 bytes as ever
+  if (g_pose_cur.set && g_pose_cur.n == nseg)
+    for (int i = 0; i < nseg; i++)
+      if (g_pose_cur.row[i] >= 0) {
+        const int parked = g_pose_cur.row[i] + 1;
+        memcpy(&dst[i].pad0, &parked, sizeof(parked));
+      }
 }
 
 // One forward frame as an entry point hands it to forward_impl.  Every extern "C" forward fills the fields it has;
@@ -934,6 +977,7 @@ struct Frame {
     fill_segments(g_seg_staging, q.segs, q.nseg, layers);
     HIP_TRY(hipMemcpyAsync(seg_dev, g_seg_staging, sizeof(SegmentDev) * (size_t)q.nseg,
                            hipMemcpyHostToDevice, stream));
+    gather_device_poses(stream, seg_dev, q.nseg);
     return GRPG_OK;
   }
 
@@ -1308,6 +1352,13 @@ int check_segments(const grpg_model_segment* segs, int nseg, int M, long long* P
     P += g.count;
   }
   if (P > (long long)ID_MASK) return fail(GRPG_ERR_INVALID_ARGUMENT, "P must be < 2^28");
+  if (g_pose_cur.set) {   // the device poses bound for this call (grpg_bind_device_poses) must fit its segments
+    if (g_pose_cur.n != nseg)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "device poses were bound for another number of segments");
+    for (int i = 0; i < nseg; i++)
+      if (g_pose_cur.row[i] >= 0 && segs[i].rigid == 0)
+        return fail(GRPG_ERR_INVALID_ARGUMENT, "a device pose row names a static segment (rigid == 0)");
+  }
   *P_out = P;
   return GRPG_OK;
 }
@@ -1451,6 +1502,29 @@ int grpg_frame_status(int ticket, int wait, int* num_rendered) {
   return r;
 }
 
+// Pure host bookkeeping: needs no device (the consuming call looks for one).  A bad binding is refused here and
+// replaces nothing -- but a binding that was pending is dropped either way: the caller meant to replace it.
+int grpg_bind_device_poses(const float* pose_rot, const float* pose_trans, const int* pose_row, int num_segments) {
+  g_last_error.clear();
+  g_pose_pending.clear();
+  if (!pose_row || num_segments <= 0 || num_segments > GRPG_MAX_SEGMENTS)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "device poses: need pose_row and 1..GRPG_MAX_SEGMENTS segments");
+  bool any = false;
+  for (int i = 0; i < num_segments; i++) {
+    if (pose_row[i] < -1 || pose_row[i] >= (1 << 28))
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "device poses: a pose_row entry is -1 or a row index below 2^28");
+    any = any || pose_row[i] >= 0;
+  }
+  if (any && (!pose_rot || !pose_trans))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "device poses: NULL pose_rot / pose_trans with a row bound");
+  g_pose_pending.set = true; g_pose_pending.any = any;
+  g_pose_pending.rot = pose_rot; g_pose_pending.trans = pose_trans; g_pose_pending.n = num_segments;
+  memcpy(g_pose_pending.row, pose_row, sizeof(int) * (size_t)num_segments);
+  return GRPG_OK;
+}
+
+int grpg_device_poses_bound(void) { return g_pose_pending.set ? 1 : 0; }
+
 int grpg_forward_composed_flags(grpg_alloc_fn geometry_alloc, void* geometry_user,
                                 grpg_alloc_fn binning_alloc, void* binning_user,
                                 grpg_alloc_fn image_alloc, void* image_user,
@@ -1459,6 +1533,7 @@ int grpg_forward_composed_flags(grpg_alloc_fn geometry_alloc, void* geometry_use
                                 const float* viewmatrix, const float* projmatrix, const float* cam_pos,
                                 float tan_fovx, float tan_fovy, float* out_color, float* out_depth,
                                 float* out_alpha, int* radii, int debug, void* hip_stream, unsigned flags) {
+  PoseScope poses;
   if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
@@ -1481,6 +1556,7 @@ int grpg_forward_composed_layers(grpg_alloc_fn geometry_alloc, void* geometry_us
                                  float* out_depth, float* out_alpha, float* out_color_bg, float* out_alpha_bg,
                                  float* out_color_obj, float* out_alpha_obj, int* radii, int debug,
                                  void* hip_stream) {
+  PoseScope poses;
   if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
@@ -1543,6 +1619,7 @@ int grpg_forward_composed_frame(grpg_alloc_fn geometry_alloc, void* geometry_use
                                 float* out_alpha, float* out_color_bg, float* out_alpha_bg, float* out_color_obj,
                                 float* out_alpha_obj, int* radii, int debug, void* hip_stream,
                                 const grpg_frame_epilogue* epilogue) {
+  PoseScope poses;
   if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
@@ -1569,6 +1646,7 @@ int grpg_forward_composed(grpg_alloc_fn geometry_alloc, void* geometry_user,
                           const float* viewmatrix, const float* projmatrix, const float* cam_pos,
                           float tan_fovx, float tan_fovy, float* out_color, float* out_depth,
                           float* out_alpha, int* radii, int debug, void* hip_stream) {
+  PoseScope poses;
   return grpg_forward_composed_flags(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc,
                                      image_user, segments, num_segments, D, M, background, width, height,
                                      scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
@@ -1617,6 +1695,7 @@ static int backward_composed_impl(const grpg_model_segment* segments, const grpg
   void* seg_grad_dev = (void*)(geom_buffer + bb.GL.seg_grad_table);
   HIP_TRY(hipMemcpyAsync(seg_dev, stg->segs, sizeof(SegmentDev) * (size_t)num_segments,
                          hipMemcpyHostToDevice, stream));
+  gather_device_poses(stream, seg_dev, num_segments);
   HIP_TRY(hipMemcpyAsync(seg_grad_dev, stg->grads, sizeof(grpg_model_segment_grad) * (size_t)num_segments,
                          hipMemcpyHostToDevice, stream));
   HIP_TRY(hipEventRecord(stg->ev, stream));
@@ -1650,6 +1729,7 @@ int grpg_backward_composed(const grpg_model_segment* segments, const grpg_model_
                            char* image_buffer, const float* dL_dpix, const float* dL_dpix_depth,
                            const float* dL_dalphas, float* dL_dmean2D, float* dL_dposes, int debug,
                            void* hip_stream) {
+  PoseScope poses;
   return backward_composed_impl(segments, grads, num_segments, D, M, R, background, width, height, scale_modifier,
                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, alphas, geom_buffer,
                                 binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dmean2D,
@@ -1674,6 +1754,7 @@ int grpg_forward_composed_features(grpg_alloc_fn geometry_alloc, void* geometry_
                                    float tan_fovx, float tan_fovy, float* out_color, float* out_depth,
                                    float* out_alpha, float* out_features, int* radii, int debug, void* hip_stream,
                                    unsigned flags) {
+  PoseScope poses;
   if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
@@ -1752,6 +1833,7 @@ int grpg_backward_composed_features(const grpg_model_segment* segments, const gr
                                     char* feature_buffer, const float* dL_dpix, const float* dL_dpix_depth,
                                     const float* dL_dalphas, const float* dL_dpix_features, float* dL_dfeatures,
                                     float* dL_dmean2D, float* dL_dposes, int debug, void* hip_stream) {
+  PoseScope poses;
   return backward_composed_features_impl(segments, grads, num_segments, seg_dL_dsemantic, S, normals, D, M, R,
                                          background, width, height, scale_modifier, viewmatrix, projmatrix, campos,
                                          tan_fovx, tan_fovy, radii, alphas, geom_buffer, binning_buffer, image_buffer,
@@ -1811,6 +1893,7 @@ int grpg_backward_composed_objects(const grpg_model_segment* segments, const grp
                                    const float* dL_dalphas, const float* dL_dpix_features, float* dL_dfeatures,
                                    float* dL_dmean2D, float* dL_dposes, const float* alpha_object, char* workspace,
                                    const float* dL_dalpha_object, int debug, void* hip_stream) {
+  PoseScope poses;
   if (int rc = begin_call()) return rc;
   if (!alpha_object || !workspace || !dL_dalpha_object || ((uintptr_t)workspace & 3u) != 0u || width <= 0 ||
       height <= 0)
@@ -1857,6 +1940,7 @@ static int temp_table_call(const grpg_model_segment* segments, int num_segments,
     e = hipMemcpyAsync(fdev + FL.table, fhost.data(), sizeof(FeatureSegDev) * n, hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);   // pageable sources: the copies must finish before they die
   if (e == hipSuccess) {
+    gather_device_poses(stream, (SegmentDev*)dev, num_segments);
     launch((const SegmentDev*)dev, feats ? (const FeatureSegDev*)(fdev + FL.table) : nullptr,
            feats ? (float*)(fdev + FL.partials) : nullptr, FL.nslots);
     e = hipGetLastError();
@@ -1869,6 +1953,7 @@ static int temp_table_call(const grpg_model_segment* segments, int num_segments,
 
 int grpg_compose_features(const grpg_model_segment* segments, int num_segments, const float* const* seg_semantic,
                           int S, int normals, const float* cam_pos, float* features, void* hip_stream) {
+  PoseScope poses;
   if (int rc = begin_call()) return rc;
   long long P = 0;
   int F = 0;
@@ -1885,6 +1970,7 @@ int grpg_compose_features(const grpg_model_segment* segments, int num_segments, 
 int grpg_compose_features_backward(const grpg_model_segment* segments, int num_segments, int S, int normals,
                                    const float* cam_pos, const float* dL_dfeatures, float* const* seg_dL_dsemantic,
                                    float* const* seg_dL_drotation, float* dL_dposes, void* hip_stream) {
+  PoseScope poses;
   if (int rc = begin_call()) return rc;
   long long P = 0;
   int F = 0;
@@ -1902,6 +1988,7 @@ int grpg_compose_features_backward(const grpg_model_segment* segments, int num_s
 
 int grpg_compose(const grpg_model_segment* segments, int num_segments, int M, float* means3D,
                  float* scales, float* rotations, float* opacities, float* shs, void* hip_stream) {
+  PoseScope poses;
   if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_segments(segments, num_segments, M, &P)) return rc;

@@ -168,7 +168,7 @@ struct SegmentDev {
   int fourier_dim, rigid;
   float rot[4];
   float trans[3];
-  float pad0;
+  float pad0;                // 0.f; in flight to segment_pose_gather_kernel: the bits of pose_row + 1 (no kernel else reads it)
   float idft[MAX_FOURIER];
 };
 static_assert(sizeof(SegmentDev) % 16 == 0, "segment table entries are read as 16-byte pieces");
@@ -399,6 +399,10 @@ void launch_preprocess_composed(hipStream_t s, int P, int D, int M, const Segmen
                                 bool binned = false /* as launch_preprocess */);
 void launch_compose(hipStream_t s, int P, int M, const SegmentDev* segs, int nseg, float* means3D,
                     float* scales, float* rotations, float* opacities, float* shs);
+// Device poses (segment_pose.hip): a row whose pad0 holds pose_row + 1 > 0 (as bits) gets rot / trans from
+// pose_rot [R,4] / pose_trans [R,3] and pad0 = 0.f; every other byte of the table stays.  One thread per segment.
+void launch_segment_pose_gather(hipStream_t s, SegmentDev* segs, int nseg, const float* pose_rot,
+                                const float* pose_trans);
 void launch_visible_filter(hipStream_t s, int P, const float* means3D, const float* scales,
                            float scale_modifier, const float* rotations,
                            const float* cov3D_precomp, const CameraArgs& cam, int* radii,

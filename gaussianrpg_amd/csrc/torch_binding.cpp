@@ -535,14 +535,49 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
            torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 RasterizeGaussiansBackwardLean(GRPG_BWD_PARAMS) { return RasterizeGaussiansBackwardImpl(GRPG_BWD_ARGS, false); }
 
+// The `poses` argument of the composed family: the host table [n,8] alone (every call from before the device poses),
+// or the tuple (host table, pose_rot [R,4], pose_trans [R,3], pose_row [n]) -- the last three optional in that sense:
+// float32 contiguous tensors on the models' device and a host int32 tensor, -1 = the host table's row holds the pose
+// (grpg_bind_device_poses).  One argument, so all ten functions take it wherever they took the table.
+struct PoseArg {
+  torch::Tensor host, rot, trans, row;   // rot / trans / row undefined: no device poses
+};
+namespace pybind11 {
+namespace detail {
+template <>
+struct type_caster<PoseArg> {
+  PYBIND11_TYPE_CASTER(PoseArg, const_name("Union[Tensor, Tuple[Tensor, Tensor, Tensor, Tensor]]"));
+  bool load(handle src, bool) {
+    if (THPVariable_Check(src.ptr())) {
+      value.host = THPVariable_Unpack(src.ptr());
+      return true;
+    }
+    if (!isinstance<tuple>(src)) return false;
+    const tuple t = reinterpret_borrow<tuple>(src);
+    if (t.size() != 4) return false;
+    torch::Tensor* const dst[4] = {&value.host, &value.rot, &value.trans, &value.row};
+    for (size_t i = 0; i < 4; i++) {
+      const handle h = t[i];
+      if (!THPVariable_Check(h.ptr())) return false;
+      *dst[i] = THPVariable_Unpack(h.ptr());
+    }
+    return true;
+  }
+  static handle cast(const PoseArg& p, return_value_policy, handle) {   // (never returned; the macro wants one)
+    return handle(THPVariable_Wrap(p.host));
+  }
+};
+}  // namespace detail
+}  // namespace pybind11
+
 // the model bundle of the composed family (below): per model one tensor of each raw parameter, the flip masks, and
-// the two host tables
+// the two host tables (the first optionally with the device poses, PoseArg)
 #define GRPG_MODEL_PARAMS                                                                                 \
   const std::vector<torch::Tensor> &xyz, const std::vector<torch::Tensor> &scaling,                         \
       const std::vector<torch::Tensor> &rotation, const std::vector<torch::Tensor> &opacity,                \
       const std::vector<torch::Tensor> &features_dc, const std::vector<torch::Tensor> &features_rest,       \
-      const std::vector<torch::Tensor> &flip, const torch::Tensor &poses, const torch::Tensor &idft
-#define GRPG_MODEL_ARGS xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses, idft
+      const std::vector<torch::Tensor> &flip, const PoseArg &poses_arg, const torch::Tensor &idft
+#define GRPG_MODEL_ARGS xyz, scaling, rotation, opacity, features_dc, features_rest, flip, poses_arg, idft
 
 torch::Tensor markVisible(torch::Tensor& means3D, torch::Tensor& viewmatrix,
                           torch::Tensor& projmatrix) {
@@ -600,7 +635,8 @@ std::tuple<torch::Tensor, torch::Tensor> RasterizeGaussiansFilter(
 // Fused scene-graph composition (additive; include/grpg_rasterizer.h: grpg_forward_composed).
 // Per model one tensor each of the RAW parameters, in the reference's concatenation order
 // (background first, then the visible actors); `poses` is a CPU float tensor [nseg, 8] =
-// (rigid flag, obj_rot w x y z, obj_trans x y z), `idft` a CPU float tensor [nseg, GRPG_MAX_FOURIER].
+// (rigid flag, obj_rot w x y z, obj_trans x y z) -- or that tensor with the device poses behind it (PoseArg) --,
+// `idft` a CPU float tensor [nseg, GRPG_MAX_FOURIER].
 // ----------------------------------------------------------------------------------------------
 namespace {
 
@@ -609,9 +645,17 @@ struct SegmentPack {
   std::vector<torch::Tensor> keep;
   int64_t P = 0;
   int M = 0;
+  // device poses (PoseArg): bound right in front of the C call that consumes them -- nothing that can throw may come
+  // between, or the binding would wait for another call
+  const float *pose_rot = nullptr, *pose_trans = nullptr;
+  const int* pose_row = nullptr;
+  int bind() const {
+    return pose_row ? grpg_bind_device_poses(pose_rot, pose_trans, pose_row, (int)segs.size()) : GRPG_OK;
+  }
 };
 
 SegmentPack pack_segments(GRPG_MODEL_PARAMS) {
+  const torch::Tensor& poses = poses_arg.host;
   const size_t n = xyz.size();
   TORCH_CHECK(flip.size() == n, "one flip mask (or an empty tensor) per model");
   TORCH_CHECK(n > 0 && n <= GRPG_MAX_SEGMENTS, "need 1..", GRPG_MAX_SEGMENTS, " models");
@@ -668,6 +712,30 @@ SegmentPack pack_segments(GRPG_MODEL_PARAMS) {
     for (int q = 0; q < GRPG_MAX_FOURIER; q++) g.idft[q] = ic.data_ptr<float>()[GRPG_MAX_FOURIER * i + q];
     pk.P += cnt;
   }
+  if (poses_arg.row.defined()) {
+    const torch::Tensor &rot = poses_arg.rot, &trans = poses_arg.trans, &row = poses_arg.row;
+    TORCH_CHECK(rot.defined() && trans.defined() && rot.is_cuda() && trans.is_cuda() &&
+                    rot.device() == like.device() && trans.device() == like.device() &&
+                    rot.scalar_type() == torch::kFloat32 && trans.scalar_type() == torch::kFloat32 &&
+                    rot.dim() == 2 && rot.size(1) == 4 && trans.dim() == 2 && trans.size(1) == 3 &&
+                    rot.size(0) == trans.size(0) && rot.is_contiguous() && trans.is_contiguous(),
+                "device poses: pose_rot [R,4] and pose_trans [R,3] must be contiguous float32 tensors on the models' device");
+    TORCH_CHECK(!row.is_cuda() && row.scalar_type() == torch::kInt32 && row.dim() == 1 && row.size(0) == (int64_t)n &&
+                    row.is_contiguous(),
+                "device poses: pose_row must be a contiguous CPU int32 tensor [num_models]");
+    const int* r = row.data_ptr<int>();
+    for (size_t i = 0; i < n; i++) {
+      TORCH_CHECK(r[i] >= -1 && r[i] < rot.size(0), "device poses: pose_row[", i, "] = ", r[i], " is neither -1 nor a row of pose_rot [",
+                  rot.size(0), ",4]");
+      TORCH_CHECK(r[i] < 0 || pk.segs[i].rigid, "device poses: model ", i, " has a pose row but no posed flag");
+    }
+    pk.keep.push_back(rot);
+    pk.keep.push_back(trans);
+    pk.keep.push_back(row);
+    pk.pose_rot = rot.data_ptr<float>();
+    pk.pose_trans = trans.data_ptr<float>();
+    pk.pose_row = r;
+  }
   return pk;
 }
 
@@ -689,6 +757,7 @@ RasterizeGaussiansComposed(const torch::Tensor& background, GRPG_MODEL_PARAMS,
   cam.require(LayerBg::kIfLayered, false);
   ForwardOutputs o(like, pk.P, H, W, c10::nullopt, true, false);
   const int rendered = run("grpg_forward_composed", [&](void* stream) {
+    if (int rc = pk.bind()) return rc;
     return grpg_forward_composed_flags(
         resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, pk.segs.data(), (int)pk.segs.size(),
         degree, pk.M, cam.bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy, o.p_color,
@@ -720,6 +789,7 @@ RasterizeGaussiansComposedLayers(const torch::Tensor& background, const torch::T
   cam.require(LayerBg::kAlways, true);
   ForwardOutputs o(like, pk.P, H, W, c10::nullopt, true, true);
   const int rendered = run("grpg_forward_composed_layers", [&](void* stream) {
+    if (int rc = pk.bind()) return rc;
     return grpg_forward_composed_layers(
         resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, pk.segs.data(), (int)pk.segs.size(),
         p_cls, degree, pk.M, cam.bg, cam.layer_bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx,
@@ -752,6 +822,7 @@ FrameResult RasterizeGaussiansComposedFrame(
   make_epilogue(ea, like, sky_cube, ray_matrix, sky_fill, clamp, want_rgb8, truncate, out_rgb8, H, W);
   ForwardOutputs o(like, pk.P, H, W, c10::nullopt, want_planes, layered);
   const int rendered = run("grpg_forward_composed_frame", [&](void* stream) {
+    if (int rc = pk.bind()) return rc;
     return grpg_forward_composed_frame(
         resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, pk.segs.data(), (int)pk.segs.size(),
         p_cls, degree, pk.M, cam.bg, cam.layer_bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx,
@@ -839,6 +910,7 @@ torch::Tensor ComposeFeatures(GRPG_MODEL_PARAMS,
   TORCH_CHECK(!normals || (p_pos && campos.numel() == 3), "normals need campos (3 floats on the device)");
   torch::Tensor features = torch::empty({pk.P, (int64_t)(3 * (normals ? 1 : 0) + sp.S)}, like.options().dtype(torch::kFloat32));
   hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (int rc = pk.bind()) raise_abi_error("grpg_bind_device_poses", rc);
   const int rc = grpg_compose_features(pk.segs.data(), (int)pk.segs.size(), sp.ptrs.data(), sp.S, normals ? 1 : 0, p_pos,
                                        features.numel() ? features.data_ptr<float>() : nullptr, (void*)stream);
   if (rc != GRPG_OK) raise_abi_error("grpg_compose_features", rc);
@@ -872,6 +944,7 @@ ComposeFeaturesBackward(GRPG_MODEL_PARAMS,
   }
   torch::Tensor dL_dposes = torch::zeros({(int64_t)n, 8}, o);
   hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (int rc = pk.bind()) raise_abi_error("grpg_bind_device_poses", rc);
   const int rc = grpg_compose_features_backward(pk.segs.data(), (int)n, S, normals ? 1 : 0, p_pos, p_g, sem.ptrs.data(),
                                                 p_rot.data(), dL_dposes.data_ptr<float>(), (void*)stream);
   if (rc != GRPG_OK) raise_abi_error("grpg_compose_features_backward", rc);
@@ -899,6 +972,7 @@ RasterizeGaussiansComposedFeatures(const torch::Tensor& background, GRPG_MODEL_P
   ForwardOutputs o(like, pk.P, H, W, F, true, false);
   torch::Tensor feat_blob = torch::empty({0}, like.options().dtype(torch::kByte));
   const int rendered = run("grpg_forward_composed_features", [&](void* stream) {
+    if (int rc = pk.bind()) return rc;
     return grpg_forward_composed_features(
         resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, resize_blob, &feat_blob, pk.segs.data(),
         (int)pk.segs.size(), sp.ptrs.data(), sp.S, normals ? 1 : 0, degree, pk.M, cam.bg, W, H, scale_modifier,
@@ -962,6 +1036,7 @@ static ComposedGrads ComposedBackwardImpl(
                   "the feature blob must be the forward's byte tensor");
       p_blob = reinterpret_cast<char*>((k_blob = featureBuffer.contiguous()).data_ptr());
     }
+    if (int rc = pk.bind()) raise_abi_error("grpg_bind_device_poses", rc);
     const int rc = grpg_backward_composed_objects(
         pk.segs.data(), mg.table.data(), n, sem.ptrs.data(), S, normals ? 1 : 0, degree, pk.M, R, cam.bg, W, H,
         scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img,
@@ -970,6 +1045,7 @@ static ComposedGrads ComposedBackwardImpl(
         p_dobj, debug ? 1 : 0, (void*)stream);
     if (rc != GRPG_OK) raise_abi_error("grpg_backward_composed_objects", rc);
   } else if (F == 0) {
+    if (int rc = pk.bind()) raise_abi_error("grpg_bind_device_poses", rc);
     const int rc = grpg_backward_composed(
         pk.segs.data(), mg.table.data(), n, degree, pk.M, R, cam.bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos,
         tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img, sv.dcolor, sv.ddepth, sv.dalpha,
@@ -980,6 +1056,7 @@ static ComposedGrads ComposedBackwardImpl(
     TORCH_CHECK(featureBuffer.scalar_type() == torch::kByte && featureBuffer.device() == like.device(),
                 "the feature blob must be the forward's byte tensor");
     const torch::Tensor k_blob = featureBuffer.contiguous();
+    if (int rc = pk.bind()) raise_abi_error("grpg_bind_device_poses", rc);
     const int rc = grpg_backward_composed_features(
         pk.segs.data(), mg.table.data(), n, sem.ptrs.data(), S, normals ? 1 : 0, degree, pk.M, R, cam.bg, W, H,
         scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy, sv.radii, p_alpha, sv.geom, sv.binning, sv.img,
@@ -1065,6 +1142,7 @@ Compose(GRPG_MODEL_PARAMS) {
                 rots = torch::empty({pk.P, 4}, o), opac = torch::empty({pk.P, 1}, o),
                 shs = torch::empty({pk.P, pk.M, 3}, o);
   hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (int rc = pk.bind()) raise_abi_error("grpg_bind_device_poses", rc);
   const int rc = grpg_compose(pk.segs.data(), (int)pk.segs.size(), pk.M, means.data_ptr<float>(),
                               scales.data_ptr<float>(), rots.data_ptr<float>(), opac.data_ptr<float>(),
                               shs.data_ptr<float>(), (void*)stream);

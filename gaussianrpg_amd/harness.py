@@ -640,6 +640,40 @@ def parse_camera_poses(actors, timestamp: float, ego_pose: torch.Tensor, num_gau
     return visible, ranges, torch.stack(rots), torch.stack(trans)
 
 
+def tracked_poses(actors, timestamp: float, ego_pose: torch.Tensor, visible, fourier_times=None, *,
+                  device_poses: bool = True, static: int = 1):
+    """Tracklets -> the pose argument of a composed frame: ``actors.poses`` (one launch), then
+      device_poses=True   ``PoseBatch.rows`` -> ``composed.PoseTable``: no launch, no copy; the library takes the rows
+                          from device memory on the frame's stream (C ABI ``grpg_bind_device_poses``)
+      device_poses=False  ``PoseBatch.frame`` -> ``composed.PoseRows``: four small launches, and one device-to-host
+                          copy when the entry point packs them
+    Both give the same frame, bit for bit (tests/test_gpu_device_poses.py)."""
+    batch = actors.poses(timestamp, ego_pose)
+    return (batch.rows if device_poses else batch.frame)(0, visible, fourier_times, static=static)
+
+
+def tracked_simulator_frame(rast, models, actors, timestamp: float, ego_pose: torch.Tensor, visible, fourier_times=None,
+                            *, device_poses: bool = True, **frame_kw) -> dict:
+    """Actor poses -> simulator frame: the closed loop's per-frame call on tracked actors --
+    ``ComposedRasterizer.forward_frame`` (composition, op, sky, clamp, bytes) on the poses of ``tracked_poses``.
+    ``models``: the background, then the visible actors' models."""
+    with torch.no_grad():
+        poses = tracked_poses(actors, timestamp, ego_pose, visible, fourier_times, device_poses=device_poses)
+        return rast.forward_frame(models, poses, **frame_kw)
+
+
+def tracked_train_step(rast, models, actors, timestamp: float, ego_pose: torch.Tensor, visible, fourier_times=None, *,
+                       device_poses: bool = True, weights=None, means2D=None):
+    """Actor poses -> train step: the forward + backward of one training iteration with ``opt_track`` -- the composed
+    training forward on the tracked poses and a backward that reaches the models' raw parameters and ``opt_trans`` /
+    ``opt_rots``.  The loss is a weighted sum of the colour plane (``weights [3,H,W]``, default ones): the caller's
+    losses are not what this measures.  Returns the detached colour plane."""
+    poses = tracked_poses(actors, timestamp, ego_pose, visible, fourier_times, device_poses=device_poses)
+    color = rast.forward(models, poses, means2D=means2D)[0]
+    (color.sum() if weights is None else (color * weights).sum()).backward()
+    return color.detach()
+
+
 def train_loss(render_pkg: dict, gt_image: torch.Tensor, lidar_depth: Optional[torch.Tensor] = None,
                sky_mask: Optional[torch.Tensor] = None, lambda_l1: float = 1.0,
                lambda_depth_lidar: float = 0.1, lambda_sky: float = 0.05, *, lambda_dssim: float = 0.0,

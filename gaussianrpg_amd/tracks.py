@@ -11,8 +11,12 @@ launches and four host waits per actor.  Here the same arithmetic is ONE launch 
     table  = TrackTable.from_tracklets(tracklets, tracklet_timestamps, obj_info)      # once per scene
     actors = TrackedActorPoses(table, camera_timestamps=camera_timestamps)             # opt_trans / opt_rots
     batch  = actors.poses(camera.meta['timestamp'], camera.ego_pose, is_val=..., cam=...)
-    rows   = batch.frame(0, visible_actor_indices, fourier_times)                      # -> composed.PoseRows
+    rows   = batch.rows(0, visible_actor_indices, fourier_times)                       # -> composed.PoseTable
     color, radii, depth, alpha = ComposedRasterizer(settings)(models, rows)
+
+``batch.rows`` leaves the poses on the device: the library's segment table takes them from there, on the stream of the
+rendering call (C ABI ``grpg_bind_device_poses``).  ``batch.frame`` (-> ``composed.PoseRows``) is the older hand-over
+through the host -- four small launches and one device-to-host copy -- and gives the same bits.
 
 The slerp is the geodesic on the shortest arc as DESIGN.md section 21 defines it -- what
 ``roma.utils.unitquat_slerp(shortest_arc=True)`` computes in real arithmetic; roma's float32 bits are not pinned.
@@ -23,7 +27,7 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
-from .composed import PoseRows
+from .composed import PoseRows, PoseTable
 from .rasterizer import _C
 
 
@@ -146,6 +150,23 @@ class PoseBatch(NamedTuple):
         rot = torch.nn.functional.pad(self.rot[t], (0, 0, 1, 0)).index_select(0, index)
         trans = torch.nn.functional.pad(self.trans[t], (0, 0, 1, 0)).index_select(0, index)
         return PoseRows(rot, trans, [False] * static + [True] * n, [0.0] * static + times)
+
+    def rows(self, t: int, actors: Sequence[int], fourier_time: Optional[Sequence[float]] = None, static: int = 1):
+        """``frame`` without its launches and without the host copy behind it: the same frame as a
+        ``composed.PoseTable`` -- the batch's own ``rot[t]`` / ``trans[t]`` (views; they keep their graph) and, per
+        model, the row it reads: -1 for the ``static`` leading models, the actor's index for the others.  No launch,
+        no copy; the library takes the rows from device memory on the stream of the call that renders the frame."""
+        n = len(actors)
+        times = [0.0] * n if fourier_time is None else [float(x) for x in fourier_time]
+        if len(times) != n:
+            raise ValueError("one fourier_time per actor (%d for %d actors)" % (len(times), n))
+        A = int(self.rot.shape[1])
+        index = [int(a) for a in actors]
+        for a in index:
+            if a < 0 or a >= A:
+                raise IndexError("actor %d is not one of the batch's %d actors" % (a, A))
+        return PoseTable(self.rot[t], self.trans[t], [-1] * static + index, [False] * static + [True] * n,
+                         [0.0] * static + times)
 
 
 class _TrackPoses(torch.autograd.Function):

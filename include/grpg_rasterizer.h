@@ -528,6 +528,38 @@ GRPG_API int grpg_backward_composed_objects(const grpg_model_segment* segments,
                  int debug, void* hip_stream);
 
 /*
+ * Actor poses from DEVICE memory (additive; ABI 7 unchanged: grpg_model_segment and every entry point above as they
+ * were).  A composed call copies obj_rot / obj_trans of its HOST segment array into the device segment table.  When
+ * the poses are computed on the device (grpg_track_poses_forward), reading them back only to hand them in again is a
+ * host wait in front of the frame.  grpg_bind_device_poses binds, for the NEXT call on this thread that takes a
+ * grpg_model_segment* -- grpg_forward_composed{,_flags,_layers,_frame,_features}, grpg_backward_composed{,_features,
+ * _objects}, grpg_compose, grpg_compose_features{,_backward} --
+ *   pose_rot   device fp32, rows of 4 (w,x,y,z), ego pose applied
+ *   pose_trans device fp32, rows of 3
+ *   pose_row   HOST int32 [num_segments] (copied by the call): the row of segment i, or -1 = keep the obj_rot /
+ *              obj_trans of segments[i] (a static model, or an actor posed by the host)
+ * That call uploads its table as always and, right behind the copy on its stream, a one-thread-per-segment kernel
+ * overwrites the pose fields of the bound rows with pose_rot[pose_row[i]] / pose_trans[pose_row[i]] -- loads and
+ * stores, no arithmetic: every output is bit for bit what the same values in obj_rot / obj_trans give.  obj_rot /
+ * obj_trans of a bound segment are not looked at; `rigid` must be 1.  A backward needs the binding its forward had,
+ * bound again: it rebuilds the table.
+ * The binding is consumed by exactly that one call and is gone when it returns, whether it succeeds or fails (without
+ * a device: GRPG_ERR_NO_DEVICE, binding gone).  The consuming call returns GRPG_ERR_INVALID_ARGUMENT if its
+ * num_segments differs from the binding's or a pose_row >= 0 names a segment with rigid == 0.  Binding again before
+ * a consuming call replaces the pending binding.  Per thread, like the capacity hints' staging and the binning mode.
+ * Lifetime: pose_rot / pose_trans must stay valid, and their contents unchanged, until the consuming call's work on
+ * its stream has run -- the rule the model parameter arrays follow; written by earlier work on the same stream is
+ * fine (stream order).  Row indices are not range-checked against the arrays: the caller knows their length.
+ * grpg_bind_device_poses itself touches no device: GRPG_OK, or GRPG_ERR_INVALID_ARGUMENT for num_segments outside
+ * 1..GRPG_MAX_SEGMENTS, a NULL pose_row, an entry below -1 (or >= 2^28), or NULL arrays with a row bound -- a
+ * refused bind leaves no binding.
+ */
+GRPG_API int grpg_bind_device_poses(const float* pose_rot, const float* pose_trans, const int* pose_row,
+                 int num_segments);
+/* 1 while a binding waits on this thread for its consuming call, 0 otherwise (a pure query: no device needed). */
+GRPG_API int grpg_device_poses_bound(void);
+
+/*
  * Sky cube map without nvdiffrast (additive).  Replaces
  * SkyCubeMap.forward (lib/models/sky_cubemap.py:77-122: get_rays_torch + mask + dr.texture(...,
  * filter_mode='linear', boundary_mode='cube') + clamp) and the composite of
