@@ -46,6 +46,9 @@ HIP_UNITS = {
     "knn.hip": ["-ffp-contract=off"],
     # hardware float atomics for the cube-map gradient
     "sky.hip": ["-munsafe-fp-atomics"],
+    # colour correction of the frame behind the sky composite: the affine map and A^T g are explicit fmaf chains, the
+    # gradient terms single products (no FMA contraction); no atomics, deterministic fixed-order reduction
+    "color_correction.hip": ["-ffp-contract=off"],
     # fused SSIM + L1 loss: no atomics, deterministic fixed-order reduction
     "ssim.hip": [],
     # fused lidar / sky / object-alpha losses: the error plane bit-identical to PyTorch's float32

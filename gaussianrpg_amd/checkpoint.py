@@ -97,8 +97,28 @@ def _model_from_ply_element(el: np.ndarray) -> Dict[str, torch.Tensor]:
 class LoadedScene:
     """Raw per-model parameters of a checkpoint, in file order."""
 
-    def __init__(self, models: "OrderedDict[str, Dict[str, torch.Tensor]]", source: str):
+    def __init__(self, models: "OrderedDict[str, Dict[str, torch.Tensor]]", source: str,
+                 color_correction: "Optional[Dict[str, torch.Tensor]]" = None):
         self.models, self.source = models, source
+        # the parameters of the file's ``color_correction`` entry (StreetGaussianModel.save_state_dict with
+        # use_color_correction: true), or None: the scene renders with the wrong colours without them
+        self.color_correction = color_correction
+
+    def color_correction_module(self, mode: str = "image", device="cpu"):
+        """The file's colour correction as a ``gaussianrpg_amd.appearance.ColorCorrection`` on ``device``, or None when
+        the file has none.  ``mode`` is the reference's ``cfg.model.color_correction.mode`` (the file does not record
+        it).  A file written with ``use_mlp: true`` raises: its layers are not constructed here."""
+        if self.color_correction is None:
+            return None
+        from .appearance import ColorCorrection
+        p = self.color_correction
+        if "affine_trans" not in p or "affine_trans_sky" not in p or p["affine_trans"].dim() != 3:
+            raise ValueError("%s: the color_correction entry is the use_mlp variant (keys %s ...); only the explicit "
+                             "[N,3,4] matrices are supported (gaussianrpg_amd.appearance)"
+                             % (self.source, sorted(p)[:2]))
+        cc = ColorCorrection(int(p["affine_trans"].shape[0]), mode=mode)
+        cc.load_state_dict({"params": p})
+        return cc.to(device)
 
     def names(self):
         return list(self.models)
@@ -126,16 +146,21 @@ class LoadedScene:
 _MODEL_KEYS = ("xyz", "feature_dc", "feature_rest", "scaling", "rotation", "opacity")
 
 
-def load_checkpoint(path: str, allow_unsafe: bool = False) -> LoadedScene:
+def load_checkpoint(path: str, allow_unsafe: bool = False, color_correction: bool = True) -> LoadedScene:
     """``.pth`` (StreetGaussianModel.save_state_dict, or a bare GaussianModel.state_dict) or ``.ply``
     (one ``vertex_<model>`` element per model, or a single ``vertex`` element) -> LoadedScene.
 
     A ``.pth`` is read with ``torch.load(weights_only=True)``.  A non-final checkpoint of the
     reference (optimizer state, bidict objects) needs the full unpickler, which EXECUTES code found
     in the file: that is only done when the caller says the file is trusted (``allow_unsafe=True``,
-    ``bench.py --trust-checkpoint``), never as a silent fallback."""
+    ``bench.py --trust-checkpoint``), never as a silent fallback.
+
+    A ``.pth`` written with ``use_color_correction: true`` carries a ``color_correction`` entry
+    (street_gaussian_model.py:153-154): its parameters are kept as ``LoadedScene.color_correction`` (None when the
+    file has none, for a ``.ply``, or with ``color_correction=False``)."""
     ext = os.path.splitext(path)[1].lower()
     models = OrderedDict()
+    cc_params = None
     if ext == ".ply":
         for name, el in read_ply(path).items():
             if not name.startswith("vertex") or "opacity" not in (el.dtype.names or ()):
@@ -156,6 +181,9 @@ def load_checkpoint(path: str, allow_unsafe: bool = False) -> LoadedScene:
             sd = torch.load(path, map_location="cpu", weights_only=False)
         if all(k in sd for k in _MODEL_KEYS):
             sd = {"background": sd}
+        cc = sd.get("color_correction")
+        if color_correction and isinstance(cc, dict) and isinstance(cc.get("params"), dict):
+            cc_params = OrderedDict((k, torch.as_tensor(v).detach().float()) for k, v in cc["params"].items())
         for name, m in sd.items():
             if isinstance(m, dict) and all(k in m for k in _MODEL_KEYS):
                 entry = {k: torch.as_tensor(m[k]).detach().float() for k in _MODEL_KEYS}
@@ -175,7 +203,7 @@ def load_checkpoint(path: str, allow_unsafe: bool = False) -> LoadedScene:
             raise ValueError("%s.feature_dc has shape %s, expected [N,F,3]" % (name, tuple(m["feature_dc"].shape)))
         if m["feature_rest"].dim() != 3 or m["feature_rest"].shape[0] != n or m["feature_rest"].shape[2] != 3:
             raise ValueError("%s.feature_rest has shape %s, expected [N,M-1,3]" % (name, tuple(m["feature_rest"].shape)))
-    return LoadedScene(models, path)
+    return LoadedScene(models, path, cc_params)
 
 
 def activated_scene(loaded: LoadedScene, names: Optional[Sequence[str]] = None):

@@ -1,5 +1,5 @@
 // The fixed-order sums behind "identical calls give identical bits" of the fused losses (ssim.hip, aux_loss.hip,
-// semantic_loss.hip, normal_loss.hip, reg_loss.hip, metrics.hip); device code only.  A loss kernel sums its lanes with block_sum into one slot per workgroup; a
+// semantic_loss.hip, normal_loss.hip, reg_loss.hip, metrics.hip) and of color_correction.hip's matrix gradient; device code only.  A loss kernel sums its lanes with block_sum into one slot per workgroup; a
 // launch of one workgroup of REDUCE_THREADS then adds the slots with slot_sum.  No atomics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +19,27 @@ __device__ __forceinline__ A block_sum(T v, A* s_red) {
   A t = 0;
   if (threadIdx.x == 0)
     for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += s_red[w];
+  __syncthreads();
+  return t;
+}
+
+// N sums over the lanes of the workgroup at once (color_correction.hip: the twelve sums of the matrix gradient): the
+// butterfly of block_sum on each v[k], one LDS slot per value and wave, and thread k adds the waves of value k in
+// ascending order.  One pair of barriers for all N.  Valid on threads 0 .. N-1: thread k returns sum k.
+// s_red: N * (blockDim.x / 64) slots; blockDim.x >= N.
+template <int N>
+__device__ __forceinline__ float block_sum_each(float (&v)[N], float* s_red) {
+  const int nw = (int)(blockDim.x >> 6);
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d, 64);
+    if ((threadIdx.x & 63) == 0) s_red[k * nw + (threadIdx.x >> 6)] = v[k];
+  }
+  __syncthreads();
+  float t = 0.f;
+  if ((int)threadIdx.x < N)
+    for (int w = 0; w < nw; w++) t += s_red[threadIdx.x * nw + w];
   __syncthreads();
   return t;
 }

@@ -1325,6 +1325,120 @@ torch::Tensor PackHWC(const torch::Tensor& color, const bool truncate) {
   return out;
 }
 
+// ---- colour correction of the frame (gaussianrpg_amd/appearance.py; csrc/color_correction.hip) ----
+namespace {
+using OptTensor = c10::optional<torch::Tensor>;
+
+bool given(const OptTensor& t) { return t.has_value() && t->defined(); }
+
+// rgb: float32 device [3,H,W]; affine: float32 [3,4] on the same device (a view of the parameter is taken as it is);
+// the sky inputs (cube, ray_matrix, acc) all or none, mask / jitter only with them.
+struct ColorCorrectIn {
+  torch::Tensor rgb, affine, cube, rm, acc, mask, jit;   // contiguous
+  int H = 0, W = 0, res = 0, rm_dev = 0;
+  const float *p_cube = nullptr, *p_rm = nullptr, *p_acc = nullptr, *p_jit = nullptr;
+  const unsigned char* p_mask = nullptr;
+};
+
+ColorCorrectIn color_correct_args(const torch::Tensor& rgb, const torch::Tensor& affine, const OptTensor& cube,
+                                  const OptTensor& ray_matrix, const OptTensor& acc, const OptTensor& mask,
+                                  const OptTensor& jitter) {
+  TORCH_CHECK(rgb.is_cuda(), "color_correct: the image must live on a ROCm/HIP device (no CPU path)");
+  TORCH_CHECK(rgb.scalar_type() == torch::kFloat32 && rgb.dim() == 3 && rgb.size(0) == 3 && rgb.numel() > 0,
+              "color_correct: the image must be a float32 tensor [3,H,W]");
+  TORCH_CHECK(affine.device() == rgb.device() && affine.scalar_type() == torch::kFloat32 && affine.dim() == 2 &&
+                  affine.size(0) == 3 && affine.size(1) == 4,
+              "color_correct: affine must be a float32 tensor [3,4] on the image's device");
+  ColorCorrectIn in;
+  in.rgb = rgb.contiguous();
+  in.affine = affine.contiguous();
+  in.H = in.rgb.size(1);
+  in.W = in.rgb.size(2);
+  if (!given(cube)) {
+    TORCH_CHECK(!given(ray_matrix) && !given(acc) && !given(mask) && !given(jitter),
+                "color_correct: ray_matrix / acc / mask / jitter need the sky cube map");
+    return in;
+  }
+  TORCH_CHECK(given(ray_matrix) && given(acc), "color_correct: the sky inputs (cube, ray_matrix, acc) go together");
+  TORCH_CHECK(cube->device() == rgb.device() && cube->scalar_type() == torch::kFloat32 && cube->dim() == 4 &&
+                  cube->size(0) == 6 && cube->size(1) == cube->size(2) && cube->size(3) == 3,
+              "sky cube map must be a float32 device tensor [6,res,res,3]");
+  check_ray_matrix(*ray_matrix, *cube);
+  TORCH_CHECK(acc->device() == rgb.device() && acc->scalar_type() == torch::kFloat32 &&
+                  acc->numel() == (int64_t)in.H * in.W, "acc must be a float32 device tensor [1,H,W]");
+  in.cube = cube->contiguous();
+  in.rm = ray_matrix->contiguous();
+  in.acc = acc->contiguous();
+  in.res = in.cube.size(1);
+  in.rm_dev = in.rm.is_cuda() ? 1 : 0;
+  in.p_cube = in.cube.data_ptr<float>();
+  in.p_rm = in.rm.data_ptr<float>();
+  in.p_acc = in.acc.data_ptr<float>();
+  in.p_mask = sky_mask_ptr(mask, in.mask, in.H, in.W);
+  in.p_jit = sky_jitter_ptr(jitter, in.jit, in.H, in.W);
+  return in;
+}
+}  // namespace
+
+// (planes [3,H,W] or undefined, rgb8 [H,W,3] or undefined).  out: optional preallocated uint8 [H,W,3] for the bytes.
+std::tuple<torch::Tensor, torch::Tensor> ColorCorrect(
+    const torch::Tensor& rgb, const torch::Tensor& affine, const bool clamp, const bool planes, const bool rgb8,
+    const bool truncate, const OptTensor& out_opt, const OptTensor& cube, const OptTensor& ray_matrix,
+    const double fill, const OptTensor& acc, const OptTensor& mask, const OptTensor& jitter) {
+  const ColorCorrectIn in = color_correct_args(rgb, affine, cube, ray_matrix, acc, mask, jitter);
+  TORCH_CHECK(planes || rgb8, "color_correct: ask for the float planes, the rgb8 frame, or both");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.rgb.device());
+  torch::Tensor out_planes, out_rgb8;
+  if (planes) out_planes = torch::empty_like(in.rgb);
+  if (rgb8) {
+    if (given(out_opt)) {
+      out_rgb8 = *out_opt;
+      TORCH_CHECK(out_rgb8.device() == in.rgb.device() && out_rgb8.scalar_type() == torch::kUInt8 &&
+                      out_rgb8.is_contiguous() && out_rgb8.dim() == 3 && out_rgb8.size(0) == in.H &&
+                      out_rgb8.size(1) == in.W && out_rgb8.size(2) == 3,
+                  "color_correct: out must be a contiguous uint8 tensor [H,W,3] on the image's device");
+    } else {
+      out_rgb8 = torch::empty({in.H, in.W, 3}, in.rgb.options().dtype(torch::kUInt8));
+    }
+  }
+  run("grpg_color_correct_forward", [&](void* stream) {
+    return grpg_color_correct_forward(in.W, in.H, in.rgb.data_ptr<float>(), in.affine.data_ptr<float>(), in.p_cube,
+                                      in.res, in.p_rm, in.rm_dev, (float)fill, in.p_acc, in.p_mask, in.p_jit,
+                                      clamp ? 1 : 0, planes ? out_planes.data_ptr<float>() : nullptr,
+                                      rgb8 ? out_rgb8.data_ptr<uint8_t>() : nullptr, truncate ? 1 : 0, stream);
+  });
+  return std::make_tuple(out_planes, out_rgb8);
+}
+
+// (grad_x [3,H,W] = A^T grad or undefined, grad_affine [3,4] or undefined)
+std::tuple<torch::Tensor, torch::Tensor> ColorCorrectBackward(
+    const torch::Tensor& rgb, const torch::Tensor& affine, const torch::Tensor& grad, const bool need_x,
+    const bool need_affine, const OptTensor& cube, const OptTensor& ray_matrix, const double fill,
+    const OptTensor& acc, const OptTensor& mask, const OptTensor& jitter) {
+  const ColorCorrectIn in = color_correct_args(rgb, affine, cube, ray_matrix, acc, mask, jitter);
+  TORCH_CHECK(grad.device() == in.rgb.device() && grad.scalar_type() == torch::kFloat32 &&
+                  grad.sizes() == in.rgb.sizes(),
+              "color_correct_backward: the gradient must be a float32 tensor [3,H,W] on the image's device");
+  TORCH_CHECK(need_x || need_affine, "color_correct_backward: ask for the image gradient, the matrix gradient, or both");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.rgb.device());
+  const torch::Tensor g = grad.contiguous();
+  torch::Tensor grad_x, grad_affine, ws;
+  if (need_x) grad_x = torch::empty_like(in.rgb);
+  if (need_affine) {
+    grad_affine = torch::empty({3, 4}, in.rgb.options());
+    ws = torch::empty({(long long)grpg_color_correct_workspace_bytes(in.W, in.H)},
+                      in.rgb.options().dtype(torch::kByte));
+  }
+  run("grpg_color_correct_backward", [&](void* stream) {
+    return grpg_color_correct_backward(in.W, in.H, in.rgb.data_ptr<float>(), in.affine.data_ptr<float>(), in.p_cube,
+                                       in.res, in.p_rm, in.rm_dev, (float)fill, in.p_acc, in.p_mask, in.p_jit,
+                                       g.data_ptr<float>(), need_x ? grad_x.data_ptr<float>() : nullptr,
+                                       need_affine ? grad_affine.data_ptr<float>() : nullptr,
+                                       need_affine ? ws.data_ptr() : nullptr, stream);
+  });
+  return std::make_tuple(grad_x, grad_affine);
+}
+
 // ---- frame -> detector input (gaussianrpg_amd/perception.py; csrc/letterbox.hip) ----
 
 // letterbox()'s arithmetic (utils/augmentations.py:121-151); host only.
@@ -2514,6 +2628,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("mask") = pybind11::none(), pybind11::arg("jitter") = pybind11::none());
   m.def("pack_u8", &PackU8, pybind11::arg("color"), pybind11::arg("out") = pybind11::none());
   m.def("pack_hwc", &PackHWC);
+  // colour correction of the frame (appearance.py): (planes, rgb8) / (grad_x, grad_affine)
+  m.def("color_correct", &ColorCorrect, pybind11::arg("rgb"), pybind11::arg("affine"), pybind11::arg("clamp") = false,
+        pybind11::arg("planes") = true, pybind11::arg("rgb8") = false, pybind11::arg("truncate") = true,
+        pybind11::arg("out") = pybind11::none(), pybind11::arg("cube") = pybind11::none(),
+        pybind11::arg("ray_matrix") = pybind11::none(), pybind11::arg("fill") = 0.0,
+        pybind11::arg("acc") = pybind11::none(), pybind11::arg("mask") = pybind11::none(),
+        pybind11::arg("jitter") = pybind11::none());
+  m.def("color_correct_backward", &ColorCorrectBackward, pybind11::arg("rgb"), pybind11::arg("affine"),
+        pybind11::arg("grad"), pybind11::arg("need_x") = true, pybind11::arg("need_affine") = true,
+        pybind11::arg("cube") = pybind11::none(), pybind11::arg("ray_matrix") = pybind11::none(),
+        pybind11::arg("fill") = 0.0, pybind11::arg("acc") = pybind11::none(), pybind11::arg("mask") = pybind11::none(),
+        pybind11::arg("jitter") = pybind11::none());
+  m.def("color_correct_workspace_bytes", [](int H, int W) { return grpg_color_correct_workspace_bytes(W, H); });
   // frame -> detector input (perception.py)
   m.def("letterbox_geometry", &LetterboxGeometry, pybind11::arg("height"), pybind11::arg("width"),
         pybind11::arg("new_h_req"), pybind11::arg("new_w_req"), pybind11::arg("auto_pad") = true,

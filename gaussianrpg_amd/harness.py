@@ -359,6 +359,51 @@ def simulator_frame(scene: Scene, cam: CameraTensors, sky=None, K=None, w2c=None
         return out.numpy()
 
 
+def render_corrected(rgb: torch.Tensor, acc: torch.Tensor, affine: torch.Tensor, sky=None, K=None, w2c=None, *,
+                     train: bool = False, fused: bool = True, mask=None, jitter=None) -> torch.Tensor:
+    """The three per-pixel steps behind the op in StreetGaussianRenderer.render (street_gaussian_renderer.py:105-116)
+    for a scene with colour correction, on the op's planes: ``rgb + sky * (1 - acc)``, ``pc.color_correction(camera,
+    rgb)`` (color_correction.py:131) with the camera's matrix ``affine`` [3,4], and outside train mode the clamp.
+      fused=False  the reference's pattern: SkyCubeMap.composite (unclamped) -> the einsum line -> clamp
+      fused=True   one launch (appearance.sky_corrected / color_correct)
+    sky: a gaussianrpg_amd.sky.SkyCubeMap with K / w2c, or None (no composite).  Differentiable when train=True."""
+    from . import appearance
+    if fused:
+        if sky is None:
+            return appearance.color_correct(rgb, affine, clamp=not train)
+        return appearance.sky_corrected(sky, rgb, acc, affine, K=K, w2c=w2c, train=train, mask=mask, jitter=jitter)
+    with torch.enable_grad() if train else torch.no_grad():
+        x = rgb if sky is None else sky.composite(rgb, acc, K, w2c, train=True, mask=mask, jitter=jitter)
+        y = torch.einsum('ij, jhw -> ihw', affine[:3, :3], x) + affine[:3, 3].unsqueeze(-1).unsqueeze(-1)
+        return y if train else torch.clamp(y, 0.0, 1.0)
+
+
+def simulator_frame_corrected(scene: Scene, cam: CameraTensors, affine: torch.Tensor, sky=None, K=None, w2c=None, *,
+                              fused: bool = True, truncate: bool = True) -> np.ndarray:
+    """simulator_frame for a scene trained with colour correction: the op's evaluation planes
+    (``forward_frame(planes=True, rgb8=False, sky_cube=None, clamp=True)`` -- its own epilogue would clamp and convert
+    before the correction could be applied), then composite, correction, clamp and bytes.
+      fused=False  render_corrected(fused=False) -> trajectory.pack_hwc: four steps and their temporaries
+      fused=True   appearance.corrected_frame: one launch, the float planes are not written
+    Returns the uint8 [H,W,3] host image."""
+    from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+    from . import appearance
+    from .trajectory import pack_hwc
+    dev = cam.viewmatrix.device
+    rast = GaussianRasterizer(GaussianRasterizationSettings(**settings_kwargs(cam, scene.sh_degree,
+                                                                              bg=torch.zeros(3, device=dev))))
+    with torch.no_grad():
+        o = rast.forward_frame(scene.means3D, scene.opacity, shs=scene.shs, scales=scene.scales,
+                               rotations=scene.rotations, planes=True, rgb8=False, sky_cube=None, clamp=True)
+        if sky is not None:
+            K, w2c = K.to(dev), w2c.to(dev)
+        if fused:
+            frame = appearance.corrected_frame(o["rgb"], o["alpha"], affine, sky=sky, K=K, w2c=w2c, truncate=truncate)
+        else:
+            frame = pack_hwc(render_corrected(o["rgb"], o["alpha"], affine, sky, K, w2c, fused=False), truncate)
+        return frame.cpu().numpy()
+
+
 def simulator_perception_frame(scene: Scene, cam: CameraTensors, plan, sky=None, K=None, w2c=None, *,
                                fused: bool = True) -> torch.Tensor:
     """The simulator node's per-frame work in its in-process perception mode (``separate_perception = False``,

@@ -606,6 +606,43 @@ GRPG_API int grpg_sky_backward_ex(const float* cube, int res, const float* ray_m
                                   const float* grad_rgb, float* grad_cube, float* grad_acc,
                                   void* hip_stream);
 
+/* ---- colour correction of the frame (additive; csrc/color_correction.hip) ----
+ * ColorCorrection.forward (lib/models/color_correction.py:129-132) -- the per-pixel affine map between the sky
+ * composite and the evaluation clamp of StreetGaussianRenderer.render (street_gaussian_renderer.py:105-116):
+ *     x   = rgb                                  without the sky inputs
+ *     x   = rgb + clamp(sky, 0, 1) * (1 - acc)   with them: grpg_sky_composite_ex's value (clamp_out = 0), bit for bit
+ *     y_i = A_i0 x_0 + A_i1 x_1 + A_i2 x_2 + A_i3,  clamped to [0,1] when clamp_out != 0
+ *   rgb         device [3,H,W]
+ *   affine      DEVICE float[12], row-major [3,4] (e.g. a view affine_trans[id] of the parameter): never read by the host
+ *   sky inputs  sky_cube [6,res,res,3], sky_res, ray_matrix (+ ray_matrix_on_device), acc [H,W]: all of them or none
+ *               (NULL / 0); sky_fill, sky_mask and sky_jitter as in grpg_sky_composite_ex, only with the sky inputs
+ *   out_planes  optional device [3,H,W]; may be rgb itself (in place)
+ *   out_rgb8    optional device uint8 [H,W,3]: grpg_pack_rgb_u8_hwc's byte of the clamped value (truncate != 0:
+ *               (unsigned char)(v * 255), else + 0.5); at least one of the two outputs
+ * grpg_color_correct_backward: grad_out [3,H,W] is dL/dy of the UNclamped map; x is recomputed from the same inputs.
+ *   grad_x      optional device [3,H,W] = A^T grad_out (dL/drgb; with the sky inputs hand it to grpg_sky_backward_ex
+ *               for the cube-map and acc gradients)
+ *   grad_affine optional device float[12], overwritten: [i][j] = sum over pixels of grad_out_i * x_j, [i][3] = sum of
+ *               grad_out_i; fixed-order sums without atomics (identical calls give identical bits; the add order is in
+ *               the .hip file's header); needs workspace: device, 4-byte aligned,
+ *               grpg_color_correct_workspace_bytes(width, height) bytes (a pure size query: no device needed, 0 for
+ *               sizes <= 0); at least one of the two outputs
+ * Both run asynchronously on hip_stream.  Purely additive exports: GRPG_ABI_VERSION stays 7.  Returns GRPG_OK,
+ * GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT for a NULL rgb / affine / grad_out, no output at all,
+ * sizes <= 0, sky inputs given in part, or grad_affine without a workspace. */
+GRPG_API size_t grpg_color_correct_workspace_bytes(int width, int height);
+GRPG_API int grpg_color_correct_forward(int width, int height, const float* rgb, const float* affine,
+                                        const float* sky_cube, int sky_res, const float* ray_matrix,
+                                        int ray_matrix_on_device, float sky_fill, const float* acc,
+                                        const unsigned char* sky_mask, const float* sky_jitter, int clamp_out,
+                                        float* out_planes, unsigned char* out_rgb8, int truncate, void* hip_stream);
+GRPG_API int grpg_color_correct_backward(int width, int height, const float* rgb, const float* affine,
+                                         const float* sky_cube, int sky_res, const float* ray_matrix,
+                                         int ray_matrix_on_device, float sky_fill, const float* acc,
+                                         const unsigned char* sky_mask, const float* sky_jitter,
+                                         const float* grad_out, float* grad_x, float* grad_affine, void* workspace,
+                                         void* hip_stream);
+
 /* Binning-blob sizing policy of grpg_forward (process-wide; see above).  The environment variable
  * GRPG_SYNC_R=1 selects GRPG_BINNING_EXACT at load time. */
 #define GRPG_BINNING_SPECULATIVE 0
