@@ -49,6 +49,10 @@ HIP_UNITS = {
     # colour correction of the frame behind the sky composite: the affine map and A^T g are explicit fmaf chains, the
     # gradient terms single products (no FMA contraction); no atomics, deterministic fixed-order reduction
     "color_correction.hip": ["-ffp-contract=off"],
+    # pose correction of the background: every step the single float32 operation of the numpy restatement
+    # (tests/pose_correction_truth.py), divisions and square roots correctly rounded; no atomics, deterministic
+    # fixed-order reduction of the row's gradient
+    "pose_correction.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # fused SSIM + L1 loss: no atomics, deterministic fixed-order reduction
     "ssim.hip": [],
     # fused lidar / sky / object-alpha losses: the error plane bit-identical to PyTorch's float32

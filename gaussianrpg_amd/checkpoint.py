@@ -98,11 +98,15 @@ class LoadedScene:
     """Raw per-model parameters of a checkpoint, in file order."""
 
     def __init__(self, models: "OrderedDict[str, Dict[str, torch.Tensor]]", source: str,
-                 color_correction: "Optional[Dict[str, torch.Tensor]]" = None):
+                 color_correction: "Optional[Dict[str, torch.Tensor]]" = None,
+                 pose_correction: "Optional[Dict[str, torch.Tensor]]" = None):
         self.models, self.source = models, source
         # the parameters of the file's ``color_correction`` entry (StreetGaussianModel.save_state_dict with
         # use_color_correction: true), or None: the scene renders with the wrong colours without them
         self.color_correction = color_correction
+        # the parameters of the file's ``pose_correction`` entry (use_pose_correction: true), or None: the background
+        # renders misaligned against the actors without them
+        self.pose_correction = pose_correction
 
     def color_correction_module(self, mode: str = "image", device="cpu"):
         """The file's colour correction as a ``gaussianrpg_amd.appearance.ColorCorrection`` on ``device``, or None when
@@ -119,6 +123,21 @@ class LoadedScene:
         cc = ColorCorrection(int(p["affine_trans"].shape[0]), mode=mode)
         cc.load_state_dict({"params": p})
         return cc.to(device)
+
+    def pose_correction_module(self, mode: str = "image", device="cpu", active: bool = True):
+        """The file's pose correction as a ``gaussianrpg_amd.pose_correction.PoseCorrection`` on ``device``, or None
+        when the file has none.  ``mode`` is the reference's ``cfg.model.pose_correction.mode`` (the file does not
+        record it); ``active=False`` for the modes in which the reference does not correct."""
+        if self.pose_correction is None:
+            return None
+        from .pose_correction import PoseCorrection
+        p = self.pose_correction
+        if "pose_correction_rots" not in p or "pose_correction_trans" not in p:
+            raise ValueError("%s: the pose_correction entry lacks pose_correction_rots / pose_correction_trans (keys %s)"
+                             % (self.source, sorted(p)))
+        pc = PoseCorrection(int(p["pose_correction_rots"].shape[0]), mode=mode, active=active)
+        pc.load_state_dict({"params": p})
+        return pc.to(device)
 
     def names(self):
         return list(self.models)
@@ -157,10 +176,12 @@ def load_checkpoint(path: str, allow_unsafe: bool = False, color_correction: boo
 
     A ``.pth`` written with ``use_color_correction: true`` carries a ``color_correction`` entry
     (street_gaussian_model.py:153-154): its parameters are kept as ``LoadedScene.color_correction`` (None when the
-    file has none, for a ``.ply``, or with ``color_correction=False``)."""
+    file has none, for a ``.ply``, or with ``color_correction=False``).  Likewise the ``pose_correction`` entry of a
+    file written with ``use_pose_correction: true`` (street_gaussian_model.py:156-157) is kept as
+    ``LoadedScene.pose_correction``."""
     ext = os.path.splitext(path)[1].lower()
     models = OrderedDict()
-    cc_params = None
+    cc_params = pc_params = None
     if ext == ".ply":
         for name, el in read_ply(path).items():
             if not name.startswith("vertex") or "opacity" not in (el.dtype.names or ()):
@@ -184,6 +205,9 @@ def load_checkpoint(path: str, allow_unsafe: bool = False, color_correction: boo
         cc = sd.get("color_correction")
         if color_correction and isinstance(cc, dict) and isinstance(cc.get("params"), dict):
             cc_params = OrderedDict((k, torch.as_tensor(v).detach().float()) for k, v in cc["params"].items())
+        pc = sd.get("pose_correction")
+        if isinstance(pc, dict) and isinstance(pc.get("params"), dict):
+            pc_params = OrderedDict((k, torch.as_tensor(v).detach().float()) for k, v in pc["params"].items())
         for name, m in sd.items():
             if isinstance(m, dict) and all(k in m for k in _MODEL_KEYS):
                 entry = {k: torch.as_tensor(m[k]).detach().float() for k in _MODEL_KEYS}
@@ -203,7 +227,7 @@ def load_checkpoint(path: str, allow_unsafe: bool = False, color_correction: boo
             raise ValueError("%s.feature_dc has shape %s, expected [N,F,3]" % (name, tuple(m["feature_dc"].shape)))
         if m["feature_rest"].dim() != 3 or m["feature_rest"].shape[0] != n or m["feature_rest"].shape[2] != 3:
             raise ValueError("%s.feature_rest has shape %s, expected [N,M-1,3]" % (name, tuple(m["feature_rest"].shape)))
-    return LoadedScene(models, path, cc_params)
+    return LoadedScene(models, path, cc_params, pc_params)
 
 
 def activated_scene(loaded: LoadedScene, names: Optional[Sequence[str]] = None):

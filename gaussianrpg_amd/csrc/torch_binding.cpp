@@ -1439,6 +1439,168 @@ std::tuple<torch::Tensor, torch::Tensor> ColorCorrectBackward(
   return std::make_tuple(grad_x, grad_affine);
 }
 
+// ---- pose correction of the background (gaussianrpg_amd/pose_correction.py; csrc/pose_correction.hip) ----
+namespace {
+// xyz [N,3] and / or rotation [N,4] (float32, on a device, the same N); rot [4] / trans [3] float32 on that device (a
+// view of the parameter is taken as it is).
+struct PoseCorrectIn {
+  torch::Tensor xyz, rotation, rot, trans;   // contiguous; xyz / rotation undefined when absent
+  int N = 0;
+  torch::Tensor any;                          // whichever input is there: device and options
+};
+
+PoseCorrectIn pose_correct_args(const OptTensor& xyz, const OptTensor& rotation, const torch::Tensor& rot,
+                                const torch::Tensor& trans) {
+  TORCH_CHECK(given(xyz) || given(rotation), "pose_correct: give xyz, rotation, or both");
+  PoseCorrectIn in;
+  in.any = given(xyz) ? *xyz : *rotation;
+  TORCH_CHECK(in.any.is_cuda(), "pose_correct: the Gaussians must live on a ROCm/HIP device (no CPU path)");
+  if (given(xyz)) {
+    TORCH_CHECK(xyz->scalar_type() == torch::kFloat32 && xyz->dim() == 2 && xyz->size(1) == 3,
+                "pose_correct: xyz must be a float32 tensor [N,3]");
+    in.xyz = xyz->contiguous();
+  }
+  if (given(rotation)) {
+    TORCH_CHECK(rotation->device() == in.any.device() && rotation->scalar_type() == torch::kFloat32 &&
+                    rotation->dim() == 2 && rotation->size(1) == 4,
+                "pose_correct: rotation must be a float32 tensor [N,4] on the device of xyz");
+    TORCH_CHECK(!given(xyz) || rotation->size(0) == xyz->size(0), "pose_correct: xyz and rotation disagree on N");
+    in.rotation = rotation->contiguous();
+  }
+  TORCH_CHECK(in.any.size(0) <= INT_MAX, "pose_correct: too many rows");
+  in.N = (int)in.any.size(0);
+  TORCH_CHECK(rot.device() == in.any.device() && rot.scalar_type() == torch::kFloat32 && rot.numel() == 4 &&
+                  trans.device() == in.any.device() && trans.scalar_type() == torch::kFloat32 && trans.numel() == 3,
+              "pose_correct: rot [4] and trans [3] must be float32 tensors on the Gaussians' device");
+  in.rot = rot.contiguous();
+  in.trans = trans.contiguous();
+  return in;
+}
+
+const float* ptr_or_null(const torch::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
+float* mut_ptr_or_null(torch::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
+}  // namespace
+
+// (xyz' [N,3] or undefined, rotation' [N,4] or undefined)
+std::tuple<torch::Tensor, torch::Tensor> PoseCorrect(const OptTensor& xyz, const OptTensor& rotation,
+                                                     const torch::Tensor& rot, const torch::Tensor& trans) {
+  const PoseCorrectIn in = pose_correct_args(xyz, rotation, rot, trans);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.any.device());
+  torch::Tensor out_xyz, out_rotation;
+  if (in.xyz.defined()) out_xyz = torch::empty_like(in.xyz);
+  if (in.rotation.defined()) out_rotation = torch::empty_like(in.rotation);
+  if (in.N == 0) return std::make_tuple(out_xyz, out_rotation);   // nothing to launch; empty tensors have no address
+  run("grpg_pose_correct_forward", [&](void* stream) {
+    return grpg_pose_correct_forward(in.N, ptr_or_null(in.xyz), ptr_or_null(in.rotation), in.rot.data_ptr<float>(),
+                                     in.trans.data_ptr<float>(), mut_ptr_or_null(out_xyz),
+                                     mut_ptr_or_null(out_rotation), stream);
+  });
+  return std::make_tuple(out_xyz, out_rotation);
+}
+
+// (g_xyz [N,3], g_rotation [N,4], g_rot [4], g_trans [3]); each undefined when not asked for.  grad_xyz /
+// grad_rotation: the upstream gradients of the outputs the forward gave (an absent one counts as zero).
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> PoseCorrectBackward(
+    const OptTensor& xyz, const OptTensor& rotation, const torch::Tensor& rot, const torch::Tensor& trans,
+    const OptTensor& grad_xyz, const OptTensor& grad_rotation, const bool need_xyz, const bool need_rotation,
+    const bool need_rot, const bool need_trans) {
+  TORCH_CHECK(given(grad_xyz) || given(grad_rotation), "pose_correct_backward: give at least one upstream gradient");
+  TORCH_CHECK((!given(grad_xyz) || given(xyz)) && (!given(grad_rotation) || given(rotation)),
+              "pose_correct_backward: an upstream gradient needs its forward input");
+  const PoseCorrectIn in = pose_correct_args(given(grad_xyz) ? xyz : OptTensor(),
+                                             given(grad_rotation) ? rotation : OptTensor(), rot, trans);
+  TORCH_CHECK(need_xyz || need_rotation || need_rot || need_trans, "pose_correct_backward: ask for a gradient");
+  TORCH_CHECK((!need_xyz || given(grad_xyz)) && (!need_rotation || given(grad_rotation)),
+              "pose_correct_backward: an input gradient needs its upstream gradient");
+  torch::Tensor gox, gor;
+  if (given(grad_xyz)) {
+    TORCH_CHECK(grad_xyz->device() == in.any.device() && grad_xyz->scalar_type() == torch::kFloat32 &&
+                    grad_xyz->sizes() == in.xyz.sizes(),
+                "pose_correct_backward: grad_xyz must be a float32 tensor [N,3] on the Gaussians' device");
+    gox = grad_xyz->contiguous();
+  }
+  if (given(grad_rotation)) {
+    TORCH_CHECK(grad_rotation->device() == in.any.device() && grad_rotation->scalar_type() == torch::kFloat32 &&
+                    grad_rotation->sizes() == in.rotation.sizes(),
+                "pose_correct_backward: grad_rotation must be a float32 tensor [N,4] on the Gaussians' device");
+    gor = grad_rotation->contiguous();
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(in.any.device());
+  torch::Tensor g_xyz, g_rotation, g_rot, g_trans, ws;
+  if (need_xyz) g_xyz = torch::empty_like(in.xyz);
+  if (need_rotation) g_rotation = torch::empty_like(in.rotation);
+  if (need_rot) g_rot = torch::empty({4}, in.any.options());
+  if (need_trans) g_trans = torch::empty({3}, in.any.options());
+  if (in.N == 0) {   // sums over no rows
+    if (need_rot) g_rot.zero_();
+    if (need_trans) g_trans.zero_();
+    return std::make_tuple(g_xyz, g_rotation, g_rot, g_trans);
+  }
+  if (need_rot || need_trans)
+    ws = torch::empty({(long long)grpg_pose_correct_workspace_bytes(in.N)}, in.any.options().dtype(torch::kByte));
+  run("grpg_pose_correct_backward", [&](void* stream) {
+    return grpg_pose_correct_backward(in.N, ptr_or_null(in.xyz), ptr_or_null(in.rotation), in.rot.data_ptr<float>(),
+                                      ptr_or_null(gox), ptr_or_null(gor), mut_ptr_or_null(g_xyz),
+                                      mut_ptr_or_null(g_rotation), mut_ptr_or_null(g_rot), mut_ptr_or_null(g_trans),
+                                      ws.defined() ? ws.data_ptr() : nullptr, stream);
+  });
+  return std::make_tuple(g_xyz, g_rotation, g_rot, g_trans);
+}
+
+namespace {
+void pose_rows_params(const torch::Tensor& corr_rots, const torch::Tensor& corr_trans, const int64_t id) {
+  TORCH_CHECK(corr_rots.is_cuda(), "pose_rows: the correction parameters must live on a ROCm/HIP device");
+  TORCH_CHECK(corr_rots.scalar_type() == torch::kFloat32 && corr_rots.dim() == 2 && corr_rots.size(1) == 4 &&
+                  corr_trans.device() == corr_rots.device() && corr_trans.scalar_type() == torch::kFloat32 &&
+                  corr_trans.dim() == 2 && corr_trans.size(1) == 3 && corr_trans.size(0) == corr_rots.size(0),
+              "pose_rows: the correction parameters must be float32 tensors [n,4] and [n,3] on one device");
+  TORCH_CHECK(id >= 0 && id < corr_rots.size(0), "pose_rows: id ", id, " is not one of the ", corr_rots.size(0),
+              " correction rows");
+}
+}  // namespace
+
+// (rot' [A+1,4], trans' [A+1,3]): the actors' rows, then the raw correction row id
+std::tuple<torch::Tensor, torch::Tensor> PoseRowsForward(const torch::Tensor& rot, const torch::Tensor& trans,
+                                                         const torch::Tensor& corr_rots,
+                                                         const torch::Tensor& corr_trans, const int64_t id) {
+  pose_rows_params(corr_rots, corr_trans, id);
+  TORCH_CHECK(rot.device() == corr_rots.device() && rot.scalar_type() == torch::kFloat32 && rot.dim() == 2 &&
+                  rot.size(1) == 4 && trans.device() == corr_rots.device() &&
+                  trans.scalar_type() == torch::kFloat32 && trans.dim() == 2 && trans.size(1) == 3 &&
+                  trans.size(0) == rot.size(0),
+              "pose_rows: the actors' rows must be float32 tensors [A,4] and [A,3] on the parameters' device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(corr_rots.device());
+  const int A = (int)rot.size(0);
+  const torch::Tensor r = rot.contiguous(), t = trans.contiguous(), cr = corr_rots.contiguous(),
+                      ct = corr_trans.contiguous();
+  torch::Tensor out_rot = torch::empty({A + 1, 4}, cr.options()), out_trans = torch::empty({A + 1, 3}, cr.options());
+  run("grpg_pose_rows_forward", [&](void* stream) {
+    return grpg_pose_rows_forward(A, A ? r.data_ptr<float>() : nullptr, A ? t.data_ptr<float>() : nullptr,
+                                  (int)cr.size(0), cr.data_ptr<float>(), ct.data_ptr<float>(), (int)id,
+                                  out_rot.data_ptr<float>(), out_trans.data_ptr<float>(), stream);
+  });
+  return std::make_tuple(out_rot, out_trans);
+}
+
+// (g_corr_rots [n,4], g_corr_trans [n,3]) from the table's gradient [A+1,4] / [A+1,3]
+std::tuple<torch::Tensor, torch::Tensor> PoseRowsBackward(const torch::Tensor& grad_rot, const torch::Tensor& grad_trans,
+                                                          const int64_t n, const int64_t id) {
+  TORCH_CHECK(grad_rot.is_cuda() && grad_rot.scalar_type() == torch::kFloat32 && grad_rot.dim() == 2 &&
+                  grad_rot.size(1) == 4 && grad_rot.size(0) >= 1 && grad_trans.device() == grad_rot.device() &&
+                  grad_trans.scalar_type() == torch::kFloat32 && grad_trans.dim() == 2 && grad_trans.size(1) == 3 &&
+                  grad_trans.size(0) == grad_rot.size(0),
+              "pose_rows_backward: the gradients must be float32 device tensors [A+1,4] and [A+1,3]");
+  TORCH_CHECK(n > 0 && n <= INT_MAX && id >= 0 && id < n, "pose_rows_backward: id must be one of the n rows");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(grad_rot.device());
+  const torch::Tensor gr = grad_rot.contiguous(), gt = grad_trans.contiguous();
+  torch::Tensor g_rots = torch::empty({n, 4}, gr.options()), g_trans = torch::empty({n, 3}, gr.options());
+  run("grpg_pose_rows_backward", [&](void* stream) {
+    return grpg_pose_rows_backward((int)gr.size(0) - 1, (int)n, (int)id, gr.data_ptr<float>(), gt.data_ptr<float>(),
+                                   g_rots.data_ptr<float>(), g_trans.data_ptr<float>(), stream);
+  });
+  return std::make_tuple(g_rots, g_trans);
+}
+
 // ---- frame -> detector input (gaussianrpg_amd/perception.py; csrc/letterbox.hip) ----
 
 // letterbox()'s arithmetic (utils/augmentations.py:121-151); host only.
@@ -2641,6 +2803,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("fill") = 0.0, pybind11::arg("acc") = pybind11::none(), pybind11::arg("mask") = pybind11::none(),
         pybind11::arg("jitter") = pybind11::none());
   m.def("color_correct_workspace_bytes", [](int H, int W) { return grpg_color_correct_workspace_bytes(W, H); });
+  // pose correction of the background (pose_correction.py): (xyz', rotation') / (g_xyz, g_rotation, g_rot, g_trans)
+  m.def("pose_correct", &PoseCorrect, pybind11::arg("xyz"), pybind11::arg("rotation"), pybind11::arg("rot"),
+        pybind11::arg("trans"));
+  m.def("pose_correct_backward", &PoseCorrectBackward, pybind11::arg("xyz"), pybind11::arg("rotation"),
+        pybind11::arg("rot"), pybind11::arg("trans"), pybind11::arg("grad_xyz"), pybind11::arg("grad_rotation"),
+        pybind11::arg("need_xyz") = true, pybind11::arg("need_rotation") = true, pybind11::arg("need_rot") = true,
+        pybind11::arg("need_trans") = true);
+  m.def("pose_correct_workspace_bytes", [](int n) { return grpg_pose_correct_workspace_bytes(n); });
+  // the frame's pose table with the background's row behind the actors' (pose_correction.py)
+  m.def("pose_rows", &PoseRowsForward, pybind11::arg("rot"), pybind11::arg("trans"), pybind11::arg("corr_rots"),
+        pybind11::arg("corr_trans"), pybind11::arg("id"));
+  m.def("pose_rows_backward", &PoseRowsBackward, pybind11::arg("grad_rot"), pybind11::arg("grad_trans"),
+        pybind11::arg("n"), pybind11::arg("id"));
   // frame -> detector input (perception.py)
   m.def("letterbox_geometry", &LetterboxGeometry, pybind11::arg("height"), pybind11::arg("width"),
         pybind11::arg("new_h_req"), pybind11::arg("new_w_req"), pybind11::arg("auto_pad") = true,

@@ -719,6 +719,113 @@ def tracked_train_step(rast, models, actors, timestamp: float, ego_pose: torch.T
     return color.detach()
 
 
+# ----------------------------------------------------------------------------------------------
+# Pose correction of the background (gaussianrpg_amd/pose_correction.py): the corrected evaluation frame and the
+# corrected training step, by the reference's own composition with the classic op and by the composed rasterizer.
+# ----------------------------------------------------------------------------------------------
+def pose_correct_torch(xyz: Optional[torch.Tensor], rotation: Optional[torch.Tensor], rot: torch.Tensor,
+                       trans: torch.Tensor):
+    """``PoseCorrection.correct_gaussian_xyz`` / ``correct_gaussian_rotation`` line by line in PyTorch
+    (camera_pose.py:89-114): what ``pose_correction.pose_correct`` replaces, for the benchmarks and as the float32
+    yardstick.  Either input may be None."""
+    q = torch.nn.functional.normalize(rot.unsqueeze(0), dim=-1)
+    out_xyz = out_rotation = None
+    if xyz is not None:
+        m = torch.cat([_unit_quat_matrix(q).squeeze(0), trans[:, None]], dim=-1)
+        m = torch.cat([m, torch.tensor([[0, 0, 0, 1]], device=m.device).float()], dim=0)
+        out_xyz = (torch.cat([xyz, torch.ones_like(xyz[..., :1])], dim=-1) @ m.T)[:, :3]
+    if rotation is not None:
+        out_rotation = _quat_mul(q, rotation)
+    return out_xyz, out_rotation
+
+
+def reference_getters(models, actor_rot: Optional[torch.Tensor], actor_trans: Optional[torch.Tensor], fourier_times=(),
+                      correction=None):
+    """``StreetGaussianModel``'s getters (street_gaussian_model.py:296-453) in PyTorch on the device, for the
+    background ``models[0]`` and the actors ``models[1:]`` with the world poses ``actor_rot [n,4]`` / ``actor_trans
+    [n,3]`` (one row per actor model): (means3D, scales, rotations, opacity, shs) as the classic op takes them.
+    ``correction``: None, or a callable ``(xyz, rotation) -> (xyz', rotation')`` applied to the background's activated
+    tensors where the reference calls ``pose_correction.correct_gaussian_*`` (:319-320, :345-346)."""
+    from .composed import idft_weights
+    F = torch.nn.functional
+    bg = models[0]
+    xyz_b, rot_b = bg.xyz, F.normalize(bg.rotation)
+    if correction is not None:
+        xyz_b, rot_b = correction(xyz_b, rot_b)
+    xyz, sca, rot, opa = [xyz_b], [torch.exp(bg.scaling)], [rot_b], [torch.sigmoid(bg.opacity)]
+    fea = [torch.cat((bg.features_dc, bg.features_rest), 1)]
+    actors = list(models[1:])
+    if actors:
+        counts = [int(m.xyz.shape[0]) for m in actors]
+        dev = bg.xyz.device
+        owner = torch.repeat_interleave(torch.arange(len(actors), device=dev), torch.tensor(counts, device=dev))
+        loc_x = torch.cat([m.xyz for m in actors]).clone()
+        loc_r = torch.cat([F.normalize(m.rotation) for m in actors]).clone()
+        if any(m.flip is not None for m in actors):
+            flip = torch.cat([torch.zeros(c, dtype=torch.bool, device=dev) if m.flip is None else m.flip.bool()
+                              for m, c in zip(actors, counts)])
+            loc_x[flip, 1] *= -1
+            loc_r[flip] = _quat_mul(torch.tensor([[0.0, 0.0, 1.0, 0.0]], device=dev), loc_r[flip])
+        orot, otr = actor_rot[owner], actor_trans[owner]
+        xyz.append(torch.einsum('bij,bj->bi', _unit_quat_matrix(orot), loc_x) + otr)
+        rot.append(F.normalize(_quat_mul(orot, loc_r)))
+        for m, t in zip(actors, fourier_times):
+            sca.append(torch.exp(m.scaling))
+            opa.append(torch.sigmoid(m.opacity))
+            base = torch.tensor(idft_weights(t, int(m.features_dc.shape[1])), device=dev)
+            fea.append(torch.cat([torch.sum(m.features_dc * base[..., None], 1, keepdim=True), m.features_rest], 1))
+    return torch.cat(xyz), torch.cat(sca), torch.cat(rot), torch.cat(opa), torch.cat(fea)
+
+
+def _corrected_classic(settings, models, batch, t, visible, fourier_times, pc, camera, fused, means2D):
+    from diff_gaussian_rasterization import GaussianRasterizer
+    correction = None
+    if pc is not None and pc.active:
+        correction = (lambda x, r: pc.correct(camera, x, r)) if fused else \
+            (lambda x, r: pose_correct_torch(x, r, *pc.row(camera)))
+    times = [0.0] * len(visible) if fourier_times is None else fourier_times
+    index = torch.tensor([int(a) for a in visible], dtype=torch.long, device=batch.rot.device)
+    x, s, r, o, sh = reference_getters(models, batch.rot[t].index_select(0, index),
+                                       batch.trans[t].index_select(0, index), times, correction)
+    return GaussianRasterizer(settings)(means3D=x, means2D=means2D, opacities=o, shs=sh, scales=s, rotations=r)
+
+
+def corrected_frame(settings, models, batch, t: int, visible, fourier_times, pc, camera, *, composed: bool = True,
+                    fused: bool = True):
+    """The evaluation frame of a scene with pose correction: (color [3,H,W] clamped, radii, depth, alpha).
+    ``models``: the background, then the visible actors' models; ``batch``: a ``tracks.PoseBatch``; ``pc``: a
+    ``pose_correction.PoseCorrection``; ``camera``: what its ``get_id`` reads.
+      composed=True   ``ComposedRasterizer`` with the background's device row (``PoseCorrection.rows``): one launch
+                      for the table, nothing else in front of the frame
+      composed=False  the reference's composition in PyTorch (``reference_getters``) and the classic op, the
+                      correction by ``pose_correct`` (``fused=True``, one launch) or by the reference's lines in
+                      PyTorch (``fused=False``)"""
+    with torch.no_grad():
+        if composed:
+            from .composed import ComposedRasterizer
+            poses, _ = pc.rows(batch, t, camera, visible, fourier_times)
+            out = ComposedRasterizer(settings).forward(models, poses)
+        else:
+            out = _corrected_classic(settings, models, batch, t, visible, fourier_times, pc, camera, fused, None)
+        return (torch.clamp(out[0], 0.0, 1.0),) + tuple(out[1:4])
+
+
+def corrected_train_step(settings, models, batch, t: int, visible, fourier_times, pc, camera, *, composed: bool = True,
+                         fused: bool = True, weights=None, means2D=None):
+    """The forward + backward of one training iteration of a scene with pose correction, by the routes of
+    ``corrected_frame``; the backward reaches the models' raw parameters, the batch (``opt_trans`` / ``opt_rots``
+    behind it) and ``pose_correction_rots`` / ``pose_correction_trans``.  The loss is a weighted sum of the colour
+    plane (``weights [3,H,W]``, default ones).  Returns the detached colour plane."""
+    if composed:
+        from .composed import ComposedRasterizer
+        poses, _ = pc.rows(batch, t, camera, visible, fourier_times)
+        color = ComposedRasterizer(settings).forward(models, poses, means2D=means2D)[0]
+    else:
+        color = _corrected_classic(settings, models, batch, t, visible, fourier_times, pc, camera, fused, means2D)[0]
+    (color.sum() if weights is None else (color * weights).sum()).backward()
+    return color.detach()
+
+
 def train_loss(render_pkg: dict, gt_image: torch.Tensor, lidar_depth: Optional[torch.Tensor] = None,
                sky_mask: Optional[torch.Tensor] = None, lambda_l1: float = 1.0,
                lambda_depth_lidar: float = 0.1, lambda_sky: float = 0.05, *, lambda_dssim: float = 0.0,

@@ -643,6 +643,47 @@ GRPG_API int grpg_color_correct_backward(int width, int height, const float* rgb
                                          const float* grad_out, float* grad_x, float* grad_affine, void* workspace,
                                          void* hip_stream);
 
+/* ---- pose correction of the background (additive; csrc/pose_correction.hip) ----
+ * PoseCorrection.correct_gaussian_xyz / correct_gaussian_rotation (lib/models/camera_pose.py:89-114): the learned
+ * rigid transform of every background Gaussian, one per image or per frame.
+ *     q^ = rot / max(|rot|, 1e-12),  R = quaternion_to_matrix(q^) (which divides by |q^| once more)
+ *     out_xyz = R xyz + trans,  out_rotation = quaternion_raw_multiply(q^, rotation)  (not normalised behind it)
+ *   n            rows (>= 0)
+ *   xyz          optional device [n,3], with out_xyz [n,3]
+ *   rotation     optional device [n,4] (w,x,y,z), taken as given, with out_rotation [n,4]; at least one of the two
+ *   rot, trans   DEVICE float[4] (w,x,y,z, raw) / float[3] (e.g. views pose_correction_rots[id] /
+ *                pose_correction_trans[id] of the parameters): never read by the host; trans only with xyz
+ * grpg_pose_correct_backward: grad_out_xyz [n,3] / grad_out_rotation [n,4] are the upstream gradients (each needs
+ * its forward input; at least one); everything else is recomputed from the inputs.
+ *   grad_xyz, grad_rotation  optional device [n,3] / [n,4]: R^T grad_out_xyz / the product's transpose
+ *   grad_rot, grad_trans     optional device float[4] / float[3], overwritten: the gradient of the raw row through the
+ *                product, R and both normalisations / the sum of grad_out_xyz.  Fixed-order sums without atomics
+ *                (identical calls give identical bits; the add order is in the .hip file's header); they need
+ *                workspace: device, grpg_pose_correct_workspace_bytes(n) bytes (a pure size query, 0 for n <= 0)
+ * grpg_pose_rows_forward: the frame's pose table with the background's row in it.  From the actors' rows rot [A,4] /
+ * trans [A,3] (A >= 0; NULL when 0) and the correction parameters corr_rots [n,4] / corr_trans [n,3] it writes
+ * out_rot [A+1,4] / out_trans [A+1,3]: rows 0..A-1 are copies, row A is the RAW correction row id (the composed
+ * entries normalise a pose row themselves).  grpg_pose_rows_backward writes the dense parameter gradients [n,4] /
+ * [n,3] from the table's gradient [A+1,4] / [A+1,3]: row id is its row A, every other row zero; the actors'
+ * gradients are the table gradient's first A rows as they are.
+ * All run asynchronously on hip_stream.  Purely additive exports: GRPG_ABI_VERSION stays 7.  Returns GRPG_OK,
+ * GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT for n < 0, neither input, an output without its
+ * input (or the reverse), a NULL correction row, sums without a workspace, an id outside the parameter, or a pointer
+ * that is not 4-byte aligned. */
+GRPG_API size_t grpg_pose_correct_workspace_bytes(int n);
+GRPG_API int grpg_pose_correct_forward(int n, const float* xyz, const float* rotation, const float* rot,
+                                       const float* trans, float* out_xyz, float* out_rotation, void* hip_stream);
+GRPG_API int grpg_pose_correct_backward(int n, const float* xyz, const float* rotation, const float* rot,
+                                        const float* grad_out_xyz, const float* grad_out_rotation, float* grad_xyz,
+                                        float* grad_rotation, float* grad_rot, float* grad_trans, void* workspace,
+                                        void* hip_stream);
+GRPG_API int grpg_pose_rows_forward(int actors, const float* rot, const float* trans, int n, const float* corr_rots,
+                                    const float* corr_trans, int id, float* out_rot, float* out_trans,
+                                    void* hip_stream);
+GRPG_API int grpg_pose_rows_backward(int actors, int n, int id, const float* grad_rot_rows,
+                                     const float* grad_trans_rows, float* grad_corr_rots, float* grad_corr_trans,
+                                     void* hip_stream);
+
 /* Binning-blob sizing policy of grpg_forward (process-wide; see above).  The environment variable
  * GRPG_SYNC_R=1 selects GRPG_BINNING_EXACT at load time. */
 #define GRPG_BINNING_SPECULATIVE 0
