@@ -599,7 +599,7 @@ class ComposedRasterizer(nn.Module):
     def forward_frame(self, models: Sequence[ModelParams], poses: Sequence[Optional[ActorPose]], *,
                       sky_cube=None, ray_matrix=None, sky_fill=0.0, clamp=True, planes=False, rgb8=True,
                       truncate=True, out=None, layers=False, object_models: Optional[Sequence[bool]] = None,
-                      layer_bg=None) -> dict:
+                      layer_bg=None, affine=None) -> dict:
         """The reference's whole per-frame evaluation path as ONE call on the raw parameters (C ABI
         ``grpg_forward_composed_frame``): scene-graph composition (street_gaussian_model.py:296-453), the op,
         ``StreetGaussianRenderer.render``'s clamp / sky composite / clamp (street_gaussian_renderer.py:106-116,
@@ -609,7 +609,9 @@ class ComposedRasterizer(nn.Module):
         device; ``out``: a preallocated device tensor, or a PINNED HOST tensor -- the bytes then land in host memory
         while the render runs, no copy behind the launch: what the simulator wants; synchronise with the stream before
         reading), with ``planes=True`` also ``rgb`` (the FINAL colour) / ``depth`` /
-        ``alpha``, with ``layers=True`` the four layer planes; ``radii``, ``num_rendered``."""
+        ``alpha``, with ``layers=True`` the four layer planes; ``radii``, ``num_rendered``.  ``affine``: the colour
+        correction of ``GaussianRasterizer.forward_frame`` (a float32 [3,4] device tensor, applied to the composition
+        between the sky composite and the final clamp); it rides on the same call as device poses (``PoseBatch.rows``)."""
         rs = self.raster_settings
         lists, pose_t, idft_t = _pack(models, poses)
         if layers and layer_bg is None:
@@ -620,7 +622,7 @@ class ComposedRasterizer(nn.Module):
                 rs.bg, layer_bg, _object_flags(object_models), bool(layers), *lists, pose_t, idft_t,
                 rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
                 rs.image_width, rs.sh_degree, rs.campos, rs.debug, sky_cube, ray_matrix, float(sky_fill), bool(clamp),
-                bool(planes), bool(rgb8), bool(truncate), out)
+                bool(planes), bool(rgb8), bool(truncate), out, affine)
         self.num_rendered = ret[0]
         return _frame_result(ret, rgb8, planes, layers)
 

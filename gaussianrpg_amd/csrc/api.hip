@@ -655,6 +655,23 @@ struct PoseScope {
     if (--g_pose_depth == 0) g_pose_cur.clear();
   }
 };
+// ---- frame correction (grpg_bind_frame_correction): the device matrix waits here until the next grpg_forward_frame /
+// grpg_forward_composed_frame on this thread, which takes it first thing -- whatever that call returns then.
+thread_local const float* g_affine_pending = nullptr;
+const float* take_frame_correction() {
+  const float* a = g_affine_pending;
+  g_affine_pending = nullptr;
+  return a;
+}
+// the epilogue a bound correction runs in (fe: the call's resolved epilogue, or NULL when it has none)
+int attach_frame_correction(const float* affine, FrameEpilogue* fe) {
+  if (affine == nullptr) return GRPG_OK;
+  if (fe == nullptr)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "a frame correction was bound, but the frame has no epilogue to apply it in");
+  fe->affine = affine;
+  return GRPG_OK;
+}
+
 // behind the asynchronous copy of a table fill_segments built: the bound rows' poses, on the same stream
 void gather_device_poses(hipStream_t stream, SegmentDev* seg_dev, int nseg) {
   if (g_pose_cur.set && g_pose_cur.any && g_pose_cur.n == nseg)
@@ -1525,6 +1542,17 @@ int grpg_bind_device_poses(const float* pose_rot, const float* pose_trans, const
 
 int grpg_device_poses_bound(void) { return g_pose_pending.set ? 1 : 0; }
 
+// Pure host bookkeeping as well.  A refused bind leaves no binding (the caller meant to replace the pending one).
+int grpg_bind_frame_correction(const float* affine_device) {
+  g_last_error.clear();
+  g_affine_pending = nullptr;
+  if (!affine_device) return fail(GRPG_ERR_INVALID_ARGUMENT, "frame correction: NULL affine matrix");
+  g_affine_pending = affine_device;
+  return GRPG_OK;
+}
+
+int grpg_frame_correction_bound(void) { return g_affine_pending ? 1 : 0; }
+
 int grpg_forward_composed_flags(grpg_alloc_fn geometry_alloc, void* geometry_user,
                                 grpg_alloc_fn binning_alloc, void* binning_user,
                                 grpg_alloc_fn image_alloc, void* image_user,
@@ -1594,6 +1622,7 @@ int grpg_forward_frame(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_a
                        float* out_alpha_bg, float* out_color_obj, float* out_alpha_obj, int* radii, int debug,
                        void* hip_stream, const grpg_frame_epilogue* epilogue) {
   g_last_error.clear();
+  const float* affine = take_frame_correction();
   const LayerArgs la = {nullptr, layer_class, layer_background, out_color_bg, out_alpha_bg, out_color_obj, out_alpha_obj};
   FrameRequest q;
   if (int rc = check_layers(la, P, true, true, &q.layers)) return rc;
@@ -1602,6 +1631,7 @@ int grpg_forward_frame(grpg_alloc_fn geometry_alloc, void* geometry_user, grpg_a
     if (int rc = resolve_epilogue(epilogue, out_color && out_depth && out_alpha, &fe)) return rc;
     q.epi = &fe;
   }
+  if (int rc = attach_frame_correction(affine, epilogue ? &fe : nullptr)) return rc;
   set_allocators(q, geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user);
   set_model(q, P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp);
   set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
@@ -1620,6 +1650,7 @@ int grpg_forward_composed_frame(grpg_alloc_fn geometry_alloc, void* geometry_use
                                 float* out_alpha_obj, int* radii, int debug, void* hip_stream,
                                 const grpg_frame_epilogue* epilogue) {
   PoseScope poses;
+  const float* affine = take_frame_correction();
   if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
@@ -1631,6 +1662,7 @@ int grpg_forward_composed_frame(grpg_alloc_fn geometry_alloc, void* geometry_use
     if (int rc = resolve_epilogue(epilogue, out_color && out_depth && out_alpha, &fe)) return rc;
     q.epi = &fe;
   }
+  if (int rc = attach_frame_correction(affine, epilogue ? &fe : nullptr)) return rc;
   set_allocators(q, geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user);
   set_model(q, segments, num_segments, P, D, M);
   set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,

@@ -33,6 +33,7 @@
 // product g_i * x_j back exactly.  Identical calls give identical bits.  The clamp has no backward (evaluation only);
 // with the sky inputs the cube-map and acc gradients come from grpg_sky_backward_ex on g_x (sky.hip, unchanged).
 #include "abi_util.h"
+#include "color_math.h"
 #include "common.h"
 #include "reduce.h"
 #include "sky_math.h"
@@ -41,10 +42,7 @@ namespace grpg {
 
 constexpr int CC_SUMS = 12;
 
-// row i of the affine map; a: 12 floats, row-major [3,4]
-__device__ __forceinline__ float affine_row(const float* a, const int i, const float (&x)[3]) {
-  return fmaf(a[4 * i + 2], x[2], fmaf(a[4 * i + 1], x[1], fmaf(a[4 * i + 0], x[0], a[4 * i + 3])));
-}
+// (row i of the affine map: affine_row, color_math.h -- shared with the frame epilogue of render_fwd.hip)
 
 // column j of A^T g
 __device__ __forceinline__ float affine_col(const float* a, const int j, const float (&g)[3]) {

@@ -517,6 +517,7 @@ struct FrameEpilogue {
   int drain_wgs;
   int truncate;
   int planes;                           // write the float planes as well
+  const float* affine;                  // colour correction (grpg_bind_frame_correction): device float[12], or NULL
 };
 void launch_render_forward(hipStream_t s, const uint2* ranges, const uint32_t* point_list,
                            const RecView rec, int W, int H, int gx, int gy, const float* bg,

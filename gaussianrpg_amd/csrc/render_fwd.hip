@@ -36,6 +36,7 @@
 // HBM-bound; its compulsory HBM traffic is 4 B (id) + 40 B (record fields) per tile instance
 // + 20 B per pixel.
 #include "blend_math.h"
+#include "color_math.h"
 #include "common.h"
 #include "sky_math.h"
 
@@ -492,6 +493,10 @@ __device__ __forceinline__ bool blend_quad_tail(WavePix<1>& s, const Cols& cols,
 //   rgb = clamp(C + T bg)                           render_kernel's evaluation clamp (street_gaussian_renderer.py:236)
 //   rgb = clamp(rgb + clamp(sky) (1 - acc))         StreetGaussianRenderer.render (:106-116), acc = 1 - T
 //   bytes [H,W,3] = uint8(rgb * 255)                the simulator's frame (simulator.py:313-314)
+// and, for a scene trained with use_color_correction (FrameEpi::affine, grpg_bind_frame_correction), between the sky
+// composite and the final clamp:
+//   x   = rgb + clamp(sky) (1 - acc)                unclamped: what grpg_color_correct_forward forms (clamp_out = 0)
+//   rgb = clamp(A[:, :3] x + A[:, 3])               pc.color_correction (:113), affine_row of color_math.h
 // The state is in registers when the walk ends: the stand-alone chain (three launches) wrote the colour and
 // alpha planes, read them back for the sky composite, wrote the colour again and read it a third time to pack.
 struct FrameEpi {
@@ -511,6 +516,10 @@ struct FrameEpi {
   unsigned char* host8;     // the pinned host frame (drained frame), or NULL
   uint32_t* unit_cnt;       // [drain waves][64] pixels arrived per unit (zero at launch, zero again at its end)
   int drain_wgs, units_x;
+  // Colour correction (grpg_bind_frame_correction): 12 floats, row-major [3,4], in DEVICE memory; NULL: none.  Read
+  // in frame_finish, behind the walk, through this wave-uniform pointer: scalar loads, nothing of the matrix is live
+  // while the lists are walked.
+  const float* affine;
 };
 // final rgb of a pixel from its blended colour (background included) and T; optional byte store
 template <bool EPI>
@@ -523,9 +532,20 @@ __device__ __forceinline__ void frame_finish(const FrameEpi& e, const int px, co
       const float acc = 1.0f - T, tr = 1.0f - acc;     // (the stand-alone launch reads acc from the alpha plane)
       float sky[3];
       sky_pixel(e.sky, px, py, pix, HW, true, tr, sky);
-      rgb[0] = sky_over(rgb[0], sky[0], tr, e.clamp);
-      rgb[1] = sky_over(rgb[1], sky[1], tr, e.clamp);
-      rgb[2] = sky_over(rgb[2], sky[2], tr, e.clamp);
+      const int sky_clamp = e.affine != nullptr ? 0 : e.clamp;   // a corrected frame clamps behind the map only
+      rgb[0] = sky_over(rgb[0], sky[0], tr, sky_clamp);
+      rgb[1] = sky_over(rgb[1], sky[1], tr, sky_clamp);
+      rgb[2] = sky_over(rgb[2], sky[2], tr, sky_clamp);
+    }
+    if (e.affine != nullptr) {   // wave-uniform; the statements of color_correct_kernel (color_correction.hip)
+      float a[12];
+      load_affine_uniform(e.affine, a);
+      const float x[3] = {rgb[0], rgb[1], rgb[2]};
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        const float y = affine_row(a, i, x);
+        rgb[i] = e.clamp ? clamp01(y) : y;
+      }
     }
     if (e.rgb8 != nullptr) {
       const uint32_t r8 = colour_u8(rgb[0], e.bias), g8 = colour_u8(rgb[1], e.bias), b8 = colour_u8(rgb[2], e.bias);
@@ -1896,7 +1916,7 @@ static FrameEpi make_frame_epi(const FrameEpilogue* e, const int W = 0, const bo
   d.sky.m_dev = e->ray_m_dev; d.sky.mask = nullptr; d.sky.jitter = nullptr;
   for (int i = 0; i < 9; i++) d.sky.m[i] = e->ray_m_dev ? 0.f : e->ray_m[i];
   d.clamp = e->clamp; d.rgb8 = e->rgb8; d.bias = e->truncate ? 0.0f : 0.5f; d.planes = e->planes;
-  d.host = e->rgb8_host;
+  d.host = e->rgb8_host; d.affine = e->affine;
   if (may_drain && e->rgb8_host && e->drain_stage != nullptr && e->drain_cnt != nullptr && e->drain_wgs > 0 &&
       (W & 15) == 0 && ((uintptr_t)e->rgb8 & 15) == 0 && ((uintptr_t)e->drain_stage & 15) == 0) {
     d.host8 = e->rgb8; d.rgb8 = e->drain_stage; d.host = 2;

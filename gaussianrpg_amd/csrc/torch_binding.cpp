@@ -334,7 +334,21 @@ RasterizeGaussiansLayers(const torch::Tensor& background, const torch::Tensor& l
 struct EpilogueArgs {
   grpg_frame_epilogue e;
   torch::Tensor k_cube, k_rm, rgb8;
+  // colour correction inside the epilogue (grpg_bind_frame_correction): 12 floats on the frame's device, or none
+  torch::Tensor k_affine;
+  const float* affine = nullptr;
+  // binds the matrix for the frame call that follows in the same scaffold
+  int bind() const { return affine ? grpg_bind_frame_correction(affine) : GRPG_OK; }
 };
+// affine: float32, 12 elements ([3,4] row-major) on the frame's device; a contiguous view such as affine_trans[id] is
+// taken as it is (no copy, no host read), anything else is made contiguous like _C.color_correct's
+static void set_frame_affine(EpilogueArgs& a, const torch::Tensor& like, const c10::optional<torch::Tensor>& affine) {
+  if (!affine.has_value() || !affine->defined()) return;
+  TORCH_CHECK(affine->device() == like.device() && affine->scalar_type() == torch::kFloat32 && affine->numel() == 12,
+              "forward_frame: affine must be a float32 tensor [3,4] on the image's device");
+  a.k_affine = affine->contiguous();
+  a.affine = a.k_affine.data_ptr<float>();
+}
 static void make_epilogue(EpilogueArgs& a, const torch::Tensor& like, const torch::Tensor& sky_cube,
                           const torch::Tensor& ray_matrix, const float sky_fill, const bool clamp, const bool want_rgb8,
                           const bool truncate, const c10::optional<torch::Tensor>& out_rgb8, const int H, const int W) {
@@ -383,7 +397,8 @@ FrameResult RasterizeGaussiansFrame(
     const float tan_fovx, const float tan_fovy, const int image_height, const int image_width,
     const torch::Tensor& sh, const int degree, const torch::Tensor& campos, const bool debug,
     const torch::Tensor& sky_cube, const torch::Tensor& ray_matrix, const float sky_fill, const bool clamp,
-    const bool want_planes, const bool want_rgb8, const bool truncate, const c10::optional<torch::Tensor>& out_rgb8) {
+    const bool want_planes, const bool want_rgb8, const bool truncate, const c10::optional<torch::Tensor>& out_rgb8,
+    const c10::optional<torch::Tensor>& affine) {
   check_means3D(means3D);
   TORCH_CHECK(want_planes || want_rgb8, kFrameAsksForNothing);
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D.device());
@@ -397,8 +412,10 @@ FrameResult RasterizeGaussiansFrame(
   cam.require(LayerBg::kIfLayered, layered);
   EpilogueArgs ea;
   make_epilogue(ea, means3D, sky_cube, ray_matrix, sky_fill, clamp, want_rgb8, truncate, out_rgb8, H, W);
+  set_frame_affine(ea, means3D, affine);
   ForwardOutputs o(means3D, g.P, H, W, c10::nullopt, want_planes, layered);
   const int rendered = run("grpg_forward_frame", [&](void* stream) {
+    if (int rc = ea.bind()) return rc;
     return grpg_forward_frame(
         resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, g.P, degree, g.M, cam.bg, W, H, g.means,
         g.sh, g.colors, g.opacity, g.scales, scale_modifier, g.rotations, g.cov3D, cam.view, cam.proj, cam.pos,
@@ -807,7 +824,7 @@ FrameResult RasterizeGaussiansComposedFrame(
     const float tan_fovx, const float tan_fovy, const int image_height, const int image_width, const int degree,
     const torch::Tensor& campos, const bool debug, const torch::Tensor& sky_cube, const torch::Tensor& ray_matrix,
     const float sky_fill, const bool clamp, const bool want_planes, const bool want_rgb8, const bool truncate,
-    const c10::optional<torch::Tensor>& out_rgb8) {
+    const c10::optional<torch::Tensor>& out_rgb8, const c10::optional<torch::Tensor>& affine) {
   SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
   const torch::Tensor& like = xyz[0];
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
@@ -820,9 +837,11 @@ FrameResult RasterizeGaussiansComposedFrame(
   cam.require(LayerBg::kIfLayered, layered);
   EpilogueArgs ea;
   make_epilogue(ea, like, sky_cube, ray_matrix, sky_fill, clamp, want_rgb8, truncate, out_rgb8, H, W);
+  set_frame_affine(ea, like, affine);
   ForwardOutputs o(like, pk.P, H, W, c10::nullopt, want_planes, layered);
   const int rendered = run("grpg_forward_composed_frame", [&](void* stream) {
     if (int rc = pk.bind()) return rc;
+    if (int rc = ea.bind()) return rc;
     return grpg_forward_composed_frame(
         resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, pk.segs.data(), (int)pk.segs.size(),
         p_cls, degree, pk.M, cam.bg, cam.layer_bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx,
@@ -2775,8 +2794,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rasterize_gaussians_composed_objects_backward", &RasterizeGaussiansComposedObjectsBackward);
   m.def("object_alpha_forward", &ObjectAlphaForward);   // (alpha_object [1,H,W], workspace)
   m.def("rasterize_gaussians_composed_layers", &RasterizeGaussiansComposedLayers);
-  m.def("rasterize_gaussians_frame", &RasterizeGaussiansFrame);
-  m.def("rasterize_gaussians_composed_frame", &RasterizeGaussiansComposedFrame);
+  // (the arguments are named for the sake of the one default: affine, the colour correction inside the epilogue)
+  m.def("rasterize_gaussians_frame", &RasterizeGaussiansFrame,
+        pybind11::arg("background"), pybind11::arg("layer_background"), pybind11::arg("layer_class"),
+        pybind11::arg("means3D"), pybind11::arg("colors"), pybind11::arg("opacity"), pybind11::arg("scales"),
+        pybind11::arg("rotations"), pybind11::arg("scale_modifier"), pybind11::arg("cov3D_precomp"),
+        pybind11::arg("viewmatrix"), pybind11::arg("projmatrix"), pybind11::arg("tan_fovx"),
+        pybind11::arg("tan_fovy"), pybind11::arg("image_height"), pybind11::arg("image_width"), pybind11::arg("sh"),
+        pybind11::arg("degree"), pybind11::arg("campos"), pybind11::arg("debug"), pybind11::arg("sky_cube"),
+        pybind11::arg("ray_matrix"), pybind11::arg("sky_fill"), pybind11::arg("clamp"), pybind11::arg("want_planes"),
+        pybind11::arg("want_rgb8"), pybind11::arg("truncate"), pybind11::arg("out_rgb8"),
+        pybind11::arg("affine") = pybind11::none());
+  m.def("rasterize_gaussians_composed_frame", &RasterizeGaussiansComposedFrame,
+        pybind11::arg("background"), pybind11::arg("layer_background"), pybind11::arg("object_model"),
+        pybind11::arg("layered"), pybind11::arg("xyz"), pybind11::arg("scaling"), pybind11::arg("rotation"),
+        pybind11::arg("opacity"), pybind11::arg("features_dc"), pybind11::arg("features_rest"), pybind11::arg("flip"),
+        pybind11::arg("poses"), pybind11::arg("idft"), pybind11::arg("scale_modifier"), pybind11::arg("viewmatrix"),
+        pybind11::arg("projmatrix"), pybind11::arg("tan_fovx"), pybind11::arg("tan_fovy"),
+        pybind11::arg("image_height"), pybind11::arg("image_width"), pybind11::arg("degree"), pybind11::arg("campos"),
+        pybind11::arg("debug"), pybind11::arg("sky_cube"), pybind11::arg("ray_matrix"), pybind11::arg("sky_fill"),
+        pybind11::arg("clamp"), pybind11::arg("want_planes"), pybind11::arg("want_rgb8"), pybind11::arg("truncate"),
+        pybind11::arg("out_rgb8"),
+        pybind11::arg("affine") = pybind11::none());
   m.def("compose", &Compose);
   m.def("compose_features", &ComposeFeatures);
   m.def("compose_features_backward", &ComposeFeaturesBackward);

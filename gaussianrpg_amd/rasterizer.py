@@ -240,7 +240,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward_frame(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                       cov3D_precomp=None, layer_class=None, layer_bg=None, sky_cube=None, ray_matrix=None,
-                      sky_fill=0.0, clamp=True, planes=False, rgb8=True, truncate=True, out=None):
+                      sky_fill=0.0, clamp=True, planes=False, rgb8=True, truncate=True, out=None, affine=None):
         """Evaluation only: the op AND what the reference's callers do with its colour per frame, in the render's own
         epilogue (additive; C ABI grpg_forward_frame) -- render_kernel's clamp, ``rgb + sky_cubemap(rays) * (1 - acc)``
         and the second clamp of StreetGaussianRenderer.render (lib/models/street_gaussian_renderer.py:106-116,
@@ -251,7 +251,14 @@ class GaussianRasterizer(nn.Module):
         (C ABI 7, ``out_rgb8_on_host``; no copy behind the launch; synchronise with the stream before reading).  sky_cube: [6,res,res,3] (``SkyCubeMap.sky_cube_map``) with ray_matrix =
         ``gaussianrpg_amd.sky.ray_matrix(K, w2c)``, or None; layer_class: a layered frame (forward_layers) with the
         epilogue on the composition; planes=False: the float planes are not even written.  Bit-identical to the
-        chain forward() / forward_layers() -> clamp -> SkyCubeMap.composite -> trajectory.pack_hwc."""
+        chain forward() / forward_layers() -> clamp -> SkyCubeMap.composite -> trajectory.pack_hwc.
+
+        affine: the colour correction of a scene trained with ``use_color_correction`` (street_gaussian_renderer.py:113),
+        a float32 [3,4] DEVICE tensor such as ``ColorCorrection.get_affine_trans(camera)`` (a view of the parameter is
+        used as it is; the host never reads it; C ABI grpg_bind_frame_correction).  The epilogue then applies
+        ``clamp(A[:, :3] (rgb + sky (1 - acc)) + A[:, 3])`` between the sky composite and the final clamp, to the
+        composition only: bit-identical to ``appearance.corrected_frame`` / ``sky_corrected`` on the planes of
+        ``forward_frame(planes=True, rgb8=False, sky_cube=None, clamp=clamp)``, without writing those planes."""
         rs = self.raster_settings
         _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp)
         layered = layer_class is not None
@@ -265,7 +272,7 @@ class GaussianRasterizer(nn.Module):
                 rs.bg, layer_bg, layer_class, means3D, colors_precomp, opacities, scales, rotations,
                 rs.scale_modifier, cov3D_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
                 rs.image_height, rs.image_width, shs, rs.sh_degree, rs.campos, rs.debug, sky_cube, ray_matrix,
-                float(sky_fill), bool(clamp), bool(planes), bool(rgb8), bool(truncate), out)
+                float(sky_fill), bool(clamp), bool(planes), bool(rgb8), bool(truncate), out, affine)
         return _frame_result(ret, rgb8, planes, layered)
 
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):

@@ -241,6 +241,34 @@ GRPG_API int grpg_forward_frame(grpg_alloc_fn geometry_alloc, void* geometry_use
                  int* radii, int debug, void* hip_stream, const grpg_frame_epilogue* epilogue);
 
 /*
+ * Colour correction inside the frame epilogue (additive; GRPG_ABI_VERSION stays 7 and grpg_frame_epilogue keeps its
+ * layout).  A scene trained with use_color_correction maps every pixel through a 3x4 matrix between the sky composite
+ * and the final clamp (street_gaussian_renderer.py:105-116).  grpg_bind_frame_correction binds that matrix for the
+ * NEXT grpg_forward_frame / grpg_forward_composed_frame on this thread, whose epilogue then computes
+ *     rgb = clamp(color)                              (clamp != 0)
+ *     x   = rgb + clamp(sky) * (1 - acc)              unclamped; rgb itself without a sky cube
+ *     y_i = fma(A_i2, x_2, fma(A_i1, x_1, fma(A_i0, x_0, A_i3)))
+ *     rgb = clamp(y)                                  (clamp != 0); bytes from the clamped value as ever
+ * -- bit for bit what grpg_color_correct_forward gives on the planes of the same frame rendered with clamp, without
+ * sky and bytes, when it is handed the same matrix, sky inputs (no mask, no jitter), clamp_out = clamp and truncate
+ * (tests/test_gpu_frame_corrected.py).  out_color, when given, receives y; depth and alpha are unchanged.  On a
+ * layered frame the composition alone is corrected (the reference's render_background / render_object are not
+ * corrected either); a frame without Gaussians is corrected too.
+ *   affine_device  DEVICE float[12], row-major [3,4] (e.g. the view affine_trans[id] of the parameter, or the output
+ *                  of the use_mlp network); the host never reads it.  Lifetime: the rule of the model arrays -- valid
+ *                  and unchanged until the consuming call's work on its stream has run; written by earlier work on the
+ *                  same stream is fine.
+ * grpg_bind_frame_correction touches no device: GRPG_OK, or GRPG_ERR_INVALID_ARGUMENT for NULL -- and a refused bind
+ * leaves no binding.  Binding again replaces the pending binding.  grpg_frame_correction_bound is a pure query: 1
+ * while a binding waits, else 0.  The consuming call takes the binding whether it succeeds or fails
+ * (GRPG_ERR_NO_DEVICE included) and returns GRPG_ERR_INVALID_ARGUMENT with a message when its `epilogue` is NULL: a
+ * correction needs an epilogue to run in.  Every other entry point leaves the binding alone.  It composes with
+ * grpg_bind_device_poses on one grpg_forward_composed_frame.
+ */
+GRPG_API int grpg_bind_frame_correction(const float* affine_device);
+GRPG_API int grpg_frame_correction_bound(void);
+
+/*
  * Deferred frames (additive; for frame loops that do not need num_rendered at once: trajectory /
  * batch rendering).  grpg_forward_deferred enqueues the frame like grpg_forward_flags but does NOT
  * wait for num_rendered: the host returns as soon as the launches are queued, so any number of
@@ -627,6 +655,7 @@ GRPG_API int grpg_sky_backward_ex(const float* cube, int res, const float* ray_m
  *               the .hip file's header); needs workspace: device, 4-byte aligned,
  *               grpg_color_correct_workspace_bytes(width, height) bytes (a pure size query: no device needed, 0 for
  *               sizes <= 0); at least one of the two outputs
+ * (The forward map inside the one-call frame's own epilogue, without the planes in between: grpg_bind_frame_correction.)
  * Both run asynchronously on hip_stream.  Purely additive exports: GRPG_ABI_VERSION stays 7.  Returns GRPG_OK,
  * GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT for a NULL rgb / affine / grad_out, no output at all,
  * sizes <= 0, sky inputs given in part, or grad_affine without a workspace. */
