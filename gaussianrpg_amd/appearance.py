@@ -14,10 +14,19 @@ The matrix is read from device memory by the kernel (``affine_trans[id]`` is a v
 backward recomputes the kernel's input instead of storing it and sums the matrix gradient in a fixed order without
 atomics: identical calls give identical bits.
 
-Covered: the explicit variant (``use_mlp: false``), both modes, training and evaluation.  Not covered: the layers of
-the ``use_mlp`` variant -- they stay PyTorch; the [3,4] matrix they regress goes through ``color_correct`` unchanged,
-gradient included -- and colour correction inside ``forward_frame``'s own epilogue: such a scene takes
+Covered: the explicit variant (``use_mlp: false``), both modes, training and evaluation.  The layers of the ``use_mlp``
+variant are ``ColorCorrectionMLP`` (below); the [3,4] matrix they regress goes through ``color_correct`` unchanged,
+gradient included.  Not covered: colour correction inside ``forward_frame``'s own epilogue: such a scene takes
 ``forward_frame(planes=True, rgb8=False, sky_cube=None, clamp=True)`` and then ``corrected_frame``.
+
+The ``use_mlp: true`` variant (csrc/color_mlp.hip) is ``ColorCorrectionMLP``: the matrix is regressed from the camera
+pose itself -- ``ego_pose @ extrinsic``, ``matrix_to_axis_angle``, four ``Linear`` layers, ``+ eye(4)[:3]`` -- so it
+exists for poses that were never trained, which is what a closed-loop simulator renders:
+
+    cc = ColorCorrectionMLP().cuda()
+    A = cc.affines(ego_pose, extrinsic)                              # [T,2,3,4] (0 plain, 1 sky): ONE launch
+    frame = rast.forward_frame(..., affine=A[0, 0])                  # the matrix never visits the host
+    rgb = cc(camera, rgb); loss = loss + cc.regularization_loss(camera)      # training: one launch each way
 """
 import torch
 import torch.nn as nn
@@ -87,8 +96,8 @@ class ColorCorrection(nn.Module):
     ``num_corrections`` is ``metadata['num_images']`` for ``mode='image'`` (one matrix per ``camera.id``) and
     ``metadata['num_cams']`` for ``mode='sensor'`` (one per ``camera.meta['cam']``).
 
-    The ``use_mlp`` variant is NOT constructed here: its layers are ordinary PyTorch; feed the matrix they regress
-    to ``color_correct``.  The optimizer is the caller's (``optim.FusedAdam`` or torch's)."""
+    The ``use_mlp`` variant is NOT constructed here: it is ``ColorCorrectionMLP``, whose matrix goes through
+    ``color_correct`` like this one's.  The optimizer is the caller's (``optim.FusedAdam`` or torch's)."""
 
     def __init__(self, num_corrections: int, mode: str = "image"):
         super().__init__()
@@ -135,6 +144,160 @@ class ColorCorrection(nn.Module):
         affine_trans_sky = self.get_affine_trans(camera, use_sky=True)
         loss = torch.abs(affine_trans - self.identity_matrix) + torch.abs(affine_trans_sky - self.identity_matrix)
         return loss.mean()
+
+
+class _ColorMlp(torch.autograd.Function):
+    """(affine [T,2,3,4], reg [T], x [T,6]) from the poses and the sixteen parameters (eight weights, then eight
+    biases, network-major).  One launch each way; nothing flows back to the poses."""
+
+    @staticmethod
+    def forward(ctx, ego_pose, extrinsic, state, *params):
+        weights, biases = list(params[:8]), list(params[8:])
+        affine, x, reg, hidden = _C.color_mlp_forward(weights, biases, ego_pose, extrinsic, True, True)
+        ctx.save_for_backward(x, hidden, affine, *params)
+        ctx.state = state
+        ctx.mark_non_differentiable(x)
+        ctx.set_materialize_grads(False)           # an absent upstream gradient stays None: a NULL in the backward
+        return affine, reg, x
+
+    @staticmethod
+    def backward(ctx, grad_affine, grad_reg, _grad_x):
+        x, hidden, affine, *params = ctx.saved_tensors
+        if ctx.state is not None:
+            ctx.state["consumed"] = True           # the node's buffers go with this call: the cache entry is spent
+        if grad_affine is None and grad_reg is None:
+            return (None,) * (3 + len(params))
+        gw, gb = _C.color_mlp_backward(list(params[:8]), list(params[8:]), x, hidden, affine, grad_affine, grad_reg)
+        return (None, None, None) + tuple(gw) + tuple(gb)
+
+
+def _mlp(input_ch: int = 6, dim: int = 64) -> nn.Sequential:
+    net = nn.Sequential(nn.Linear(input_ch, dim), nn.ReLU(), nn.Linear(dim, dim), nn.ReLU(), nn.Linear(dim, dim),
+                        nn.ReLU(), nn.Linear(dim, 12))
+    net[6].weight.data.fill_(0)
+    net[6].bias.data.fill_(0)
+    return net
+
+
+MLP_KEYS = tuple("%s.%d.%s" % (net, layer, kind) for net in ("affine_trans", "affine_trans_sky")
+                 for layer in (0, 2, 4, 6) for kind in ("weight", "bias"))
+
+
+class ColorCorrectionMLP(nn.Module):
+    """Drop-in for the ``use_mlp: true`` variant of lib/models/color_correction.py:ColorCorrection: the two
+    ``nn.Sequential`` networks of the reference's shape under the reference's names (state-dict keys
+    ``affine_trans.0.weight`` ... ``affine_trans_sky.6.bias``, last layer zero-initialised), the same
+    ``get_affine_trans`` / ``forward`` / ``regularization_loss`` and the same ``{'params': ...}`` state-dict layout.
+    The matrix is regressed from the camera pose itself (``camera.ego_pose @ camera.extrinsic``), so it exists for
+    poses that were never trained.  ``mode`` is kept for the reference's configuration; the networks do not depend on
+    it.
+
+    ``affines(ego_pose, extrinsic)`` -> ``[T,2,3,4]`` (index 0 plain, 1 sky) is ONE launch for T cameras and both
+    networks; ``affines_and_reg`` returns the regulariser ``[T]`` of the same launch as well.  Both are differentiable
+    w.r.t. the parameters (one backward launch for all sixteen gradients); the pose gets no gradient, as in the
+    reference.  A row ``affines(...)[t, 0]`` is directly what ``color_correct`` / ``forward_frame(affine=...)`` take.
+
+    Cache.  One training iteration calls ``get_affine_trans`` plain, sky and ``regularization_loss`` on the same
+    camera; the three share the last launch when NOTHING it read can have changed: the same camera object, the same
+    pose tensors at the same version, the same parameter storages at the same versions (an optimizer step, ``copy_``
+    or ``load_state_dict`` bumps the version; a replaced ``.data`` changes the storage), the same grad mode, and its
+    autograd node not yet backpropagated.  The three results then hang off ONE autograd node: backpropagate them
+    together (the sum of the losses, as the trainer does), or pass ``retain_graph=True`` to separate backward calls,
+    or set ``cache = False`` -- then every method call launches once.  Poses held as numpy arrays are never cached.
+
+    No CPU path.  The optimizer is the caller's."""
+
+    def __init__(self, mode: str = "image"):
+        super().__init__()
+        if mode not in ("image", "sensor"):
+            raise ValueError("Invalid mode: %s" % mode)
+        self.mode = mode
+        self.register_buffer("identity_matrix", torch.eye(4).float()[:3].clone(), persistent=False)
+        self.affine_trans = _mlp()
+        self.affine_trans_sky = _mlp()
+        self.cur_affine_trans = None
+        self.cache = True
+        self._cached = None        # (key, camera, state, affine, reg, x)
+
+    def __getstate__(self):
+        # copies and pickles leave the cache behind: it holds results with an autograd history and a camera
+        state = self.__dict__.copy()
+        state["_cached"] = None
+        return state
+
+    def save_state_dict(self, is_final: bool = True):
+        state_dict = {"params": self.state_dict()}
+        if not is_final and getattr(self, "optimizer", None) is not None:
+            state_dict["optimizer"] = self.optimizer.state_dict()
+        return state_dict
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        params = state_dict["params"]
+        if "affine_trans" in params:
+            raise ValueError("the state dict holds the explicit variant of the colour correction (affine_trans "
+                             "[N,3,4]): load it into gaussianrpg_amd.appearance.ColorCorrection")
+        return super().load_state_dict(params, strict=strict)
+
+    def get_id(self, camera):
+        if self.mode == "image":
+            return camera.id
+        return camera.meta["cam"]
+
+    def _params(self):
+        nets = (self.affine_trans, self.affine_trans_sky)
+        weights = [net[l].weight for net in nets for l in (0, 2, 4, 6)]
+        biases = [net[l].bias for net in nets for l in (0, 2, 4, 6)]
+        if not weights[0].is_cuda:
+            raise RuntimeError("no CPU path: ColorCorrectionMLP runs on a ROCm/HIP device only")
+        return weights + biases
+
+    def _poses(self, ego_pose, extrinsic, params):
+        dev = params[0].device
+        ego = torch.as_tensor(ego_pose, dtype=torch.float32, device=dev)
+        ext = torch.as_tensor(extrinsic, dtype=torch.float32, device=dev)
+        return ego.reshape(-1, 4, 4), ext.reshape(-1, 4, 4)
+
+    def affines_and_reg(self, ego_pose, extrinsic, _state=None):
+        """``(affine [T,2,3,4], reg [T], x [T,6])`` of ONE launch: ``ego_pose`` [T,4,4] (or [4,4]), ``extrinsic``
+        [T,4,4] or one [4,4] / [1,4,4] for all T.  ``reg[t]`` is ``regularization_loss`` of camera t; ``x`` the
+        axis-angle and translation the networks were fed (no gradient)."""
+        params = self._params()
+        ego, ext = self._poses(ego_pose, extrinsic, params)
+        return _ColorMlp.apply(ego.detach(), ext.detach(), _state, *params)
+
+    def affines(self, ego_pose, extrinsic):
+        return self.affines_and_reg(ego_pose, extrinsic)[0]
+
+    def _camera(self, camera):
+        """(affine [1,2,3,4], reg [1]) of one camera object, through the cache (class docstring)."""
+        ego, ext = camera.ego_pose, camera.extrinsic
+        if not (self.cache and isinstance(ego, torch.Tensor) and isinstance(ext, torch.Tensor)):
+            return self.affines_and_reg(ego, ext)[:2]
+        params = self._params()
+        key = (id(camera), id(ego), ego._version, id(ext), ext._version, torch.is_grad_enabled(),
+               tuple((id(p), p.data_ptr(), p._version, p.requires_grad) for p in params))
+        c = self._cached
+        if c is not None and c[0] == key and c[1] is camera and c[2] is ego and c[3] is ext \
+                and not c[4]["consumed"]:
+            return c[5], c[6]
+        state = {"consumed": False}
+        affine, reg, _ = self.affines_and_reg(ego, ext, state)
+        # the entry keeps the camera and its pose tensors alive, so their ids cannot be handed out again
+        self._cached = (key, camera, ego, ext, state, affine, reg)
+        return affine, reg
+
+    def get_affine_trans(self, camera, use_sky: bool = False):
+        affine_trans = self._camera(camera)[0][0, 1 if use_sky else 0]
+        self.cur_affine_trans = affine_trans
+        return affine_trans
+
+    def forward(self, camera, image: torch.Tensor, use_sky: bool = False):
+        return color_correct(image, self.get_affine_trans(camera, use_sky))
+
+    def regularization_loss(self, camera):
+        affine, reg = self._camera(camera)
+        self.cur_affine_trans = affine[0, 1]       # the reference's last get_affine_trans call is the sky one
+        return reg[0]
 
 
 def _sky_inputs(sky, rgb, camera, K, w2c, mask, jitter):

@@ -49,6 +49,10 @@ HIP_UNITS = {
     # colour correction of the frame behind the sky composite: the affine map and A^T g are explicit fmaf chains, the
     # gradient terms single products (no FMA contraction); no atomics, deterministic fixed-order reduction
     "color_correction.hip": ["-ffp-contract=off"],
+    # colour correction, use_mlp variant (pose -> the two 3x4 matrices): every layer a rounded multiply and a rounded
+    # add per term in ascending order, as the numpy restatement (tests/color_mlp_truth.py); divisions and square roots
+    # of the axis-angle correctly rounded; no atomics
+    "color_mlp.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # pose correction of the background: every step the single float32 operation of the numpy restatement
     # (tests/pose_correction_truth.py), divisions and square roots correctly rounded; no atomics, deterministic
     # fixed-order reduction of the row's gradient
@@ -92,8 +96,9 @@ HIP_UNITS = {
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept
 # next to the object as <unit>.remarks: the render launch's occupancy is a budget the sources promise
 # (render_fwd.hip render_min_waves; tests/test_render_resources.py reads the file), and so is
-# the eight waves per SIMD of the specialised preprocess instantiations (tests/test_preprocess_resources.py)
-REMARK_UNITS = ("render_fwd.hip", "preprocess.hip")
+# the eight waves per SIMD of the specialised preprocess instantiations (tests/test_preprocess_resources.py); the
+# use_mlp colour correction promises kernels without scratch (tests/test_color_mlp_host.py)
+REMARK_UNITS = ("render_fwd.hip", "preprocess.hip", "color_mlp.hip")
 
 
 def headers():

@@ -111,7 +111,8 @@ class LoadedScene:
     def color_correction_module(self, mode: str = "image", device="cpu"):
         """The file's colour correction as a ``gaussianrpg_amd.appearance.ColorCorrection`` on ``device``, or None when
         the file has none.  ``mode`` is the reference's ``cfg.model.color_correction.mode`` (the file does not record
-        it).  A file written with ``use_mlp: true`` raises: its layers are not constructed here."""
+        it).  A file written with ``use_mlp: true`` raises: its layers are not constructed here but by
+        ``color_correction_mlp``."""
         if self.color_correction is None:
             return None
         from .appearance import ColorCorrection
@@ -122,6 +123,23 @@ class LoadedScene:
                              % (self.source, sorted(p)[:2]))
         cc = ColorCorrection(int(p["affine_trans"].shape[0]), mode=mode)
         cc.load_state_dict({"params": p})
+        return cc.to(device)
+
+    def color_correction_mlp(self, mode: str = "image", device="cpu"):
+        """The file's colour correction as a ``gaussianrpg_amd.appearance.ColorCorrectionMLP`` on ``device`` when the
+        file was written with ``use_mlp: true`` (keys ``affine_trans.0.weight`` ... ``affine_trans_sky.6.bias``), or
+        None when the file has no colour correction.  An entry that lacks some of the sixteen tensors -- the explicit
+        variant among them: that one is ``color_correction_module`` -- raises, naming the missing keys."""
+        if self.color_correction is None:
+            return None
+        from .appearance import MLP_KEYS, ColorCorrectionMLP
+        p = self.color_correction
+        missing = [k for k in MLP_KEYS if k not in p]
+        if missing:
+            raise ValueError("%s: the color_correction entry is not a complete use_mlp variant, missing keys: %s"
+                             % (self.source, ", ".join(missing)))
+        cc = ColorCorrectionMLP(mode=mode)
+        cc.load_state_dict({"params": OrderedDict((k, p[k]) for k in MLP_KEYS)})
         return cc.to(device)
 
     def pose_correction_module(self, mode: str = "image", device="cpu", active: bool = True):

@@ -1458,6 +1458,114 @@ std::tuple<torch::Tensor, torch::Tensor> ColorCorrectBackward(
   return std::make_tuple(grad_x, grad_affine);
 }
 
+// ---- colour correction, use_mlp variant (gaussianrpg_amd/appearance.py ColorCorrectionMLP; csrc/color_mlp.hip) ----
+namespace {
+const int64_t kColorMlpShape[4][2] = {{64, 6}, {64, 64}, {64, 64}, {12, 64}};
+
+// weights / biases: eight tensors each, network-major ([affine_trans layers 0..3], [affine_trans_sky layers 0..3]);
+// taken in place: float32, contiguous, on one device
+torch::Device color_mlp_check(const std::vector<torch::Tensor>& weights, const std::vector<torch::Tensor>& biases,
+                              const char* what) {
+  TORCH_CHECK(weights.size() == 8 && biases.size() == 8, what, ": eight weights and eight biases (two networks x four layers)");
+  TORCH_CHECK(weights[0].is_cuda(), what, ": the parameters must live on a ROCm/HIP device (no CPU path)");
+  const torch::Device dev = weights[0].device();
+  for (int i = 0; i < 8; i++) {
+    const int64_t* s = kColorMlpShape[i & 3];
+    TORCH_CHECK(weights[i].device() == dev && weights[i].scalar_type() == torch::kFloat32 &&
+                    weights[i].is_contiguous() && weights[i].dim() == 2 && weights[i].size(0) == s[0] &&
+                    weights[i].size(1) == s[1],
+                what, ": weight ", i, " must be a contiguous float32 tensor [", s[0], ",", s[1], "] on one device");
+    TORCH_CHECK(biases[i].device() == dev && biases[i].scalar_type() == torch::kFloat32 && biases[i].is_contiguous() &&
+                    biases[i].dim() == 1 && biases[i].size(0) == s[0],
+                what, ": bias ", i, " must be a contiguous float32 tensor [", s[0], "] on one device");
+  }
+  return dev;
+}
+
+grpg_color_mlp_params color_mlp_params(const std::vector<torch::Tensor>& weights,
+                                       const std::vector<torch::Tensor>& biases) {
+  grpg_color_mlp_params p;
+  for (int i = 0; i < 8; i++) {
+    p.weight[i >> 2][i & 3] = weights[i].data_ptr<float>();
+    p.bias[i >> 2][i & 3] = biases[i].data_ptr<float>();
+  }
+  return p;
+}
+}  // namespace
+
+// (affine [T,2,3,4], x [T,6], reg [T] or undefined, hidden [T,2,3,64] or undefined)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> ColorMlpForward(
+    const std::vector<torch::Tensor>& weights, const std::vector<torch::Tensor>& biases, const torch::Tensor& ego_pose,
+    const torch::Tensor& extrinsic, const bool want_reg, const bool want_hidden) {
+  const torch::Device dev = color_mlp_check(weights, biases, "color_mlp_forward");
+  TORCH_CHECK(ego_pose.device() == dev && ego_pose.scalar_type() == torch::kFloat32 && ego_pose.dim() == 3 &&
+                  ego_pose.size(0) >= 1 && ego_pose.size(0) <= (1 << 20) && ego_pose.size(1) == 4 &&
+                  ego_pose.size(2) == 4,
+              "color_mlp_forward: ego_pose must be a float32 tensor [T,4,4] (1 <= T <= 2^20) on the parameters' device");
+  const int T = (int)ego_pose.size(0);
+  TORCH_CHECK(extrinsic.device() == dev && extrinsic.scalar_type() == torch::kFloat32 && extrinsic.dim() == 3 &&
+                  (extrinsic.size(0) == T || extrinsic.size(0) == 1) && extrinsic.size(1) == 4 &&
+                  extrinsic.size(2) == 4,
+              "color_mlp_forward: extrinsic must be a float32 tensor [T,4,4] or [1,4,4] on the parameters' device");
+  const torch::Tensor ego = ego_pose.contiguous(), ext = extrinsic.contiguous();
+  const int shared = (extrinsic.size(0) == 1 && T > 1) ? 1 : 0;
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const auto opt = ego.options();
+  torch::Tensor affine = torch::empty({T, 2, 3, 4}, opt), x = torch::empty({T, 6}, opt), reg, hidden;
+  if (want_reg) reg = torch::empty({T}, opt);
+  if (want_hidden) hidden = torch::empty({T, 2, 3, 64}, opt);
+  const grpg_color_mlp_params p = color_mlp_params(weights, biases);
+  run("grpg_color_mlp_forward", [&](void* stream) {
+    return grpg_color_mlp_forward(&p, T, ego.data_ptr<float>(), ext.data_ptr<float>(), shared,
+                                  affine.data_ptr<float>(), x.data_ptr<float>(),
+                                  want_reg ? reg.data_ptr<float>() : nullptr,
+                                  want_hidden ? hidden.data_ptr<float>() : nullptr, stream);
+  });
+  return std::make_tuple(affine, x, reg, hidden);
+}
+
+// (weight gradients x 8, bias gradients x 8), network-major like the parameters.  grad_affine [T,2,3,4] and / or
+// grad_reg [T]; affine: the forward's output (read only with grad_reg).
+std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>> ColorMlpBackward(
+    const std::vector<torch::Tensor>& weights, const std::vector<torch::Tensor>& biases, const torch::Tensor& x,
+    const torch::Tensor& hidden, const torch::Tensor& affine, const c10::optional<torch::Tensor>& grad_affine,
+    const c10::optional<torch::Tensor>& grad_reg) {
+  const torch::Device dev = color_mlp_check(weights, biases, "color_mlp_backward");
+  TORCH_CHECK(x.device() == dev && x.scalar_type() == torch::kFloat32 && x.is_contiguous() && x.dim() == 2 &&
+                  x.size(0) >= 1 && x.size(0) <= (1 << 20) && x.size(1) == 6,
+              "color_mlp_backward: x must be the forward's contiguous float32 [T,6]");
+  const int64_t T = x.size(0);
+  const auto is = [&](const torch::Tensor& t, at::IntArrayRef shape) {
+    return t.device() == dev && t.scalar_type() == torch::kFloat32 && t.sizes() == shape;
+  };
+  TORCH_CHECK(is(hidden, {T, 2, 3, 64}) && hidden.is_contiguous() && is(affine, {T, 2, 3, 4}) && affine.is_contiguous(),
+              "color_mlp_backward: hidden [T,2,3,64] and affine [T,2,3,4] must be the forward's outputs");
+  const bool has_ga = grad_affine.has_value() && grad_affine->defined();
+  const bool has_gr = grad_reg.has_value() && grad_reg->defined();
+  TORCH_CHECK(has_ga || has_gr, "color_mlp_backward: give grad_affine, grad_reg, or both");
+  TORCH_CHECK(!has_ga || is(*grad_affine, {T, 2, 3, 4}), "color_mlp_backward: grad_affine must be float32 [T,2,3,4]");
+  TORCH_CHECK(!has_gr || is(*grad_reg, {T}), "color_mlp_backward: grad_reg must be float32 [T]");
+  torch::Tensor ga, gr;
+  if (has_ga) ga = grad_affine->contiguous();
+  if (has_gr) gr = grad_reg->contiguous();
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  std::vector<torch::Tensor> gw, gb;
+  grpg_color_mlp_grads g;
+  for (int i = 0; i < 8; i++) {
+    gw.push_back(torch::empty_like(weights[i]));
+    gb.push_back(torch::empty_like(biases[i]));
+    g.weight[i >> 2][i & 3] = gw[i].data_ptr<float>();
+    g.bias[i >> 2][i & 3] = gb[i].data_ptr<float>();
+  }
+  const grpg_color_mlp_params p = color_mlp_params(weights, biases);
+  run("grpg_color_mlp_backward", [&](void* stream) {
+    return grpg_color_mlp_backward(&p, (int)T, x.data_ptr<float>(), hidden.data_ptr<float>(),
+                                   affine.data_ptr<float>(), has_ga ? ga.data_ptr<float>() : nullptr,
+                                   has_gr ? gr.data_ptr<float>() : nullptr, &g, stream);
+  });
+  return std::make_tuple(gw, gb);
+}
+
 // ---- pose correction of the background (gaussianrpg_amd/pose_correction.py; csrc/pose_correction.hip) ----
 namespace {
 // xyz [N,3] and / or rotation [N,4] (float32, on a device, the same N); rot [4] / trans [3] float32 on that device (a
@@ -2842,6 +2950,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("fill") = 0.0, pybind11::arg("acc") = pybind11::none(), pybind11::arg("mask") = pybind11::none(),
         pybind11::arg("jitter") = pybind11::none());
   m.def("color_correct_workspace_bytes", [](int H, int W) { return grpg_color_correct_workspace_bytes(W, H); });
+  // colour correction, use_mlp variant (appearance.py ColorCorrectionMLP): (affine, x, reg, hidden) / (gw x 8, gb x 8)
+  m.def("color_mlp_forward", &ColorMlpForward, pybind11::arg("weights"), pybind11::arg("biases"),
+        pybind11::arg("ego_pose"), pybind11::arg("extrinsic"), pybind11::arg("want_reg") = true,
+        pybind11::arg("want_hidden") = true);
+  m.def("color_mlp_backward", &ColorMlpBackward, pybind11::arg("weights"), pybind11::arg("biases"), pybind11::arg("x"),
+        pybind11::arg("hidden"), pybind11::arg("affine"), pybind11::arg("grad_affine") = pybind11::none(),
+        pybind11::arg("grad_reg") = pybind11::none());
   // pose correction of the background (pose_correction.py): (xyz', rotation') / (g_xyz, g_rotation, g_rot, g_trans)
   m.def("pose_correct", &PoseCorrect, pybind11::arg("xyz"), pybind11::arg("rotation"), pybind11::arg("rot"),
         pybind11::arg("trans"));

@@ -378,10 +378,56 @@ def render_corrected(rgb: torch.Tensor, acc: torch.Tensor, affine: torch.Tensor,
         return y if train else torch.clamp(y, 0.0, 1.0)
 
 
-def simulator_frame_corrected(scene: Scene, cam: CameraTensors, affine: torch.Tensor, sky=None, K=None, w2c=None, *,
+def _axis_angle_torch(matrix: torch.Tensor) -> torch.Tensor:
+    """[B,4,4] -> [B,6]: the axis-angle of the rotation block in front of the translation column, in ordinary PyTorch
+    with the boolean-mask indexing such code is usually written with (every masked read or write on a device tensor
+    is a ``nonzero`` and a host wait): the unfused route of ``camera_affine``, written from csrc/color_mlp.hip's
+    header, steps b and c."""
+    m = matrix[..., :3, :3].reshape(-1, 9)
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = m.unbind(-1)
+    s = torch.stack([1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22], -1)
+    q_abs = torch.zeros_like(s)
+    positive = s > 0
+    q_abs[positive] = torch.sqrt(s[positive])
+    rows = torch.stack([torch.stack([q_abs[:, 0] ** 2, m21 - m12, m02 - m20, m10 - m01], -1),
+                        torch.stack([m21 - m12, q_abs[:, 1] ** 2, m10 + m01, m02 + m20], -1),
+                        torch.stack([m02 - m20, m10 + m01, q_abs[:, 2] ** 2, m12 + m21], -1),
+                        torch.stack([m10 - m01, m20 + m02, m21 + m12, q_abs[:, 3] ** 2], -1)], -2)
+    rows = rows / (2.0 * q_abs[..., None].clamp_min(0.1))
+    pick = torch.nn.functional.one_hot(q_abs.argmax(-1), 4) > 0.5
+    q = rows[pick, :].reshape(-1, 4)
+    n = torch.sqrt((q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2]) + q[:, 3] * q[:, 3])[:, None]
+    half = torch.atan2(n, q[:, :1])
+    angle = 2.0 * half
+    small = angle.abs() < 1e-6
+    div = torch.empty_like(angle)
+    div[~small] = torch.sin(half[~small]) / angle[~small]
+    div[small] = 0.5 - (angle[small] * angle[small]) / 48.0
+    return torch.cat([q[:, 1:] / div, matrix[..., :3, 3].reshape(-1, 3)], -1)
+
+
+def camera_affine(module, cam, fused: bool = True, use_sky: bool = False) -> torch.Tensor:
+    """The [3,4] colour-correction matrix an ``appearance.ColorCorrectionMLP`` regresses for a camera object with
+    ``ego_pose`` / ``extrinsic`` [4,4] device tensors (color_correction.py:110-116).
+      fused=True   ``module.affines``: one launch, no host wait
+      fused=False  the same computation in ordinary PyTorch: the 4x4 product, ``_axis_angle_torch``, the module's own
+                   ``nn.Sequential`` and ``+ identity_matrix`` -- several dozen launches and a host wait per masked
+                   index (tools/bench_color_mlp.py counts both)
+    Differentiable w.r.t. the module's parameters either way."""
+    if fused:
+        return module.affines(cam.ego_pose, cam.extrinsic)[0, 1 if use_sky else 0]
+    x = _axis_angle_torch((cam.ego_pose @ cam.extrinsic).unsqueeze(0)).squeeze(0)
+    net = module.affine_trans_sky if use_sky else module.affine_trans
+    return net(x).view(3, 4) + module.identity_matrix
+
+
+def simulator_frame_corrected(scene: Scene, cam: CameraTensors, affine, sky=None, K=None, w2c=None, *,
                               fused: bool = True, truncate: bool = True, one_call: bool = False,
-                              out: Optional[torch.Tensor] = None) -> np.ndarray:
-    """simulator_frame for a scene trained with colour correction.
+                              out: Optional[torch.Tensor] = None, camera=None) -> np.ndarray:
+    """simulator_frame for a scene trained with colour correction.  ``affine``: the camera's [3,4] device matrix, or
+    an ``appearance.ColorCorrectionMLP`` with ``camera`` (an object with ``ego_pose`` / ``extrinsic`` device tensors):
+    the matrix is then ``affines(...)[0, 0]`` of one launch and goes from device memory into the frame, it never
+    visits the host.
       one_call=True  ``forward_frame(..., affine=affine, out=out)``: composite, correction, clamp and bytes inside the
                      render's own epilogue; ``out``: a pinned host tensor the bytes are stored into while the render
                      runs (allocated here if absent).  No float plane is written, nothing is copied behind the launch.
@@ -397,6 +443,10 @@ def simulator_frame_corrected(scene: Scene, cam: CameraTensors, affine: torch.Te
     rast = GaussianRasterizer(GaussianRasterizationSettings(**settings_kwargs(cam, scene.sh_degree,
                                                                               bg=torch.zeros(3, device=dev))))
     with torch.no_grad():
+        if isinstance(affine, appearance.ColorCorrectionMLP):
+            if camera is None:
+                raise ValueError("a ColorCorrectionMLP needs the camera whose ego_pose / extrinsic it regresses from")
+            affine = affine.affines(camera.ego_pose, camera.extrinsic)[0, 0]
         if one_call:
             from .sky import ray_matrix
             if out is None:

@@ -672,6 +672,43 @@ GRPG_API int grpg_color_correct_backward(int width, int height, const float* rgb
                                          const float* grad_out, float* grad_x, float* grad_affine, void* workspace,
                                          void* hip_stream);
 
+/* ---- colour correction, use_mlp variant: camera pose -> the 3x4 matrices (additive; csrc/color_mlp.hip) ----
+ * ColorCorrection.get_affine_trans with use_mlp: true (lib/models/color_correction.py:24-50, 110-116): for each of T
+ * cameras c2w = ego_pose @ extrinsic, matrix_to_axis_angle (general_utils.py:148-218, 356-392), then for BOTH networks
+ * (index 0: affine_trans, 1: affine_trans_sky) Linear(6,64) ReLU Linear(64,64) ReLU Linear(64,64) ReLU Linear(64,12),
+ * view(3,4) + eye(4)[:3].  The branch table of the axis-angle and the arithmetic order of the layers are in the .hip
+ * file's header.  ONE launch each way.
+ *   params       the sixteen tensors as nn.Linear holds them, DEVICE, read in place: weight[n][l] is [out,in]
+ *                row-major ([64,6], [64,64], [64,64], [12,64]), bias[n][l] is [out]
+ *   ego_pose     device [T,4,4] row-major;  extrinsic  device [T,4,4], or [4,4] for all T with extrinsic_shared != 0
+ *   affine       optional device [T,2,3,4]: row [t][0] is what grpg_bind_frame_correction and grpg_color_correct_* take
+ *   x            optional device [T,6]: the axis-angle and the translation the networks are fed
+ *   reg          optional device [T]: mean(|A - I| + |A_sky - I|) (regularization_loss), twelve terms added in index
+ *                order inside the camera's workgroup; at least one of affine / x / reg
+ *   hidden       optional device [T,2,3,64]: the post-ReLU vectors, for the backward
+ * grpg_color_mlp_backward: the forward's x and hidden, and its affine when grad_reg is given; grad_affine [T,2,3,4]
+ * and / or grad_reg [T] are the upstream gradients (grad_reg[t] * sign(A - I) / 12 is added to both networks' output
+ * gradient inside the kernel).  grads: the sixteen gradient tensors in the parameters' layout, every element
+ * overwritten: sums over t in ascending order, no atomics, no workspace (identical calls give identical bits).
+ * Nothing flows back to the pose.
+ * Both run asynchronously on hip_stream.  Purely additive exports: GRPG_ABI_VERSION stays 7.  Returns GRPG_OK,
+ * GRPG_ERR_NO_DEVICE without a device, GRPG_ERR_INVALID_ARGUMENT for a NULL or misaligned parameter / gradient tensor
+ * or pose, T <= 0 or T > 2^20, no output, no upstream gradient, or grad_reg without affine. */
+typedef struct grpg_color_mlp_params {
+  const float* weight[2][4];
+  const float* bias[2][4];
+} grpg_color_mlp_params;
+typedef struct grpg_color_mlp_grads {
+  float* weight[2][4];
+  float* bias[2][4];
+} grpg_color_mlp_grads;
+GRPG_API int grpg_color_mlp_forward(const grpg_color_mlp_params* params, int T, const float* ego_pose,
+                                    const float* extrinsic, int extrinsic_shared, float* affine, float* x, float* reg,
+                                    float* hidden, void* hip_stream);
+GRPG_API int grpg_color_mlp_backward(const grpg_color_mlp_params* params, int T, const float* x, const float* hidden,
+                                     const float* affine, const float* grad_affine, const float* grad_reg,
+                                     const grpg_color_mlp_grads* grads, void* hip_stream);
+
 /* ---- pose correction of the background (additive; csrc/pose_correction.hip) ----
  * PoseCorrection.correct_gaussian_xyz / correct_gaussian_rotation (lib/models/camera_pose.py:89-114): the learned
  * rigid transform of every background Gaussian, one per image or per frame.
