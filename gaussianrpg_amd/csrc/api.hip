@@ -459,48 +459,6 @@ CameraArgs make_camera(const float* view, const float* proj, const float* campos
   return c;
 }
 
-// The first half of every backward (grpg_backward, grpg_backward_composed*): the camera and the blob layouts of the
-// frame, then -- run() -- the blend backward into the cleared gradient records.  The caller owns it: the preprocess
-// backward takes cam / GL / rec / grad_rec from it, marks btr once more (2) and sets btg.done.
-struct BlendBackward {
-  const int P;
-  const CameraArgs cam;
-  const GeomLayout GL;
-  const ImgLayout IL;
-  char *const geom_buffer, *const binning_buffer, *const image_buffer;
-  const RecView rec;
-  float* const grad_rec;   // per-Gaussian gradient records (one 64-byte line each) in the tail of the geometry blob
-  BwdTimingRecord* btr = nullptr;
-  BwdTimingGuard btg{nullptr};
-
-  BlendBackward(int P_, int width, int height, const float* viewmatrix, const float* projmatrix, const float* campos,
-                float tan_fovx, float tan_fovy, char* geom_buffer_, char* binning_buffer_, char* image_buffer_)
-      : P(P_), cam(make_camera(viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy)),
-        GL(geom_layout((size_t)P_)), IL(img_layout((size_t)cam.gx * (size_t)cam.gy, (size_t)width * height)),
-        geom_buffer(geom_buffer_), binning_buffer(binning_buffer_), image_buffer(image_buffer_),
-        rec{(const float4*)(geom_buffer_ + GL.rec)}, grad_rec((float*)(geom_buffer_ + GL.grad_rec)) {}
-
-  // features [P,F] / dL_dpix_features [F,H,W] / dL_dfeatures [P,F] (accumulated into): NULL at F == 0
-  int run(hipStream_t stream, int debug, int R, const float* background, const float* alphas, const float* features,
-          int F, const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dalphas,
-          const float* dL_dpix_features, float* dL_dfeatures) {
-    // the point list is the first array of the binning blob whatever capacity it was carved for
-    const uint32_t* point_list = (const uint32_t*)(binning_buffer + bin_layout(0).val_a);
-    const uint2* ranges = (const uint2*)(image_buffer + IL.ranges);
-    const uint32_t* n_contrib = (const uint32_t*)(image_buffer + IL.n_contrib);
-    HIP_TRY(hipMemsetAsync(grad_rec, 0, (size_t)P * GRAD_STRIDE * sizeof(float), stream));
-    btg.r = btr = bwd_timing_begin(stream);
-    launch_render_backward(stream, ranges, point_list, rec, features, F, cam.W, cam.H, cam.gx, cam.gy, background,
-                           alphas, n_contrib, (const uint32_t*)(image_buffer + IL.work), dL_dpix, dL_dpix_depth,
-                           dL_dalphas, dL_dpix_features, grad_rec, dL_dfeatures, (const BlobHeader*)binning_buffer,
-                           (const uint32_t*)(image_buffer + IL.ck_count),
-                           (const uint32_t*)(image_buffer + IL.bwd_ctl), (uint32_t)R);
-    STAGE_CHECK("render backward");
-    bwd_timing_mark(btr, 1, stream);
-    return GRPG_OK;
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -807,6 +765,110 @@ int validate(const FrameRequest& q) {
     return fail(GRPG_ERR_INVALID_ARGUMENT, "feature planes of a composed frame: not in a layered or deferred frame");
   return GRPG_OK;
 }
+
+// One backward as an entry point hands it to its body.  Every extern "C" backward fills the fields it has; the rest
+// stay zero / NULL.  All four fill the frame (set_frame).  grpg_backward: P, the flat tensors and its per-Gaussian
+// outputs; its semantic channels are the blend's feature channels (F = S, dL_dpix_features / dL_dfeatures =
+// dL_dpix_semantic / dL_dsemantic).  grpg_backward_composed: segs / nseg / grads and dL_dposes (set_model; P is the sum
+// of the counts, the body's); _features adds the feature planes (set_features), _objects the object-alpha plane.
+struct BackwardRequest {
+  const float *means3D = nullptr, *shs = nullptr, *colors_precomp = nullptr, *semantics = nullptr, *scales = nullptr,
+              *rotations = nullptr, *cov3D_precomp = nullptr;
+  const grpg_model_segment* segs = nullptr;
+  const grpg_model_segment_grad* grads = nullptr;
+  int nseg = 0, P = 0, D = 0, M = 0, R = 0;
+  const float *background = nullptr, *viewmatrix = nullptr, *projmatrix = nullptr, *campos = nullptr;
+  int width = 0, height = 0;
+  float scale_modifier = 0.f, tan_fovx = 0.f, tan_fovy = 0.f;
+  const int* radii = nullptr;
+  const float* alphas = nullptr;
+  char *geom_buffer = nullptr, *binning_buffer = nullptr, *image_buffer = nullptr, *feature_buffer = nullptr,
+       *workspace = nullptr;   // (workspace: the object-alpha plane's)
+  const float *dL_dpix = nullptr, *dL_dpix_depth = nullptr, *dL_dalphas = nullptr, *dL_dpix_features = nullptr;
+  int S = 0, normals = 0, F = 0;   // the blend's feature channels: F = 3 * normals + S composed, F = S flat
+  float* const* seg_dL_dsemantic = nullptr;
+  float *dL_dfeatures = nullptr, *dL_dmean2D = nullptr, *dL_dposes = nullptr;
+  const float *alpha_object = nullptr, *dL_dalpha_object = nullptr;   // alpha_object == NULL: no object-alpha plane
+  float *dL_dconic = nullptr, *dL_dopacity = nullptr, *dL_dcolor = nullptr, *dL_ddepth = nullptr,
+        *dL_dmean3D = nullptr, *dL_dcov3D = nullptr, *dL_dsh = nullptr, *dL_dscale = nullptr, *dL_drot = nullptr;
+  int debug = 0;
+  hipStream_t stream = nullptr;
+};
+
+// The frame: the camera, what the forward left, and the gradients of its three planes.
+void set_frame(BackwardRequest& q, int R, const float* background, int width, int height, float scale_modifier,
+               const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+               const int* radii, const float* alphas, char* geom_buffer, char* binning_buffer, char* image_buffer,
+               const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dalphas, float* dL_dmean2D, int debug,
+               void* hip_stream) {
+  q.R = R; q.background = background; q.width = width; q.height = height; q.scale_modifier = scale_modifier;
+  q.viewmatrix = viewmatrix; q.projmatrix = projmatrix; q.campos = campos; q.tan_fovx = tan_fovx;
+  q.tan_fovy = tan_fovy; q.radii = radii; q.alphas = alphas; q.geom_buffer = geom_buffer;
+  q.binning_buffer = binning_buffer; q.image_buffer = image_buffer; q.dL_dpix = dL_dpix;
+  q.dL_dpix_depth = dL_dpix_depth; q.dL_dalphas = dL_dalphas; q.dL_dmean2D = dL_dmean2D; q.debug = debug;
+  q.stream = (hipStream_t)hip_stream;
+}
+// The segments of a composition with the tables of their gradients, and its feature planes (F is formed here; the
+// body checks the split, check_feature_split, before anything reads it).
+void set_model(BackwardRequest& q, const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
+               int num_segments, int D, int M, float* dL_dposes) {
+  q.segs = segments; q.grads = grads; q.nseg = num_segments; q.D = D; q.M = M; q.dL_dposes = dL_dposes;
+}
+void set_features(BackwardRequest& q, float* const* seg_dL_dsemantic, int S, int normals, char* feature_buffer,
+                  const float* dL_dpix_features, float* dL_dfeatures) {
+  q.seg_dL_dsemantic = seg_dL_dsemantic; q.S = S; q.normals = normals; q.F = 3 * normals + S;
+  q.feature_buffer = feature_buffer; q.dL_dpix_features = dL_dpix_features; q.dL_dfeatures = dL_dfeatures;
+}
+
+// The frame of every backward (grpg_backward, grpg_backward_composed*): the camera and the blob layouts, then -- run()
+// -- the blend backward into the cleared gradient records; the caller's preprocess backward takes cam / GL / rec /
+// grad_rec from it, and finish() closes the call behind that launch.
+struct BlendBackward {
+  const BackwardRequest& q;
+  const int P;
+  const hipStream_t stream;
+  const int debug;
+  const CameraArgs cam;
+  const GeomLayout GL;
+  const ImgLayout IL;
+  const RecView rec;
+  float* const grad_rec;   // per-Gaussian gradient records (one 64-byte line each) in the tail of the geometry blob
+  BwdTimingRecord* btr = nullptr;
+  BwdTimingGuard btg{nullptr};
+
+  BlendBackward(const BackwardRequest& q_, int P_)
+      : q(q_), P(P_), stream(q_.stream), debug(q_.debug),
+        cam(make_camera(q_.viewmatrix, q_.projmatrix, q_.campos, q_.width, q_.height, q_.tan_fovx, q_.tan_fovy)),
+        GL(geom_layout((size_t)P_)), IL(img_layout((size_t)cam.gx * (size_t)cam.gy, (size_t)q_.width * q_.height)),
+        rec{(const float4*)(q_.geom_buffer + GL.rec)}, grad_rec((float*)(q_.geom_buffer + GL.grad_rec)) {}
+
+  // the point list is the first array of the binning blob whatever capacity it was carved for
+  const uint32_t* point_list() const { return (const uint32_t*)(q.binning_buffer + bin_layout(0).val_a); }
+  const uint2* ranges() const { return (const uint2*)(q.image_buffer + IL.ranges); }
+
+  // features [P,F] / q.dL_dpix_features [F,H,W] / q.dL_dfeatures [P,F] (accumulated into): NULL at F == 0
+  int run(const float* features) {
+    char* const image_buffer = q.image_buffer;
+    HIP_TRY(hipMemsetAsync(grad_rec, 0, (size_t)P * GRAD_STRIDE * sizeof(float), stream));
+    btg.r = btr = bwd_timing_begin(stream);
+    launch_render_backward(stream, ranges(), point_list(), rec, features, q.F, cam.W, cam.H, cam.gx, cam.gy,
+                           q.background, q.alphas, (const uint32_t*)(image_buffer + IL.n_contrib),
+                           (const uint32_t*)(image_buffer + IL.work), q.dL_dpix, q.dL_dpix_depth, q.dL_dalphas,
+                           q.dL_dpix_features, grad_rec, q.dL_dfeatures, (const BlobHeader*)q.binning_buffer,
+                           (const uint32_t*)(image_buffer + IL.ck_count),
+                           (const uint32_t*)(image_buffer + IL.bwd_ctl), (uint32_t)q.R);
+    STAGE_CHECK("render backward");
+    bwd_timing_mark(btr, 1, stream);
+    return GRPG_OK;
+  }
+  // behind the preprocess backward's launch (`stage`: its label)
+  int finish(const char* stage) {
+    bwd_timing_mark(btr, 2, stream);
+    btg.done = true;
+    STAGE_CHECK(stage);
+    return GRPG_OK;
+  }
+};
 
 uint32_t num_tiles(const CameraArgs& c) { return (uint32_t)c.gx * (uint32_t)c.gy; }
 
@@ -1686,88 +1748,6 @@ int grpg_forward_composed(grpg_alloc_fn geometry_alloc, void* geometry_user,
                                      GRPG_FORWARD_NO_BACKWARD);
 }
 
-// Shared body of grpg_backward_composed (F = 0) and grpg_backward_composed_features: the blend backward over the
-// frame's F feature channels, then the composed preprocess backward.  obj (grpg_backward_composed_objects; NULL: none):
-// the object-alpha plane's gradient is added to the gradient records between the two.
-struct ObjectAlphaGrad { const float* alpha_object; char* workspace; const float* dL_dalpha_object; };
-static int backward_composed_impl(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
-                                  int num_segments, int D, int M, int R, const float* background, int width,
-                                  int height, float scale_modifier, const float* viewmatrix,
-                                  const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                                  const int* radii, const float* alphas, char* geom_buffer, char* binning_buffer,
-                                  char* image_buffer, const float* dL_dpix, const float* dL_dpix_depth,
-                                  const float* dL_dalphas, float* dL_dmean2D, float* dL_dposes, int debug,
-                                  void* hip_stream, const float* features, int F, const float* dL_dpix_features,
-                                  float* dL_dfeatures, const ObjectAlphaGrad* obj = nullptr) {
-  if (int rc = begin_call()) return rc;
-  long long Pll = 0;
-  if (int rc = check_composed_model(segments, num_segments, D, M, &Pll)) return rc;
-  const int P = (int)Pll;
-  if (!grads || !geom_buffer || !binning_buffer || !image_buffer)
-    return fail(GRPG_ERR_BAD_BUFFER, "NULL gradient table / state buffer");
-  if (int rc = check_backward_state(geom_buffer, P, (hipStream_t)hip_stream)) return rc;
-  if (!dL_dpix || !dL_dpix_depth || !dL_dalphas || !alphas || !dL_dmean2D || !dL_dposes || !radii ||
-      !background || !viewmatrix || !projmatrix || !campos)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL pointer");
-  for (int i = 0; i < num_segments; i++) {
-    const grpg_model_segment_grad& g = grads[i];
-    if (!g.xyz || !g.scaling || !g.rotation || !g.opacity || !g.features_dc || (M > 1 && !g.features_rest))
-      return fail(GRPG_ERR_INVALID_ARGUMENT, "segment gradient with a NULL array");
-  }
-  hipStream_t stream = (hipStream_t)hip_stream;
-  BlendBackward bb(P, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, geom_buffer, binning_buffer,
-                   image_buffer);
-  // tables: the segments (as in the forward; re-uploaded: the caller may hand over other arrays of
-  // the same values) and the six output pointers per segment, through pinned staging
-  BwdStagingSlot* stg = bwd_staging_acquire();
-  if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
-  fill_segments(stg->segs, segments, num_segments, nullptr);
-  for (int i = 0; i < num_segments; i++) stg->grads[i] = grads[i];
-  SegmentDev* seg_dev = (SegmentDev*)(geom_buffer + bb.GL.seg_table);
-  void* seg_grad_dev = (void*)(geom_buffer + bb.GL.seg_grad_table);
-  HIP_TRY(hipMemcpyAsync(seg_dev, stg->segs, sizeof(SegmentDev) * (size_t)num_segments,
-                         hipMemcpyHostToDevice, stream));
-  gather_device_poses(stream, seg_dev, num_segments);
-  HIP_TRY(hipMemcpyAsync(seg_grad_dev, stg->grads, sizeof(grpg_model_segment_grad) * (size_t)num_segments,
-                         hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipEventRecord(stg->ev, stream));
-  if (int rc = bb.run(stream, debug, R, background, alphas, features, F, dL_dpix, dL_dpix_depth, dL_dalphas,
-                      dL_dpix_features, dL_dfeatures))
-    return rc;
-  if (obj) {
-    const ObjAlphaLayout OL = obj_alpha_layout((size_t)bb.cam.gx * (size_t)bb.cam.gy, (size_t)width * height);
-    launch_object_alpha_backward(stream, (const uint2*)(image_buffer + bb.IL.ranges),
-                                 (const uint32_t*)(binning_buffer + bin_layout(0).val_a), bb.rec,
-                                 (const unsigned char*)(geom_buffer + bb.GL.aux_c),
-                                 (const unsigned char*)(obj->workspace + OL.tile_flags), width, height, bb.cam.gx,
-                                 bb.cam.gy, obj->alpha_object, (const uint32_t*)(obj->workspace + OL.n_contrib),
-                                 obj->dL_dalpha_object, bb.grad_rec);
-    STAGE_CHECK("object-alpha backward");
-  }
-  launch_preprocess_backward_composed(stream, P, D, M, seg_dev, seg_grad_dev, num_segments, radii, bb.rec,
-                                      scale_modifier, bb.cam, bb.grad_rec, dL_dmean2D,
-                                      (float*)(geom_buffer + bb.GL.pose_acc), dL_dposes);
-  bwd_timing_mark(bb.btr, 2, stream);
-  bb.btg.done = true;
-  STAGE_CHECK("preprocess backward (composed)");
-  return GRPG_OK;
-}
-
-int grpg_backward_composed(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
-                           int num_segments, int D, int M, int R, const float* background, int width,
-                           int height, float scale_modifier, const float* viewmatrix,
-                           const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                           const int* radii, const float* alphas, char* geom_buffer, char* binning_buffer,
-                           char* image_buffer, const float* dL_dpix, const float* dL_dpix_depth,
-                           const float* dL_dalphas, float* dL_dmean2D, float* dL_dposes, int debug,
-                           void* hip_stream) {
-  PoseScope poses;
-  return backward_composed_impl(segments, grads, num_segments, D, M, R, background, width, height, scale_modifier,
-                                viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, alphas, geom_buffer,
-                                binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dmean2D,
-                                dL_dposes, debug, hip_stream, nullptr, 0, nullptr, nullptr);
-}
-
 // the channel split of a composed frame's feature planes: S >= 0, normals 0 / 1 -> F
 static int check_feature_split(int S, int normals, int* F) {
   if (S < 0 || (normals != 0 && normals != 1))
@@ -1808,52 +1788,96 @@ int grpg_forward_composed_features(grpg_alloc_fn geometry_alloc, void* geometry_
   return forward_impl(q);
 }
 
-// grpg_backward_composed_features, and grpg_backward_composed_objects with the object-alpha plane's three arguments
-static int backward_composed_features_impl(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
-                                    int num_segments, float* const* seg_dL_dsemantic, int S, int normals, int D,
-                                    int M, int R, const float* background, int width, int height,
-                                    float scale_modifier, const float* viewmatrix, const float* projmatrix,
-                                    const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                                    const float* alphas, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                                    char* feature_buffer, const float* dL_dpix, const float* dL_dpix_depth,
-                                    const float* dL_dalphas, const float* dL_dpix_features, float* dL_dfeatures,
-                                    float* dL_dmean2D, float* dL_dposes, int debug, void* hip_stream,
-                                    const ObjectAlphaGrad* obj) {
+// Shared body of grpg_backward_composed (F = 0), grpg_backward_composed_features and grpg_backward_composed_objects:
+// the blend backward over the frame's F feature channels, the object-alpha plane's gradient added to the gradient
+// records (q.alpha_object), the composed preprocess backward, and -- F > 0 -- the feature gradient back to the models.
+static int backward_composed_impl(const BackwardRequest& q) {
   if (int rc = begin_call()) return rc;
-  int F = 0;
-  if (int rc = check_feature_split(S, normals, &F)) return rc;
+  int F = 0;   // (== q.F)
+  if (int rc = check_feature_split(q.S, q.normals, &F)) return rc;
   if (F > GRPG_MAX_SEMANTIC_BACKWARD)   // the blend backward carries the channels in registers
     return fail(GRPG_ERR_INVALID_ARGUMENT,
                 "backward supports at most 32 semantic channels (the reference: 20, config.h:16)");
-  if (F > 0 && (!feature_buffer || !dL_dpix_features || !dL_dfeatures))
+  if (F > 0 && (!q.feature_buffer || !q.dL_dpix_features || !q.dL_dfeatures))
     return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL semantic pointer with S>0");
-  const float* features = F > 0 ? (const float*)(feature_buffer + feat_layout(0, 0).features) : nullptr;
-  if (int rc = backward_composed_impl(segments, grads, num_segments, D, M, R, background, width, height,
-                                      scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
-                                      alphas, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth,
-                                      dL_dalphas, dL_dmean2D, dL_dposes, debug, hip_stream, features, F,
-                                      dL_dpix_features, dL_dfeatures, obj))
-    return rc;
-  if (F == 0) return GRPG_OK;
-  // the feature gradient back to the models, behind the preprocess backward on the same stream (it ADDS to the
-  // rotation and pose gradients that one has written)
-  hipStream_t stream = (hipStream_t)hip_stream;
-  long long P = 0;
-  for (int i = 0; i < num_segments; i++) P += segments[i].count;
+  long long Pll = 0;
+  if (int rc = check_composed_model(q.segs, q.nseg, q.D, q.M, &Pll)) return rc;
+  const int P = (int)Pll;
+  if (!q.grads || !q.geom_buffer || !q.binning_buffer || !q.image_buffer)
+    return fail(GRPG_ERR_BAD_BUFFER, "NULL gradient table / state buffer");
+  const hipStream_t stream = q.stream;
+  const int debug = q.debug;
+  if (int rc = check_backward_state(q.geom_buffer, P, stream)) return rc;
+  if (!q.dL_dpix || !q.dL_dpix_depth || !q.dL_dalphas || !q.alphas || !q.dL_dmean2D || !q.dL_dposes || !q.radii ||
+      !q.background || !q.viewmatrix || !q.projmatrix || !q.campos)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL pointer");
+  for (int i = 0; i < q.nseg; i++) {
+    const grpg_model_segment_grad& g = q.grads[i];
+    if (!g.xyz || !g.scaling || !g.rotation || !g.opacity || !g.features_dc || (q.M > 1 && !g.features_rest))
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "segment gradient with a NULL array");
+  }
+  BlendBackward bb(q, P);
+  // tables: the segments (as in the forward; re-uploaded: the caller may hand over other arrays of
+  // the same values) and the six output pointers per segment, through pinned staging
   BwdStagingSlot* stg = bwd_staging_acquire();
   if (!stg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
-  for (int i = 0; i < num_segments; i++)
-    stg->feats[i] = FeatureSegDev{nullptr, seg_dL_dsemantic ? seg_dL_dsemantic[i] : nullptr, grads[i].rotation, nullptr};
-  const FeatLayout FL = feat_layout((size_t)P, (size_t)F);
-  FeatureSegDev* fdev = (FeatureSegDev*)(feature_buffer + FL.table);
-  HIP_TRY(hipMemcpyAsync(fdev, stg->feats, sizeof(FeatureSegDev) * (size_t)num_segments, hipMemcpyHostToDevice, stream));
+  fill_segments(stg->segs, q.segs, q.nseg, nullptr);
+  for (int i = 0; i < q.nseg; i++) stg->grads[i] = q.grads[i];
+  SegmentDev* seg_dev = (SegmentDev*)(q.geom_buffer + bb.GL.seg_table);
+  void* seg_grad_dev = (void*)(q.geom_buffer + bb.GL.seg_grad_table);
+  HIP_TRY(hipMemcpyAsync(seg_dev, stg->segs, sizeof(SegmentDev) * (size_t)q.nseg, hipMemcpyHostToDevice, stream));
+  gather_device_poses(stream, seg_dev, q.nseg);
+  HIP_TRY(hipMemcpyAsync(seg_grad_dev, stg->grads, sizeof(grpg_model_segment_grad) * (size_t)q.nseg,
+                         hipMemcpyHostToDevice, stream));
   HIP_TRY(hipEventRecord(stg->ev, stream));
-  const GeomLayout GL = geom_layout((size_t)P);
-  launch_compose_features_backward(stream, (int)P, (const SegmentDev*)(geom_buffer + GL.seg_table), fdev,
-                                   num_segments, S, normals, campos, dL_dfeatures,
-                                   (float*)(feature_buffer + FL.partials), FL.nslots, dL_dposes);
+  if (int rc = bb.run(F > 0 ? (const float*)(q.feature_buffer + feat_layout(0, 0).features) : nullptr)) return rc;
+  if (q.alpha_object) {
+    const ObjAlphaLayout OL = obj_alpha_layout((size_t)bb.cam.gx * (size_t)bb.cam.gy, (size_t)q.width * q.height);
+    launch_object_alpha_backward(stream, bb.ranges(), bb.point_list(), bb.rec,
+                                 (const unsigned char*)(q.geom_buffer + bb.GL.aux_c),
+                                 (const unsigned char*)(q.workspace + OL.tile_flags), q.width, q.height, bb.cam.gx,
+                                 bb.cam.gy, q.alpha_object, (const uint32_t*)(q.workspace + OL.n_contrib),
+                                 q.dL_dalpha_object, bb.grad_rec);
+    STAGE_CHECK("object-alpha backward");
+  }
+  launch_preprocess_backward_composed(stream, P, q.D, q.M, seg_dev, seg_grad_dev, q.nseg, q.radii, bb.rec,
+                                      q.scale_modifier, bb.cam, bb.grad_rec, q.dL_dmean2D,
+                                      (float*)(q.geom_buffer + bb.GL.pose_acc), q.dL_dposes);
+  if (int rc = bb.finish("preprocess backward (composed)")) return rc;
+  if (F == 0) return GRPG_OK;
+  // the feature gradient back to the models, behind the preprocess backward on the same stream (it ADDS to the
+  // rotation and pose gradients that one has written).  Its table travels through a staging slot of its own: the
+  // ring turns by two per feature backward.
+  BwdStagingSlot* fstg = bwd_staging_acquire();
+  if (!fstg) return fail(GRPG_ERR_HIP, "pinned staging allocation failed");
+  for (int i = 0; i < q.nseg; i++)
+    fstg->feats[i] = FeatureSegDev{nullptr, q.seg_dL_dsemantic ? q.seg_dL_dsemantic[i] : nullptr, q.grads[i].rotation,
+                                   nullptr};
+  const FeatLayout FL = feat_layout((size_t)P, (size_t)F);
+  FeatureSegDev* fdev = (FeatureSegDev*)(q.feature_buffer + FL.table);
+  HIP_TRY(hipMemcpyAsync(fdev, fstg->feats, sizeof(FeatureSegDev) * (size_t)q.nseg, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(fstg->ev, stream));
+  launch_compose_features_backward(stream, P, seg_dev, fdev, q.nseg, q.S, q.normals, q.campos, q.dL_dfeatures,
+                                   (float*)(q.feature_buffer + FL.partials), FL.nslots, q.dL_dposes);
   STAGE_CHECK("feature backward");
   return GRPG_OK;
+}
+
+int grpg_backward_composed(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
+                           int num_segments, int D, int M, int R, const float* background, int width,
+                           int height, float scale_modifier, const float* viewmatrix,
+                           const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                           const int* radii, const float* alphas, char* geom_buffer, char* binning_buffer,
+                           char* image_buffer, const float* dL_dpix, const float* dL_dpix_depth,
+                           const float* dL_dalphas, float* dL_dmean2D, float* dL_dposes, int debug,
+                           void* hip_stream) {
+  PoseScope poses;
+  BackwardRequest q;
+  set_model(q, segments, grads, num_segments, D, M, dL_dposes);
+  set_frame(q, R, background, width, height, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+            alphas, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dmean2D, debug,
+            hip_stream);
+  return backward_composed_impl(q);
 }
 
 int grpg_backward_composed_features(const grpg_model_segment* segments, const grpg_model_segment_grad* grads,
@@ -1866,11 +1890,13 @@ int grpg_backward_composed_features(const grpg_model_segment* segments, const gr
                                     const float* dL_dalphas, const float* dL_dpix_features, float* dL_dfeatures,
                                     float* dL_dmean2D, float* dL_dposes, int debug, void* hip_stream) {
   PoseScope poses;
-  return backward_composed_features_impl(segments, grads, num_segments, seg_dL_dsemantic, S, normals, D, M, R,
-                                         background, width, height, scale_modifier, viewmatrix, projmatrix, campos,
-                                         tan_fovx, tan_fovy, radii, alphas, geom_buffer, binning_buffer, image_buffer,
-                                         feature_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dpix_features,
-                                         dL_dfeatures, dL_dmean2D, dL_dposes, debug, hip_stream, nullptr);
+  BackwardRequest q;
+  set_model(q, segments, grads, num_segments, D, M, dL_dposes);
+  set_features(q, seg_dL_dsemantic, S, normals, feature_buffer, dL_dpix_features, dL_dfeatures);
+  set_frame(q, R, background, width, height, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+            alphas, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dmean2D, debug,
+            hip_stream);
+  return backward_composed_impl(q);
 }
 
 size_t grpg_object_alpha_workspace_bytes(int width, int height) {
@@ -1930,12 +1956,14 @@ int grpg_backward_composed_objects(const grpg_model_segment* segments, const grp
   if (!alpha_object || !workspace || !dL_dalpha_object || ((uintptr_t)workspace & 3u) != 0u || width <= 0 ||
       height <= 0)
     return fail(GRPG_ERR_INVALID_ARGUMENT, "object-alpha backward: NULL pointer, misaligned workspace or bad size");
-  const ObjectAlphaGrad obj = {alpha_object, workspace, dL_dalpha_object};
-  return backward_composed_features_impl(segments, grads, num_segments, seg_dL_dsemantic, S, normals, D, M, R,
-                                         background, width, height, scale_modifier, viewmatrix, projmatrix, campos,
-                                         tan_fovx, tan_fovy, radii, alphas, geom_buffer, binning_buffer, image_buffer,
-                                         feature_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dpix_features,
-                                         dL_dfeatures, dL_dmean2D, dL_dposes, debug, hip_stream, &obj);
+  BackwardRequest q;
+  set_model(q, segments, grads, num_segments, D, M, dL_dposes);
+  set_features(q, seg_dL_dsemantic, S, normals, feature_buffer, dL_dpix_features, dL_dfeatures);
+  set_frame(q, R, background, width, height, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+            alphas, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dmean2D, debug,
+            hip_stream);
+  q.alpha_object = alpha_object; q.workspace = workspace; q.dL_dalpha_object = dL_dalpha_object;
+  return backward_composed_impl(q);
 }
 
 // the arguments the two stand-alone feature entries share
@@ -2034,6 +2062,56 @@ int grpg_compose(const grpg_model_segment* segments, int num_segments, int M, fl
                          });
 }
 
+static int backward_flat_impl(const BackwardRequest& q) {
+  if (int rc = begin_call()) return rc;
+  if (q.P <= 0) return GRPG_OK;
+  if (!q.geom_buffer || !q.binning_buffer || !q.image_buffer)
+    return fail(GRPG_ERR_BAD_BUFFER, "NULL state buffer");
+  const hipStream_t stream = q.stream;
+  if (int rc = check_backward_state(q.geom_buffer, q.P, stream)) return rc;
+  // dL_dconic / dL_ddepth (pure intermediates of the reference's binding) and dL_dcolor / dL_dcov3D
+  // (gradients of the OPTIONAL inputs colors_precomp / cov3D_precomp) may be NULL: not written then
+  if (!q.dL_dpix || !q.dL_dpix_depth || !q.dL_dalphas || !q.alphas || !q.dL_dmean2D || !q.dL_dopacity || !q.dL_dmean3D)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL gradient pointer");
+  if ((q.colors_precomp && !q.dL_dcolor) || (q.cov3D_precomp && !q.dL_dcov3D))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "colors_precomp / cov3D_precomp given without their gradient array");
+  // every gradient array is WRITTEN, not accumulated: the inputs in use need theirs
+  if (!q.colors_precomp && (!q.shs || !q.dL_dsh))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "shs (no colors_precomp) needs shs and dL_dsh");
+  if (!q.cov3D_precomp && (!q.scales || !q.rotations || !q.dL_dscale || !q.dL_drot))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "scales / rotations (no cov3D_precomp) need dL_dscale and dL_drot");
+  if (!q.means3D || !q.background || !q.viewmatrix || !q.projmatrix || !q.campos)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL means3D / camera / background pointer");
+  if (q.S > 0 && (!q.semantics || !q.dL_dpix_features || !q.dL_dfeatures))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL semantic pointer with S>0");
+  if (q.S > GRPG_MAX_SEMANTIC_BACKWARD)   // the blend backward carries the channels in registers
+    return fail(GRPG_ERR_INVALID_ARGUMENT,
+                "backward supports at most 32 semantic channels (the reference: 20, config.h:16)");
+  BlendBackward bb(q, q.P);
+  if (q.debug) {  // validate the blobs (costs a sync; only in debug mode, like the reference's checks)
+    BlobHeader h[3];
+    HIP_TRY(hipMemcpyAsync(&h[0], q.geom_buffer, sizeof(BlobHeader), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h[1], q.binning_buffer, sizeof(BlobHeader), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h[2], q.image_buffer, sizeof(BlobHeader), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (h[0].magic != GEOM_MAGIC || h[1].magic != BIN_MAGIC || h[2].magic != IMG_MAGIC ||
+        h[0].P != (uint32_t)q.P || h[0].R != (uint32_t)q.R || h[1].Rcap < (uint32_t)q.R ||
+        h[2].W != (uint32_t)q.width || h[2].H != (uint32_t)q.height)
+      return fail(GRPG_ERR_BAD_BUFFER, "state buffers do not match this call (P/R/W/H or magic)");
+    if (h[0].has_grad_rec == 0u)
+      return fail(GRPG_ERR_BAD_BUFFER, "the geometry buffer was carved by an evaluation forward (no gradient records)");
+    if (h[2].pc_timeout != 0u)
+      return fail(GRPG_ERR_HIP, "the forward of this frame reported a producer/consumer timeout: its image is invalid");
+  }
+  const int* radii_int = q.radii ? q.radii : (const int*)(q.geom_buffer + bb.GL.radii);
+  if (int rc = bb.run(q.semantics)) return rc;
+  launch_preprocess_backward(stream, q.P, q.D, q.M, q.means3D, radii_int, q.colors_precomp ? nullptr : q.shs, bb.rec,
+                             q.cov3D_precomp ? nullptr : q.scales, q.rotations, q.scale_modifier, q.cov3D_precomp,
+                             bb.cam, bb.grad_rec, q.dL_dmean2D, q.dL_dconic, q.dL_dopacity, q.dL_dmean3D, q.dL_dcolor,
+                             q.dL_ddepth, q.dL_dcov3D, q.colors_precomp ? nullptr : q.dL_dsh, q.dL_dscale, q.dL_drot);
+  return bb.finish("preprocess backward");
+}
+
 int grpg_backward(int P, int D, int M, int R, int S, const float* background, int width,
                   int height, const float* means3D, const float* shs, const float* colors_precomp,
                   const float* semantics, const float* alphas, const float* scales,
@@ -2046,60 +2124,17 @@ int grpg_backward(int P, int D, int M, int R, int S, const float* background, in
                   float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D,
                   float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                   float* dL_dsemantic, int debug, void* hip_stream) {
-  if (int rc = begin_call()) return rc;
-  if (P <= 0) return GRPG_OK;
-  if (!geom_buffer || !binning_buffer || !image_buffer)
-    return fail(GRPG_ERR_BAD_BUFFER, "NULL state buffer");
-  if (int rc = check_backward_state(geom_buffer, P, (hipStream_t)hip_stream)) return rc;
-  // dL_dconic / dL_ddepth (pure intermediates of the reference's binding) and dL_dcolor / dL_dcov3D
-  // (gradients of the OPTIONAL inputs colors_precomp / cov3D_precomp) may be NULL: not written then
-  if (!dL_dpix || !dL_dpix_depth || !dL_dalphas || !alphas || !dL_dmean2D || !dL_dopacity || !dL_dmean3D)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL gradient pointer");
-  if ((colors_precomp && !dL_dcolor) || (cov3D_precomp && !dL_dcov3D))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "colors_precomp / cov3D_precomp given without their gradient array");
-  // every gradient array is WRITTEN, not accumulated: the inputs in use need theirs
-  if (!colors_precomp && (!shs || !dL_dsh))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "shs (no colors_precomp) needs shs and dL_dsh");
-  if (!cov3D_precomp && (!scales || !rotations || !dL_dscale || !dL_drot))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "scales / rotations (no cov3D_precomp) need dL_dscale and dL_drot");
-  if (!means3D || !background || !viewmatrix || !projmatrix || !campos)
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL means3D / camera / background pointer");
-  if (S > 0 && (!semantics || !dL_dpix_semantic || !dL_dsemantic))
-    return fail(GRPG_ERR_INVALID_ARGUMENT, "NULL semantic pointer with S>0");
-  if (S > GRPG_MAX_SEMANTIC_BACKWARD)   // the blend backward carries the channels in registers
-    return fail(GRPG_ERR_INVALID_ARGUMENT,
-                "backward supports at most 32 semantic channels (the reference: 20, config.h:16)");
-  hipStream_t stream = (hipStream_t)hip_stream;
-  BlendBackward bb(P, width, height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, geom_buffer, binning_buffer,
-                   image_buffer);
-  if (debug) {  // validate the blobs (costs a sync; only in debug mode, like the reference's checks)
-    BlobHeader h[3];
-    HIP_TRY(hipMemcpyAsync(&h[0], geom_buffer, sizeof(BlobHeader), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(&h[1], binning_buffer, sizeof(BlobHeader), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(&h[2], image_buffer, sizeof(BlobHeader), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (h[0].magic != GEOM_MAGIC || h[1].magic != BIN_MAGIC || h[2].magic != IMG_MAGIC ||
-        h[0].P != (uint32_t)P || h[0].R != (uint32_t)R || h[1].Rcap < (uint32_t)R ||
-        h[2].W != (uint32_t)width || h[2].H != (uint32_t)height)
-      return fail(GRPG_ERR_BAD_BUFFER, "state buffers do not match this call (P/R/W/H or magic)");
-    if (h[0].has_grad_rec == 0u)
-      return fail(GRPG_ERR_BAD_BUFFER, "the geometry buffer was carved by an evaluation forward (no gradient records)");
-    if (h[2].pc_timeout != 0u)
-      return fail(GRPG_ERR_HIP, "the forward of this frame reported a producer/consumer timeout: its image is invalid");
-  }
-  const int* radii_int = radii ? radii : (const int*)(geom_buffer + bb.GL.radii);
-  if (int rc = bb.run(stream, debug, R, background, alphas, semantics, S, dL_dpix, dL_dpix_depth, dL_dalphas,
-                      dL_dpix_semantic, dL_dsemantic))
-    return rc;
-  launch_preprocess_backward(stream, P, D, M, means3D, radii_int, colors_precomp ? nullptr : shs,
-                             bb.rec, cov3D_precomp ? nullptr : scales, rotations, scale_modifier,
-                             cov3D_precomp, bb.cam, bb.grad_rec, dL_dmean2D, dL_dconic, dL_dopacity,
-                             dL_dmean3D, dL_dcolor, dL_ddepth, dL_dcov3D,
-                             colors_precomp ? nullptr : dL_dsh, dL_dscale, dL_drot);
-  bwd_timing_mark(bb.btr, 2, stream);
-  bb.btg.done = true;
-  STAGE_CHECK("preprocess backward");
-  return GRPG_OK;
+  BackwardRequest q;
+  set_frame(q, R, background, width, height, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+            alphas, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dalphas, dL_dmean2D, debug,
+            hip_stream);
+  q.P = P; q.D = D; q.M = M; q.means3D = means3D; q.shs = shs; q.colors_precomp = colors_precomp; q.scales = scales;
+  q.rotations = rotations; q.cov3D_precomp = cov3D_precomp;
+  // the semantic channels are the blend's feature channels of a flat frame
+  q.S = q.F = S; q.semantics = semantics; q.dL_dpix_features = dL_dpix_semantic; q.dL_dfeatures = dL_dsemantic;
+  q.dL_dconic = dL_dconic; q.dL_dopacity = dL_dopacity; q.dL_dcolor = dL_dcolor; q.dL_ddepth = dL_ddepth;
+  q.dL_dmean3D = dL_dmean3D; q.dL_dcov3D = dL_dcov3D; q.dL_dsh = dL_dsh; q.dL_dscale = dL_dscale; q.dL_drot = dL_drot;
+  return backward_flat_impl(q);
 }
 
 int grpg_mark_visible(int P, const float* means3D, const float* viewmatrix,
