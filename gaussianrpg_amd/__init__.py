@@ -14,6 +14,8 @@ Layout:
                   the detector's output as detections: NMS + the mapping back to the frame, no host wait
   tracks.py       tracklets + optimised corrections + timestamp + ego pose -> every actor's world pose in one
                   launch, with backward to opt_trans / opt_rots (the step in front of composed.py)
+  session.py      closed-loop evaluation: a scene bound once to a pose tape (segment tables of all frames baked on the
+                  device), then one call per frame with nothing in front of its first launch
   build.py        in-tree build (hipcc for gfx950, g++ for the binding)
 
 Importing this package does not load native code; ``gaussianrpg_amd.rasterizer`` does, and fails

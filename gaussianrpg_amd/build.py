@@ -91,6 +91,8 @@ HIP_UNITS = {
     "tracks.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # actor poses from device memory into the segment table: loads and stores only, no arithmetic
     "segment_pose.hip": [],
+    # segment tables of a whole pose tape, baked once at bind time: loads and stores only as well
+    "frame_table.hip": [],
     "api.hip": [],
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept

@@ -630,6 +630,19 @@ int attach_frame_correction(const float* affine, FrameEpilogue* fe) {
   return GRPG_OK;
 }
 
+// ---- a baked frame table (grpg_bind_frame_table): one frame's rows of a grpg_frame_tables_bake table wait here until
+// the next composed forward on this thread, which takes them first thing -- whatever that call returns then.
+struct TableBinding {
+  const SegmentDev* rows = nullptr;
+  int n = 0, P = 0;
+};
+thread_local TableBinding g_table_pending;
+TableBinding take_frame_table() {
+  const TableBinding t = g_table_pending;
+  g_table_pending = TableBinding{};
+  return t;
+}
+
 // behind the asynchronous copy of a table fill_segments built: the bound rows' poses, on the same stream
 void gather_device_poses(hipStream_t stream, SegmentDev* seg_dev, int nseg) {
   if (g_pose_cur.set && g_pose_cur.any && g_pose_cur.n == nseg)
@@ -695,6 +708,8 @@ struct FrameRequest {
   int* radii = nullptr;
   const grpg_model_segment* segs = nullptr;
   int nseg = 0;
+  // grpg_bind_frame_table: the frame's device rows, baked earlier -- read in place of a table staged from segs
+  const SegmentDev* bound_rows = nullptr;
   // grpg_forward_composed_features: the segments' semantic arrays (host array of device pointers, or NULL), the
   // channel split S = 3 * feat_normals + feat_S, and the blob whose head is the [P,S] array `semantics` points at
   const float* const* seg_semantic = nullptr;
@@ -733,6 +748,24 @@ void set_model(FrameRequest& q, int P, int D, int M, const float* means3D, const
 // ... or the checked segments of a composition (P: check_composed_model's)
 void set_model(FrameRequest& q, const grpg_model_segment* segments, int num_segments, long long P, int D, int M) {
   q.segs = segments; q.nseg = num_segments; q.P = (int)P; q.D = D; q.M = M;
+}
+
+// A bound frame table joins the composed evaluation frame it was baked for (q: model, camera and flags set) -- or the
+// call is refused: the table holds no gradient bookkeeping's worth of a training frame (its backward rebuilds the
+// table from the host segments), feature planes stage a table of their own next to it, and device poses would be
+// gathered into the caller's baked rows.
+int attach_frame_table(const TableBinding& tb, FrameRequest& q) {
+  if (tb.rows == nullptr) return GRPG_OK;
+  if (q.training())
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "a frame table was bound in front of a training forward");
+  if (q.feat_blob != nullptr || q.S != 0)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "a frame table was bound in front of a frame with feature planes");
+  if (g_pose_cur.set)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "a frame table and device poses were bound for the same call");
+  if (tb.n != q.nseg || tb.P != q.P)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "the bound frame table was baked for another number of segments or Gaussians");
+  q.bound_rows = tb.rows;
+  return GRPG_OK;
 }
 
 // the argument checks of every forward, behind ensure_device
@@ -1088,8 +1121,13 @@ struct Frame {
                         q.shs, q.cov3D_precomp, q.colors_precomp, cam, radii_int, rec_w, key_a, tiles, rects,
                         fat_sort ? ds_table : nullptr, pre_counts, marks, binned_rects);
     } else {
-      SegmentDev* seg_dev = (SegmentDev*)(geom + GL.seg_table);
-      if (int rc = stage_segments(seg_dev)) return rc;
+      // the frame's table: staged into the geometry blob, or the rows baked for it earlier, where they lie
+      const SegmentDev* seg_dev = q.bound_rows;
+      if (seg_dev == nullptr) {
+        SegmentDev* staged = (SegmentDev*)(geom + GL.seg_table);
+        if (int rc = stage_segments(staged)) return rc;
+        seg_dev = staged;
+      }
       launch_preprocess_composed(stream, q.P, q.D, q.M, seg_dev, q.nseg, q.scale_modifier, cam, radii_int, rec_w,
                                  key_a, tiles, rects, fat_sort ? ds_table : nullptr, pre_counts, marks, binned_rects);
       if (q.S > 0) {   // the frame's feature planes: [P,S] from the models' own arrays (features.hip)
@@ -1615,6 +1653,98 @@ int grpg_bind_frame_correction(const float* affine_device) {
 
 int grpg_frame_correction_bound(void) { return g_affine_pending ? 1 : 0; }
 
+size_t grpg_frame_tables_bytes(long long total_rows) {
+  return total_rows > 0 ? sizeof(SegmentDev) * (size_t)total_rows : 0;
+}
+
+// Bind time: the static part of every frame's rows through fill_segments itself (so a baked row and a staged row are
+// the same bytes by construction), one upload, one launch for the tracked poses, one wait.
+int grpg_frame_tables_bake(void* rows_device, const grpg_model_segment* models, int num_models, const int* frame_first,
+                           int num_frames, const int* row_model, const int* row_pose, const float* row_idft,
+                           const unsigned char* row_class, const float* pose_rot, const float* pose_trans,
+                           long long num_pose_rows, void* hip_stream) {
+  if (int rc = begin_call()) return rc;
+  if (!rows_device || ((uintptr_t)rows_device & 15u) || !models || num_models <= 0 || !frame_first || num_frames <= 0 ||
+      !row_model || !row_pose || !row_idft)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "frame tables: NULL or misaligned pointer, or no models / frames");
+  if (num_pose_rows < 0 || num_pose_rows >= (1ll << 28))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "frame tables: num_pose_rows must be in 0..2^28-1");
+  if (frame_first[0] != 0) return fail(GRPG_ERR_INVALID_ARGUMENT, "frame tables: frame_first[0] must be 0");
+  for (int k = 0; k < num_frames; k++) {
+    const long long n = (long long)frame_first[k + 1] - frame_first[k];
+    if (n < 1 || n > GRPG_MAX_SEGMENTS)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "frame tables: every frame needs 1..GRPG_MAX_SEGMENTS rows");
+  }
+  const long long R = frame_first[num_frames];
+  bool any = false;
+  for (long long i = 0; i < R; i++) {
+    if (row_model[i] < 0 || row_model[i] >= num_models)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "frame tables: a row names a model outside the scene");
+    if (row_pose[i] < -1 || row_pose[i] >= num_pose_rows)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "frame tables: a pose row is neither -1 nor a row of the pose tables");
+    if (row_pose[i] >= 0 && models[row_model[i]].rigid == 0)
+      return fail(GRPG_ERR_INVALID_ARGUMENT, "frame tables: a pose row names a static model (rigid == 0)");
+    any = any || row_pose[i] >= 0;
+  }
+  if (any && (!pose_rot || !pose_trans))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "frame tables: NULL pose_rot / pose_trans with a pose row given");
+  const hipStream_t stream = (hipStream_t)hip_stream;
+  SegmentDev* host = nullptr;
+  HIP_TRY(hipHostMalloc((void**)&host, sizeof(SegmentDev) * (size_t)R, hipHostMallocDefault));
+  std::vector<grpg_model_segment> segs;
+  int rc = GRPG_OK;
+  for (int k = 0; k < num_frames && rc == GRPG_OK; k++) {
+    const int first = frame_first[k], n = frame_first[k + 1] - first;
+    segs.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+      segs[i] = models[row_model[first + i]];
+      memcpy(segs[i].idft, row_idft + (size_t)GRPG_MAX_FOURIER * (size_t)(first + i), sizeof(float) * GRPG_MAX_FOURIER);
+    }
+    long long P = 0;
+    // the checks of a composed call on these segments (features_rest: the consuming call knows M); outside a
+    // PoseScope no device-pose binding is current, so fill_segments parks nothing: the tape's own rows follow
+    rc = check_segments(segs.data(), n, 1, &P);
+    if (rc != GRPG_OK) break;
+    const LayerArgs la = {row_class ? row_class + first : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    fill_segments(host + first, segs.data(), n, row_class ? &la : nullptr);
+    for (int i = 0; i < n; i++)
+      if (row_pose[first + i] >= 0) {
+        const int parked = row_pose[first + i] + 1;
+        memcpy(&host[first + i].pad0, &parked, sizeof(parked));
+      }
+  }
+  hipError_t e = hipSuccess;
+  if (rc == GRPG_OK) {
+    e = hipMemcpyAsync(rows_device, host, sizeof(SegmentDev) * (size_t)R, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && any) {
+      launch_frame_table_bake(stream, (SegmentDev*)rows_device, R, pose_rot, pose_trans);
+      e = hipGetLastError();
+    }
+    const hipError_t w = hipStreamSynchronize(stream);   // the staging is freed below
+    if (e == hipSuccess) e = w;
+  }
+  (void)hipHostFree(host);
+  if (rc != GRPG_OK) return rc;
+  if (e != hipSuccess) return fail(GRPG_ERR_HIP, std::string("frame tables: ") + hipGetErrorString(e));
+  return GRPG_OK;
+}
+
+// A refused bind leaves no binding (the caller meant to replace the pending one).
+int grpg_bind_frame_table(const void* rows_device, int num_segments, int P) {
+  g_table_pending = TableBinding{};
+  if (int rc = begin_call()) return rc;
+  if (!rows_device || ((uintptr_t)rows_device & 15u))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "frame table: NULL or misaligned rows");
+  if (num_segments <= 0 || num_segments > GRPG_MAX_SEGMENTS || P <= 0 || (unsigned)P > ID_MASK)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "frame table: need 1..GRPG_MAX_SEGMENTS segments and 0 < P < 2^28");
+  g_table_pending.rows = (const SegmentDev*)rows_device;
+  g_table_pending.n = num_segments;
+  g_table_pending.P = P;
+  return GRPG_OK;
+}
+
+int grpg_frame_tables_bound(void) { return g_table_pending.rows ? 1 : 0; }
+
 int grpg_forward_composed_flags(grpg_alloc_fn geometry_alloc, void* geometry_user,
                                 grpg_alloc_fn binning_alloc, void* binning_user,
                                 grpg_alloc_fn image_alloc, void* image_user,
@@ -1624,6 +1754,7 @@ int grpg_forward_composed_flags(grpg_alloc_fn geometry_alloc, void* geometry_use
                                 float tan_fovx, float tan_fovy, float* out_color, float* out_depth,
                                 float* out_alpha, int* radii, int debug, void* hip_stream, unsigned flags) {
   PoseScope poses;
+  const TableBinding table = take_frame_table();
   if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
@@ -1632,6 +1763,7 @@ int grpg_forward_composed_flags(grpg_alloc_fn geometry_alloc, void* geometry_use
   set_model(q, segments, num_segments, P, D, M);
   set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
              out_color, out_depth, out_alpha, radii, debug, hip_stream, flags);
+  if (int rc = attach_frame_table(table, q)) return rc;
   return forward_impl(q);
 }
 
@@ -1647,6 +1779,7 @@ int grpg_forward_composed_layers(grpg_alloc_fn geometry_alloc, void* geometry_us
                                  float* out_color_obj, float* out_alpha_obj, int* radii, int debug,
                                  void* hip_stream) {
   PoseScope poses;
+  const TableBinding table = take_frame_table();
   if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
@@ -1657,6 +1790,7 @@ int grpg_forward_composed_layers(grpg_alloc_fn geometry_alloc, void* geometry_us
   set_model(q, segments, num_segments, P, D, M);
   set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
              out_color, out_depth, out_alpha, radii, debug, hip_stream, GRPG_FORWARD_NO_BACKWARD);
+  if (int rc = attach_frame_table(table, q)) return rc;
   return forward_impl(q);
 }
 
@@ -1713,6 +1847,7 @@ int grpg_forward_composed_frame(grpg_alloc_fn geometry_alloc, void* geometry_use
                                 const grpg_frame_epilogue* epilogue) {
   PoseScope poses;
   const float* affine = take_frame_correction();
+  const TableBinding table = take_frame_table();
   if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;
@@ -1729,6 +1864,7 @@ int grpg_forward_composed_frame(grpg_alloc_fn geometry_alloc, void* geometry_use
   set_model(q, segments, num_segments, P, D, M);
   set_camera(q, background, width, height, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
              out_color, out_depth, out_alpha, radii, debug, hip_stream, GRPG_FORWARD_NO_BACKWARD);
+  if (int rc = attach_frame_table(table, q)) return rc;
   return forward_impl(q);
 }
 
@@ -1767,6 +1903,10 @@ int grpg_forward_composed_features(grpg_alloc_fn geometry_alloc, void* geometry_
                                    float* out_alpha, float* out_features, int* radii, int debug, void* hip_stream,
                                    unsigned flags) {
   PoseScope poses;
+  if (take_frame_table().rows != nullptr) {   // (gone, like every binding its call refuses)
+    g_last_error.clear();
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "a frame table was bound in front of a frame with feature planes");
+  }
   if (int rc = begin_call()) return rc;
   long long P = 0;
   if (int rc = check_composed_model(segments, num_segments, D, M, &P)) return rc;

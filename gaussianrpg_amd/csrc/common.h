@@ -403,6 +403,11 @@ void launch_compose(hipStream_t s, int P, int M, const SegmentDev* segs, int nse
 // pose_rot [R,4] / pose_trans [R,3] and pad0 = 0.f; every other byte of the table stays.  One thread per segment.
 void launch_segment_pose_gather(hipStream_t s, SegmentDev* segs, int nseg, const float* pose_rot,
                                 const float* pose_trans);
+// Segment tables of a whole tape (frame_table.hip): the same hand-over over `nrows` rows of all frames at once, into
+// caller-owned memory, at bind time.  One thread per row, FRAME_TABLE_THREADS per workgroup.
+constexpr int FRAME_TABLE_THREADS = 256;
+void launch_frame_table_bake(hipStream_t s, SegmentDev* rows, long long nrows, const float* pose_rot,
+                             const float* pose_trans);
 void launch_visible_filter(hipStream_t s, int P, const float* means3D, const float* scales,
                            float scale_modifier, const float* rotations,
                            const float* cov3D_precomp, const CameraArgs& cam, int* radii,

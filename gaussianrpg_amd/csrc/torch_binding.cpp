@@ -851,6 +851,124 @@ FrameResult RasterizeGaussiansComposedFrame(
   return o.frame(rendered, ea.rgb8);
 }
 
+// ---- the baked segment tables of a pose tape (grpg_frame_tables_bake / grpg_bind_frame_table): session.FrameSession ----
+// What a bound frame needs per call: the device rows, and per frame the host segments its checks read (pointers,
+// counts, Fourier dimensions; the poses in them are not looked at) -- built once, so a frame call packs nothing.
+struct FrameTables {
+  torch::Tensor rows;                     // uint8 [R * 144] on the device
+  std::vector<grpg_model_segment> segs;   // [R] host rows, frame after frame
+  std::vector<int> first;                 // [T + 1]
+  std::vector<int64_t> P;                 // [T]
+  std::vector<torch::Tensor> keep;
+  torch::Tensor like;                     // a parameter tensor: the device and options of what a frame allocates
+  int M = 0;
+  int64_t num_frames() const { return (int64_t)P.size(); }
+};
+
+// models: the SCENE's models (GRPG_MODEL_PARAMS; poses [n,8] = posed flag and the pose of a row without a pose row,
+// idft ignored); frame_first [T+1], row_model [R], row_pose [R] (row of the flattened pose batch, or -1): host ints;
+// row_idft [R, GRPG_MAX_FOURIER] host float32; row_class uint8 [R] on the host or empty; pose_rot [*,4] / pose_trans
+// [*,3]: the pose batch on the device.
+std::shared_ptr<FrameTables> BakeFrameTables(GRPG_MODEL_PARAMS, const std::vector<int>& frame_first,
+                                             const std::vector<int>& row_model, const std::vector<int>& row_pose,
+                                             const torch::Tensor& row_idft, const torch::Tensor& row_class,
+                                             const torch::Tensor& pose_rot, const torch::Tensor& pose_trans) {
+  SegmentPack pk = pack_segments(GRPG_MODEL_ARGS);
+  const torch::Tensor& like = xyz[0];
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
+  TORCH_CHECK(frame_first.size() >= 2 && frame_first[0] == 0, "frame_first must be [T+1] host ints starting at 0");
+  const int T = (int)frame_first.size() - 1;
+  for (int k = 0; k < T; k++)
+    TORCH_CHECK(frame_first[k + 1] > frame_first[k] && frame_first[k + 1] - frame_first[k] <= GRPG_MAX_SEGMENTS,
+                "frame ", k, " needs 1..", GRPG_MAX_SEGMENTS, " rows");
+  const int64_t R = frame_first[T];
+  TORCH_CHECK((int64_t)row_model.size() == R && (int64_t)row_pose.size() == R, "one model and one pose row per row");
+  TORCH_CHECK(!row_idft.is_cuda() && row_idft.scalar_type() == torch::kFloat32 && row_idft.dim() == 2 &&
+                  row_idft.size(0) == R && row_idft.size(1) == GRPG_MAX_FOURIER && row_idft.is_contiguous(),
+              "row_idft must be a contiguous CPU float tensor [rows, ", GRPG_MAX_FOURIER, "]");
+  const unsigned char* p_cls = nullptr;
+  if (row_class.defined() && row_class.numel() != 0) {
+    TORCH_CHECK(!row_class.is_cuda() && row_class.scalar_type() == torch::kUInt8 && row_class.numel() == R &&
+                    row_class.is_contiguous(),
+                "row_class must be a contiguous uint8 HOST tensor with one element per row");
+    p_cls = row_class.data_ptr<unsigned char>();
+  }
+  TORCH_CHECK(pose_rot.is_cuda() && pose_trans.is_cuda() && pose_rot.device() == like.device() &&
+                  pose_trans.device() == like.device() && pose_rot.scalar_type() == torch::kFloat32 &&
+                  pose_trans.scalar_type() == torch::kFloat32 && pose_rot.dim() == 2 && pose_rot.size(1) == 4 &&
+                  pose_trans.dim() == 2 && pose_trans.size(1) == 3 && pose_rot.size(0) == pose_trans.size(0) &&
+                  pose_rot.is_contiguous() && pose_trans.is_contiguous(),
+              "pose_rot [R,4] and pose_trans [R,3] must be contiguous float32 tensors on the models' device");
+  const int64_t num_pose_rows = pose_rot.size(0);
+  auto ft = std::make_shared<FrameTables>();
+  ft->first = frame_first;
+  ft->M = pk.M;
+  ft->like = like;
+  ft->keep = pk.keep;
+  ft->segs.resize((size_t)R);
+  const float* idft_p = row_idft.data_ptr<float>();
+  for (int k = 0; k < T; k++) {
+    int64_t P = 0;
+    for (int i = frame_first[k]; i < frame_first[k + 1]; i++) {
+      TORCH_CHECK(row_model[i] >= 0 && row_model[i] < (int)pk.segs.size(), "row ", i, " names a model outside the scene");
+      TORCH_CHECK(row_pose[i] >= -1 && row_pose[i] < num_pose_rows, "row ", i, ": pose row outside the pose batch");
+      grpg_model_segment& g = ft->segs[(size_t)i];
+      g = pk.segs[(size_t)row_model[i]];
+      for (int q = 0; q < GRPG_MAX_FOURIER; q++) g.idft[q] = idft_p[(size_t)GRPG_MAX_FOURIER * i + q];
+      P += g.count;
+    }
+    ft->P.push_back(P);
+  }
+  ft->rows = torch::empty({(int64_t)grpg_frame_tables_bytes(R)}, like.options().dtype(torch::kByte));
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  int rc;
+  {
+    pybind11::gil_scoped_release nogil;
+    rc = grpg_frame_tables_bake(ft->rows.data_ptr(), pk.segs.data(), (int)pk.segs.size(), frame_first.data(), T,
+                                row_model.data(), row_pose.data(), idft_p, p_cls, pose_rot.data_ptr<float>(),
+                                pose_trans.data_ptr<float>(), num_pose_rows, (void*)stream);
+  }
+  if (rc != GRPG_OK) raise_abi_error("grpg_frame_tables_bake", rc);
+  return ft;
+}
+
+// Frame k of a baked tape as one call: grpg_bind_frame_table + grpg_forward_composed_frame.  The camera tensors and
+// the ray matrix are device tensors (views of the session's rows); nothing is packed, filled or uploaded here.
+FrameResult RasterizeGaussiansBoundFrame(
+    const std::shared_ptr<FrameTables>& ft, const int64_t k, const torch::Tensor& background,
+    const torch::Tensor& layer_background, const bool layered, const float scale_modifier,
+    const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+    const int image_height, const int image_width, const int degree, const torch::Tensor& campos, const bool debug,
+    const torch::Tensor& sky_cube, const torch::Tensor& ray_matrix, const float sky_fill, const bool clamp,
+    const bool want_planes, const bool want_rgb8, const bool truncate, const c10::optional<torch::Tensor>& out_rgb8,
+    const c10::optional<torch::Tensor>& affine) {
+  TORCH_CHECK(ft != nullptr && k >= 0 && k < ft->num_frames(), "frame ", k, " is not one of the baked frames");
+  const torch::Tensor& like = ft->like;
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
+  TORCH_CHECK(want_planes || want_rgb8, kFrameAsksForNothing);
+  const int H = image_height, W = image_width;
+  CameraPtrs cam(like, background, &layer_background);
+  cam.pose(like, viewmatrix, projmatrix, campos);
+  cam.require(LayerBg::kIfLayered, layered);
+  EpilogueArgs ea;
+  make_epilogue(ea, like, sky_cube, ray_matrix, sky_fill, clamp, want_rgb8, truncate, out_rgb8, H, W);
+  set_frame_affine(ea, like, affine);
+  const int first = ft->first[(size_t)k], nseg = ft->first[(size_t)k + 1] - first;
+  const int64_t P = ft->P[(size_t)k];
+  const unsigned char* rows = ft->rows.data_ptr<unsigned char>() + (size_t)first * grpg_frame_tables_bytes(1);
+  ForwardOutputs o(like, P, H, W, c10::nullopt, want_planes, layered);
+  const int rendered = run("grpg_forward_composed_frame", [&](void* stream) {
+    if (int rc = ea.bind()) return rc;
+    if (int rc = grpg_bind_frame_table(rows, nseg, (int)P)) return rc;
+    return grpg_forward_composed_frame(
+        resize_blob, &o.geom, resize_blob, &o.binning, resize_blob, &o.img, ft->segs.data() + first, nseg, nullptr,
+        degree, ft->M, cam.bg, cam.layer_bg, W, H, scale_modifier, cam.view, cam.proj, cam.pos, tan_fovx, tan_fovy,
+        o.p_color, o.p_depth, o.p_alpha, o.p_color_bg, o.p_alpha_bg, o.p_color_obj, o.p_alpha_obj, o.p_radii,
+        debug ? 1 : 0, stream, &ea.e);
+  });
+  return o.frame(rendered, ea.rgb8);
+}
+
 // ---- feature planes of a composed frame (grpg_*_features): F = 3 * normals + S channels, normals first ----
 namespace {
 
@@ -2928,6 +3046,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("compose_features", &ComposeFeatures);
   m.def("compose_features_backward", &ComposeFeaturesBackward);
   m.def("rasterize_gaussians_composed_features", &RasterizeGaussiansComposedFeatures);
+  // the baked segment tables of a pose tape and the frame call on them (session.py FrameSession)
+  pybind11::class_<FrameTables, std::shared_ptr<FrameTables>>(m, "FrameTables")
+      .def_property_readonly("rows", [](const FrameTables& t) { return t.rows; })   // uint8 [R * 144], device
+      .def_property_readonly("first", [](const FrameTables& t) { return t.first; })
+      .def_property_readonly("num_gaussians", [](const FrameTables& t) { return t.P; })
+      .def("__len__", &FrameTables::num_frames);
+  m.def("bake_frame_tables", &BakeFrameTables);
+  m.def("rasterize_gaussians_bound_frame", &RasterizeGaussiansBoundFrame);
+  m.def("frame_tables_bytes", [](long long rows) { return grpg_frame_tables_bytes(rows); });
+  m.def("bind_frame_table", [](const torch::Tensor& rows, int num_segments, int P) {   // the tests' refusals
+    return grpg_bind_frame_table(rows.data_ptr(), num_segments, P);
+  });
+  m.def("frame_tables_bound", []() { return grpg_frame_tables_bound(); });
   m.def("sky_composite", &SkyComposite, pybind11::arg("cube"), pybind11::arg("ray_matrix"),
         pybind11::arg("fill"), pybind11::arg("clamp_out"), pybind11::arg("rgb"), pybind11::arg("acc"),
         pybind11::arg("height"), pybind11::arg("width"), pybind11::arg("want_sky"),

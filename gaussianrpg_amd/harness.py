@@ -777,6 +777,95 @@ def tracked_simulator_frame(rast, models, actors, timestamp: float, ego_pose: to
         return rast.forward_frame(models, poses, **frame_kw)
 
 
+class ClosedLoopScene(NamedTuple):
+    """What a closed-loop evaluation is started with -- the arguments of ``session.FrameSession``, in its order:
+    ``FrameSession(*scene[:6], **scene.options())``."""
+    settings: object
+    background: object
+    actor_models: list
+    actors: object
+    tape: list
+    spans: list
+    visibility: Optional[list] = None
+    sky_cube: Optional[torch.Tensor] = None
+    K: object = None
+    sky_fill: float = 0.0
+    affines: Optional[torch.Tensor] = None
+    object_models: Optional[list] = None
+    layer_bg: Optional[torch.Tensor] = None
+
+    def options(self) -> dict:
+        return {f: getattr(self, f) for f in self._fields[6:]}
+
+
+def closed_loop_frame(scene: ClosedLoopScene, k: int, camera=None, *, bound: bool = True, session=None, K=None,
+                      **frame_kw) -> dict:
+    """Frame ``k`` of the closed loop (simulator.py:215-328): the tape entry's scene from the tape's own pose
+    (``camera=None``) or from a moved camera (CPU ``CameraTensors`` or an ``(R, T)`` pair, :226-242).
+      bound=True   ``session.frame(k, camera)`` on a ``FrameSession`` bound once to ``scene`` (``session=``)
+      bound=False  the per-frame route: the visible list and the Fourier times on the host, ``make_camera(...,
+                   device=dev)`` and a settings object for that camera, ``tracked_simulator_frame(device_poses=True)``
+                   (the pose launch, the packing, the table upload and the pose gather), ``ray_matrix_host`` for the
+                   sky, ``affine=`` where given.  It reads nothing a session baked.
+    Both give the same frame, bit for bit (tests/test_gpu_session.py)."""
+    if bound:
+        if session is None:
+            raise ValueError("bound=True needs the FrameSession bound to the scene (session=)")
+        return session.frame(k, camera, K=K, **frame_kw)
+    from .composed import ComposedRasterizer, ModelParams
+    from .rasterizer import GaussianRasterizationSettings
+    from .sky import ray_matrix_host
+    from .trajectory import camera_from_tape
+    rs, entry = scene.settings, scene.tape[k]
+    H, W = int(rs.image_height), int(rs.image_width)
+    dev = rs.bg.device
+    table = scene.actors.table
+    ts = float(entry["timestamp"])
+    visible = [a for a in range(table.shape[2]) if table.start[a] <= ts <= table.end[a]
+               and (scene.visibility is None or scene.visibility[a])]
+    frame = entry.get("frame", entry["id"])
+    times = []
+    for a in visible:     # gaussian_model_actor.py:74-75; a one-frame span of a Fourier dimension 1 actor: time 0
+        start, end, scale = scene.spans[a]
+        times.append(0.0 if end == start else float(scale) * ((frame - start) / (end - start)))
+    statics = [scene.background] if isinstance(scene.background, ModelParams) else list(scene.background)
+    models = statics + [scene.actor_models[a] for a in visible]
+    if camera is None:
+        cam = camera_from_tape(entry, W=W, H=H, device=dev)
+        w2c = world2view(np.asarray(entry["rotation_matrix"], dtype=np.float64), np.asarray(entry["position"], dtype=np.float64))
+    elif isinstance(camera, CameraTensors):
+        w2c = camera.viewmatrix.transpose(0, 1).contiguous()
+        cam = CameraTensors(*camera[:4], camera.viewmatrix.to(dev), camera.projmatrix.to(dev), camera.campos.to(dev))
+    else:
+        R, T = (np.asarray(x, dtype=np.float64) for x in camera)
+        cam = camera_from_tape(dict(rotation_matrix=R, position=T), W=W, H=H, device=dev)
+        w2c = world2view(R, T)
+    settings = GaussianRasterizationSettings(**settings_kwargs(cam, rs.sh_degree, bg=rs.bg, scale_modifier=rs.scale_modifier,
+                                                               debug=rs.debug))
+    kw = dict(frame_kw)
+    if scene.sky_cube is not None:
+        if K is None:
+            K = scene.K
+        if K is None:
+            s = W / WAYMO_W
+            K = [[WAYMO_FX * s, 0.0, W / 2.0], [0.0, WAYMO_FY * s, H / 2.0], [0.0, 0.0, 1.0]]
+        kw.update(sky_cube=scene.sky_cube, ray_matrix=ray_matrix_host(K, w2c), sky_fill=scene.sky_fill)
+    if scene.affines is not None:
+        kw["affine"] = scene.affines[k]
+    if scene.object_models is not None:
+        n = len(statics)
+        kw["object_models"] = list(scene.object_models[:n]) + [scene.object_models[n + a] for a in visible]
+    if scene.layer_bg is not None:
+        kw["layer_bg"] = scene.layer_bg
+    ego = torch.from_numpy(np.asarray(entry["ego_pose"], dtype=np.float32).reshape(4, 4)).to(dev, non_blocking=True)
+    rast = ComposedRasterizer(settings)
+    if len(statics) == 1:
+        return tracked_simulator_frame(rast, models, scene.actors, ts, ego, visible, times, device_poses=True, **kw)
+    with torch.no_grad():     # (tracked_simulator_frame with more static models in front of the actors)
+        poses = tracked_poses(scene.actors, ts, ego, visible, times, device_poses=True, static=len(statics))
+        return rast.forward_frame(models, poses, **kw)
+
+
 def tracked_train_step(rast, models, actors, timestamp: float, ego_pose: torch.Tensor, visible, fourier_times=None, *,
                        device_poses: bool = True, weights=None, means2D=None):
     """Actor poses -> train step: the forward + backward of one training iteration with ``opt_track`` -- the composed

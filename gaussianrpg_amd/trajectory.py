@@ -48,6 +48,26 @@ def camera_from_tape(entry: dict, *, W=hz.WAYMO_W, H=hz.WAYMO_H, device="cpu") -
                           cy=H / 2.0, device=device)
 
 
+def extend_tape(tape: List[dict], n: int, period: float) -> List[dict]:
+    """The tape with ``n`` more entries that repeat its last pose at ``timestamp + i * period`` (i = 1..n), ``id``
+    counting on: what the simulator does when the loop outruns the tape (simulator.py:221-223).  A new list; the
+    entries of ``tape`` are shared, the new ones are copies."""
+    if not tape:
+        raise ValueError("the tape is empty: there is no last pose to repeat")
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    last = tape[-1]
+    out = list(tape)
+    for i in range(1, n + 1):
+        e = dict(last)
+        e["id"] = last["id"] + i
+        e["timestamp"] = last["timestamp"] + i * period
+        if "frame" in last:
+            e["frame"] = last["frame"] + i
+        out.append(e)
+    return out
+
+
 def shard_frames(num_frames: int, rank: int, world: int) -> List[int]:
     """Round-robin frame ownership: frame i belongs to rank i mod world."""
     return list(range(rank, num_frames, world))

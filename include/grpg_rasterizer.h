@@ -588,6 +588,57 @@ GRPG_API int grpg_bind_device_poses(const float* pose_rot, const float* pose_tra
 GRPG_API int grpg_device_poses_bound(void);
 
 /*
+ * Segment tables of a whole pose tape, baked once (additive; ABI 7 unchanged).  A closed-loop evaluation session
+ * replays a tape of T entries; everything in a frame's device segment table -- which models the frame shows, their
+ * index ranges, the IDFT rows, the tracked poses -- is fixed by the tape entry, only the camera moves.
+ * grpg_frame_tables_bake builds the tables of all T frames in CALLER-OWNED device memory, in one upload and one launch;
+ * grpg_bind_frame_table then hands one frame's rows to the next evaluation call, which reads them where they lie: no
+ * host fill, no table upload, no pose gather in front of the frame.
+ *
+ * grpg_frame_tables_bytes(total_rows): the bytes `rows_device` needs for total_rows rows (all frames' rows, frame
+ * after frame); 0 for total_rows <= 0.  A pure size query: no device needed.  One row is 144 bytes; a frame's rows
+ * start at rows_device + 144 * frame_first[k].  rows_device must be 16-byte aligned.
+ *
+ * grpg_frame_tables_bake
+ *   models / num_models   the scene's model descriptors (HOST array): pointers, count, fourier_dim, rigid, flip as
+ *                         in a composed call; obj_rot / obj_trans are the pose of a row WITHOUT a pose row (a static
+ *                         model: ignored by the kernels; an actor the host poses: taken as they are); idft is ignored
+ *   frame_first           HOST int32 [num_frames + 1]: frame k owns rows frame_first[k] .. frame_first[k+1] - 1;
+ *                         frame_first[0] = 0, ascending, 1..GRPG_MAX_SEGMENTS rows per frame
+ *   row_model             HOST int32 [total_rows]: the model of each row
+ *   row_pose              HOST int32 [total_rows]: the row of pose_rot / pose_trans the row takes its pose from
+ *                         (for a [T,A,*] pose batch: frame * A + actor), or -1; a row >= 0 needs a rigid model
+ *   row_idft              HOST fp32 [total_rows, GRPG_MAX_FOURIER]
+ *   row_class             HOST bytes [total_rows], != 0 = the row's model belongs to the object layer
+ *                         (grpg_forward_composed_layers' segment_class), or NULL: the model's rigid flag
+ *   pose_rot / pose_trans device fp32 [num_pose_rows, 4] (w,x,y,z) / [num_pose_rows, 3], ego pose applied
+ * Every baked row is byte for byte the row a composed call with the same segments, and the same poses bound through
+ * grpg_bind_device_poses, leaves in its own table: the kernel copies words (csrc/frame_table.hip).  The call waits
+ * for its stream before it returns (the staging it uploads from is its own); it is a bind-time call.
+ * Returns GRPG_OK, GRPG_ERR_NO_DEVICE, GRPG_ERR_INVALID_ARGUMENT (a NULL or misaligned pointer, an index out of
+ * range, a pose row for a model with rigid == 0, a descriptor a composed call would refuse) or GRPG_ERR_HIP.
+ *
+ * grpg_bind_frame_table(rows_device, num_segments, P): binds one frame's rows (device pointer to its first row, the
+ * number of rows, the sum of their counts) for the NEXT grpg_forward_composed{,_flags,_layers,_frame,_features} on
+ * this thread.  That call still takes the frame's `segments` (its checks and P come from them; the poses and idft in
+ * them are not looked at), but reads the bound rows in place of building a table.  The binding is cleared whatever
+ * that call returns.  The call refuses it with GRPG_ERR_INVALID_ARGUMENT when it is a training forward (no
+ * GRPG_FORWARD_NO_BACKWARD: the backward rebuilds the table from the host), when it renders feature planes, when its
+ * num_segments or P differs from the binding's, or when device poses are bound for the same call.  Lifetime: the
+ * rows, and everything they point at, stay valid and unchanged until the consuming call's work on its stream has run.
+ * Returns GRPG_OK, GRPG_ERR_NO_DEVICE (binding gone), or GRPG_ERR_INVALID_ARGUMENT (NULL or misaligned rows,
+ * num_segments outside 1..GRPG_MAX_SEGMENTS, P outside 1..2^28-1) -- a refused bind leaves no binding.
+ * grpg_frame_tables_bound: 1 while a binding waits on this thread, 0 otherwise (a pure query).
+ */
+GRPG_API size_t grpg_frame_tables_bytes(long long total_rows);
+GRPG_API int grpg_frame_tables_bake(void* rows_device, const grpg_model_segment* models, int num_models,
+                 const int* frame_first, int num_frames, const int* row_model, const int* row_pose,
+                 const float* row_idft, const unsigned char* row_class, const float* pose_rot,
+                 const float* pose_trans, long long num_pose_rows, void* hip_stream);
+GRPG_API int grpg_bind_frame_table(const void* rows_device, int num_segments, int P);
+GRPG_API int grpg_frame_tables_bound(void);
+
+/*
  * Sky cube map without nvdiffrast (additive).  Replaces
  * SkyCubeMap.forward (lib/models/sky_cubemap.py:77-122: get_rays_torch + mask + dr.texture(...,
  * filter_mode='linear', boundary_mode='cube') + clamp) and the composite of
