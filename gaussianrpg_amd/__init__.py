@@ -16,6 +16,8 @@ Layout:
                   launch, with backward to opt_trans / opt_rots (the step in front of composed.py)
   session.py      closed-loop evaluation: a scene bound once to a pose tape (segment tables of all frames baked on the
                   device), then one call per frame with nothing in front of its first launch
+  closed_loop.py  the loop around the session on the device: detections -> object positions, brake decision, ego step
+                  and the next frame's camera row in one launch per frame, no host wait
   build.py        in-tree build (hipcc for gfx950, g++ for the binding)
 
 Importing this package does not load native code; ``gaussianrpg_amd.rasterizer`` does, and fails

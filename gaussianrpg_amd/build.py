@@ -93,6 +93,11 @@ HIP_UNITS = {
     "segment_pose.hip": [],
     # segment tables of a whole pose tape, baked once at bind time: loads and stores only as well
     "frame_table.hip": [],
+    # the closed loop's tail (ranging, brake decision, ego step, next camera row): float64, every step the single
+    # operation of the numpy restatement (tests/loop_truth.py) -- contraction off for the whole unit; the three
+    # reductions numpy gives to BLAS are explicit fma() chains; the float32 xywh / gn a correctly rounded division;
+    # no atomics
+    "ego_loop.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "api.hip": [],
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept

@@ -2136,6 +2136,141 @@ std::tuple<torch::Tensor, torch::Tensor> DetectDetections(
   return std::make_tuple(det, count);
 }
 
+// ---- the closed loop's tail (gaussianrpg_amd/closed_loop.py; csrc/ego_loop.hip) ----
+
+namespace {
+// det / count / pos / n and the ranging constants of one call, checked before the device is needed.  params: fy,
+// cam_height, k_inv 9, p_inv 16.
+struct RangingCall {
+  grpg_object_positions_request r{};
+  torch::Device device;
+  RangingCall(const std::string& who, const torch::Tensor& det, const torch::Tensor& count, const int64_t height,
+              const int64_t width, const int64_t nc, const uint64_t mask_lo, const uint64_t mask_hi,
+              const std::vector<double>& params, const torch::Tensor& pos, const torch::Tensor& n)
+      : device(det.device()) {
+    TORCH_CHECK(det.scalar_type() == torch::kFloat32 && det.dim() == 3 && det.size(2) == 6 && det.size(0) >= 1 &&
+                    det.is_contiguous(),
+                who, ": det must be a contiguous float32 [bs,max_det,6] tensor (got ", det.sizes(), ")");
+    const int64_t bs = det.size(0), max_det = det.size(1);
+    TORCH_CHECK(max_det >= 1 && max_det <= GRPG_EGO_MAX_DET, who, ": max_det must lie in [1, ", GRPG_EGO_MAX_DET,
+                "] (got ", max_det, "): one lane of one wave owns a detection row");
+    TORCH_CHECK(nc >= 0 && nc <= GRPG_EGO_MAX_CLASSES, who, ": nc must lie in [0, ", GRPG_EGO_MAX_CLASSES, "] (got ", nc,
+                ")");
+    TORCH_CHECK(bs < (int64_t(1) << 24), who, ": bs must be below 2^24");
+    TORCH_CHECK(det.is_cuda(), who, ": det is on ", det.device(), "; it must live on a ROCm/HIP device (torch device "
+                "'cuda'): this op has no CPU path");
+    TORCH_CHECK(count.scalar_type() == torch::kInt32 && count.dim() == 1 && count.size(0) == bs &&
+                    count.is_contiguous() && count.device() == device,
+                who, ": count must be a contiguous int32 [", bs, "] tensor on ", device);
+    TORCH_CHECK(pos.scalar_type() == torch::kFloat64 && pos.dim() == 3 && pos.size(0) == bs && pos.size(1) == max_det &&
+                    pos.size(2) == 2 && pos.is_contiguous() && pos.device() == device,
+                who, ": pos must be a contiguous float64 [", bs, ",", max_det, ",2] tensor on ", device);
+    TORCH_CHECK(n.scalar_type() == torch::kInt32 && n.dim() == 1 && n.size(0) == bs && n.is_contiguous() &&
+                    n.device() == device,
+                who, ": n must be a contiguous int32 [", bs, "] tensor on ", device);
+    TORCH_CHECK(params.size() == 27, who, ": the ranging constants are fy, cam_height, k_inv (9) and p_inv (16)");
+    TORCH_CHECK(height >= 1 && width >= 1 && height < (1 << 24) && width < (1 << 24), who,
+                ": the frame's height and width must lie in [1, 2^24)");
+    r.det = det.data_ptr<float>();
+    r.count = count.data_ptr<int>();
+    r.bs = (int)bs;
+    r.max_det = (int)max_det;
+    r.pos = pos.data_ptr<double>();
+    r.n = n.data_ptr<int>();
+    grpg_ranging& g = r.ranging;
+    g.height = (int)height;
+    g.width = (int)width;
+    g.nc = (int)nc;
+    g.class_mask[0] = mask_lo;
+    g.class_mask[1] = mask_hi;
+    g.fy = params[0];
+    g.cam_height = params[1];
+    std::copy(params.begin() + 2, params.begin() + 11, g.k_inv);
+    std::copy(params.begin() + 11, params.end(), g.p_inv);
+  }
+};
+}  // namespace
+
+void ObjectPositions(const torch::Tensor& det, const torch::Tensor& count, const int64_t height, const int64_t width,
+                     const int64_t nc, const uint64_t mask_lo, const uint64_t mask_hi, const std::vector<double>& params,
+                     const torch::Tensor& pos, const torch::Tensor& n) {
+  RangingCall c("object_positions", det, count, height, width, nc, mask_lo, mask_hi, params, pos, n);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(c.device);
+  run("grpg_object_positions", [&](void* stream) {
+    c.r.hip_stream = stream;
+    return grpg_object_positions(&c.r);
+  });
+}
+
+void EgoLoopStep(const torch::Tensor& det, const torch::Tensor& count, const int64_t height, const int64_t width,
+                 const int64_t nc, const uint64_t mask_lo, const uint64_t mask_hi, const std::vector<double>& params,
+                 const torch::Tensor& pos, const torch::Tensor& n, const int64_t policy, const int64_t substeps,
+                 const double brake_distance, const double cipv_lat_range, const double command,
+                 const c10::optional<torch::Tensor>& command_device, const double period, const torch::Tensor& tape,
+                 const torch::Tensor& cameras, const std::vector<double>& proj_t, const std::vector<double>& ray_k_inv,
+                 const torch::Tensor& state, const c10::optional<torch::Tensor>& log, const int64_t log_index,
+                 const torch::Tensor& camera) {
+  const std::string who = "ego_loop_step";
+  RangingCall c(who, det, count, height, width, nc, mask_lo, mask_hi, params, pos, n);
+  const torch::Device device = c.device;
+  TORCH_CHECK(policy == GRPG_POLICY_NONE || policy == GRPG_POLICY_AEB, who, ": unknown policy ", policy);
+  TORCH_CHECK(substeps >= 1 && substeps < (1 << 20), who, ": substeps must be at least 1 (got ", substeps, ")");
+  TORCH_CHECK(period > 0.0 && std::isfinite(period), who, ": period must be positive and finite");
+  TORCH_CHECK(tape.scalar_type() == torch::kFloat64 && tape.dim() == 2 && tape.size(0) >= 1 && tape.size(1) == 13 &&
+                  tape.is_contiguous() && tape.device() == device && tape.size(0) < (int64_t(1) << 24),
+              who, ": tape must be a contiguous float64 [T,13] tensor on ", device);
+  const int64_t T = tape.size(0);
+  TORCH_CHECK(cameras.scalar_type() == torch::kFloat32 && cameras.dim() == 2 && cameras.size(0) == T &&
+                  cameras.size(1) == GRPG_CAMERA_ROW && cameras.is_contiguous() && cameras.device() == device,
+              who, ": cameras must be a contiguous float32 [", T, ",", GRPG_CAMERA_ROW, "] tensor on ", device);
+  TORCH_CHECK(camera.scalar_type() == torch::kFloat32 && camera.dim() == 1 && camera.size(0) == GRPG_CAMERA_ROW &&
+                  camera.is_contiguous() && camera.device() == device,
+              who, ": camera must be a contiguous float32 [", GRPG_CAMERA_ROW, "] tensor on ", device);
+  TORCH_CHECK(state.scalar_type() == torch::kFloat64 && state.dim() == 1 && state.size(0) == GRPG_EGO_STATE &&
+                  state.is_contiguous() && state.device() == device,
+              who, ": state must be a contiguous float64 [", GRPG_EGO_STATE, "] tensor on ", device);
+  TORCH_CHECK(proj_t.size() == 16 && (ray_k_inv.empty() || ray_k_inv.size() == 9), who,
+              ": proj_t holds 16 values, ray_k_inv none or 9");
+  grpg_ego_loop_request q{};
+  if (log.has_value() && log->defined()) {
+    TORCH_CHECK(log->scalar_type() == torch::kFloat64 && log->dim() == 2 && log->size(1) == GRPG_EGO_STATE &&
+                    log->is_contiguous() && log->device() == device,
+                who, ": log must be a contiguous float64 [steps,", GRPG_EGO_STATE, "] tensor on ", device);
+    TORCH_CHECK(log_index >= 0 && log_index < log->size(0), who, ": log index ", log_index, " is outside the log's ",
+                log->size(0), " rows");
+    q.log = log->data_ptr<double>();
+    q.log_rows = log->size(0);
+    q.log_index = log_index;
+  }
+  if (command_device.has_value() && command_device->defined()) {
+    TORCH_CHECK(policy == GRPG_POLICY_NONE, who, ": a command is given only with policy=None");
+    TORCH_CHECK(command_device->scalar_type() == torch::kFloat64 && command_device->numel() == 1 &&
+                    command_device->device() == device,
+                who, ": a device command must be a one-element float64 tensor on ", device);
+    q.command_device = command_device->data_ptr<double>();
+  }
+  q.policy = (int)policy;
+  q.substeps = (int)substeps;
+  q.tape_len = (int)T;
+  q.has_ray = ray_k_inv.empty() ? 0 : 1;
+  q.brake_distance = brake_distance;
+  q.cipv_lat_range = cipv_lat_range;
+  q.command = command;
+  q.period = period;
+  q.tape = tape.data_ptr<double>();
+  q.cameras = cameras.data_ptr<float>();
+  for (int i = 0; i < 16; ++i) q.proj_t[i] = (float)proj_t[i];
+  for (size_t i = 0; i < ray_k_inv.size(); ++i) q.ray_k_inv[i] = ray_k_inv[i];
+  q.state = state.data_ptr<double>();
+  q.camera = camera.data_ptr<float>();
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(device);
+  run("grpg_ego_loop_step", [&](void* stream) {
+    q.detections = c.r;
+    q.detections.hip_stream = stream;
+    return grpg_ego_loop_step(&q);
+  });
+}
+
 // ---- tracklets -> actor poses (gaussianrpg_amd/tracks.py; csrc/tracks.hip) ----
 
 namespace {
@@ -3131,6 +3266,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("max_wh") = 7680.0, pybind11::arg("frame_map") = std::vector<double>(),
         pybind11::arg("det_out") = pybind11::none(), pybind11::arg("count_out") = pybind11::none());
   m.def("detect_workspace_bytes", [](int bs, int N) { return grpg_detect_workspace_bytes(bs, N); });
+  // the closed loop's tail: ranging alone, and the fused step (closed_loop.py)
+  m.def("object_positions", &ObjectPositions);
+  m.def("ego_loop_step", &EgoLoopStep);
   // tracklets -> actor poses (tracks.py): (rot [T,A,4], trans [T,A,3], active [T,A], chosen [T,A,4]) and the dense
   // (g_opt_trans [F,M,3], g_opt_rots [F,M,1])
   m.def("track_poses_forward", &TrackPosesForward, pybind11::arg("table"), pybind11::arg("timestamps"),

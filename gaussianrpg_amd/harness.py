@@ -866,6 +866,75 @@ def closed_loop_frame(scene: ClosedLoopScene, k: int, camera=None, *, bound: boo
         return rast.forward_frame(models, poses, **kw)
 
 
+def closed_loop_step(session, loop, heads_of, geom, *, plan=None, max_det: int = 10, conf_thres: float = 0.25,
+                     iou_thres: float = 0.45, command=None) -> dict:
+    """One frame of ``closed_loop_run`` on either route, told apart by the loop object: render the loop's next frame,
+    ``heads_of(frame)`` -> ``detections_from_heads``, the loop's step.  Returns the frame."""
+    from .closed_loop import EgoLoop
+    from .perception import detections_from_heads
+    on_device = isinstance(loop, EgoLoop)
+    frame = session.frame(loop.k, camera=loop.camera if on_device else (loop.R, loop.T))
+    det, count = detections_from_heads(heads_of(frame), geom, conf_thres, iou_thres, max_det=max_det, plan=plan)
+    if on_device:
+        loop.step(det, count, command)
+    else:
+        det_host = det.cpu().numpy()               # the one host wait of the route
+        # (count[b] without a second copy: a kept row's confidence lies above conf_thres >= 0, the rows below are zeros)
+        loop.step([rows[:int((rows[:, 4] > 0).sum())] for rows in det_host], command)
+    return frame
+
+
+def closed_loop_run(scene: ClosedLoopScene, heads_for_frame, steps: int, *, device_loop: bool = True, session=None,
+                    ranging=None, geom=None, plan=None, max_det: int = 10, conf_thres: float = 0.25,
+                    iou_thres: float = 0.45, policy="aeb", command_for_step=None, keep_frames: bool = False,
+                    keep_rows: bool = False, read: bool = True, loop=None, **loop_kw) -> dict:
+    """``steps`` frames of the closed loop (simulator.py:215-426 with the dummy AEB controller), in the order
+    ``closed_loop.py`` fixes: render, detect, ranging, policy, ego step.  ``heads_for_frame(i, frame)`` returns the
+    detector's conv outputs for step ``i`` (``detections_from_heads``'s ``heads``); ``geom`` / ``plan`` / ``max_det``
+    / the thresholds are that function's.  ``ranging``: a ``closed_loop.Ranging``.  ``policy`` and ``loop_kw``
+    (``brake_distance``, ``cipv_lat_range``, ``period``, ``substeps``): ``EgoLoop``'s; with ``policy=None``,
+    ``command_for_step(i)`` gives step i's command.
+      device_loop=True   ``session.frame(loop.k, camera=loop.camera)``, ``detections_from_heads``, ``EgoLoop.step``:
+                         nothing waits on the host until the log is read (``read=False``: not even then; the caller
+                         reads ``result['loop'].log()``)
+      device_loop=False  the route without the kernel: ``session.frame(k, camera=(R, T))``, ``detections_from_heads``,
+                         ONE wait for ``det`` / ``count``, ``closed_loop.HostLoop`` (numpy tail, Python controller)
+    ``loop``: an ``EgoLoop`` / ``HostLoop`` built earlier for this route; it is reset and used (building one uploads the
+    tape, which waits for the device).
+    Returns ``loop``, ``log`` (float64 [steps,16], ``closed_loop.LOG_FIELDS``; None with ``read=False``), and with
+    ``keep_frames`` / ``keep_rows`` the rgb8 frames (device tensors) and the float32 [48] camera row each frame was
+    rendered with (device tensors on the device route, numpy rows on the host route)."""
+    from . import closed_loop as cl
+    from .session import FrameSession, _camera_row, camera_from_pose
+    if session is None:
+        session = FrameSession(*scene[:6], **scene.options())
+    if ranging is None or geom is None:
+        raise ValueError("closed_loop_run needs ranging= (closed_loop.Ranging) and geom= (perception.DetectGeometry)")
+    H, W = session._size
+    frames, rows = [], []
+    if loop is not None:
+        loop.reset()
+    elif device_loop:
+        loop = cl.EgoLoop(session, ranging, policy=policy, steps=steps, **loop_kw)
+    else:
+        loop = cl.HostLoop(scene.tape, ranging, policy=policy, **loop_kw)
+    for i in range(steps):
+        if keep_rows:
+            rows.append(loop.camera.row.clone() if device_loop else
+                        _camera_row(camera_from_pose(loop.R, loop.T, W, H), session._Kinv))
+        command = None if policy is not None or command_for_step is None else command_for_step(i)
+        frame = closed_loop_step(session, loop, lambda frame: heads_for_frame(i, frame), geom, plan=plan,
+                                 max_det=max_det, conf_thres=conf_thres, iou_thres=iou_thres, command=command)
+        if keep_frames:
+            frames.append(frame["rgb8"].clone())
+    out = dict(loop=loop, log=loop.log() if read else None)
+    if keep_frames:
+        out["frames"] = frames
+    if keep_rows:
+        out["rows"] = rows
+    return out
+
+
 def tracked_train_step(rast, models, actors, timestamp: float, ego_pose: torch.Tensor, visible, fourier_times=None, *,
                        device_poses: bool = True, weights=None, means2D=None):
     """Actor poses -> train step: the forward + backward of one training iteration with ``opt_track`` -- the composed

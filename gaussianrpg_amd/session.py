@@ -150,6 +150,27 @@ def _camera_row(cam: hz.CameraTensors, Kinv: Optional[np.ndarray]) -> np.ndarray
     return row
 
 
+class CameraRow:
+    """A camera that already lies on the device: one contiguous float32 ``[CAMERA_ROW]`` row in the layout of the
+    session's own cameras (view^T 16, full projection^T 16, centre 3 + 1 spare, ray matrix 9 + 3 spare).
+    ``FrameSession.frame(k, camera=row)`` hands its four views straight to the frame call: no staging, no copy, no
+    event.  ``closed_loop.EgoLoop.camera`` is one; the kernel that wrote the row and the frame that reads it are
+    ordered by the stream they share."""
+
+    def __init__(self, row: torch.Tensor):
+        if not (isinstance(row, torch.Tensor) and row.is_cuda and row.dtype == torch.float32
+                and tuple(row.shape) == (CAMERA_ROW,) and row.is_contiguous()):
+            raise ValueError("a CameraRow is a contiguous float32 [%d] device tensor" % CAMERA_ROW)
+        self.row = row.detach()
+        self.views = (self.row[_VIEW], self.row[_PROJ], self.row[_POS], self.row[_RAY])
+
+    def tensors(self, H, W, tanfovx, tanfovy) -> hz.CameraTensors:
+        """The row read back as CPU ``CameraTensors`` (one device-to-host copy, one host wait): for tests and logs."""
+        r = self.row.cpu()
+        return hz.CameraTensors(int(H), int(W), tanfovx, tanfovy, r[_VIEW].reshape(4, 4).clone(),
+                                r[_PROJ].reshape(4, 4).clone(), r[_POS].clone())
+
+
 class FrameSession:
     """A scene bound to a pose tape for evaluation: ``session.frame(k)`` is the closed loop's per-frame call.
 
@@ -287,12 +308,19 @@ class FrameSession:
         """Frame ``k`` of the tape -> the dict of ``ComposedRasterizer.forward_frame``.  ``camera=None``: the tape's
         own pose -- no host-to-device copy at all.  ``camera``: CPU ``CameraTensors`` or an ``(R, T)`` pair (the closed
         loop's moved camera); its 35 floats and the ray matrix reach the device in ONE asynchronous copy from a pinned
-        ring slot.  ``K``: other intrinsics for this frame's sky rays (then the ray matrix is staged like a moved
-        camera's).  ``k`` outside ``0..T-1`` raises ``IndexError`` before anything is enqueued."""
+        ring slot.  ``camera``: a ``CameraRow`` (a float32 ``[48]`` row on the device, ``closed_loop.EgoLoop.camera``):
+        its views go to the frame call as they are -- no staging, no copy, no event.  ``K``: other intrinsics for this
+        frame's sky rays (then the ray matrix is staged like a moved camera's).  ``k`` outside ``0..T-1`` raises ``IndexError`` before anything is enqueued."""
         k = self.plan.check(k)
         rs = self.settings
         H, W = self._size
-        if camera is None and (K is None or self.sky_cube is None):
+        if isinstance(camera, CameraRow):
+            if K is not None:
+                raise ValueError("a CameraRow carries its own ray matrix: K cannot be given with it")
+            if camera.row.device != self.device:
+                raise ValueError("the CameraRow is on %s, the session on %s" % (camera.row.device, self.device))
+            view, proj, campos, ray = camera.views
+        elif camera is None and (K is None or self.sky_cube is None):
             view, proj, campos, ray = self._tape_views[k]
         else:
             Kinv = self._Kinv

@@ -1111,6 +1111,93 @@ GRPG_API int grpg_track_poses_backward(const grpg_track_table* table, int T, con
                                        float* g_opt_trans, float* g_opt_rots, void* hip_stream);
 
 /*
+ * The closed loop's tail on the device (csrc/ego_loop.hip): detections -> object positions
+ * (simulator.py:379-399, :163-213), the dummy AEB controller (AEB_controller.py:52-97), control_callback (:422-426),
+ * `substeps` ticks of next_frame's dynamics (:218-242, :264-269) and the next frame's camera row, in ONE launch of one
+ * wave on the caller's stream.  No atomics, no host wait, nothing read back.  All ranging and dynamics arithmetic is
+ * float64; tests/loop_truth.py restates every step in numpy.
+ *
+ * grpg_ranging: height / width the frame's (self.H, self.W), fy = K[1][1], cam_height, k_inv / p_inv the float64
+ * inverses of the intrinsics [3,3] and the extrinsics [4,4], row-major, computed once by the caller; class c is kept
+ * when c < nc and bit (c & 63) of class_mask[c >> 6] is set (nc <= 128).
+ *
+ * grpg_object_positions: det float32 [bs,max_det,6] and count int32 [bs] as grpg_nms_detections leaves them
+ * (count is clamped to 0..max_det); lane d of image b's wave takes row d.  (x1+x2)/2, (y1+y2)/2, x2-x1, y2-y1 and
+ * their division by W, H, W, H are float32 (torch), then float64: u = x W, v = y H, w, h; v1 = v + h/2;
+ * b = atan((v1 - H/2) / fy); depth = (cam_height / sin b) cos b; c = k_inv (depth (u, v1, 1)); o = p_inv (c, 1);
+ * d = (o[0], -o[1]); d[0] <= 0 -> (0, 0); the row is kept when d[0] != 0 or d[1] != 0 (a NaN is kept).  The two
+ * matrix-vector products are ascending fused chains fma(a2, x2, fma(a1, x1, a0 x0)), every other step one rounded
+ * operation.  pos float64 [bs,max_det,2] gets the kept rows in the order of `reversed(det)` (last row first) and
+ * zeros below n[b]; n int32 [bs].  Every element of pos and n is written.
+ *
+ * grpg_ego_loop_step: the same ranging for every image (one wave takes them in turn; the positions of all images
+ * form one list, image after image, as the reference appends them to one PoseArray), then
+ *   policy GRPG_POLICY_AEB   cipv_lon_dist = Python's min() over x of the positions with -lat < y < lat, kept from the
+ *                            earlier frame when there is none; command = -13.5 / -10 / -8 / 0 for lon_velocity
+ *                            > 2 / > 1 / > 0.001 / else when cipv_lon_dist < brake_distance, else 0;
+ *          GRPG_POLICY_NONE  command = *command_device when given, else `command`;
+ *   |command| > 0 sets activated and command_brake; a zero command changes nothing;
+ *   `substeps` ticks: entry e = idx < T ? idx : T - 1, timestamp = tape[e] (+ (idx - T + 1) period beyond the tape);
+ *   activated: v = max(forward_velocity + command_brake period, 0) (a NaN stays), position = last position +
+ *   (v period) (0, 0, -1), rotation the last one; else the entry's pose; idx += 1; forward_velocity =
+ *   sqrt(fused chain of the squared differences) / period; the AEB's pose_callback with the stamp split into
+ *   sec = int(t) and nanosec = int(t 1e9) mod 1e9 (int64 truncation);
+ *   the camera row of the last tick's pose into camera float32 [48] (view^T 16, full projection^T 16, centre 3 + 1,
+ *   ray matrix 9 + 3): not activated -> cameras[e] copied; activated -> float64 R, T rounded once to float32, the
+ *   projection sum_k view_t[i][k] proj_t[k][j] and the centre -(R T) in float64 from the float32 operands, k
+ *   ascending, rounded once, the ray matrix R k_inv (has_ray) rounded once.
+ * tape float64 [T,13]: rotation 9, position 3, timestamp.  cameras float32 [T,48].  state float64 [16]: position 3,
+ * forward_velocity, command_brake, activated, cipv_lon_dist, lon_velocity, the AEB's last stamp, idx, the AEB's last
+ * z, the tape entry of the held rotation, timestamp, 3 spare.  log (may be NULL) float64 [log_rows,16], row
+ * log_index: the frame's stamp, n over all images, cipv_lon_dist, command, then the state after the ticks:
+ * forward_velocity, position 3, activated, lon_velocity, command_brake, idx, timestamp; candidate seen (0/1), the
+ * held rotation's entry, 0.
+ *
+ * Purely additive exports: GRPG_ABI_VERSION stays 7.  GRPG_ERR_INVALID_ARGUMENT -- before anything is enqueued -- for
+ * a NULL request or pointer, a misaligned pointer, bs < 1, max_det outside [1, 64], nc outside [0, 128], height or
+ * width < 1, an unknown policy, tape_len < 1, substeps < 1, a period that is not positive and finite, log_index
+ * outside [0, log_rows).
+ */
+#define GRPG_EGO_MAX_DET 64
+#define GRPG_EGO_MAX_CLASSES 128
+#define GRPG_EGO_STATE 16
+#define GRPG_CAMERA_ROW 48
+#define GRPG_POLICY_NONE 0
+#define GRPG_POLICY_AEB 1
+typedef struct grpg_ranging {
+  int height, width, nc, reserved;
+  unsigned long long class_mask[2];
+  double fy, cam_height;
+  double k_inv[9];
+  double p_inv[16];
+} grpg_ranging;
+typedef struct grpg_object_positions_request {
+  const float* det;
+  const int* count;
+  int bs, max_det;
+  grpg_ranging ranging;
+  double* pos;
+  int* n;
+  void* hip_stream;
+} grpg_object_positions_request;
+typedef struct grpg_ego_loop_request {
+  grpg_object_positions_request detections;
+  int policy, substeps, tape_len, has_ray;
+  double brake_distance, cipv_lat_range, command, period;
+  const double* command_device;
+  const double* tape;
+  const float* cameras;
+  float proj_t[16];
+  double ray_k_inv[9];
+  double* state;
+  double* log;
+  long long log_rows, log_index;
+  float* camera;
+} grpg_ego_loop_request;
+GRPG_API int grpg_object_positions(const grpg_object_positions_request* request);
+GRPG_API int grpg_ego_loop_step(const grpg_ego_loop_request* request);
+
+/*
  * Per-stage device timing, measured with HIP events recorded on the op's own stream (so it sees
  * the real kernel durations whatever stream torch calls "current").  While enabled, every
  * grpg_forward on this thread records GRPG_NUM_STAGES+1 events and returns without waiting;
