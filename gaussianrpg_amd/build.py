@@ -98,14 +98,19 @@ HIP_UNITS = {
     # reductions numpy gives to BLAS are explicit fma() chains; the float32 xywh / gn a correctly rounded division;
     # no atomics
     "ego_loop.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # the detector's network: an implicit-GEMM convolution on the f32 matrix instructions (the chain of an output
+    # element is the instruction's own, contraction has no say in it) and SPP's max-pools; SiLU's x * (1 / (1 + expf(-x)))
+    # is a correctly rounded division and a rounded product, as nms.hip's sigmoid; no atomics
+    "detector.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "api.hip": [],
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept
 # next to the object as <unit>.remarks: the render launch's occupancy is a budget the sources promise
 # (render_fwd.hip render_min_waves; tests/test_render_resources.py reads the file), and so is
 # the eight waves per SIMD of the specialised preprocess instantiations (tests/test_preprocess_resources.py); the
-# use_mlp colour correction promises kernels without scratch (tests/test_color_mlp_host.py)
-REMARK_UNITS = ("render_fwd.hip", "preprocess.hip", "color_mlp.hip")
+# use_mlp colour correction promises kernels without scratch (tests/test_color_mlp_host.py), and so do the detector's
+# convolution and pool, whose LDS per workgroup is a budget too (tests/test_detector_resources.py)
+REMARK_UNITS = ("render_fwd.hip", "preprocess.hip", "color_mlp.hip", "detector.hip")
 
 
 def headers():

@@ -630,6 +630,81 @@ def simulator_detections_from_heads(heads, geom, plan, fused: bool = True, *, co
                                 iou_thres=iou_thres, classes=classes, agnostic=agnostic, max_det=max_det)
 
 
+def detector_torch(spec, state_dict, dtype=torch.float32, device="cpu", per_layer: bool = False):
+    """The detector's network as ordinary PyTorch ops -- the reference's lines (models/yolo.py:119-159 over
+    models/common.py) with ``F.conv2d``, ``F.silu``, ``torch.cat``, ``F.max_pool2d`` and ``F.interpolate``: the route
+    ``detector.DetectorNet`` replaces.  spec: a ``detector.DetectorSpec``; state_dict: fused or unfused tensors, folded
+    in ``dtype`` as ``fuse_conv_and_bn`` does.  Usable on the CPU in float32 and float64.  Returns ``run(x)`` -> the
+    list of nl heads (``per_layer=True``: ``(heads, [every layer's output])``)."""
+    import torch.nn.functional as F
+    from .detector import fused_parameters
+    params = {c["key"]: (w.to(device), b.to(device))
+              for c, (w, b) in zip(spec.convs(), fused_parameters(spec, state_dict, dtype))}
+
+    def conv(key, x, k=1, s=1, act=True):
+        w, b = params[key]
+        y = F.conv2d(x, w, b, stride=s, padding=k // 2)
+        return F.silu(y) if act else y
+
+    def run(x):
+        with torch.no_grad():
+            x = x.to(device, dtype)
+            ys, heads = [], None
+            for i, L in enumerate(spec.layers):
+                ins = [x if j < 0 else ys[j] for j in L["f"]]
+                t, v = L["type"], ins[0]
+                if t == "Focus":
+                    v = torch.cat([v[..., ::2, ::2], v[..., 1::2, ::2], v[..., ::2, 1::2], v[..., 1::2, 1::2]], 1)
+                    y = conv("%d.conv" % i, v, L["k"], L["s"])
+                elif t == "Conv":
+                    y = conv("%d" % i, v, L["k"], L["s"])
+                elif t == "C3":
+                    m = conv("%d.cv1" % i, v)
+                    for j in range(L["n"]):
+                        z = conv("%d.m.%d.cv2" % (i, j), conv("%d.m.%d.cv1" % (i, j), m), 3)
+                        m = m + z if L["shortcut"] else z
+                    y = conv("%d.cv3" % i, torch.cat((m, conv("%d.cv2" % i, v)), 1))
+                elif t == "SPP":
+                    v = conv("%d.cv1" % i, v)
+                    y = conv("%d.cv2" % i, torch.cat([v] + [F.max_pool2d(v, k, 1, k // 2) for k in (5, 9, 13)], 1))
+                elif t == "Upsample":
+                    y = F.interpolate(v, scale_factor=2.0, mode="nearest")
+                elif t == "Concat":
+                    y = torch.cat(ins, 1)
+                else:
+                    heads = [conv("%d.m.%d" % (i, l), h, act=False) for l, h in enumerate(ins)]
+                    y = None
+                ys.append(y)
+            return (heads, ys) if per_layer else heads
+    return run
+
+
+def simulator_detections_from_frame(frame: torch.Tensor, net, plan, fused: bool = True, *, torch_net=None,
+                                    conf_thres: float = 0.25, iou_thres: float = 0.45, classes=None,
+                                    agnostic: bool = False, max_det: int = 10) -> list:
+    """The simulator node's perception, frame in and detections out (simulator.py:333-368):
+    ``detector_input`` -> the network -> ``simulator_detections_from_heads``.  frame: the uint8 [H,W,3] device frame;
+    net: a ``detector.DetectorNet``; plan: the frame's ``LetterboxPlan``.
+      fused=True   ``net(x)`` (one native call), then ``detections_from_heads``
+      fused=False  ``torch_net(x)`` -- ``detector_torch(net.spec, state_dict, device=frame.device)`` -- then the
+                   reference's lines in PyTorch"""
+    from . import perception
+    x = perception.detector_input(frame, plan)
+    if not fused and torch_net is None:
+        raise ValueError("simulator_detections_from_frame: fused=False needs torch_net= (harness.detector_torch)")
+    heads = net(x) if fused else torch_net(x)
+    return simulator_detections_from_heads(heads, net.geometry, plan, fused, conf_thres=conf_thres, iou_thres=iou_thres,
+                                           classes=classes, agnostic=agnostic, max_det=max_det)
+
+
+def closed_loop_run_with_detector(scene, net, steps: int, *, plan, ranging, **kw) -> dict:
+    """``closed_loop_run`` with the real network in its ``heads_for_frame`` slot: every frame goes from the render to
+    the brake decision on the device, the detector's convolutions included."""
+    from . import perception
+    return closed_loop_run(scene, lambda i, f: net(perception.detector_input(f["rgb8"], plan)), steps, plan=plan,
+                           ranging=ranging, geom=net.geometry, **kw)
+
+
 def _quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """quaternion_raw_multiply (general_utils.py:220-238)"""
     aw, ax, ay, az = torch.unbind(a, -1)

@@ -1592,6 +1592,67 @@ GRPG_API int grpg_densify_apply(const grpg_densify_model* models, int num_models
                                 const grpg_densify_output* outputs, grpg_alloc_fn table_alloc, void* table_user,
                                 void* hip_stream);
 
+/*
+ * The detector's network (csrc/detector.hip): the inference forward of the reference's YOLOv5
+ * (models/yolo.py:119-159 over models/common.py) between grpg_letterbox_* and grpg_detect_detections, as a list of
+ * launches the caller builds once per input shape.  Additive; GRPG_ABI_VERSION stays 7.  FP32, NCHW, no atomics:
+ * identical calls give identical bits.  Every tensor is addressed as (pointer to a contiguous [bs, ct, h, w] tensor,
+ * first channel c0): a layer reads or writes the channel slice [c0, c0 + c) of it and leaves the other channels alone.
+ *
+ * Weights: grpg_conv2d_pack_weights repacks a contiguous float32 [c_out, c_in, k, k] weight and a [c_out] bias (NULL:
+ * zeros) on the device into the order the kernel streams them -- [bias][K][c_out], c_out padded to 128 and
+ * K = c_in * k * k to 16 with zeros -- into `packed`, grpg_conv2d_packed_bytes(c_out, c_in, k) bytes on the device,
+ * 16-byte aligned (0: arguments out of range; a pure size query).  Once per model, one launch, no host wait.
+ *
+ * GRPG_DET_CONV: out = act(bias + conv(in)) [+ res], k in {1, 3}, stride in {1, 2}, padding k / 2, groups 1.  Every
+ * output element is the float32 fma chain acc = bias; acc = fma(w[k], x[k], acc) for k = (ci * k + ky) * k + kx
+ * ascending (the weight tensor's own order), whichever tile shape runs it.  act: GRPG_DET_ACT_SILU is
+ * x * (1 / (1 + expf(-x))) with a correctly rounded division.  res (or NULL): a [bs, res_ct, h_out, w_out] tensor whose
+ * slice is added AFTER the activation, as res + act(...) (Bottleneck's shortcut).  in_mode GRPG_DET_IN_FOCUS: the
+ * stored tensor is [bs, in_ct, h_in, w_in] with h_in, w_in even and the convolution sees Focus's [bs, c_in, h_in / 2,
+ * w_in / 2] (common.py:175): logical channel blk * (c_in / 4) + c is stored channel in_c0 + c at
+ * (2 y + (blk & 1), 2 x + (blk >> 1)).  up (or NULL): a [bs, up_ct, 2 h_out, 2 w_out] tensor whose slice receives every
+ * output value 2 x 2 replicated, nn.Upsample(scale_factor = 2, mode = 'nearest') as a second store.  h_in, w_in are the
+ * STORED input's; h_out, w_out must be what k, stride and the padding give.  tile: which kernel shape runs the layer
+ * (128 x 128 or 64 x 64 outputs per workgroup); the result does not depend on it.
+ * GRPG_DET_POOL: SPP's three max-pools (common.py:160-164: kernel 5, 9, 13, stride 1, -inf padding) of the slice
+ * [in_c0, in_c0 + c_in) into [out_c0, out_c0 + 3 c_in): the 5-pool's channels first, then the 9- and the 13-pool's;
+ * c_out = 3 c_in, h_out = h_in, w_out = w_in.  in and out may be one tensor if the slices are disjoint (SPP's cat).
+ * Bit-identical to nn.MaxPool2d.  packed, res, up, k, stride, act, in_mode and tile are ignored.
+ *
+ * grpg_detector_run checks EVERY layer before it enqueues anything (GRPG_ERR_INVALID_ARGUMENT: NULL or misaligned
+ * pointers, sizes < 1, a slice that leaves its tensor, an unknown kind, k, stride, activation, mode or tile, a layer
+ * that writes a tensor it reads), then GRPG_ERR_NO_DEVICE, then enqueues the n launches on hip_stream in order and
+ * returns without a host wait.  It cannot know the tensors' sizes: ct, h and w are the caller's word.
+ */
+#define GRPG_DET_CONV 0
+#define GRPG_DET_POOL 1
+#define GRPG_DET_ACT_NONE 0
+#define GRPG_DET_ACT_SILU 1
+#define GRPG_DET_IN_PLAIN 0
+#define GRPG_DET_IN_FOCUS 1
+#define GRPG_DET_TILE_128 0
+#define GRPG_DET_TILE_64 1
+typedef struct grpg_detector_layer {
+  int kind;                          /* GRPG_DET_CONV / GRPG_DET_POOL */
+  const float* in;                   /* [bs, in_ct, h_in, w_in] */
+  int in_c0, in_ct;
+  float* out;                        /* [bs, out_ct, h_out, w_out] */
+  int out_c0, out_ct;
+  const float* res;                  /* [bs, res_ct, h_out, w_out] or NULL */
+  int res_c0, res_ct;
+  float* up;                         /* [bs, up_ct, 2 h_out, 2 w_out] or NULL: the second, 2 x 2 replicated store */
+  int up_c0, up_ct;
+  const float* packed;               /* grpg_conv2d_pack_weights */
+  int bs, c_in, c_out;
+  int h_in, w_in, h_out, w_out;
+  int k, stride, act, in_mode, tile;
+} grpg_detector_layer;
+GRPG_API size_t grpg_conv2d_packed_bytes(int c_out, int c_in, int k);   /* pure size query */
+GRPG_API int grpg_conv2d_pack_weights(const float* weight, const float* bias, int c_out, int c_in, int k,
+                                      float* packed, void* hip_stream);
+GRPG_API int grpg_detector_run(const grpg_detector_layer* layers, int n, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
