@@ -6,13 +6,14 @@ iterations (CUDA events, after --warmup).  Also the config-5 training step (P = 
 op's forward, the fused L1 + SSIM mix, the aux terms, the backward of all), with no aux terms, with the PyTorch ones
 and with the fused ones.  Prints one JSON line."""
 import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+import benchkit
+from benchkit import median
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd import loss as fused_loss
 
@@ -40,11 +41,6 @@ def fused_aux(depth, acc, lidar, mask, sky, acc_obj, bound):
     return fused_loss.aux_loss(depth, acc, lidar_depth=lidar, mask=mask, sky_mask=sky, acc_obj=acc_obj,
                                obj_bound=bound, lambda_depth_lidar=LAMBDA_LIDAR, lambda_sky=LAMBDA_SKY,
                                lambda_reg=LAMBDA_REG)[0]
-
-
-def _median(x):
-    x = sorted(x)
-    return x[len(x) // 2]
 
 
 def _planes(H, W, coverage, dev):
@@ -78,7 +74,7 @@ def time_loss(fn, planes, with_obj, steps, warmup):
             fw.append(e[0].elapsed_time(e[1]))
             bw.append(e[1].elapsed_time(e[2]))
             both.append(e[0].elapsed_time(e[2]))
-    return {"forward_ms": _median(fw), "backward_ms": _median(bw), "fwd_bwd_ms": _median(both)}
+    return {"forward_ms": median(fw), "backward_ms": median(bw), "fwd_bwd_ms": median(both)}
 
 
 def time_train_step(aux_fn, P, steps, warmup, dev):
@@ -87,26 +83,23 @@ def time_train_step(aux_fn, P, steps, warmup, dev):
     H, W = hz.WAYMO_H, hz.WAYMO_W
     gt = torch.rand(3, H, W, device=dev)
     _, _, lidar, mask, sky, _, bound = _planes(H, W, 0.66, dev)
-    ts = []
-    for it in range(warmup + steps):
-        cam = hz.trajectory_camera(it % 200, device=dev)
+    frames = iter(range(warmup + steps))
+
+    def prepare():
         for t in leaves:
             if isinstance(t, torch.Tensor):
                 t.grad = None
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
+        return hz.trajectory_camera(next(frames) % 200, device=dev)
+
+    def step(cam):
         pkg = hz.render_kernel(leaves, cam, mode="train")
         loss = fused_loss.l1_ssim_loss(pkg["rgb"], gt, lambda_l1=1.0, lambda_dssim=0.2)[0]
         # acc stands in for the object render's acc_obj (the second render is not part of this measurement)
         if aux_fn is not None:
             loss = loss + aux_fn(pkg["depth"], pkg["acc"], lidar, mask, sky, pkg["acc"], bound)
         loss.backward()
-        e1.record()
-        torch.cuda.synchronize()
-        if it >= warmup:
-            ts.append(e0.elapsed_time(e1))
-    return _median(ts)
+        return pkg, loss    # held until after the synchronize, as before
+    return benchkit.medians(benchkit.timed(step, steps, warmup, prepare=prepare, wall=False))["device_us"] / 1e3
 
 
 def main():
@@ -116,6 +109,7 @@ def main():
     ap.add_argument("--gaussians", type=int, default=1_000_000)
     ap.add_argument("--no-train-step", action="store_true")
     args = ap.parse_args()
+    benchkit.require_gpu("bench_aux_loss")
     dev = torch.device("cuda:0")
     out = {"bench": "tools/bench_aux_loss.py: train.py lidar (0.1), sky (0.05), obj (0.1) terms, fwd + bwd",
            "steps": args.steps}
@@ -130,7 +124,7 @@ def main():
         for name, fn in (("none", None), ("torch", torch_aux), ("fused", fused_aux)):
             out["train_step_P%d_1920x1280_aux_%s_ms" % (args.gaussians, name)] = time_train_step(
                 fn, args.gaussians, max(args.steps // 3, 5), args.warmup, dev)
-    print(json.dumps(out))
+    benchkit.emit(out)
 
 
 if __name__ == "__main__":

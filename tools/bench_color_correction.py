@@ -13,9 +13,11 @@ Cases: "train"  forward + backward of sum(y * g) w.r.t. the cube map, rgb, acc a
 Per route and case: the wall time per call of a batch of --inner back-to-back calls between two synchronises (what a
 frame loop pays) and the device time per call between two events around the batch; median over --batches batches after
 --warmup batches, --reps times.  Prints one JSON line; --out FILE also writes it (profiles/color_correction_bench.json)."""
-import argparse, json, os, sys, time
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import benchkit
+from benchkit import column, median
 from gaussianrpg_amd import appearance, harness
 from gaussianrpg_amd.sky import SkyCubeMap
 from gaussianrpg_amd.trajectory import pack_hwc
@@ -30,26 +32,9 @@ ap.add_argument("--height", type=int, default=1280)
 ap.add_argument("--width", type=int, default=1920)
 args = ap.parse_args()
 
-assert torch.cuda.is_available(), "bench_color_correction.py measures on the GPU: there is nothing to time without one"
+benchkit.require_gpu("bench_color_correction")
 dev = torch.device("cuda:0")
 H, W = args.height, args.width
-
-
-def median(xs):
-    return sorted(xs)[len(xs) // 2]
-
-
-def batch(fn):
-    """(wall us per call, device us per call) of args.inner back-to-back calls"""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    e0.record()
-    for _ in range(args.inner):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e6 / args.inner, e0.elapsed_time(e1) * 1e3 / args.inner
-
 
 g = torch.Generator().manual_seed(H + W)
 sky = SkyCubeMap(1024, mode="evaluate").to(dev)
@@ -95,15 +80,10 @@ for name, make, s in (("train", train, sky), ("bytes", frame, sky), ("train_no_s
     routes = {"fused": make(True, s), "unfused": make(False, s)}
     reps = {k: {"wall": [], "device": []} for k in routes}
     for _ in range(args.reps):
-        seen = {k: [] for k in routes}
-        for b in range(args.warmup + args.batches):
-            for k, fn in routes.items():
-                r = batch(fn)
-                if b >= args.warmup:
-                    seen[k].append(r)
+        seen = benchkit.alternating(routes, args.batches, args.warmup, inner=args.inner)
         for k in routes:
-            reps[k]["wall"].append(median([r[0] for r in seen[k]]))
-            reps[k]["device"].append(median([r[1] for r in seen[k]]))
+            reps[k]["wall"].append(median(column(seen[k], "wall_us")))
+            reps[k]["device"].append(median(column(seen[k], "device_us")))
     cell = {}
     for k in routes:
         cell[k] = {"wall_us": median(reps[k]["wall"]), "wall_repetitions_us": reps[k]["wall"],
@@ -112,9 +92,4 @@ for name, make, s in (("train", train, sky), ("bytes", frame, sky), ("train_no_s
     cell["unfused_over_fused_device"] = cell["unfused"]["device_us"] / cell["fused"]["device_us"]
     result["cases"][name] = cell
 
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(json.dumps(result, indent=1) + "\n")
+benchkit.emit(result, args.out)

@@ -14,7 +14,6 @@ Also the host synchronisations torch sees in one call (sync debug mode) and the 
 No speed threshold belongs to this tool: the op is launch-sized, and the claim it measures is the launches and waits it
 removes.  Prints one JSON line; --out FILE also writes it (profiles/color_mlp_bench.json)."""
 import argparse
-import json
 import os
 import sys
 import types
@@ -23,7 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from bench_tracks import count_launches, count_syncs, median, timed
+import benchkit
+from benchkit import count_syncs, median, spread
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd.appearance import ColorCorrectionMLP
 
@@ -42,23 +42,16 @@ def poses(T, dev, seed=0):
 
 
 def count_own_launches(fn):
-    """count_launches, plus how many of the kernels are this op's own (color_mlp_*): the rest of a training call is
-    the loss arithmetic around it (products, sums and their autograd), the same on both routes."""
-    out = count_launches(fn)
-    if not isinstance(out, dict) or "kernels" not in out:
+    """benchkit.count_launches, plus how many of the kernels are this op's own (color_mlp_*): the rest of a training
+    call is the loss arithmetic around it (products, sums and their autograd), the same on both routes."""
+    def figure():
+        kernels = benchkit.device_kernels(fn)
+        out = benchkit.launch_counts(kernels)
+        if out is not None:
+            out["color_mlp_forward_kernels"] = sum("color_mlp_forward" in n for n, _ in kernels)
+            out["color_mlp_backward_kernels"] = sum("color_mlp_backward" in n for n, _ in kernels)
         return out
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        names = [e.name for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")]
-        out["color_mlp_forward_kernels"] = sum("color_mlp_forward" in n for n in names)
-        out["color_mlp_backward_kernels"] = sum("color_mlp_backward" in n for n in names)
-    except Exception as e:   # the figure is optional; the times are not
-        out["error"] = "%s: %s" % (type(e).__name__, e)
-    return out
+    return benchkit.optional(figure)
 
 
 def torch_route(cc, ego, ext, reg):
@@ -80,8 +73,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--points", type=int, default=300000)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_color_mlp: needs an MI355X (no ROCm device visible); nothing is measured without one")
+    benchkit.require_gpu("bench_color_mlp")
     dev = torch.device("cuda:0")
     result = {"bench": "tools/bench_color_mlp.py: pose -> colour-correction matrices of the use_mlp variant, fused HIP "
                        "against ordinary PyTorch; us per call (wall on the host with the device idle before and waited "
@@ -114,15 +106,10 @@ def main():
         routes = {"fused": lambda: run(True), "torch": lambda: run(False)}
         a, b = run(True), [t.clone() for t in run(False)]
         cell = {"T": T, "max_abs_difference_between_routes": max(float((x - y).abs().max()) for x, y in zip(a, b))}
-        reps = {k: [] for k in routes}
-        for r in range(args.reps):
-            for k, fn in routes.items():
-                reps[k].append(timed(fn, args.steps, args.warmup if r == 0 else 1))
+        reps = benchkit.windows(routes, args.reps, args.steps, args.warmup)
         for k, fn in routes.items():
-            wall, device = [x[0] for x in reps[k]], [x[1] for x in reps[k]]
-            cell[k] = {"wall_us": median(wall), "wall_min_us": min(wall), "wall_max_us": max(wall),
-                       "device_events_us": median(device), "wall_medians_us": wall,
-                       "host_syncs": count_syncs(fn), "launches": count_own_launches(fn)}
+            cell[k] = dict(spread(reps[k]["wall_us"], prefix="wall_"), device_events_us=median(reps[k]["device_us"]),
+                           host_syncs=count_syncs(fn), launches=count_own_launches(fn))
         cell["torch_over_fused_wall"] = cell["torch"]["wall_us"] / cell["fused"]["wall_us"]
         result["cases"][name] = cell
 
@@ -148,23 +135,12 @@ def main():
     a, b = frame(True).copy(), frame(False).copy()
     cell = {"points": args.points, "width": int(cam.image_width), "height": int(cam.image_height),
             "bytes_that_differ_between_routes": int((a != b).sum())}
-    reps = {k: [] for k in routes}
-    for r in range(args.reps):
-        for k, fn in routes.items():
-            reps[k].append(timed(fn, args.steps, args.warmup if r == 0 else 1))
+    reps = benchkit.windows(routes, args.reps, args.steps, args.warmup)
     for k, fn in routes.items():
-        wall = [x[0] for x in reps[k]]
-        cell[k] = {"wall_us": median(wall), "wall_min_us": min(wall), "wall_max_us": max(wall), "wall_medians_us": wall,
-                   "host_syncs": count_syncs(fn)}
+        cell[k] = dict(spread(reps[k]["wall_us"], prefix="wall_"), host_syncs=count_syncs(fn))
     cell["torch_over_fused_wall"] = cell["torch"]["wall_us"] / cell["fused"]["wall_us"]
     result["cases"]["evaluation_frame"] = cell
-
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(json.dumps(result, indent=1) + "\n")
+    benchkit.emit(result, args.out)
 
 
 if __name__ == "__main__":

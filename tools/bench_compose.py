@@ -3,13 +3,15 @@
 (b) gaussianrpg_amd.composed.ComposedRasterizer (fused into preprocess).
 Scene: scene-002-like, 1.9 M background Gaussians + 10 actors of 10 k.
 Prints one JSON line (synchronize-bracketed medians over the 200-pose drive)."""
-import json, math, os, sys, time
+import math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import benchkit
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd.composed import ActorPose, ComposedRasterizer, ModelParams, idft_weights
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 
+benchkit.require_gpu("bench_compose")
 dev = torch.device("cuda:0")
 g = torch.Generator().manual_seed(2)
 NB, NA, PA, F = 1_900_000, 10, 10_000, 5
@@ -119,7 +121,7 @@ def time_train(fn, n=24):
         fn(k)
         torch.cuda.synchronize(); ts.append((time.time() - t0) * 1e3)
     ts = sorted(ts[2:])
-    return {"iterations": len(ts), "median_ms": ts[len(ts) // 2], "p95_ms": ts[int(0.95 * len(ts))]}
+    return {"iterations": len(ts), "median_ms": benchkit.median(ts), "p95_ms": ts[int(0.95 * len(ts))]}
 
 
 ta = time_train(train_ref)
@@ -165,11 +167,11 @@ def render_all_fused(f):
 
 ra = hz.time_frames(render_all_ref, 40)
 rb = hz.time_frames(render_all_fused, 40)
-print(json.dumps({"what": "scene-graph composition + forward op, 1.9 M background + 10 actors x 10 k, 1920x1280",
-                  "torch_composition_then_op_ms": a, "fused_composed_op_ms": b,
-                  "render_all": {"what": "the evaluation path's three renders per frame (all / background / objects), "
-                                         "each with its own composition, vs one composed layered forward",
-                                 "torch_composition_and_three_ops_ms": ra, "fused_composed_layers_ms": rb},
-                  "train_step": {"what": "forward + backward down to the raw parameters (loss = mean colour + "
-                                         "0.1 mean depth + mean alpha), synchronize-bracketed wall time",
-                                 "torch_composition_autograd_plus_op_ms": ta, "fused_composed_op_ms": tb}}))
+benchkit.emit({"what": "scene-graph composition + forward op, 1.9 M background + 10 actors x 10 k, 1920x1280",
+               "torch_composition_then_op_ms": a, "fused_composed_op_ms": b,
+               "render_all": {"what": "the evaluation path's three renders per frame (all / background / objects), "
+                                      "each with its own composition, vs one composed layered forward",
+                              "torch_composition_and_three_ops_ms": ra, "fused_composed_layers_ms": rb},
+               "train_step": {"what": "forward + backward down to the raw parameters (loss = mean colour + "
+                                      "0.1 mean depth + mean alpha), synchronize-bracketed wall time",
+                              "torch_composition_autograd_plus_op_ms": ta, "fused_composed_op_ms": tb}})

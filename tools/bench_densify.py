@@ -12,15 +12,15 @@ Host synchronisations are counted with torch's sync debug mode in one extra call
 (the plan's, inside the library, invisible to torch) is added by hand.  Kernel times come from a run of their own under
 rocprofv3 --kernel-trace --stats with --only fused.  Prints one JSON line."""
 import argparse
-import json
 import math
 import os
 import sys
-import warnings
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+import benchkit
+from benchkit import count_syncs
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd.optim import DensifyModel, DensifyRule, FusedAdam, densify_and_prune
 
@@ -28,11 +28,6 @@ TAILS = ((3,), (1, 3), (3, 3), (1,), (3,), (4,), (0,))          # xyz f_dc f_res
 NAMES = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "semantic")
 FLOATS_PER_GAUSSIAN = 23
 BYTES_PER_ROW = 3 * 4 * FLOATS_PER_GAUSSIAN                      # parameter, exp_avg, exp_avg_sq
-
-
-def _median(x):
-    x = sorted(x)
-    return x[len(x) // 2]
 
 
 def make_inputs(P, k, dev, seed):
@@ -83,34 +78,8 @@ def run_reference(inputs):
 
 
 def timed(fn, prepare, steps, warmup):
-    """Median over `steps` calls of fn(prepare()); prepare() (the optimizers of one call) is not timed."""
-    ts = []
-    for it in range(warmup + steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        arg = prepare()
-        torch.cuda.synchronize()
-        e0.record()
-        out = fn(arg)
-        e1.record()
-        torch.cuda.synchronize()
-        del out
-        if it >= warmup:
-            ts.append(e0.elapsed_time(e1))
-    return _median(ts)
-
-
-def count_syncs(fn):
-    """Host synchronisations torch sees in one call (sync debug mode warns at each)."""
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    torch.cuda.synchronize()
-    return sum("synchroniz" in str(x.message).lower() for x in w)
+    """Median ms over `steps` calls of fn(prepare()); prepare() (the optimizers of one call) is not timed."""
+    return benchkit.medians(benchkit.timed(fn, steps, warmup, prepare=prepare, wall=False))["device_us"] / 1e3
 
 
 def bench_size(tag, sizes, args, dev, out):
@@ -139,11 +108,10 @@ def bench_size(tag, sizes, args, dev, out):
         fused.append(timed(densify_and_prune, lambda: fused_models(inputs), args.steps, args.warmup if r == 0 else 1))
         if args.only != "fused":
             refs.append(timed(run_reference, lambda: inputs, args.steps, args.warmup if r == 0 else 1))
-    pack = lambda m: {"ms": _median(m), "min_ms": min(m), "max_ms": max(m), "medians_ms": m}   # noqa: E731
-    o["fused"] = pack(fused)
+    o["fused"] = benchkit.spread(fused, unit="ms")
     o["fused"]["host_syncs"] = count_syncs(lambda: run_fused(inputs)) + 1        # + the plan's own stream wait
     if args.only != "fused":
-        o["reference_sequence"] = pack(refs)
+        o["reference_sequence"] = benchkit.spread(refs, unit="ms")
         o["reference_sequence"]["host_syncs"] = count_syncs(lambda: run_reference(inputs))
         o["speedup"] = o["reference_sequence"]["ms"] / o["fused"]["ms"]
 
@@ -156,8 +124,7 @@ def main():
     ap.add_argument("--only", choices=("all", "fused"), default="all")
     ap.add_argument("--sizes", choices=("all", "a", "b"), default="all")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_densify: needs an MI355X (no ROCm device visible); nothing is measured without one")
+    benchkit.require_gpu("bench_densify")
     dev = torch.device("cuda:0")
     out = {"bench": "tools/bench_densify.py: densify_and_prune, the reference's PyTorch sequence against fused HIP",
            "steps": args.steps, "reps": args.reps}
@@ -165,7 +132,7 @@ def main():
         bench_size("config5_P1M", [1_000_000], args, dev, out)
     if args.sizes in ("all", "b"):
         bench_size("street_1p9M_10x10k", [1_900_000] + [10_000] * 10, args, dev, out)
-    print(json.dumps(out))
+    benchkit.emit(out)
 
 
 if __name__ == "__main__":

@@ -21,15 +21,15 @@ the median over its dispatches, the first KERNEL_WARMUP of them left out.
 Prints one JSON line; --out FILE also writes it (profiles/detect_bench.json)."""
 import argparse
 import csv
-import json
 import os
 import sys
-import warnings
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+import benchkit
+from benchkit import count_syncs, median, spread
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd.perception import DetectGeometry, LetterboxPlan, decode_heads, detections, detections_from_heads
 
@@ -44,10 +44,6 @@ CASES = {
 }
 KERNELS = ("detect_decode_kernel", "detect_candidates_kernel", "nms_candidates_kernel", "nms_walk_kernel",
            "radix_hist_kernel", "radix_digit_scan_kernel", "radix_scatter_kernel")
-
-
-def median(xs):
-    return sorted(xs)[len(xs) // 2]
 
 
 def make_heads(size, n_cand, n_obj, seed):
@@ -81,35 +77,6 @@ def make_heads(size, n_cand, n_obj, seed):
     return heads
 
 
-def timed(fn, steps, warmup):
-    ts = []
-    for it in range(warmup + steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        out = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        del out
-        if it >= warmup:
-            ts.append(e0.elapsed_time(e1) * 1e3)
-    return median(ts)
-
-
-def count_syncs(fn):
-    """Host synchronisations torch sees in one call (sync debug mode warns at each)."""
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    torch.cuda.synchronize()
-    return sum("synchroniz" in str(x.message).lower() for x in w)
-
-
 KERNEL_WARMUP = 5
 
 
@@ -140,8 +107,7 @@ def main():
     ap.add_argument("--case", choices=list(CASES), action="append")
     ap.add_argument("--kernel-trace", action="append", default=[], metavar="CASE=FILE")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_detect: needs an MI355X (no ROCm device visible); nothing is measured without one")
+    benchkit.require_gpu("bench_detect")
     dev = torch.device("cuda:0")
     stats = dict(s.split("=", 1) for s in args.kernel_trace)
     geom = DetectGeometry(np.asarray(ANCHORS, np.float32), STRIDES, NC)
@@ -193,13 +159,9 @@ def main():
         cell["b_floor_us_at_8TBs"] = cell["b_bytes"] / 8e12 * 1e6
         cell["c_floor_us_at_8TBs"] = cell["c_bytes_upper"] / 8e12 * 1e6
         both = dict(routes, **stages)
-        reps = {k: [] for k in both}
-        for r in range(args.reps):
-            for k, fn in both.items():
-                reps[k].append(timed(fn, args.steps, args.warmup if r == 0 else 1))
+        reps = benchkit.windows(both, args.reps, args.steps, args.warmup, wall=False)
         for k, fn in both.items():
-            cell[k] = {"us": median(reps[k]), "min_us": min(reps[k]), "max_us": max(reps[k]), "medians_us": reps[k],
-                       "host_syncs": count_syncs(fn)}
+            cell[k] = dict(spread(reps[k]["device_us"]), host_syncs=count_syncs(fn))
         cell["b_over_c"] = cell["b_decode_heads"]["us"] / cell["c_from_heads"]["us"]
         if args.only == "all":
             cell["a_over_c"] = cell["a_torch_decode"]["us"] / cell["c_from_heads"]["us"]
@@ -210,12 +172,7 @@ def main():
             if "detect_decode_kernel" in kt:
                 cell["decode_kernel_GBps"] = 2 * head_bytes / kt["detect_decode_kernel"]["median_us"] / 1e3
         result["cases"][name] = cell
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(json.dumps(result, indent=1) + "\n")
+    benchkit.emit(result, args.out)
 
 
 if __name__ == "__main__":

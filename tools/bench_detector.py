@@ -16,18 +16,19 @@ alternating call by call: that tool's fixed synthetic heads (no network: the par
 (a) and route (b) behind perception.detector_input.  No speed threshold belongs to this tool.  Prints one JSON line; --out FILE also writes it
 (profiles/detector_bench.json)."""
 import argparse
-import json
+import functools
 import os
 import sys
 import time
-import warnings
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 
+import benchkit
 import detector_truth as T
+from benchkit import column, count_syncs, median
 from gaussianrpg_amd import detector as D
 from gaussianrpg_amd import harness as hz
 
@@ -35,40 +36,19 @@ PEAK_F32_MATRIX = 157.3e12
 SIZES = {"1600x1088": (1088, 1600), "1920x1280": (1280, 1920)}
 
 
-def median(xs):
-    return sorted(xs)[len(xs) // 2]
-
-
 def wall(fn, steps):
-    out = []
-    for _ in range(steps):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append((time.perf_counter() - t) * 1e3)
-    return out
+    """ms per call, wall on the host, of `steps` calls"""
+    return [us / 1e3 for us in column(benchkit.timed(fn, steps, 0, events=False), "wall_us")]
 
 
-def count_syncs(fn):
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    return sum("synchroniz" in str(x.message).lower() for x in w)
-
-
-def count_launches(fn):
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return sum(str(getattr(e, "device_type", "")).endswith("CUDA") for e in prof.events())
+def alternating_wall(routes, steps, reps):
+    """{route: [each repetition's median wall us]}: the routes alternate call by call"""
+    meds = {r: [] for r in routes}
+    for _ in range(reps):
+        seen = benchkit.alternating(routes, steps, 0, events=False)
+        for r in routes:
+            meds[r].append(median(column(seen[r], "wall_us")))
+    return meds
 
 
 def per_layer(net, P, reps):
@@ -98,8 +78,7 @@ def per_layer(net, P, reps):
 def closed_loop_frame(dev, routes_of, steps, reps):
     """us per braking frame for every entry of routes_of(plan) -> {name: heads_of(frame)}."""
     import numpy as np
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import bench_ego_loop as be
+    import benchkit_scenes as be
     from diff_gaussian_rasterization import GaussianRasterizationSettings
     from gaussianrpg_amd import closed_loop as cl
     from gaussianrpg_amd.perception import LetterboxPlan
@@ -123,14 +102,7 @@ def closed_loop_frame(dev, routes_of, steps, reps):
     for _ in range(4):
         for r in routes:
             call(r)
-    meds = {r: [] for r in routes}
-    for _ in range(reps):
-        samples = {r: [] for r in routes}
-        for _ in range(steps):
-            for r in routes:
-                samples[r] += wall(lambda: call(r), 1)
-        for r in routes:
-            meds[r].append(median(samples[r]) * 1e3)
+    meds = alternating_wall({r: functools.partial(call, r) for r in routes}, steps, reps)
     out = {"scene": "1.9 M + 10 x 10 k Gaussians, 1920 x 1280, detector input %s" % (list(plan.out_shape),)}
     for r in routes:
         out[r] = {"wall_us": median(meds[r]), "min": min(meds[r]), "max": max(meds[r]), "host_syncs": count_syncs(lambda: call(r))}
@@ -147,6 +119,7 @@ def main():
     ap.add_argument("--layer-reps", type=int, default=5)
     ap.add_argument("--size", action="append", choices=list(SIZES))
     args = ap.parse_args()
+    benchkit.require_gpu("bench_detector")
     dev = torch.device("cuda:0")
     spec = T.spec_of(False)
     sd = T.build_weights(spec, 12)
@@ -178,17 +151,10 @@ def main():
             ht, hn = tnet(x), net(x)
             row["routes_rel_l2"] = [T.rel_l2(a.cpu(), b.cpu()) for a, b in zip(hn, ht)]
         wall(routes["native"], 3)
-        meds = {r: [] for r in routes}
-        for _ in range(args.reps):
-            samples = {r: [] for r in routes}
-            for _ in range(args.steps):              # alternating call by call
-                for r, fn in routes.items():
-                    samples[r] += wall(fn, 1)
-            for r in routes:
-                meds[r].append(median(samples[r]))
+        meds = {r: [us / 1e3 for us in v] for r, v in alternating_wall(routes, args.steps, args.reps).items()}
         for r, fn in routes.items():
-            row[r] = {"wall_ms": median(meds[r]), "min": min(meds[r]), "max": max(meds[r]), "launches": count_launches(fn),
-                      "host_syncs": count_syncs(fn)}
+            row[r] = {"wall_ms": median(meds[r]), "min": min(meds[r]), "max": max(meds[r]),
+                      "launches": len(benchkit.device_kernels(fn)), "host_syncs": count_syncs(fn)}
         P = net.plan(1, h, w, dev)
         layers = per_layer(net, P, args.layer_reps)
         flops = sum(l.get("flops", 0) for l in layers)
@@ -211,10 +177,7 @@ def main():
             return r, net.geometry
         res["closed_loop_frame"] = closed_loop_frame(dev, routes_of, args.steps, args.reps)
         print("closed loop", {k: v["wall_us"] for k, v in res["closed_loop_frame"].items() if isinstance(v, dict)}, file=sys.stderr)
-    print(json.dumps(res))
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(json.dumps(res, indent=1) + "\n")
+    benchkit.emit(res, args.out)
 
 
 if __name__ == "__main__":

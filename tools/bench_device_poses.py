@@ -13,92 +13,18 @@ one call (sync debug mode).  The two routes' frames are compared byte for byte f
 No speed threshold belongs to this tool.  Prints one JSON line; --out FILE also writes it
 (profiles/device_poses_bench.json)."""
 import argparse
-import json
 import os
 import sys
-import time
-import warnings
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
+import benchkit
+from benchkit import column, count_syncs, median, spread
+from benchkit_scenes import BASE, LENGTH, make_actors, make_models
 from gaussianrpg_amd import harness as hz
-from gaussianrpg_amd.composed import ComposedRasterizer, ModelParams
+from gaussianrpg_amd.composed import ComposedRasterizer
 from gaussianrpg_amd.rasterizer import GaussianRasterizationSettings
-from gaussianrpg_amd.tracks import TrackTable, TrackedActorPoses
-
-LENGTH = 198
-BASE = 1.5e9
-FOURIER = 5
-
-
-def median(xs):
-    return sorted(xs)[len(xs) // 2]
-
-
-def make_actors(A, dev, seed=0):
-    """A cars on the road ahead, ten to a row, driving slowly forward: tracks of LENGTH entries, one column per actor"""
-    rng = np.random.RandomState(seed)
-    F = LENGTH
-    tr = np.zeros((F, A, 8), np.float32)
-    for a in range(A):
-        yaw = 0.05 * (a % 10) + 0.002 * np.arange(F) + rng.normal(0, 0.002, F)
-        tr[:, a, 0] = a
-        tr[:, a, 1:4] = np.stack([np.full(F, -12.0 + 2.5 * (a % 10)) + 0.6 * (a // 10), np.full(F, 0.8),
-                                  10.0 + 8.0 * (a % 10) + 1.5 * (a // 10) + 0.05 * np.arange(F)], 1)
-        tr[:, a, 4], tr[:, a, 6] = np.cos(yaw / 2), np.sin(yaw / 2)
-    stamps = BASE + 0.1 * np.arange(F)
-    info = {a: dict(start_timestamp=stamps[0], end_timestamp=stamps[-1]) for a in range(A)}
-    m = TrackedActorPoses(TrackTable.from_tracklets(tr, stamps, info), device=dev)
-    with torch.no_grad():
-        m.opt_trans.normal_(0, 0.02)
-        m.opt_rots.normal_(0, 0.01)
-    return m
-
-
-def make_models(A, NB, PA, dev, grad, seed=2):
-    g = torch.Generator().manual_seed(seed)
-    sc = hz.street_scene(NB, seed=seed)
-    op = sc.opacity.clamp(1e-4, 1 - 1e-4)
-    raw = [(sc.means3D, torch.log(sc.scales), sc.rotations * 1.7, torch.log(op / (1 - op)), sc.shs[:, :1].contiguous(),
-            sc.shs[:, 1:].contiguous())]
-    for _ in range(A):
-        raw.append(((torch.rand(PA, 3, generator=g) - 0.5) * torch.tensor([4.5, 1.6, 2.0]),
-                    float(np.log(0.05)) + 0.5 * torch.randn(PA, 3, generator=g), torch.randn(PA, 4, generator=g),
-                    1.0 + 2.0 * torch.randn(PA, 1, generator=g), 0.5 * torch.randn(PA, FOURIER, 3, generator=g),
-                    0.15 * torch.randn(PA, 3, 3, generator=g)))
-    return [ModelParams(*(t.to(dev).requires_grad_(grad) for t in m)) for m in raw]
-
-
-def timed_alternating(routes, steps, warmup):
-    """{route: [wall us per call]}: the routes take turns, call by call"""
-    wall = {k: [] for k in routes}
-    for it in range(warmup + steps):
-        for k, fn in routes.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = fn()
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            del out
-            if it >= warmup:
-                wall[k].append((t1 - t0) * 1e6)
-    return wall
-
-
-def count_syncs(fn):
-    """Host synchronisations torch sees in one call (sync debug mode warns at each): the device-to-host copies"""
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    torch.cuda.synchronize()
-    return sum("synchroniz" in str(x.message).lower() for x in w)
 
 
 def main():
@@ -111,8 +37,7 @@ def main():
     ap.add_argument("--background", type=int, default=200_000)
     ap.add_argument("--actor-gaussians", type=int, default=2_000)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_device_poses: needs an MI355X (no ROCm device visible); nothing is measured without one")
+    benchkit.require_gpu("bench_device_poses")
     dev = torch.device("cuda:0")
     result = {"bench": "tools/bench_device_poses.py: tracked actor poses into a composed frame, PoseTable (device rows, "
                        "grpg_bind_device_poses) against PoseRows (the host hand-over); us per call, wall on the host with "
@@ -147,23 +72,16 @@ def main():
             cell = {"A": A, "frames_equal": bool(torch.equal(a, b))}
             meds = {k: [] for k in routes}
             for r in range(args.reps):
-                wall = timed_alternating(routes, args.steps, args.warmup if r == 0 else 1)
+                seen = benchkit.alternating(routes, args.steps, args.warmup if r == 0 else 1, events=False)
                 for k in routes:
-                    meds[k].append(median(wall[k]))
+                    meds[k].append(median(column(seen[k], "wall_us")))
             for k, fn in routes.items():
-                m = [round(x, 1) for x in meds[k]]
-                cell[k] = {"wall_us": median(m), "wall_min_us": min(m), "wall_max_us": max(m), "wall_medians_us": m,
-                           "host_syncs": count_syncs(fn)}
+                cell[k] = dict(spread([round(x, 1) for x in meds[k]], prefix="wall_"), host_syncs=count_syncs(fn))
             cell["rows_minus_table_us"] = round(cell["rows"]["wall_us"] - cell["table"]["wall_us"], 1)
             cell["rows_spread_us"] = round(cell["rows"]["wall_max_us"] - cell["rows"]["wall_min_us"], 1)
             result["cases"]["A%d_%s" % (A, mode)] = cell
             del models, params
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(json.dumps(result, indent=1) + "\n")
+    benchkit.emit(result, args.out)
 
 
 if __name__ == "__main__":

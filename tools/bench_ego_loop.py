@@ -17,7 +17,7 @@ written (count read back, then row by row over the DEVICE tensor: int() and torc
 each a wait), with the numpy ranging behind it.  No speed threshold belongs to this tool.  Prints one JSON line; --out
 FILE also writes it (profiles/ego_loop_bench.json)."""
 import argparse
-import json
+import functools
 import os
 import sys
 import time
@@ -26,34 +26,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from bench_device_poses import count_syncs, make_actors, make_models, median
-from bench_session import make_tape
+import benchkit
+from benchkit import column, count_syncs, median, spread
+from benchkit_scenes import ANCHORS, H, MAX_DET, NC, STRIDES, W, make_actors, make_models, make_tape, synthetic_heads
 from gaussianrpg_amd import closed_loop as cl
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd import rasterizer
 from gaussianrpg_amd.perception import DetectGeometry, LetterboxPlan, detections_from_heads
 from gaussianrpg_amd.rasterizer import GaussianRasterizationSettings
 from gaussianrpg_amd.session import FrameSession
-
-W, H = hz.WAYMO_W, hz.WAYMO_H
-NC, NA, MAX_DET = 80, 3, 10
-ANCHORS = [[[10, 13], [16, 30], [33, 23]], [[30, 61], [62, 45], [59, 119]], [[116, 90], [156, 198], [373, 326]]]
-STRIDES = [8.0, 16.0, 32.0]
-
-
-def synthetic_heads(dev, boxes, seed=11):
-    """three conv outputs [1, 255, H/s, W/s]: logits around -7 (nothing passes), and `boxes` cells of the coarsest
-    level with objectness and the class 'car' (2) at +3, below the horizon row"""
-    g = torch.Generator().manual_seed(seed)
-    heads = [torch.randn(1, NA * (5 + NC), H // int(s), W // int(s), generator=g) * 0.5 - 7.0 for s in STRIDES]
-    ny, nx = H // 32, W // 32
-    for i in range(boxes):
-        gy, gx, a = ny // 2 + 2 + (i % 5) * 3, 3 + (i * 7) % (nx - 6), i % NA
-        base = a * (5 + NC)
-        heads[2][0, base:base + 4, gy, gx] = torch.tensor([0.0, 0.0, -1.0 + 0.1 * i, -1.0])
-        heads[2][0, base + 4, gy, gx] = 3.0 - 0.1 * i
-        heads[2][0, base + 5 + 2, gy, gx] = 3.0
-    return [h.contiguous().to(dev) for h in heads]
 
 
 class FrontTimer:
@@ -95,15 +76,7 @@ def literal_tail(det, count, ranging):
 
 
 def timed(fn, steps, warmup=2):
-    us = []
-    for it in range(warmup + steps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if it >= warmup:
-            us.append((time.perf_counter() - t0) * 1e6)
-    return median(us)
+    return median(column(benchkit.timed(fn, steps, warmup, events=False), "wall_us"))
 
 
 def main():
@@ -118,8 +91,7 @@ def main():
     ap.add_argument("--tape", type=int, default=200)
     ap.add_argument("--boxes", type=int, default=10)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_ego_loop: needs an MI355X (no ROCm device visible); nothing is measured without one")
+    benchkit.require_gpu("bench_ego_loop")
     dev = torch.device("cuda:0")
     T = args.tape
     result = {"bench": "tools/bench_ego_loop.py: one braking frame of the closed loop (render from the moved camera, "
@@ -163,20 +135,11 @@ def main():
         assert loops["device"].state()["activated"] == 1.0 and loops["host"].activated
         cell = {"A": A}
         meds = {r: [] for r in loops}
+        routes = {r: functools.partial(call, r) for r in loops}
         for rep in range(args.reps):
-            wall = {r: [] for r in loops}
-            for it in range((args.warmup if rep == 0 else 1) + args.steps):
-                for r in loops:
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    out = call(r)
-                    torch.cuda.synchronize()
-                    t1 = time.perf_counter()
-                    del out
-                    if it >= (args.warmup if rep == 0 else 1):
-                        wall[r].append((t1 - t0) * 1e6)
+            seen = benchkit.alternating(routes, args.steps, args.warmup if rep == 0 else 1, events=False)
             for r in loops:
-                meds[r].append(round(median(wall[r]), 1))
+                meds[r].append(round(median(column(seen[r], "wall_us")), 1))
         front = {r: [] for r in loops}
         with FrontTimer() as ft:
             for it in range(args.steps):
@@ -187,9 +150,8 @@ def main():
                     front[r].append((ft.at - t0) * 1e6)
         torch.cuda.synchronize()
         for r in loops:
-            m = meds[r]
-            cell[r] = {"wall_us": median(m), "wall_min_us": min(m), "wall_max_us": max(m), "wall_medians_us": m,
-                       "front_us": round(median(front[r]), 1), "host_syncs": count_syncs(lambda: call(r))}
+            cell[r] = dict(spread(meds[r], prefix="wall_"), front_us=round(median(front[r]), 1),
+                           host_syncs=count_syncs(lambda: call(r)))
         cell["host_minus_device_us"] = round(cell["host"]["wall_us"] - cell["device"]["wall_us"], 1)
         cell["spread_us"] = round(max(cell[r]["wall_max_us"] - cell[r]["wall_min_us"] for r in loops), 1)
         result["cases"]["A%d" % A] = cell
@@ -223,12 +185,7 @@ def main():
                 "host_loop_host_syncs": count_syncs(host_tail),
                 "device_step_host_syncs": count_syncs(lambda: loop.step(det, count, -0.001))}
         del session, sc, loops, models, actors
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(json.dumps(result, indent=1) + "\n")
+    benchkit.emit(result, args.out)
 
 
 if __name__ == "__main__":

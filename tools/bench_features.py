@@ -6,9 +6,11 @@ Scene: config 5's P = 1 M background + 10 actors x 10 k, 1920x1280, S = 15; run 
 (F = 18).  Method of DESIGN.md section 13: two device synchronisations around each call, median of 30 calls, five
 repetitions.  Prints one JSON line; --out FILE also writes it (profiles/features_bench.json).
 --only fused|torch, --normals 0|1 and --reps N cut a run down to one cell (for a kernel trace of its own)."""
-import argparse, json, math, os, sys, time
+import argparse, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import benchkit
+from benchkit import median
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd.composed import ActorPose, ComposedRasterizer, ModelParams, idft_weights
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
@@ -21,6 +23,7 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--calls", type=int, default=30)
 args = ap.parse_args()
 
+benchkit.require_gpu("bench_features")
 dev = torch.device("cuda:0")
 g = torch.Generator().manual_seed(2)
 NB, NA, PA, FD, S = 1_000_000, 10, 10_000, 5, 15
@@ -124,11 +127,8 @@ def one_rep(fn, normals):
     ts = []
     for k in range(args.calls + 2):
         zero_grads()
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        fn(k, normals)
-        torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
-    ts = sorted(ts[2:])     # two warm-up calls
-    return ts[len(ts) // 2]
+        ts.append(benchkit.once(fn, k, normals, events=False)["wall_us"] / 1e3)
+    return median(ts[2:])     # two warm-up calls
 
 
 result = {"what": "train step with feature planes, 1 M background + 10 actors x 10 k, 1920x1280, S = 15; per cell the "
@@ -140,13 +140,8 @@ for normals in ((0, 1) if args.normals is None else (args.normals,)):
         if args.only and (args.only == "fused") != (fn is train_fused):
             continue
         reps = [one_rep(fn, normals) for _ in range(args.reps)]
-        cell[name] = {"median_ms": sorted(reps)[len(reps) // 2], "repetitions_ms": reps}
+        cell[name] = {"median_ms": median(reps), "repetitions_ms": reps}
     if len(cell) == 2:
         cell["ratio"] = cell["torch_composition_cat_classic_op"]["median_ms"] / cell["forward_features"]["median_ms"]
     result["cells"]["F=%d (normals %s)" % (3 * normals + S, "on" if normals else "off")] = cell
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(json.dumps(result, indent=1) + "\n")
+benchkit.emit(result, args.out)

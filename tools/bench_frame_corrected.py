@@ -18,9 +18,11 @@ costs nothing when this-against-parent lies inside it.
 Per route: the wall time per frame of a batch of --inner back-to-back frames between two synchronises; median over
 --batches batches after --warmup batches, --reps times with their min - max.  Prints one JSON line; --out FILE also
 writes it (profiles/frame_corrected_bench.json)."""
-import argparse, ctypes, json, os, sys, time
+import argparse, ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import benchkit
+from benchkit import column, median
 from gaussianrpg_amd import build, harness
 from gaussianrpg_amd.rasterizer import _C
 from gaussianrpg_amd.sky import SkyCubeMap, ray_matrix
@@ -42,36 +44,19 @@ ap.add_argument("--lib-order", default="this,parent,parent_b",
 ap.add_argument("--skip-corrected", action="store_true", help="only the uncorrected A/B")
 args = ap.parse_args()
 
-assert torch.cuda.is_available(), "bench_frame_corrected.py measures on the GPU: there is nothing to time without one"
+benchkit.require_gpu("bench_frame_corrected")
 dev = torch.device("cuda:0")
 H, W = args.height, args.width
 
 
-def median(xs):
-    return sorted(xs)[len(xs) // 2]
-
-
-def batch(fn):
-    """wall us per frame of args.inner back-to-back frames"""
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    for _ in range(args.inner):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e6 / args.inner
-
-
 def measure(routes):
-    """{route: {"us", "repetitions_us", "min_us", "max_us"}}; the routes alternate batch by batch"""
+    """{route: {"us", "repetitions_us", "min_us", "max_us"}}; the routes alternate batch by batch; wall us per frame of
+    args.inner back-to-back frames"""
     reps = {k: [] for k in routes}
     for _ in range(args.reps):
-        seen = {k: [] for k in routes}
-        for b in range(args.warmup + args.batches):
-            for k, fn in routes.items():
-                r = batch(fn)
-                if b >= args.warmup:
-                    seen[k].append(r)
+        seen = benchkit.alternating(routes, args.batches, args.warmup, inner=args.inner, events=False)
         for k in routes:
-            reps[k].append(median(seen[k]))
+            reps[k].append(median(column(seen[k], "wall_us")))
     return {k: {"us": median(v), "repetitions_us": v, "min_us": min(v), "max_us": max(v)} for k, v in reps.items()}
 
 
@@ -209,9 +194,4 @@ if args.parent and args.parent_b:
 else:
     result["uncorrected_device"] = result["uncorrected_host"] = "not measured: no --parent / --parent-b library given"
 
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(json.dumps(result, indent=1) + "\n")
+benchkit.emit(result, args.out)

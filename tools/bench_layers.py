@@ -1,12 +1,14 @@
 """Layered forward (grpg_forward_layers) on the bench frame with ten actor-sized clusters marked as objects:
 device time per frame and the stage breakdown, next to the plain forward of the same scene.  One JSON line."""
-import json, os, sys
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import benchkit
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd.rasterizer import _C
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 
+benchkit.require_gpu("bench_layers")
 dev = torch.device("cuda:0")
 sc = hz.street_scene(2_000_000, seed=2).to(dev)
 P = sc.means3D.shape[0]
@@ -20,15 +22,7 @@ kw = dict(shs=sc.shs, scales=sc.scales, rotations=sc.rotations)
 
 
 def timed(fn, n=20, warm=3):
-    ms = []
-    for i in range(n + warm):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record()
-        torch.cuda.synchronize()
-        if i >= warm:
-            ms.append(e0.elapsed_time(e1))
-    ms.sort()
-    return ms[len(ms) // 2]
+    return benchkit.medians(benchkit.timed(fn, n, warm, wall=False))["device_us"] / 1e3
 
 
 def stages(fn):
@@ -87,4 +81,4 @@ with torch.no_grad():
                 "actors_render_stage_ms": st2[6], "actors_stage_ms_layers": st2,
                 "actors_plain_render_stage_ms": st_pl[6], "actors_background_only_render_stage_ms": st_bg[6],
                 "actors_object_pixels_share": float((o2["alpha_object"] > 0).float().mean())})
-print(json.dumps(out))
+benchkit.emit(out)

@@ -11,10 +11,12 @@ Per route and case: the wall time per call of a batch of --inner back-to-back ca
 frame loop pays), median over --batches batches after --warmup batches, --reps times; for (a) and (b) also the device
 time per call between two events around the batch.
 Prints one JSON line; --out FILE also writes it (profiles/letterbox_bench.json)."""
-import argparse, json, os, sys, time
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
+import benchkit
+from benchkit import column, median
 from gaussianrpg_amd.perception import LetterboxPlan, detector_input
 
 ap = argparse.ArgumentParser()
@@ -25,30 +27,10 @@ ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--inner", type=int, default=200)
 args = ap.parse_args()
 
-assert torch.cuda.is_available(), "bench_letterbox.py measures on the GPU: there is nothing to time without one"
+benchkit.require_gpu("bench_letterbox")
 dev = torch.device("cuda:0")
 CASES = [("1066x1600 pad-only", 1066, 1600, None), ("1280x1920 pad-only", 1280, 1920, None),
          ("1280x1920 -> 640", 1280, 1920, 640)]
-
-
-def median(xs):
-    return sorted(xs)[len(xs) // 2]
-
-
-def batch(fn, device_time):
-    """(wall us per call, device us per call or None) of args.inner back-to-back calls"""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    if device_time:
-        e0.record()
-    for _ in range(args.inner):
-        fn()
-    if device_time:
-        e1.record()
-    torch.cuda.synchronize()
-    wall = (time.perf_counter() - t0) * 1e6 / args.inner
-    return wall, (e0.elapsed_time(e1) * 1e3 / args.inner if device_time else None)
-
 
 result = {"what": "frame -> detector input, float32 [1,3,h,w]; us per call: per cell the median over %d repetitions of "
                   "(median over %d batches of %d back-to-back calls between two synchronises, after %d warm-up "
@@ -85,13 +67,13 @@ for name, H, W, new_shape in CASES:
         seen = {k: [] for k in routes}
         for b in range(args.warmup + args.batches):
             for k, (fn, dt) in routes.items():
-                r = batch(fn, dt)
+                r = benchkit.batch(fn, args.inner, events=dt)
                 if b >= args.warmup:
                     seen[k].append(r)
         for k in routes:
-            reps[k]["wall"].append(median([r[0] for r in seen[k]]))
+            reps[k]["wall"].append(median(column(seen[k], "wall_us")))
             if routes[k][1]:
-                reps[k]["device"].append(median([r[1] for r in seen[k]]))
+                reps[k]["device"].append(median(column(seen[k], "device_us")))
     cell = {"plan": repr(plan), "bytes_read": 3 * H * W, "bytes_written": 12 * h * w}
     for k in routes:
         cell[k] = {"wall_us": median(reps[k]["wall"]), "wall_repetitions_us": reps[k]["wall"]}
@@ -102,9 +84,4 @@ for name, H, W, new_shape in CASES:
     cell["fused_device_GBps"] = (cell["bytes_read"] + cell["bytes_written"]) / cell["fused"]["device_us"] / 1e3
     result["cases"][name] = cell
 
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(json.dumps(result, indent=1) + "\n")
+benchkit.emit(result, args.out)

@@ -19,16 +19,15 @@ row) at 8 TB/s; its achieved bytes/s needs the kernel's own time, from a run of 
 whose *kernel_stats.csv goes in with --kernel-stats K=FILE (repeatable) on the run that writes the result.
 Prints one JSON line; --out FILE also writes it (profiles/nms_bench.json)."""
 import argparse
-import csv
-import json
 import os
 import sys
-import warnings
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+import benchkit
+from benchkit import count_syncs, spread
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd.perception import LetterboxPlan, detections
 
@@ -39,10 +38,8 @@ CASES = {
     "N107100_c3000": (107100, (1088, 1600), (1066, 1600), 3000, 100, 300),
     "N107100_c3000_maxdet10": (107100, (1088, 1600), (1066, 1600), 3000, 100, 10),
 }
-
-
-def median(xs):
-    return sorted(xs)[len(xs) // 2]
+KERNELS = ("nms_candidates_kernel", "nms_walk_kernel", "radix_hist_kernel", "radix_digit_scan_kernel",
+           "radix_scatter_kernel")
 
 
 def make_prediction(N, size, n_cand, n_obj, seed):
@@ -66,47 +63,6 @@ def make_prediction(N, size, n_cand, n_obj, seed):
     return p
 
 
-def timed(fn, steps, warmup):
-    ts = []
-    for it in range(warmup + steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        out = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        del out
-        if it >= warmup:
-            ts.append(e0.elapsed_time(e1) * 1e3)
-    return median(ts)
-
-
-def count_syncs(fn):
-    """Host synchronisations torch sees in one call (sync debug mode warns at each)."""
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    torch.cuda.synchronize()
-    return sum("synchroniz" in str(x.message).lower() for x in w)
-
-
-def kernel_times(path):
-    """{short kernel name: average us} of a rocprofv3 kernel_stats.csv"""
-    out = {}
-    with open(path) as f:
-        for r in csv.DictReader(f):
-            for k in ("nms_candidates_kernel", "nms_walk_kernel", "radix_hist_kernel", "radix_digit_scan_kernel",
-                      "radix_scatter_kernel"):
-                if k in r["Name"]:
-                    out[k] = {"avg_us": float(r["AverageNs"]) / 1e3, "calls": int(r["Calls"])}
-    return out
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -117,8 +73,7 @@ def main():
     ap.add_argument("--case", choices=list(CASES), action="append")
     ap.add_argument("--kernel-stats", action="append", default=[], metavar="CASE=FILE")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_nms: needs an MI355X (no ROCm device visible); nothing is measured without one")
+    benchkit.require_gpu("bench_nms")
     dev = torch.device("cuda:0")
     stats = dict(s.split("=", 1) for s in args.kernel_stats)
     result = {"bench": "tools/bench_nms.py: detector output -> detections in the frame, fused HIP against PyTorch on "
@@ -146,29 +101,20 @@ def main():
         cell["candidate_pass_bytes"] = 4 * N + 4 * NC * n_cand + 8 * N
         cell["candidate_pass_floor_us_at_8TBs"] = cell["candidate_pass_bytes"] / 8e12 * 1e6
         cell["prediction_bytes"] = 4 * N * (5 + NC)
-        reps = {k: [] for k in routes}
-        for r in range(args.reps):
-            for k, fn in routes.items():
-                reps[k].append(timed(fn, args.steps, args.warmup if r == 0 else 1))
+        reps = benchkit.windows(routes, args.reps, args.steps, args.warmup, wall=False)
         for k, fn in routes.items():
-            cell[k] = {"us": median(reps[k]), "min_us": min(reps[k]), "max_us": max(reps[k]), "medians_us": reps[k],
-                       "host_syncs": count_syncs(fn)}
+            cell[k] = dict(spread(reps[k]["device_us"]), host_syncs=count_syncs(fn))
         if args.only == "all":
             cell["torch_over_fused"] = cell["torch"]["us"] / cell["fused"]["us"]
         if name in stats:
-            kt = kernel_times(stats[name])
+            kt = benchkit.kernel_stats(stats[name], KERNELS)
             cell["kernels"] = kt
             if "nms_candidates_kernel" in kt:
                 us = kt["nms_candidates_kernel"]["avg_us"]
                 cell["candidate_pass_GBps"] = cell["candidate_pass_bytes"] / us / 1e3
                 cell["candidate_pass_share_of_8TBs_floor"] = cell["candidate_pass_floor_us_at_8TBs"] / us
         result["cases"][name] = cell
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(json.dumps(result, indent=1) + "\n")
+    benchkit.emit(result, args.out)
 
 
 if __name__ == "__main__":

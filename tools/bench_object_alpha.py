@@ -10,9 +10,11 @@ synchronize-bracketed steps after --warmup steps, --reps times.  The two new ker
 kernel as the difference of the library's preprocess-backward device time (grpg_get_backward_timing, which contains
 it) with and without the plane's gradient, same medians.
 Prints one JSON line; --out FILE also writes it (profiles/object_alpha_bench.json)."""
-import argparse, json, math, os, sys, time
+import argparse, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import benchkit
+from benchkit import median
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd.composed import ActorPose, ComposedRasterizer, ModelParams
 from gaussianrpg_amd.loss import obj_acc_loss
@@ -28,7 +30,7 @@ ap.add_argument("--width", type=int, default=hz.WAYMO_W)
 ap.add_argument("--height", type=int, default=hz.WAYMO_H)
 args = ap.parse_args()
 
-assert torch.cuda.is_available(), "bench_object_alpha.py measures on the GPU: there is nothing to time without one"
+benchkit.require_gpu("bench_object_alpha")
 dev = torch.device("cuda:0")
 NA, PA = 10, 10_000
 W, H = args.width, args.height
@@ -56,17 +58,6 @@ def poses_at(f):
         out.append(ActorPose([math.cos(a / 2), 0.0, math.sin(a / 2), 0.0],
                              [-12.0 + 2.5 * k, 0.8, 10.0 + 8.0 * k + 0.5 * f], 0.0))
     return out
-
-
-def median(xs):
-    return sorted(xs)[len(xs) // 2]
-
-
-def timed(fn):
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    r = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, r
 
 
 nframes = args.warmup + args.calls
@@ -130,8 +121,8 @@ for NB in args.backgrounds:
     for _ in range(args.reps):
         t2, t1, ks = [], [], []
         for f in range(nframes):
-            a, _ = timed(lambda: two_calls(f))
-            b, _ = timed(lambda: one_call(f))
+            a = benchkit.once(two_calls, f, events=False)["wall_us"] / 1e3
+            b = benchkit.once(one_call, f, events=False)["wall_us"] / 1e3
             _C.set_stage_timing(1)
             k = kernels(f)
             _C.set_stage_timing(0)
@@ -150,9 +141,4 @@ for NB in args.backgrounds:
     del models
     torch.cuda.empty_cache()
 
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(json.dumps(result, indent=1) + "\n")
+benchkit.emit(result, args.out)

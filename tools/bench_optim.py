@@ -11,24 +11,19 @@ at (a) config 5: one model, P = 1 M, SH degree 1 (23 floats per Gaussian) and (b
 of those medians and their spread (min, max).  --only fused runs nothing but the fused calls (for a kernel trace).
 Prints one JSON line."""
 import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+import benchkit
 from gaussianrpg_amd.optim import FusedAdam, densification_stats_update, fused_adam_step
 
 TAILS = ((3,), (1, 3), (3, 3), (1,), (3,), (4,), (0,))          # xyz f_dc f_rest opacity scaling rotation semantic
 NAMES = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "semantic")
 LRS = (1.6e-4, 0.0025, 0.0025 / 20.0, 0.05, 0.005, 0.001, 0.0)
 FLOATS_PER_GAUSSIAN = 23
-
-
-def _median(x):
-    x = sorted(x)
-    return x[len(x) // 2]
 
 
 def make_models(sizes, cls, dev, seed=0):
@@ -43,23 +38,9 @@ def make_models(sizes, cls, dev, seed=0):
     return models
 
 
-def timed(fn, steps, warmup):
-    ts = []
-    for it in range(warmup + steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if it >= warmup:
-            ts.append(e0.elapsed_time(e1))
-    return _median(ts)
-
-
 def repeated(fn, steps, warmup, reps):
-    meds = [timed(fn, steps, warmup if r == 0 else 2) for r in range(reps)]
-    return {"ms": _median(meds), "min_ms": min(meds), "max_ms": max(meds), "medians_ms": meds}
+    meds = benchkit.windows({"fn": fn}, reps, steps, warmup, again=2, wall=False)["fn"]["device_us"]
+    return benchkit.spread([us / 1e3 for us in meds], unit="ms")
 
 
 def torch_densify(viewspace_grad, radii, ranges, models):
@@ -124,12 +105,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", choices=("all", "fused"), default="all")
     args = ap.parse_args()
+    benchkit.require_gpu("bench_optim")
     dev = torch.device("cuda:0")
     out = {"bench": "tools/bench_optim.py: optimizer.step() and densification statistics, PyTorch against fused HIP",
            "steps": args.steps, "reps": args.reps}
     bench_size("config5_P1M", [1_000_000], args, dev, out)
     bench_size("street_1p9M_10x10k", [1_900_000] + [10_000] * 10, args, dev, out)
-    print(json.dumps(out))
+    benchkit.emit(out)
 
 
 if __name__ == "__main__":

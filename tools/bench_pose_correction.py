@@ -16,9 +16,11 @@ median of the repetitions and all of them (their spread).  For the composed rout
 kernels of one call with their times (torch.profiler; null where it is not available), so that a difference between
 the corrected and the uncorrected step can be laid at a kernel's door.  No speed threshold belongs to this tool.
 Prints one JSON line; --out FILE also writes it (profiles/pose_correction_bench.json)."""
-import argparse, json, os, sys, time, types
+import argparse, os, sys, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import benchkit
+from benchkit import column, median
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd.composed import ModelParams
 from gaussianrpg_amd.pose_correction import PoseCorrection, pose_correct
@@ -40,39 +42,18 @@ ap.add_argument("--only", choices=["op", "step", "frame"], action="append")
 args = ap.parse_args()
 only = args.only or ["op", "step", "frame"]
 
-assert torch.cuda.is_available(), "bench_pose_correction.py measures on the GPU: there is nothing to time without one"
+benchkit.require_gpu("bench_pose_correction")
 dev = torch.device("cuda:0")
 PEAK_BYTES_PER_S = 8e12
-
-
-def median(xs):
-    return sorted(xs)[len(xs) // 2]
-
-
-def batch(fn, inner):
-    """(wall us per call, device us per call) of `inner` back-to-back calls"""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    e0.record()
-    for _ in range(inner):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e6 / inner, e0.elapsed_time(e1) * 1e3 / inner
 
 
 def alternate(routes, inner):
     reps = {k: {"wall": [], "device": []} for k in routes}
     for _ in range(args.reps):
-        seen = {k: [] for k in routes}
-        for b in range(args.warmup + args.batches):
-            for k, fn in routes.items():
-                r = batch(fn, inner)
-                if b >= args.warmup:
-                    seen[k].append(r)
+        seen = benchkit.alternating(routes, args.batches, args.warmup, inner=inner)
         for k in routes:
-            reps[k]["wall"].append(median([r[0] for r in seen[k]]))
-            reps[k]["device"].append(median([r[1] for r in seen[k]]))
+            reps[k]["wall"].append(median(column(seen[k], "wall_us")))
+            reps[k]["device"].append(median(column(seen[k], "device_us")))
     return {k: {"wall_us": median(reps[k]["wall"]), "wall_repetitions_us": reps[k]["wall"],
                 "device_us": median(reps[k]["device"]), "device_repetitions_us": reps[k]["device"],
                 "device_spread_us": max(reps[k]["device"]) - min(reps[k]["device"])} for k in routes}
@@ -80,22 +61,15 @@ def alternate(routes, inner):
 
 def kernels(fn):
     """[(kernel, calls, total us)] of one call, longest first, or an error record where the profiler cannot tell."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
+    def figure():
         fn()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
         agg = {}
-        for e in prof.events():
-            if str(getattr(e, "device_type", "")).endswith("CUDA"):
-                c = agg.setdefault(e.name[:96], [0, 0.0])
-                c[0] += 1
-                c[1] += float(getattr(e, "device_time", 0.0) or getattr(e, "cuda_time", 0.0) or 0.0)
+        for name, us in benchkit.device_kernels(fn):
+            c = agg.setdefault(name[:96], [0, 0.0])
+            c[0] += 1
+            c[1] += us
         return [dict(kernel=k, calls=v[0], us=v[1]) for k, v in sorted(agg.items(), key=lambda kv: -kv[1][1])][:24] or None
-    except Exception as e:   # the figure is optional; the times are not
-        return {"error": "%s: %s" % (type(e).__name__, e)}
+    return benchkit.optional(figure)
 
 
 result = {"what": "pose correction of the background; us per call: per cell the median over %d repetitions of (median "
@@ -203,9 +177,4 @@ if "step" in only or "frame" in only:
         result[name] = cell
         result[name]["scene"] = "%d background + %d x %d, %dx%d" % (NB, NA, PA, int(cam.image_width), int(cam.image_height))
 
-line = json.dumps(result)
-print(line)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(json.dumps(result, indent=1) + "\n")
+benchkit.emit(result, args.out)

@@ -10,13 +10,14 @@ algorithm needs per call and the achieved GB/s over the e
 the launches and the tiny reduce kernel, so the kernel-only rate is higher.  Prints one JSON line; --out writes it
 to a file as well."""
 import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+import benchkit
+from benchkit import median
 from gaussianrpg_amd import loss as fused_loss
 
 HBM_PEAK_GBS = 8000.0
@@ -69,11 +70,6 @@ def torch_psnr(img1, img2, mask):
 
 # ---- timing ----
 
-def _median(x):
-    x = sorted(x)
-    return x[len(x) // 2]
-
-
 class Timed:
     """One path of one row: fn(*leaves) -> loss; the leaves receive gradients (none: forward only)."""
 
@@ -100,9 +96,9 @@ class Timed:
                 self.both.append(e[0].elapsed_time(e[2]))
 
     def result(self):
-        r = {"forward_ms": _median(self.fw)}
+        r = {"forward_ms": median(self.fw)}
         if self.leaves:
-            r["backward_ms"], r["fwd_bwd_ms"] = _median(self.bw), _median(self.both)
+            r["backward_ms"], r["fwd_bwd_ms"] = median(self.bw), median(self.both)
         return r
 
 
@@ -142,8 +138,7 @@ def main():
     ap.add_argument("--object-points", type=int, default=10_000)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/bench_reg_losses.py needs a ROCm device: nothing is measured without one")
+    benchkit.require_gpu("bench_reg_losses")
     dev = torch.device("cuda:0")
     H, W = args.height, args.width
     n = H * W
@@ -193,12 +188,7 @@ def main():
                                                                  lambda_scale_flatten=0.1, lambda_opacity_sparse=0.1)[0],
                       [_leaf(scaling)] + [_leaf(o) for o in opacities]), args,
                 12 * sizes[0] + 4 * P + 4 * nvis, 24 * sizes[0] + 8 * P + 4 * nvis)
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    benchkit.emit(out, args.out)
 
 
 if __name__ == "__main__":

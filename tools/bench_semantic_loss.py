@@ -9,13 +9,14 @@ GB/s over the event time and its share of the 8 TB/s floor; "backward_bytes_move
 what the backward really moves: it reads sem and the logsumexp only at valid pixels.  The event times include
 the launches and, forward, the tiny reduce kernel, so the kernel-only share is a little higher.  Prints one JSON line."""
 import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+import benchkit
+from benchkit import median
 from gaussianrpg_amd import loss as fused_loss
 
 HBM_PEAK_GBS = 8000.0
@@ -34,11 +35,6 @@ def torch_semantic(semantic, gt, mode):
 
 def fused_semantic(semantic, gt, mode):
     return fused_loss.semantic_loss(semantic, gt, mode=mode)
-
-
-def _median(x):
-    x = sorted(x)
-    return x[len(x) // 2]
 
 
 def _inputs(S, H, W, mode, dev):
@@ -66,7 +62,7 @@ def time_loss(fn, sem, gt, mode, steps, warmup):
             fw.append(e[0].elapsed_time(e[1]))
             bw.append(e[1].elapsed_time(e[2]))
             both.append(e[0].elapsed_time(e[2]))
-    return {"forward_ms": _median(fw), "backward_ms": _median(bw), "fwd_bwd_ms": _median(both)}
+    return {"forward_ms": median(fw), "backward_ms": median(bw), "fwd_bwd_ms": median(both)}
 
 
 def fused_bytes(S, n, n_valid, target_bytes=8):
@@ -86,6 +82,7 @@ def main():
     ap.add_argument("--height", type=int, default=1280)
     ap.add_argument("--channels", type=int, nargs="+", default=[3, 15, 19, 32])
     args = ap.parse_args()
+    benchkit.require_gpu("bench_semantic_loss")
     dev = torch.device("cuda:0")
     H, W = args.height, args.width
     out = {"bench": "tools/bench_semantic_loss.py: train.py semantic cross-entropy, fwd + bwd, %dx%d, %d %% ignored"
@@ -107,7 +104,7 @@ def main():
                 out["S%d_%s_%s" % (S, mode, name)] = r
             t, f = out["S%d_%s_torch" % (S, mode)], out["S%d_%s_fused" % (S, mode)]
             out["S%d_%s_speedup" % (S, mode)] = t["fwd_bwd_ms"] / f["fwd_bwd_ms"]
-    print(json.dumps(out))
+    benchkit.emit(out)
 
 
 if __name__ == "__main__":

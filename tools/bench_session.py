@@ -17,7 +17,6 @@ launch lies inside that span); the host synchronisations torch sees in one call;
 The two routes' frames are compared byte for byte first.  No speed threshold belongs to this tool.  Prints one JSON
 line; --out FILE also writes it (profiles/session_bench.json)."""
 import argparse
-import json
 import math
 import os
 import sys
@@ -27,27 +26,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from bench_device_poses import BASE, LENGTH, count_syncs, make_actors, make_models, median
+import benchkit
+from benchkit import count_syncs, median, spread
+from benchkit_scenes import H, W, make_actors, make_models, make_tape
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd import rasterizer
 from gaussianrpg_amd.rasterizer import GaussianRasterizationSettings
 from gaussianrpg_amd.session import FrameSession
-
-W, H = hz.WAYMO_W, hz.WAYMO_H
-
-
-def make_tape(T):
-    """T entries spread over the tracks' life, a camera creeping forward with a slight yaw, the ego pose along"""
-    tape = []
-    for k in range(T):
-        yaw = 0.01 * math.sin(0.1 * k)
-        R = np.array([[math.cos(yaw), 0.0, math.sin(yaw)], [0.0, 1.0, 0.0], [-math.sin(yaw), 0.0, math.cos(yaw)]])
-        C = np.array([0.0, 0.0, 0.02 * k])
-        ego = np.eye(4)
-        ego[:3, 3] = [0.3, -0.2, 0.5 + 0.02 * k]
-        tape.append(dict(id=k, timestamp=BASE + 0.1 * (0.3 + k * (LENGTH - 2.0) / T), rotation_matrix=R.tolist(),
-                         position=(-R.transpose() @ C).tolist(), ego_pose=ego.tolist()))
-    return tape
 
 
 def moved(k):
@@ -87,14 +72,9 @@ def timed_alternating(routes, steps, warmup, T):
     for it in range(warmup + steps):
         k = (7 * it) % T
         for r, fn in routes.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = fn(k)
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            del out
+            s = benchkit.once(fn, k, events=False)
             if it >= warmup:
-                wall[r].append((t1 - t0) * 1e6)
+                wall[r].append(s["wall_us"])
     return wall
 
 
@@ -124,8 +104,7 @@ def main():
     ap.add_argument("--actor-gaussians", type=int, default=10_000)
     ap.add_argument("--tape", type=int, default=200)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_session: needs an MI355X (no ROCm device visible); nothing is measured without one")
+    benchkit.require_gpu("bench_session")
     dev = torch.device("cuda:0")
     T = args.tape
     result = {"bench": "tools/bench_session.py: the closed loop's frame, FrameSession (bound once: baked segment tables, "
@@ -173,20 +152,14 @@ def main():
                     meds[r].append(median(wall[r]))
             front = front_times(routes, args.steps, T)
             for r, fn in routes.items():
-                m = [round(x, 1) for x in meds[r]]
-                cell[r] = {"wall_us": median(m), "wall_min_us": min(m), "wall_max_us": max(m), "wall_medians_us": m,
-                           "front_us": front[r], "host_syncs": count_syncs(lambda: fn(T // 2))}
+                cell[r] = dict(spread([round(x, 1) for x in meds[r]], prefix="wall_"), front_us=front[r],
+                               host_syncs=count_syncs(lambda: fn(T // 2)))
             cell["unbound_minus_bound_us"] = round(cell["unbound"]["wall_us"] - cell["bound"]["wall_us"], 1)
             cell["spread_us"] = round(max(cell[r]["wall_max_us"] - cell[r]["wall_min_us"] for r in routes), 1)
             result["cases"]["A%d_%s" % (A, case)] = cell
             del session, sc
         del models, actors
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(json.dumps(result, indent=1) + "\n")
+    benchkit.emit(result, args.out)
 
 
 if __name__ == "__main__":

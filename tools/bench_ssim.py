@@ -7,7 +7,6 @@ when a mask is given.  Also the config-5 training step (P = 1 M street scene at 
 + loss forward + loss backward + the op's backward) with this loss mix, both ways.
 Prints one JSON line."""
 import argparse
-import json
 import math
 import os
 import sys
@@ -16,6 +15,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
 
+import benchkit
+from benchkit import median
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd import loss as fused_loss
 
@@ -60,11 +61,6 @@ def fused_mix(img, gt, mask=None, lam=0.2):
     return fused_loss.l1_ssim_loss(img, gt, mask, lambda_l1=1.0, lambda_dssim=lam)[0]
 
 
-def _median(x):
-    x = sorted(x)
-    return x[len(x) // 2]
-
-
 def time_loss(fn, H, W, mask, steps, warmup, dev):
     img = torch.rand(3, H, W, device=dev)
     gt = torch.rand(3, H, W, device=dev)
@@ -83,7 +79,7 @@ def time_loss(fn, H, W, mask, steps, warmup, dev):
             fw.append(e[0].elapsed_time(e[1]))
             bw.append(e[1].elapsed_time(e[2]))
             both.append(e[0].elapsed_time(e[2]))
-    return {"forward_ms": _median(fw), "backward_ms": _median(bw), "fwd_bwd_ms": _median(both)}
+    return {"forward_ms": median(fw), "backward_ms": median(bw), "fwd_bwd_ms": median(both)}
 
 
 def time_train_step(fn, P, steps, warmup, dev):
@@ -91,24 +87,22 @@ def time_train_step(fn, P, steps, warmup, dev):
     sc = hz.street_scene(P, seed=149).to(dev)
     leaves = [t.clone().requires_grad_(True) for t in (sc.means3D, sc.opacity, sc.shs, sc.scales, sc.rotations)]
     gt = torch.rand(3, hz.WAYMO_H, hz.WAYMO_W, device=dev)
-    ts = []
-    for it in range(warmup + steps):
-        cam = hz.trajectory_camera(it % 200, device=dev)
-        rast = GaussianRasterizer(GaussianRasterizationSettings(**hz.settings_kwargs(cam, 1)))
-        means2D = torch.zeros(P, 3, device=dev, requires_grad=True)
+    frames = iter(range(warmup + steps))
+
+    def prepare():
+        cam = hz.trajectory_camera(next(frames) % 200, device=dev)
         for t in leaves:
             t.grad = None
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
+        return (GaussianRasterizer(GaussianRasterizationSettings(**hz.settings_kwargs(cam, 1))),
+                torch.zeros(P, 3, device=dev, requires_grad=True))
+
+    def step(arg):
+        rast, means2D = arg
         color = rast(means3D=leaves[0], means2D=means2D, opacities=leaves[1], shs=leaves[2], scales=leaves[3],
                      rotations=leaves[4])[0]
         fn(color, gt, None).backward()
-        e1.record()
-        torch.cuda.synchronize()
-        if it >= warmup:
-            ts.append(e0.elapsed_time(e1))
-    return _median(ts)
+        return color        # held until after the synchronize, as before
+    return benchkit.medians(benchkit.timed(step, steps, warmup, prepare=prepare, wall=False))["device_us"] / 1e3
 
 
 def main():
@@ -118,6 +112,7 @@ def main():
     ap.add_argument("--gaussians", type=int, default=1_000_000)
     ap.add_argument("--no-train-step", action="store_true")
     args = ap.parse_args()
+    benchkit.require_gpu("bench_ssim")
     dev = torch.device("cuda:0")
     out = {"bench": "tools/bench_ssim.py: train.py:118 loss mix (lambda_dssim 0.2), C=3", "steps": args.steps}
     for W, H in ((1920, 1280), (1242, 375)):
@@ -129,7 +124,7 @@ def main():
         for name, fn in (("torch", torch_mix), ("fused", fused_mix)):
             out["train_step_P%d_1920x1280_%s_ms" % (args.gaussians, name)] = time_train_step(
                 fn, args.gaussians, max(args.steps // 3, 5), args.warmup, dev)
-    print(json.dumps(out))
+    benchkit.emit(out)
 
 
 if __name__ == "__main__":

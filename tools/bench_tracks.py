@@ -12,16 +12,15 @@ mode) and the device kernels one call launches (torch.profiler; null where the p
 No speed threshold belongs to this tool: the op is launch-sized, and the claim it measures is the launches and
 waits it removes.  Prints one JSON line; --out FILE also writes it (profiles/tracks_bench.json)."""
 import argparse
-import json
 import os
 import sys
-import time
-import warnings
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+import benchkit
+from benchkit import count_launches, count_syncs, median, spread
 from gaussianrpg_amd import harness as hz
 from gaussianrpg_amd.tracks import TrackTable, TrackedActorPoses
 
@@ -29,11 +28,8 @@ LENGTH = 198
 BASE = 1.5e9
 
 
-def median(xs):
-    return sorted(xs)[len(xs) // 2]
-
-
-def make_actors(A, dev, seed=0):
+def make_turning_actors(A, dev, seed=0):
+    """A actors on diverging, turning tracks (benchkit_scenes.make_actors is another scene: cars in rows ahead)"""
     rng = np.random.RandomState(seed)
     F = LENGTH
     tr = np.zeros((F, A, 8), np.float32)
@@ -51,55 +47,6 @@ def make_actors(A, dev, seed=0):
     return m
 
 
-def timed(fn, steps, warmup):
-    wall, device = [], []
-    for it in range(warmup + steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        e0.record()
-        out = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        del out
-        if it >= warmup:
-            wall.append((t1 - t0) * 1e6)
-            device.append(e0.elapsed_time(e1) * 1e3)
-    return median(wall), median(device)
-
-
-def count_syncs(fn):
-    """Host synchronisations torch sees in one call (sync debug mode warns at each)."""
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    torch.cuda.synchronize()
-    return sum("synchroniz" in str(x.message).lower() for x in w)
-
-
-def count_launches(fn):
-    """Device kernels (and memsets / copies apart) one call launches, or None where the profiler cannot tell."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        kernels = [e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")]
-        if not kernels:
-            return None
-        copies = sum(("memcpy" in e.name.lower()) or ("memset" in e.name.lower()) for e in kernels)
-        return {"kernels": len(kernels) - copies, "copies_and_memsets": copies}
-    except Exception as e:   # the figure is optional; the times are not
-        return {"error": "%s: %s" % (type(e).__name__, e)}
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -108,8 +55,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--actors", type=int, action="append")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_tracks: needs an MI355X (no ROCm device visible); nothing is measured without one")
+    benchkit.require_gpu("bench_tracks")
     dev = torch.device("cuda:0")
     result = {"bench": "tools/bench_tracks.py: parse_camera's actor poses, fused HIP against the reference's per-actor "
                        "PyTorch; us per call (wall on the host with the device idle before and waited for after, and "
@@ -120,7 +66,7 @@ def main():
     ego[:3, 3] = torch.tensor([3.0, -2.0, 0.5], device=dev)
     t = BASE + 0.1 * 77.3
     for A in args.actors or [10, 50]:
-        m = make_actors(A, dev)
+        m = make_turning_actors(A, dev)
         counts = [1000] * A
         g_rot, g_trans = torch.randn(A, 4, device=dev), torch.randn(A, 3, device=dev)
 
@@ -137,23 +83,13 @@ def main():
             routes = {"fused": lambda: run(True, train), "torch": lambda: run(False, train)}
             a, b = run(True, train), run(False, train)
             cell = {"A": A, "max_abs_difference_between_routes": [float((x - y).abs().max()) for x, y in zip(a, b)]}
-            reps = {k: [] for k in routes}
-            for r in range(args.reps):
-                for k, fn in routes.items():
-                    reps[k].append(timed(fn, args.steps, args.warmup if r == 0 else 1))
+            reps = benchkit.windows(routes, args.reps, args.steps, args.warmup)
             for k, fn in routes.items():
-                wall, device = [x[0] for x in reps[k]], [x[1] for x in reps[k]]
-                cell[k] = {"wall_us": median(wall), "wall_min_us": min(wall), "wall_max_us": max(wall),
-                           "device_events_us": median(device), "wall_medians_us": wall,
-                           "host_syncs": count_syncs(fn), "launches": count_launches(fn)}
+                cell[k] = dict(spread(reps[k]["wall_us"], prefix="wall_"), device_events_us=median(reps[k]["device_us"]),
+                               host_syncs=count_syncs(fn), launches=count_launches(fn))
             cell["torch_over_fused_wall"] = cell["torch"]["wall_us"] / cell["fused"]["wall_us"]
             result["cases"]["A%d_%s" % (A, mode)] = cell
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(json.dumps(result, indent=1) + "\n")
+    benchkit.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -3,9 +3,11 @@
 lib/models/street_gaussian_renderer.py:157-162) and a loss that makes all four output gradients
 non-zero (L1 to a fixed target + depth/acc term, mirrors train.py:116-118,164-176).
 Prints one JSON line: forward ms, backward ms (torch.cuda.synchronize-bracketed, per iteration)."""
-import argparse, json, os, sys, time
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import benchkit
+from benchkit import median
 from gaussianrpg_amd import harness as hz
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 
@@ -14,6 +16,7 @@ ap.add_argument("--gaussians", type=int, default=1_000_000)
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 args = ap.parse_args()
+benchkit.require_gpu("bench_train")
 dev = torch.device("cuda:0")
 sc = hz.street_scene(args.gaussians, seed=149).to(dev)
 leaves = [t.clone().requires_grad_(True) for t in (sc.means3D, sc.opacity, sc.shs, sc.scales, sc.rotations)]
@@ -40,9 +43,8 @@ for it in range(args.warmup + args.steps):
     torch.cuda.synchronize(); t3 = time.perf_counter()
     if it >= args.warmup:
         fw.append(t1 - t0); bw.append(t3 - t2); ob.append(e0.elapsed_time(e1))
-fw.sort(); bw.sort(); ob.sort()
-print(json.dumps({"config": "configs[4]: train fwd+bwd, scene-149-like P=%d @1920x1280" % args.gaussians,
-                  "forward_ms_median": 1e3 * fw[len(fw) // 2], "backward_ms_median": 1e3 * bw[len(bw) // 2],
-                  "op_backward_device_ms_median": ob[len(ob) // 2],
-                  "backward_includes": "_C.rasterize_gaussians_backward alone (wall, and device time between two events)",
-                  "steps": args.steps}))
+benchkit.emit({"config": "configs[4]: train fwd+bwd, scene-149-like P=%d @1920x1280" % args.gaussians,
+               "forward_ms_median": 1e3 * median(fw), "backward_ms_median": 1e3 * median(bw),
+               "op_backward_device_ms_median": median(ob),
+               "backward_includes": "_C.rasterize_gaussians_backward alone (wall, and device time between two events)",
+               "steps": args.steps})

@@ -4,7 +4,6 @@ and their ratio -- the figure tests/test_gpu_ego_loop.py::test_ranging_accuracy 
 and camera rows: the number of elements that differ in any bit from the restatement (expected 0).  Prints one JSON
 line; --out FILE also writes it (profiles/ego_loop_parity.json)."""
 import argparse
-import json
 import os
 import sys
 
@@ -14,6 +13,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
+import benchkit
 import loop_truth as lt
 import test_gpu_ego_loop as tg
 from gaussianrpg_amd import closed_loop as cl
@@ -23,8 +23,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("ego_loop_parity: needs an MI355X (no ROCm device visible)")
+    benchkit.require_gpu("ego_loop_parity")
     dev = torch.device("cuda:0")
     C = lt.Constants()
     ranging = cl.Ranging(C.K, C.extrinsics, C.cam_height, C.H, C.W, names=lt.NAMES)
@@ -42,12 +41,7 @@ def main():
     for name in lt.SCENARIOS:
         log, rows, ks, loop, want, poses, truth = tg.run_device(world, ranging, name, sky=True)
         result["scenarios"][name] = {"steps": len(log), "log_elements_differing": int((log.view(np.uint64) != want.view(np.uint64)).sum())}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(json.dumps(result, indent=1) + "\n")
+    benchkit.emit(result, args.out)
 
 
 if __name__ == "__main__":

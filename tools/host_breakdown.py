@@ -2,14 +2,16 @@
 time.perf_counter() around the pose objects, the ray matrix, composed._pack, the binding call (returns when the frame
 is enqueued) and the final synchronize.  The GPU is idle until the binding's first launch: everything in front of it is
 on the frame's critical path in a closed loop."""
-import json, math, os, sys, time
+import math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
+import benchkit
 from gaussianrpg_amd import composed as C, harness as hz
 from gaussianrpg_amd.sky import SkyCubeMap, ray_matrix_host
 from diff_gaussian_rasterization import GaussianRasterizationSettings
 
+benchkit.require_gpu("host_breakdown")
 dev = torch.device("cuda:0")
 W, H = bench.W, bench.H
 g = torch.Generator().manual_seed(2)
@@ -53,5 +55,5 @@ with torch.no_grad():
         if f >= 10:
             for k, v in zip(acc, (t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, t5 - t0)):
                 acc[k].append(1e6 * v)
-med = {k: sorted(v)[len(v) // 2] for k, v in acc.items()}
-print(json.dumps({"median_us": med, "what": __doc__.split("\n")[0]}))
+med = {k: benchkit.median(v) for k, v in acc.items()}
+benchkit.emit({"median_us": med, "what": __doc__.split("\n")[0]})
