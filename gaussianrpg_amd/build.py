@@ -102,6 +102,9 @@ HIP_UNITS = {
     # element is the instruction's own, contraction has no say in it) and SPP's max-pools; SiLU's x * (1 / (1 + expf(-x)))
     # is a correctly rounded division and a rounded product, as nms.hip's sigmoid; no atomics
     "detector.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # the detector's network in fp16: the same launch list on the f16 matrix instructions, float32 accumulation and
+    # epilogue, one rounding to fp16 per layer; SiLU as in detector.hip; no atomics
+    "detector_f16.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "api.hip": [],
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept
@@ -109,8 +112,9 @@ HIP_UNITS = {
 # (render_fwd.hip render_min_waves; tests/test_render_resources.py reads the file), and so is
 # the eight waves per SIMD of the specialised preprocess instantiations (tests/test_preprocess_resources.py); the
 # use_mlp colour correction promises kernels without scratch (tests/test_color_mlp_host.py), and so do the detector's
-# convolution and pool, whose LDS per workgroup is a budget too (tests/test_detector_resources.py)
-REMARK_UNITS = ("render_fwd.hip", "preprocess.hip", "color_mlp.hip", "detector.hip")
+# convolution and pool, whose LDS per workgroup is a budget too (tests/test_detector_resources.py,
+# tests/test_detector_f16_resources.py)
+REMARK_UNITS = ("render_fwd.hip", "preprocess.hip", "color_mlp.hip", "detector.hip", "detector_f16.hip")
 
 
 def headers():

@@ -2193,6 +2193,63 @@ void DetectorRun(const torch::Tensor& records, const torch::Tensor& arena) {
   run("grpg_detector_run", [&](void* stream) { return grpg_detector_run(layers.data(), (int)n, stream); });
 }
 
+// ---- the detector's network in fp16 (gaussianrpg_amd/detector.py; csrc/detector_f16.hip) ----
+
+// The same float32 weight and bias -> the fp16 network's packed buffer (uint8: a float32 bias block, then fp16).
+torch::Tensor DetectorPackWeightsF16(const torch::Tensor& weight, const torch::Tensor& bias) {
+  TORCH_CHECK(weight.scalar_type() == torch::kFloat32 && bias.scalar_type() == torch::kFloat32,
+              "detector_pack_weights_f16: weight and bias must be float32 (the kernel rounds the weight once)");
+  TORCH_CHECK(weight.dim() == 4 && weight.size(2) == weight.size(3) && bias.dim() == 1 && bias.size(0) == weight.size(0) &&
+                  weight.is_contiguous() && bias.is_contiguous(),
+              "detector_pack_weights_f16: weight must be a contiguous [c_out, c_in, k, k] and bias [c_out] (got ",
+              weight.sizes(), " and ", bias.sizes(), ")");
+  TORCH_CHECK(weight.is_cuda() && bias.device() == weight.device(),
+              "detector_pack_weights_f16: weight and bias must live on one ROCm/HIP device (torch device 'cuda'); this "
+              "op has no CPU path");
+  TORCH_CHECK(weight.size(0) < (int64_t(1) << 24) && weight.size(1) < (int64_t(1) << 20), "detector_pack_weights_f16: too large");
+  const int c_out = (int)weight.size(0), c_in = (int)weight.size(1), k = (int)weight.size(2);
+  const size_t bytes = grpg_conv2d_packed_bytes_f16(c_out, c_in, k);
+  TORCH_CHECK(bytes > 0, "detector_pack_weights_f16: k must be 1 or 3 (got ", k, ")");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(weight.device());
+  torch::Tensor packed = torch::empty({(int64_t)bytes}, weight.options().dtype(torch::kUInt8));
+  run("grpg_conv2d_pack_weights_f16", [&](void* stream) {
+    return grpg_conv2d_pack_weights_f16(weight.data_ptr<float>(), bias.data_ptr<float>(), c_out, c_in, k,
+                                        packed.data_ptr(), stream);
+  });
+  return packed;
+}
+
+// records: a HOST int64 [n, 27] table, one grpg_detector_layer_f16 per row in the struct's field order.
+void DetectorRunF16(const torch::Tensor& records, const torch::Tensor& arena) {
+  TORCH_CHECK(records.scalar_type() == torch::kInt64 && records.dim() == 2 && records.size(1) == 27 &&
+                  records.size(0) >= 1 && records.is_contiguous() && !records.is_cuda(),
+              "detector_run_f16: records must be a contiguous host int64 [n, 27] table");
+  TORCH_CHECK(arena.is_cuda(), "detector_run_f16: the network's tensors must live on a ROCm/HIP device (torch device "
+                               "'cuda'); this op has no CPU path");
+  const int64_t n = records.size(0);
+  TORCH_CHECK(n < (int64_t(1) << 20), "detector_run_f16: too many layers");
+  std::vector<grpg_detector_layer_f16> layers((size_t)n);
+  const int64_t* r = records.data_ptr<int64_t>();
+  for (int64_t i = 0; i < n; i++, r += 27) {
+    for (int j = 0; j < 27; j++)
+      if (j != 1 && j != 4 && j != 7 && j != 10 && j != 13)
+        TORCH_CHECK(r[j] >= INT32_MIN && r[j] <= INT32_MAX, "detector_run_f16: layer ", i, ": field ", j, " out of range");
+    grpg_detector_layer_f16& L = layers[(size_t)i];
+    L.kind = (int)r[0];
+    L.in = reinterpret_cast<const void*>((uintptr_t)r[1]); L.in_c0 = (int)r[2]; L.in_ct = (int)r[3];
+    L.out = reinterpret_cast<void*>((uintptr_t)r[4]); L.out_c0 = (int)r[5]; L.out_ct = (int)r[6];
+    L.res = reinterpret_cast<const void*>((uintptr_t)r[7]); L.res_c0 = (int)r[8]; L.res_ct = (int)r[9];
+    L.up = reinterpret_cast<void*>((uintptr_t)r[10]); L.up_c0 = (int)r[11]; L.up_ct = (int)r[12];
+    L.packed = reinterpret_cast<const void*>((uintptr_t)r[13]);
+    L.bs = (int)r[14]; L.c_in = (int)r[15]; L.c_out = (int)r[16];
+    L.h_in = (int)r[17]; L.w_in = (int)r[18]; L.h_out = (int)r[19]; L.w_out = (int)r[20];
+    L.k = (int)r[21]; L.stride = (int)r[22]; L.act = (int)r[23]; L.in_mode = (int)r[24]; L.tile = (int)r[25];
+    L.out_f32 = (int)r[26];
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(arena.device());
+  run("grpg_detector_run_f16", [&](void* stream) { return grpg_detector_run_f16(layers.data(), (int)n, stream); });
+}
+
 // ---- the closed loop's tail (gaussianrpg_amd/closed_loop.py; csrc/ego_loop.hip) ----
 
 namespace {
@@ -3326,6 +3383,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // the detector's network: weight repack once, then the whole launch list in one call (detector.py)
   m.def("detector_pack_weights", &DetectorPackWeights);
   m.def("detector_run", &DetectorRun);
+  m.def("detector_pack_weights_f16", &DetectorPackWeightsF16);
+  m.def("detector_run_f16", &DetectorRunF16);
   // the closed loop's tail: ranging alone, and the fused step (closed_loop.py)
   m.def("object_positions", &ObjectPositions);
   m.def("ego_loop_step", &EgoLoopStep);

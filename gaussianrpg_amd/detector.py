@@ -1,10 +1,12 @@
 """The detector's network on the device: the inference forward of the reference's YOLOv5 between ``detector_input``
 and ``detections_from_heads`` (models/yolo.py:119-159 over models/common.py: ``Focus``, ``Conv``, ``Bottleneck``,
-``C3``, ``SPP``, ``nn.Upsample``, ``Concat`` and ``Detect``'s 1x1 convs), FP32, as ONE native call per frame
-(csrc/detector.hip).
+``C3``, ``SPP``, ``nn.Upsample``, ``Concat`` and ``Detect``'s 1x1 convs), as ONE native call per frame: FP32
+(csrc/detector.hip) or, with ``dtype=torch.float16``, fp16 activations
+and weights with float32 accumulation and float32 heads (csrc/detector_f16.hip).
 
     spec = DetectorSpec.from_yaml("yolov5s.yaml")            # or DetectorSpec.from_module(attempt_load(...))
     net = DetectorNet(spec, state_dict)                      # fused or unfused tensors, the reference's keys
+    net = DetectorNet(spec, state_dict, dtype=torch.float16) # takes detector_input(..., dtype=torch.float16)
     heads = net(detector_input(frame["rgb8"], plan))         # the nl conv outputs [bs, na*(5+nc), ny, nx]
     det, count = net.detections(x, plan=plan)
 
@@ -15,7 +17,7 @@ does around a convolution is part of a convolution's launch record: SiLU, the Bo
 ``Concat`` / ``torch.cat`` (producers write into a channel slice of the consumer's buffer) and ``nn.Upsample`` (a
 second, 2 x 2 replicated store of the producer).  Only SPP's three max-pools are a launch of their own, one for all.
 
-Not here: fp16 / bf16 execution, loading a pickled ``.pt``, augmented inference, training.
+Not here: bf16 execution, loading a pickled ``.pt``, augmented inference, training.
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple, Union
@@ -33,6 +35,7 @@ TILE_128, TILE_64 = 0, 1
 RECORD_FIELDS = ("kind", "in", "in_c0", "in_ct", "out", "out_c0", "out_ct", "res", "res_c0", "res_ct", "up", "up_c0",
                  "up_ct", "packed", "bs", "c_in", "c_out", "h_in", "w_in", "h_out", "w_out", "k", "stride", "act",
                  "in_mode", "tile")
+RECORD_FIELDS_F16 = RECORD_FIELDS + ("out_f32",)   # grpg_detector_layer_f16
 SPP_KERNELS = (5, 9, 13)
 CUS = 256   # MI355X: the tile policy wants at least one 128 x 128 tile per compute unit
 
@@ -404,6 +407,17 @@ def pool_record(in_ptr, in_c0, in_ct, out_ptr, out_c0, out_ct, bs, c, h, w) -> L
             0, 0, 0, 0, 0]
 
 
+def conv_record_f16(*args, out_f32=False, **kw) -> List[int]:
+    """One GRPG_DET_CONV row of the fp16 network: ``conv_record``'s arguments; out_f32: ``out`` is float32 (Detect's
+    heads; no res, no up)."""
+    return conv_record(*args, **kw) + [int(bool(out_f32))]
+
+
+def pool_record_f16(*args) -> List[int]:
+    """One GRPG_DET_POOL row of the fp16 network: ``pool_record``'s arguments."""
+    return pool_record(*args) + [0]
+
+
 def _C():
     from .rasterizer import _C as ext
     return ext
@@ -423,6 +437,22 @@ def run_records(records: Union[torch.Tensor, Sequence[Sequence[int]]], like: tor
     _C().detector_run(records, like)
 
 
+def pack_weights_f16(weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The SAME float32 [c_out, c_in, k, k] (+ [c_out] bias) on the device -> the fp16 network's buffer, uint8:
+    [bias: M_pad float32][M_pad][K_pad] fp16 with c_out padded to 128, K to 32 and zeros in the padding; the weight is
+    rounded once, to nearest even, in the launch."""
+    if bias is None:
+        bias = torch.zeros(weight.shape[0], dtype=weight.dtype, device=weight.device)
+    return _C().detector_pack_weights_f16(weight.contiguous(), bias.contiguous())
+
+
+def run_records_f16(records: Union[torch.Tensor, Sequence[Sequence[int]]], like: torch.Tensor) -> None:
+    """``run_records`` for rows of ``conv_record_f16`` / ``pool_record_f16``."""
+    if not isinstance(records, torch.Tensor):
+        records = torch.tensor([list(map(int, r)) for r in records], dtype=torch.int64)
+    _C().detector_run_f16(records, like)
+
+
 class DetectorPlan:
     """What ``DetectorNet.plan`` builds for one (bs, h, w, device): the arena, the records, the heads (views of the
     arena) and, for the tests, the symbolic launch list ``steps`` the records were made from."""
@@ -433,7 +463,8 @@ class DetectorPlan:
         self.steps: List[dict] = []
         self.arena = self.records = None
         self.heads: List[torch.Tensor] = []
-        self.offsets: Dict[str, int] = {}
+        self.offsets: Dict[str, int] = {}                    # name -> first byte in the arena
+        self.arena_bytes = 0
         self.input_rows: List[int] = []
 
     @property
@@ -446,9 +477,15 @@ class DetectorNet:
     the first call for a shape -- no allocation: the heads are views of that shape's arena and are overwritten by the
     next call with the same shape (clone what must outlive it).
 
-    state_dict: the reference's keys (``model.<i>...`` or ``<i>...``), fused or unfused (see ``fused_parameters``)."""
+    state_dict: the reference's keys (``model.<i>...`` or ``<i>...``), fused or unfused (see ``fused_parameters``).
+    dtype: torch.float32 (the default) or torch.float16.  The half network folds BatchNorm in float32 exactly as the
+    float32 one, rounds every weight once to fp16 (the bias stays float32), takes a float16 ``x``, rounds every
+    activation once per layer and returns float32 heads."""
 
-    def __init__(self, spec: DetectorSpec, state_dict: Dict[str, torch.Tensor]):
+    def __init__(self, spec: DetectorSpec, state_dict: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float32):
+        if dtype not in (torch.float32, torch.float16):
+            raise TypeError("DetectorNet: dtype must be torch.float32 or torch.float16 (got %s)" % (dtype,))
+        self.dtype = dtype
         self.spec = spec
         self.params = fused_parameters(spec, state_dict)
         self.geometry = spec.geometry()
@@ -457,8 +494,8 @@ class DetectorNet:
         self._plans: Dict[tuple, DetectorPlan] = {}
 
     @classmethod
-    def from_module(cls, model) -> "DetectorNet":
-        return cls(DetectorSpec.from_module(model), model.state_dict())
+    def from_module(cls, model, dtype: torch.dtype = torch.float32) -> "DetectorNet":
+        return cls(DetectorSpec.from_module(model), model.state_dict(), dtype)
 
     # ---- planning ----
     def layout(self, bs: int, h: int, w: int, tile: Optional[int] = None) -> DetectorPlan:
@@ -593,8 +630,42 @@ class DetectorNet:
     def packed(self, device) -> List[torch.Tensor]:
         device = _device(device)
         if device not in self._packed:
-            self._packed[device] = [pack_weights(w.to(device), b.to(device)) for w, b in self.params]
+            pack = pack_weights_f16 if self.dtype == torch.float16 else pack_weights
+            self._packed[device] = [pack(w.to(device), b.to(device)) for w, b in self.params]
         return self._packed[device]
+
+    def arena_layout(self, P: DetectorPlan) -> Tuple[Dict[str, int], int]:
+        """({buffer: first byte}, bytes) of the arena of a ``layout()``: every buffer 256-byte aligned, ``self.dtype``
+        elements -- except, in the half network, the float32 head buffers.  Host only."""
+        offsets, total = {}, 0
+        for name, (c, bh, bw) in P.buffers.items():
+            size = 4 if self.dtype == torch.float32 or name.startswith("head") else 2
+            offsets[name] = total
+            total += -(-(P.bs * c * bh * bw * size) // 256) * 256
+        return offsets, total
+
+    def records_of(self, P: DetectorPlan, offsets: Dict[str, int], base: int, packed: Sequence[int]) -> List[List[int]]:
+        """The launch records of a ``layout()`` whose buffers start ``offsets`` bytes behind ``base``; packed: the
+        address of every convolution's packed weights.  Rows of ``RECORD_FIELDS`` (float32) or ``RECORD_FIELDS_F16``
+        (half: ``out_f32`` on the rows that write a head).  The input's address is left 0.  Host only."""
+        bs, half = P.bs, self.dtype == torch.float16
+        ptr = lambda name: 0 if name == "input" else base + offsets[name]
+        ct = lambda name: self.spec.ch_in if name == "input" else P.buffers[name][0]
+        rows = []
+        for n, s in enumerate(P.steps):
+            (sb, sc0, sc), (db, dc0, dc) = s["src"], s["dst"]
+            if s["kind"] == "pool":
+                rows.append((pool_record_f16 if half else pool_record)(
+                    ptr(sb), sc0, ct(sb), ptr(db), dc0, ct(db), bs, sc, s["hw_in"][0], s["hw_in"][1]))
+                continue
+            res = None if s["res"] is None else (ptr(s["res"][0]), s["res"][1], ct(s["res"][0]))
+            up = None if s["up"] is None else (ptr(s["up"][0]), s["up"][1], ct(s["up"][0]))
+            kw = dict(out_f32=db.startswith("head")) if half else {}
+            rows.append((conv_record_f16 if half else conv_record)(
+                ptr(sb), sc0, ct(sb), s["hw_in"][0], s["hw_in"][1], ptr(db), dc0, ct(db), packed[s["conv"]],
+                bs, s["c_in"], s["c_out"], s["k"], s["s"], s["act"], res=res, up=up, focus=s["focus"], tile=s["tile"],
+                **kw))
+        return rows
 
     def plan(self, bs: int, h: int, w: int, device="cuda", tile: Optional[int] = None) -> DetectorPlan:
         """The plan for inputs [bs, ch, h, w] on ``device``: built and allocated once, then cached.  tile: force one
@@ -606,32 +677,22 @@ class DetectorNet:
         P = self.layout(int(bs), int(h), int(w), tile)
         P.device = device
         packed = self.packed(device)
-        total = 0
-        for name, (c, bh, bw) in P.buffers.items():
-            P.offsets[name] = total
-            total += -(-(bs * c * bh * bw) // 64) * 64        # 256-byte aligned buffers
-        P.arena = torch.empty(total, dtype=torch.float32, device=device)
-        base = P.arena.data_ptr()
-        ptr = lambda name: 0 if name == "input" else base + 4 * P.offsets[name]
-        ct = lambda name: self.spec.ch_in if name == "input" else P.buffers[name][0]
-        rows = []
-        for n, s in enumerate(P.steps):
-            (sb, sc0, sc), (db, dc0, dc) = s["src"], s["dst"]
-            if sb == "input":
-                P.input_rows.append(n)
-            if s["kind"] == "pool":
-                rows.append(pool_record(ptr(sb), sc0, ct(sb), ptr(db), dc0, ct(db), bs, sc, s["hw_in"][0], s["hw_in"][1]))
-                continue
-            res = None if s["res"] is None else (ptr(s["res"][0]), s["res"][1], ct(s["res"][0]))
-            up = None if s["up"] is None else (ptr(s["up"][0]), s["up"][1], ct(s["up"][0]))
-            rows.append(conv_record(ptr(sb), sc0, ct(sb), s["hw_in"][0], s["hw_in"][1], ptr(db), dc0, ct(db),
-                                    packed[s["conv"]].data_ptr(), bs, s["c_in"], s["c_out"], s["k"], s["s"], s["act"],
-                                    res=res, up=up, focus=s["focus"], tile=s["tile"]))
+        half = self.dtype == torch.float16
+        P.offsets, P.arena_bytes = self.arena_layout(P)
+        if half:
+            P.arena = torch.empty(P.arena_bytes, dtype=torch.uint8, device=device)
+        else:
+            P.arena = torch.empty(P.arena_bytes // 4, dtype=torch.float32, device=device)
+        rows = self.records_of(P, P.offsets, P.arena.data_ptr(), [t.data_ptr() for t in packed])
+        P.input_rows = [n for n, s in enumerate(P.steps) if s["src"][0] == "input"]
         P.records = torch.tensor(rows, dtype=torch.int64)
         for l in range(self.spec.nl):
             c, hh, ww = P.buffers["head%d" % l]
             o = P.offsets["head%d" % l]
-            P.heads.append(P.arena[o:o + bs * c * hh * ww].view(bs, c, hh, ww))
+            if half:
+                P.heads.append(P.arena[o:o + 4 * bs * c * hh * ww].view(torch.float32).view(bs, c, hh, ww))
+            else:
+                P.heads.append(P.arena[o // 4:o // 4 + bs * c * hh * ww].view(bs, c, hh, ww))
         self._plans[key] = P
         return P
 
@@ -639,7 +700,10 @@ class DetectorNet:
     def _check(self, x):
         if not isinstance(x, torch.Tensor):
             raise TypeError("DetectorNet: x must be a tensor (got %s)" % type(x).__name__)
-        if x.dtype != torch.float32:
+        if self.dtype == torch.float16 and x.dtype != torch.float16:
+            raise TypeError("DetectorNet: x must be float16 (got %s) for a dtype=torch.float16 network: no hidden cast; "
+                            "detector_input(..., dtype=torch.float16) makes it" % (x.dtype,))
+        if self.dtype == torch.float32 and x.dtype != torch.float32:
             raise TypeError("DetectorNet: x must be float32 (got %s); the network is the FP32 model the reference loads, "
                             "a half-precision run is a different contract" % (x.dtype,))
         if x.dim() != 4 or x.shape[1] != self.spec.ch_in:
@@ -658,7 +722,7 @@ class DetectorNet:
         P = self.plan(x.shape[0], x.shape[2], x.shape[3], x.device, tile)
         for n in P.input_rows:
             P.records[n, 1] = x.data_ptr()
-        _C().detector_run(P.records, P.arena)
+        (_C().detector_run_f16 if self.dtype == torch.float16 else _C().detector_run)(P.records, P.arena)
         return P.heads
 
     def detections(self, x: torch.Tensor, conf_thres: float = 0.25, iou_thres: float = 0.45,

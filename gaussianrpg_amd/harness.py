@@ -689,7 +689,7 @@ def simulator_detections_from_frame(frame: torch.Tensor, net, plan, fused: bool 
       fused=False  ``torch_net(x)`` -- ``detector_torch(net.spec, state_dict, device=frame.device)`` -- then the
                    reference's lines in PyTorch"""
     from . import perception
-    x = perception.detector_input(frame, plan)
+    x = perception.detector_input(frame, plan, dtype=getattr(net, "dtype", torch.float32))   # a half net: a half input
     if not fused and torch_net is None:
         raise ValueError("simulator_detections_from_frame: fused=False needs torch_net= (harness.detector_torch)")
     heads = net(x) if fused else torch_net(x)
@@ -701,8 +701,9 @@ def closed_loop_run_with_detector(scene, net, steps: int, *, plan, ranging, **kw
     """``closed_loop_run`` with the real network in its ``heads_for_frame`` slot: every frame goes from the render to
     the brake decision on the device, the detector's convolutions included."""
     from . import perception
-    return closed_loop_run(scene, lambda i, f: net(perception.detector_input(f["rgb8"], plan)), steps, plan=plan,
-                           ranging=ranging, geom=net.geometry, **kw)
+    dtype = getattr(net, "dtype", torch.float32)
+    return closed_loop_run(scene, lambda i, f: net(perception.detector_input(f["rgb8"], plan, dtype=dtype)), steps,
+                           plan=plan, ranging=ranging, geom=net.geometry, **kw)
 
 
 def _quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -1653,6 +1653,48 @@ GRPG_API int grpg_conv2d_pack_weights(const float* weight, const float* bias, in
                                       float* packed, void* hip_stream);
 GRPG_API int grpg_detector_run(const grpg_detector_layer* layers, int n, void* hip_stream);
 
+/*
+ * The detector's network in FP16 (csrc/detector_f16.hip): the same launch list with fp16
+ * activations and weights on the f16 matrix instructions.  Additive; GRPG_ABI_VERSION stays 7; grpg_detector_layer
+ * and the three entry points above are untouched.  Everything said above holds, with these differences:
+ *
+ * Tensors are fp16 (IEEE binary16), 2-byte aligned, NCHW.  grpg_conv2d_pack_weights_f16 takes the SAME float32
+ * weight and bias and writes [bias: M_pad floats][M_pad][K_pad] fp16 -- c_out padded to 128, K = c_in * k * k to 32,
+ * zeros in the padding, every weight rounded once to nearest even, the bias kept in float32 -- into `packed`,
+ * grpg_conv2d_packed_bytes_f16(c_out, c_in, k) bytes, 16-byte aligned.
+ *
+ * GRPG_DET_CONV computes, in this order: the float32 bias plus the float32 accumulation of the exact fp16 x fp16
+ * products (k ascending in steps of 16, one v_mfma_f32_32x32x16_f16 each; the order inside a step is the
+ * hardware's); the activation in float32; res (read as fp16) added in float32 after the activation; ONE rounding to
+ * fp16, to nearest even, overflowing to inf.  That rounded value goes to out and, 2 x 2 replicated, to up.  Both tile
+ * shapes give the same bits.  out_f32 = 1: out is a float32 tensor (4-byte aligned) and receives the value unrounded
+ * -- Detect's heads, what grpg_detect_detections reads; res and up must then be NULL.
+ * GRPG_DET_POOL: the same pools on fp16 (exact); out_f32 must be 0.
+ *
+ * grpg_detector_run_f16 checks every layer before it enqueues anything, as grpg_detector_run does; the overlap check
+ * works in bytes.
+ */
+typedef struct grpg_detector_layer_f16 {
+  int kind;                          /* GRPG_DET_CONV / GRPG_DET_POOL */
+  const void* in;                    /* fp16 [bs, in_ct, h_in, w_in] */
+  int in_c0, in_ct;
+  void* out;                         /* fp16 (out_f32 = 0) or float32 (out_f32 = 1) [bs, out_ct, h_out, w_out] */
+  int out_c0, out_ct;
+  const void* res;                   /* fp16 [bs, res_ct, h_out, w_out] or NULL */
+  int res_c0, res_ct;
+  void* up;                          /* fp16 [bs, up_ct, 2 h_out, 2 w_out] or NULL */
+  int up_c0, up_ct;
+  const void* packed;                /* grpg_conv2d_pack_weights_f16 */
+  int bs, c_in, c_out;
+  int h_in, w_in, h_out, w_out;
+  int k, stride, act, in_mode, tile;
+  int out_f32;
+} grpg_detector_layer_f16;
+GRPG_API size_t grpg_conv2d_packed_bytes_f16(int c_out, int c_in, int k);   /* pure size query */
+GRPG_API int grpg_conv2d_pack_weights_f16(const float* weight, const float* bias, int c_out, int c_in, int k,
+                                          void* packed, void* hip_stream);
+GRPG_API int grpg_detector_run_f16(const grpg_detector_layer_f16* layers, int n, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

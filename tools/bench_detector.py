@@ -13,8 +13,12 @@ share of the 157 TFLOP/s f32 matrix peak.  --routes b measures (b) alone (a mach
 layer).  --closed-loop adds the braking frame of tools/bench_ego_loop.py (1.9 M + 10 x 10 k Gaussians at 1920 x 1280,
 closed_loop.EgoLoop, commanded braking, max_det 10) with three things in harness.closed_loop_step's heads slot,
 alternating call by call: that tool's fixed synthetic heads (no network: the parent's figure and the baseline), route
-(a) and route (b) behind perception.detector_input.  No speed threshold belongs to this tool.  Prints one JSON line; --out FILE also writes it
-(profiles/detector_bench.json)."""
+(a) and route (b) behind perception.detector_input.  --half adds the fp16 rows to the same alternation (DESIGN.md section
+31): native_f16, DetectorNet(dtype=torch.float16) on a half input (csrc/detector_f16.hip; its share is of the f16 matrix
+peak, 16 x the f32 one), and -- with route (a) -- torch_f16, harness.detector_torch(dtype=torch.float16) on the device
+with the float32-fused weights rounded to half, warmed up the same way; with --closed-loop also the braking frame with
+each of them behind detector_input(..., dtype=torch.float16) (profiles/detector_f16_bench.json).  No speed threshold
+belongs to this tool.  Prints one JSON line; --out FILE also writes it (profiles/detector_bench.json)."""
 import argparse
 import functools
 import os
@@ -33,6 +37,7 @@ from gaussianrpg_amd import detector as D
 from gaussianrpg_amd import harness as hz
 
 PEAK_F32_MATRIX = 157.3e12
+PEAK_F16_MATRIX = 16 * PEAK_F32_MATRIX
 SIZES = {"1600x1088": (1088, 1600), "1920x1280": (1280, 1920)}
 
 
@@ -60,7 +65,7 @@ def per_layer(net, P, reps):
         for _ in range(reps):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            D.run_records(rec, P.arena)
+            (D.run_records_f16 if net.dtype == torch.float16 else D.run_records)(rec, P.arena)
             b.record()
             torch.cuda.synchronize()
             ts.append(a.elapsed_time(b))
@@ -114,6 +119,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--closed-loop", action="store_true")
     ap.add_argument("--routes", default="ab", choices=["ab", "b"])
+    ap.add_argument("--half", action="store_true")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--layer-reps", type=int, default=5)
@@ -128,41 +134,61 @@ def main():
     for c, (w, b) in zip(spec.convs(), net.params):
         pre = c["key"] + ("" if c["plain"] else ".conv")
         fused[pre + ".weight"], fused[pre + ".bias"] = w, b
+    net16 = D.DetectorNet(spec, sd, dtype=torch.float16) if args.half else None
     res = {"device": torch.cuda.get_device_name(0), "model": "yolov5s nc 80, seeded weights, bs 1", "routes": args.routes,
+           "half": args.half,
            "steps": args.steps, "reps": args.reps, "miopen_find_mode": os.environ.get("MIOPEN_FIND_MODE"), "sizes": {}}
     for name in args.size or list(SIZES):
         h, w = SIZES[name]
         x = torch.from_numpy(T.build_input(1, h, w, 5)).to(dev)
         routes = {"native": lambda: net(x)}
+        nets = {"native": net}
         row = {"input": [1, 3, h, w]}
-        if args.routes == "ab":
-            tnet = hz.detector_torch(spec, fused, device=dev)
-            routes["torch"] = lambda: tnet(x)
+        if args.half:
+            xh = x.half()
+            routes["native_f16"] = lambda: net16(xh)
+            nets["native_f16"] = net16
+
+        def settle_torch(name, suffix=""):
             t0 = time.perf_counter()
             prev, settle = None, []
             for _ in range(30):
-                t = median(wall(routes["torch"], 1))
+                t = median(wall(routes[name], 1))
                 settle.append(t)
                 if prev is not None and abs(t - prev) <= 0.05 * prev:
                     break
                 prev = t
-            row["torch_warmup_calls_ms"] = settle
-            row["torch_warmup_s"] = time.perf_counter() - t0
+            row["torch%s_warmup_calls_ms" % suffix] = settle
+            row["torch%s_warmup_s" % suffix] = time.perf_counter() - t0
+        if args.routes == "ab":
+            tnet = hz.detector_torch(spec, fused, device=dev)
+            routes["torch"] = lambda: tnet(x)
+            settle_torch("torch")
             ht, hn = tnet(x), net(x)
             row["routes_rel_l2"] = [T.rel_l2(a.cpu(), b.cpu()) for a, b in zip(hn, ht)]
-        wall(routes["native"], 3)
+            if args.half:
+                tnet16 = hz.detector_torch(spec, fused, dtype=torch.float16, device=dev)
+                routes["torch_f16"] = lambda: tnet16(xh)
+                settle_torch("torch_f16", "_f16")
+                row["routes_f16_rel_l2"] = [T.rel_l2(a.cpu(), b.float().cpu()) for a, b in zip(net16(xh), tnet16(xh))]
+                row["native_f16_from_native_rel_l2"] = [T.rel_l2(a.cpu(), b.cpu()) for a, b in zip(net16(xh), net(x))]
+        for r in nets:
+            wall(routes[r], 3)
         meds = {r: [us / 1e3 for us in v] for r, v in alternating_wall(routes, args.steps, args.reps).items()}
         for r, fn in routes.items():
             row[r] = {"wall_ms": median(meds[r]), "min": min(meds[r]), "max": max(meds[r]),
                       "launches": len(benchkit.device_kernels(fn)), "host_syncs": count_syncs(fn)}
-        P = net.plan(1, h, w, dev)
-        layers = per_layer(net, P, args.layer_reps)
-        flops = sum(l.get("flops", 0) for l in layers)
-        dev_ms = sum(l["ms"] for l in layers)
-        row["native"].update(arena_mib=P.arena.numel() * 4 / 2 ** 20, gflop=flops / 1e9, sum_of_layer_ms=dev_ms,
-                             tflops_over_wall=flops / (row["native"]["wall_ms"] * 1e-3) / 1e12,
-                             share_of_f32_matrix_peak=flops / (row["native"]["wall_ms"] * 1e-3) / PEAK_F32_MATRIX,
-                             tile128_layers=sum(l.get("tile") == 128 for l in layers), layers=layers)
+        for r, n in nets.items():
+            P = n.plan(1, h, w, dev)
+            layers = per_layer(n, P, args.layer_reps)
+            flops = sum(l.get("flops", 0) for l in layers)
+            dev_ms = sum(l["ms"] for l in layers)
+            half = n.dtype == torch.float16
+            row[r].update({"arena_mib": P.arena_bytes / 2 ** 20, "gflop": flops / 1e9, "sum_of_layer_ms": dev_ms,
+                           "tflops_over_wall": flops / (row[r]["wall_ms"] * 1e-3) / 1e12,
+                           "share_of_f16_matrix_peak" if half else "share_of_f32_matrix_peak":
+                               flops / (row[r]["wall_ms"] * 1e-3) / (PEAK_F16_MATRIX if half else PEAK_F32_MATRIX),
+                           "tile128_layers": sum(l.get("tile") == 128 for l in layers), "layers": layers})
         res["sizes"][name] = row
         print(name, {r: row[r]["wall_ms"] for r in routes}, file=sys.stderr)
     if args.closed_loop:
@@ -174,6 +200,12 @@ def main():
             if args.routes == "ab":
                 tnet = hz.detector_torch(spec, fused, device=dev)
                 r["torch"] = lambda frame: tnet(detector_input(frame["rgb8"], plan))
+            if args.half:
+                r["native_f16"] = lambda frame: net16(detector_input(frame["rgb8"], plan, dtype=torch.float16))
+                if args.routes == "ab":
+                    tnet16 = hz.detector_torch(spec, fused, dtype=torch.float16, device=dev)
+                    r["torch_f16"] = lambda frame: [h.float() for h in tnet16(detector_input(frame["rgb8"], plan,
+                                                                                            dtype=torch.float16))]
             return r, net.geometry
         res["closed_loop_frame"] = closed_loop_frame(dev, routes_of, args.steps, args.reps)
         print("closed loop", {k: v["wall_us"] for k, v in res["closed_loop_frame"].items() if isinstance(v, dict)}, file=sys.stderr)
