@@ -16,7 +16,8 @@
 // P = sum N_i, in composed order; the segment table (pointers, first flat index, length) is read from device memory,
 // each thread keeping the segment it last found.  Visible: radii[j] > 0.  float32:
 //   o = 1 / (1 + exp(-x)), u = 1 / (1 + exp(x))   (u = 1 - o without the cancellation; activated: o = x, u = 1 - x)
-//   inside = 1e-6 <= o <= 1 - 1e-6;  oc = inside ? o : min(max(o, 1e-6), 1 - 1e-6),  uc = inside ? u : 1 - oc
+//   inside = 1e-6 <= o <= 1 - 1e-6;  oc = inside ? o : clamp(o, 1e-6, 1 - 1e-6) (NaN stays NaN, as torch.clamp: the
+//   term of a visible Gaussian with a NaN opacity is NaN, its gradient 0),  uc = inside ? u : 1 - oc
 //   term = -(oc log oc + uc log uc) (the logs float32, the products and sums float64),
 //   opacity_sparse_loss = sum over the visible / n_visible   (NaN for none)
 // Accurate expf / logf, no FMA contraction: the backward recomputes the forward bit for bit.
@@ -127,7 +128,9 @@ struct RgOpacity {
       u = 1.0f / (1.0f + expf(x));
     }
     inside = o >= RG_OMIN && o <= RG_OMAX;
-    oc = inside ? o : fminf(fmaxf(o, RG_OMIN), RG_OMAX);
+    // torch.clamp: NaN passes through (fminf / fmaxf would return the bound and hide a NaN opacity of a visible
+    // Gaussian, which the reference's mean shows)
+    oc = inside ? o : (o < RG_OMIN ? RG_OMIN : (o > RG_OMAX ? RG_OMAX : o));
     uc = inside ? u : 1.0f - oc;
     lo = logf(oc);
     lu = logf(uc);

@@ -17,6 +17,9 @@
 // One walk with an online softmax (running max m, running sum s of exp(x - m)) yields lse = m + log(s); it also
 // captures x at the target and the running argmax of the raw plane values (strict >: ties go to the lowest
 // channel; the probabilities transform is monotone, so this is the argmax of x as well without its rounding ties).
+// A channel at -inf adds 0 to s, also while m is still -inf: (-inf, -inf, 0) has lse 0, and a pixel whose channels
+// are all -inf has lse -inf and the loss NaN, as F.cross_entropy.  The backward needs no such case: it takes lse from
+// the forward, and exp(-inf - lse) is 0 for a finite lse.
 // Accurate expf / logf, no FMA contraction: the backward recomputes x bit for bit.
 //
 // Pixels: valid when 0 <= target < S; ignored when target == -1; anything else is bad: counted, treated as
@@ -153,7 +156,8 @@ semantic_ce_forward_kernel(const ScArgs A, const ScWs ws, unsigned char* __restr
           s = s * expf(m - x) + 1.0f;
           m = x;
         } else {
-          s = s + expf(x - m);
+          // a channel at -inf has probability 0, also while the running max is still -inf (-inf - -inf is NaN)
+          s = s + (x == -INFINITY ? 0.0f : expf(x - m));
         }
         if (r > best) {
           best = r;

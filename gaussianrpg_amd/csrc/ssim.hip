@@ -20,9 +20,11 @@
 //                   + mask(p) sign(x1 - x2) s_l1
 //     over in-image q (the partial planes are zero-padded in LDS).  s_b and s_l1 are formed on the
 //     device from the upstream gradient of the stats vector and the forward's count: no host sync.
-// Semantics of loss_utils kept exactly: the mask zeroes both images before any moment; the SSIM mean
-// runs over all B*C*H*W positions, the L1 mean over the selected elements only (all-false mask: NaN,
-// gradient 0); C1 = 0.01^2, C2 = 0.03^2; variances as E[x^2] - mu^2.
+// Semantics of loss_utils kept exactly: the mask selects both images before any moment, as
+// torch.where(mask, img, 0) does -- a deselected element counts as 0 whatever it holds (NaN and Inf
+// included; it is never multiplied), and its gradient is exactly 0; the SSIM mean runs over all
+// B*C*H*W positions, the L1 mean over the selected elements only (all-false mask: NaN, gradient 0);
+// C1 = 0.01^2, C2 = 0.03^2; variances as E[x^2] - mu^2.
 #include "abi_util.h"
 #include "common.h"
 #include "reduce.h"
@@ -82,9 +84,11 @@ ssim_forward_kernel(const SsimShape s, const float* __restrict__ x1, const float
     float a = 0.f, v = 0.f;
     if (gy >= 0 && gy < s.H && gx >= 0 && gx < s.W) {
       const size_t pix = (size_t)gy * s.W + gx;
-      const float m = mask_at(mask, s, b, c, pix);
-      a = m * x1[base + pix];
-      v = m * x2[base + pix];
+      // select, as torch.where does: 0 * NaN and 0 * Inf are NaN, and a deselected value must not reach a moment
+      if (mask_at(mask, s, b, c, pix) != 0.f) {
+        a = x1[base + pix];
+        v = x2[base + pix];
+      }
     }
     s_a[r][q] = a;
     s_b[r][q] = v;

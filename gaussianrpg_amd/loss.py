@@ -11,8 +11,8 @@ Drop-ins for the reference's loss code (lib/utils/loss_utils.py) and its trainin
       device scalars for logging.
 
 Inputs are float32 device tensors [C,H,W] or [B,C,H,W] (non-contiguous ones are copied).  The mask is a
-bool (or uint8) tensor that broadcasts against the image the way ``torch.where(mask, img, 0)`` does.
-Only the first image receives a gradient.  No host synchronisation in forward or backward.  There is no
+bool (or uint8) tensor that broadcasts against the image the way ``torch.where(mask, img, 0)`` does, and selects the
+way it does: an element under a false mask counts as 0 whatever it holds.  Only the first image receives a gradient.  No host synchronisation in forward or backward.  There is no
 CPU or PyTorch fallback: CPU tensors, other dtypes, window_size != 11, mismatched shapes and a second
 image that requires a gradient are errors.
 
@@ -80,6 +80,26 @@ The per-Gaussian regularisers of train.py (csrc/reg_loss.hip):
 
 An empty selection (no pixel, no visible Gaussian, N == 0) gives NaN with an exactly-zero gradient, as mean() of an
 empty gather does.  No host synchronisation in any forward or backward, no atomics.
+
+What a deselected element holds never reaches a result: the ops select as the reference's boolean gather and
+torch.where do, they do not multiply by a 0/1 mask.  NaN, +-Inf or garbage in the elements below changes no bit of a
+value, a count or a gradient, and the gradient there is exactly 0 (tests/test_gpu_selection.py):
+
+  ssim, l1_loss, l1_ssim_loss            img1 / img2 where the (broadcast) mask is false
+  psnr                                   img1 / img2 where the mask is false
+  lidar_depth_loss, aux_loss (lidar)     depth and acc where !(lidar_depth > 0) or the mask is false (acc only while
+                                         the sky term is off); lidar_depth where the mask is false is only compared
+                                         with 0, and a NaN there deselects itself
+  semantic_loss, semantic_loss_stats     every channel of a pixel whose label is -1 or outside [-1, S) (the 'labels'
+                                         plane is the argmax of every pixel and does read them)
+  normal_loss, normal_loss_terms         normals / mono_normal outside mask & ~sky_mask & (row >= top_rows)
+  opacity_sparse_loss, gaussian_reg_loss the opacities of Gaussians with radii <= 0
+  optim.densification_stats_update       the viewspace_grad rows of Gaussians with radii <= 0
+
+sky_loss and obj_acc_loss read EVERY pixel, by the reference's own definition: their masks only choose the branch of
+a torch.where over the whole plane, so a NaN anywhere in acc / acc_obj makes the term NaN.  scale_flatten_loss reads
+every Gaussian.  A NaN at a selected element of the ops above shows in the value as it does in the reference (in the
+lidar term by its top-k rule: a NaN error sorts above +inf).
 """
 import torch
 

@@ -123,6 +123,33 @@ def test_batched_per_image_values(dev):
     assert float((got.double() - ref).abs().max()) < 1e-5
 
 
+@pytest.mark.parametrize("masked", [False, True])
+def test_per_image_upstream_weights(dev, masked):
+    """size_average=False under unequal upstream weights, one of them negative: .sum() hands every image the same
+    coefficient, so only this shows an image that was scaled by its neighbour's.  The file's two gradient bars hold
+    for each image's slice on its own, where a wrong coefficient cannot hide in the norm of the batch."""
+    from gaussianrpg_amd import loss
+    a, b = _imgs((3, 3, 24, 31), 8, dev)
+    w = torch.tensor([0.3, -1.7, 2.0], device=dev)
+    g = torch.Generator(device="cpu").manual_seed(9)
+    m = (torch.rand(3, 1, 24, 31, generator=g) > 0.4).to(dev) if masked else None
+    fused = lambda x, y, mm: (loss.ssim(x, y, size_average=False, mask=mm) * w).sum()
+    ref = lambda x, y, mm: (ssim_truth.ssim(x, y, size_average=False, mask=mm) * w.to(x.dtype)).sum()
+    v, gr = _grad(fused, a, b, m)
+    v64, g64 = _grad(ref, a.double(), b.double(), m)
+    v32, g32 = _grad(ref, a, b, m)
+    torch.cuda.synchronize()
+    e, e32 = abs(float(v) - float(v64)), abs(float(v32) - float(v64))
+    print("weighted per-image ssim: value %.9g float64 %.9g (float32 torch error %.3g)" % (float(v), float(v64), e32))
+    assert e < 1e-5, (float(v), float(v64))
+    assert e <= 2 * e32 + VAL_FLOOR, (e, e32)
+    for i in range(3):
+        r, r32 = _rel(gr[i], g64[i]), _rel(g32[i], g64[i])
+        print("image %d (weight %g): gradient rel L2 %.3g (float32 torch %.3g)" % (i, float(w[i]), r, r32))
+        assert r < 1e-3, (i, r)
+        assert r <= 2 * r32 + GRAD_FLOOR, (i, r, r32)
+
+
 def test_non_contiguous(dev):
     big_a, big_b = _imgs((3, 90, 2 * 70), 3, dev)
     a, b = big_a[:, 5:85, ::2], big_b[:, 5:85, ::2]

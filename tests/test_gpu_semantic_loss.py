@@ -183,6 +183,51 @@ def test_large_logits_do_not_overflow(dev, S):
     _check(sem, gt, "logits", "30x logits S=%d" % S)
 
 
+NINF = float("-inf")
+MINUS_INF_PIXELS = {"ninf_ninf_0": (NINF, NINF, 0.0), "ninf_0_ninf": (NINF, 0.0, NINF), "0_ninf_ninf": (0.0, NINF, NINF),
+                    "all_ninf": (NINF, NINF, NINF)}
+
+
+@pytest.mark.parametrize("name", list(MINUS_INF_PIXELS))
+@pytest.mark.parametrize("S", [3, 40])
+def test_minus_inf_logits(dev, S, name):
+    """A channel at -inf has probability 0: the log-sum-exp of (-inf, -inf, 0) is 0, not exp(-inf - -inf) = NaN.
+    One pixel at a time (every other label -1), each target 0..2, in the register form (S = 3) and the memory form
+    (S = 40, the further channels -inf): the loss is finite and inside the file's bars where float64 F.cross_entropy
+    is finite, +inf where it is +inf (the target itself at -inf), NaN where it is NaN (every channel -inf); the
+    gradient is exactly 0 at every -inf channel where the truth's is."""
+    H, W = 3, 5
+    sem = torch.full((S, H, W), NINF, device=dev)
+    sem[:3] = torch.randn(3, H, W, generator=torch.Generator().manual_seed(S)).to(dev)
+    sem[:3, 1, 2] = torch.tensor(MINUS_INF_PIXELS[name], device=dev)
+    for t in range(3):
+        what = "%s target %d S=%d" % (name, t, S)
+        gt = torch.full((H, W), -1, dtype=torch.int64, device=dev)
+        gt[1, 2] = t
+        v, g = _fused(sem, gt, "logits")
+        x64 = sem.double().requires_grad_(True)
+        v64 = truth.loss64(x64, gt, "logits")
+        v64.backward()
+        v64, g64 = float(v64.detach()), x64.grad
+        print("%s: value %r float64 %r" % (what, float(v), v64))
+        if math.isfinite(v64):
+            _val_ok(v, v64, truth.loss32(sem, gt, "logits"), what)
+        elif math.isnan(v64):
+            assert math.isnan(float(v)), (what, float(v))
+        else:
+            assert float(v) == v64, (what, float(v), v64)
+        assert torch.equal(torch.isnan(g).cpu(), torch.isnan(g64).cpu()), what
+        zero = (sem == NINF) & (g64 == 0)
+        assert bool((g[zero] == 0).all()), what
+        if bool(torch.isfinite(g64).all()):
+            _grad_ok(g, g64, what)
+    # among ordinary pixels: the three patterns whose target holds the 0 join a mean of finite losses
+    if name != "all_ninf":
+        gt = torch.randint(0, 3, (H, W), generator=torch.Generator().manual_seed(S + 1)).to(dev)
+        gt[1, 2] = MINUS_INF_PIXELS[name].index(0.0)
+        _check(sem, gt, "logits", "%s among finite pixels S=%d" % (name, S))
+
+
 @pytest.mark.parametrize("S", [3, 19, 40])
 def test_probabilities_edge_inputs_stay_finite(dev, S):
     from gaussianrpg_amd import loss
