@@ -18,6 +18,8 @@ Layout:
                   device), then one call per frame with nothing in front of its first launch
   closed_loop.py  the loop around the session on the device: detections -> object positions, brake decision, ego step
                   and the next frame's camera row in one launch per frame, no host wait
+  lpips.py        LPIPS (AlexNet, VGG16) as one native call: the third number of the reference's metrics.py, next to
+                  loss.ssim and loss.psnr
   build.py        in-tree build (hipcc for gfx950, g++ for the binding)
 
 Importing this package does not load native code; ``gaussianrpg_amd.rasterizer`` does, and fails

@@ -105,6 +105,12 @@ HIP_UNITS = {
     # the detector's network in fp16: the same launch list on the f16 matrix instructions, float32 accumulation and
     # epilogue, one rounding to fp16 per layer; SiLU as in detector.hip; no atomics
     "detector_f16.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # LPIPS: the detector's implicit-GEMM convolution with AlexNet's / VGG16's geometries, a z-score in the first
+    # layer's gather ((x - mean) / std: a rounded subtraction and a correctly rounded division) and a ReLU epilogue;
+    # the distance normalises with correctly rounded square roots and divisions and sums w (a - b)^2 one rounding per
+    # operation (no FMA contraction; the sums of squares are explicit fmaf chains); no atomics, deterministic
+    # fixed-order reduction
+    "lpips.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "api.hip": [],
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept
@@ -113,8 +119,8 @@ HIP_UNITS = {
 # the eight waves per SIMD of the specialised preprocess instantiations (tests/test_preprocess_resources.py); the
 # use_mlp colour correction promises kernels without scratch (tests/test_color_mlp_host.py), and so do the detector's
 # convolution and pool, whose LDS per workgroup is a budget too (tests/test_detector_resources.py,
-# tests/test_detector_f16_resources.py)
-REMARK_UNITS = ("render_fwd.hip", "preprocess.hip", "color_mlp.hip", "detector.hip", "detector_f16.hip")
+# tests/test_detector_f16_resources.py) and LPIPS's kernels (tests/test_lpips_resources.py)
+REMARK_UNITS = ("render_fwd.hip", "preprocess.hip", "color_mlp.hip", "detector.hip", "detector_f16.hip", "lpips.hip")
 
 
 def headers():

@@ -1,6 +1,6 @@
 // Host helpers shared by the C-ABI entry points (include/grpg_rasterizer.h) of libgrpg_rasterizer.so.  The frame's
 // entries live in api.hip; every self-contained op keeps its entries next to its kernels (ssim.hip, aux_loss.hip,
-// semantic_loss.hip, normal_loss.hip, reg_loss.hip, metrics.hip, optim.hip, knn.hip, sky.hip, color_correction.hip, color_mlp.hip, pose_correction.hip, letterbox.hip, nms.hip, tracks.hip, ego_loop.hip, detector.hip).  Declarations only:
+// semantic_loss.hip, normal_loss.hip, reg_loss.hip, metrics.hip, optim.hip, knn.hip, sky.hip, color_correction.hip, color_mlp.hip, pose_correction.hip, letterbox.hip, nms.hip, tracks.hip, ego_loop.hip, detector.hip, lpips.hip).  Declarations only:
 // each helper is defined once, in api.hip, which also owns the one thread-local string behind grpg_last_error().
 #pragma once
 #include <hip/hip_runtime.h>

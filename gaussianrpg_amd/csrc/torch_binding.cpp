@@ -2250,6 +2250,160 @@ void DetectorRunF16(const torch::Tensor& records, const torch::Tensor& arena) {
   run("grpg_detector_run_f16", [&](void* stream) { return grpg_detector_run_f16(layers.data(), (int)n, stream); });
 }
 
+// ---- LPIPS (gaussianrpg_amd/lpips.py; csrc/lpips.hip) ----
+
+namespace {
+const float* lpips_f32(const torch::Tensor& t, const torch::Device& dev, const char* fn, const char* what) {
+  TORCH_CHECK(t.defined(), fn, ": undefined ", what);
+  TORCH_CHECK(t.is_cuda(), fn, ": ", what, " must live on a ROCm/HIP device (torch device 'cuda'); this op has no CPU path");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, fn, ": ", what, " must be float32 (got ", t.scalar_type(), "): no hidden cast");
+  TORCH_CHECK(t.device() == dev, fn, ": ", what, " is on another device");
+  TORCH_CHECK(t.is_contiguous(), fn, ": ", what, " must be contiguous");
+  return t.data_ptr<float>();
+}
+}  // namespace
+
+// float32 [c_out, c_in, k, k] weight and [c_out] bias on the device -> the packed buffer the convolution streams.
+torch::Tensor LpipsPackWeights(const torch::Tensor& weight, const torch::Tensor& bias) {
+  TORCH_CHECK(weight.defined() && weight.is_cuda(), "lpips_pack_weights: weight must live on a ROCm/HIP device (torch "
+              "device 'cuda'); this op has no CPU path");
+  const float* w = lpips_f32(weight, weight.device(), "lpips_pack_weights", "weight");
+  const float* b = lpips_f32(bias, weight.device(), "lpips_pack_weights", "bias");
+  TORCH_CHECK(weight.dim() == 4 && weight.size(2) == weight.size(3) && bias.dim() == 1 && bias.size(0) == weight.size(0),
+              "lpips_pack_weights: weight must be [c_out, c_in, k, k] and bias [c_out] (got ", weight.sizes(), " and ",
+              bias.sizes(), ")");
+  TORCH_CHECK(weight.size(0) < (int64_t(1) << 24) && weight.size(1) < (int64_t(1) << 20), "lpips_pack_weights: too large");
+  const int c_out = (int)weight.size(0), c_in = (int)weight.size(1), k = (int)weight.size(2);
+  const size_t bytes = grpg_lpips_conv_packed_bytes(c_out, c_in, k);
+  TORCH_CHECK(bytes > 0, "lpips_pack_weights: k must be 3, 5 or 11 (got ", k, ")");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(weight.device());
+  torch::Tensor packed = torch::empty({(int64_t)(bytes / sizeof(float))}, weight.options());
+  run("grpg_lpips_conv_pack_weights", [&](void* stream) {
+    return grpg_lpips_conv_pack_weights(w, b, c_out, c_in, k, packed.data_ptr<float>(), stream);
+  });
+  return packed;
+}
+
+int64_t LpipsWorkspaceBytes(const int64_t net, const int64_t pairs, const int64_t h, const int64_t w) {
+  if (pairs > INT32_MAX || h > INT32_MAX || w > INT32_MAX || pairs < 0 || h < 0 || w < 0) return 0;
+  return (int64_t)grpg_lpips_workspace_bytes((int)net, (int)pairs, (int)h, (int)w);
+}
+
+int64_t LpipsWorkspaceMapOffset(const int64_t net, const int64_t pairs, const int64_t h, const int64_t w, const int64_t tap) {
+  if (pairs > INT32_MAX || h > INT32_MAX || w > INT32_MAX || pairs < 0 || h < 0 || w < 0) return 0;
+  return (int64_t)grpg_lpips_workspace_map_offset((int)net, (int)pairs, (int)h, (int)w, (int)tap);
+}
+
+// x, y: contiguous float32 [pairs, 3, h, w]; workspace: uint8 of lpips_workspace_bytes; out_pairs [pairs] and out_taps
+// [pairs, 5] are the caller's (lpips.py keeps them per shape: no allocation after a shape's first call).
+void LpipsForward(const int64_t net, const std::vector<torch::Tensor>& packed, const std::vector<torch::Tensor>& lin,
+                  const torch::Tensor& x, const torch::Tensor& y, const torch::Tensor& workspace,
+                  const torch::Tensor& out_pairs, const torch::Tensor& out_taps) {
+  static const int widths[2][5] = {{64, 192, 384, 256, 256}, {64, 128, 256, 512, 512}};
+  TORCH_CHECK(net == GRPG_LPIPS_ALEX || net == GRPG_LPIPS_VGG16, "lpips_forward: unknown net");
+  TORCH_CHECK(x.defined() && x.is_cuda(), "lpips_forward: x must live on a ROCm/HIP device (torch device 'cuda'); this op "
+              "has no CPU path");
+  const torch::Device dev = x.device();
+  const float* px = lpips_f32(x, dev, "lpips_forward", "x");
+  const float* py = lpips_f32(y, dev, "lpips_forward", "y");
+  TORCH_CHECK(x.dim() == 4 && x.size(1) == 3 && x.sizes() == y.sizes(), "lpips_forward: x and y must be [pairs, 3, h, w] of "
+              "one shape (got ", x.sizes(), " and ", y.sizes(), ")");
+  const int64_t pairs = x.size(0), h = x.size(2), w = x.size(3);
+  const int64_t bytes = LpipsWorkspaceBytes(net, pairs, h, w);
+  TORCH_CHECK(bytes > 0, "lpips_forward: ", pairs, " pairs of ", h, " x ", w, " are refused: the image must be at least ",
+              net == GRPG_LPIPS_ALEX ? "31 x 31" : "16 x 16", ", pairs in 1 .. 65535 and every layer below 2^31 pixels");
+  TORCH_CHECK(packed.size() == (net == GRPG_LPIPS_ALEX ? 5u : 13u) && lin.size() == 5, "lpips_forward: the net takes ",
+              net == GRPG_LPIPS_ALEX ? 5 : 13, " packed convolutions and 5 lin weights");
+  std::vector<const float*> pp, pl;
+  for (const torch::Tensor& t : packed) pp.push_back(lpips_f32(t, dev, "lpips_forward", "packed weights"));
+  for (size_t l = 0; l < 5; l++) {
+    pl.push_back(lpips_f32(lin[l], dev, "lpips_forward", "lin weights"));
+    TORCH_CHECK(lin[l].numel() == widths[net][l], "lpips_forward: lin weights of tap ", l, " have ", lin[l].numel(),
+                " elements, the tap has ", widths[net][l], " channels");
+  }
+  TORCH_CHECK(workspace.defined() && workspace.is_cuda() && workspace.device() == dev && workspace.is_contiguous() &&
+                  workspace.scalar_type() == torch::kByte && workspace.numel() >= bytes,
+              "lpips_forward: workspace must be a contiguous uint8 tensor of lpips_workspace_bytes on x's device");
+  float* po = const_cast<float*>(lpips_f32(out_pairs, dev, "lpips_forward", "out_pairs"));
+  float* pt = const_cast<float*>(lpips_f32(out_taps, dev, "lpips_forward", "out_taps"));
+  TORCH_CHECK(out_pairs.numel() == pairs && out_taps.numel() == 5 * pairs, "lpips_forward: out_pairs must be [pairs] and "
+              "out_taps [pairs, 5]");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  run("grpg_lpips_forward", [&](void* stream) {
+    return grpg_lpips_forward((int)net, pp.data(), pl.data(), px, py, (int)pairs, (int)h, (int)w, workspace.data_ptr(), po,
+                              pt, stream);
+  });
+}
+
+// The leaves (tests, tools): ONE convolution + ReLU; zscore: empty, or mean and std (3 + 3 values).
+torch::Tensor LpipsConv2d(const torch::Tensor& x, const torch::Tensor& packed, const int64_t c_out, const int64_t k,
+                          const int64_t stride, const int64_t pad, const std::vector<double>& zscore, const int64_t tile) {
+  TORCH_CHECK(x.defined() && x.is_cuda(), "lpips_conv2d: x must live on a ROCm/HIP device (torch device 'cuda'); this op "
+              "has no CPU path");
+  const float* px = lpips_f32(x, x.device(), "lpips_conv2d", "x");
+  const float* pw = lpips_f32(packed, x.device(), "lpips_conv2d", "packed");
+  TORCH_CHECK(x.dim() == 4 && x.numel() > 0, "lpips_conv2d: x must be a non-empty [bs, c_in, h, w]");
+  TORCH_CHECK(zscore.empty() || zscore.size() == 6, "lpips_conv2d: zscore is empty or mean[3] + std[3]");
+  TORCH_CHECK(x.size(0) <= INT32_MAX && x.size(1) <= INT32_MAX && x.size(2) <= INT32_MAX && x.size(3) <= INT32_MAX &&
+                  c_out >= 1 && c_out <= (1 << 24) && stride >= 1 && stride <= 4 && pad >= 0 && pad < k,
+              "lpips_conv2d: sizes out of range");
+  const int bs = (int)x.size(0), c_in = (int)x.size(1), h = (int)x.size(2), w = (int)x.size(3);
+  const size_t bytes = grpg_lpips_conv_packed_bytes((int)c_out, c_in, (int)k);
+  TORCH_CHECK(bytes > 0 && (size_t)packed.numel() * sizeof(float) == bytes, "lpips_conv2d: packed does not match c_out, "
+              "c_in and k (k must be 3, 5 or 11)");
+  TORCH_CHECK(h + 2 * pad >= k && w + 2 * pad >= k, "lpips_conv2d: the input is smaller than the window");
+  float mean[3], sdev[3];
+  for (size_t i = 0; i < zscore.size() / 2; i++) { mean[i] = (float)zscore[i]; sdev[i] = (float)zscore[3 + i]; }
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  torch::Tensor out = torch::empty({bs, c_out, (h + 2 * pad - k) / stride + 1, (w + 2 * pad - k) / stride + 1}, x.options());
+  run("grpg_lpips_conv2d", [&](void* stream) {
+    return grpg_lpips_conv2d(px, pw, out.data_ptr<float>(), bs, c_in, (int)c_out, h, w, (int)k, (int)stride, (int)pad,
+                             zscore.empty() ? nullptr : mean, zscore.empty() ? nullptr : sdev, (int)tile, stream);
+  });
+  return out;
+}
+
+// MaxPool2d(k, 2), k in {2, 3}, no padding, floor mode, of [..., h, w].
+torch::Tensor LpipsMaxPool(const torch::Tensor& x, const int64_t k) {
+  TORCH_CHECK(x.defined() && x.is_cuda(), "lpips_max_pool: x must live on a ROCm/HIP device (torch device 'cuda'); this "
+              "op has no CPU path");
+  const float* px = lpips_f32(x, x.device(), "lpips_max_pool", "x");
+  TORCH_CHECK(x.dim() == 4 && x.numel() > 0 && (k == 2 || k == 3) && x.size(2) >= k && x.size(3) >= k &&
+                  x.size(2) <= INT32_MAX && x.size(3) <= INT32_MAX,
+              "lpips_max_pool: x must be [bs, c, h, w] with h, w >= k, and k 2 or 3");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  torch::Tensor out = torch::empty({x.size(0), x.size(1), (x.size(2) - k) / 2 + 1, (x.size(3) - k) / 2 + 1}, x.options());
+  run("grpg_lpips_max_pool", [&](void* stream) {
+    return grpg_lpips_max_pool(px, out.data_ptr<float>(), (long long)(x.size(0) * x.size(1)), (int)x.size(2), (int)x.size(3),
+                               (int)k, stream);
+  });
+  return out;
+}
+
+// One tap: feat [2 * pairs, c, h, w] (x's first), lin [c] -> (mean of s per pair [pairs], s [pairs, h, w]).
+std::tuple<torch::Tensor, torch::Tensor> LpipsDistance(const torch::Tensor& feat, const torch::Tensor& lin) {
+  TORCH_CHECK(feat.defined() && feat.is_cuda(), "lpips_distance: feat must live on a ROCm/HIP device (torch device "
+              "'cuda'); this op has no CPU path");
+  const float* pf = lpips_f32(feat, feat.device(), "lpips_distance", "feat");
+  const float* pl = lpips_f32(lin, feat.device(), "lpips_distance", "lin");
+  TORCH_CHECK(feat.dim() == 4 && feat.numel() > 0 && feat.size(0) % 2 == 0 && lin.numel() == feat.size(1),
+              "lpips_distance: feat must be [2 * pairs, c, h, w] and lin hold c weights (got ", feat.sizes(), " and ",
+              lin.numel(), ")");
+  const int64_t pairs = feat.size(0) / 2, c = feat.size(1), hw = feat.size(2) * feat.size(3);
+  TORCH_CHECK(pairs <= 65535 && c <= INT32_MAX && hw < (int64_t(1) << 31) - 256, "lpips_distance: too large");
+  const size_t bytes = grpg_lpips_distance_workspace_bytes((int)pairs, (int)c, (int)hw);
+  TORCH_CHECK(bytes > 0, "lpips_distance: sizes out of range (at most 768 channels)");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(feat.device());
+  torch::Tensor ws = torch::empty({(int64_t)bytes}, feat.options().dtype(torch::kByte));
+  torch::Tensor map = torch::empty({pairs, feat.size(2), feat.size(3)}, feat.options());
+  torch::Tensor out = torch::empty({pairs}, feat.options());
+  run("grpg_lpips_distance", [&](void* stream) {
+    return grpg_lpips_distance(pf, pl, (int)pairs, (int)c, (int)hw, ws.data_ptr(), map.data_ptr<float>(),
+                               out.data_ptr<float>(), stream);
+  });
+  return std::make_tuple(out, map);
+}
+
 // ---- the closed loop's tail (gaussianrpg_amd/closed_loop.py; csrc/ego_loop.hip) ----
 
 namespace {
@@ -3385,6 +3539,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("detector_run", &DetectorRun);
   m.def("detector_pack_weights_f16", &DetectorPackWeightsF16);
   m.def("detector_run_f16", &DetectorRunF16);
+  // LPIPS: weight repack once, then the whole metric in one call; the leaves for the tests (lpips.py)
+  m.def("lpips_pack_weights", &LpipsPackWeights);
+  m.def("lpips_workspace_bytes", &LpipsWorkspaceBytes);
+  m.def("lpips_workspace_map_offset", &LpipsWorkspaceMapOffset);
+  m.def("lpips_forward", &LpipsForward);
+  m.def("lpips_conv2d", &LpipsConv2d);
+  m.def("lpips_max_pool", &LpipsMaxPool);
+  m.def("lpips_distance", &LpipsDistance);
   // the closed loop's tail: ranging alone, and the fused step (closed_loop.py)
   m.def("object_positions", &ObjectPositions);
   m.def("ego_loop_step", &EgoLoopStep);

@@ -679,6 +679,49 @@ def detector_torch(spec, state_dict, dtype=torch.float32, device="cpu", per_laye
     return run
 
 
+def lpips_torch(net_type, features, lin, dtype=torch.float32, device="cpu", per_tap: bool = False):
+    """LPIPS as ordinary PyTorch ops -- ``F.conv2d``, ``F.relu``, ``F.max_pool2d`` over the tables of ``lpips.LAYERS``
+    and the reference's lines for the rest (``BaseNet.z_score`` / ``forward``, ``normalize_activation``, ``LinLayers``,
+    ``LPIPS.forward``): the route ``lpips.LPIPS`` replaces, and the float32 comparison of its tests.  Takes the two
+    state dicts ``lpips.LPIPS`` takes.  Usable on the CPU in float32 and float64.  Returns ``run(x, y)`` -> [1, 1, 1, 1]
+    (``per_tap=True``: ``(value, [the per-pixel maps [B, 1, H_l, W_l]])``)."""
+    import torch.nn.functional as F
+    from . import lpips as lp
+    layers, targets = lp.LAYERS[lp._net(net_type)], lp.TARGETS[net_type]
+    params = {i: (w.to(device, dtype), b.to(device, dtype))
+              for i, (w, b) in zip(lp.conv_indices(net_type), lp.feature_parameters(net_type, features))}
+    lins = [v.to(device, dtype).reshape(1, -1, 1, 1) for v in lp.lin_parameters(net_type, lin)]
+    mean = torch.tensor(lp.MEAN, dtype=torch.float32).to(device, dtype)[None, :, None, None]
+    std = torch.tensor(lp.STD, dtype=torch.float32).to(device, dtype)[None, :, None, None]
+
+    def net(x):
+        x = (x - mean) / std
+        output = []
+        for i, L in enumerate(layers, 1):
+            if L[0] == "conv":
+                x = F.conv2d(x, *params[i - 1], stride=L[4], padding=L[5])
+            elif L[0] == "relu":
+                x = F.relu(x)
+            else:
+                x = F.max_pool2d(x, L[1], L[2])
+            if i in targets:
+                output.append(x / (torch.sqrt(torch.sum(x ** 2, dim=1, keepdim=True)) + lp.EPS))
+            if len(output) == len(targets):
+                break
+        return output
+
+    def run(x, y):
+        with torch.no_grad():
+            x, y = (t.to(device, dtype) for t in (x, y))
+            x, y = (t if t.dim() == 4 else t[None] for t in (x, y))
+            diff = [(fx - fy) ** 2 for fx, fy in zip(net(x), net(y))]
+            maps = [F.conv2d(d, l) for d, l in zip(diff, lins)]
+            res = [m.mean((2, 3), True) for m in maps]
+            value = torch.sum(torch.cat(res, 0), 0, True)
+            return (value, maps) if per_tap else value
+    return run
+
+
 def simulator_detections_from_frame(frame: torch.Tensor, net, plan, fused: bool = True, *, torch_net=None,
                                     conf_thres: float = 0.25, iou_thres: float = 0.45, classes=None,
                                     agnostic: bool = False, max_det: int = 10) -> list:

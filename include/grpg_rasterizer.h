@@ -1695,6 +1695,66 @@ GRPG_API int grpg_conv2d_pack_weights_f16(const float* weight, const float* bias
                                           void* packed, void* hip_stream);
 GRPG_API int grpg_detector_run_f16(const grpg_detector_layer_f16* layers, int n, void* hip_stream);
 
+/*
+ * LPIPS (csrc/lpips.hip): the reference's third quality number (metrics.py:81 over
+ * lib/utils/lpipsPyTorch/modules/{lpips,networks,utils}.py) with the AlexNet or the VGG16 backbone.  Additive;
+ * GRPG_ABI_VERSION stays 7.  FP32, NCHW, no atomics, no split-K: identical calls give identical bits.  No gradient.
+ *
+ * Weights: grpg_lpips_conv_pack_weights has grpg_conv2d_pack_weights' contract and layout for k in {3, 5, 11}: a
+ * contiguous float32 [c_out, c_in, k, k] weight and a [c_out] bias (NULL: zeros) -> [bias][K][c_out], c_out padded to
+ * 128 and K = c_in * k * k to 16 with zeros, grpg_lpips_conv_packed_bytes(c_out, c_in, k) bytes on the device, 16-byte
+ * aligned (0: arguments out of range; a pure size query).  Once per model, one launch, no host wait.
+ *
+ * grpg_lpips_forward: x and y are contiguous float32 [pairs, 3, h, w] on the device, used as given (the z-score of
+ * BaseNet, (v - mean_c) / std_c with mean (-.030, -.088, -.188) and std (.458, .448, .450), is part of the first
+ * convolution's gather; the padding is applied after it).  packed: HOST array of the net's 5 (AlexNet) or 13 (VGG16)
+ * device pointers, the convolutions of torchvision's alexnet().features / vgg16().features in order.  lin: HOST array
+ * of 5 device pointers, tap l's [C_l] weights of LinLayers' 1 x 1 convolution (C = 64, 192, 384, 256, 256 for AlexNet;
+ * 64, 128, 256, 512, 512 for VGG16).  The 2 * pairs images run as one batch.  A tap is a ReLU's output before any pool
+ * (layers 2, 5, 8, 10, 12 / 4, 9, 16, 23, 30, counted from 1); per tap, pixel and pair
+ *   nx = sqrtf(sum_c x_c^2) (an fma chain, c ascending), a_c = x_c / (nx + 1e-10f), likewise ny and b_c,
+ *   s = sum_c w_c * ((a_c - b_c) * (a_c - b_c)) (c ascending), and the tap's term is the mean of s over the pixels,
+ * summed in a fixed order.  out_pairs[p] is the sum of pair p's five terms in tap order; out_taps (or NULL) receives
+ * the terms, [pairs, 5].  The reference's LPIPS.forward is the sum of out_pairs.  Convolutions: every output element is
+ * the chain of grpg_detector_run's GRPG_DET_CONV (k ascending in blocks of 32, the block sums added in order onto the
+ * bias), then ReLU; the pools are MaxPool2d(3, 2) / MaxPool2d(2, 2), floor mode, bit-identical to PyTorch's.
+ * workspace: grpg_lpips_workspace_bytes(net, pairs, h, w) bytes on the device, 256-byte aligned (a pure size query; 0
+ * for sizes the call refuses): two ping-pong activations, the per-pixel maps s of the five taps -- tap l's
+ * [pairs, H_l, W_l] floats start grpg_lpips_workspace_map_offset(net, pairs, h, w, l) bytes in and stay valid until
+ * the next call -- and one partial sum per workgroup.  Launches: 5 + 2 + 6 for AlexNet, 13 + 4 + 6 for VGG16.
+ *
+ * Every argument is checked before anything is enqueued (GRPG_ERR_INVALID_ARGUMENT: an unknown net, NULL or
+ * misaligned pointers, pairs outside 1 .. 65535, h or w below 31 (AlexNet) / 16 (VGG16), a layer with
+ * 2 * pairs * H_out * W_out >= 2^31 - 256), then GRPG_ERR_NO_DEVICE; the call returns without a host wait.
+ *
+ * The leaves, for callers that build another network from them (and for the tests): grpg_lpips_conv2d is ONE
+ * convolution + ReLU of a contiguous [bs, c_in, h_in, w_in] tensor into [bs, c_out, h_out, w_out] with
+ * h_out = (h_in + 2 pad - k) / stride + 1; mean / std (HOST arrays of 3, or both NULL) switch the z-score on, c_in = 3
+ * then; tile picks the kernel shape, the result does not depend on it.  grpg_lpips_max_pool: k in {2, 3}, stride 2, of
+ * `planes` contiguous h x w planes.  grpg_lpips_distance: one tap, feat a contiguous [2 * pairs, c, hw] tensor (x's
+ * first), c <= 768, map [pairs, hw] receives s, out_pairs [pairs] the mean; workspace
+ * grpg_lpips_distance_workspace_bytes(pairs, c, hw) bytes.
+ */
+#define GRPG_LPIPS_ALEX 0
+#define GRPG_LPIPS_VGG16 1
+#define GRPG_LPIPS_TILE_128 0
+#define GRPG_LPIPS_TILE_64 1
+GRPG_API size_t grpg_lpips_conv_packed_bytes(int c_out, int c_in, int k);   /* pure size query */
+GRPG_API int grpg_lpips_conv_pack_weights(const float* weight, const float* bias, int c_out, int c_in, int k,
+                                          float* packed, void* hip_stream);
+GRPG_API size_t grpg_lpips_workspace_bytes(int net, int pairs, int h, int w);   /* pure size query */
+GRPG_API size_t grpg_lpips_workspace_map_offset(int net, int pairs, int h, int w, int tap);   /* pure size query */
+GRPG_API int grpg_lpips_forward(int net, const float* const* packed, const float* const* lin, const float* x,
+                                const float* y, int pairs, int h, int w, void* workspace, float* out_pairs,
+                                float* out_taps, void* hip_stream);
+GRPG_API int grpg_lpips_conv2d(const float* in, const float* packed, float* out, int bs, int c_in, int c_out, int h_in,
+                               int w_in, int k, int stride, int pad, const float* mean, const float* std, int tile,
+                               void* hip_stream);
+GRPG_API int grpg_lpips_max_pool(const float* in, float* out, long long planes, int h, int w, int k, void* hip_stream);
+GRPG_API size_t grpg_lpips_distance_workspace_bytes(int pairs, int c, int hw);   /* pure size query */
+GRPG_API int grpg_lpips_distance(const float* feat, const float* lin, int pairs, int c, int hw, void* workspace,
+                                 float* map, float* out_pairs, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
