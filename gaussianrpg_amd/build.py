@@ -111,6 +111,9 @@ HIP_UNITS = {
     # operation (no FMA contraction; the sums of squares are explicit fmaf chains); no atomics, deterministic
     # fixed-order reduction
     "lpips.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # LPIPS backward: convolution backward-data on the same matrix instructions, the pool's gather and the distance's
+    # derivative with lpips.hip's roundings (its norms must be the forward's bits); no atomics
+    "lpips_bwd.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "api.hip": [],
 }
 # units whose per-kernel register / scratch / LDS / occupancy report (-Rpass-analysis=kernel-resource-usage) is kept
@@ -119,8 +122,10 @@ HIP_UNITS = {
 # the eight waves per SIMD of the specialised preprocess instantiations (tests/test_preprocess_resources.py); the
 # use_mlp colour correction promises kernels without scratch (tests/test_color_mlp_host.py), and so do the detector's
 # convolution and pool, whose LDS per workgroup is a budget too (tests/test_detector_resources.py,
-# tests/test_detector_f16_resources.py) and LPIPS's kernels (tests/test_lpips_resources.py)
-REMARK_UNITS = ("render_fwd.hip", "preprocess.hip", "color_mlp.hip", "detector.hip", "detector_f16.hip", "lpips.hip")
+# tests/test_detector_f16_resources.py) and LPIPS's kernels (tests/test_lpips_resources.py,
+# tests/test_lpips_bwd_resources.py)
+REMARK_UNITS = ("render_fwd.hip", "preprocess.hip", "color_mlp.hip", "detector.hip", "detector_f16.hip", "lpips.hip",
+                "lpips_bwd.hip")
 
 
 def headers():

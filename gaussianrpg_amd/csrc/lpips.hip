@@ -35,11 +35,15 @@
 // of vgg16().features, counted from 1 (networks.py:57-63, 82, 93); VGG16's fifth pool is never run.  A tap's distance
 // is enqueued right behind its convolution, so the workspace is two ping-pong activations, the per-pixel maps and the
 // slots.  Launches: 5 convolutions + 2 pools + 5 distances + 1 finish for AlexNet, 13 + 4 + 5 + 1 for VGG16.
+//
+// grpg_lpips_forward_train is the same launch list on the host with every convolution's output kept in a larger
+// workspace (lpips_train.h) for the backward (lpips_bwd.hip): no kernel of its own, the same bits.
 #include <cmath>
 #include <cstdint>
 
 #include "abi_util.h"
 #include "common.h"
+#include "lpips_train.h"
 #include "reduce.h"
 
 namespace grpg {
@@ -465,6 +469,56 @@ bool conv_k_ok(const int k) { return k == 3 || k == 5 || k == 11; }
 
 }  // namespace
 
+// The training workspace (lpips_train.h): the eval plan's maps and slots, then EVERY convolution's output (the
+// backward reads the x images' post-ReLU activations and both sides' taps), one buffer for the pools' outputs, and the
+// backward's gradients.  The kernels, the tile policy and so the pair values are grpg_lpips_forward's.
+bool lpips_train_plan(const int net, const int pairs, const int h, const int w, LpipsTrainPlan& T) {
+  Plan P;
+  if (!plan_of(net, pairs, h, w, P)) return false;
+  T.n_layers = P.n_layers;
+  T.n_convs = P.n_convs;
+  size_t off = 0;
+  for (int t = 0; t < LP_TAPS; t++) {
+    T.tap_c[t] = P.tap_c[t]; T.tap_hw[t] = P.tap_hw[t]; T.tap_nblk[t] = P.tap_nblk[t];
+    T.map_off[t] = off;
+    off += align256(sizeof(float) * (size_t)pairs * P.tap_hw[t]);
+  }
+  for (int t = 0; t < LP_TAPS; t++) {
+    T.slot_off[t] = off;
+    off += align256(sizeof(float) * (size_t)pairs * P.tap_nblk[t]);
+  }
+  size_t most_pool = 0, most_grad = 0, most_tap = 0;
+  for (int i = 0; i < P.n_layers; i++) {
+    const Layer& l = P.L[i];
+    const size_t one = sizeof(float) * (size_t)l.c_out * l.h_out * l.w_out;   // one image
+    if (l.pool && 2 * pairs * one > most_pool) most_pool = 2 * pairs * one;
+    if (pairs * one > most_grad) most_grad = pairs * one;
+    if (l.tap >= 0 && pairs * one > most_tap) most_tap = pairs * one;
+  }
+  const size_t pool_off = off;
+  off += align256(most_pool);
+  for (int i = 0; i < P.n_layers; i++) {
+    const Layer& l = P.L[i];
+    LpipsTrainLayer& o = T.L[i];
+    o.pool = l.pool; o.c_in = l.c_in; o.c_out = l.c_out; o.k = l.k; o.stride = l.stride; o.pad = l.pad; o.tap = l.tap;
+    o.h_in = l.h_in; o.w_in = l.w_in; o.h_out = l.h_out; o.w_out = l.w_out;
+    if (l.pool) {
+      o.out_off = pool_off;
+    } else {
+      o.out_off = off;
+      off += align256(sizeof(float) * 2 * (size_t)pairs * l.c_out * l.h_out * l.w_out);
+    }
+  }
+  for (int g = 0; g < 2; g++) {
+    T.grad_off[g] = off;
+    off += align256(most_grad);
+  }
+  T.tapgrad_off = off;
+  off += align256(most_tap);
+  T.total = off;
+  return true;
+}
+
 }  // namespace grpg
 
 using namespace grpg;
@@ -621,6 +675,77 @@ int grpg_lpips_forward(int net, const float* const* packed, const float* const* 
     }
     cur = dst;
     side ^= 1;
+  }
+  f.out_pairs = out_pairs; f.out_taps = out_taps;
+  lpips_finish_kernel<<<pairs, REDUCE_THREADS, 0, st>>>(f);
+  HIP_TRY(hipGetLastError());
+  return GRPG_OK;
+}
+
+size_t grpg_lpips_train_workspace_bytes(int net, int pairs, int h, int w) {
+  LpipsTrainPlan T;
+  return lpips_train_plan(net, pairs, h, w, T) ? T.total : 0;
+}
+
+size_t grpg_lpips_train_activation_offset(int net, int pairs, int h, int w, int conv) {
+  LpipsTrainPlan T;
+  if (conv < 0 || !lpips_train_plan(net, pairs, h, w, T)) return 0;
+  for (int i = 0; i < T.n_layers; i++)
+    if (!T.L[i].pool && conv-- == 0) return T.L[i].out_off;
+  return 0;
+}
+
+int grpg_lpips_forward_train(int net, const float* const* packed, const float* const* lin, const float* x, const float* y,
+                             int pairs, int h, int w, void* workspace, float* out_pairs, float* out_taps,
+                             void* hip_stream) {
+  fail(GRPG_OK, "");
+  if (net != GRPG_LPIPS_ALEX && net != GRPG_LPIPS_VGG16) return fail(GRPG_ERR_INVALID_ARGUMENT, "lpips_forward_train: unknown net");
+  if (!packed || !lin || !x || !y || !workspace || !out_pairs)
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "lpips_forward_train: NULL packed / lin / x / y / workspace / out_pairs");
+  if (misaligned(x) || misaligned(y) || misaligned(out_pairs) || misaligned(out_taps))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, "lpips_forward_train: x, y, out_pairs and out_taps must be 4-byte aligned");
+  if ((uintptr_t)workspace & 255) return fail(GRPG_ERR_INVALID_ARGUMENT, "lpips_forward_train: workspace must be 256-byte aligned");
+  LpipsTrainPlan T;
+  if (!lpips_train_plan(net, pairs, h, w, T))
+    return fail(GRPG_ERR_INVALID_ARGUMENT, std::string("lpips_forward_train: pairs must be in 1 .. 65535, the image at least ") +
+                (net == GRPG_LPIPS_ALEX ? "31 x 31" : "16 x 16") + " and 2 * pairs * H_out * W_out below 2^31 - 256 in every layer");
+  for (int i = 0; i < T.n_convs; i++) {
+    if (!packed[i]) return fail(GRPG_ERR_INVALID_ARGUMENT, "lpips_forward_train: NULL packed weights of convolution " + std::to_string(i));
+    if ((uintptr_t)packed[i] & 15) return fail(GRPG_ERR_INVALID_ARGUMENT, "lpips_forward_train: packed weights must be 16-byte aligned");
+  }
+  for (int t = 0; t < LP_TAPS; t++)
+    if (!lin[t] || misaligned(lin[t])) return fail(GRPG_ERR_INVALID_ARGUMENT, "lpips_forward_train: NULL or misaligned lin weights of tap " + std::to_string(t));
+  if (int rc = begin_call()) return rc;
+  hipStream_t st = (hipStream_t)hip_stream;
+  char* ws = (char*)workspace;
+  const int bs = 2 * pairs;
+  const float* cur = nullptr;   // NULL: the two input tensors
+  int conv = 0;
+  FinishArgs f;
+  for (int i = 0; i < T.n_layers; i++) {
+    const LpipsTrainLayer& l = T.L[i];
+    float* dst = (float*)(ws + l.out_off);
+    if (l.pool) {
+      pool_enqueue(cur, dst, (long long)bs * l.c_in, l.h_in, l.w_in, l.k, st);
+    } else {
+      const long long n = (long long)bs * l.h_out * l.w_out;
+      if (!cur)
+        conv_enqueue(x, y, pairs, dst, packed[conv], bs, l.c_in, l.c_out, l.h_in, l.w_in, l.h_out, l.w_out, l.k, l.stride,
+                     l.pad, LP_MEAN, LP_STD, choose_tile(l.c_out, n), st);
+      else
+        conv_enqueue(cur, cur, bs, dst, packed[conv], bs, l.c_in, l.c_out, l.h_in, l.w_in, l.h_out, l.w_out, l.k, l.stride,
+                     l.pad, nullptr, nullptr, choose_tile(l.c_out, n), st);
+      conv++;
+    }
+    HIP_TRY(hipGetLastError());
+    if (l.tap >= 0) {
+      const int t = l.tap;
+      float* slots = (float*)(ws + T.slot_off[t]);
+      distance_enqueue(dst, lin[t], pairs, T.tap_c[t], T.tap_hw[t], (float*)(ws + T.map_off[t]), slots, st);
+      HIP_TRY(hipGetLastError());
+      f.slots[t] = slots; f.nblk[t] = T.tap_nblk[t]; f.hw[t] = T.tap_hw[t];
+    }
+    cur = dst;
   }
   f.out_pairs = out_pairs; f.out_taps = out_taps;
   lpips_finish_kernel<<<pairs, REDUCE_THREADS, 0, st>>>(f);

@@ -2294,11 +2294,22 @@ int64_t LpipsWorkspaceMapOffset(const int64_t net, const int64_t pairs, const in
   return (int64_t)grpg_lpips_workspace_map_offset((int)net, (int)pairs, (int)h, (int)w, (int)tap);
 }
 
+int64_t LpipsTrainWorkspaceBytes(const int64_t net, const int64_t pairs, const int64_t h, const int64_t w) {
+  if (pairs > INT32_MAX || h > INT32_MAX || w > INT32_MAX || pairs < 0 || h < 0 || w < 0) return 0;
+  return (int64_t)grpg_lpips_train_workspace_bytes((int)net, (int)pairs, (int)h, (int)w);
+}
+
+int64_t LpipsTrainActivationOffset(const int64_t net, const int64_t pairs, const int64_t h, const int64_t w, const int64_t conv) {
+  if (pairs > INT32_MAX || h > INT32_MAX || w > INT32_MAX || pairs < 0 || h < 0 || w < 0 || conv < 0 || conv > 64) return 0;
+  return (int64_t)grpg_lpips_train_activation_offset((int)net, (int)pairs, (int)h, (int)w, (int)conv);
+}
+
 // x, y: contiguous float32 [pairs, 3, h, w]; workspace: uint8 of lpips_workspace_bytes; out_pairs [pairs] and out_taps
 // [pairs, 5] are the caller's (lpips.py keeps them per shape: no allocation after a shape's first call).
-void LpipsForward(const int64_t net, const std::vector<torch::Tensor>& packed, const std::vector<torch::Tensor>& lin,
-                  const torch::Tensor& x, const torch::Tensor& y, const torch::Tensor& workspace,
-                  const torch::Tensor& out_pairs, const torch::Tensor& out_taps) {
+namespace {
+void lpips_forward_call(const bool train, const int64_t net, const std::vector<torch::Tensor>& packed,
+                        const std::vector<torch::Tensor>& lin, const torch::Tensor& x, const torch::Tensor& y,
+                        const torch::Tensor& workspace, const torch::Tensor& out_pairs, const torch::Tensor& out_taps) {
   static const int widths[2][5] = {{64, 192, 384, 256, 256}, {64, 128, 256, 512, 512}};
   TORCH_CHECK(net == GRPG_LPIPS_ALEX || net == GRPG_LPIPS_VGG16, "lpips_forward: unknown net");
   TORCH_CHECK(x.defined() && x.is_cuda(), "lpips_forward: x must live on a ROCm/HIP device (torch device 'cuda'); this op "
@@ -2309,7 +2320,7 @@ void LpipsForward(const int64_t net, const std::vector<torch::Tensor>& packed, c
   TORCH_CHECK(x.dim() == 4 && x.size(1) == 3 && x.sizes() == y.sizes(), "lpips_forward: x and y must be [pairs, 3, h, w] of "
               "one shape (got ", x.sizes(), " and ", y.sizes(), ")");
   const int64_t pairs = x.size(0), h = x.size(2), w = x.size(3);
-  const int64_t bytes = LpipsWorkspaceBytes(net, pairs, h, w);
+  const int64_t bytes = train ? LpipsTrainWorkspaceBytes(net, pairs, h, w) : LpipsWorkspaceBytes(net, pairs, h, w);
   TORCH_CHECK(bytes > 0, "lpips_forward: ", pairs, " pairs of ", h, " x ", w, " are refused: the image must be at least ",
               net == GRPG_LPIPS_ALEX ? "31 x 31" : "16 x 16", ", pairs in 1 .. 65535 and every layer below 2^31 pixels");
   TORCH_CHECK(packed.size() == (net == GRPG_LPIPS_ALEX ? 5u : 13u) && lin.size() == 5, "lpips_forward: the net takes ",
@@ -2323,16 +2334,32 @@ void LpipsForward(const int64_t net, const std::vector<torch::Tensor>& packed, c
   }
   TORCH_CHECK(workspace.defined() && workspace.is_cuda() && workspace.device() == dev && workspace.is_contiguous() &&
                   workspace.scalar_type() == torch::kByte && workspace.numel() >= bytes,
-              "lpips_forward: workspace must be a contiguous uint8 tensor of lpips_workspace_bytes on x's device");
+              "lpips_forward: workspace must be a contiguous uint8 tensor of lpips_workspace_bytes (training: "
+              "lpips_train_workspace_bytes) on x's device");
   float* po = const_cast<float*>(lpips_f32(out_pairs, dev, "lpips_forward", "out_pairs"));
   float* pt = const_cast<float*>(lpips_f32(out_taps, dev, "lpips_forward", "out_taps"));
   TORCH_CHECK(out_pairs.numel() == pairs && out_taps.numel() == 5 * pairs, "lpips_forward: out_pairs must be [pairs] and "
               "out_taps [pairs, 5]");
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  run("grpg_lpips_forward", [&](void* stream) {
-    return grpg_lpips_forward((int)net, pp.data(), pl.data(), px, py, (int)pairs, (int)h, (int)w, workspace.data_ptr(), po,
-                              pt, stream);
+  run(train ? "grpg_lpips_forward_train" : "grpg_lpips_forward", [&](void* stream) {
+    return (train ? grpg_lpips_forward_train : grpg_lpips_forward)((int)net, pp.data(), pl.data(), px, py, (int)pairs, (int)h,
+                                                                    (int)w, workspace.data_ptr(), po, pt, stream);
   });
+}
+}  // namespace
+
+void LpipsForward(const int64_t net, const std::vector<torch::Tensor>& packed, const std::vector<torch::Tensor>& lin,
+                  const torch::Tensor& x, const torch::Tensor& y, const torch::Tensor& workspace,
+                  const torch::Tensor& out_pairs, const torch::Tensor& out_taps) {
+  lpips_forward_call(false, net, packed, lin, x, y, workspace, out_pairs, out_taps);
+}
+
+// The training forward: the same kernels and bits, every convolution's output kept in a workspace of
+// lpips_train_workspace_bytes for LpipsBackward.
+void LpipsForwardTrain(const int64_t net, const std::vector<torch::Tensor>& packed, const std::vector<torch::Tensor>& lin,
+                       const torch::Tensor& x, const torch::Tensor& y, const torch::Tensor& workspace,
+                       const torch::Tensor& out_pairs, const torch::Tensor& out_taps) {
+  lpips_forward_call(true, net, packed, lin, x, y, workspace, out_pairs, out_taps);
 }
 
 // The leaves (tests, tools): ONE convolution + ReLU; zscore: empty, or mean and std (3 + 3 values).
@@ -2402,6 +2429,153 @@ std::tuple<torch::Tensor, torch::Tensor> LpipsDistance(const torch::Tensor& feat
                                out.data_ptr<float>(), stream);
   });
   return std::make_tuple(out, map);
+}
+
+// ---- LPIPS backward (gaussianrpg_amd/lpips.py; csrc/lpips_bwd.hip) ----
+
+namespace {
+const float* lpips_opt_f32(const c10::optional<torch::Tensor>& t, const torch::Tensor& like, const char* fn, const char* what) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  const float* p = lpips_f32(*t, like.device(), fn, what);
+  TORCH_CHECK(t->sizes() == like.sizes(), fn, ": ", what, " must have the produced gradient's shape ", like.sizes(), " (got ",
+              t->sizes(), ")");
+  return p;
+}
+}  // namespace
+
+// float32 [c_out, c_in, k, k] on the device -> the layout the backward-data kernel streams (once per model).
+torch::Tensor LpipsBwdPackWeights(const torch::Tensor& weight, const int64_t stride) {
+  TORCH_CHECK(weight.defined() && weight.is_cuda(), "lpips_bwd_pack_weights: weight must live on a ROCm/HIP device (torch "
+              "device 'cuda'); this op has no CPU path");
+  const float* w = lpips_f32(weight, weight.device(), "lpips_bwd_pack_weights", "weight");
+  TORCH_CHECK(weight.dim() == 4 && weight.size(2) == weight.size(3), "lpips_bwd_pack_weights: weight must be [c_out, c_in, k, k] "
+              "(got ", weight.sizes(), ")");
+  TORCH_CHECK(weight.size(0) < (int64_t(1) << 20) && weight.size(1) < (int64_t(1) << 20) && stride >= 1 && stride <= 4,
+              "lpips_bwd_pack_weights: sizes out of range");
+  const int c_out = (int)weight.size(0), c_in = (int)weight.size(1), k = (int)weight.size(2);
+  const size_t bytes = grpg_lpips_conv_bwd_packed_bytes(c_out, c_in, k, (int)stride);
+  TORCH_CHECK(bytes > 0, "lpips_bwd_pack_weights: the backward covers k 3 or 5 at stride 1, and k 11 at stride 4 with at most "
+              "4 input channels (got k ", k, ", stride ", stride, ", c_in ", c_in, ")");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(weight.device());
+  torch::Tensor packed = torch::empty({(int64_t)(bytes / sizeof(float))}, weight.options());
+  run("grpg_lpips_conv_bwd_pack_weights", [&](void* stream) {
+    return grpg_lpips_conv_bwd_pack_weights(w, c_out, c_in, k, (int)stride, packed.data_ptr<float>(), stream);
+  });
+  return packed;
+}
+
+// workspace: the one LpipsForwardTrain filled for this shape; grad_pairs [pairs]; grad_x [pairs, 3, h, w] is the caller's.
+void LpipsBackward(const int64_t net, const std::vector<torch::Tensor>& packed_bwd, const std::vector<torch::Tensor>& lin,
+                   const torch::Tensor& workspace, const torch::Tensor& grad_pairs, const torch::Tensor& grad_x) {
+  TORCH_CHECK(net == GRPG_LPIPS_ALEX || net == GRPG_LPIPS_VGG16, "lpips_backward: unknown net");
+  TORCH_CHECK(grad_x.defined() && grad_x.is_cuda(), "lpips_backward: grad_x must live on a ROCm/HIP device (torch device "
+              "'cuda'); this op has no CPU path");
+  const torch::Device dev = grad_x.device();
+  float* pgx = const_cast<float*>(lpips_f32(grad_x, dev, "lpips_backward", "grad_x"));
+  const float* pgp = lpips_f32(grad_pairs, dev, "lpips_backward", "grad_pairs");
+  TORCH_CHECK(grad_x.dim() == 4 && grad_x.size(1) == 3 && grad_pairs.numel() == grad_x.size(0),
+              "lpips_backward: grad_x must be [pairs, 3, h, w] and grad_pairs [pairs] (got ", grad_x.sizes(), " and ",
+              grad_pairs.sizes(), ")");
+  const int64_t pairs = grad_x.size(0), h = grad_x.size(2), w = grad_x.size(3);
+  const int64_t bytes = LpipsTrainWorkspaceBytes(net, pairs, h, w);
+  TORCH_CHECK(bytes > 0, "lpips_backward: ", pairs, " pairs of ", h, " x ", w, " are refused: the image must be at least ",
+              net == GRPG_LPIPS_ALEX ? "31 x 31" : "16 x 16", ", pairs in 1 .. 65535 and every layer below 2^31 pixels");
+  TORCH_CHECK(packed_bwd.size() == (net == GRPG_LPIPS_ALEX ? 5u : 13u) && lin.size() == 5, "lpips_backward: the net takes ",
+              net == GRPG_LPIPS_ALEX ? 5 : 13, " packed convolutions and 5 lin weights");
+  std::vector<const float*> pp, pl;
+  for (const torch::Tensor& t : packed_bwd) pp.push_back(lpips_f32(t, dev, "lpips_backward", "packed weights"));
+  for (const torch::Tensor& t : lin) pl.push_back(lpips_f32(t, dev, "lpips_backward", "lin weights"));
+  TORCH_CHECK(workspace.defined() && workspace.is_cuda() && workspace.device() == dev && workspace.is_contiguous() &&
+                  workspace.scalar_type() == torch::kByte && workspace.numel() >= bytes,
+              "lpips_backward: workspace must be the contiguous uint8 tensor of lpips_train_workspace_bytes that "
+              "lpips_forward_train filled, on grad_x's device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  run("grpg_lpips_backward", [&](void* stream) {
+    return grpg_lpips_backward((int)net, pp.data(), pl.data(), workspace.data_ptr(), pgp, pgx, (int)pairs, (int)h, (int)w,
+                               stream);
+  });
+}
+
+// The leaves (tests, tools).  ONE convolution backward-data: grad_out [bs, c_out, h_out, w_out] -> [bs, c_in, h_in, w_in];
+// act / tap: the ReLU output the gradient lands on and its tap gradient, or None; std: empty, or the z-score's 3 values.
+torch::Tensor LpipsConv2dBackwardData(const torch::Tensor& grad_out, const torch::Tensor& packed_bwd,
+                                      const c10::optional<torch::Tensor>& act, const c10::optional<torch::Tensor>& tap,
+                                      const int64_t c_in, const int64_t h_in, const int64_t w_in, const int64_t k,
+                                      const int64_t stride, const int64_t pad, const std::vector<double>& sdev,
+                                      const int64_t tile) {
+  TORCH_CHECK(grad_out.defined() && grad_out.is_cuda(), "lpips_conv2d_backward_data: grad_out must live on a ROCm/HIP device "
+              "(torch device 'cuda'); this op has no CPU path");
+  const float* pg = lpips_f32(grad_out, grad_out.device(), "lpips_conv2d_backward_data", "grad_out");
+  const float* pw = lpips_f32(packed_bwd, grad_out.device(), "lpips_conv2d_backward_data", "packed_bwd");
+  TORCH_CHECK(grad_out.dim() == 4 && grad_out.numel() > 0, "lpips_conv2d_backward_data: grad_out must be a non-empty [bs, c_out, h, w]");
+  TORCH_CHECK(sdev.empty() || sdev.size() == 3, "lpips_conv2d_backward_data: std is empty or 3 values");
+  TORCH_CHECK(grad_out.size(0) <= 65535 && grad_out.size(1) < (1 << 20) && c_in >= 1 && c_in < (1 << 20) && h_in >= 1 &&
+                  w_in >= 1 && h_in <= (1 << 24) && w_in <= (1 << 24) && k >= 1 && k <= 11 && stride >= 1 && stride <= 4 &&
+                  pad >= 0 && pad < k,
+              "lpips_conv2d_backward_data: sizes out of range");
+  const int bs = (int)grad_out.size(0), c_out = (int)grad_out.size(1);
+  const size_t bytes = grpg_lpips_conv_bwd_packed_bytes(c_out, (int)c_in, (int)k, (int)stride);
+  TORCH_CHECK(bytes > 0 && (size_t)packed_bwd.numel() * sizeof(float) == bytes, "lpips_conv2d_backward_data: packed_bwd does "
+              "not match c_out, c_in, k and stride (k 3 or 5 at stride 1, k 11 at stride 4)");
+  TORCH_CHECK(h_in + 2 * pad >= k && w_in + 2 * pad >= k && grad_out.size(2) == (h_in + 2 * pad - k) / stride + 1 &&
+                  grad_out.size(3) == (w_in + 2 * pad - k) / stride + 1,
+              "lpips_conv2d_backward_data: grad_out ", grad_out.sizes(), " is not the convolution's output of a ", h_in, " x ",
+              w_in, " input");
+  float sd[3] = {1.0f, 1.0f, 1.0f};
+  for (size_t i = 0; i < sdev.size(); i++) sd[i] = (float)sdev[i];
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(grad_out.device());
+  torch::Tensor out = torch::empty({bs, c_in, h_in, w_in}, grad_out.options());
+  const float* pa = lpips_opt_f32(act, out, "lpips_conv2d_backward_data", "act");
+  const float* pt = lpips_opt_f32(tap, out, "lpips_conv2d_backward_data", "tap");
+  run("grpg_lpips_conv2d_backward_data", [&](void* stream) {
+    return grpg_lpips_conv2d_backward_data(pg, pw, pa, pt, out.data_ptr<float>(), bs, (int)c_in, c_out, (int)h_in, (int)w_in,
+                                           (int)k, (int)stride, (int)pad, sdev.empty() ? nullptr : sd, (int)tile, stream);
+  });
+  return out;
+}
+
+// MaxPool2d(k, 2) backward in gather form: act [bs, c, h, w] is the pool's input, grad_out its output's gradient.
+torch::Tensor LpipsMaxPoolBackward(const torch::Tensor& act, const torch::Tensor& grad_out,
+                                   const c10::optional<torch::Tensor>& tap, const int64_t k) {
+  TORCH_CHECK(act.defined() && act.is_cuda(), "lpips_max_pool_backward: act must live on a ROCm/HIP device (torch device "
+              "'cuda'); this op has no CPU path");
+  const float* pa = lpips_f32(act, act.device(), "lpips_max_pool_backward", "act");
+  const float* pg = lpips_f32(grad_out, act.device(), "lpips_max_pool_backward", "grad_out");
+  TORCH_CHECK(act.dim() == 4 && act.numel() > 0 && (k == 2 || k == 3) && act.size(2) >= k && act.size(3) >= k &&
+                  act.size(2) <= INT32_MAX && act.size(3) <= INT32_MAX,
+              "lpips_max_pool_backward: act must be [bs, c, h, w] with h, w >= k, and k 2 or 3");
+  TORCH_CHECK(grad_out.dim() == 4 && grad_out.size(0) == act.size(0) && grad_out.size(1) == act.size(1) &&
+                  grad_out.size(2) == (act.size(2) - k) / 2 + 1 && grad_out.size(3) == (act.size(3) - k) / 2 + 1,
+              "lpips_max_pool_backward: grad_out ", grad_out.sizes(), " is not the pool's output of ", act.sizes());
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(act.device());
+  torch::Tensor out = torch::empty_like(act);
+  const float* pt = lpips_opt_f32(tap, out, "lpips_max_pool_backward", "tap");
+  run("grpg_lpips_max_pool_backward", [&](void* stream) {
+    return grpg_lpips_max_pool_backward(pa, pg, pt, out.data_ptr<float>(), (long long)(act.size(0) * act.size(1)),
+                                        (int)act.size(2), (int)act.size(3), (int)k, stream);
+  });
+  return out;
+}
+
+// One tap's gradient: feat [2 * pairs, c, h, w] (x's first), lin [c], grad_pairs [pairs] -> [pairs, c, h, w].
+torch::Tensor LpipsDistanceBackward(const torch::Tensor& feat, const torch::Tensor& lin, const torch::Tensor& grad_pairs) {
+  TORCH_CHECK(feat.defined() && feat.is_cuda(), "lpips_distance_backward: feat must live on a ROCm/HIP device (torch device "
+              "'cuda'); this op has no CPU path");
+  const float* pf = lpips_f32(feat, feat.device(), "lpips_distance_backward", "feat");
+  const float* pl = lpips_f32(lin, feat.device(), "lpips_distance_backward", "lin");
+  const float* pg = lpips_f32(grad_pairs, feat.device(), "lpips_distance_backward", "grad_pairs");
+  TORCH_CHECK(feat.dim() == 4 && feat.numel() > 0 && feat.size(0) % 2 == 0 && lin.numel() == feat.size(1) &&
+                  grad_pairs.numel() == feat.size(0) / 2,
+              "lpips_distance_backward: feat must be [2 * pairs, c, h, w], lin hold c weights and grad_pairs pairs values");
+  const int64_t pairs = feat.size(0) / 2, c = feat.size(1), hw = feat.size(2) * feat.size(3);
+  TORCH_CHECK(pairs <= 65535 && c <= 768 && hw < (int64_t(1) << 31) - 256, "lpips_distance_backward: sizes out of range (at "
+              "most 768 channels)");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(feat.device());
+  torch::Tensor out = torch::empty({pairs, c, feat.size(2), feat.size(3)}, feat.options());
+  run("grpg_lpips_distance_backward", [&](void* stream) {
+    return grpg_lpips_distance_backward(pf, pl, pg, (int)pairs, (int)c, (int)hw, out.data_ptr<float>(), stream);
+  });
+  return out;
 }
 
 // ---- the closed loop's tail (gaussianrpg_amd/closed_loop.py; csrc/ego_loop.hip) ----
@@ -3547,6 +3721,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lpips_conv2d", &LpipsConv2d);
   m.def("lpips_max_pool", &LpipsMaxPool);
   m.def("lpips_distance", &LpipsDistance);
+  // LPIPS as a loss: the forward that keeps its activations, the backward to x, and the backward's leaves
+  m.def("lpips_train_workspace_bytes", &LpipsTrainWorkspaceBytes);
+  m.def("lpips_train_activation_offset", &LpipsTrainActivationOffset);
+  m.def("lpips_forward_train", &LpipsForwardTrain);
+  m.def("lpips_bwd_pack_weights", &LpipsBwdPackWeights);
+  m.def("lpips_backward", &LpipsBackward);
+  m.def("lpips_conv2d_backward_data", &LpipsConv2dBackwardData);
+  m.def("lpips_max_pool_backward", &LpipsMaxPoolBackward);
+  m.def("lpips_distance_backward", &LpipsDistanceBackward);
   // the closed loop's tail: ranging alone, and the fused step (closed_loop.py)
   m.def("object_positions", &ObjectPositions);
   m.def("ego_loop_step", &EgoLoopStep);

@@ -679,12 +679,13 @@ def detector_torch(spec, state_dict, dtype=torch.float32, device="cpu", per_laye
     return run
 
 
-def lpips_torch(net_type, features, lin, dtype=torch.float32, device="cpu", per_tap: bool = False):
+def lpips_torch(net_type, features, lin, dtype=torch.float32, device="cpu", per_tap: bool = False, grad: bool = False):
     """LPIPS as ordinary PyTorch ops -- ``F.conv2d``, ``F.relu``, ``F.max_pool2d`` over the tables of ``lpips.LAYERS``
     and the reference's lines for the rest (``BaseNet.z_score`` / ``forward``, ``normalize_activation``, ``LinLayers``,
     ``LPIPS.forward``): the route ``lpips.LPIPS`` replaces, and the float32 comparison of its tests.  Takes the two
     state dicts ``lpips.LPIPS`` takes.  Usable on the CPU in float32 and float64.  Returns ``run(x, y)`` -> [1, 1, 1, 1]
-    (``per_tap=True``: ``(value, [the per-pixel maps [B, 1, H_l, W_l]])``)."""
+    (``per_tap=True``: ``(value, [the per-pixel maps [B, 1, H_l, W_l]])``).  ``grad=True``: under autograd, so an ``x``
+    that requires grad receives one (``y``'s features are constants): the route ``lpips.LPIPS.loss`` replaces."""
     import torch.nn.functional as F
     from . import lpips as lp
     layers, targets = lp.LAYERS[lp._net(net_type)], lp.TARGETS[net_type]
@@ -711,10 +712,13 @@ def lpips_torch(net_type, features, lin, dtype=torch.float32, device="cpu", per_
         return output
 
     def run(x, y):
-        with torch.no_grad():
+        with torch.enable_grad() if grad else torch.no_grad():
             x, y = (t.to(device, dtype) for t in (x, y))
             x, y = (t if t.dim() == 4 else t[None] for t in (x, y))
-            diff = [(fx - fy) ** 2 for fx, fy in zip(net(x), net(y))]
+            fxs = net(x)
+            with torch.no_grad():
+                fys = net(y)
+            diff = [(fx - fy) ** 2 for fx, fy in zip(fxs, fys)]
             maps = [F.conv2d(d, l) for d, l in zip(diff, lins)]
             res = [m.mean((2, 3), True) for m in maps]
             value = torch.sum(torch.cat(res, 0), 0, True)

@@ -11,8 +11,11 @@ call per batch of pairs (csrc/lpips.hip; DESIGN.md section 32, INTEGRATION.md se
 
 The backbone comes from ``torchvision`` in the reference; here it is two tables (``LAYERS``) and the caller's state
 dict, so neither torchvision nor a download is needed.  Inputs are used as given: ``metrics.py`` passes [0, 1] images
-into a z-score made for [-1, 1], and so does this.  There is no gradient (a metric, not a loss), no CPU path, no
-SqueezeNet, no half precision.
+into a z-score made for [-1, 1], and so does this.  No CPU path, no SqueezeNet, no half precision.
+
+As a training term (csrc/lpips_bwd.hip): ``criterion.loss(x, y)`` is [B] with a gradient to ``x``
+-- and to ``x`` only -- through one native backward call; ``lpips_loss(x, y, criterion, reduction)`` reduces it.  Every
+other entry point stays a detached metric.
 """
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -80,7 +83,8 @@ def shape_plan(net_type: str, pairs: int, h: int, w: int) -> dict:
     """What one call does, on the host: ``steps`` (one dict per launch up to the fifth tap: kind "conv" / "pool", the
     sizes, ``tap`` on a convolution whose ReLU output is a tap), ``taps`` [(C, H, W)], and the workspace arithmetic of
     csrc/lpips.hip: ``act_bytes`` (ONE of the two ping-pong activations), ``map_offsets`` / ``slot_offsets`` (bytes) and
-    ``workspace_bytes``.  Raises ValueError for a size the native call refuses."""
+    ``workspace_bytes``; ``launches`` of the forward and ``backward_launches`` of ``LPIPS.loss``'s backward (one per
+    convolution, pool and tap).  Raises ValueError for a size the native call refuses."""
     net_type = _net(net_type)
     least = MIN_SIZE[net_type]
     if pairs < 1 or pairs > 65535:
@@ -126,7 +130,8 @@ def shape_plan(net_type: str, pairs: int, h: int, w: int) -> dict:
     convs, pools = sum(s["kind"] == "conv" for s in steps), sum(s["kind"] == "pool" for s in steps)
     return dict(net_type=net_type, pairs=pairs, h=h, w=w, steps=steps, taps=taps, act_bytes=act, map_offsets=map_offsets,
                 slot_offsets=slot_offsets, workspace_bytes=off,
-                launches=dict(conv=convs, pool=pools, distance=len(taps), finish=1, total=convs + pools + len(taps) + 1))
+                launches=dict(conv=convs, pool=pools, distance=len(taps), finish=1, total=convs + pools + len(taps) + 1),
+                backward_launches=dict(conv=convs, pool=pools, distance=len(taps), total=convs + pools + len(taps)))
 
 
 # ---- the two state dicts ----
@@ -212,6 +217,32 @@ def max_pool(x: torch.Tensor, k: int) -> torch.Tensor:
     return _C().lpips_max_pool(x, int(k))
 
 
+def pack_weights_bwd(weight: torch.Tensor, stride: int = 1) -> torch.Tensor:
+    """float32 [c_out, c_in, k, k] on the device -> the layout the backward-data kernel streams: k in {3, 5} at stride
+    1, or k 11 at stride 4 with c_in <= 4; one launch, once per model."""
+    return _C().lpips_bwd_pack_weights(weight.contiguous(), int(stride))
+
+
+def conv2d_backward_data(grad_out: torch.Tensor, packed_bwd: torch.Tensor, c_in: int, hw_in: Tuple[int, int], k: int,
+                         stride: int = 1, pad: int = 0, act: Optional[torch.Tensor] = None,
+                         tap: Optional[torch.Tensor] = None, std: bool = False, tile: int = TILE_64) -> torch.Tensor:
+    """ONE launch of the backward-data kernel: the gradient of a convolution's input from its pre-activation's;
+    ``act`` (the ReLU output the gradient lands on) switches the select ``act > 0 ? g + tap : 0`` on, ``std`` the
+    division by BaseNet's std (the image's gradient)."""
+    return _C().lpips_conv2d_backward_data(grad_out, packed_bwd, act, tap, int(c_in), int(hw_in[0]), int(hw_in[1]), int(k),
+                                           int(stride), int(pad), list(STD) if std else [], int(tile))
+
+
+def max_pool_backward(act: torch.Tensor, grad_out: torch.Tensor, k: int, tap: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``MaxPool2d(k, 2)`` backward onto its input ``act`` (a ReLU output): ``act > 0 ? gathered + tap : 0``; one launch."""
+    return _C().lpips_max_pool_backward(act, grad_out, tap, int(k))
+
+
+def tap_distance_backward(feat: torch.Tensor, lin: torch.Tensor, grad_pairs: torch.Tensor) -> torch.Tensor:
+    """One tap's gradient to the x half of ``feat`` [2 * pairs, C, H, W]: [pairs, C, H, W], 0 where x is not positive."""
+    return _C().lpips_distance_backward(feat, lin, grad_pairs)
+
+
 def tap_distance(feat: torch.Tensor, lin: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """One tap: feat [2 * pairs, C, H, W] (x's features first, then y's), lin [C] -> (the tap's term per pair [pairs],
     the per-pixel map s [pairs, H, W])."""
@@ -246,7 +277,9 @@ class LPIPS(nn.Module):
         self.params = feature_parameters(self.net_type, features)
         self.lin = lin_parameters(self.net_type, lin)
         self._packed: Dict[torch.device, tuple] = {}
+        self._packed_bwd: Dict[torch.device, list] = {}
         self._buffers_of: Dict[tuple, tuple] = {}
+        self._train_of: Dict[tuple, list] = {}
         if device is not None or torch.cuda.is_available():
             self.packed(device if device is not None else "cuda")
 
@@ -257,6 +290,14 @@ class LPIPS(nn.Module):
             self._packed[device] = ([pack_weights(w.to(device), b.to(device)) for w, b in self.params],
                                     [v.to(device) for v in self.lin])
         return self._packed[device]
+
+    def packed_bwd(self, device) -> list:
+        """[the backward layout of every convolution's weights] on ``device``: repacked once per device."""
+        device = _device(device)
+        if device not in self._packed_bwd:
+            strides = [LAYERS[self.net_type][i][4] for i in conv_indices(self.net_type)]
+            self._packed_bwd[device] = [pack_weights_bwd(w.to(device), s) for (w, _), s in zip(self.params, strides)]
+        return self._packed_bwd[device]
 
     def _check(self, x, y):
         for t, n in ((x, "x"), (y, "y")):
@@ -314,6 +355,90 @@ class LPIPS(nn.Module):
 
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         return self.distances(x, y).sum().reshape(1, 1, 1, 1)
+
+    # ---- the training term ----
+
+    def _run_train(self, x, y):
+        """The forward that keeps its activations: (plan, key, state) with state = [workspace, out, taps, generation,
+        grad_pairs buffer] of the shape; every call raises the generation, so a backward can tell that its activations
+        are gone."""
+        plan = self._check(x, y)
+        key = (plan["pairs"], plan["h"], plan["w"], x.device)
+        if key not in self._train_of:
+            nbytes = _C().lpips_train_workspace_bytes(NETS[self.net_type], plan["pairs"], plan["h"], plan["w"])
+            self._train_of[key] = [torch.empty(nbytes, dtype=torch.uint8, device=x.device),
+                                   torch.empty(plan["pairs"], dtype=torch.float32, device=x.device),
+                                   torch.empty(plan["pairs"], 5, dtype=torch.float32, device=x.device), 0,
+                                   torch.empty(plan["pairs"], dtype=torch.float32, device=x.device)]
+            self.packed_bwd(x.device)
+        state = self._train_of[key]
+        packed, lin = self.packed(x.device)
+        shape = (plan["pairs"], 3, plan["h"], plan["w"])
+        state[3] += 1
+        with torch.no_grad():
+            _C().lpips_forward_train(NETS[self.net_type], packed, lin, x.detach().view(shape), y.detach().view(shape),
+                                     state[0], state[1], state[2])
+        return plan, key, state
+
+    def loss(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """[B]: ``distances(x, y)`` bit for bit, as a fresh tensor with a gradient to ``x`` (one native backward call;
+        no host wait, and after a shape's first forward + backward no allocation but the returned tensors).  The
+        gradient goes to ``x`` only: a ``y`` that requires grad is refused.  The activations live in the shape's
+        workspace until the next ``loss`` / ``train_activations`` call of that shape: call backward before it."""
+        if isinstance(y, torch.Tensor) and y.requires_grad:
+            raise ValueError("gaussianrpg_amd.lpips: y requires grad, but the gradient goes to x only; pass y.detach()")
+        return _LpipsLoss.apply(x, y, self)
+
+    def train_activations(self, x: torch.Tensor, y: torch.Tensor) -> List[torch.Tensor]:
+        """The kept post-ReLU activations of the x images [B, C_i, H_i, W_i] (copies), one per convolution, for the
+        tests and tools/lpips_bwd_parity.py: what the backward's selects and pool winners are decided by."""
+        plan, _, state = self._run_train(x, y)
+        acts = []
+        for i, s in enumerate(s for s in plan["steps"] if s["kind"] == "conv"):
+            off = _C().lpips_train_activation_offset(NETS[self.net_type], plan["pairs"], plan["h"], plan["w"], i)
+            n = plan["pairs"] * s["c_out"] * s["hw_out"][0] * s["hw_out"][1]
+            acts.append(state[0][off:off + 4 * n].view(torch.float32).view(plan["pairs"], s["c_out"], *s["hw_out"]).clone())
+        return acts
+
+
+class _LpipsLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, crit):
+        plan, key, state = crit._run_train(x, y)
+        ctx.crit, ctx.key, ctx.generation, ctx.x_shape = crit, key, state[3], x.shape
+        ctx.save_for_backward(state[1])            # torch's own guard against a second backward through the graph
+        ctx.set_materialize_grads(False)
+        return state[1].clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        ctx.saved_tensors                          # raises once the graph's buffers are freed
+        if grad is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        crit, key = ctx.crit, ctx.key
+        state = crit._train_of[key]
+        if state[3] != ctx.generation:
+            raise RuntimeError("gaussianrpg_amd.lpips: the activations of this loss were overwritten by a later loss / "
+                               "train_activations call of the same shape; call backward before it")
+        if grad.dtype != torch.float32 or not grad.is_cuda:
+            raise TypeError("gaussianrpg_amd.lpips: the incoming gradient must be a float32 device tensor")
+        pairs, h, w, device = key
+        grad_x = torch.empty((pairs, 3, h, w), dtype=torch.float32, device=device)
+        if not grad.is_contiguous():               # e.g. sum()'s expanded scalar: into the shape's own buffer
+            grad = state[4].copy_(grad)
+        _C().lpips_backward(NETS[crit.net_type], crit.packed_bwd(device), crit.packed(device)[1], state[0], grad, grad_x)
+        return grad_x.view(ctx.x_shape), None, None
+
+
+def lpips_loss(x: torch.Tensor, y: torch.Tensor, criterion: LPIPS, reduction: str = "mean") -> torch.Tensor:
+    """The training term: ``criterion.loss(x, y)`` reduced over the pairs ('mean', 'sum') or as it is ('none')."""
+    if not isinstance(criterion, LPIPS):
+        raise TypeError("gaussianrpg_amd.lpips: criterion must be a gaussianrpg_amd.lpips.LPIPS (got %s); build it once "
+                        "from the two state dicts" % type(criterion).__name__)
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError("gaussianrpg_amd.lpips: reduction must be 'mean', 'sum' or 'none' (got %r)" % (reduction,))
+    d = criterion.loss(x, y)
+    return d.mean() if reduction == "mean" else d.sum() if reduction == "sum" else d
 
 
 def lpips(x: torch.Tensor, y: torch.Tensor, criterion: LPIPS) -> torch.Tensor:

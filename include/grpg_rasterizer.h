@@ -1698,7 +1698,8 @@ GRPG_API int grpg_detector_run_f16(const grpg_detector_layer_f16* layers, int n,
 /*
  * LPIPS (csrc/lpips.hip): the reference's third quality number (metrics.py:81 over
  * lib/utils/lpipsPyTorch/modules/{lpips,networks,utils}.py) with the AlexNet or the VGG16 backbone.  Additive;
- * GRPG_ABI_VERSION stays 7.  FP32, NCHW, no atomics, no split-K: identical calls give identical bits.  No gradient.
+ * GRPG_ABI_VERSION stays 7.  FP32, NCHW, no atomics, no split-K: identical calls give identical bits.  A metric: the gradient is
+ * the next block's (grpg_lpips_forward_train / grpg_lpips_backward).
  *
  * Weights: grpg_lpips_conv_pack_weights has grpg_conv2d_pack_weights' contract and layout for k in {3, 5, 11}: a
  * contiguous float32 [c_out, c_in, k, k] weight and a [c_out] bias (NULL: zeros) -> [bias][K][c_out], c_out padded to
@@ -1754,6 +1755,57 @@ GRPG_API int grpg_lpips_max_pool(const float* in, float* out, long long planes, 
 GRPG_API size_t grpg_lpips_distance_workspace_bytes(int pairs, int c, int hw);   /* pure size query */
 GRPG_API int grpg_lpips_distance(const float* feat, const float* lin, int pairs, int c, int hw, void* workspace,
                                  float* map, float* out_pairs, void* hip_stream);
+
+/*
+ * LPIPS backward (csrc/lpips_bwd.hip): the gradient of sum_p grad_pairs[p] * out_pairs[p] with
+ * respect to the images x, and nothing else (not y, not the weights; no double backward).  Additive; GRPG_ABI_VERSION
+ * stays 7.  FP32, no atomics: identical calls give identical bits.
+ *
+ * grpg_lpips_forward_train has grpg_lpips_forward's arguments, kernels, tile policy and so its bits in out_pairs /
+ * out_taps, but lays every convolution's output out in a workspace of grpg_lpips_train_workspace_bytes(net, pairs, h,
+ * w) bytes (a pure size query, 0 exactly where grpg_lpips_workspace_bytes is 0; 256-byte aligned): the post-ReLU
+ * activations of all 2 * pairs images (x's first) stay valid until the next call on that workspace, convolution i's
+ * [2 * pairs, C_i, H_i, W_i] floats grpg_lpips_train_activation_offset(net, pairs, h, w, i) bytes in (pure; 0 if
+ * refused).  The workspace also holds the backward's gradients.
+ *
+ * grpg_lpips_backward reads that workspace (same net, pairs, h, w, and the forward enqueued before it on the same
+ * stream) and writes grad_x [pairs, 3, h, w].  packed_bwd: HOST array of the net's 5 / 13 device pointers to the
+ * BACKWARD layout of each convolution's weights, made once per model by grpg_lpips_conv_bwd_pack_weights from the
+ * contiguous float32 [c_out, c_in, k, k] weight (grpg_lpips_conv_bwd_packed_bytes(c_out, c_in, k, stride) bytes, 16-byte
+ * aligned; 0: not covered -- the backward covers k in {3, 5} at stride 1 and k 11 at stride 4 with c_in <= 4); lin as
+ * in the forward; grad_pairs [pairs] on the device.  Launches: one per convolution, pool and tap, 12 for AlexNet and
+ * 22 for VGG16; no host wait.  A gradient that lands on a ReLU output a is stored as a > 0 ? g : 0 (a select: a
+ * non-finite g under a dead activation gives 0); a pool sends a window's gradient to its first maximum in row-major
+ * order; the norm's derivative at an all-zero feature vector is 0; image rows and columns under no window get 0.
+ * Checks and refusals are the forward's.
+ *
+ * The leaves: grpg_lpips_conv2d_backward_data turns grad_out [bs, c_out, h_out, w_out] into grad_in [bs, c_in, h_in,
+ * w_in], summed over k = (co, ky, kx) ascending in blocks of 32 (stride 1) or as one fma chain over the taps with
+ * (y + pad - ky) % stride == 0 (the strided layer); act (or NULL) is the [bs, c_in, h_in, w_in] ReLU output the
+ * gradient lands on, tap (or NULL; needs act) a gradient added before the select; std (HOST array of 3, or NULL;
+ * c_in = 3, excludes act) divides channel c by std[c].  grpg_lpips_max_pool_backward: act [planes, h, w] is the pool's
+ * input (required: the winners are recomputed from it), grad_out [planes, ho, wo], tap or NULL, k in {2, 3}.
+ * grpg_lpips_distance_backward: feat [2 * pairs, c, hw] as in grpg_lpips_distance, grad_x [pairs, c, hw] receives
+ * x_c > 0 ? (grad_pairs[p] / hw) * d s / d x_c : 0.
+ */
+GRPG_API size_t grpg_lpips_train_workspace_bytes(int net, int pairs, int h, int w);   /* pure size query */
+GRPG_API size_t grpg_lpips_train_activation_offset(int net, int pairs, int h, int w, int conv);   /* pure size query */
+GRPG_API int grpg_lpips_forward_train(int net, const float* const* packed, const float* const* lin, const float* x,
+                                      const float* y, int pairs, int h, int w, void* workspace, float* out_pairs,
+                                      float* out_taps, void* hip_stream);
+GRPG_API size_t grpg_lpips_conv_bwd_packed_bytes(int c_out, int c_in, int k, int stride);   /* pure size query */
+GRPG_API int grpg_lpips_conv_bwd_pack_weights(const float* weight, int c_out, int c_in, int k, int stride,
+                                              float* packed, void* hip_stream);
+GRPG_API int grpg_lpips_backward(int net, const float* const* packed_bwd, const float* const* lin, void* workspace,
+                                 const float* grad_pairs, float* grad_x, int pairs, int h, int w, void* hip_stream);
+GRPG_API int grpg_lpips_conv2d_backward_data(const float* grad_out, const float* packed_bwd, const float* act,
+                                             const float* tap, float* grad_in, int bs, int c_in, int c_out, int h_in,
+                                             int w_in, int k, int stride, int pad, const float* std, int tile,
+                                             void* hip_stream);
+GRPG_API int grpg_lpips_max_pool_backward(const float* act, const float* grad_out, const float* tap, float* grad_in,
+                                          long long planes, int h, int w, int k, void* hip_stream);
+GRPG_API int grpg_lpips_distance_backward(const float* feat, const float* lin, const float* grad_pairs, int pairs, int c,
+                                          int hw, float* grad_x, void* hip_stream);
 
 #ifdef __cplusplus
 }
